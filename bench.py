@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- IK solves/s of the MI355X-native GraphIK RiemannianSolver path.
 
-    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5]
+    python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds everything
+else: the CPU baseline, the serving measurement, and -- on the default workload -- the other
+BASELINE configs, the column-form lines and seeds 1-3.  `--dump-outputs DIR` writes what the last
+timed step computed (q, the per-problem statistics and the points Y) as DIR/<name>.npy, float64.
 
 `--gpus N` with N > 1 brings up N ranks itself (it re-executes this file under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`, one
@@ -94,14 +99,19 @@ def parse_args(argv=None):
                     help="parity configs outside BASELINE's list (overrides --config's robot)")
     ap.add_argument("--batch", type=int, default=0, help="goals per GPU (overrides the config's size)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: CPU baseline, serving, and on the "
+                         "default workload the c3 / c4 / c5 and column-form lines and seeds 1-3")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's results (q, per-problem statistics, Y) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", type=int, default=0, help="problems for the CPU baseline (0=auto)")
     ap.add_argument("--streams", type=int, default=1,
                     help="batches in flight in the TIMED region (default 1: steps back to back, the "
                          "headline configuration)")
     ap.add_argument("--serving-streams", type=int, default=16,
-                    help="extra, separately labelled measurement after the timed region: the same "
-                         "batches issued round-robin on this many HIP streams (0 = skip)")
+                    help="with --full: extra, separately labelled measurement after the timed region: the "
+                         "same batches issued round-robin on this many HIP streams (0 = skip)")
     ap.add_argument("--hessian-form", choices=["auto", "column", "per_edge"], default="auto",
                     help="3-D arms on the wavefront kernel: how lhess is rendered (gik_template_desc.hessian_form); "
                          "auto (the library's default, the BASELINE line) = per_edge: s = y.w once per edge as "
@@ -112,11 +122,14 @@ def parse_args(argv=None):
                          "hinges the reference means to create (SURVEY 8(f)3); NOT the reference's observable "
                          "semantics and not the BASELINE line")
     ap.add_argument("--headline-only", action="store_true",
-                    help="default invocation: skip the c3 / c4 / c5 measurements that follow the headline")
+                    help="with --full on the default workload: skip the c3 / c4 / c5 measurements that follow the headline")
     ap.add_argument("--backend", default=None, choices=["nccl", "gloo"])
     ap.add_argument("--dry-solve", action="store_true",
                     help="no GPU: deterministic stand-in for the solve (tests of the N>1 logic)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def self_launch(args):
@@ -183,6 +196,35 @@ def dry_solve(T_goal, n):
     return {"q": q, "pos_err": 1e-4 * key, "rot_err": 1e-4 * (key + 1.0), "f": 1e-12 * key, "gradnorm": 1e-10 * key,
             "iterations": its, "inner_total": 40.0 * its, "n_accept": np.floor(0.8 * its),
             "stop": np.zeros_like(key), "inner_executed": 38.0 * its}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, table, n, Y=None, seed=0):
+    """--dump-outputs: the gathered per-problem results of the last timed step -- q [B, n], every
+    statistic of graphik_amd.distributed.RESULT_STATS [B] and, when given, the points Y [B, N, k] --
+    one float64 .npy each.  Beyond DUMP_LIMIT_BYTES a fixed, seeded sample of rows is written (the
+    same rows of every array) and its row numbers as sample_rows.npy.  Returns the line's record."""
+    from graphik_amd import distributed as gd
+    q, _, info = gd.unpack_results(table, n)
+    arrays = {"q": q, **{k: info[k] for k in gd.RESULT_STATS}}
+    if Y is not None:
+        arrays["Y"] = Y
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    rows = len(q)
+    nbytes = sum(a.nbytes for a in arrays.values())
+    sampled = nbytes > DUMP_LIMIT_BYTES
+    if sampled:
+        keep = int(DUMP_LIMIT_BYTES // (nbytes // rows + 8))
+        idx = np.sort(np.random.RandomState(seed).choice(rows, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["sample_rows"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {"dir": out_dir, "arrays": sorted(arrays), "rows": rows, "sampled": sampled,
+            "bytes": int(sum(a.nbytes for a in arrays.values()))}
 
 
 def cpu_baseline(prob, T_goal, Y0_h, B, args):
@@ -292,7 +334,7 @@ class Bench:
         lb, ub = robot.limits_arrays()
         return robot.fk_batch(lb + (ub - lb) * U), hi - lo
 
-    def measure_dry(self, cfg, robot_name, total, scaling, steps, warmup):
+    def measure_dry(self, cfg, robot_name, total, scaling, steps, warmup, dump_dir=None):
         gd, torch = self.gd, self.torch
         robot, graph = build_graph(robot_name)
         T_goal, B = self.goals(robot, total, self.args.seed)
@@ -312,6 +354,7 @@ class Bench:
         if self.rank != 0:
             return None
         a = allstats.numpy()
+        dumped = dump_outputs(dump_dir, a, robot.n) if dump_dir else None
         return {
             "metric": "IK solves/sec (batched random goals)", "value": None, "unit": "solves/s",
             "dry_solve": True, "n_gpus": self.world, "steps": steps, "warmup": warmup,
@@ -321,12 +364,13 @@ class Bench:
             "per_rank": [dict(zip(("ms", "max_outer", "frac_maxiter", "goals"), v)) for v in per_rank],
             "rows": int(a.shape[0]), "row_bytes": int(a.shape[1]) * 8, "checksum": float(a.sum()),
             "rows_sha": __import__("hashlib").sha256(np.ascontiguousarray(a).tobytes()).hexdigest(),
-        }
+        } | ({"outputs": dumped} if dumped else {})
 
     def measure(self, cfg, robot_name, total, scaling, steps, warmup, serving_streams=0,
-                cpu=False, n_streams=1, intended=False, seed=None, use_limits=True, hessian_form=None):
+                cpu=False, n_streams=1, intended=False, seed=None, use_limits=True, hessian_form=None,
+                dump_dir=None):
         if self.dry:
-            return self.measure_dry(cfg, robot_name, total, scaling, steps, warmup)
+            return self.measure_dry(cfg, robot_name, total, scaling, steps, warmup, dump_dir=dump_dir)
         args, torch, gd, dev, rank, world = self.args, self.torch, self.gd, self.dev, self.rank, self.world
         seed = args.seed if seed is None else seed
         robot, graph = build_graph(robot_name)
@@ -461,7 +505,11 @@ class Bench:
         # single gather of the per-problem results at the end (RCCL over xGMI when N > 1): the table of
         # graphik_amd.distributed.solve_batch_sharded -- joint angles + statistics per problem
         allstats = gd.gather_rows(gd.pack_results(res, device=dev), total, dst=0)
-        Y0_h = res["Y0"].cpu().numpy()
+        Y_all = None
+        if dump_dir:        # the points of every rank as well (a second gather, only when they are written)
+            x = res["x"].double()
+            Y_all = gd.gather_rows(x, total, dst=0)
+        Y0_h = res["Y0"].cpu().numpy() if cpu else None      # (the CPU baseline's starting points)
 
         flags_local = res["flags"] if "flags" in res else None
         lowrank_local = float((flags_local & 1).double().mean()) if flags_local is not None else 0.0
@@ -478,6 +526,7 @@ class Bench:
                           "RCCL): q [n] + " + ", ".join(gd.RESULT_STATS) + " -- the table of "
                           "graphik_amd.distributed.solve_batch_sharded (the points Y travel on request: with_Y)"}
         _, _, ginfo = gd.unpack_results(st, robot.n)
+        dumped = dump_outputs(dump_dir, st, robot.n, Y=Y_all.cpu().numpy()) if dump_dir else None
         pos, rot, its, inner, nacc, stop, execd = (ginfo[k].astype(float) for k in (
             "pos_err", "rot_err", "iterations", "inner_total", "n_accept", "stop", "inner_executed"))
         inner_local = float(res["inner_total"].double().sum())        # as the reference counts them
@@ -556,6 +605,8 @@ class Bench:
                              "bytes_per_launch": hbm_bytes},
         }
         out["gather"] = gather
+        if dumped:
+            out["outputs"] = dumped
         out["per_rank"] = [dict(zip(("ms", "max_outer", "frac_maxiter", "goals"), v)) for v in per_rank]
         if serving is not None:
             # the same flops per batch as the timed region's, S batches in flight: what the chip does on this config
@@ -677,15 +728,16 @@ def main():
 
     b = Bench(args)
     cfg, robot_name, total, scaling = workload(args, b.world)
+    # a plain run measures the headline alone; the CPU baseline and the serving figure come with --full
     out = b.measure(cfg, robot_name, total, scaling, args.steps, args.warmup,
-                    serving_streams=args.serving_streams, cpu=True, n_streams=args.streams,
-                    intended=args.intended)
-    # The default invocation (`python bench.py [--gpus N]`, what the driver runs) also times the other
+                    serving_streams=(args.serving_streams if args.full else 0), cpu=args.full,
+                    n_streams=args.streams, intended=args.intended, dump_dir=args.dump_outputs)
+    # `--full` on the default workload (`python bench.py --full [--gpus N]`) also times the other
     # BASELINE workloads after the headline, a few steps each, and reports them under "configs" in
     # the same line: c3 (UR10 + table, 4096 goals per GPU), c4 (KUKA, 65536 goals sharded over the
     # GPUs: strong scaling; on one GPU also its 8192-goal per-GPU share of an 8-GPU run) and c5
     # (planar-10, 65536 sharded).  --headline-only skips them.
-    default_run = (args.config is None and args.robot is None and not args.batch and not args.intended
+    default_run = (args.full and args.config is None and args.robot is None and not args.batch and not args.intended
                    and args.streams == 1 and not args.headline_only)
     if default_run:
         extra = {}

@@ -89,9 +89,9 @@ def test_bench_self_launches_ranks_and_gathers():
     assert one["rows_sha"] == two["rows_sha"]
     assert two["scaling"] == "strong"
     # weak-scaling default (BASELINE configs[1]): every rank brings its own 4096 goals
-    w2 = _bench_line("--gpus", "2")
+    w2 = _bench_line("--gpus", "2", "--full")
     assert w2["config"]["robot"] == "lwa4d" and w2["rows"] == 2 * 4096 and w2["scaling"] == "weak"
-    # ... and the default line (what the driver runs at every N) carries the other BASELINE workloads
+    # ... and the default line with --full carries the other BASELINE workloads
     # under "configs": the c4 / c5 tables gathered from two shards equal the one-rank tables
     cf = w2["configs"]
     assert set(cf) == {"c3", "c4", "c5", "c5_nolimits", "c2_column", "c4_column"}     # (the 8192-goal share line is single-GPU only)
@@ -110,6 +110,52 @@ def test_bench_self_launches_ranks_and_gathers():
     assert p1["rows_sha"] == p3["rows_sha"] and p3["rows"] == 65536
     assert cf["c5"]["rows_sha"] == p1["rows_sha"]
     assert "configs" not in p1                       # explicit --config: that workload only
+
+
+def test_bench_plain_run_dumps_its_last_step(tmp_path):
+    """A plain run (no --full) measures the headline alone; with --dump-outputs it writes the gathered
+    table of its last timed step as float64 .npy files: q and every statistic, the same table whose
+    sha256 the line reports, and the same arrays from one rank and from two."""
+    import hashlib
+    from graphik_amd import distributed as gd
+    plain = _bench_line("--gpus", "1")
+    assert "configs" not in plain and "seeds" not in plain and plain["steps"] == 2
+    one = _bench_line("--gpus", "1", "--config", "c4", "--dump-outputs", str(tmp_path / "one"))
+    two = _bench_line("--gpus", "2", "--config", "c4", "--dump-outputs", str(tmp_path / "two"))
+    names = ["q"] + list(gd.RESULT_STATS)
+    assert one["outputs"]["arrays"] == two["outputs"]["arrays"] == sorted(names) and not one["outputs"]["sampled"]
+    got = {}
+    for tag in ("one", "two"):
+        got[tag] = {k: np.load(tmp_path / tag / (k + ".npy")) for k in names}
+        assert all(a.dtype == np.float64 and len(a) == 65536 for a in got[tag].values())
+    assert got["one"]["q"].shape == (65536, 7)
+    table = np.column_stack([got["one"][k] for k in names])
+    assert hashlib.sha256(np.ascontiguousarray(table).tobytes()).hexdigest() == one["rows_sha"] == two["rows_sha"]
+    for k in names:
+        assert np.array_equal(got["one"][k], got["two"][k]), k
+
+
+def test_bench_dump_samples_large_outputs(tmp_path, monkeypatch):
+    """Beyond the size limit --dump-outputs writes a fixed, seeded sample of rows (the same rows of every
+    array, their row numbers in sample_rows.npy) and stays within the limit."""
+    # (importing bench.py sets a HIP environment default: keep it out of this process's environment)
+    monkeypatch.setenv("GPU_MAX_HW_QUEUES", os.environ.get("GPU_MAX_HW_QUEUES", "4"))
+    import bench
+    from graphik_amd import distributed as gd
+    n, rows = 7, 1000
+    table = np.random.RandomState(3).rand(rows, n + len(gd.RESULT_STATS))
+    Y = np.random.RandomState(4).rand(rows, 18, 3)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 200 * 1024)
+    rec = bench.dump_outputs(str(tmp_path / "a"), table, n, Y=Y)
+    bench.dump_outputs(str(tmp_path / "b"), table, n, Y=Y)
+    assert rec["sampled"] and rec["bytes"] <= 200 * 1024 and "sample_rows" in rec["arrays"]
+    idx = np.load(tmp_path / "a" / "sample_rows.npy")
+    assert idx.dtype == np.float64 and np.array_equal(idx, np.load(tmp_path / "b" / "sample_rows.npy"))
+    idx = idx.astype(int)
+    assert 0 < len(idx) < rows and np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "q.npy"), table[idx, :n])
+    assert np.array_equal(np.load(tmp_path / "a" / "Y.npy"), Y[idx])
+    assert np.array_equal(np.load(tmp_path / "a" / "f.npy"), table[idx, n + list(gd.RESULT_STATS).index("f")])
 
 
 def test_bench_refuses_a_wrong_world_size():

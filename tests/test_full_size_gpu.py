@@ -406,9 +406,9 @@ def test_rccl_gather_under_torchrun(torch_cuda):
     # strong-scaling workload through the same path (c5: cheap)
     c = _bench(launcher, "--backend", "nccl", "--config", "c5")
     assert c["gather"]["rows"] == 65536 and c["scaling"] == "strong" and c["success_rate"] > 0.99
-    # the driver's own invocation (no --config) under the launcher: the headline plus every other
+    # the default workload with --full under the launcher: the headline plus every other
     # BASELINE workload under "configs", all through the same process group
-    d = _bench(launcher, "--backend", "nccl")
+    d = _bench(launcher, "--backend", "nccl", "--full")
     assert d["config"]["config"] == "c2" and d["gather"]["backend"] == "nccl" and d["gather"]["rows"] == 4096
     assert set(d["configs"]) == {"c3", "c4", "c4_share_of_8", "c5", "c5_nolimits", "c2_column", "c4_column"}
     # the default lines run the per-edge product form, the *_column lines the column form -- and say so
@@ -424,6 +424,33 @@ def test_rccl_gather_under_torchrun(torch_cuda):
         cf = d["configs"][name]
         assert cf["value"] > lo and 0 < cf["roofline"]["frac_executed"] <= cf["roofline"]["frac"] < 1, (name, cf)
     assert d["configs"]["c3"]["success_rate"] > 0.88 and d["configs"]["c5"]["success_rate"] > 0.999
+
+
+def test_bench_plain_run_dumps_its_last_step(torch_cuda, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times the headline alone (no CPU baseline, serving,
+    other configs or seeds) and with --dump-outputs writes what its last timed step computed: q and the
+    statistics are the table whose sha256 the line reports, Y the points [B, N, k], float64 throughout."""
+    import hashlib
+    from graphik_amd import distributed as gd
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--batch", "256", "--dump-outputs", str(tmp_path)], env=env, timeout=600,
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "f64"
+    assert not {"configs", "seeds", "cpu_baseline", "serving"} & set(d), sorted(d)
+    names = ["q"] + list(gd.RESULT_STATS)
+    got = {k: np.load(tmp_path / (k + ".npy")) for k in names + ["Y"]}
+    assert all(a.dtype == np.float64 and len(a) == 256 for a in got.values())
+    assert got["q"].shape == (256, 7) and got["Y"].shape == (256, 18, 3)
+    table = np.column_stack([got[k] for k in names])
+    assert hashlib.sha256(np.ascontiguousarray(table).tobytes()).hexdigest() == d["gather"]["sha256"]
+    assert np.mean(got["pos_err"] < 0.01) > 0.9
 
 
 SHARDED_RCCL = r'''

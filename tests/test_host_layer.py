@@ -159,13 +159,12 @@ def test_api_surface():
     assert len(rs.RiemannianSolver.create_cost_limits(np.zeros((4, 4)), om, 0 * om, 0 * om)) == 3
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/graphik/robots/urdfs"),
-                    reason="reference URDF data only exists in the build container")
 @pytest.mark.parametrize("name,urdf", [("lwa4d", "lwa4d.urdf"), ("ur10", "ur10_mod.urdf"),
                                        ("kuka", "kuka_iiwr.urdf")])
 def test_urdf_reader_reproduces_packaged_constants(name, urdf):
+    """The reference's URDF files (stored as fixtures under tests/golden/urdf/) read by our URDF reader."""
     from graphik_amd.utils.roboturdf import RobotURDF
-    u = RobotURDF("/root/reference/graphik/robots/urdfs/" + urdf)
+    u = RobotURDF(os.path.join(REPO, "tests", "golden", "urdf", urdf))
     n = u.n_q_joints
     r = u.make_Revolute3d(np.pi * np.ones(n), -np.pi * np.ones(n))
     assert np.abs(r.T0_array() - load_golden(name)["T0"]).max() < 1e-12
