@@ -343,9 +343,14 @@ __device__ inline void rtr_solve_one(Ctx &cx, const Params &p, const gik_trace &
           // 1072 -> 1048 -> 1004 cycles per iteration)
           // (the last permitted iteration, :495, is routed through the cold block as well, so
           // that the loop has a single exit edge)
+          // SPLIT: the residual test is applied from j = 0 on, without the scalar test of j against mininner.  A step
+          // before mininner that meets it merely takes the cold block, which tests j >= mininner itself, finds no exit
+          // and falls through with the same values; a NaN new_r_r still passes !(x <= t) as before.  Together with the
+          // structurizer leaving uniform branches alone (build.py, UNIT_FLAGS) this takes 191 -> 185 instructions
+          // out of the lone wavefront's step (NOTEBOOK 12); without that flag the same source is slower.
+          const bool rr_plain = SPLIT ? !(new_r_r <= target2_hi) : !((j >= p.mininner) & (new_r_r <= target2_hi));
           const bool plain = (model_value < model_prev) & (d_Hd > 0.0) & (e_Pe_new < T_cur) &
-                             (beta_p >= 1e-3) & !((j >= p.mininner) & (new_r_r <= target2_hi)) &
-                             (j + 1 < p.maxinner);
+                             (beta_p >= 1e-3) & rr_plain & (j + 1 < p.maxinner);
           double beta = beta_p;
           double rr_test = new_r_r;      // what the residual test sees (the recurrences keep the prediction)
           if (__builtin_expect(UNI(!plain), 0)) {   // any exit, a NaN, or the accuracy guard
