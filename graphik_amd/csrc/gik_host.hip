@@ -206,6 +206,12 @@ struct gik_template {
   std::mutex prep_mutex;            // for the previous one (whatever stream it ran on)
   bool prep_pending = false;
   int sweeps;
+  // joint-configuration seeds (gik_seed_batch): FK tables built at attach; seed_ok is false (and seed_why says why)
+  // for a graph with a node that neither a frame nor an anchor places
+  gik::SeedConst sc = {};
+  size_t seed_smem = 0;
+  bool seed_ok = false;
+  std::string seed_why;
 };
 static constexpr int kCounterRing = 256;
 
@@ -973,6 +979,88 @@ void gik_template_destroy(gik_template *t) {
   delete t;
 }
 
+// The tables of seed_kernel: T0[parent]^-1 T0[j] per joint, the parents along the end-effector paths, a root-first
+// order, and per graph node where graph.realization puts it (_pose_goal, graph_revolute.py:243-249: p_j = trans F_j,
+// q_j = p_j + axis_length z_j; graph_planar.py:136-145: every child u pins p_u = trans F_u and its parent
+// p_parent = p_u - |parent u| x_u, the last child in get_all_poses' order winning; nodes it does not name keep
+// their POS: anchor_pos).  Returns false only when an upload fails; a graph the recipe does not cover leaves
+// seed_ok false.
+static bool seed_tables(gik_template *t, const gik_pipeline_desc *d, const std::vector<int> &path, int n_ee) {
+  const int N = t->N, K = t->K, D = K + 1, DD = D * D, n = d->n_joints;
+  std::vector<int> parent(n + 1, -2), order;
+  for (int e = 0; e < n_ee; ++e)
+    for (int k = 0; k <= n; ++k) {
+      const int j = path[(size_t)e * (n + 1) + k];
+      if (j < 0) break;
+      const int p = k == 0 ? -1 : path[(size_t)e * (n + 1) + k - 1];
+      if (parent[j] == -2) {
+        parent[j] = p;
+        order.push_back(j);
+      } else if (parent[j] != p) {
+        t->seed_why = "joint " + std::to_string(j) + " has two parents on the end-effector paths";
+        return true;
+      }
+    }
+  std::vector<double> Trel((size_t)(n + 1) * DD, 0.0);
+  for (int j : order) {
+    const int p = parent[j];
+    if (p < 0) continue;
+    const double *A = d->T0 + (size_t)p * DD, *B = d->T0 + (size_t)j * DD;
+    double *R = Trel.data() + (size_t)j * DD;
+    // rigid inverse of A times B: rotation A_R^T B_R, translation A_R^T (B_t - A_t)
+    for (int r = 0; r < K; ++r) {
+      for (int c = 0; c < K; ++c) {
+        double acc = 0.0;
+        for (int u = 0; u < K; ++u) acc += A[u * D + r] * B[u * D + c];
+        R[r * D + c] = acc;
+      }
+      double acc = 0.0;
+      for (int u = 0; u < K; ++u) acc += A[u * D + r] * (B[u * D + K] - A[u * D + K]);
+      R[r * D + K] = acc;
+    }
+    R[K * D + K] = 1.0;
+  }
+  std::vector<int> frame(N, -1), anchor(N, -1);
+  std::vector<double> coef(N, 0.0);
+  for (int a = 0; a < d->n_anchor; ++a)
+    if (d->anchor_index[a] >= 0 && d->anchor_index[a] < N) anchor[d->anchor_index[a]] = a;
+  for (int j : order) {
+    if (K == 3) {
+      frame[d->p_index[j]] = j;
+      coef[d->p_index[j]] = 0.0;
+      frame[d->q_index[j]] = j;
+      coef[d->q_index[j]] = d->axis_length;
+    } else if (parent[j] >= 0) {
+      const double *R = Trel.data() + (size_t)j * DD;
+      frame[d->p_index[j]] = j;
+      coef[d->p_index[j]] = 0.0;
+      frame[d->p_index[parent[j]]] = j;
+      coef[d->p_index[parent[j]]] = -std::sqrt(R[0 * D + K] * R[0 * D + K] + R[1 * D + K] * R[1 * D + K]);
+    }
+  }
+  for (int i = 0; i < N; ++i)
+    if (frame[i] < 0 && anchor[i] < 0) {
+      t->seed_why = "graph node " + std::to_string(i) + " is placed by neither a joint frame nor an anchor";
+      return true;
+    }
+  bool ok = true;
+  gik::SeedConst sc;
+  sc.Trel = upload(t, Trel.data(), Trel.size(), ok);
+  std::vector<int> par(parent);
+  for (int &p : par) p = p < -1 ? -1 : p;
+  sc.fk_parent = upload(t, par.data(), par.size(), ok);
+  sc.fk_order = upload(t, order.data(), order.size(), ok);
+  sc.node_frame = upload(t, frame.data(), frame.size(), ok);
+  sc.node_coef = upload(t, coef.data(), coef.size(), ok);
+  sc.node_anchor = upload(t, anchor.data(), anchor.size(), ok);
+  sc.n_fk = (int)order.size();
+  if (!ok) return false;
+  t->sc = sc;
+  t->seed_smem = sizeof(double) * (size_t)(n + 1) * DD;
+  t->seed_ok = true;
+  return true;
+}
+
 int gik_pipeline_attach(gik_template *t, const gik_pipeline_desc *d) {
   using namespace gik;
   if (!t || !d) return fail("null argument");
@@ -1111,6 +1199,7 @@ int gik_pipeline_attach(gik_template *t, const gik_pipeline_desc *d) {
       }
     }
   }
+  if (!seed_tables(t, d, path, pc.n_ee)) return fail("device upload failed");
   t->has_pipe = true;
   return 0;
 }
@@ -1199,6 +1288,48 @@ int gik_ik_batch(const gik_template *t, const double *d_T_goal, int B, double *d
                  double *d_Y, gik_stats *d_stats, double *d_q, double *d_pos_err,
                  double *d_rot_err, void *stream) {
   int rc = gik_prepare_batch(t, d_T_goal, B, d_targets, d_Y, nullptr, stream);
+  if (rc) return rc;
+  rc = gik_solve_batch(t, d_Y, d_targets, B, d_Y, d_stats, nullptr, stream);
+  if (rc) return rc;
+  return gik_recover_batch(t, d_Y, d_T_goal, B, d_q, d_pos_err, d_rot_err, stream);
+}
+
+int gik_seed_batch(const gik_template *t, const double *d_T_goal, const double *d_q_init, int B, double *d_targets,
+                   double *d_Y_init, void *stream) {
+  using namespace gik;
+  if (!t || B < 0) return fail("bad argument");
+  if (!t->has_pipe) return fail("no pipeline attached (gik_pipeline_attach)");
+  if (!t->seed_ok) return fail("gik_seed_batch: this graph cannot be seeded on the device: " + t->seed_why);
+  if (B == 0) return 0;
+  if (!d_q_init) return fail("gik_seed_batch: null d_q_init (seed joint angles [B][n] are required)");
+  if (!d_T_goal || !d_targets || !d_Y_init) return fail("null buffer");
+  SeedArgs a;
+  a.pc = t->pc;
+  a.sc = t->sc;
+  a.T_goal = d_T_goal;
+  a.q_init = d_q_init;
+  a.targets = d_targets;
+  a.Y_init = d_Y_init;
+  a.B = B;
+  const int grid = std::min(B, t->n_cu * 8);
+  hipLaunchKernelGGL(seed_kernel, dim3(grid), dim3(WAVE), t->seed_smem, (hipStream_t)stream, a);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int gik_ik_batch_seeded(const gik_template *t, const double *d_T_goal, const double *d_q_init, int B,
+                        double *d_targets, double *d_Y, gik_stats *d_stats, double *d_q, double *d_pos_err,
+                        double *d_rot_err, void *stream) {
+  using namespace gik;
+  if (!t || B < 0) return fail("bad argument");
+  if (!t->has_pipe) return fail("no pipeline attached (gik_pipeline_attach)");
+  if (B == 0) return 0;
+  if (!d_q_init) return fail("gik_ik_batch_seeded: null d_q_init (seed joint angles [B][n] are required)");
+  if (!d_T_goal || !d_targets || !d_Y || !d_stats || !d_q || !d_pos_err || !d_rot_err) return fail("null buffer");
+  // refused before the seed kernel is queued, so that a capture is left without half a call in it
+  if (capturing_stream(stream))
+    return fail("gik_ik_batch_seeded: the stream is capturing (hipStreamBeginCapture); batch calls cannot be captured into a graph");
+  int rc = gik_seed_batch(t, d_T_goal, d_q_init, B, d_targets, d_Y, stream);
   if (rc) return rc;
   rc = gik_solve_batch(t, d_Y, d_targets, B, d_Y, d_stats, nullptr, stream);
   if (rc) return rc;

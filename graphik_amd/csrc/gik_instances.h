@@ -3,7 +3,7 @@
 // GIK_KERNELS_<GROUP>(X) calls X(<function signature>) for every instantiation of the group; gik_k_<group>.hip expands
 // it with GIK_INSTANTIATE, gik_host.hip expands all groups with GIK_EXTERN_TEMPLATE (so that taking a kernel's address
 // there -- the variant tables, hipLaunchKernelGGL -- refers to the other file's symbol instead of compiling the kernel
-// a second time).  The four non-template kernels (prep_wave_kernel, recover_kernel, anch_init_kernel,
+// a second time).  The five non-template kernels (prep_wave_kernel, recover_kernel, seed_kernel, anch_init_kernel,
 // anch_gather_kernel) are defined where GIK_DEFINE_PLAIN_KERNELS is set: gik_k_prep.hip.
 #pragma once
 

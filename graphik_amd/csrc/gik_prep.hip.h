@@ -1463,6 +1463,95 @@ __global__ void __launch_bounds__(64) recover_kernel(RecoverArgs a)
 }
 #endif
 
+// ---------------------------------------------------------------------------------------------
+// seed_kernel: joint-configuration warm start.  One wavefront per goal:
+//   targets [T]  -- exactly the prepare kernels' rule (goal_distance, src >= 0 ? g*g : term_static)
+//   Y_init [N*K] -- graph.realization(q_init) in node order (graph_base.py:112-120 through _pose_goal,
+//                   graph_revolute.py:243-249 / graph_planar.py:136-145): the frames of q_init by
+//                   F_j = F_parent(j) Rz(q_j) T0_parent^-1 T0_j (recover_kernel's walk, each joint once),
+//                   then row i = trans(F_f) + coef * axis(F_f) for its recipe (f, coef), or anchor_pos.
+// Lane 0 walks the frames into LDS (a handful of 4x4 products per joint); the rows and targets are
+// written by all lanes, consecutive lanes on consecutive doubles.
+struct SeedConst {
+  const double *Trel;      // [n+1][(K+1)^2]  T0[parent(j)]^-1 T0[j]  (row j = 0 unused)
+  const int *fk_parent;    // [n+1]  parent joint on the ee paths (-1: root)
+  const int *fk_order;     // [n_fk] joints in an order that puts every parent before its children (root first)
+  const int *node_frame;   // [N]  frame a node is read from, -1: anchor_pos[node_anchor]
+  const double *node_coef; // [N]  row = trans + coef * axis (axis z for K = 3, x for K = 2)
+  const int *node_anchor;  // [N]  anchor slot of a node without frame
+  int n_fk;
+};
+
+struct SeedArgs {
+  PipeConst pc;
+  SeedConst sc;
+  const double *T_goal;  // [B][n_ee][(K+1)^2]
+  const double *q_init;  // [B][n]
+  double *targets;       // [B][T]
+  double *Y_init;        // [B][N*K]
+  int B;
+};
+
+__global__ void __launch_bounds__(WAVE) seed_kernel(SeedArgs a)
+#ifndef GIK_DEFINE_PLAIN_KERNELS
+    ;      // (defined in gik_k_prep.hip)
+#else
+{
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const PipeConst &pc = a.pc;
+  const SeedConst &sc = a.sc;
+  const int N = pc.N, K = pc.K, D = K + 1, DD = D * D, n = pc.n_joints, lane = threadIdx.x;
+  const int axis = (K == 3) ? 2 : 0;
+  double *F = smem;   // [n+1][DD] frames of this goal's q_init
+  for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
+    const double *Tg = a.T_goal + (size_t)b * DD * pc.n_ee;
+    for (int t = lane; t < pc.T; t += WAVE) {
+      const int src = pc.term_src[t];
+      double g = 0.0;
+      if (src >= 0) {
+        int an, gn;
+        g = goal_distance(pc, Tg, src, an, gn);
+      }
+      a.targets[(size_t)b * pc.T + t] = src >= 0 ? g * g : pc.term_static[t];
+    }
+    if (lane == 0) {
+      const double *q = a.q_init + (size_t)b * n;
+      for (int o = 0; o < sc.n_fk; ++o) {
+        const int j = sc.fk_order[o], p = sc.fk_parent[j];
+        double *Fj = F + j * DD;
+        if (p < 0) {
+          for (int e = 0; e < DD; ++e) Fj[e] = pc.T0[j * DD + e];
+          continue;
+        }
+        const double *Fp = F + p * DD, *R = sc.Trel + j * DD;
+        const double c = cos(q[j - 1]), s = sin(q[j - 1]);
+        for (int r = 0; r < K; ++r) {
+          // row r of Fp Rz(q): columns 0, 1 rotate, the rest stay
+          double m[4];
+          m[0] = Fp[r * D + 0] * c + Fp[r * D + 1] * s;
+          m[1] = Fp[r * D + 1] * c - Fp[r * D + 0] * s;
+          for (int cc = 2; cc < D; ++cc) m[cc] = Fp[r * D + cc];
+          for (int cc = 0; cc < D; ++cc) {
+            double acc = (cc == K) ? m[K] : 0.0;
+            for (int t = 0; t < K; ++t) acc += m[t] * R[t * D + cc];
+            Fj[r * D + cc] = acc;
+          }
+        }
+        for (int cc = 0; cc < D; ++cc) Fj[K * D + cc] = (cc == K) ? 1.0 : 0.0;
+      }
+    }
+    __syncthreads();
+    double *Y = a.Y_init + (size_t)b * N * K;
+    for (int e = lane; e < N * K; e += WAVE) {
+      const int node = e / K, c = e - node * K, f = sc.node_frame[node];
+      Y[e] = f >= 0 ? F[f * DD + c * D + K] + sc.node_coef[node] * F[f * DD + c * D + axis]
+                    : pc.anchor_pos[sc.node_anchor[node] * K + c];
+    }
+    __syncthreads();   // (F is rewritten by the next goal)
+  }
+}
+#endif
+
 
 // ---------------------------------------------------------------------------------------------
 // Fixed-anchor formulation: glue between the robot-graph pipeline and the anchored

@@ -365,17 +365,47 @@ class Template:
                                                   self._stream()))
         return q, pe, re
 
-    def ik(self, T_goal, out=None):
+    def _seed_angles(self, q_init, B):
+        q = _dev(q_init, self.device)
+        if q.dim() == 1:
+            q = q[None].expand(B, -1)
+        assert q.shape == (B, self.n_joints), (tuple(q.shape), (B, self.n_joints))
+        return q.contiguous()
+
+    def seed(self, T_goal, q_init):
+        """goal poses + seed joint angles [B,n] (or [n]) -> (targets [B,T], Y_init [B,N,k]) on the
+        device (gik_seed_batch): the prepare kernels' targets and graph.realization(q_init)."""
+        T, B = self._poses(T_goal)
+        q = self._seed_angles(q_init, B)
+        targets = torch.empty(B, self.T, dtype=torch.float64, device=self.device)
+        Y0 = torch.empty(B, self.N * self.k, dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _ffi.check(self.lib.gik_seed_batch(self._h, T.data_ptr(), q.data_ptr(), B, targets.data_ptr(),
+                                               Y0.data_ptr(), self._stream()))
+        return targets, Y0.reshape(B, self.N, self.k)
+
+    def ik(self, T_goal, out=None, q_init=None):
         """Whole solve_with_riemannian pipeline for a batch of goal poses, one stream, no host
-        round trip: prepare -> solve -> recover.  Returns a dict of device tensors."""
+        round trip: prepare -> solve -> recover.  With q_init (seed joint angles [B,n] or [n], a
+        device tensor may be out["q"] itself) the initial point is the realization of q_init instead
+        of the bound-smoothing + MDS one: seed -> solve -> recover (gik_ik_batch_seeded).  Returns a
+        dict of device tensors."""
         T, B = self._poses(T_goal)
         if out is None:
             out = self.alloc_ik_buffers(B)
         with torch.cuda.device(self.device):
-            _ffi.check(self.lib.gik_ik_batch(self._h, T.data_ptr(), B, out["targets"].data_ptr(),
-                                             out["Y"].data_ptr(), out["stats"].data_ptr(),
-                                             out["q"].data_ptr(), out["pos_err"].data_ptr(),
-                                             out["rot_err"].data_ptr(), self._stream()))
+            if q_init is None:
+                _ffi.check(self.lib.gik_ik_batch(self._h, T.data_ptr(), B, out["targets"].data_ptr(),
+                                                 out["Y"].data_ptr(), out["stats"].data_ptr(),
+                                                 out["q"].data_ptr(), out["pos_err"].data_ptr(),
+                                                 out["rot_err"].data_ptr(), self._stream()))
+            else:
+                q0 = self._seed_angles(q_init, B)
+                _ffi.check(self.lib.gik_ik_batch_seeded(self._h, T.data_ptr(), q0.data_ptr(), B,
+                                                        out["targets"].data_ptr(), out["Y"].data_ptr(),
+                                                        out["stats"].data_ptr(), out["q"].data_ptr(),
+                                                        out["pos_err"].data_ptr(), out["rot_err"].data_ptr(),
+                                                        self._stream()))
         res = {"x": out["Y"].reshape(B, self.N, self.k), "q": out["q"], "pos_err": out["pos_err"],
                "rot_err": out["rot_err"]}
         res.update(_decode_stats(out["stats"]))

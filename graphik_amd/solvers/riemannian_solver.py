@@ -16,7 +16,7 @@ import time
 import numpy as np
 import torch
 
-from ..engine import Template, build_terms
+from ..engine import Template, _alloc_stats, _decode_stats, build_terms
 from ..utils import dgp
 from ..utils.constants import POS
 from ..utils.lie import as_matrix
@@ -383,6 +383,66 @@ class BatchProblem:
                 Ys = list(ex.map(one, spans))
         return self.targets_from_D(D), np.concatenate(Ys, axis=0)
 
+    def _seed_recipe(self):
+        """How graph.realization places each node (graph_base.py:112-120 through _pose_goal): the
+        joints' parents along the end-effector paths in root-first order, T0[parent]^-1 T0[j], and
+        per node the frame it is read from (-1: its POS) and the coefficient of the frame axis
+        (z for 3-D, x for planar) added to the frame's translation."""
+        if getattr(self, "_recipe", None) is not None:
+            return self._recipe
+        g, d, N = self.graph, self.dim, self.N
+        T0 = self.robot.T0_array()
+        parent, order = {}, []
+        for ee in self.end_effectors:                   # get_all_poses' order (robot_base.py:185-193)
+            path = [int(name[1:]) for name in self.robot.kinematic_map["p0"][ee]]
+            for k, j in enumerate(path):
+                if j not in parent:
+                    parent[j] = path[k - 1] if k else -1
+                    order.append(j)
+        Trel = np.zeros_like(T0)
+        for j in order:
+            if parent[j] >= 0:
+                Trel[j] = np.linalg.inv(T0[parent[j]]) @ T0[j]
+        frame, coef = np.full(N, -1, dtype=np.int64), np.zeros(N)
+        for j in order:
+            if d == 3:                                  # graph_revolute.py:243-249
+                frame[g.index(f"p{j}")] = frame[g.index(f"q{j}")] = j
+                coef[g.index(f"q{j}")] = g.axis_length
+            elif parent[j] >= 0:                        # graph_planar.py:136-145: the last child wins
+                u, v = g.index(f"p{j}"), g.index(f"p{parent[j]}")
+                frame[u], coef[u] = j, 0.0
+                frame[v], coef[v] = j, -g.dist[v, u]
+        pos = np.full((N, d), np.nan)
+        for i, name in enumerate(g.node_ids):
+            if POS in g.nodes[name]:
+                pos[i] = g.nodes[name][POS]
+        self._recipe = (T0, parent, order, Trel, frame, coef, pos)
+        return self._recipe
+
+    def seed_points(self, q):
+        """Joint angles [B,n] (or [n]) -> their graph realizations [B,N,k] in node order: the
+        reference's warm start pos_from_graph(graph.realization(q)) (the Y_init of
+        experiments/simple_ik_examples/test_chain_2d_new.py:46-59), batched.  The host mirror of
+        gik_seed_batch."""
+        T0, parent, order, Trel, frame, coef, pos = self._seed_recipe()
+        Q = np.atleast_2d(np.asarray(q, dtype=float))
+        B, d = Q.shape[0], self.dim
+        F = np.zeros((B,) + T0.shape)
+        for j in order:
+            if parent[j] < 0:
+                F[:, j] = T0[j]
+                continue
+            c, s = np.cos(Q[:, j - 1]), np.sin(Q[:, j - 1])
+            Rz = np.broadcast_to(np.identity(d + 1), (B, d + 1, d + 1)).copy()
+            Rz[:, 0, 0], Rz[:, 0, 1], Rz[:, 1, 0], Rz[:, 1, 1] = c, -s, s, c
+            F[:, j] = F[:, parent[j]] @ Rz @ Trel[j]
+        axis = 2 if d == 3 else 0
+        Y = np.broadcast_to(pos, (B, self.N, d)).copy()
+        on = frame >= 0
+        Fn = F[:, frame[on]]                             # [B, nodes, d+1, d+1]
+        Y[:, on] = Fn[:, :, :d, d] + coef[on][None, :, None] * Fn[:, :, :d, axis]
+        return Y
+
     def targets_from_D(self, D):
         """[B,N,N] squared-distance matrices -> [B,T] per-term targets (Template.targets_from_D without
         a device handle)."""
@@ -570,14 +630,56 @@ def clear_problem_cache():
     _closure_templates.clear()
 
 
-def solve_batch(graph, T_goals, use_limits=True, params=None, device=None, Y_init=None):
+def _seed_angles(q_init, B, n, name="q_init"):
+    """[B,n] or [n] (broadcast) finite joint angles -> [B,n] float array; ValueError otherwise."""
+    q = q_init.detach().cpu().numpy() if isinstance(q_init, torch.Tensor) else np.asarray(q_init, dtype=float)
+    q = np.asarray(q, dtype=float)
+    if q.shape == (n,):
+        q = np.broadcast_to(q, (B, n))
+    if q.shape != (B, n):
+        raise ValueError(f"{name} must have shape [{B}, {n}] or [{n}], got {list(q.shape)}")
+    if not np.all(np.isfinite(q)):
+        raise ValueError(f"{name} has non-finite entries")
+    return np.ascontiguousarray(q)
+
+
+def solve_batch(graph, T_goals, use_limits=True, params=None, device=None, Y_init=None, q_init=None):
     """Batched solve_with_riemannian.  T_goals: [B,d+1,d+1] array or list of poses.
-    Returns (q [B,n], Y [B,N,k], info dict of arrays)."""
+    Returns (q [B,n], Y [B,N,k], info dict of arrays).
+
+    q_init (warm start): joint angles [B,n] or [n] (one seed for all goals), columns in
+    robot.q_to_array order.  Each solve then starts from the realization of its seed -- the
+    reference's RiemannianSolver.solve(D_goal, omega, Y_init=pos_from_graph(graph.realization(q_init)),
+    bounds=None) -- instead of from bound smoothing + MDS; on the device pipeline that is one
+    gik_ik_batch_seeded call, otherwise the host realization (BatchProblem.seed_points) feeds the
+    device solve.  Y_init and q_init exclude each other."""
     T = np.stack([as_matrix(t) for t in T_goals]) if not isinstance(T_goals, np.ndarray) \
         else np.asarray(T_goals, dtype=float)
+    if q_init is not None:
+        if Y_init is not None:
+            raise ValueError("pass Y_init or q_init, not both")
+        q_init = _seed_angles(q_init, T.shape[0], graph.robot.n)
     prob = _problem_for(graph, use_limits, params, device)
     t0 = time.time()
-    if prob.device_pipeline and Y_init is None:
+    if q_init is not None:
+        if prob.device_pipeline:
+            res = prob.template.ik(T, q_init=q_init)      # seed -> solve -> recover (gik_ik_batch_seeded)
+            torch.cuda.synchronize(prob.template.device)
+            dt = time.time() - t0
+            Y = res["x"].cpu().numpy()
+            q = res["q"].cpu().numpy()
+            pos, rot = res["pos_err"].cpu().numpy(), res["rot_err"].cpu().numpy()
+        else:
+            targets = prob.targets_from_D(prob.assemble(T)[0])
+            Y0 = prob.seed_points(q_init)
+            t0 = time.time()
+            res = prob.template.solve(Y0, targets)
+            torch.cuda.synchronize(prob.template.device)
+            dt = time.time() - t0
+            Y = res["x"].cpu().numpy()
+            q = prob.joint_variables(Y, T)
+            pos, rot = prob.pose_errors(q, T)
+    elif prob.device_pipeline and Y_init is None:
         # everything on the device: prepare -> solve -> recover (gik_ik_batch)
         res = prob.template.ik(T)
         torch.cuda.synchronize(prob.template.device)
@@ -601,6 +703,66 @@ def solve_batch(graph, T_goals, use_limits=True, params=None, device=None, Y_ini
             "inner_iterations": res["inner_total"].cpu().numpy(),
             "stop": res["stop"].cpu().numpy(), "time": np.full(len(Y), dt / max(len(Y), 1)),
             "solve_time": dt, "pos_err": pos, "rot_err": rot}
+    return q, Y, info
+
+
+def solve_trajectory(graph, T_path, q_start, use_limits=True, params=None, device=None, return_Y=False):
+    """Path tracking: B paths of L waypoints, each waypoint a warm-started solve_batch.
+
+    T_path: [B, L, d+1, d+1] goal poses ([B, L, n_ee, 4, 4] for robots with several end effectors).
+    Waypoint 0 is seeded by q_start ([B,n] or [n]); waypoint l by the joint angles recovered at
+    waypoint l-1.  On the device pipeline those angles never leave the device: the L calls of
+    gik_ik_batch_seeded are queued on one stream without a host synchronisation in between.  A
+    waypoint whose solve fails (stop != 0, or a large pos_err) still seeds the next one; there is no
+    retry -- check info["stop"] / info["pos_err"].
+
+    Returns q [B, L, n], Y [B, L, N, k] (None unless return_Y), and info with [B, L] arrays
+    iterations, inner_iterations, stop, f(x), gradnorm, pos_err, rot_err, plus solve_time (seconds,
+    whole path)."""
+    T = np.asarray(T_path, dtype=float)
+    B, L = T.shape[:2]
+    n = graph.robot.n
+    q0 = _seed_angles(q_start, B, n, "q_start")
+    prob = _problem_for(graph, use_limits, params, device)
+    if not prob.device_pipeline:
+        qs, Ys, infos, dt = [], [], [], 0.0
+        q_prev = q0
+        for l in range(L):
+            q_prev, Y, info = solve_batch(graph, T[:, l], use_limits, params, device, q_init=q_prev)
+            qs.append(q_prev)
+            Ys.append(Y)
+            infos.append(info)
+            dt += info["solve_time"]
+        out = {key: np.stack([i[key] for i in infos], axis=1)
+               for key in ("iterations", "inner_iterations", "stop", "f(x)", "gradnorm", "pos_err", "rot_err")}
+        out["solve_time"] = dt
+        return np.stack(qs, axis=1), (np.stack(Ys, axis=1) if return_Y else None), out
+    tpl = prob.template
+    dev = tpl.device
+    f64 = dict(dtype=torch.float64, device=dev)
+    Tw = torch.from_numpy(np.ascontiguousarray(np.swapaxes(T, 0, 1))).to(dev)     # [L, B, ...]: waypoint-major
+    q_all = torch.empty(L, B, n, **f64)
+    Y_all = torch.empty(L if return_Y else 1, B, tpl.N * tpl.k, **f64)
+    stats = _alloc_stats(L * B, dev).reshape(L, B, -1)
+    pe, re = torch.empty(L, B, **f64), torch.empty(L, B, **f64)
+    targets = torch.empty(B, tpl.T, **f64)
+    q_prev = torch.from_numpy(q0).to(dev)
+    torch.cuda.synchronize(dev)
+    t0 = time.time()
+    for l in range(L):
+        out = {"targets": targets, "Y": Y_all[l if return_Y else 0], "stats": stats[l], "q": q_all[l],
+               "pos_err": pe[l], "rot_err": re[l]}
+        tpl.ik(Tw[l], out=out, q_init=q_prev)
+        q_prev = q_all[l]
+    torch.cuda.synchronize(dev)
+    dt = time.time() - t0
+    st = _decode_stats(stats.reshape(L * B, -1))
+    info = {"iterations": st["iterations"], "inner_iterations": st["inner_total"], "stop": st["stop"],
+            "f(x)": st["f"], "gradnorm": st["gradnorm"], "pos_err": pe.reshape(-1), "rot_err": re.reshape(-1)}
+    info = {key: v.reshape(L, B).T.cpu().numpy() for key, v in info.items()}
+    info["solve_time"] = dt
+    q = q_all.permute(1, 0, 2).cpu().numpy()
+    Y = Y_all.reshape(L, B, tpl.N, tpl.k).permute(1, 0, 2, 3).cpu().numpy() if return_Y else None
     return q, Y, info
 
 

@@ -147,7 +147,7 @@ enum {
  *   - anchored templates: the event pair read by gik_anchored_last_solve_ms (diagnostic; with
  *     concurrent callers it reports whichever call recorded last).
  * Because of that bookkeeping a batch call cannot be captured into a HIP graph: on a stream that is capturing
- * (hipStreamBeginCapture) gik_solve_batch / gik_ik_batch / gik_anchored_ik_batch -- and gik_prepare_batch where it
+ * (hipStreamBeginCapture) gik_solve_batch / gik_ik_batch / gik_ik_batch_seeded / gik_anchored_ik_batch -- and gik_prepare_batch where it
  * uses the workgroup kernel -- return an error before touching the stream.  (A batch is one persistent launch; there
  * is no launch overhead for a graph to remove.)
  * Results never depend on that bookkeeping, on the stream, on the number of calls in flight or on how the problems of
@@ -345,6 +345,30 @@ int gik_recover_batch(const gik_template *t, const double *d_Y, const double *d_
 int gik_ik_batch(const gik_template *t, const double *d_T_goal, int B, double *d_targets,
                  double *d_Y, gik_stats *d_stats, double *d_q, double *d_pos_err,
                  double *d_rot_err, void *stream);
+
+/* ---- joint-configuration warm starts --------------------------------------------------------
+ * The reference's warm start is RiemannianSolver.solve(D_goal, omega, Y_init=..., bounds=None)
+ * (riemannian_solver.py:178-218; a `bounds` argument would discard the seed, :197-198), with the seed
+ * built as its examples build it: Y_init = pos_from_graph(graph.realization(q_init))
+ * (experiments/simple_ik_examples/test_chain_2d_new.py:46-59; graph_base.py:112-120).
+ *
+ * gik_seed_batch: goal poses [B][n_ee][(k+1)^2] + seed angles d_q_init [B][n] (joint p_i in column i-1)
+ *   -> per-term targets [B][T], bit-identical to gik_prepare_batch's, and Y_init [B][N*k]: the realization of
+ *   q_init in node order -- p_i = translation of frame i and (k = 3) q_i = p_i + axis_length z_i
+ *   (graph_revolute.py:243-249); k = 2: graph_planar.py:136-145 (a child u pins p_u and its parent's
+ *   p_u - |parent u| x_u); every other node (x, y, obstacles) at its anchor_pos.  The goal nodes take the
+ *   SEED's positions, as in the reference.  Frames follow ee_path from T0 (gik_recover_batch's walk).  No
+ *   bound smoothing, no MDS.  Errors: no pipeline attached, B < 0, a null buffer; a graph with a node that
+ *   neither a joint frame nor an anchor places.
+ * gik_ik_batch_seeded: gik_seed_batch -> gik_solve_batch -> gik_recover_batch on one stream; the buffers
+ *   are gik_ik_batch's.  d_q_init MAY alias d_q (the seed is read by the first kernel, q written by the
+ *   last; path tracking feeds each waypoint's answer back this way).  A capturing stream is refused before
+ *   anything is queued, like gik_ik_batch.                                                      */
+int gik_seed_batch(const gik_template *t, const double *d_T_goal, const double *d_q_init, int B,
+                   double *d_targets, double *d_Y_init, void *stream);
+int gik_ik_batch_seeded(const gik_template *t, const double *d_T_goal, const double *d_q_init, int B,
+                        double *d_targets, double *d_Y, gik_stats *d_stats, double *d_q,
+                        double *d_pos_err, double *d_rot_err, void *stream);
 
 /* ---- fixed-anchor formulation: "intended" obstacle semantics (opt-in) -----------------------
  * graph_base.py:182-211 ties every node with a known position (base frame, goal nodes, obstacle
