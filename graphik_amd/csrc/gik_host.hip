@@ -1642,8 +1642,9 @@ int gik_solve_batch(const gik_template *t, const double *d_Y_init, const double 
   // (At one wave per SIMD -- batches up to 6 problems per SIMD -- round-robin slicing LOSES 5-8 %: a
   // straggler that happens to start at t = 0 is better off keeping its slot than sharing it for the
   // first ~20 ms; measured on 4096 LWA4D / KUKA / UR10 goals, four seeds each, tools/attic/dev_rr_midbatch.py.)
-  const bool mig = !t->is_block && !cg && !t->anchored && t->variant->solve_mig &&
-                   (!t->hess_per_edge || t->variant->solve_strict_mig) && t->p.theta == 1.0 &&
+  // (the build of the form that runs: <3, 10> has a per-edge tail-spreading build but no column-form one)
+  const bool mig = !t->is_block && !cg && !t->anchored &&
+                   (t->hess_per_edge ? t->variant->solve_strict_mig : t->variant->solve_mig) && t->p.theta == 1.0 &&
                    wpc > 4 && B > grid && !(a.dbg & (1 | 512));
   gik_template::SliceWs *sw = nullptr;
   // graphs beyond 128 nodes (node-per-lane kernel on four wavefronts): the clique's target triangle of every resident
