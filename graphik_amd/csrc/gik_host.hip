@@ -4,6 +4,7 @@
 
 #include "gik_kernels.hip.h"
 #include "gik_instances.h"
+#include <memory>
 
 namespace gik {
 GIK_ALL_KERNELS(GIK_EXTERN_TEMPLATE)
@@ -16,16 +17,8 @@ struct NptVariant {
   size_t (*lds)(int, int, int, int);
   size_t (*ctg)(int);      // doubles of global clique-target workspace per workgroup (0: the triangle sits in LDS)
 };
-template <int TL, int NS, int NW, bool CTG>
-static size_t npt_lds_of(int n_pairs, int n_wrows, int n_rows, int n_terms) {
-  return NptCtx<TL, NS, NW, CTG>::lds_bytes(n_pairs, n_wrows, n_rows, n_terms);
-}
-template <int TL, int NS, int NW, bool CTG>
-static size_t npt_ctg_of(int n_pairs) {
-  return NptCtx<TL, NS, NW, CTG>::ctg_doubles(n_pairs);
-}
 #define GIK_NPT_VARIANT(TL, NS, NW, CTG) \
-  {TL, NW, rtr_npt_kernel<TL, NS, NW, CTG>, kat_npt_kernel<TL, NS, NW, CTG>, npt_lds_of<TL, NS, NW, CTG>, npt_ctg_of<TL, NS, NW, CTG>}
+  {TL, NW, rtr_npt_kernel<TL, NS, NW, CTG>, kat_npt_kernel<TL, NS, NW, CTG>, NptCtx<TL, NS, NW, CTG>::lds_bytes, NptCtx<TL, NS, NW, CTG>::ctg_doubles}
 // (four wavefronts per problem: graphs of 129 .. 255 nodes, clique targets in global memory)
 static const NptVariant kNptVariants[] = {GIK_NPT_VARIANT(1, 1, 2, false), GIK_NPT_VARIANT(4, 1, 2, false),
                                           GIK_NPT_VARIANT(1, 2, 1, false), GIK_NPT_VARIANT(4, 2, 1, false),
@@ -51,65 +44,67 @@ typedef void (*solve_fn)(SolveArgs);
 typedef void (*kat_fn)(KatArgs);
 typedef size_t (*lds_fn)(int);
 
-template <int K, int D>
-static size_t lds_bytes_of(int T) {
-  return WaveCtx<K, D>::lds_bytes(T);
-}
-
-template <int K, int D>
-static size_t lds_bytes_strict(int T) {
-  if constexpr (K == 3) return WaveCtxStrict<D>::lds_bytes(T);
-  return 0;
-}
-
-template <int K, int D>
-static size_t lds_bytes_anch(int T) {
-  return WaveCtx<K, D, true>::lds_bytes(T);
-}
-struct Variant {
-  int K, maxdeg;
-  solve_fn solve;        // theta == 1 (reference default)
-  solve_fn solve_theta;  // any theta
-  solve_fn solve_cg;     // ConjugateGradient
-  kat_fn kat;
-  lds_fn lds;
-  solve_fn solve_anch;   // fixed-anchor formulation (k = 3, theta == 1), or null
-  kat_fn kat_anch;
-  lds_fn lds_anch;
-  solve_fn solve_mig;    // theta == 1 with tail spreading (MigCtl), or null
-  solve_fn solve_strict, solve_strict_mig;   // hessian_form = GIK_HESS_PER_EDGE (k = 3, theta == 1), or null
-  kat_fn kat_strict;
-  lds_fn lds_strict;
-  solve_fn solve_strict_theta;               // ... any theta
+// The compiled one-unknown-per-lane builds: one row per (K, slots, form), exactly what gik_instances.h instantiates.
+// A build a form does not have stays null: only the functions below fill a row, each with what its form compiles.
+// (PER_EDGE: hessian_form = GIK_HESS_PER_EDGE, k = 3, TrustRegions; ANCHORED: the fixed-anchor formulation, k = 3, theta == 1)
+enum Form { COLUMN, PER_EDGE, ANCHORED };
+struct WaveRow {
+  int K, slots;
+  Form form;
+  solve_fn solve = nullptr;         // theta == 1 (reference default)
+  solve_fn solve_theta = nullptr;   // any theta
+  solve_fn solve_cg = nullptr;      // ConjugateGradient
+  solve_fn solve_spread = nullptr;  // theta == 1 with tail spreading (MigCtl)
+  kat_fn kat = nullptr;
+  lds_fn lds = nullptr;
 };
-#define GIK_VARIANT(K, D) \
-  {K, D, rtr_wave_kernel<K, D, true>, rtr_wave_kernel<K, D, false>, rcg_wave_kernel<K, D>, kat_wave_kernel<K, D>, \
-   lds_bytes_of<K, D>, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}
-#define GIK_VARIANT_S(K, D) \
-  {K, D, rtr_wave_kernel<K, D, true>, rtr_wave_kernel<K, D, false>, rcg_wave_kernel<K, D>, kat_wave_kernel<K, D>, \
-   lds_bytes_of<K, D>, nullptr, nullptr, nullptr, nullptr, rtr_wave_kernel<K, D, true, false, false, true>, \
-   rtr_wave_kernel<K, D, true, false, true, true>, kat_wave_kernel<K, D, false, true>, lds_bytes_strict<K, D>, \
-   rtr_wave_kernel<K, D, false, false, false, true>}
-#define GIK_VARIANT_A(K, D) \
-  {K, D, rtr_wave_kernel<K, D, true>, rtr_wave_kernel<K, D, false>, rcg_wave_kernel<K, D>, kat_wave_kernel<K, D>, \
-   lds_bytes_of<K, D>, rtr_wave_kernel<K, D, true, true>, kat_wave_kernel<K, D, true>, lds_bytes_anch<K, D>, nullptr, \
-   nullptr, nullptr, nullptr, nullptr, nullptr}
-#define GIK_VARIANT_AM(K, D) \
-  {K, D, rtr_wave_kernel<K, D, true>, rtr_wave_kernel<K, D, false>, rcg_wave_kernel<K, D>, kat_wave_kernel<K, D>, \
-   lds_bytes_of<K, D>, rtr_wave_kernel<K, D, true, true>, kat_wave_kernel<K, D, true>, lds_bytes_anch<K, D>, \
-   rtr_wave_kernel<K, D, true, false, true>, rtr_wave_kernel<K, D, true, false, false, true>, \
-   rtr_wave_kernel<K, D, true, false, true, true>, kat_wave_kernel<K, D, false, true>, lds_bytes_strict<K, D>, \
-   rtr_wave_kernel<K, D, false, false, false, true>}
-// anchored templates only: the free-free formulation with more than 10 terms at a node runs on the
-// workgroup kernels (the 20-slot wavefront variant needed 796 B of scratch per lane: measured on the
+template <int K, int D>
+static WaveRow column_row(solve_fn solve_spread = nullptr) {
+  WaveRow r{K, D, COLUMN};
+  r.solve = rtr_wave_kernel<K, D, true>;
+  r.solve_theta = rtr_wave_kernel<K, D, false>;
+  r.solve_cg = rcg_wave_kernel<K, D>;
+  r.solve_spread = solve_spread;
+  r.kat = kat_wave_kernel<K, D>;
+  r.lds = WaveCtx<K, D>::lds_bytes;
+  return r;
+}
+template <int K, int D>
+static WaveRow per_edge_row() {
+  WaveRow r{K, D, PER_EDGE};
+  r.solve = rtr_wave_kernel<K, D, true, false, false, true>;
+  r.solve_theta = rtr_wave_kernel<K, D, false, false, false, true>;
+  r.solve_spread = rtr_wave_kernel<K, D, true, false, true, true>;
+  r.kat = kat_wave_kernel<K, D, false, true>;
+  r.lds = WaveCtxStrict<D>::lds_bytes;
+  return r;
+}
+template <int K, int D>
+static WaveRow anchored_row() {
+  WaveRow r{K, D, ANCHORED};
+  r.solve = rtr_wave_kernel<K, D, true, true>;
+  r.kat = kat_wave_kernel<K, D, true>;
+  r.lds = WaveCtx<K, D, true>::lds_bytes;
+  return r;
+}
+// <3, 20> is compiled for anchored templates only: the free-free formulation with more than 10 terms at a node runs
+// on the workgroup kernels (the 20-slot wavefront variant needed 796 B of scratch per lane: measured on the
 // two-end-effector tree of tests/golden/tree5.npz, 13 terms, 144 k against 382 k solves/s;
 // tools/gpu_variants.py.  <3,10> 48 B: -1.3 % against <3,9>; <2,16> 168 B: 5x faster than the
 // workgroup kernels on the planar trees -- both stay)
-#define GIK_VARIANT_ANCH_ONLY(K, D) \
-  {K, D, nullptr, nullptr, nullptr, nullptr, lds_bytes_of<K, D>, rtr_wave_kernel<K, D, true, true>, \
-   kat_wave_kernel<K, D, true>, lds_bytes_anch<K, D>, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}
-static const Variant kVariants[] = {GIK_VARIANT_AM(3, 9), GIK_VARIANT_S(3, 10), GIK_VARIANT_ANCH_ONLY(3, 20),
-                                    GIK_VARIANT(2, 6), GIK_VARIANT(2, 16), GIK_VARIANT(2, 31)};
+static const WaveRow kWaveRows[] = {
+    column_row<3, 9>(rtr_wave_kernel<3, 9, true, false, true>), per_edge_row<3, 9>(), anchored_row<3, 9>(),
+    column_row<3, 10>(), per_edge_row<3, 10>(),
+    anchored_row<3, 20>(),
+    column_row<2, 6>(), column_row<2, 16>(), column_row<2, 31>()};
+
+// the row of (K, form) with the fewest slots that hold `slots` terms per node, or null
+static const WaveRow *find_row(int K, Form form, int slots) {
+  const WaveRow *best = nullptr;
+  for (const WaveRow &r : kWaveRows)
+    if (r.K == K && r.form == form && r.slots >= slots && (!best || r.slots < best->slots)) best = &r;
+  return best;
+}
 
 }  // namespace gik
 
@@ -118,7 +113,7 @@ struct gik_template {
   // fixed-anchor formulation (gik_template_create_anchored)
   bool anchored = false;
   hipEvent_t ev_solve0 = nullptr, ev_solve1 = nullptr;   // around the solve kernel of the last gik_anchored_ik_batch
-  gik::AnchArgs an;                 // device pointers + counts (anchor_goal filled per call)
+  gik::AnchArgs an = {};            // device pointers + counts (anchor_goal filled per call)
   double *d_targets_const = nullptr;   // [T] template-constant targets of the free-free terms
   int full_N = 0, n_anchor = 0;
   int *d_free_full = nullptr, *d_anchor_full = nullptr;   // node index in the full robot graph
@@ -126,13 +121,21 @@ struct gik_template {
   int solver;
   gik::CgParams cg;
   gik::Params p;
-  const gik::Variant *variant;
-  uint32_t *d_slot_meta;
+  // the kernels of this template, resolved once at creation (resolve_kernels)
+  struct Kernels {
+    void (*solve)(gik::SolveArgs) = nullptr;          // wavefront path: the solve kernel ...
+    void (*solve_spread)(gik::SolveArgs) = nullptr;   // ... its tail-spreading build, or null: none compiled for this solver / theta / form
+    void (*kat)(gik::KatArgs) = nullptr;              // ... and the known-answer kernel
+    void (*block_solve)(gik::SolveArgs, int) = nullptr;   // workgroup path
+    void (*block_kat)(gik::KatArgs, int) = nullptr;
+    const void *occupancy = nullptr;                  // the kernel waves_per_cu was queried on
+  } kernels;
+  uint32_t *d_slot_meta = nullptr;
   // Ring of work-queue heads, one per in-flight solve call.  A slot is handed out again only
   // behind the event recorded after the launch that used it last (the new call's stream waits for
   // it), so a wrap of the ring can never reset the counter of a kernel that is still running --
   // whatever the number of calls in flight.
-  unsigned int *d_counters;
+  unsigned int *d_counters = nullptr;
   struct CounterSlot {
     hipEvent_t done = nullptr;
     bool pending = false;
@@ -173,7 +176,6 @@ struct gik_template {
   size_t smem_bytes;
   bool is_block;  // workgroup-per-problem path
   int SL;         // slots per thread on the block path
-  int SLE;        // ... of which the first SLE hold equality terms (or padding) only
   gik::BlockTabs bt = {nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, 0, 0};
   // node-per-lane path (rtr_npt_kernel): trust-region solves and the known-answer entry points of
   // 3-D graphs beyond one wavefront's 64 unknowns; the workgroup tables above stay (ConjugateGradient)
@@ -187,10 +189,11 @@ struct gik_template {
   void (*quad_solve)(gik::SolveArgs) = nullptr;
   size_t quad_smem = 0;
   int quad_waves_per_cu = 8;
-  int quad_min_batch = 0;      // smallest batch that runs it (12 problems per CU; GIK_QUAD_MIN_BATCH)
+  int quad_min_batch = -1;     // smallest batch that runs it (GIK_QUAD_MIN_BATCH; else 12 problems per CU, set with quad_solve)
+  bool no_npt = false, no_quad = false;   // GIK_NO_NPT / GIK_NO_QUAD: creation leaves these kernels out
   // device pre/post-processing (gik_pipeline_attach)
-  bool has_pipe;
-  gik::PipeConst pc;
+  bool has_pipe = false;
+  gik::PipeConst pc = {};
   std::vector<void *> pipe_allocs;
   size_t prep_smem;
   int prep_waves_per_cu = 8;   // resident prepare waves (workgroups on the block variant) per CU
@@ -260,6 +263,668 @@ static const T *upload(gik_template *t, const T *host, size_t count, bool &ok) {
   return static_cast<const T *>(d);
 }
 
+namespace gik {      // ---- template creation, step by step (create_impl below) ----
+
+// everything that needs no table; the order of the checks is the order in which two faults are reported
+static int validate_desc(const gik_template_desc *d, const gik_anchored_desc *ad) {
+  if (ad) {
+    if (d->k != 3 || d->solver != GIK_SOLVER_TRUST_REGIONS || d->theta != 1.0 || d->force_block_path)
+      return fail("anchored templates: k = 3, TrustRegions, theta = 1, wavefront path");
+    if (ad->n_anchor < 1 || ad->n_anchor > ANCH_MAXA || ad->n_goal_anchor < 0 || ad->n_goal_anchor > ad->n_anchor)
+      return fail("anchored templates: 1 <= n_anchor <= 16, goal anchors are the last rows");
+    if (ad->n_obs > ANCH_MAXOBS) return fail("anchored templates: at most 128 obstacles");
+    if (ad->n_obs < 0 || ad->n_pin < 0 || d->N > 63 || !ad->term_target || !ad->free_full_index ||
+        !ad->anchor_full_index || !ad->anchor_pos)
+      return fail("anchored templates: bad descriptor");
+  }
+  if (d->abi_version != GIK_ABI_VERSION) return fail("ABI version mismatch");
+  if (d->k != 2 && d->k != 3) return fail("k must be 2 or 3");
+  if (d->solver != GIK_SOLVER_TRUST_REGIONS && d->solver != GIK_SOLVER_CONJUGATE_GRADIENT)
+    return fail("solver must be GIK_SOLVER_TRUST_REGIONS or GIK_SOLVER_CONJUGATE_GRADIENT");
+  if (d->cg_beta_type < 0 || d->cg_beta_type > 3) return fail("cg_beta_type must be 0..3");
+  if (d->clique_closed_form < GIK_CLIQUE_AUTO || d->clique_closed_form > GIK_CLIQUE_DENSE)
+    return fail("clique_closed_form must be GIK_CLIQUE_AUTO, _OFF or _DENSE");
+  if (d->hessian_form != GIK_HESS_COLUMN && d->hessian_form != GIK_HESS_PER_EDGE && d->hessian_form != GIK_HESS_AUTO)
+    return fail("hessian_form must be GIK_HESS_AUTO, GIK_HESS_COLUMN or GIK_HESS_PER_EDGE");
+  // 255 = what the node-per-lane kernel's 8-bit row fields take (four wavefronts per problem beyond 128 nodes);
+  // every other kernel stops at 128 (checked in create_impl, where the kernel is chosen)
+  if (d->N < 2 || d->N > 255) return fail("N must be in [2, 255]");
+  if (d->N > BLOCK_MAXN &&
+      (ad || d->k != 3 || d->solver != GIK_SOLVER_TRUST_REGIONS || d->theta != 1.0 || d->force_block_path == 1))
+    return fail("graphs of more than 128 nodes run on the node-per-lane kernel only: k = 3, TrustRegions, theta = 1, "
+                "not anchored, force_block_path != 1");
+  if (d->n_terms < 1 || d->n_terms > 65535) return fail("n_terms out of range");
+  return 0;
+}
+
+// solver parameters and scheduling knobs: the descriptor's, then the developer overrides of the environment -- read
+// once, here, never inside a batch call
+static void read_params(gik_template *t, const gik_template_desc *d) {
+  t->N = d->N;
+  t->K = d->k;
+  t->T = d->n_terms;
+  t->p.mingradnorm = d->mingradnorm;
+  t->p.theta = d->theta;
+  t->p.kappa = d->kappa;
+  t->p.rho_prime = d->rho_prime;
+  t->p.rho_regularization = d->rho_regularization;
+  t->p.maxiter = d->maxiter;
+  t->p.maxinner = d->maxinner;
+  t->p.mininner = d->mininner;
+  t->p.planar_proj_exact = d->planar_proj_exact;
+  t->solver = d->solver;
+  t->cg.mingradnorm = d->mingradnorm;
+  t->cg.minstepsize = d->cg_minstepsize;
+  t->cg.orth_value = d->cg_orth_value;
+  t->cg.maxiter = d->maxiter;
+  t->cg.beta_type = d->cg_beta_type;
+  t->cg.planar_proj_exact = d->planar_proj_exact;
+  t->dbg = d->debug_flags;
+  if (const char *e = getenv("GIK_DBG")) t->dbg = atoi(e);
+  t->wpc_override = std::max(0, d->waves_per_cu);
+  if (const char *e = getenv("GIK_WAVES_PER_CU")) t->wpc_override = std::max(1, atoi(e));
+  // workgroup kernel, table scene, 4096 goals (round 3): slice 96 / 160 / 256 -> 1430 / 1430 / 1409 solves/s and
+  // 755 / 586 / 368 MB of HBM traffic per launch (every resumed slice re-reads the problem's 45 KB of
+  // targets; 207 MB are the algorithmic bytes).  Without slicing: ~15 % slower (round 2: 795 vs 929).
+  t->slice_its = d->slice_outer_its < 0 ? 256 : d->slice_outer_its;
+  // node-per-lane kernel, table scene, 4096 goals (round 4): slice 0 / 48 / 96 / 256 / 600 -> 1689 / 1896 / 1894 / 1861 /
+  // 1774 solves/s (two problems per CU: 512 slots, a third of the requeues of the workgroup kernel)
+  // HBM traffic per launch (PMC): 603 MB at 128 = 2.9 x the algorithmic 207 MB (every resume re-reads the problem's 45 KB of
+  // clique targets); 192 is the compromise
+  t->npt_slice_its = d->slice_outer_its < 0 ? 192 : d->slice_outer_its;
+  // wavefront kernel: 256 ... 32 iterations per slice give the same time (NOTEBOOK 8.3); the longest of
+  // them moves the fewest problems through HBM (KUKA 65536: 118 k hand-overs of ~1.5 KB instead of 562 k at 64)
+  t->wave_slice_its = d->slice_outer_its < 0 ? 256 : d->slice_outer_its;
+  t->wave_slice_auto = d->slice_outer_its < 0 && !getenv("GIK_SLICE");   // (an explicit length is taken literally)
+  if (const char *e = getenv("GIK_SLICE")) t->slice_its = t->npt_slice_its = t->wave_slice_its = std::max(0, atoi(e));
+  if (const char *e = getenv("GIK_SLICE_CYCLES")) t->wave_slice_cycles = std::max(0, atoi(e));
+  t->counter_slot.resize(kCounterRing);
+  if (const char *e = getenv("GIK_COUNTER_RING")) t->counter_ring = std::min(kCounterRing, std::max(1, atoi(e)));
+  if (const char *e = getenv("GIK_SLICE_POOL")) t->slice_pool = std::min(gik_template::kSlicePool, std::max(1, atoi(e)));
+  t->no_npt = getenv("GIK_NO_NPT") != nullptr;      // (developer A/B switches)
+  t->no_quad = getenv("GIK_NO_QUAD") != nullptr;
+  if (const char *e = getenv("GIK_QUAD_MIN_BATCH")) t->quad_min_batch = std::max(0, atoi(e));
+}
+
+struct Ent { int j, kind, term, owner; };
+typedef std::vector<std::vector<Ent>> SlotLists;
+static void sort_slot_lists(SlotLists &ents) {
+  for (auto &e : ents)
+    std::stable_sort(e.begin(), e.end(), [](const Ent &a, const Ent &b) {
+      return a.j != b.j ? a.j < b.j : a.kind < b.kind;
+    });
+}
+
+// the slot table of the one-unknown-per-lane kernels, [slots][64]
+static std::vector<uint32_t> wave_slot_table(const gik_template_desc *d, const SlotLists &ents, int slots) {
+  std::vector<uint32_t> meta((size_t)slots * WAVE, 0);
+  for (int lane = 0; lane < WAVE; ++lane) {
+    const bool active = lane < d->N * d->k;
+    const int node = active ? lane / d->k : 0;
+    const int comp = active ? lane % d->k : 0;
+    for (int s = 0; s < slots; ++s) {
+      // padding slot: this lane's own row (idle lanes: the all-zero dump row), kind none
+      uint32_t m = meta_pack(active ? node : TILE_ROWS - 1, 0, 0, 0);
+      if (active && s < (int)ents[node].size()) {
+        const Ent &e = ents[node][s];
+        m = meta_pack(e.j, e.term, e.kind, (comp == 0 && e.owner) ? 1 : 0);
+      }
+      meta[(size_t)s * WAVE + lane] = m;
+    }
+  }
+  return meta;
+}
+
+// A rigid clique -- a set of nodes every pair of which is tied by an equality term (the
+// anchors of a scene with many obstacles) -- is taken out of the slot tables and handled in
+// closed form (gik_block.hip.h).  Greedy by equality degree; rows 0..n_clq-1 of the LDS
+// arrays are the clique's nodes in ascending order, the other nodes follow.
+struct CliqueRows {
+  int n_clq = 0;
+  std::vector<int> eqterm;        // [N][N] the equality term that ties two nodes, -1 = none
+  std::vector<char> in_clq;       // [N]
+  std::vector<int> node_of_row;   // [rowcap] -1 = none
+  std::vector<int> nc_term;       // the terms kept in the slot tables, in the caller's order
+  SlotLists ents;                 // [rowcap] their slot entries in row numbering; `term` = index in nc_term
+};
+static CliqueRows clique_rows(const gik_template_desc *d, int dbg, int rowcap) {
+  const int N = d->N, T = d->n_terms;
+  CliqueRows c;
+  std::vector<int> deg(N, 0), order(N), row_of(N);
+  c.eqterm.assign((size_t)N * N, -1);
+  c.in_clq.assign(N, 0);
+  c.node_of_row.assign(rowcap, -1);
+  for (int t = 0; t < T; ++t) {
+    const int i = d->term_i[t], j = d->term_j[t];
+    if (d->term_kind[t] == GIK_TERM_EQ && c.eqterm[(size_t)i * N + j] < 0) {
+      c.eqterm[(size_t)i * N + j] = c.eqterm[(size_t)j * N + i] = t;
+      ++deg[i];
+      ++deg[j];
+    }
+  }
+  const int clique_min = (dbg & 64) ? 4 : 16;
+  if (d->k == 3 && !(dbg & 128) && d->clique_closed_form != GIK_CLIQUE_OFF) {
+    for (int i = 0; i < N; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return deg[a] > deg[b]; });
+    std::vector<int> A;
+    for (int v : order) {
+      bool all = true;
+      for (int a : A) all = all && c.eqterm[(size_t)v * N + a] >= 0;
+      if (all) A.push_back(v);
+    }
+    if ((int)A.size() >= clique_min) {
+      c.n_clq = (int)A.size();
+      for (int a : A) c.in_clq[a] = 1;
+    }
+  }
+  // with a clique the other nodes take the LAST rows (128 - F ...): their threads, the only
+  // ones with more than a slot or two, then sit in wavefronts that have no clique work
+  int r = 0;
+  for (int pass = 0; pass < 2; ++pass) {
+    if (pass == 1 && c.n_clq) r = rowcap - (N - c.n_clq);
+    for (int i = 0; i < N; ++i)
+      if ((c.in_clq[i] != 0) == (pass == 0)) {
+        row_of[i] = r;
+        c.node_of_row[r++] = i;
+      }
+  }
+  // slot entries in row numbering, clique pairs left out; `term` = index in the LDS target table
+  c.ents.assign(rowcap, {});
+  for (int t = 0; t < T; ++t) {
+    const int i = d->term_i[t], j = d->term_j[t], kind = d->term_kind[t];
+    if (c.n_clq && kind == GIK_TERM_EQ && c.in_clq[i] && c.in_clq[j] && c.eqterm[(size_t)i * N + j] == t) continue;
+    const int ri = row_of[i], rj = row_of[j], tc = (int)c.nc_term.size();
+    c.nc_term.push_back(t);
+    c.ents[ri].push_back({rj, kind, tc, ri < rj ? 1 : 0});
+    c.ents[rj].push_back({ri, kind, tc, rj < ri ? 1 : 0});
+  }
+  sort_slot_lists(c.ents);
+  return c;
+}
+
+// tables of the 512-thread workgroup kernels (128 rows); graphs beyond 128 nodes have none (all-zero loop bounds, one slot word)
+struct BlockHost {
+  std::vector<int> clq_term, clq_pair_term, wave_sl = std::vector<int>(2 * BLOCK_WAVES, 0);
+  std::vector<unsigned short> clq_pid;   // [M][512] compact pair id per (thread, partner), 0xffff = none
+  std::vector<uint32_t> meta = std::vector<uint32_t>(1, 0u);
+  int SL = 0;      // slots per thread
+};
+static BlockHost block_tables(int N, int T, const CliqueRows &c) {
+  BlockHost b;
+  const int n_clq = c.n_clq, M = (n_clq + 3) / 4;
+  b.clq_term.assign((size_t)std::max(M, 1) * BLOCK_NT, -1);
+  for (int tid = 0; tid < BLOCK_NT; ++tid) {
+    const int row = tid >> 2, part = tid & 3;
+    for (int m = 0; m < M && row < n_clq; ++m) {
+      const int j = 4 * m + part;
+      if (j < n_clq && j != row)
+        b.clq_term[(size_t)m * BLOCK_NT + tid] = c.eqterm[(size_t)c.node_of_row[row] * N + c.node_of_row[j]];
+    }
+  }
+  // each clique pair once (its target is staged in LDS per problem) + the pair id of every
+  // (thread, partner): ids fit 16 bits (at most 128 * 127 / 2 pairs)
+  std::vector<int> pid_of_term((size_t)T, -1);
+  b.clq_pid.assign((size_t)std::max(M, 1) * BLOCK_NT, (unsigned short)0xffff);
+  for (size_t q = 0; q < b.clq_term.size(); ++q) {
+    const int term = b.clq_term[q];
+    if (term < 0) continue;
+    if (pid_of_term[term] < 0) {
+      pid_of_term[term] = (int)b.clq_pair_term.size();
+      b.clq_pair_term.push_back(term);
+    }
+    b.clq_pid[q] = (unsigned short)pid_of_term[term];
+  }
+  // four threads per node; a node's equality terms are dealt to them in turn, then its hinge
+  // terms continuing the rotation, so that both kinds spread evenly (the padded slot count of a
+  // wavefront is the largest equality count plus the largest hinge count among its threads:
+  // 3 + 2 -> 2 + 1 for the free nodes of the table scene).  Within a thread the equality terms
+  // come first (slots [0, SLE_w): no kind decoding in the kernels) and the hinge terms last
+  // (slots [SLE_w, SL_w)), with the bounds of the thread's wavefront w; unused slots are inert
+  // padding (own node, kind 0, not owner)
+  SlotLists eqs(BLOCK_NT), hinges(BLOCK_NT);
+  for (int node = 0; node < BLOCK_MAXN; ++node) {
+    int turn = 0;
+    for (int pass = 0; pass < 2; ++pass)
+      for (const Ent &en : c.ents[node])
+        if ((en.kind == GIK_TERM_EQ) == (pass == 0))
+          (pass == 0 ? eqs : hinges)[4 * node + (turn++ & 3)].push_back(en);
+  }
+  for (int tid = 0; tid < BLOCK_NT; ++tid) {
+    const int w = tid / WAVE;
+    b.wave_sl[2 * w] = std::max(b.wave_sl[2 * w], (int)eqs[tid].size());
+    b.wave_sl[2 * w + 1] = std::max(b.wave_sl[2 * w + 1], (int)hinges[tid].size());
+  }
+  // A wavefront with few slots runs them as ONE kind-decoding loop over each thread's equality
+  // terms followed by its hinge terms ({0, T_w}: T_w = most terms of any of its threads) when that
+  // is shorter than the padded split loops (table scene: 1 + 1 -> 1 for the base / goal nodes,
+  // 3 + 1 -> 3 for the free nodes; an iteration is two dependent LDS round trips).
+  std::vector<char> merged(BLOCK_WAVES, 0);
+  for (int w = 0; w < BLOCK_WAVES; ++w) {
+    int tot = 0;
+    for (int tid = w * WAVE; tid < (w + 1) * WAVE; ++tid)
+      tot = std::max(tot, (int)(eqs[tid].size() + hinges[tid].size()));
+    if (tot <= 8 && tot < b.wave_sl[2 * w] + b.wave_sl[2 * w + 1]) {
+      merged[w] = 1;
+      b.wave_sl[2 * w] = 0;
+      b.wave_sl[2 * w + 1] = tot;
+    } else {
+      b.wave_sl[2 * w + 1] += b.wave_sl[2 * w];   // {SLE_w, SL_w}
+    }
+    b.SL = std::max(b.SL, b.wave_sl[2 * w + 1]);
+  }
+  b.meta.assign((size_t)std::max(b.SL, 1) * BLOCK_NT, 0);
+  for (int tid = 0; tid < BLOCK_NT; ++tid) {
+    const int node = tid >> 2, w = tid / WAVE, sle = merged[w] ? (int)eqs[tid].size() : b.wave_sl[2 * w];
+    for (int s = 0; s < b.SL; ++s) {
+      uint32_t m = meta_pack(c.node_of_row[node] >= 0 ? node : 0, 0, 0, 0);
+      const std::vector<Ent> &src = s < sle ? eqs[tid] : hinges[tid];
+      const int e = s < sle ? s : s - sle;
+      if (e < (int)src.size()) m = meta_pack(src[e].j, src[e].term, src[e].kind, src[e].owner);
+      b.meta[(size_t)s * BLOCK_NT + tid] = m;
+    }
+  }
+  return b;
+}
+
+// ---- node-per-lane tables (gik_npt.hip.h): the host side of NptTabs, field for field ----
+struct NptHost {
+  bool ok = false;      // the graph fits the kernel's tables
+  std::vector<int> node_of_row, clq_pair_term, term_tgt;
+  std::vector<unsigned char> prow_of_slot, wslot_of_row;
+  std::vector<uint32_t> term_rec;
+  std::vector<unsigned short> gather;
+  NptTabs n = {};       // the counts; its pointers are set by the upload, one per vector above
+};
+// Two layouts.  Two wavefronts per problem, one node per lane (default): the nodes outside the
+// clique take the first rows, then the clique's nodes, those that carry slot terms first -- every
+// end node of a slot term then sits in wavefront 0, which evaluates the terms, and the
+// direction / term tables need no barrier of their own.  One wavefront, two nodes per lane
+// (debug_flags 2048): the clique's nodes take rows 0..n_clq-1, the others follow; nodes that carry
+// slot terms go to EVEN rows where possible, so that a lane's second node has few or none (its
+// gather list is as long as the busiest second node's).
+// NW wavefronts per problem ("two_waves": one node per lane, else two), `rows` thread slots
+static NptHost npt_tables(const gik_template_desc *d, const CliqueRows &c, bool two_waves, int NW, int rows) {
+  const int N = d->N, n_clq = c.n_clq, NSn = two_waves ? 1 : 2, NTn = NW * WAVE;
+  NptHost h;
+  h.n.n_clq = n_clq;
+  std::vector<int> sdeg(N, 0);
+  for (int t : c.nc_term) {
+    ++sdeg[d->term_i[t]];
+    ++sdeg[d->term_j[t]];
+  }
+  std::vector<int> cl_busy, cl_idle, others;
+  for (int i = 0; i < N; ++i) {
+    if (c.in_clq[i]) (sdeg[i] ? cl_busy : cl_idle).push_back(i);
+    else others.push_back(i);
+  }
+  auto by_deg = [&](int a, int b) { return sdeg[a] > sdeg[b]; };
+  std::stable_sort(cl_busy.begin(), cl_busy.end(), by_deg);
+  std::stable_sort(others.begin(), others.end(), by_deg);
+  // nrow[v]: row of node v in the point table; node_of_row[t]: node held by thread slot t
+  h.node_of_row.assign(rows, -1);
+  h.prow_of_slot.assign(rows, 0);
+  std::vector<int> nrow(N, -1), nslot(N, -1);
+  int n_rows = 0;
+  if (two_waves) {
+    h.n.cbase = (int)others.size();
+    int r = 0;
+    for (int v : others) nrow[v] = r++;
+    for (int v : cl_busy) nrow[v] = r++;
+    for (int v : cl_idle) nrow[v] = r++;
+    n_rows = r;
+    // thread slots: the nodes that carry slot terms on the even lanes 0, 2, ... of wavefront 0, each with a
+    // clique node WITHOUT slot terms next to it (its helper in the gather); everything else behind
+    std::vector<int> busy(others.begin(), others.end());
+    busy.insert(busy.end(), cl_busy.begin(), cl_busy.end());
+    busy.erase(std::remove_if(busy.begin(), busy.end(), [&](int v) { return sdeg[v] == 0; }), busy.end());
+    std::stable_sort(busy.begin(), busy.end(), by_deg);
+    std::vector<char> placed(N, 0);
+    int slot = 0;
+    size_t ih = 0;
+    const bool can_help = 2 * busy.size() <= (size_t)WAVE && cl_idle.size() >= busy.size();
+    for (int v : busy) {
+      h.node_of_row[slot] = v;
+      nslot[v] = slot++;
+      placed[v] = 1;
+      if (can_help) {
+        const int hn = cl_idle[ih++];
+        h.node_of_row[slot] = hn;
+        nslot[hn] = slot++;
+        placed[hn] = 1;
+      }
+    }
+    h.n.n_helped = can_help ? (int)busy.size() : 0;
+    for (int pass = 0; pass < 3; ++pass)
+      for (int v : (pass == 0 ? others : (pass == 1 ? cl_busy : cl_idle)))
+        if (!placed[v]) {
+          h.node_of_row[slot] = v;
+          nslot[v] = slot++;
+          placed[v] = 1;
+        }
+  } else {
+    h.n.cbase = 0;
+    size_t ib = 0, ii = 0;
+    for (int r = 0; r < n_clq; ++r) {
+      const bool want_busy = (r & 1) == 0;
+      int v;
+      if ((want_busy && ib < cl_busy.size()) || ii >= cl_idle.size()) v = cl_busy[ib++];
+      else v = cl_idle[ii++];
+      nrow[v] = r;
+    }
+    const int start = (n_clq + 1) & ~1;
+    const bool even_only = others.empty() || start + 2 * ((int)others.size() - 1) < rows;
+    n_rows = n_clq;
+    for (size_t q = 0; q < others.size(); ++q) {
+      const int r = even_only ? start + 2 * (int)q : n_clq + (int)q;
+      nrow[others[q]] = r;
+      n_rows = r + 1;
+    }
+    for (int v = 0; v < N; ++v) {      // thread slot = row
+      h.node_of_row[nrow[v]] = v;
+      nslot[v] = nrow[v];
+    }
+  }
+  for (int v = 0; v < N; ++v) h.prow_of_slot[nslot[v]] = (unsigned char)nrow[v];
+  h.n.n_rows = (n_rows + 1) & ~1;
+  // compact direction table: one row per node that carries slot terms
+  h.wslot_of_row.assign(rows, 255);
+  int n_wrows = 0;
+  std::vector<int> wslot_of_node(N, 255);
+  for (int t = 0; t < rows; ++t)
+    if (h.node_of_row[t] >= 0 && sdeg[h.node_of_row[t]]) {
+      wslot_of_node[h.node_of_row[t]] = n_wrows;
+      h.wslot_of_row[t] = (unsigned char)n_wrows++;
+      if (two_waves && t >= WAVE) h.n.term_sync = 1;
+    }
+  const int Tn = (int)c.nc_term.size();
+  if (Tn > 64 * 4 || n_wrows > 127) return h;
+  h.n.TL = Tn <= 64 ? 1 : 4;
+  h.term_rec.assign((size_t)h.n.TL * WAVE, 0u);
+  h.term_tgt.assign((size_t)h.n.TL * WAVE, -1);
+  for (size_t q = 0; q < h.term_rec.size(); ++q)   // padding: rows 0 / 0, kind 0, the zero direction row
+    h.term_rec[q] = ((uint32_t)n_wrows << 18) | ((uint32_t)n_wrows << 25);
+  struct GEnt { int other, kind, slot, neg; };
+  std::vector<std::vector<GEnt>> glist(rows);
+  for (int q = 0; q < Tn; ++q) {
+    const int t = c.nc_term[q], i = d->term_i[t], j = d->term_j[t], kind = d->term_kind[t];
+    const int ri = nrow[i], rj = nrow[j];
+    h.term_rec[q] = (uint32_t)ri | ((uint32_t)rj << 8) | ((uint32_t)kind << 16) |
+                    ((uint32_t)wslot_of_node[i] << 18) | ((uint32_t)wslot_of_node[j] << 25);
+    h.term_tgt[q] = t;
+    // term slot q = u * 64 + lane: the order of nc_term (= the reference's edge order)
+    glist[nslot[i]].push_back({j, kind, q, 0});
+    glist[nslot[j]].push_back({i, kind, q, 1});
+  }
+  int deg[2] = {0, 0};
+  for (int r = 0; r < rows; ++r)
+    std::stable_sort(glist[r].begin(), glist[r].end(), [](const GEnt &a, const GEnt &b) {
+      return a.other != b.other ? a.other < b.other : a.kind < b.kind;
+    });
+  for (int i = 0; i < h.n.n_helped; ++i) {      // the second half of a busy node's list moves to its helper
+    std::vector<GEnt> &own = glist[2 * i], &hlp = glist[2 * i + 1];
+    const size_t keep = (own.size() + 1) / 2;
+    hlp.assign(own.begin() + keep, own.end());
+    own.resize(keep);
+  }
+  for (int r = 0; r < rows; ++r) {
+    const int sl = NSn == 1 ? 0 : (r & 1);
+    deg[sl] = std::max(deg[sl], (int)glist[r].size());
+  }
+  h.n.DEG0 = deg[0];
+  h.n.DEG1 = deg[1];
+  const unsigned short pad = (unsigned short)(2 * Tn);
+  h.gather.assign((size_t)std::max(1, deg[0] + deg[1]) * NTn, pad);
+  for (int r = 0; r < rows; ++r) {
+    const int thr = r / NSn, sl = r % NSn;
+    for (size_t e = 0; e < glist[r].size(); ++e)
+      h.gather[(size_t)(sl ? deg[0] + (int)e : (int)e) * NTn + thr] =
+          (unsigned short)((glist[r][e].slot << 1) | glist[r][e].neg);
+  }
+  std::vector<int> node_at_row(rows, 0);
+  for (int v = 0; v < N; ++v) node_at_row[nrow[v]] = v;
+  for (int a = 0; a < c.n_clq; ++a)
+    for (int b = a + 1; b < c.n_clq; ++b)
+      h.clq_pair_term.push_back(c.eqterm[(size_t)node_at_row[h.n.cbase + a] * N + node_at_row[h.n.cbase + b]]);
+  h.n.n_pairs = (int)h.clq_pair_term.size();
+  h.n.n_wrows = n_wrows;
+  h.n.n_terms = Tn;
+  h.ok = deg[0] + deg[1] <= 16;      // NptCtx::NG packed words
+  return h;
+}
+
+// The kernels this template launches, chosen once from path, solver, theta, anchored and Hessian form; with them
+// hess_per_edge and the LDS bytes of a launch.  `row`: the wavefront path's table row (column form or anchored).
+static int resolve_kernels(gik_template *t, const gik_template_desc *d, const WaveRow *row, size_t block_lds) {
+  const bool cg = d->solver == GIK_SOLVER_CONJUGATE_GRADIENT, k3 = d->k == 3, theta1 = d->theta == 1.0;
+  gik_template::Kernels &kn = t->kernels;
+  if (t->is_block) {
+    kn.block_solve = cg ? (k3 ? rcg_block_kernel<3> : rcg_block_kernel<2>) : (k3 ? rtr_block_kernel<3> : rtr_block_kernel<2>);
+    kn.block_kat = k3 ? kat_block_kernel<3> : kat_block_kernel<2>;
+    kn.occupancy = (const void *)kn.block_solve;
+    t->smem_bytes = block_lds;
+    return block_lds > 160 * 1024 ? fail("graph too large for the LDS-resident block path") : 0;
+  }
+  // The product form concerns the one-unknown-per-lane kernel only (every other kernel forms s = y . w per edge
+  // anyway).  There the per-edge form exists for k = 3, TrustRegions, free-free graphs and is what GIK_HESS_AUTO
+  // selects; an explicit GIK_HESS_PER_EDGE without such a kernel is refused.
+  const WaveRow *pe = find_row(d->k, PER_EDGE, row->slots);
+  if (k3 && d->hessian_form != GIK_HESS_COLUMN) {
+    const bool have = row->form == COLUMN && !cg && pe && pe->slots == row->slots && pe->solve && pe->solve_theta;
+    if (!have && d->hessian_form == GIK_HESS_PER_EDGE)
+      return fail("hessian_form = GIK_HESS_PER_EDGE: wavefront kernel of 3-D free-free graphs, TrustRegions only");
+    t->hess_per_edge = have;
+  }
+  const WaveRow *r = t->hess_per_edge ? pe : row;
+  kn.solve = cg ? r->solve_cg : (theta1 ? r->solve : r->solve_theta);
+  kn.solve_spread = (cg || !theta1) ? nullptr : r->solve_spread;
+  kn.kat = r->kat;
+  // occupancy: of the build large batches run -- the small-batch build trades registers for latency, gik_rtr.hip.h SPLIT.  (Per-edge
+  // form: the tail-spreading build where there is one; column form: always the theta == 1 build.  The grids were tuned on these.)
+  kn.occupancy = (const void *)(t->hess_per_edge ? (kn.solve_spread ? kn.solve_spread : kn.solve) : (cg ? r->solve_cg : r->solve));
+  t->smem_bytes = r->lds(t->T);
+  return 0;
+}
+
+// device, slot table, work-queue heads, occupancy; `occ`: the unclamped answer of the occupancy query
+static int device_setup(gik_template *t, const gik_template_desc *d, const std::vector<uint32_t> &meta, int &occ) {
+  if (t->is_block && t->smem_bytes > 48 * 1024) {
+    // more than the default dynamic-LDS allowance: opt in for exactly what this template needs
+    for (const void *fn : {t->kernels.occupancy, (const void *)t->kernels.block_kat})
+      if (raise_dynamic_lds(fn, t->smem_bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail("cannot reserve " + std::to_string(t->smem_bytes) + " bytes of LDS per workgroup");
+      }
+  }
+  hipDeviceProp_t prop;
+  if (hipGetDevice(&t->device) != hipSuccess ||
+      hipGetDeviceProperties(&prop, t->device) != hipSuccess ||
+      hipMalloc((void **)&t->d_slot_meta, meta.size() * sizeof(uint32_t)) != hipSuccess ||
+      hipMalloc((void **)&t->d_counters, kCounterRing * sizeof(unsigned int)) != hipSuccess ||
+      hipMemcpy(t->d_slot_meta, meta.data(), meta.size() * sizeof(uint32_t),
+                hipMemcpyHostToDevice) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, t->kernels.occupancy, t->is_block ? BLOCK_NT : WAVE,
+                                                   t->smem_bytes) != hipSuccess)
+    return fail("HIP device setup failed (no GPU?)");
+  t->n_cu = prop.multiProcessorCount;
+  t->waves_per_cu = std::max(1, std::min(occ, 32));
+  if (!t->is_block && !t->anchored && t->solver == GIK_SOLVER_TRUST_REGIONS && t->K == 2 && t->N <= QUAD_NODES &&
+      t->maxdeg == 6 && d->theta == 1.0 && !(d->debug_flags & 8192) && !t->no_quad) {
+    t->quad_solve = rtr_quad_kernel<6>;
+    t->quad_smem = QuadCtx<6>::lds_bytes();
+    int qocc = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&qocc, (const void *)t->quad_solve, WAVE, t->quad_smem) == hipSuccess)
+      t->quad_waves_per_cu = std::max(1, std::min(qocc, 32));
+    if (t->quad_min_batch < 0) t->quad_min_batch = 12 * t->n_cu;
+  }
+  return 0;
+}
+
+// ---- fixed-anchor data ----
+static int upload_anchored(gik_template *t, const gik_anchored_desc *ad) {
+  const int N = t->N;
+  bool ok = true;
+  std::vector<double> tab(4 * ANCH_MAXA, 0.0);
+  for (int r = 0; r < ad->n_anchor; ++r)
+    for (int c = 0; c < 3; ++c) tab[r * 4 + c] = ad->anchor_pos[r * 3 + c];
+  std::vector<uint32_t> pm((size_t)ANCH_PMAX * WAVE, 0u);
+  std::vector<double> pt((size_t)ANCH_PMAX * WAVE, 0.0);
+  std::vector<int> cnt(N, 0);
+  for (int q = 0; q < ad->n_pin; ++q) {
+    const int i = ad->pin_node[q], r = ad->pin_anchor[q], kind = ad->pin_kind[q];
+    if (i < 0 || i >= N || r < 0 || r >= ad->n_anchor || kind < GIK_TERM_EQ || kind > GIK_TERM_UPPER || cnt[i] >= ANCH_PMAX) {
+      ok = false;
+      break;
+    }
+    for (int c = 0; c < 3; ++c) {      // every lane of the node walks all of the node's pinned terms
+      pm[(size_t)cnt[i] * WAVE + i * 3 + c] = (uint32_t)r | ((uint32_t)kind << 8);
+      pt[(size_t)cnt[i] * WAVE + i * 3 + c] = ad->pin_target[q];
+    }
+    ++cnt[i];
+  }
+  unsigned long long mask = 0;
+  for (int i = 0; i < N && ad->obs_node_mask; ++i)
+    if (ad->obs_node_mask[i]) mask |= 1ull << i;
+  AnchArgs &an = t->an;
+  an.anch_const = ok ? upload(t, tab.data(), tab.size(), ok) : nullptr;
+  an.pin_meta = upload(t, pm.data(), pm.size(), ok);
+  an.pin_tgt = upload(t, pt.data(), pt.size(), ok);
+  an.obs = ad->n_obs ? upload(t, ad->obs, (size_t)ad->n_obs * 4, ok) : nullptr;
+  an.obs_mask = mask;
+  an.n_obs = ad->n_obs;
+  an.n_goal = ad->n_goal_anchor;
+  an.goal_row0 = ad->n_anchor - ad->n_goal_anchor;
+  t->d_targets_const = const_cast<double *>(upload(t, ad->term_target, (size_t)t->T, ok));
+  t->d_free_full = const_cast<int *>(upload(t, ad->free_full_index, (size_t)N, ok));
+  t->d_anchor_full = const_cast<int *>(upload(t, ad->anchor_full_index, (size_t)ad->n_anchor, ok));
+  t->full_N = ad->full_N;
+  t->n_anchor = ad->n_anchor;
+  t->axis_length = ad->axis_length;
+  if (hipEventCreate(&t->ev_solve0) != hipSuccess || hipEventCreate(&t->ev_solve1) != hipSuccess) ok = false;
+  return ok ? 0 : fail("anchored templates: bad pinned term (node / anchor / kind out of range, or more than 8 per node) "
+                       "or device upload failed");
+}
+
+// upload of the node-per-lane tables and the kernel's LDS / occupancy; a template that did not ask for this kernel
+// (force_block_path != 2) stays on the workgroup kernels when the device refuses
+static int setup_npt(gik_template *t, const gik_template_desc *d, const NptHost &h, int NW) {
+  bool ok = true;
+  t->nt = h.n;
+  t->nt.node_of_row = upload(t, h.node_of_row.data(), h.node_of_row.size(), ok);
+  t->nt.clq_pair_term = upload(t, h.clq_pair_term.data(), h.clq_pair_term.size(), ok);
+  t->nt.term_rec = upload(t, h.term_rec.data(), h.term_rec.size(), ok);
+  t->nt.term_tgt = upload(t, h.term_tgt.data(), h.term_tgt.size(), ok);
+  t->nt.gather = upload(t, h.gather.data(), h.gather.size(), ok);
+  t->nt.wslot_of_row = upload(t, h.wslot_of_row.data(), h.wslot_of_row.size(), ok);
+  t->nt.prow_of_slot = upload(t, h.prow_of_slot.data(), h.prow_of_slot.size(), ok);
+  t->nt.clq_euclid = t->bt.clq_euclid;
+  for (const NptVariant &v : kNptVariants)
+    if (v.TL == h.n.TL && v.NW == NW) t->npt_variant = &v;
+  t->npt_smem = t->npt_variant->lds(h.n.n_pairs, h.n.n_wrows, h.n.n_rows, h.n.n_terms);
+  const void *fns[2] = {(const void *)t->npt_variant->solve, (const void *)t->npt_variant->kat};
+  int occ_npt = 0;
+  ok = ok && t->npt_smem <= 160 * 1024;
+  if (ok && t->npt_smem > 48 * 1024)
+    for (const void *fn : fns) ok = ok && raise_dynamic_lds(fn, t->npt_smem) == hipSuccess;
+  ok = ok && hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_npt, fns[0], WAVE * NW, t->npt_smem) == hipSuccess;
+  if (!ok) {
+    (void)hipGetLastError();
+    return d->force_block_path == 2 ? fail("node-per-lane kernel: device setup failed (LDS)") : 0;
+  }
+  t->is_npt = true;
+  t->npt_waves_per_cu = std::max(1, std::min(occ_npt, 4));   // problems (workgroups) per CU
+  return 0;
+}
+
+}  // namespace gik
+
+static int create_impl(const gik_template_desc *d, const gik_anchored_desc *ad, gik_template **out) {
+  using namespace gik;
+  if (!d || !out) return fail("null argument");
+  if (validate_desc(d, ad)) return -1;
+  std::unique_ptr<gik_template, void (*)(gik_template *)> t(new gik_template(), gik_template_destroy);   // (every error return releases it)
+  read_params(t.get(), d);
+  t->anchored = ad != nullptr;
+  // per-node slot lists, in (neighbour, kind) order == the order the reference's edge loop
+  // (row-major upper-triangle index pairs) accumulates into each row
+  SlotLists ents(d->N);
+  for (int i = 0; i < d->n_terms; ++i) {
+    const int a = d->term_i[i], b = d->term_j[i], kind = d->term_kind[i];
+    if (a < 0 || b < 0 || a >= d->N || b >= d->N || a == b) return fail("bad term indices");
+    if (kind < GIK_TERM_EQ || kind > GIK_TERM_UPPER) return fail("bad term kind");
+    ents[a].push_back({b, kind, i, a < b ? 1 : 0});
+    ents[b].push_back({a, kind, i, b < a ? 1 : 0});
+  }
+  sort_slot_lists(ents);
+  int maxdeg = 0;
+  for (const auto &e : ents) maxdeg = std::max(maxdeg, (int)e.size());
+  // the path: one unknown per lane with the smallest compiled slot count that holds the busiest node, else a workgroup per problem; there
+  // the node-per-lane kernel for 3-D graphs beyond one wavefront, trust-region solver, theta = 1 (force_block_path: 1 = never, 2 = always)
+  const bool big = d->N > BLOCK_MAXN;
+  const WaveRow *row = nullptr;
+  if (d->N * d->k <= WAVE && d->N <= 32 && !d->force_block_path) row = find_row(d->k, ad ? ANCHORED : COLUMN, maxdeg);
+  t->is_block = !row;      // (also: a node busier than any wave variant)
+  if (t->is_block && ad) return fail("anchored templates need N * k <= 64 free unknowns and at most 20 terms per node");
+  const bool npt_wanted = t->is_block && d->k == 3 && d->solver == GIK_SOLVER_TRUST_REGIONS && d->theta == 1.0 && !ad &&
+                          (d->force_block_path == 2 || (d->force_block_path == 0 && d->N * d->k > WAVE && !t->no_npt));
+  const bool npt_two_waves = big || !(t->dbg & 2048);      // 2048: one wavefront per problem, two nodes per lane
+  const int npt_NW = big ? 4 : (npt_two_waves ? 2 : 1);    // wavefronts per problem ("two_waves": one node per lane)
+  CliqueRows clq;
+  BlockHost bh;      // (the workgroup tables stay next to the node-per-lane ones: ConjugateGradient, known answers)
+  NptHost npt;
+  if (t->is_block) {
+    clq = clique_rows(d, t->dbg, big ? 256 : BLOCK_MAXN);      // rows of the host-side tables (the workgroup kernels' are 128)
+    if (!big) bh = block_tables(d->N, d->n_terms, clq);
+    if (npt_wanted) npt = npt_tables(d, clq, npt_two_waves, npt_NW, big ? 4 * WAVE : NPT_MAXN);
+  } else {
+    bh.meta = wave_slot_table(d, ents, row->slots);
+  }
+  t->SL = bh.SL;
+  t->maxdeg = t->is_block ? bh.SL : row->slots;
+  const int Tc = (int)clq.nc_term.size(), n_pairs = (int)bh.clq_pair_term.size();
+  const size_t block_lds = !t->is_block ? 0 : d->k == 3 ? BlockCtx<3>::lds_bytes(Tc, bh.SL, n_pairs, clq.n_clq) : BlockCtx<2>::lds_bytes(Tc, bh.SL);
+  int occ = 0;
+  if (resolve_kernels(t.get(), d, row, block_lds) || device_setup(t.get(), d, bh.meta, occ)) return -1;
+  if (ad && upload_anchored(t.get(), ad)) return -1;
+  if (t->is_block) {
+    bool ok = true;
+    t->bt.nc_term = upload(t.get(), clq.nc_term.data(), clq.nc_term.size(), ok);
+    t->bt.clq_term = upload(t.get(), bh.clq_term.data(), bh.clq_term.size(), ok);
+    t->bt.clq_pair_term = upload(t.get(), bh.clq_pair_term.data(), bh.clq_pair_term.size(), ok);
+    t->bt.clq_pid_t = upload(t.get(), bh.clq_pid.data(), bh.clq_pid.size(), ok);
+    t->bt.n_pairs = n_pairs;
+    t->bt.node_of_row = upload(t.get(), clq.node_of_row.data(), clq.node_of_row.size(), ok);
+    t->bt.wave_sl = upload(t.get(), bh.wave_sl.data(), bh.wave_sl.size(), ok);
+    t->bt.Tc = Tc;
+    t->bt.n_clq = clq.n_clq;
+    t->bt.clq_euclid = (clq.n_clq && !(t->dbg & 256) && d->clique_closed_form != GIK_CLIQUE_DENSE) ? 1 : 0;   // 256: always the dense D w product
+    t->clique_mode = !clq.n_clq ? GIK_CLIQUE_OFF : (t->bt.clq_euclid ? GIK_CLIQUE_AUTO : GIK_CLIQUE_DENSE);
+    if (!ok) return fail("device upload of the workgroup-path tables failed");
+  }
+  if (d->force_block_path == 2 && !npt.ok)
+    return fail("node-per-lane kernel: k = 3, TrustRegions, theta = 1, at most 256 terms outside the rigid clique, at most 16 per lane");
+  if (npt.ok && setup_npt(t.get(), d, npt, npt_NW)) return -1;
+  if (big && !t->is_npt)
+    return fail("graphs of more than 128 nodes need the node-per-lane kernel: at most 256 terms outside the rigid clique "
+                "(16 per node), at most 127 nodes that carry such terms");
+  if ((t->dbg & 32) && t->is_npt)
+    fprintf(stderr, "  node-per-lane kernel: %d wavefront(s) per problem, TL=%d, %d slot terms (sync %d), %d direction rows, gather lists %d + %d, "
+            "clique rows from %d, lds=%zu B, %d problems per CU\n",
+            t->npt_variant->NW, t->nt.TL, t->nt.n_terms, t->nt.term_sync, t->nt.n_wrows, t->nt.DEG0, t->nt.DEG1, t->nt.cbase,
+            t->npt_smem, t->npt_waves_per_cu);
+  if (t->dbg & 32)
+      fprintf(stderr, "gik_template_create: N=%d k=%d T=%d %s maxdeg=%d lds=%zu B occupancy=%d per CU, %d CUs; "
+              "clique %d, slot terms %d, slots %d\n",
+              t->N, t->K, t->T, t->is_block ? "block" : "wave", t->is_block ? 0 : t->maxdeg,
+              t->smem_bytes, occ, t->n_cu, clq.n_clq, t->is_block ? Tc : t->T, t->SL);
+  if ((t->dbg & 32) && t->is_block) {
+    fprintf(stderr, "  slot loop bounds per wavefront {equalities, all}:");
+    for (int w = 0; w < BLOCK_WAVES; ++w) fprintf(stderr, " {%d, %d}", bh.wave_sl[2 * w], bh.wave_sl[2 * w + 1]);
+    fprintf(stderr, "\n");
+  }
+  *out = t.release();
+  return 0;
+}
+
 extern "C" {
 
 const char *gik_last_error(void) { return gik::g_err.c_str(); }
@@ -301,8 +966,6 @@ void gik_default_cg_params(gik_template_desc *d) {
   d->maxiter = 100000;          // :55  (10e4)
 }
 
-static int create_impl(const gik_template_desc *d, const gik_anchored_desc *ad, gik_template **out);
-
 int gik_template_create(const gik_template_desc *d, gik_template **out) {
   return create_impl(d, nullptr, out);
 }
@@ -310,656 +973,6 @@ int gik_template_create(const gik_template_desc *d, gik_template **out) {
 int gik_template_create_anchored(const gik_template_desc *d, const gik_anchored_desc *ad, gik_template **out) {
   if (!ad) return gik::fail("null argument");
   return create_impl(d, ad, out);
-}
-
-static int create_impl(const gik_template_desc *d, const gik_anchored_desc *ad, gik_template **out) {
-  using namespace gik;
-  if (!d || !out) return fail("null argument");
-  if (ad) {
-    if (d->k != 3 || d->solver != GIK_SOLVER_TRUST_REGIONS || d->theta != 1.0 || d->force_block_path)
-      return fail("anchored templates: k = 3, TrustRegions, theta = 1, wavefront path");
-    if (ad->n_anchor < 1 || ad->n_anchor > ANCH_MAXA || ad->n_goal_anchor < 0 || ad->n_goal_anchor > ad->n_anchor)
-      return fail("anchored templates: 1 <= n_anchor <= 16, goal anchors are the last rows");
-    if (ad->n_obs > ANCH_MAXOBS) return fail("anchored templates: at most 128 obstacles");
-    if (ad->n_obs < 0 || ad->n_pin < 0 || d->N > 63 || !ad->term_target || !ad->free_full_index ||
-        !ad->anchor_full_index || !ad->anchor_pos)
-      return fail("anchored templates: bad descriptor");
-  }
-  if (d->abi_version != GIK_ABI_VERSION) return fail("ABI version mismatch");
-  if (d->k != 2 && d->k != 3) return fail("k must be 2 or 3");
-  if (d->solver != GIK_SOLVER_TRUST_REGIONS && d->solver != GIK_SOLVER_CONJUGATE_GRADIENT)
-    return fail("solver must be GIK_SOLVER_TRUST_REGIONS or GIK_SOLVER_CONJUGATE_GRADIENT");
-  if (d->cg_beta_type < 0 || d->cg_beta_type > 3) return fail("cg_beta_type must be 0..3");
-  if (d->clique_closed_form < GIK_CLIQUE_AUTO || d->clique_closed_form > GIK_CLIQUE_DENSE)
-    return fail("clique_closed_form must be GIK_CLIQUE_AUTO, _OFF or _DENSE");
-  if (d->hessian_form != GIK_HESS_COLUMN && d->hessian_form != GIK_HESS_PER_EDGE && d->hessian_form != GIK_HESS_AUTO)
-    return fail("hessian_form must be GIK_HESS_AUTO, GIK_HESS_COLUMN or GIK_HESS_PER_EDGE");
-
-  bool is_block = d->N * d->k > WAVE || d->N > 32 || d->force_block_path != 0;
-  // 255 = what the node-per-lane kernel's 8-bit row fields take (four wavefronts per problem beyond 128 nodes);
-  // every other kernel stops at 128 (checked below, where the kernel is chosen)
-  if (d->N < 2 || d->N > 255) return fail("N must be in [2, 255]");
-  const bool big = d->N > BLOCK_MAXN;
-  if (big && (ad || d->k != 3 || d->solver != GIK_SOLVER_TRUST_REGIONS || d->theta != 1.0 || d->force_block_path == 1))
-    return fail("graphs of more than 128 nodes run on the node-per-lane kernel only: k = 3, TrustRegions, theta = 1, "
-                "not anchored, force_block_path != 1");
-  if (d->n_terms < 1 || d->n_terms > 65535) return fail("n_terms out of range");
-  const int N = d->N, T = d->n_terms;
-  int dbg_eff = d->debug_flags;   // developer override, read once here (never inside a batch call)
-  if (const char *e = getenv("GIK_DBG")) dbg_eff = atoi(e);
-  // per-node slot lists, in (neighbour, kind) order == the order the reference's edge loop
-  // (row-major upper-triangle index pairs) accumulates into each row
-  std::vector<std::vector<uint32_t>> slots(N);
-  struct Ent { int j, kind, term, owner; };
-  std::vector<std::vector<Ent>> ents(N);
-  for (int t = 0; t < T; ++t) {
-    const int i = d->term_i[t], j = d->term_j[t], kind = d->term_kind[t];
-    if (i < 0 || j < 0 || i >= N || j >= N || i == j) return fail("bad term indices");
-    if (kind < GIK_TERM_EQ || kind > GIK_TERM_UPPER) return fail("bad term kind");
-    ents[i].push_back({j, kind, t, i < j ? 1 : 0});
-    ents[j].push_back({i, kind, t, j < i ? 1 : 0});
-  }
-  int maxdeg = 0;
-  for (int i = 0; i < N; ++i) {
-    std::stable_sort(ents[i].begin(), ents[i].end(), [](const Ent &a, const Ent &b) {
-      return a.j != b.j ? a.j < b.j : a.kind < b.kind;
-    });
-    maxdeg = std::max(maxdeg, (int)ents[i].size());
-  }
-  const Variant *var = nullptr;
-  int MD = 0, SL = 0, SLE = 0;
-  std::vector<uint32_t> meta;
-  if (!is_block) {   // smallest compiled slot count that holds the busiest node
-    for (const Variant &v : kVariants)
-      if (v.K == d->k && v.maxdeg >= maxdeg && (!var || v.maxdeg < var->maxdeg) && (ad ? v.solve_anch != nullptr : v.solve != nullptr))
-        var = &v;
-    if (!var) is_block = true;   // a node busier than any wave variant: workgroup-per-problem path
-  }
-  if (is_block && ad) return fail("anchored templates need N * k <= 64 free unknowns and at most 20 terms per node");
-  // workgroup-per-problem tables (BlockTabs)
-  int n_clq = 0, Tc = T;
-  const int ROWCAP = big ? 256 : BLOCK_MAXN;       // rows of the host-side tables (the workgroup kernels' are 128)
-  std::vector<int> nc_term, clq_term, clq_pair_term, node_of_row(ROWCAP, -1), wave_sl(2 * BLOCK_WAVES, 0);
-  std::vector<unsigned short> clq_pid;   // [M][512] compact pair id per (thread, partner), 0xffff = none
-  // node-per-lane path: 3-D graphs beyond one wavefront, trust-region solver, theta = 1.
-  // force_block_path: 0 = automatic, 1 = the workgroup kernels, 2 = the node-per-lane kernel
-  if (d->force_block_path == 2) is_block = true;
-  const bool npt_wanted = is_block && d->k == 3 && d->solver == GIK_SOLVER_TRUST_REGIONS && d->theta == 1.0 && !ad &&
-                          (d->force_block_path == 2 ||
-                           (d->force_block_path == 0 && d->N * d->k > WAVE && !getenv("GIK_NO_NPT")));   // (developer A/B switch, read once)
-  bool npt_ok = false;
-  const bool npt_two_waves = big || !(dbg_eff & 2048);      // 2048: one wavefront per problem, two nodes per lane
-  const int npt_NW = big ? 4 : (npt_two_waves ? 2 : 1);     // wavefronts per problem ("two_waves": one node per lane)
-  const int NPT_ROWS = big ? 4 * WAVE : NPT_MAXN;
-  int npt_TL = 1, npt_DEG0 = 0, npt_DEG1 = 0, npt_n_wrows = 0, npt_cbase = 0, npt_n_rows = 0, npt_n_terms = 0, npt_term_sync = 0;
-  std::vector<int> npt_node_of_row, npt_term_tgt, npt_pair_term;
-  std::vector<uint32_t> npt_term_rec;
-  std::vector<unsigned short> npt_gather;
-  std::vector<unsigned char> npt_wslot, npt_prow;
-  int npt_n_helped = 0;
-  if (is_block) {
-    // A rigid clique -- a set of nodes every pair of which is tied by an equality term (the
-    // anchors of a scene with many obstacles) -- is taken out of the slot tables and handled in
-    // closed form (gik_block.hip.h).  Greedy by equality degree; rows 0..n_clq-1 of the LDS
-    // arrays are the clique's nodes in ascending order, the other nodes follow.
-    std::vector<int> eqterm((size_t)N * N, -1), deg(N, 0), order(N), row_of(N);
-    for (int t = 0; t < T; ++t) {
-      const int i = d->term_i[t], j = d->term_j[t];
-      if (d->term_kind[t] == GIK_TERM_EQ && eqterm[(size_t)i * N + j] < 0) {
-        eqterm[(size_t)i * N + j] = eqterm[(size_t)j * N + i] = t;
-        ++deg[i];
-        ++deg[j];
-      }
-    }
-    std::vector<char> in_clq(N, 0);
-    const int clique_min = (dbg_eff & 64) ? 4 : 16;
-    if (d->k == 3 && !(dbg_eff & 128) && d->clique_closed_form != GIK_CLIQUE_OFF) {
-      for (int i = 0; i < N; ++i) order[i] = i;
-      std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return deg[a] > deg[b]; });
-      std::vector<int> A;
-      for (int v : order) {
-        bool all = true;
-        for (int a : A) all = all && eqterm[(size_t)v * N + a] >= 0;
-        if (all) A.push_back(v);
-      }
-      if ((int)A.size() >= clique_min) {
-        n_clq = (int)A.size();
-        for (int a : A) in_clq[a] = 1;
-      }
-    }
-    // with a clique the other nodes take the LAST rows (128 - F ...): their threads, the only
-    // ones with more than a slot or two, then sit in wavefronts that have no clique work
-    int r = 0;
-    for (int pass = 0; pass < 2; ++pass) {
-      if (pass == 1 && n_clq) r = ROWCAP - (N - n_clq);
-      for (int i = 0; i < N; ++i)
-        if ((in_clq[i] != 0) == (pass == 0)) {
-          row_of[i] = r;
-          node_of_row[r++] = i;
-        }
-    }
-    // slot entries in row numbering, clique pairs left out; `term` = index in the LDS target table
-    ents.assign(ROWCAP, {});
-    for (int t = 0; t < T; ++t) {
-      const int i = d->term_i[t], j = d->term_j[t], kind = d->term_kind[t];
-      if (n_clq && kind == GIK_TERM_EQ && in_clq[i] && in_clq[j] && eqterm[(size_t)i * N + j] == t) continue;
-      const int ri = row_of[i], rj = row_of[j], tc = (int)nc_term.size();
-      nc_term.push_back(t);
-      ents[ri].push_back({rj, kind, tc, ri < rj ? 1 : 0});
-      ents[rj].push_back({ri, kind, tc, rj < ri ? 1 : 0});
-    }
-    Tc = (int)nc_term.size();
-    for (auto &e : ents)
-      std::stable_sort(e.begin(), e.end(), [](const Ent &a, const Ent &b) {
-        return a.j != b.j ? a.j < b.j : a.kind < b.kind;
-      });
-    if (!big) {      // tables of the 512-thread workgroup kernels (128 rows)
-    const int M = (n_clq + 3) / 4;
-    clq_term.assign((size_t)std::max(M, 1) * BLOCK_NT, -1);
-    for (int tid = 0; tid < BLOCK_NT; ++tid) {
-      const int row = tid >> 2, part = tid & 3;
-      for (int m = 0; m < M && row < n_clq; ++m) {
-        const int j = 4 * m + part;
-        if (j < n_clq && j != row)
-          clq_term[(size_t)m * BLOCK_NT + tid] = eqterm[(size_t)node_of_row[row] * N + node_of_row[j]];
-      }
-    }
-    // each clique pair once (its target is staged in LDS per problem) + the pair id of every
-    // (thread, partner): ids fit 16 bits (at most 128 * 127 / 2 pairs)
-    {
-      std::vector<int> pid_of_term((size_t)T, -1);
-      clq_pid.assign((size_t)std::max(M, 1) * BLOCK_NT, (unsigned short)0xffff);
-      for (size_t q = 0; q < clq_term.size(); ++q) {
-        const int term = clq_term[q];
-        if (term < 0) continue;
-        if (pid_of_term[term] < 0) {
-          pid_of_term[term] = (int)clq_pair_term.size();
-          clq_pair_term.push_back(term);
-        }
-        clq_pid[q] = (unsigned short)pid_of_term[term];
-      }
-    }
-    // four threads per node; a node's equality terms are dealt to them in turn, then its hinge
-    // terms continuing the rotation, so that both kinds spread evenly (the padded slot count of a
-    // wavefront is the largest equality count plus the largest hinge count among its threads:
-    // 3 + 2 -> 2 + 1 for the free nodes of the table scene).  Within a thread the equality terms
-    // come first (slots [0, SLE_w): no kind decoding in the kernels) and the hinge terms last
-    // (slots [SLE_w, SL_w)), with the bounds of the thread's wavefront w; unused slots are inert
-    // padding (own node, kind 0, not owner)
-    std::vector<std::vector<Ent>> eqs(BLOCK_NT), hinges(BLOCK_NT);
-    for (int node = 0; node < BLOCK_MAXN; ++node) {
-      int turn = 0;
-      for (int pass = 0; pass < 2; ++pass)
-        for (const Ent &en : ents[node])
-          if ((en.kind == GIK_TERM_EQ) == (pass == 0))
-            (pass == 0 ? eqs : hinges)[4 * node + (turn++ & 3)].push_back(en);
-    }
-    for (int tid = 0; tid < BLOCK_NT; ++tid) {
-      const int w = tid / WAVE;
-      wave_sl[2 * w] = std::max(wave_sl[2 * w], (int)eqs[tid].size());
-      wave_sl[2 * w + 1] = std::max(wave_sl[2 * w + 1], (int)hinges[tid].size());
-    }
-    // A wavefront with few slots runs them as ONE kind-decoding loop over each thread's equality
-    // terms followed by its hinge terms ({0, T_w}: T_w = most terms of any of its threads) when that
-    // is shorter than the padded split loops (table scene: 1 + 1 -> 1 for the base / goal nodes,
-    // 3 + 1 -> 3 for the free nodes; an iteration is two dependent LDS round trips).
-    std::vector<char> merged(BLOCK_WAVES, 0);
-    for (int w = 0; w < BLOCK_WAVES; ++w) {
-      int tot = 0;
-      for (int tid = w * WAVE; tid < (w + 1) * WAVE; ++tid)
-        tot = std::max(tot, (int)(eqs[tid].size() + hinges[tid].size()));
-      if (tot <= 8 && tot < wave_sl[2 * w] + wave_sl[2 * w + 1]) {
-        merged[w] = 1;
-        wave_sl[2 * w] = 0;
-        wave_sl[2 * w + 1] = tot;
-      } else {
-        wave_sl[2 * w + 1] += wave_sl[2 * w];   // {SLE_w, SL_w}
-      }
-      SLE = std::max(SLE, wave_sl[2 * w]);
-      SL = std::max(SL, wave_sl[2 * w + 1]);
-    }
-    meta.assign((size_t)std::max(SL, 1) * BLOCK_NT, 0);
-    for (int tid = 0; tid < BLOCK_NT; ++tid) {
-      const int node = tid >> 2, w = tid / WAVE, sle = merged[w] ? (int)eqs[tid].size() : wave_sl[2 * w];
-      for (int s = 0; s < SL; ++s) {
-        uint32_t m = meta_pack(node_of_row[node] >= 0 ? node : 0, 0, 0, 0);
-        const std::vector<Ent> &src = s < sle ? eqs[tid] : hinges[tid];
-        const int e = s < sle ? s : s - sle;
-        if (e < (int)src.size()) m = meta_pack(src[e].j, src[e].term, src[e].kind, src[e].owner);
-        meta[(size_t)s * BLOCK_NT + tid] = m;
-      }
-    }
-
-    }
-    // ---- node-per-lane tables (NptTabs, gik_npt.hip.h) ----
-    // Two layouts.  Two wavefronts per problem, one node per lane (default): the nodes outside the
-    // clique take the first rows, then the clique's nodes, those that carry slot terms first -- every
-    // end node of a slot term then sits in wavefront 0, which evaluates the terms, and the
-    // direction / term tables need no barrier of their own.  One wavefront, two nodes per lane
-    // (debug_flags 2048): the clique's nodes take rows 0..n_clq-1, the others follow; nodes that carry
-    // slot terms go to EVEN rows where possible, so that a lane's second node has few or none (its
-    // gather list is as long as the busiest second node's).
-    if (npt_wanted) {
-      const int NSn = npt_two_waves ? 1 : 2, NTn = npt_NW * WAVE;
-      std::vector<int> sdeg(N, 0);
-      for (int t : nc_term) {
-        ++sdeg[d->term_i[t]];
-        ++sdeg[d->term_j[t]];
-      }
-      std::vector<int> cl_busy, cl_idle, others;
-      for (int i = 0; i < N; ++i) {
-        if (in_clq[i]) (sdeg[i] ? cl_busy : cl_idle).push_back(i);
-        else others.push_back(i);
-      }
-      auto by_deg = [&](int a, int b) { return sdeg[a] > sdeg[b]; };
-      std::stable_sort(cl_busy.begin(), cl_busy.end(), by_deg);
-      std::stable_sort(others.begin(), others.end(), by_deg);
-      // nrow[v]: row of node v in the point table; npt_node_of_row[t]: node held by thread slot t
-      npt_node_of_row.assign(NPT_ROWS, -1);
-      npt_prow.assign(NPT_ROWS, 0);
-      std::vector<int> nrow(N, -1), nslot(N, -1);
-      int n_rows = 0;
-      npt_n_helped = 0;
-      if (npt_two_waves) {
-        npt_cbase = (int)others.size();
-        int r = 0;
-        for (int v : others) nrow[v] = r++;
-        for (int v : cl_busy) nrow[v] = r++;
-        for (int v : cl_idle) nrow[v] = r++;
-        n_rows = r;
-        // thread slots: the nodes that carry slot terms on the even lanes 0, 2, ... of wavefront 0, each with a
-        // clique node WITHOUT slot terms next to it (its helper in the gather); everything else behind
-        std::vector<int> busy(others.begin(), others.end());
-        busy.insert(busy.end(), cl_busy.begin(), cl_busy.end());
-        busy.erase(std::remove_if(busy.begin(), busy.end(), [&](int v) { return sdeg[v] == 0; }), busy.end());
-        std::stable_sort(busy.begin(), busy.end(), by_deg);
-        std::vector<char> placed(N, 0);
-        int slot = 0;
-        size_t ih = 0;
-        const bool can_help = 2 * busy.size() <= (size_t)WAVE && cl_idle.size() >= busy.size();
-        for (int v : busy) {
-          npt_node_of_row[slot] = v;
-          nslot[v] = slot++;
-          placed[v] = 1;
-          if (can_help) {
-            const int h = cl_idle[ih++];
-            npt_node_of_row[slot] = h;
-            nslot[h] = slot++;
-            placed[h] = 1;
-          }
-        }
-        npt_n_helped = can_help ? (int)busy.size() : 0;
-        for (int pass = 0; pass < 3; ++pass)
-          for (int v : (pass == 0 ? others : (pass == 1 ? cl_busy : cl_idle)))
-            if (!placed[v]) {
-              npt_node_of_row[slot] = v;
-              nslot[v] = slot++;
-              placed[v] = 1;
-            }
-      } else {
-        npt_cbase = 0;
-        size_t ib = 0, ii = 0;
-        for (int r = 0; r < n_clq; ++r) {
-          const bool want_busy = (r & 1) == 0;
-          int v;
-          if ((want_busy && ib < cl_busy.size()) || ii >= cl_idle.size()) v = cl_busy[ib++];
-          else v = cl_idle[ii++];
-          nrow[v] = r;
-        }
-        const int start = (n_clq + 1) & ~1;
-        const bool even_only = others.empty() || start + 2 * ((int)others.size() - 1) < NPT_ROWS;
-        n_rows = n_clq;
-        for (size_t q = 0; q < others.size(); ++q) {
-          const int r = even_only ? start + 2 * (int)q : n_clq + (int)q;
-          nrow[others[q]] = r;
-          n_rows = r + 1;
-        }
-        for (int v = 0; v < N; ++v) {      // thread slot = row
-          npt_node_of_row[nrow[v]] = v;
-          nslot[v] = nrow[v];
-        }
-      }
-      for (int v = 0; v < N; ++v) npt_prow[nslot[v]] = (unsigned char)nrow[v];
-      npt_n_rows = (n_rows + 1) & ~1;
-      // compact direction table: one row per node that carries slot terms
-      npt_wslot.assign(NPT_ROWS, 255);
-      int n_wrows = 0;
-      npt_term_sync = 0;
-      std::vector<int> wslot_of_node(N, 255);
-      for (int t = 0; t < NPT_ROWS; ++t)
-        if (npt_node_of_row[t] >= 0 && sdeg[npt_node_of_row[t]]) {
-          wslot_of_node[npt_node_of_row[t]] = n_wrows;
-          npt_wslot[t] = (unsigned char)n_wrows++;
-          if (npt_two_waves && t >= WAVE) npt_term_sync = 1;
-        }
-      const int Tn = (int)nc_term.size();
-      const int TLn = Tn <= 64 ? 1 : 4;
-      npt_ok = Tn <= 64 * 4 && n_wrows <= 127;
-      bool npt_lists_fit = true;
-      if (npt_ok) {
-        npt_TL = TLn;
-        npt_term_rec.assign((size_t)TLn * WAVE, 0u);
-        npt_term_tgt.assign((size_t)TLn * WAVE, -1);
-        for (size_t q = 0; q < npt_term_rec.size(); ++q)   // padding: rows 0 / 0, kind 0, the zero direction row
-          npt_term_rec[q] = ((uint32_t)n_wrows << 18) | ((uint32_t)n_wrows << 25);
-        struct GEnt { int other, kind, slot, neg; };
-        std::vector<std::vector<GEnt>> glist(NPT_ROWS);
-        for (int q = 0; q < Tn; ++q) {
-          const int t = nc_term[q], i = d->term_i[t], j = d->term_j[t], kind = d->term_kind[t];
-          const int ri = nrow[i], rj = nrow[j];
-          npt_term_rec[q] = (uint32_t)ri | ((uint32_t)rj << 8) | ((uint32_t)kind << 16) |
-                            ((uint32_t)wslot_of_node[i] << 18) | ((uint32_t)wslot_of_node[j] << 25);
-          npt_term_tgt[q] = t;
-          // term slot q = u * 64 + lane: the order of nc_term (= the reference's edge order)
-          glist[nslot[i]].push_back({j, kind, q, 0});
-          glist[nslot[j]].push_back({i, kind, q, 1});
-        }
-        int deg[2] = {0, 0};
-        for (int r = 0; r < NPT_ROWS; ++r)
-          std::stable_sort(glist[r].begin(), glist[r].end(), [](const GEnt &a, const GEnt &b) {
-            return a.other != b.other ? a.other < b.other : a.kind < b.kind;
-          });
-        for (int i = 0; i < npt_n_helped; ++i) {      // the second half of a busy node's list moves to its helper
-          std::vector<GEnt> &own = glist[2 * i], &hlp = glist[2 * i + 1];
-          const size_t keep = (own.size() + 1) / 2;
-          hlp.assign(own.begin() + keep, own.end());
-          own.resize(keep);
-        }
-        for (int r = 0; r < NPT_ROWS; ++r) {
-          const int sl = NSn == 1 ? 0 : (r & 1);
-          deg[sl] = std::max(deg[sl], (int)glist[r].size());
-        }
-        npt_DEG0 = deg[0];
-        npt_DEG1 = deg[1];
-        npt_lists_fit = deg[0] + deg[1] <= 16;      // NptCtx::NG packed words
-        const unsigned short pad = (unsigned short)(2 * Tn);
-        npt_gather.assign((size_t)std::max(1, deg[0] + deg[1]) * NTn, pad);
-        for (int r = 0; r < NPT_ROWS; ++r) {
-          const int thr = r / NSn, sl = r % NSn;
-          for (size_t e = 0; e < glist[r].size(); ++e)
-            npt_gather[(size_t)(sl ? deg[0] + (int)e : (int)e) * NTn + thr] =
-                (unsigned short)((glist[r][e].slot << 1) | glist[r][e].neg);
-        }
-        npt_pair_term.clear();
-        std::vector<int> node_at_row(NPT_ROWS, 0);
-        for (int v = 0; v < N; ++v) node_at_row[nrow[v]] = v;
-        for (int a = 0; a < n_clq; ++a)
-          for (int b = a + 1; b < n_clq; ++b)
-            npt_pair_term.push_back(eqterm[(size_t)node_at_row[npt_cbase + a] * N + node_at_row[npt_cbase + b]]);
-        npt_n_wrows = n_wrows;
-        npt_n_terms = Tn;
-      }
-      npt_ok = npt_ok && npt_lists_fit;
-    }
-  } else {
-  MD = var->maxdeg;
-  meta.assign((size_t)MD * WAVE, 0);
-  for (int lane = 0; lane < WAVE; ++lane) {
-    const bool active = lane < N * d->k;
-    const int node = active ? lane / d->k : 0;
-    const int comp = active ? lane % d->k : 0;
-    for (int s = 0; s < MD; ++s) {
-      // padding slot: this lane's own row (idle lanes: the all-zero dump row), kind none
-      uint32_t m = meta_pack(active ? node : TILE_ROWS - 1, 0, 0, 0);
-      if (active && s < (int)ents[node].size()) {
-        const Ent &e = ents[node][s];
-        m = meta_pack(e.j, e.term, e.kind, (comp == 0 && e.owner) ? 1 : 0);
-      }
-      meta[(size_t)s * WAVE + lane] = m;
-    }
-  }
-  }
-  if (meta.empty()) meta.assign(1, 0u);      // (graphs beyond 128 nodes: no slot table of the 512-thread kernels)
-  gik_template *t = new gik_template();
-  t->is_block = is_block;
-  t->SL = SL;
-  t->SLE = SLE;
-  t->N = N;
-  t->K = d->k;
-  t->T = T;
-  t->maxdeg = is_block ? SL : MD;
-  t->variant = var;
-  // The product form concerns the one-unknown-per-lane kernel only (every other kernel forms s = y . w per edge
-  // anyway).  There the per-edge form exists for k = 3, TrustRegions, free-free graphs and is what GIK_HESS_AUTO
-  // selects; an explicit GIK_HESS_PER_EDGE without such a kernel is refused.
-  if (!is_block && d->k == 3 && d->hessian_form != GIK_HESS_COLUMN) {
-    const bool have = !ad && d->solver == GIK_SOLVER_TRUST_REGIONS && var->solve_strict && var->solve_strict_theta;
-    if (!have && d->hessian_form == GIK_HESS_PER_EDGE) {
-      delete t;
-      return fail("hessian_form = GIK_HESS_PER_EDGE: wavefront kernel of 3-D free-free graphs, TrustRegions only");
-    }
-    t->hess_per_edge = have;
-  }
-  t->p.mingradnorm = d->mingradnorm;
-  t->p.theta = d->theta;
-  t->p.kappa = d->kappa;
-  t->p.rho_prime = d->rho_prime;
-  t->p.rho_regularization = d->rho_regularization;
-  t->p.maxiter = d->maxiter;
-  t->p.maxinner = d->maxinner;
-  t->p.mininner = d->mininner;
-  t->p.planar_proj_exact = d->planar_proj_exact;
-  t->solver = d->solver;
-  t->cg.mingradnorm = d->mingradnorm;
-  t->cg.minstepsize = d->cg_minstepsize;
-  t->cg.orth_value = d->cg_orth_value;
-  t->cg.maxiter = d->maxiter;
-  t->cg.beta_type = d->cg_beta_type;
-  t->cg.planar_proj_exact = d->planar_proj_exact;
-  t->dbg = dbg_eff;
-  t->wpc_override = std::max(0, d->waves_per_cu);
-  // workgroup kernel, table scene, 4096 goals (round 3): slice 96 / 160 / 256 -> 1430 / 1430 / 1409 solves/s and
-  // 755 / 586 / 368 MB of HBM traffic per launch (every resumed slice re-reads the problem's 45 KB of
-  // targets; 207 MB are the algorithmic bytes).  Without slicing: ~15 % slower (round 2: 795 vs 929).
-  t->slice_its = d->slice_outer_its < 0 ? 256 : d->slice_outer_its;
-  // node-per-lane kernel, table scene, 4096 goals (round 4): slice 0 / 48 / 96 / 256 / 600 -> 1689 / 1896 / 1894 / 1861 /
-  // 1774 solves/s (two problems per CU: 512 slots, a third of the requeues of the workgroup kernel)
-  // HBM traffic per launch (PMC): 603 MB at 128 = 2.9 x the algorithmic 207 MB (every resume re-reads the problem's 45 KB of
-  // clique targets); 192 is the compromise
-  t->npt_slice_its = d->slice_outer_its < 0 ? 192 : d->slice_outer_its;
-  // developer overrides, read once here (never inside a batch call)
-  if (const char *e = getenv("GIK_WAVES_PER_CU")) t->wpc_override = std::max(1, atoi(e));
-  // wavefront kernel: 256 ... 32 iterations per slice give the same time (NOTEBOOK 8.3); the longest of
-  // them moves the fewest problems through HBM (KUKA 65536: 118 k hand-overs of ~1.5 KB instead of 562 k at 64)
-  t->wave_slice_its = d->slice_outer_its < 0 ? 256 : d->slice_outer_its;
-  t->wave_slice_auto = d->slice_outer_its < 0 && !getenv("GIK_SLICE");   // (an explicit length is taken literally)
-  if (const char *e = getenv("GIK_SLICE")) t->slice_its = t->npt_slice_its = t->wave_slice_its = std::max(0, atoi(e));
-  if (const char *e = getenv("GIK_SLICE_CYCLES")) t->wave_slice_cycles = std::max(0, atoi(e));
-  t->d_slot_meta = nullptr;
-  t->d_counters = nullptr;
-  t->next_counter = 0;
-  t->counter_slot.resize(kCounterRing);
-  t->counter_ring = kCounterRing;
-  if (const char *e = getenv("GIK_COUNTER_RING")) t->counter_ring = std::min(kCounterRing, std::max(1, atoi(e)));
-  if (const char *e = getenv("GIK_SLICE_POOL")) t->slice_pool = std::min(gik_template::kSlicePool, std::max(1, atoi(e)));
-  t->has_pipe = false;
-  t->smem_bytes = is_block ? (d->k == 3 ? BlockCtx<3>::lds_bytes(Tc, SL, (int)clq_pair_term.size(), n_clq)
-                                        : BlockCtx<2>::lds_bytes(Tc, SL))
-                           : (ad ? var->lds_anch(T) : (t->hess_per_edge ? var->lds_strict(T) : var->lds(T)));
-  if (is_block && t->smem_bytes > 160 * 1024) {
-    delete t;
-    return fail("graph too large for the LDS-resident block path");
-  }
-  const bool cg = d->solver == GIK_SOLVER_CONJUGATE_GRADIENT;
-  const void *solve_kernel =
-      is_block ? (cg ? (d->k == 3 ? (const void *)rcg_block_kernel<3> : (const void *)rcg_block_kernel<2>)
-                     : (d->k == 3 ? (const void *)rtr_block_kernel<3> : (const void *)rtr_block_kernel<2>))
-               : (const void *)(ad ? var->solve_anch : (cg ? var->solve_cg : (t->hess_per_edge ? (d->theta == 1.0 ? (var->solve_strict_mig ? var->solve_strict_mig : var->solve_strict) : var->solve_strict_theta) : var->solve)));      // (occupancy: of the build large batches run -- the small-batch build trades registers for latency, gik_rtr.hip.h SPLIT)
-  if (is_block && t->smem_bytes > 48 * 1024) {
-    // more than the default dynamic-LDS allowance: opt in for exactly what this template needs
-    const void *fns[2] = {solve_kernel, d->k == 3 ? (const void *)kat_block_kernel<3>
-                                                  : (const void *)kat_block_kernel<2>};
-    for (const void *fn : fns) {
-      if (raise_dynamic_lds(fn, t->smem_bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        const std::string msg =
-            "cannot reserve " + std::to_string(t->smem_bytes) + " bytes of LDS per workgroup";
-        delete t;
-        return fail(msg);
-      }
-    }
-  }
-  hipDeviceProp_t prop;
-  int occ = 0;
-  if (hipGetDevice(&t->device) != hipSuccess ||
-      hipGetDeviceProperties(&prop, t->device) != hipSuccess ||
-      hipMalloc((void **)&t->d_slot_meta, meta.size() * sizeof(uint32_t)) != hipSuccess ||
-      hipMalloc((void **)&t->d_counters, kCounterRing * sizeof(unsigned int)) != hipSuccess ||
-      hipMemcpy(t->d_slot_meta, meta.data(), meta.size() * sizeof(uint32_t),
-                hipMemcpyHostToDevice) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, solve_kernel, is_block ? BLOCK_NT : WAVE,
-                                                   t->smem_bytes) != hipSuccess) {
-    if (t->d_slot_meta) (void)hipFree(t->d_slot_meta);
-    if (t->d_counters) (void)hipFree(t->d_counters);
-    delete t;
-    return fail("HIP device setup failed (no GPU?)");
-  }
-  t->n_cu = prop.multiProcessorCount;
-  t->waves_per_cu = std::max(1, std::min(occ, 32));
-  if (!is_block && !ad && !cg && d->k == 2 && N <= QUAD_NODES && var->maxdeg == 6 && d->theta == 1.0 &&
-      !(d->debug_flags & 8192) && !getenv("GIK_NO_QUAD")) {
-    t->quad_solve = rtr_quad_kernel<6>;
-    t->quad_smem = QuadCtx<6>::lds_bytes();
-    int qocc = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&qocc, (const void *)t->quad_solve, WAVE, t->quad_smem) == hipSuccess)
-      t->quad_waves_per_cu = std::max(1, std::min(qocc, 32));
-    t->quad_min_batch = 12 * t->n_cu;
-    if (const char *e = getenv("GIK_QUAD_MIN_BATCH")) t->quad_min_batch = std::max(0, atoi(e));
-  }
-  if (ad) {
-    // ---- fixed-anchor data ----
-    bool ok = true;
-    std::vector<double> tab(4 * ANCH_MAXA, 0.0);
-    for (int r = 0; r < ad->n_anchor; ++r)
-      for (int c = 0; c < 3; ++c) tab[r * 4 + c] = ad->anchor_pos[r * 3 + c];
-    std::vector<uint32_t> pm((size_t)ANCH_PMAX * WAVE, 0u);
-    std::vector<double> pt((size_t)ANCH_PMAX * WAVE, 0.0);
-    std::vector<int> cnt(N, 0);
-    for (int q = 0; q < ad->n_pin; ++q) {
-      const int i = ad->pin_node[q], r = ad->pin_anchor[q], kind = ad->pin_kind[q];
-      if (i < 0 || i >= N || r < 0 || r >= ad->n_anchor || kind < GIK_TERM_EQ || kind > GIK_TERM_UPPER || cnt[i] >= ANCH_PMAX) {
-        ok = false;
-        break;
-      }
-      for (int c = 0; c < 3; ++c) {      // every lane of the node walks all of the node's pinned terms
-        pm[(size_t)cnt[i] * WAVE + i * 3 + c] = (uint32_t)r | ((uint32_t)kind << 8);
-        pt[(size_t)cnt[i] * WAVE + i * 3 + c] = ad->pin_target[q];
-      }
-      ++cnt[i];
-    }
-    unsigned long long mask = 0;
-    for (int i = 0; i < N && ad->obs_node_mask; ++i)
-      if (ad->obs_node_mask[i]) mask |= 1ull << i;
-    AnchArgs an;
-    an.anch_const = ok ? upload(t, tab.data(), tab.size(), ok) : nullptr;
-    an.pin_meta = upload(t, pm.data(), pm.size(), ok);
-    an.pin_tgt = upload(t, pt.data(), pt.size(), ok);
-    an.obs = ad->n_obs ? upload(t, ad->obs, (size_t)ad->n_obs * 4, ok) : nullptr;
-    an.anchor_goal = nullptr;
-    an.obs_mask = mask;
-    an.n_obs = ad->n_obs;
-    an.n_goal = ad->n_goal_anchor;
-    an.goal_row0 = ad->n_anchor - ad->n_goal_anchor;
-    t->an = an;
-    t->d_targets_const = const_cast<double *>(upload(t, ad->term_target, (size_t)T, ok));
-    t->d_free_full = const_cast<int *>(upload(t, ad->free_full_index, (size_t)N, ok));
-    t->d_anchor_full = const_cast<int *>(upload(t, ad->anchor_full_index, (size_t)ad->n_anchor, ok));
-    t->full_N = ad->full_N;
-    t->n_anchor = ad->n_anchor;
-    t->axis_length = ad->axis_length;
-    t->anchored = true;
-    if (hipEventCreate(&t->ev_solve0) != hipSuccess || hipEventCreate(&t->ev_solve1) != hipSuccess) ok = false;
-    if (!ok) {
-      gik_template_destroy(t);
-      return fail("anchored templates: bad pinned term (node / anchor / kind out of range, or more than 8 per node) "
-                  "or device upload failed");
-    }
-  }
-  if (is_block) {
-    bool ok = true;
-    t->bt.nc_term = upload(t, nc_term.data(), nc_term.size(), ok);
-    t->bt.clq_term = upload(t, clq_term.data(), clq_term.size(), ok);
-    t->bt.clq_pair_term = upload(t, clq_pair_term.data(), clq_pair_term.size(), ok);
-    t->bt.clq_pid_t = upload(t, clq_pid.data(), clq_pid.size(), ok);
-    t->bt.n_pairs = (int)clq_pair_term.size();
-    t->bt.node_of_row = upload(t, node_of_row.data(), node_of_row.size(), ok);
-    t->bt.wave_sl = upload(t, wave_sl.data(), wave_sl.size(), ok);
-    t->bt.Tc = Tc;
-    t->bt.n_clq = n_clq;
-    t->bt.clq_euclid = (n_clq && !(dbg_eff & 256) && d->clique_closed_form != GIK_CLIQUE_DENSE) ? 1 : 0;   // 256: always the dense D w product
-    t->clique_mode = !n_clq ? GIK_CLIQUE_OFF : (t->bt.clq_euclid ? GIK_CLIQUE_AUTO : GIK_CLIQUE_DENSE);
-    if (!ok) {
-      gik_template_destroy(t);
-      return fail("device upload of the workgroup-path tables failed");
-    }
-  }
-  if (d->force_block_path == 2 && !npt_ok) {
-    gik_template_destroy(t);
-    return fail("node-per-lane kernel: k = 3, TrustRegions, theta = 1, at most 256 terms outside the rigid clique, at most 16 per lane");
-  }
-  if (npt_ok) {
-    bool ok = true;
-    t->nt.node_of_row = upload(t, npt_node_of_row.data(), npt_node_of_row.size(), ok);
-    t->nt.clq_pair_term = upload(t, npt_pair_term.data(), npt_pair_term.size(), ok);
-    t->nt.term_rec = upload(t, npt_term_rec.data(), npt_term_rec.size(), ok);
-    t->nt.term_tgt = upload(t, npt_term_tgt.data(), npt_term_tgt.size(), ok);
-    t->nt.gather = upload(t, npt_gather.data(), npt_gather.size(), ok);
-    t->nt.wslot_of_row = upload(t, npt_wslot.data(), npt_wslot.size(), ok);
-    t->nt.prow_of_slot = upload(t, npt_prow.data(), npt_prow.size(), ok);
-    t->nt.n_helped = npt_n_helped;
-    t->nt.n_clq = n_clq;
-    t->nt.n_pairs = (int)npt_pair_term.size();
-    t->nt.DEG0 = npt_DEG0;
-    t->nt.DEG1 = npt_DEG1;
-    t->nt.n_wrows = npt_n_wrows;
-    t->nt.TL = npt_TL;
-    t->nt.clq_euclid = t->bt.clq_euclid;
-    t->nt.cbase = npt_cbase;
-    t->nt.n_rows = npt_n_rows;
-    t->nt.n_terms = npt_n_terms;
-    t->nt.term_sync = npt_term_sync;
-    for (const NptVariant &v : kNptVariants)
-      if (v.TL == npt_TL && v.NW == npt_NW) t->npt_variant = &v;
-    t->npt_smem = t->npt_variant->lds(t->nt.n_pairs, npt_n_wrows, npt_n_rows, npt_n_terms);
-    const void *fns[2] = {(const void *)t->npt_variant->solve, (const void *)t->npt_variant->kat};
-    int occ_npt = 0;
-    ok = ok && t->npt_smem <= 160 * 1024;
-    if (ok && t->npt_smem > 48 * 1024)
-      for (const void *fn : fns) ok = ok && raise_dynamic_lds(fn, t->npt_smem) == hipSuccess;
-    ok = ok && hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_npt, fns[0], WAVE * t->npt_variant->NW, t->npt_smem) == hipSuccess;
-    if (!ok) {
-      (void)hipGetLastError();
-      if (d->force_block_path == 2) {
-        gik_template_destroy(t);
-        return fail("node-per-lane kernel: device setup failed (LDS)");
-      }
-    } else {
-      t->is_npt = true;
-      t->npt_waves_per_cu = std::max(1, std::min(occ_npt, 4));   // problems (workgroups) per CU
-    }
-  }
-  if (big && !t->is_npt) {
-    gik_template_destroy(t);
-    return fail("graphs of more than 128 nodes need the node-per-lane kernel: at most 256 terms outside the rigid clique "
-                "(16 per node), at most 127 nodes that carry such terms");
-  }
-  if ((t->dbg & 32) && t->is_npt)
-    fprintf(stderr, "  node-per-lane kernel: %d wavefront(s) per problem, TL=%d, %d slot terms (sync %d), %d direction rows, gather lists %d + %d, "
-            "clique rows from %d, lds=%zu B, %d problems per CU\n",
-            t->npt_variant->NW, t->nt.TL, t->nt.n_terms, t->nt.term_sync, t->nt.n_wrows, t->nt.DEG0, t->nt.DEG1, t->nt.cbase,
-            t->npt_smem, t->npt_waves_per_cu);
-  if (t->dbg & 32)
-      fprintf(stderr, "gik_template_create: N=%d k=%d T=%d %s maxdeg=%d lds=%zu B occupancy=%d per CU, %d CUs; "
-              "clique %d, slot terms %d, slots %d\n",
-              t->N, t->K, t->T, is_block ? "block" : "wave", is_block ? 0 : t->variant->maxdeg,
-              t->smem_bytes, occ, t->n_cu, n_clq, Tc, SL);
-  if ((t->dbg & 32) && is_block) {
-    fprintf(stderr, "  slot loop bounds per wavefront {equalities, all}:");
-    for (int w = 0; w < BLOCK_WAVES; ++w) fprintf(stderr, " {%d, %d}", wave_sl[2 * w], wave_sl[2 * w + 1]);
-    fprintf(stderr, "\n");
-  }
-  *out = t;
-  return 0;
 }
 
 void gik_template_destroy(gik_template *t) {
@@ -1440,9 +1453,6 @@ static int launch_kat(const gik_template *t, int mode, const double *d_Y, const 
     a.an = t->an;
     a.an.anchor_goal = d_targets;          // (anchored templates: the per-problem input is the goal anchors)
     a.targets = t->d_targets_const;
-    hipLaunchKernelGGL(t->variant->kat_anch, dim3(B), dim3(WAVE), t->smem_bytes, (hipStream_t)stream, a);
-    HIP_OK(hipGetLastError());
-    return 0;
   }
   if (t->quad_solve && (t->dbg & 16384) && !(t->dbg & (1 | 8192))) {
     hipLaunchKernelGGL(kat_quad_kernel<6>, dim3((B + QUAD_SLOTS - 1) / QUAD_SLOTS), dim3(WAVE), t->quad_smem,
@@ -1458,15 +1468,9 @@ static int launch_kat(const gik_template *t, int mode, const double *d_Y, const 
     hipLaunchKernelGGL(t->npt_variant->kat, dim3(B), dim3(WAVE * t->npt_variant->NW), t->npt_smem, (hipStream_t)stream, a);
     if (ws) HIP_OK(hipFreeAsync(ws, (hipStream_t)stream));
   } else if (t->is_block) {
-    if (t->K == 3)
-      hipLaunchKernelGGL(kat_block_kernel<3>, dim3(B), dim3(BLOCK_NT), t->smem_bytes,
-                         (hipStream_t)stream, a, t->SL);
-    else
-      hipLaunchKernelGGL(kat_block_kernel<2>, dim3(B), dim3(BLOCK_NT), t->smem_bytes,
-                         (hipStream_t)stream, a, t->SL);
+    hipLaunchKernelGGL(t->kernels.block_kat, dim3(B), dim3(BLOCK_NT), t->smem_bytes, (hipStream_t)stream, a, t->SL);
   } else {
-    hipLaunchKernelGGL(t->hess_per_edge ? t->variant->kat_strict : t->variant->kat, dim3(B), dim3(WAVE), t->smem_bytes,
-                       (hipStream_t)stream, a);
+    hipLaunchKernelGGL(t->kernels.kat, dim3(B), dim3(WAVE), t->smem_bytes, (hipStream_t)stream, a);
   }
   HIP_OK(hipGetLastError());
   return 0;
@@ -1577,11 +1581,6 @@ int gik_solve_batch(const gik_template *t, const double *d_Y_init, const double 
       std::this_thread::yield();      // every slot is between hand-out and launch in some other thread
     }
   };
-  auto give_back = [&](auto &slot) {
-    std::lock_guard<std::mutex> lock(mt->call_mutex);
-    slot.pending = true;
-    slot.in_use = false;
-  };
   gik_template::CounterSlot &cs = mt->counter_slot[take(mt->counter_slot, mt->next_counter, (unsigned)t->counter_ring)];
   struct Release {      // error paths hand the slots back too (no launch: nothing pending)
     gik_template *mt;
@@ -1642,10 +1641,8 @@ int gik_solve_batch(const gik_template *t, const double *d_Y_init, const double 
   // (At one wave per SIMD -- batches up to 6 problems per SIMD -- round-robin slicing LOSES 5-8 %: a
   // straggler that happens to start at t = 0 is better off keeping its slot than sharing it for the
   // first ~20 ms; measured on 4096 LWA4D / KUKA / UR10 goals, four seeds each, tools/attic/dev_rr_midbatch.py.)
-  // (the build of the form that runs: <3, 10> has a per-edge tail-spreading build but no column-form one)
-  const bool mig = !t->is_block && !cg && !t->anchored &&
-                   (t->hess_per_edge ? t->variant->solve_strict_mig : t->variant->solve_mig) && t->p.theta == 1.0 &&
-                   wpc > 4 && B > grid && !(a.dbg & (1 | 512));
+  // (kernels.solve_spread is the build of the form that runs: <3, 10> has a per-edge one but no column-form one)
+  const bool mig = t->kernels.solve_spread && wpc > 4 && B > grid && !(a.dbg & (1 | 512));
   gik_template::SliceWs *sw = nullptr;
   // graphs beyond 128 nodes (node-per-lane kernel on four wavefronts): the clique's target triangle of every resident
   // workgroup lives in global memory -- a region of the same pooled workspace
@@ -1724,18 +1721,9 @@ int gik_solve_batch(const gik_template *t, const double *d_Y_init, const double 
     a.nt = t->nt;
     hipLaunchKernelGGL(t->npt_variant->solve, dim3(grid), dim3(WAVE * t->npt_variant->NW), t->npt_smem, (hipStream_t)stream, a);
   } else if (t->is_block) {
-    void (*kern)(SolveArgs, int) =
-        cg ? (t->K == 3 ? rcg_block_kernel<3> : rcg_block_kernel<2>)
-           : (t->K == 3 ? rtr_block_kernel<3> : rtr_block_kernel<2>);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK_NT), t->smem_bytes, (hipStream_t)stream, a, t->SL);
+    hipLaunchKernelGGL(t->kernels.block_solve, dim3(grid), dim3(BLOCK_NT), t->smem_bytes, (hipStream_t)stream, a, t->SL);
   } else {
-    hipLaunchKernelGGL(t->anchored ? t->variant->solve_anch
-                       : cg        ? t->variant->solve_cg
-                       : t->hess_per_edge ? (t->p.theta != 1.0 ? t->variant->solve_strict_theta
-                                             : (mig ? t->variant->solve_strict_mig : t->variant->solve_strict))
-                       : mig       ? t->variant->solve_mig
-                                   : (t->p.theta == 1.0 ? t->variant->solve : t->variant->solve_theta),
-                       dim3(grid), dim3(WAVE), t->smem_bytes, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(mig ? t->kernels.solve_spread : t->kernels.solve, dim3(grid), dim3(WAVE), t->smem_bytes, (hipStream_t)stream, a);
   }
   HIP_OK(hipGetLastError());
   // The slots go back "pending" only behind an event that really covers this launch.  If a record fails,
@@ -1755,7 +1743,7 @@ int gik_template_get_info(const gik_template *t, gik_template_info *info) {
   if (!t || !info) return gik::fail("null argument");
   std::memset(info, 0, sizeof(*info));
   info->is_block = t->is_block ? 1 : 0;
-  info->max_terms_per_node = t->is_block ? 0 : t->variant->maxdeg;
+  info->max_terms_per_node = t->is_block ? 0 : t->maxdeg;
   info->n_clique = t->bt.n_clq;
   info->n_slot_terms = t->is_block ? t->bt.Tc : t->T;
   info->slots_per_thread = t->SL;

@@ -299,6 +299,8 @@ BATCH_CASES = {
     "mig_d9_column": dict(graph="w3_n21_d9_column", params={"hessian_form": "column"},
                           reaches=["rtr_wave_kernel<3,9,true,false,true>"], mig=True),
     "mig_d10": dict(graph="w3_n21_d10", params={}, reaches=["rtr_wave_kernel<3,10,true,false,true,true>"], mig=True),
+    # (<3, 10> has no column-form tail-spreading build: the same batch runs on the plain one, nothing moves)
+    "mig_d10_column": dict(graph="w3_n21_d10_column", params={"hessian_form": "column"}, reaches=_column(10)[:1], mig=False),
     "mig_d10_off": dict(graph="w3_n21_d10", params={"debug_flags": 512}, reaches=_strict(10)[:1], mig=False),
     "quad_below": dict(graph="w2_n16_quad", params={}, reaches=["rtr_wave_kernel<2,6,true>"], quad=-1),
     "quad_above": dict(graph="w2_n16_quad", params={}, reaches=["rtr_quad_kernel<6>"], quad=3),
