@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GIK_LIB_PATH") or os.path.join(_HERE, "lib", "libgraphik_amd.so")
 
 TERM_EQ, TERM_LOWER, TERM_UPPER = 1, 2, 3
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 
 class TemplateDesc(C.Structure):
@@ -101,6 +101,12 @@ class AnchoredDesc(C.Structure):
     ]
 
 
+class RetryOpts(C.Structure):
+    """gik_retry_opts"""
+    _fields_ = [("retries", C.c_int32), ("reserved0", C.c_int32), ("seed", C.c_uint64),
+                ("pos_tol", C.c_double), ("rot_tol", C.c_double), ("d_q_lo", C.c_void_p), ("d_q_hi", C.c_void_p)]
+
+
 class PrepareDiag(C.Structure):
     _fields_ = [("d_lb", C.c_void_p), ("d_ub", C.c_void_p), ("d_eig", C.c_void_p)]
 
@@ -143,6 +149,15 @@ SYMBOLS = {
                                  C.c_void_p]),
     "gik_ik_batch_seeded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gik_retry_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double,
+                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gik_retry_seeds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gik_retry_merge": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double] +
+                        11 * [C.c_void_p] + [C.c_void_p]),
+    "gik_retry_ws_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
+    "gik_ik_batch_retry": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(RetryOpts)] +
+                           8 * [C.c_void_p] + [C.c_void_p]),
 }
 
 _lib = None

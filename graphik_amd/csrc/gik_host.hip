@@ -4,6 +4,7 @@
 
 #include "gik_kernels.hip.h"
 #include "gik_instances.h"
+#include "gik_retry.hip.h"
 #include <memory>
 
 namespace gik {
@@ -1347,6 +1348,183 @@ int gik_ik_batch_seeded(const gik_template *t, const double *d_T_goal, const dou
   rc = gik_solve_batch(t, d_Y, d_targets, B, d_Y, d_stats, nullptr, stream);
   if (rc) return rc;
   return gik_recover_batch(t, d_Y, d_T_goal, B, d_q, d_pos_err, d_rot_err, stream);
+}
+
+// ---- restarts from random joint configurations (gik_retry.hip.h) --------------------------------------
+int gik_retry_select(const gik_stats *d_stats, const double *d_pos_err, const double *d_rot_err, int B, double pos_tol,
+                     double rot_tol, int32_t *d_idx, int32_t *d_count, void *stream) {
+  using namespace gik;
+  if (B < 0) return fail("bad argument");
+  if (!d_idx || !d_count) return fail("null buffer");
+  HIP_OK(hipMemsetAsync(d_count, 0, sizeof(int32_t), (hipStream_t)stream));
+  if (B == 0) return 0;
+  if (!d_stats || !d_pos_err || !d_rot_err) return fail("null buffer");
+  RetrySelectArgs a;
+  a.stats = d_stats;
+  a.pos_err = d_pos_err;
+  a.rot_err = d_rot_err;
+  a.pos_tol = pos_tol;
+  a.rot_tol = rot_tol;
+  a.idx = d_idx;
+  a.count = d_count;
+  a.B = B;
+  hipLaunchKernelGGL(retry_select_kernel, dim3((B + RETRY_WAVE - 1) / RETRY_WAVE), dim3(RETRY_WAVE), 0,
+                     (hipStream_t)stream, a);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+static int retry_grid(const gik_template *t, int count) { return std::min(count, t->n_cu * 8); }
+
+int gik_retry_seeds(const gik_template *t, const double *d_T_goal, const int32_t *d_idx, int count, uint64_t seed,
+                    int attempt, const double *d_q_lo, const double *d_q_hi, double *d_T_out, double *d_q_out,
+                    void *stream) {
+  using namespace gik;
+  if (!t || count < 0) return fail("bad argument");
+  if (!t->has_pipe) return fail("no pipeline attached (gik_pipeline_attach)");
+  if (attempt < 0 || attempt > 63) return fail("gik_retry_seeds: attempt must be within 0 .. 63");
+  if (!d_q_lo || !d_q_hi) return fail("gik_retry_seeds: null joint limits (d_q_lo / d_q_hi, [n] each, are required)");
+  if (count == 0) return 0;
+  if (!d_T_goal || !d_idx || !d_T_out || !d_q_out) return fail("null buffer");
+  RetrySeedArgs a;
+  a.T_goal = d_T_goal;
+  a.idx = d_idx;
+  a.q_lo = d_q_lo;
+  a.q_hi = d_q_hi;
+  a.T_out = d_T_out;
+  a.q_out = d_q_out;
+  a.seed = seed;
+  a.count = count;
+  a.pose_w = t->pc.n_ee * (t->K + 1) * (t->K + 1);
+  a.n = t->pc.n_joints;
+  a.attempt = attempt;
+  hipLaunchKernelGGL(retry_seed_kernel, dim3(retry_grid(t, count)), dim3(RETRY_WAVE), 0, (hipStream_t)stream, a);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int gik_retry_merge(const gik_template *t, const int32_t *d_idx, int count, int attempt, double pos_tol, double rot_tol,
+                    const double *d_Y_r, const gik_stats *d_stats_r, const double *d_q_r, const double *d_pos_err_r,
+                    const double *d_rot_err_r, double *d_Y, gik_stats *d_stats, double *d_q, double *d_pos_err,
+                    double *d_rot_err, int32_t *d_attempt, void *stream) {
+  using namespace gik;
+  if (!t || count < 0) return fail("bad argument");
+  if (!t->has_pipe) return fail("no pipeline attached (gik_pipeline_attach)");
+  if (count == 0) return 0;
+  if (!d_idx || !d_Y_r || !d_stats_r || !d_q_r || !d_pos_err_r || !d_rot_err_r || !d_Y || !d_stats || !d_q ||
+      !d_pos_err || !d_rot_err || !d_attempt)
+    return fail("null buffer");
+  RetryMergeArgs a;
+  a.idx = d_idx;
+  a.Y_r = d_Y_r;
+  a.stats_r = d_stats_r;
+  a.q_r = d_q_r;
+  a.pos_r = d_pos_err_r;
+  a.rot_r = d_rot_err_r;
+  a.Y = d_Y;
+  a.stats = d_stats;
+  a.q = d_q;
+  a.pos_err = d_pos_err;
+  a.rot_err = d_rot_err;
+  a.attempt = d_attempt;
+  a.pos_tol = pos_tol;
+  a.rot_tol = rot_tol;
+  a.count = count;
+  a.row = t->N * t->K;
+  a.n = t->pc.n_joints;
+  a.attempt_no = attempt;
+  hipLaunchKernelGGL(retry_merge_kernel, dim3(retry_grid(t, count)), dim3(RETRY_WAVE), 0, (hipStream_t)stream, a);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// The caller-owned workspace of gik_ik_batch_retry, every array sized for B failed goals:
+//   count (8 bytes) | idx [B] int32, padded to 8 bytes | poses | seed angles | targets | Y | stats | q | pos_err | rot_err
+namespace gik {
+struct RetryWs {
+  int32_t *count, *idx;
+  double *T, *q_seed, *targets, *Y, *q, *pos_err, *rot_err;
+  gik_stats *stats;
+  size_t bytes;
+};
+static RetryWs retry_ws(const gik_template *t, int B, void *base) {
+  const size_t b = (size_t)B, n = (size_t)t->pc.n_joints, pose_w = (size_t)t->pc.n_ee * (t->K + 1) * (t->K + 1);
+  const uintptr_t p = reinterpret_cast<uintptr_t>(base);      // (null: gik_retry_ws_bytes only wants the size)
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    const uintptr_t at = p + off;
+    off += (bytes + 7) / 8 * 8;
+    return at;
+  };
+  RetryWs w;
+  w.count = reinterpret_cast<int32_t *>(take(8));
+  w.idx = reinterpret_cast<int32_t *>(take(b * sizeof(int32_t)));
+  w.T = reinterpret_cast<double *>(take(b * pose_w * sizeof(double)));
+  w.q_seed = reinterpret_cast<double *>(take(b * n * sizeof(double)));
+  w.targets = reinterpret_cast<double *>(take(b * (size_t)t->T * sizeof(double)));
+  w.Y = reinterpret_cast<double *>(take(b * (size_t)t->N * t->K * sizeof(double)));
+  w.stats = reinterpret_cast<gik_stats *>(take(b * sizeof(gik_stats)));
+  w.q = reinterpret_cast<double *>(take(b * n * sizeof(double)));
+  w.pos_err = reinterpret_cast<double *>(take(b * sizeof(double)));
+  w.rot_err = reinterpret_cast<double *>(take(b * sizeof(double)));
+  w.bytes = off;
+  return w;
+}
+}  // namespace gik
+
+size_t gik_retry_ws_bytes(const gik_template *t, int B) {
+  if (!t || !t->has_pipe || B < 0) return 0;
+  return gik::retry_ws(t, B, nullptr).bytes;
+}
+
+int gik_ik_batch_retry(const gik_template *t, const double *d_T_goal, const double *d_q_init, int B,
+                       const gik_retry_opts *opts, void *d_ws, double *d_targets, double *d_Y, gik_stats *d_stats,
+                       double *d_q, double *d_pos_err, double *d_rot_err, int32_t *d_attempt, void *stream) {
+  using namespace gik;
+  // every refusal comes before anything is queued
+  if (!t || B < 0 || !opts) return fail("bad argument");
+  if (!t->has_pipe) return fail("gik_ik_batch_retry: no pipeline attached (gik_pipeline_attach)");
+  if (opts->retries < 0 || opts->retries > 63) return fail("gik_ik_batch_retry: retries must be within 0 .. 63");
+  if (opts->retries > 0) {
+    if (!t->seed_ok) return fail("gik_ik_batch_retry: this graph cannot be seeded on the device: " + t->seed_why);
+    if (!opts->d_q_lo || !opts->d_q_hi)
+      return fail("gik_ik_batch_retry: null joint limits (opts->d_q_lo / d_q_hi, [n] each, are what the seeds are drawn from)");
+    if (!(opts->pos_tol > 0.0) || !(opts->rot_tol > 0.0)) return fail("gik_ik_batch_retry: pos_tol and rot_tol must be positive");
+    if (!d_ws && B > 0) return fail("gik_ik_batch_retry: null workspace (gik_retry_ws_bytes)");
+    if ((uintptr_t)d_ws % 8) return fail("gik_ik_batch_retry: the workspace must be 8-byte aligned");
+  }
+  if (capturing_stream(stream))
+    return fail("gik_ik_batch_retry: the stream is capturing (hipStreamBeginCapture); batch calls cannot be captured into a graph");
+  if (B == 0) return 0;
+  if (!d_T_goal || !d_targets || !d_Y || !d_stats || !d_q || !d_pos_err || !d_rot_err || !d_attempt) return fail("null buffer");
+  hipStream_t s = (hipStream_t)stream;
+  HIP_OK(hipMemsetAsync(d_attempt, 0, (size_t)B * sizeof(int32_t), s));
+  int rc = d_q_init ? gik_ik_batch_seeded(t, d_T_goal, d_q_init, B, d_targets, d_Y, d_stats, d_q, d_pos_err, d_rot_err, stream)
+                    : gik_ik_batch(t, d_T_goal, B, d_targets, d_Y, d_stats, d_q, d_pos_err, d_rot_err, stream);
+  if (rc) return rc;
+  const RetryWs w = retry_ws(t, B, d_ws);
+  for (int a = 1; a <= opts->retries; ++a) {
+    rc = gik_retry_select(d_stats, d_pos_err, d_rot_err, B, opts->pos_tol, opts->rot_tol, w.idx, w.count, stream);
+    if (rc) return rc;
+    // the solve kernels take their batch size from the host: the count comes back, the stream drains
+    int32_t count = 0;
+    HIP_OK(hipMemcpyAsync(&count, w.count, sizeof(count), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    if (count < 0 || count > B) return fail("gik_ik_batch_retry: the failed-goal count came back out of range");
+    if (count == 0) break;
+    rc = gik_retry_seeds(t, d_T_goal, w.idx, count, opts->seed, a, opts->d_q_lo, opts->d_q_hi, w.T, w.q_seed, stream);
+    if (rc) return rc;
+    rc = gik_seed_batch(t, w.T, w.q_seed, count, w.targets, w.Y, stream);
+    if (rc) return rc;
+    rc = gik_solve_batch(t, w.Y, w.targets, count, w.Y, w.stats, nullptr, stream);
+    if (rc) return rc;
+    rc = gik_recover_batch(t, w.Y, w.T, count, w.q, w.pos_err, w.rot_err, stream);
+    if (rc) return rc;
+    rc = gik_retry_merge(t, w.idx, count, a, opts->pos_tol, opts->rot_tol, w.Y, w.stats, w.q, w.pos_err, w.rot_err, d_Y,
+                         d_stats, d_q, d_pos_err, d_rot_err, d_attempt, stream);
+    if (rc) return rc;
+  }
+  return 0;
 }
 
 size_t gik_anchored_ws_doubles(const gik_template *anch, const gik_template *base, int B) {

@@ -70,6 +70,32 @@ def _decode_stats(stats):
     return out
 
 
+RETRY_MAX = 63          # attempts share 6 bits of the seed generator's counter (include/graphik_amd.h)
+RETRY_MAX_JOINTS = 125
+
+
+def check_retry_args(retries, pos_tol, rot_tol, q_limits, n):
+    """Arguments of a solve with restarts, checked on the host before any device call: retries within
+    0 .. 63, positive tolerances, joint limits (q_lo [n], q_hi [n]) finite and ordered.  Returns
+    (retries, q_lo, q_hi) with the limits as contiguous float64 arrays; ValueError otherwise."""
+    if int(retries) != retries or not 0 <= int(retries) <= RETRY_MAX:
+        raise ValueError(f"retries must be an integer within 0 .. {RETRY_MAX}, got {retries!r}")
+    if not (pos_tol > 0 and rot_tol > 0):
+        raise ValueError("pos_tol and rot_tol must be positive")
+    if n > RETRY_MAX_JOINTS:
+        raise ValueError(f"restarts cover robots of at most {RETRY_MAX_JOINTS} joints")
+    if q_limits is None:
+        raise ValueError("retries > 0 needs q_limits=(q_lo, q_hi): the seeds are drawn inside them")
+    lo, hi = (np.ascontiguousarray(np.asarray(a, dtype=np.float64)) for a in q_limits)
+    if lo.shape != (n,) or hi.shape != (n,):
+        raise ValueError(f"q_limits must be two arrays of shape [{n}], got {list(lo.shape)} and {list(hi.shape)}")
+    if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi))):
+        raise ValueError("q_limits has non-finite entries: random seeds need finite joint limits")
+    if np.any(lo > hi):
+        raise ValueError("q_limits: a lower limit exceeds its upper limit")
+    return int(retries), lo, hi
+
+
 class Template:
     """Goal-independent part of an IK problem family, resident on one GPU."""
 
@@ -384,17 +410,46 @@ class Template:
                                                Y0.data_ptr(), self._stream()))
         return targets, Y0.reshape(B, self.N, self.k)
 
-    def ik(self, T_goal, out=None, q_init=None):
+    def ik(self, T_goal, out=None, q_init=None, retries=0, retry_seed=0, pos_tol=0.01, rot_tol=0.01, q_limits=None):
         """Whole solve_with_riemannian pipeline for a batch of goal poses, one stream, no host
         round trip: prepare -> solve -> recover.  With q_init (seed joint angles [B,n] or [n], a
         device tensor may be out["q"] itself) the initial point is the realization of q_init instead
         of the bound-smoothing + MDS one: seed -> solve -> recover (gik_ik_batch_seeded).  Returns a
-        dict of device tensors."""
+        dict of device tensors.
+
+        retries > 0 (gik_ik_batch_retry): goals that fail -- stop != 0, pos_err > pos_tol or rot_err >
+        rot_tol -- are solved again, up to `retries` times, from joint angles drawn uniformly inside
+        q_limits = (q_lo [n], q_hi [n]) by a generator keyed on (retry_seed, goal, attempt), and the
+        better answer is kept; "attempt" [B] int32 says which one each goal holds.  That call
+        synchronises the stream once per attempt.  `out` may carry "attempt" [B] int32, "retry_ws" (a
+        buffer of gik_retry_ws_bytes) and "q_lo" / "q_hi" device tensors to reuse between calls."""
+        if retries:
+            if not getattr(self, "has_pipeline", False):
+                raise _ffi.GikError("no pipeline attached (attach_pipeline): restarts need the device pipeline")
+            retries, lo, hi = check_retry_args(retries, pos_tol, rot_tol, q_limits, self.n_joints)
         T, B = self._poses(T_goal)
         if out is None:
             out = self.alloc_ik_buffers(B)
         with torch.cuda.device(self.device):
-            if q_init is None:
+            if retries:
+                q0 = None if q_init is None else self._seed_angles(q_init, B)
+                attempt = out.get("attempt")
+                if attempt is None:
+                    attempt = torch.empty(B, dtype=torch.int32, device=self.device)
+                ws = out.get("retry_ws")
+                nbytes = int(self.lib.gik_retry_ws_bytes(self._h, B))
+                if ws is None or ws.numel() * ws.element_size() < nbytes:
+                    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=self.device)
+                q_lo = out["q_lo"] if "q_lo" in out else _dev(lo, self.device)
+                q_hi = out["q_hi"] if "q_hi" in out else _dev(hi, self.device)
+                opts = _ffi.RetryOpts(retries=retries, seed=int(retry_seed) & (2 ** 64 - 1), pos_tol=float(pos_tol),
+                                      rot_tol=float(rot_tol), d_q_lo=q_lo.data_ptr(), d_q_hi=q_hi.data_ptr())
+                _ffi.check(self.lib.gik_ik_batch_retry(self._h, T.data_ptr(), None if q0 is None else q0.data_ptr(), B,
+                                                       C.byref(opts), ws.data_ptr(), out["targets"].data_ptr(),
+                                                       out["Y"].data_ptr(), out["stats"].data_ptr(), out["q"].data_ptr(),
+                                                       out["pos_err"].data_ptr(), out["rot_err"].data_ptr(),
+                                                       attempt.data_ptr(), self._stream()))
+            elif q_init is None:
                 _ffi.check(self.lib.gik_ik_batch(self._h, T.data_ptr(), B, out["targets"].data_ptr(),
                                                  out["Y"].data_ptr(), out["stats"].data_ptr(),
                                                  out["q"].data_ptr(), out["pos_err"].data_ptr(),
@@ -408,6 +463,8 @@ class Template:
                                                         self._stream()))
         res = {"x": out["Y"].reshape(B, self.N, self.k), "q": out["q"], "pos_err": out["pos_err"],
                "rot_err": out["rot_err"]}
+        if retries:
+            res["attempt"], res["_retry_ws"] = attempt, ws      # (the workspace lives as long as the result)
         res.update(_decode_stats(out["stats"]))
         return res
 

@@ -16,7 +16,7 @@ import time
 import numpy as np
 import torch
 
-from ..engine import Template, _alloc_stats, _decode_stats, build_terms
+from ..engine import Template, _alloc_stats, _decode_stats, build_terms, check_retry_args
 from ..utils import dgp
 from ..utils.constants import POS
 from ..utils.lie import as_matrix
@@ -643,7 +643,38 @@ def _seed_angles(q_init, B, n, name="q_init"):
     return np.ascontiguousarray(q)
 
 
-def solve_batch(graph, T_goals, use_limits=True, params=None, device=None, Y_init=None, q_init=None):
+def retry_uniform_host(seed, goals, attempt, n):
+    """The restart generator's uniform numbers in [0, 1), [len(goals), n]: splitmix64's finaliser over the
+    counter of (goal, attempt, joint) in uint64 arithmetic -- bit for bit what retry_seed_kernel draws
+    (include/graphik_amd.h)."""
+    if not 0 <= int(attempt) <= 63 or not 0 < int(n) <= 125:
+        raise ValueError("attempt must be within 0 .. 63 and n within 1 .. 125")
+    u64 = np.uint64
+    g = np.asarray(goals, dtype=np.int64).reshape(-1)
+    if np.any(g < 0):
+        raise ValueError("goal indices must not be negative")
+    with np.errstate(over="ignore"):
+        c = (g.astype(u64)[:, None] * u64(64) + u64(int(attempt))) * u64(128) + np.arange(n, dtype=u64)[None, :] + u64(1)
+        z = u64(int(seed) & (2 ** 64 - 1)) + u64(0x9E3779B97F4A7C15) * c
+        z ^= z >> u64(30)
+        z *= u64(0xBF58476D1CE4E5B9)
+        z ^= z >> u64(27)
+        z *= u64(0x94D049BB133111EB)
+        z ^= z >> u64(31)
+    return (z >> u64(11)).astype(np.float64) * 2.0 ** -53
+
+
+def retry_seeds_host(seed, goals, attempt, q_lo, q_hi):
+    """Host mirror of gik_retry_seeds: the joint angles [len(goals), n] that restart `attempt` of goals
+    `goals` starts from, q = q_lo + u (q_hi - q_lo) with u from retry_uniform_host.  A function of
+    (seed, goal, attempt, joint) alone; the same bits as the device draws."""
+    lo, hi = np.asarray(q_lo, dtype=np.float64), np.asarray(q_hi, dtype=np.float64)
+    u = retry_uniform_host(seed, goals, attempt, len(lo))
+    return lo[None, :] + u * (hi - lo)[None, :]
+
+
+def solve_batch(graph, T_goals, use_limits=True, params=None, device=None, Y_init=None, q_init=None,
+                retries=0, retry_seed=0, pos_tol=0.01, rot_tol=0.01):
     """Batched solve_with_riemannian.  T_goals: [B,d+1,d+1] array or list of poses.
     Returns (q [B,n], Y [B,N,k], info dict of arrays).
 
@@ -652,16 +683,41 @@ def solve_batch(graph, T_goals, use_limits=True, params=None, device=None, Y_ini
     reference's RiemannianSolver.solve(D_goal, omega, Y_init=pos_from_graph(graph.realization(q_init)),
     bounds=None) -- instead of from bound smoothing + MDS; on the device pipeline that is one
     gik_ik_batch_seeded call, otherwise the host realization (BatchProblem.seed_points) feeds the
-    device solve.  Y_init and q_init exclude each other."""
+    device solve.  Y_init and q_init exclude each other.
+
+    retries > 0 (restarts, device pipeline only): a goal that fails -- stop != 0, pos_err > pos_tol or
+    rot_err > rot_tol -- is solved again up to `retries` (<= 63) times from joint angles drawn uniformly
+    inside graph.robot.limits_arrays() (retry_seeds_host(retry_seed, [g], attempt, lo, hi) are goal g's),
+    and the better answer is kept; info["attempt"] [B] int32 is the attempt each goal's answer comes
+    from (0: the first).  With q_init the first attempt is seeded and the later ones are random.  Y_init
+    cannot be combined with retries, and a graph off the device pipeline has none: ValueError."""
     T = np.stack([as_matrix(t) for t in T_goals]) if not isinstance(T_goals, np.ndarray) \
         else np.asarray(T_goals, dtype=float)
     if q_init is not None:
         if Y_init is not None:
             raise ValueError("pass Y_init or q_init, not both")
         q_init = _seed_angles(q_init, T.shape[0], graph.robot.n)
+    retry = {}
+    if retries:
+        if Y_init is not None:
+            raise ValueError("retries > 0 cannot be combined with Y_init (pass q_init, or no start at all)")
+        check_retry_args(retries, pos_tol, rot_tol, graph.robot.limits_arrays(), graph.robot.n)
+        retry = dict(retries=retries, retry_seed=retry_seed, pos_tol=pos_tol, rot_tol=rot_tol,
+                     q_limits=graph.robot.limits_arrays())
     prob = _problem_for(graph, use_limits, params, device)
+    if retries and not prob.device_pipeline:
+        raise ValueError("retries > 0 needs the device pipeline, which this graph is outside of")
     t0 = time.time()
-    if q_init is not None:
+    attempt = None
+    if retries:
+        res = prob.template.ik(T, q_init=q_init, **retry)      # gik_ik_batch_retry
+        torch.cuda.synchronize(prob.template.device)
+        dt = time.time() - t0
+        Y = res["x"].cpu().numpy()
+        q = res["q"].cpu().numpy()
+        pos, rot = res["pos_err"].cpu().numpy(), res["rot_err"].cpu().numpy()
+        attempt = res["attempt"].cpu().numpy()
+    elif q_init is not None:
         if prob.device_pipeline:
             res = prob.template.ik(T, q_init=q_init)      # seed -> solve -> recover (gik_ik_batch_seeded)
             torch.cuda.synchronize(prob.template.device)
@@ -702,39 +758,50 @@ def solve_batch(graph, T_goals, use_limits=True, params=None, device=None, Y_ini
             "iterations": res["iterations"].cpu().numpy(),
             "inner_iterations": res["inner_total"].cpu().numpy(),
             "stop": res["stop"].cpu().numpy(), "time": np.full(len(Y), dt / max(len(Y), 1)),
-            "solve_time": dt, "pos_err": pos, "rot_err": rot}
+            "solve_time": dt, "pos_err": pos, "rot_err": rot,
+            "attempt": attempt if attempt is not None else np.zeros(len(Y), dtype=np.int32)}
     return q, Y, info
 
 
-def solve_trajectory(graph, T_path, q_start, use_limits=True, params=None, device=None, return_Y=False):
+def solve_trajectory(graph, T_path, q_start, use_limits=True, params=None, device=None, return_Y=False,
+                     retries=0, retry_seed=0, pos_tol=0.01, rot_tol=0.01):
     """Path tracking: B paths of L waypoints, each waypoint a warm-started solve_batch.
 
     T_path: [B, L, d+1, d+1] goal poses ([B, L, n_ee, 4, 4] for robots with several end effectors).
     Waypoint 0 is seeded by q_start ([B,n] or [n]); waypoint l by the joint angles recovered at
     waypoint l-1.  On the device pipeline those angles never leave the device: the L calls of
     gik_ik_batch_seeded are queued on one stream without a host synchronisation in between.  A
-    waypoint whose solve fails (stop != 0, or a large pos_err) still seeds the next one; there is no
-    retry -- check info["stop"] / info["pos_err"].
+    waypoint whose solve fails (stop != 0, or a large pos_err) still seeds the next one; by default
+    there is no retry -- check info["stop"] / info["pos_err"].
+
+    retries > 0: every waypoint is a solve_batch(..., q_init=previous angles, retries=...) -- a failed
+    waypoint is solved again from random joint angles (see solve_batch), and a rescued waypoint seeds
+    the next one with its rescued angles.  Each waypoint then synchronises the stream once per attempt.
 
     Returns q [B, L, n], Y [B, L, N, k] (None unless return_Y), and info with [B, L] arrays
-    iterations, inner_iterations, stop, f(x), gradnorm, pos_err, rot_err, plus solve_time (seconds,
-    whole path)."""
+    iterations, inner_iterations, stop, f(x), gradnorm, pos_err, rot_err, attempt, plus solve_time
+    (seconds, whole path)."""
     T = np.asarray(T_path, dtype=float)
     B, L = T.shape[:2]
     n = graph.robot.n
     q0 = _seed_angles(q_start, B, n, "q_start")
+    retry = {}
+    if retries:
+        _, q_lo, q_hi = check_retry_args(retries, pos_tol, rot_tol, graph.robot.limits_arrays(), n)
+        retry = dict(retries=retries, retry_seed=retry_seed, pos_tol=pos_tol, rot_tol=rot_tol)
     prob = _problem_for(graph, use_limits, params, device)
     if not prob.device_pipeline:
         qs, Ys, infos, dt = [], [], [], 0.0
         q_prev = q0
         for l in range(L):
-            q_prev, Y, info = solve_batch(graph, T[:, l], use_limits, params, device, q_init=q_prev)
+            q_prev, Y, info = solve_batch(graph, T[:, l], use_limits, params, device, q_init=q_prev, **retry)
             qs.append(q_prev)
             Ys.append(Y)
             infos.append(info)
             dt += info["solve_time"]
         out = {key: np.stack([i[key] for i in infos], axis=1)
-               for key in ("iterations", "inner_iterations", "stop", "f(x)", "gradnorm", "pos_err", "rot_err")}
+               for key in ("iterations", "inner_iterations", "stop", "f(x)", "gradnorm", "pos_err", "rot_err",
+                           "attempt")}
         out["solve_time"] = dt
         return np.stack(qs, axis=1), (np.stack(Ys, axis=1) if return_Y else None), out
     tpl = prob.template
@@ -747,18 +814,26 @@ def solve_trajectory(graph, T_path, q_start, use_limits=True, params=None, devic
     pe, re = torch.empty(L, B, **f64), torch.empty(L, B, **f64)
     targets = torch.empty(B, tpl.T, **f64)
     q_prev = torch.from_numpy(q0).to(dev)
+    attempt = torch.zeros(L, B, dtype=torch.int32, device=dev)
+    shared = {}
+    if retries:      # one restart workspace and one copy of the limits for all waypoints
+        nbytes = int(tpl.lib.gik_retry_ws_bytes(tpl._h, B))
+        shared = {"retry_ws": torch.empty((nbytes + 7) // 8, **f64), "q_lo": torch.from_numpy(q_lo).to(dev),
+                  "q_hi": torch.from_numpy(q_hi).to(dev)}
+        retry["q_limits"] = (q_lo, q_hi)
     torch.cuda.synchronize(dev)
     t0 = time.time()
     for l in range(L):
         out = {"targets": targets, "Y": Y_all[l if return_Y else 0], "stats": stats[l], "q": q_all[l],
-               "pos_err": pe[l], "rot_err": re[l]}
-        tpl.ik(Tw[l], out=out, q_init=q_prev)
+               "pos_err": pe[l], "rot_err": re[l], "attempt": attempt[l], **shared}
+        tpl.ik(Tw[l], out=out, q_init=q_prev, **retry)
         q_prev = q_all[l]
     torch.cuda.synchronize(dev)
     dt = time.time() - t0
     st = _decode_stats(stats.reshape(L * B, -1))
     info = {"iterations": st["iterations"], "inner_iterations": st["inner_total"], "stop": st["stop"],
-            "f(x)": st["f"], "gradnorm": st["gradnorm"], "pos_err": pe.reshape(-1), "rot_err": re.reshape(-1)}
+            "f(x)": st["f"], "gradnorm": st["gradnorm"], "pos_err": pe.reshape(-1), "rot_err": re.reshape(-1),
+            "attempt": attempt.reshape(-1)}
     info = {key: v.reshape(L, B).T.cpu().numpy() for key, v in info.items()}
     info["solve_time"] = dt
     q = q_all.permute(1, 0, 2).cpu().numpy()

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define GIK_ABI_VERSION 6
+#define GIK_ABI_VERSION 7
 
 /* Residual-term kinds: one "term" per (index pair, kind) exactly as the loops of
  * costs.py:80-207 visit them: equality (omega != 0), lower hinge (psi_L != 0), upper hinge
@@ -369,6 +369,70 @@ int gik_seed_batch(const gik_template *t, const double *d_T_goal, const double *
 int gik_ik_batch_seeded(const gik_template *t, const double *d_T_goal, const double *d_q_init, int B,
                         double *d_targets, double *d_Y, gik_stats *d_stats, double *d_q,
                         double *d_pos_err, double *d_rot_err, void *stream);
+
+/* ---- restarts from random joint configurations (opt-in) ---------------------------------------
+ * The reference has ONE start per goal (the 0.9-interpolated bounds + MDS, riemannian_solver.py:67-75), and a goal
+ * that start does not solve stays unsolved.  Here a failed goal can be solved again from joint angles drawn uniformly
+ * inside the joint limits (the seeded solve above), and the better of the answers is kept -- without the batch
+ * leaving the device: the failed goals are compacted, seeded, solved as a batch of their own and merged back.
+ *
+ * failed(goal)  :=  stats.stop != 0  ||  !(pos_err <= pos_tol)  ||  !(rot_err <= rot_tol)      (NaN counts as failed)
+ * score(goal)   :=  max(pos_err / pos_tol, rot_err / rot_tol);  +inf if either error is NaN
+ * better(r, i)  :=  (r succeeds and i failed)  ||  (same success class  &&  score(r) < score(i))
+ *                   -- a NaN never wins, a tie keeps the incumbent.
+ *
+ * gik_retry_select: d_idx[0 .. *d_count) = the failed goals of the batch, in NO particular order (one atomic per
+ *   wavefront); *d_count is zeroed by the call.  d_idx holds B entries.
+ * gik_retry_seeds: for compact slot r, goal g = d_idx[r]: d_T_out[r] = d_T_goal[g] (n_ee (k+1)^2 doubles) and
+ *   d_q_out[r][j] = q_lo[j] + u (q_hi[j] - q_lo[j]) (one rounded product, one rounded sum), u in [0, 1) from a
+ *   counter-based generator -- a function of (seed, g, attempt, j) alone, so a goal's seed depends neither on which
+ *   other goals failed nor on its slot:
+ *       c = (g * 64 + attempt) * 128 + j + 1;   z = seed + 0x9E3779B97F4A7C15 * c   (mod 2^64)
+ *       z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9;  z ^= z >> 27;  z *= 0x94D049BB133111EB;  z ^= z >> 31   (splitmix64)
+ *       u = (z >> 11) * 2^-53
+ *   (attempt 0 .. 63, n <= 125.)  graphik_amd.solvers.riemannian_solver.retry_seeds_host returns the same bits.
+ * gik_retry_merge: for compact slot r (one wavefront each), goal g = d_idx[r] (entries distinct): if the retry's
+ *   answer is better than the incumbent's, the Y row, the gik_stats record, the q row, pos_err and rot_err of goal g
+ *   are replaced together and d_attempt[g] = attempt; otherwise nothing of goal g is written.
+ * gik_ik_batch_retry: attempt 0 is exactly gik_ik_batch (d_q_init NULL) or gik_ik_batch_seeded on the caller's
+ *   buffers, preceded by a memset of d_attempt [B] to 0; with retries = 0 the call queues exactly that and nothing
+ *   else.  Then for a = 1 .. retries: select -> the 4-byte count is copied to the host -> stop if it is 0 -> seeds ->
+ *   gik_seed_batch, gik_solve_batch, gik_recover_batch on the compact buffers in d_ws with B' = count -> merge.
+ *   THIS CALL SYNCHRONISES ITS STREAM (hipStreamSynchronize) ONCE PER ATTEMPT after the first: the solve kernels take
+ *   their batch size from the host.  The last merge is queued like every other batch call: synchronise the stream
+ *   before reading the results.
+ *   What comes back: d_attempt[g] = the attempt whose answer goal g holds (0: the first).  A 3-D problem's bits do not
+ *   depend on the batch it is solved in (see the note on the handle), so a goal with d_attempt[g] = a > 0 holds exactly
+ *   what gik_ik_batch_seeded returns for that goal alone from the seed of (seed, g, a); planar graphs' last bits may
+ *   depend on the batch size, as everywhere.
+ *   d_ws: caller-owned, gik_retry_ws_bytes(t, B) bytes (sized for the case that every goal fails), 8-byte aligned.
+ *   Refused, with a message, before anything is queued: a capturing stream; a template without a pipeline; retries
+ *   outside 0 .. 63; and with retries > 0 a graph gik_seed_batch cannot seed (its reason is passed on), null limits,
+ *   a tolerance that is not positive, a null workspace.                                                       */
+typedef struct {
+  int32_t retries;        /* further attempts for goals that failed: 0 .. 63                              */
+  int32_t reserved0;
+  uint64_t seed;          /* of the generator; the same seed gives the same answers                       */
+  double pos_tol;         /* a goal succeeds with stop == 0, pos_err <= pos_tol and rot_err <= rot_tol    */
+  double rot_tol;
+  const double *d_q_lo;   /* [n] device: the seeds are drawn uniformly in [q_lo[j], q_hi[j]]              */
+  const double *d_q_hi;   /* [n] device                                                                   */
+} gik_retry_opts;
+
+int gik_retry_select(const gik_stats *d_stats, const double *d_pos_err, const double *d_rot_err, int B,
+                     double pos_tol, double rot_tol, int32_t *d_idx, int32_t *d_count, void *stream);
+int gik_retry_seeds(const gik_template *t, const double *d_T_goal, const int32_t *d_idx, int count, uint64_t seed,
+                    int attempt, const double *d_q_lo, const double *d_q_hi, double *d_T_out, double *d_q_out,
+                    void *stream);
+int gik_retry_merge(const gik_template *t, const int32_t *d_idx, int count, int attempt, double pos_tol,
+                    double rot_tol, const double *d_Y_r, const gik_stats *d_stats_r, const double *d_q_r,
+                    const double *d_pos_err_r, const double *d_rot_err_r, double *d_Y, gik_stats *d_stats,
+                    double *d_q, double *d_pos_err, double *d_rot_err, int32_t *d_attempt, void *stream);
+size_t gik_retry_ws_bytes(const gik_template *t, int B);
+int gik_ik_batch_retry(const gik_template *t, const double *d_T_goal, const double *d_q_init /* may be NULL */,
+                       int B, const gik_retry_opts *opts, void *d_ws, double *d_targets, double *d_Y,
+                       gik_stats *d_stats, double *d_q, double *d_pos_err, double *d_rot_err,
+                       int32_t *d_attempt, void *stream);
 
 /* ---- fixed-anchor formulation: "intended" obstacle semantics (opt-in) -----------------------
  * graph_base.py:182-211 ties every node with a known position (base frame, goal nodes, obstacle
