@@ -5,10 +5,14 @@
 #include "gik_kernels.hip.h"
 #include "gik_instances.h"
 #include "gik_retry.hip.h"
+#include "gik_plan.h"
+#include "gik_slots.h"
 #include <memory>
 
 namespace gik {
 GIK_ALL_KERNELS(GIK_EXTERN_TEMPLATE)
+static_assert(PLAN_MIG_SIMDS == MIG_SIMDS && PLAN_SLICE_STATE_BYTES == sizeof(SliceState) && PLAN_QUAD_SLOTS == QUAD_SLOTS,
+              "gik_plan.h restates these constants of the kernel headers");
 
 // the compiled node-per-lane variants
 struct NptVariant {
@@ -110,7 +114,8 @@ static const WaveRow *find_row(int K, Form form, int slots) {
 }  // namespace gik
 
 struct gik_template {
-  int N, K, T, maxdeg;
+  int N, T, maxdeg;
+  gik::SolveFacts f;   // what the launch plan of a batch call reads (gik_plan.h); complete at the end of creation
   // fixed-anchor formulation (gik_template_create_anchored)
   bool anchored = false;
   hipEvent_t ev_solve0 = nullptr, ev_solve1 = nullptr;   // around the solve kernel of the last gik_anchored_ik_batch
@@ -164,33 +169,18 @@ struct gik_template {
   unsigned next_slice = 0;
   int slice_pool = kSlicePool;   // slots in use (GIK_SLICE_POOL at creation: tests shrink it to force reuse)
   int device;
-  int n_cu;
-  // scheduling knobs, fixed at creation (descriptor fields, overridden once by the environment)
-  int dbg;            // SolveArgs::dbg
-  int wpc_override;   // persistent waves per CU, 0 = automatic
-  int slice_its;      // time slice of the block kernel in outer iterations, 0 = off
-  int npt_slice_its = 192;   // ... of the node-per-lane kernel
-  int wave_slice_its; // round-robin slice of the wavefront kernel (large batches), 0 = off
-  bool wave_slice_auto = true;   // ... scaled with the queue depth (gik_solve_batch)
-  int wave_slice_cycles = 2000000;   // ... and its shortest duration (GIK_SLICE_CYCLES)
-  int waves_per_cu;  // resident solve wavefronts per CU (from the occupancy query)
   size_t smem_bytes;
-  bool is_block;  // workgroup-per-problem path
   int SL;         // slots per thread on the block path
   gik::BlockTabs bt = {nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, 0, 0};
   // node-per-lane path (rtr_npt_kernel): trust-region solves and the known-answer entry points of
   // 3-D graphs beyond one wavefront's 64 unknowns; the workgroup tables above stay (ConjugateGradient)
-  bool is_npt = false;
   gik::NptTabs nt = {};
   const gik::NptVariant *npt_variant = nullptr;
   size_t npt_smem = 0;
-  int npt_waves_per_cu = 1;
   // four-problems-per-wavefront path (rtr_quad_kernel): trust-region solves of planar graphs with at most
   // 16 nodes and 6 terms per node; everything else of such a template stays on the wavefront kernels
   void (*quad_solve)(gik::SolveArgs) = nullptr;
   size_t quad_smem = 0;
-  int quad_waves_per_cu = 8;
-  int quad_min_batch = -1;     // smallest batch that runs it (GIK_QUAD_MIN_BATCH; else 12 problems per CU, set with quad_solve)
   bool no_npt = false, no_quad = false;   // GIK_NO_NPT / GIK_NO_QUAD: creation leaves these kernels out
   // device pre/post-processing (gik_pipeline_attach)
   bool has_pipe = false;
@@ -250,6 +240,11 @@ static bool capturing_stream(void *stream) {
   }
   return st != hipStreamCaptureStatusNone;
 }
+// the refusal of an entry point whose bookkeeping (events, workspaces, counters) cannot happen under capture
+static int refuse_capture(const char *entry, void *stream) {
+  if (!capturing_stream(stream)) return 0;
+  return gik::fail(std::string(entry) + ": the stream is capturing (hipStreamBeginCapture); batch calls cannot be captured into a graph");
+}
 
 template <typename T>
 static const T *upload(gik_template *t, const T *host, size_t count, bool &ok) {
@@ -302,7 +297,7 @@ static int validate_desc(const gik_template_desc *d, const gik_anchored_desc *ad
 // once, here, never inside a batch call
 static void read_params(gik_template *t, const gik_template_desc *d) {
   t->N = d->N;
-  t->K = d->k;
+  t->f.K = d->k;
   t->T = d->n_terms;
   t->p.mingradnorm = d->mingradnorm;
   t->p.theta = d->theta;
@@ -320,31 +315,31 @@ static void read_params(gik_template *t, const gik_template_desc *d) {
   t->cg.maxiter = d->maxiter;
   t->cg.beta_type = d->cg_beta_type;
   t->cg.planar_proj_exact = d->planar_proj_exact;
-  t->dbg = d->debug_flags;
-  if (const char *e = getenv("GIK_DBG")) t->dbg = atoi(e);
-  t->wpc_override = std::max(0, d->waves_per_cu);
-  if (const char *e = getenv("GIK_WAVES_PER_CU")) t->wpc_override = std::max(1, atoi(e));
+  t->f.dbg = d->debug_flags;
+  if (const char *e = getenv("GIK_DBG")) t->f.dbg = atoi(e);
+  t->f.wpc_override = std::max(0, d->waves_per_cu);
+  if (const char *e = getenv("GIK_WAVES_PER_CU")) t->f.wpc_override = std::max(1, atoi(e));
   // workgroup kernel, table scene, 4096 goals (round 3): slice 96 / 160 / 256 -> 1430 / 1430 / 1409 solves/s and
   // 755 / 586 / 368 MB of HBM traffic per launch (every resumed slice re-reads the problem's 45 KB of
   // targets; 207 MB are the algorithmic bytes).  Without slicing: ~15 % slower (round 2: 795 vs 929).
-  t->slice_its = d->slice_outer_its < 0 ? 256 : d->slice_outer_its;
+  t->f.slice_its = d->slice_outer_its < 0 ? 256 : d->slice_outer_its;
   // node-per-lane kernel, table scene, 4096 goals (round 4): slice 0 / 48 / 96 / 256 / 600 -> 1689 / 1896 / 1894 / 1861 /
   // 1774 solves/s (two problems per CU: 512 slots, a third of the requeues of the workgroup kernel)
   // HBM traffic per launch (PMC): 603 MB at 128 = 2.9 x the algorithmic 207 MB (every resume re-reads the problem's 45 KB of
   // clique targets); 192 is the compromise
-  t->npt_slice_its = d->slice_outer_its < 0 ? 192 : d->slice_outer_its;
+  t->f.npt_slice_its = d->slice_outer_its < 0 ? 192 : d->slice_outer_its;
   // wavefront kernel: 256 ... 32 iterations per slice give the same time (NOTEBOOK 8.3); the longest of
   // them moves the fewest problems through HBM (KUKA 65536: 118 k hand-overs of ~1.5 KB instead of 562 k at 64)
-  t->wave_slice_its = d->slice_outer_its < 0 ? 256 : d->slice_outer_its;
-  t->wave_slice_auto = d->slice_outer_its < 0 && !getenv("GIK_SLICE");   // (an explicit length is taken literally)
-  if (const char *e = getenv("GIK_SLICE")) t->slice_its = t->npt_slice_its = t->wave_slice_its = std::max(0, atoi(e));
-  if (const char *e = getenv("GIK_SLICE_CYCLES")) t->wave_slice_cycles = std::max(0, atoi(e));
+  t->f.wave_slice_its = d->slice_outer_its < 0 ? 256 : d->slice_outer_its;
+  t->f.wave_slice_auto = d->slice_outer_its < 0 && !getenv("GIK_SLICE");   // (an explicit length is taken literally)
+  if (const char *e = getenv("GIK_SLICE")) t->f.slice_its = t->f.npt_slice_its = t->f.wave_slice_its = std::max(0, atoi(e));
+  if (const char *e = getenv("GIK_SLICE_CYCLES")) t->f.wave_slice_cycles = std::max(0, atoi(e));
   t->counter_slot.resize(kCounterRing);
   if (const char *e = getenv("GIK_COUNTER_RING")) t->counter_ring = std::min(kCounterRing, std::max(1, atoi(e)));
   if (const char *e = getenv("GIK_SLICE_POOL")) t->slice_pool = std::min(gik_template::kSlicePool, std::max(1, atoi(e)));
   t->no_npt = getenv("GIK_NO_NPT") != nullptr;      // (developer A/B switches)
   t->no_quad = getenv("GIK_NO_QUAD") != nullptr;
-  if (const char *e = getenv("GIK_QUAD_MIN_BATCH")) t->quad_min_batch = std::max(0, atoi(e));
+  if (const char *e = getenv("GIK_QUAD_MIN_BATCH")) t->f.quad_min_batch = std::max(0, atoi(e));
 }
 
 struct Ent { int j, kind, term, owner; };
@@ -698,7 +693,7 @@ static NptHost npt_tables(const gik_template_desc *d, const CliqueRows &c, bool 
 static int resolve_kernels(gik_template *t, const gik_template_desc *d, const WaveRow *row, size_t block_lds) {
   const bool cg = d->solver == GIK_SOLVER_CONJUGATE_GRADIENT, k3 = d->k == 3, theta1 = d->theta == 1.0;
   gik_template::Kernels &kn = t->kernels;
-  if (t->is_block) {
+  if (t->f.is_block) {
     kn.block_solve = cg ? (k3 ? rcg_block_kernel<3> : rcg_block_kernel<2>) : (k3 ? rtr_block_kernel<3> : rtr_block_kernel<2>);
     kn.block_kat = k3 ? kat_block_kernel<3> : kat_block_kernel<2>;
     kn.occupancy = (const void *)kn.block_solve;
@@ -728,7 +723,7 @@ static int resolve_kernels(gik_template *t, const gik_template_desc *d, const Wa
 
 // device, slot table, work-queue heads, occupancy; `occ`: the unclamped answer of the occupancy query
 static int device_setup(gik_template *t, const gik_template_desc *d, const std::vector<uint32_t> &meta, int &occ) {
-  if (t->is_block && t->smem_bytes > 48 * 1024) {
+  if (t->f.is_block && t->smem_bytes > 48 * 1024) {
     // more than the default dynamic-LDS allowance: opt in for exactly what this template needs
     for (const void *fn : {t->kernels.occupancy, (const void *)t->kernels.block_kat})
       if (raise_dynamic_lds(fn, t->smem_bytes) != hipSuccess) {
@@ -743,19 +738,19 @@ static int device_setup(gik_template *t, const gik_template_desc *d, const std::
       hipMalloc((void **)&t->d_counters, kCounterRing * sizeof(unsigned int)) != hipSuccess ||
       hipMemcpy(t->d_slot_meta, meta.data(), meta.size() * sizeof(uint32_t),
                 hipMemcpyHostToDevice) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, t->kernels.occupancy, t->is_block ? BLOCK_NT : WAVE,
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, t->kernels.occupancy, t->f.is_block ? BLOCK_NT : WAVE,
                                                    t->smem_bytes) != hipSuccess)
     return fail("HIP device setup failed (no GPU?)");
-  t->n_cu = prop.multiProcessorCount;
-  t->waves_per_cu = std::max(1, std::min(occ, 32));
-  if (!t->is_block && !t->anchored && t->solver == GIK_SOLVER_TRUST_REGIONS && t->K == 2 && t->N <= QUAD_NODES &&
+  t->f.n_cu = prop.multiProcessorCount;
+  t->f.waves_per_cu = std::max(1, std::min(occ, 32));
+  if (!t->f.is_block && !t->anchored && t->solver == GIK_SOLVER_TRUST_REGIONS && t->f.K == 2 && t->N <= QUAD_NODES &&
       t->maxdeg == 6 && d->theta == 1.0 && !(d->debug_flags & 8192) && !t->no_quad) {
     t->quad_solve = rtr_quad_kernel<6>;
     t->quad_smem = QuadCtx<6>::lds_bytes();
     int qocc = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&qocc, (const void *)t->quad_solve, WAVE, t->quad_smem) == hipSuccess)
-      t->quad_waves_per_cu = std::max(1, std::min(qocc, 32));
-    if (t->quad_min_batch < 0) t->quad_min_batch = 12 * t->n_cu;
+      t->f.quad_waves_per_cu = std::max(1, std::min(qocc, 32));
+    if (t->f.quad_min_batch < 0) t->f.quad_min_batch = 12 * t->f.n_cu;
   }
   return 0;
 }
@@ -831,8 +826,8 @@ static int setup_npt(gik_template *t, const gik_template_desc *d, const NptHost 
     (void)hipGetLastError();
     return d->force_block_path == 2 ? fail("node-per-lane kernel: device setup failed (LDS)") : 0;
   }
-  t->is_npt = true;
-  t->npt_waves_per_cu = std::max(1, std::min(occ_npt, 4));   // problems (workgroups) per CU
+  t->f.is_npt = true;
+  t->f.npt_waves_per_cu = std::max(1, std::min(occ_npt, 4));   // problems (workgroups) per CU
   return 0;
 }
 
@@ -863,30 +858,30 @@ static int create_impl(const gik_template_desc *d, const gik_anchored_desc *ad, 
   const bool big = d->N > BLOCK_MAXN;
   const WaveRow *row = nullptr;
   if (d->N * d->k <= WAVE && d->N <= 32 && !d->force_block_path) row = find_row(d->k, ad ? ANCHORED : COLUMN, maxdeg);
-  t->is_block = !row;      // (also: a node busier than any wave variant)
-  if (t->is_block && ad) return fail("anchored templates need N * k <= 64 free unknowns and at most 20 terms per node");
-  const bool npt_wanted = t->is_block && d->k == 3 && d->solver == GIK_SOLVER_TRUST_REGIONS && d->theta == 1.0 && !ad &&
+  t->f.is_block = !row;      // (also: a node busier than any wave variant)
+  if (t->f.is_block && ad) return fail("anchored templates need N * k <= 64 free unknowns and at most 20 terms per node");
+  const bool npt_wanted = t->f.is_block && d->k == 3 && d->solver == GIK_SOLVER_TRUST_REGIONS && d->theta == 1.0 && !ad &&
                           (d->force_block_path == 2 || (d->force_block_path == 0 && d->N * d->k > WAVE && !t->no_npt));
-  const bool npt_two_waves = big || !(t->dbg & 2048);      // 2048: one wavefront per problem, two nodes per lane
+  const bool npt_two_waves = big || !(t->f.dbg & 2048);      // 2048: one wavefront per problem, two nodes per lane
   const int npt_NW = big ? 4 : (npt_two_waves ? 2 : 1);    // wavefronts per problem ("two_waves": one node per lane)
   CliqueRows clq;
   BlockHost bh;      // (the workgroup tables stay next to the node-per-lane ones: ConjugateGradient, known answers)
   NptHost npt;
-  if (t->is_block) {
-    clq = clique_rows(d, t->dbg, big ? 256 : BLOCK_MAXN);      // rows of the host-side tables (the workgroup kernels' are 128)
+  if (t->f.is_block) {
+    clq = clique_rows(d, t->f.dbg, big ? 256 : BLOCK_MAXN);      // rows of the host-side tables (the workgroup kernels' are 128)
     if (!big) bh = block_tables(d->N, d->n_terms, clq);
     if (npt_wanted) npt = npt_tables(d, clq, npt_two_waves, npt_NW, big ? 4 * WAVE : NPT_MAXN);
   } else {
     bh.meta = wave_slot_table(d, ents, row->slots);
   }
   t->SL = bh.SL;
-  t->maxdeg = t->is_block ? bh.SL : row->slots;
+  t->maxdeg = t->f.is_block ? bh.SL : row->slots;
   const int Tc = (int)clq.nc_term.size(), n_pairs = (int)bh.clq_pair_term.size();
-  const size_t block_lds = !t->is_block ? 0 : d->k == 3 ? BlockCtx<3>::lds_bytes(Tc, bh.SL, n_pairs, clq.n_clq) : BlockCtx<2>::lds_bytes(Tc, bh.SL);
+  const size_t block_lds = !t->f.is_block ? 0 : d->k == 3 ? BlockCtx<3>::lds_bytes(Tc, bh.SL, n_pairs, clq.n_clq) : BlockCtx<2>::lds_bytes(Tc, bh.SL);
   int occ = 0;
   if (resolve_kernels(t.get(), d, row, block_lds) || device_setup(t.get(), d, bh.meta, occ)) return -1;
   if (ad && upload_anchored(t.get(), ad)) return -1;
-  if (t->is_block) {
+  if (t->f.is_block) {
     bool ok = true;
     t->bt.nc_term = upload(t.get(), clq.nc_term.data(), clq.nc_term.size(), ok);
     t->bt.clq_term = upload(t.get(), bh.clq_term.data(), bh.clq_term.size(), ok);
@@ -897,31 +892,37 @@ static int create_impl(const gik_template_desc *d, const gik_anchored_desc *ad, 
     t->bt.wave_sl = upload(t.get(), bh.wave_sl.data(), bh.wave_sl.size(), ok);
     t->bt.Tc = Tc;
     t->bt.n_clq = clq.n_clq;
-    t->bt.clq_euclid = (clq.n_clq && !(t->dbg & 256) && d->clique_closed_form != GIK_CLIQUE_DENSE) ? 1 : 0;   // 256: always the dense D w product
+    t->bt.clq_euclid = (clq.n_clq && !(t->f.dbg & 256) && d->clique_closed_form != GIK_CLIQUE_DENSE) ? 1 : 0;   // 256: always the dense D w product
     t->clique_mode = !clq.n_clq ? GIK_CLIQUE_OFF : (t->bt.clq_euclid ? GIK_CLIQUE_AUTO : GIK_CLIQUE_DENSE);
     if (!ok) return fail("device upload of the workgroup-path tables failed");
   }
   if (d->force_block_path == 2 && !npt.ok)
     return fail("node-per-lane kernel: k = 3, TrustRegions, theta = 1, at most 256 terms outside the rigid clique, at most 16 per lane");
   if (npt.ok && setup_npt(t.get(), d, npt, npt_NW)) return -1;
-  if (big && !t->is_npt)
+  if (big && !t->f.is_npt)
     return fail("graphs of more than 128 nodes need the node-per-lane kernel: at most 256 terms outside the rigid clique "
                 "(16 per node), at most 127 nodes that carry such terms");
-  if ((t->dbg & 32) && t->is_npt)
+  if ((t->f.dbg & 32) && t->f.is_npt)
     fprintf(stderr, "  node-per-lane kernel: %d wavefront(s) per problem, TL=%d, %d slot terms (sync %d), %d direction rows, gather lists %d + %d, "
             "clique rows from %d, lds=%zu B, %d problems per CU\n",
             t->npt_variant->NW, t->nt.TL, t->nt.n_terms, t->nt.term_sync, t->nt.n_wrows, t->nt.DEG0, t->nt.DEG1, t->nt.cbase,
-            t->npt_smem, t->npt_waves_per_cu);
-  if (t->dbg & 32)
+            t->npt_smem, t->f.npt_waves_per_cu);
+  if (t->f.dbg & 32)
       fprintf(stderr, "gik_template_create: N=%d k=%d T=%d %s maxdeg=%d lds=%zu B occupancy=%d per CU, %d CUs; "
               "clique %d, slot terms %d, slots %d\n",
-              t->N, t->K, t->T, t->is_block ? "block" : "wave", t->is_block ? 0 : t->maxdeg,
-              t->smem_bytes, occ, t->n_cu, clq.n_clq, t->is_block ? Tc : t->T, t->SL);
-  if ((t->dbg & 32) && t->is_block) {
+              t->N, t->f.K, t->T, t->f.is_block ? "block" : "wave", t->f.is_block ? 0 : t->maxdeg,
+              t->smem_bytes, occ, t->f.n_cu, clq.n_clq, t->f.is_block ? Tc : t->T, t->SL);
+  if ((t->f.dbg & 32) && t->f.is_block) {
     fprintf(stderr, "  slot loop bounds per wavefront {equalities, all}:");
     for (int w = 0; w < BLOCK_WAVES; ++w) fprintf(stderr, " {%d, %d}", bh.wave_sl[2 * w], bh.wave_sl[2 * w + 1]);
     fprintf(stderr, "\n");
   }
+  // the rest of what a batch call's plan reads, now that kernels, parameters and tables are settled
+  t->f.cg = t->solver == GIK_SOLVER_CONJUGATE_GRADIENT;
+  t->f.maxiter = t->p.maxiter;
+  t->f.has_spread = t->kernels.solve_spread != nullptr;
+  t->f.has_quad = t->quad_solve != nullptr;
+  t->f.ctg_doubles = t->f.is_npt ? t->npt_variant->ctg(t->nt.n_pairs) : 0;
   *out = t.release();
   return 0;
 }
@@ -1000,7 +1001,7 @@ void gik_template_destroy(gik_template *t) {
 // their POS: anchor_pos).  Returns false only when an upload fails; a graph the recipe does not cover leaves
 // seed_ok false.
 static bool seed_tables(gik_template *t, const gik_pipeline_desc *d, const std::vector<int> &path, int n_ee) {
-  const int N = t->N, K = t->K, D = K + 1, DD = D * D, n = d->n_joints;
+  const int N = t->N, K = t->f.K, D = K + 1, DD = D * D, n = d->n_joints;
   std::vector<int> parent(n + 1, -2), order;
   for (int e = 0; e < n_ee; ++e)
     for (int k = 0; k <= n; ++k) {
@@ -1079,7 +1080,7 @@ int gik_pipeline_attach(gik_template *t, const gik_pipeline_desc *d) {
   using namespace gik;
   if (!t || !d) return fail("null argument");
   if (t->has_pipe) return fail("pipeline already attached");
-  const int N = t->N, K = t->K, n = d->n_joints;
+  const int N = t->N, K = t->f.K, n = d->n_joints;
   if (n < 1 || n > 125) return fail("n_joints out of range (1 .. 125)");
   if (d->n_anchor < 1 || d->n_anchor > PREP_MAXA) return fail("n_anchor must be in [1, 256]");
   if (N > PREP_BIGN - 1 || (N > PREP_MAXN && K != 3))
@@ -1182,7 +1183,7 @@ int gik_pipeline_attach(gik_template *t, const gik_pipeline_desc *d) {
     occ = std::max(1, std::min(occ, 2));   // 5 N^2 doubles per workgroup: keep the slabs cache-resident
     if (const char *e = getenv("GIK_PREP_WAVES_PER_CU")) occ = std::max(1, atoi(e));
     t->prep_waves_per_cu = occ;
-    const size_t bytes = sizeof(double) * (t->prep_big ? 6 : 5) * (size_t)N * N * (size_t)t->n_cu * occ;
+    const size_t bytes = sizeof(double) * (t->prep_big ? 6 : 5) * (size_t)N * N * (size_t)t->f.n_cu * occ;
     void *ws = nullptr;
     if (hipMalloc(&ws, bytes) != hipSuccess) return fail("cannot allocate the prepare workspace");
     t->pipe_allocs.push_back(ws);
@@ -1231,8 +1232,7 @@ int gik_prepare_batch_debug(const gik_template *t, const double *d_T_goal, int B
   if (!t->has_pipe) return fail("no pipeline attached (gik_pipeline_attach)");
   if (B == 0) return 0;
   if (!d_T_goal || !d_targets || !d_Y_init) return fail("null buffer");
-  if (t->prep_block && capturing_stream(stream))      // (the workgroup variant chains its launches by an event)
-    return fail("gik_prepare_batch: the stream is capturing (hipStreamBeginCapture); batch calls cannot be captured into a graph");
+  if (t->prep_block && refuse_capture("gik_prepare_batch", stream)) return -1;      // (the workgroup variant chains its launches by an event)
   PrepArgs a;
   a.pc = t->pc;
   a.T_goal = d_T_goal;
@@ -1250,7 +1250,7 @@ int gik_prepare_batch_debug(const gik_template *t, const double *d_T_goal, int B
 #ifdef GIK_DEV
   if (const char *e = getenv("GIK_PREP_STOP")) a.stop_phase = atoi(e);   // developer build: timing of the phases
 #endif
-  const int grid = std::min(B, t->n_cu * t->prep_waves_per_cu);
+  const int grid = std::min(B, t->f.n_cu * t->prep_waves_per_cu);
   if (t->prep_block) {
     gik_template *mt = const_cast<gik_template *>(t);   // the workspace hand-over is the mutable part
     std::lock_guard<std::mutex> lock(mt->prep_mutex);
@@ -1268,7 +1268,7 @@ int gik_prepare_batch_debug(const gik_template *t, const double *d_T_goal, int B
     mt->prep_pending = true;
   } else if (t->prep_quad && !a.dbg_lb && !a.dbg_eig) {
     // (the diagnostics -- bounds and spectra of gik_prepare_batch_debug -- come from the one-goal-per-wavefront kernel)
-    const int qgrid = std::min((B + QUAD_SLOTS - 1) / QUAD_SLOTS, t->n_cu * t->prep_quad_waves_per_cu);
+    const int qgrid = std::min((B + QUAD_SLOTS - 1) / QUAD_SLOTS, t->f.n_cu * t->prep_quad_waves_per_cu);
     hipLaunchKernelGGL(t->N == 13 ? prep_quad_kernel<13> : prep_quad_kernel<0>, dim3(qgrid), dim3(WAVE), t->prep_quad_smem,
                        (hipStream_t)stream, a);
   } else
@@ -1325,7 +1325,7 @@ int gik_seed_batch(const gik_template *t, const double *d_T_goal, const double *
   a.targets = d_targets;
   a.Y_init = d_Y_init;
   a.B = B;
-  const int grid = std::min(B, t->n_cu * 8);
+  const int grid = std::min(B, t->f.n_cu * 8);
   hipLaunchKernelGGL(seed_kernel, dim3(grid), dim3(WAVE), t->seed_smem, (hipStream_t)stream, a);
   HIP_OK(hipGetLastError());
   return 0;
@@ -1341,8 +1341,7 @@ int gik_ik_batch_seeded(const gik_template *t, const double *d_T_goal, const dou
   if (!d_q_init) return fail("gik_ik_batch_seeded: null d_q_init (seed joint angles [B][n] are required)");
   if (!d_T_goal || !d_targets || !d_Y || !d_stats || !d_q || !d_pos_err || !d_rot_err) return fail("null buffer");
   // refused before the seed kernel is queued, so that a capture is left without half a call in it
-  if (capturing_stream(stream))
-    return fail("gik_ik_batch_seeded: the stream is capturing (hipStreamBeginCapture); batch calls cannot be captured into a graph");
+  if (refuse_capture("gik_ik_batch_seeded", stream)) return -1;
   int rc = gik_seed_batch(t, d_T_goal, d_q_init, B, d_targets, d_Y, stream);
   if (rc) return rc;
   rc = gik_solve_batch(t, d_Y, d_targets, B, d_Y, d_stats, nullptr, stream);
@@ -1374,7 +1373,7 @@ int gik_retry_select(const gik_stats *d_stats, const double *d_pos_err, const do
   return 0;
 }
 
-static int retry_grid(const gik_template *t, int count) { return std::min(count, t->n_cu * 8); }
+static int retry_grid(const gik_template *t, int count) { return std::min(count, t->f.n_cu * 8); }
 
 int gik_retry_seeds(const gik_template *t, const double *d_T_goal, const int32_t *d_idx, int count, uint64_t seed,
                     int attempt, const double *d_q_lo, const double *d_q_hi, double *d_T_out, double *d_q_out,
@@ -1395,7 +1394,7 @@ int gik_retry_seeds(const gik_template *t, const double *d_T_goal, const int32_t
   a.q_out = d_q_out;
   a.seed = seed;
   a.count = count;
-  a.pose_w = t->pc.n_ee * (t->K + 1) * (t->K + 1);
+  a.pose_w = t->pc.n_ee * (t->f.K + 1) * (t->f.K + 1);
   a.n = t->pc.n_joints;
   a.attempt = attempt;
   hipLaunchKernelGGL(retry_seed_kernel, dim3(retry_grid(t, count)), dim3(RETRY_WAVE), 0, (hipStream_t)stream, a);
@@ -1430,7 +1429,7 @@ int gik_retry_merge(const gik_template *t, const int32_t *d_idx, int count, int 
   a.pos_tol = pos_tol;
   a.rot_tol = rot_tol;
   a.count = count;
-  a.row = t->N * t->K;
+  a.row = t->N * t->f.K;
   a.n = t->pc.n_joints;
   a.attempt_no = attempt;
   hipLaunchKernelGGL(retry_merge_kernel, dim3(retry_grid(t, count)), dim3(RETRY_WAVE), 0, (hipStream_t)stream, a);
@@ -1448,7 +1447,7 @@ struct RetryWs {
   size_t bytes;
 };
 static RetryWs retry_ws(const gik_template *t, int B, void *base) {
-  const size_t b = (size_t)B, n = (size_t)t->pc.n_joints, pose_w = (size_t)t->pc.n_ee * (t->K + 1) * (t->K + 1);
+  const size_t b = (size_t)B, n = (size_t)t->pc.n_joints, pose_w = (size_t)t->pc.n_ee * (t->f.K + 1) * (t->f.K + 1);
   const uintptr_t p = reinterpret_cast<uintptr_t>(base);      // (null: gik_retry_ws_bytes only wants the size)
   size_t off = 0;
   auto take = [&](size_t bytes) {
@@ -1462,7 +1461,7 @@ static RetryWs retry_ws(const gik_template *t, int B, void *base) {
   w.T = reinterpret_cast<double *>(take(b * pose_w * sizeof(double)));
   w.q_seed = reinterpret_cast<double *>(take(b * n * sizeof(double)));
   w.targets = reinterpret_cast<double *>(take(b * (size_t)t->T * sizeof(double)));
-  w.Y = reinterpret_cast<double *>(take(b * (size_t)t->N * t->K * sizeof(double)));
+  w.Y = reinterpret_cast<double *>(take(b * (size_t)t->N * t->f.K * sizeof(double)));
   w.stats = reinterpret_cast<gik_stats *>(take(b * sizeof(gik_stats)));
   w.q = reinterpret_cast<double *>(take(b * n * sizeof(double)));
   w.pos_err = reinterpret_cast<double *>(take(b * sizeof(double)));
@@ -1493,8 +1492,7 @@ int gik_ik_batch_retry(const gik_template *t, const double *d_T_goal, const doub
     if (!d_ws && B > 0) return fail("gik_ik_batch_retry: null workspace (gik_retry_ws_bytes)");
     if ((uintptr_t)d_ws % 8) return fail("gik_ik_batch_retry: the workspace must be 8-byte aligned");
   }
-  if (capturing_stream(stream))
-    return fail("gik_ik_batch_retry: the stream is capturing (hipStreamBeginCapture); batch calls cannot be captured into a graph");
+  if (refuse_capture("gik_ik_batch_retry", stream)) return -1;
   if (B == 0) return 0;
   if (!d_T_goal || !d_targets || !d_Y || !d_stats || !d_q || !d_pos_err || !d_rot_err || !d_attempt) return fail("null buffer");
   hipStream_t s = (hipStream_t)stream;
@@ -1537,7 +1535,7 @@ int gik_anchored_ik_batch(const gik_template *anch, const gik_template *base, co
                           double *d_pos_err, double *d_rot_err, void *stream) {
   using namespace gik;
   if (!anch || !base || !anch->anchored || B < 0) return fail("bad argument");
-  if (!base->has_pipe || base->K != 3 || base->N != anch->full_N)
+  if (!base->has_pipe || base->f.K != 3 || base->N != anch->full_N)
     return fail("the base template must be the robot graph (full_N nodes) with its pipeline attached");
   if (B == 0) return 0;
   if (!d_T_goal || !d_ws || !d_Y_full || !d_stats || !d_q || !d_pos_err || !d_rot_err) return fail("null buffer");
@@ -1623,7 +1621,7 @@ static int launch_kat(const gik_template *t, int mode, const double *d_Y, const 
   a.mode = mode;
   a.planar_proj_exact = t->p.planar_proj_exact;
   if (t->anchored && mode == 3) {          // the anchors fix the gauge: proj is the identity
-    HIP_OK(hipMemcpyAsync(d_out, d_W, sizeof(double) * (size_t)B * t->N * t->K, hipMemcpyDeviceToDevice,
+    HIP_OK(hipMemcpyAsync(d_out, d_W, sizeof(double) * (size_t)B * t->N * t->f.K, hipMemcpyDeviceToDevice,
                           (hipStream_t)stream));
     return 0;
   }
@@ -1632,20 +1630,20 @@ static int launch_kat(const gik_template *t, int mode, const double *d_Y, const 
     a.an.anchor_goal = d_targets;          // (anchored templates: the per-problem input is the goal anchors)
     a.targets = t->d_targets_const;
   }
-  if (t->quad_solve && (t->dbg & 16384) && !(t->dbg & (1 | 8192))) {
+  if (t->quad_solve && (t->f.dbg & 16384) && !(t->f.dbg & (1 | 8192))) {
     hipLaunchKernelGGL(kat_quad_kernel<6>, dim3((B + QUAD_SLOTS - 1) / QUAD_SLOTS), dim3(WAVE), t->quad_smem,
                        (hipStream_t)stream, a);
-  } else if (t->is_npt) {
+  } else if (t->f.is_npt) {
     a.nt = t->nt;
     // (graphs beyond 128 nodes: a stream-ordered scratch for the clique target triangles of this call's workgroups;
     //  these one-call-at-a-time entry points are the known-answer interface, not the batch path)
-    const size_t ctg = t->npt_variant->ctg(t->nt.n_pairs) * sizeof(double) * (size_t)B;
+    const size_t ctg = t->f.ctg_doubles * sizeof(double) * (size_t)B;
     void *ws = nullptr;
     if (ctg) HIP_OK(hipMallocAsync(&ws, ctg, (hipStream_t)stream));
     a.npt_ctg_ws = static_cast<double *>(ws);
     hipLaunchKernelGGL(t->npt_variant->kat, dim3(B), dim3(WAVE * t->npt_variant->NW), t->npt_smem, (hipStream_t)stream, a);
     if (ws) HIP_OK(hipFreeAsync(ws, (hipStream_t)stream));
-  } else if (t->is_block) {
+  } else if (t->f.is_block) {
     hipLaunchKernelGGL(t->kernels.block_kat, dim3(B), dim3(BLOCK_NT), t->smem_bytes, (hipStream_t)stream, a, t->SL);
   } else {
     hipLaunchKernelGGL(t->kernels.kat, dim3(B), dim3(WAVE), t->smem_bytes, (hipStream_t)stream, a);
@@ -1681,14 +1679,22 @@ int gik_proj(const gik_template *t, const double *d_Y, const double *d_Z, int B,
   return launch_kat(t, 3, d_Y, d_Z, nullptr, B, d_out, stream);
 }
 
-int gik_solve_batch(const gik_template *t, const double *d_Y_init, const double *d_targets,
-                    int B, double *d_Y_out, gik_stats *d_stats, const gik_trace *trace,
-                    void *stream) {
-  using namespace gik;
-  if (!t || B < 0) return fail("bad argument");
-  if (B == 0) return 0;
-  if (!d_Y_init || !d_targets || !d_Y_out || !d_stats) return fail("null buffer");
-  SolveArgs a;
+// ---- one batch call, step by step (gik_solve_batch below) ----
+
+#ifdef GIK_DEV
+// the dump buffer of debug_flags 4 / 8 / 4096, zeroed for this call (gik_debug_fetch copies it to the host)
+static double *dev_debug_buffer() {
+  static double *buf = nullptr;
+  if (!buf) (void)hipMalloc((void **)&buf, (1 << 20) * sizeof(double));
+  (void)hipMemset(buf, 0, (1 << 20) * sizeof(double));
+  gik::g_dbg_buf = buf;
+  return buf;
+}
+#endif
+
+// everything of SolveArgs that does not depend on the plan; the queues start out absent
+static void fill_args(const gik_template *t, gik::SolveArgs &a, const double *d_Y_init, const double *d_targets, int B,
+                      double *d_Y_out, gik_stats *d_stats, const gik_trace *trace) {
   a.slot_meta = t->d_slot_meta;
   a.bt = t->bt;
   a.targets = d_targets;
@@ -1710,101 +1716,11 @@ int gik_solve_batch(const gik_template *t, const double *d_Y_init, const double 
     a.an.anchor_goal = d_targets;          // anchored templates: per-problem goal anchors [B][n_goal*3]
     a.targets = t->d_targets_const;
   }
-  a.dbg = t->dbg;
+  a.dbg = t->f.dbg;
   a.dbg_buf = nullptr;
 #ifdef GIK_DEV
-  if (a.dbg & (4 | 8 | 4096)) {
-    static double *buf = nullptr;
-    if (!buf) (void)hipMalloc((void **)&buf, (1 << 20) * sizeof(double));
-    (void)hipMemset(buf, 0, (1 << 20) * sizeof(double));
-    a.dbg_buf = buf;
-    g_dbg_buf = buf;
-  }
+  if (a.dbg & (4 | 8 | 4096)) a.dbg_buf = dev_debug_buffer();
 #endif
-  // The handle's mutable parts: the ring of work-queue heads and the time-slicing workspaces.  Both
-  // are handed out under call_mutex, held until the event that guards their reuse is recorded, so
-  // concurrent calls on one handle (any number of host threads and streams) are safe.
-  gik_template *mt = const_cast<gik_template *>(t);
-  // Hand-out of a slot: the one used last if the launch that used it has completed (hipEventQuery) -- a
-  // sequence of calls then keeps ONE workspace warm instead of growing all of the pool --, else the next one
-  // that no other call holds.  The lock covers the hand-out only: waiting for a slot's previous user, growing
-  // its workspace (hipEventSynchronize / hipFree / hipMalloc) and the launch happen outside it, on a slot
-  // marked in_use.
-  // Stream capture is refused: the slot protocol below queries, waits for and records events, grows workspaces
-  // (hipMalloc / hipFree) and resets a counter the kernel consumes -- none of which may happen under capture, and a
-  // replayed graph would reuse this call's counter slot and workspace behind the library's back.  A batch is ONE
-  // persistent launch; there is no launch overhead for a graph to remove.
-  if (capturing_stream(stream)) return fail("gik_solve_batch: the stream is capturing (hipStreamBeginCapture); batch calls cannot be captured into a graph");
-  auto take = [&](auto &slots, unsigned &next, unsigned n) -> int {
-    for (;;) {
-      {
-        std::lock_guard<std::mutex> lock(mt->call_mutex);
-        const unsigned last = (next + n - 1) % n;
-        auto &ls = slots[last];
-        if (!ls.in_use && ls.done && (!ls.pending || hipEventQuery(ls.done) == hipSuccess)) {
-          ls.pending = false;
-          ls.in_use = true;
-          return (int)last;
-        }
-        (void)hipGetLastError();      // (hipErrorNotReady of the query)
-        for (unsigned k = 0; k < n; ++k) {
-          const unsigned i = (next + k) % n;
-          if (!slots[i].in_use) {
-            slots[i].in_use = true;
-            next = (i + 1) % n;
-            return (int)i;
-          }
-        }
-      }
-      std::this_thread::yield();      // every slot is between hand-out and launch in some other thread
-    }
-  };
-  gik_template::CounterSlot &cs = mt->counter_slot[take(mt->counter_slot, mt->next_counter, (unsigned)t->counter_ring)];
-  struct Release {      // error paths hand the slots back too (no launch: nothing pending)
-    gik_template *mt;
-    gik_template::CounterSlot *cs;
-    gik_template::SliceWs *sw = nullptr;
-    bool launched = false;
-    ~Release() {
-      std::lock_guard<std::mutex> lock(mt->call_mutex);
-      cs->in_use = false;
-      if (launched) cs->pending = true;
-      if (sw) {
-        sw->in_use = false;
-        if (launched) sw->pending = true;
-      }
-    }
-  } release{mt, &cs};
-  a.work_counter = t->d_counters + (&cs - mt->counter_slot.data());
-  if (!cs.done && hipEventCreateWithFlags(&cs.done, hipEventDisableTiming) != hipSuccess)
-    return fail("hipEventCreate failed");
-  if (cs.pending) HIP_OK(hipStreamWaitEvent((hipStream_t)stream, cs.done, 0));   // ring wrapped: previous user first
-  HIP_OK(hipMemsetAsync(a.work_counter, 0, sizeof(unsigned int), (hipStream_t)stream));
-  // Persistent waves per CU: as many as fit (two per SIMD at 249 VGPRs).  Two waves share a SIMD's
-  // fp64 pipe and each runs 20-50 % slower than alone, which used to cost small batches -- whose
-  // time is that of their slowest problem -- more than the extra throughput returned; with the age
-  // priority of rtr_solve_one the old problems keep a lone wave's speed next to a young neighbour
-  // (kernel ms at 1 / 2 waves per SIMD without, and 2 per SIMD with priorities -- LWA4D B=4096:
-  // 116.9 / 132.4 / 116.3, B=16384: 190.6 / 196.7 / 187.7; KUKA B=8192: 182.8 / 156.4 / 155.4,
-  // B=65536: 755.7 / 545.5 / 544.2).
-  // Small batches still get one wave per SIMD: their time is the run time of the few problems that
-  // go to maxiter, and two of THOSE on one SIMD (equal priority) slow each other down -- at 4096
-  // LWA4D goals a third of the launches drew such a pair (128 instead of 116 ms).
-  int wpc = t->is_npt ? t->npt_waves_per_cu : t->waves_per_cu;
-  if (!t->is_block && t->K == 3 && wpc > 4 && (long long)B <= 6LL * 4 * t->n_cu) wpc = 4;
-  // THREE waves per SIMD (the per-edge form: 153 VGPRs, 8.3 KB of LDS) only for queues of 128 problems per CU and more:
-  // measured round 6 on KUKA, 65536 goals 130.5 k -> 134.2 k solves/s (+2.9 %), but 8192 goals 55.4 k -> 51.5 k (-7 %) --
-  // a mid-size batch is its stragglers, and a straggler with two co-resident waves runs slower than with one
-  if (!t->is_block && t->K == 3 && wpc > 8 && (long long)B < 128LL * t->n_cu) wpc = 8;
-  if (t->wpc_override > 0) wpc = t->wpc_override;
-  const int grid = std::min(B, t->n_cu * wpc);
-  // Time slicing (workgroup-per-problem kernel): only when there are more problems than resident
-  // workgroups (otherwise everything starts at once anyway).  Slice length: the handle's
-  // slice_outer_its, 0 disables.  Measured on UR10 + table, 4096 goals: 8.9 -> 7.7 s.
-  int slice = t->is_npt ? t->npt_slice_its : t->slice_its;
-  const bool cg = t->solver == GIK_SOLVER_CONJUGATE_GRADIENT;
-  if (!t->is_block || cg || B <= grid || (a.dbg & 1) || slice <= 0 || t->p.maxiter <= slice) slice = 0;
-  a.slice_its = slice;
   a.y_head = a.y_tail = a.y_seq = nullptr;
   a.y_ids = a.y_avail = nullptr;
   a.y_cap = 0;
@@ -1813,131 +1729,157 @@ int gik_solve_batch(const gik_template *t, const double *d_Y_init, const double 
   a.q_ids = nullptr;
   a.q_seq = nullptr;
   a.q_state = nullptr;
-  // Tail spreading (wavefront kernel): only where two waves share a SIMD and the batch outlasts
-  // the queue -- more problems than resident waves -- and only on the tuned default variant
-  // (trust-region solver, theta = 1, not anchored).  debug_flags 512 turns it off (tests compare).
-  // (At one wave per SIMD -- batches up to 6 problems per SIMD -- round-robin slicing LOSES 5-8 %: a
-  // straggler that happens to start at t = 0 is better off keeping its slot than sharing it for the
-  // first ~20 ms; measured on 4096 LWA4D / KUKA / UR10 goals, four seeds each, tools/attic/dev_rr_midbatch.py.)
-  // (kernels.solve_spread is the build of the form that runs: <3, 10> has a per-edge one but no column-form one)
-  const bool mig = t->kernels.solve_spread && wpc > 4 && B > grid && !(a.dbg & (1 | 512));
-  gik_template::SliceWs *sw = nullptr;
-  // graphs beyond 128 nodes (node-per-lane kernel on four wavefronts): the clique's target triangle of every resident
-  // workgroup lives in global memory -- a region of the same pooled workspace
-  const size_t ctg_bytes = t->is_npt ? t->npt_variant->ctg(t->nt.n_pairs) * sizeof(double) * (size_t)grid : 0;
-  if (slice > 0 || mig || ctg_bytes) {
-    const size_t cap = mig ? (size_t)B + (size_t)grid + 64 : (slice > 0 ? (size_t)B * (size_t)(t->p.maxiter / slice + 1) : 0);
-    // wavefront kernel: round-robin slicing (slice length: the handle's wave_slice_its)
-    // Slice length grows with the queue: 256 iterations up to 8 problems per wave, 4 x that from 32 per wave on.
-    // A hand-over moves ~4.5 KB through HBM (point, state, the targets re-read; PMC, round 3: 624 MB per 65536-goal
-    // KUKA launch = 6.3 x the algorithmic bytes at 118 k hand-overs); measured round 4 (tools/slice_scan.py), KUKA
-    // 65536: slice 256 / 512 / 1024 / 2048 -> 501.5 / 500.9 / 510.6 / 514.0 ms and 118 k / 51 k / 19 k / 7.5 k
-    // hand-overs; KUKA 8192: 145.5 / 147.7 / 161.6 ms -- short queues want the short slice.
-    int wslice = (mig && !(a.dbg & 1024)) ? t->wave_slice_its : 0;
-    // (PMC, round 4, 65536 KUKA goals, tools/attic/c4_slice_traffic.sh: no slicing 202 MB per launch = 2.0 x the
-    // algorithmic bytes -- the floor of this kernel's 432 / 600-byte rows -- at 555 ms; slice 1024: 287 MB, 519 ms;
-    // 1536: 526 ms; 2048: 239 MB = 2.4 x, 537 ms.  Throughput decides: 1024.)
-    if (wslice > 0 && t->wave_slice_auto && (long long)B > 8LL * grid)
-      wslice = (int)std::min<long long>(4LL * wslice, (long long)wslice * B / (8LL * grid));
-    // yield queue: a problem yields at most maxiter / slice + 1 times; the margin covers the waves that may be
-    // between the capacity test and their push (mig_anyone_waiting)
-    const size_t ycap = wslice > 0 ? std::min((size_t)B * (size_t)(t->p.maxiter / wslice + 2), (size_t)16 * B + 8192) +
-                                         2 * (size_t)grid + 256
-                                   : 0;      // (very short slices: the queue fills and the problems stop yielding)
-    const size_t off_simd = 32, off_seq = off_simd + (mig ? sizeof(int) * MIG_SIMDS : 0), off_ids = off_seq + cap * 4,
-                 off_state = (off_ids + cap * 4 + 15) & ~(size_t)15,
-                 off_yseq = off_state + (((size_t)B * sizeof(SliceState) + 15) & ~(size_t)15), off_yids = off_yseq + ycap * 4;
-    const size_t off_ctg = (off_yids + ycap * 4 + 63) & ~(size_t)63;
-    const size_t bytes = off_ctg + ctg_bytes;
-    sw = &mt->slice_ws[take(mt->slice_ws, mt->next_slice, (unsigned)t->slice_pool)];
-    release.sw = sw;
-    if (!sw->done && hipEventCreateWithFlags(&sw->done, hipEventDisableTiming) != hipSuccess)
-      return fail("hipEventCreate failed");
-    if (sw->bytes < bytes) {
-      if (sw->pending) (void)hipEventSynchronize(sw->done);
-      if (sw->base) (void)hipFree(sw->base);
-      sw->base = nullptr;
-      sw->bytes = 0;
-      if (hipMalloc(&sw->base, bytes) != hipSuccess) return fail("cannot allocate the time-slicing workspace");
-      sw->bytes = bytes;
-      sw->pending = false;
-    }
-    if (sw->pending) HIP_OK(hipStreamWaitEvent((hipStream_t)stream, sw->done, 0));
-    char *base = static_cast<char *>(sw->base);
-    a.q_tail = reinterpret_cast<unsigned int *>(base);
-    a.q_done = a.q_tail + 1;
-    a.q_head = a.q_tail + 2;
-    a.mig_credits = reinterpret_cast<int *>(a.q_tail + 3);
-    a.mig_simd_run = reinterpret_cast<int *>(base + off_simd);
-    a.q_seq = reinterpret_cast<unsigned int *>(base + off_seq);
-    a.q_ids = reinterpret_cast<int *>(base + off_ids);
-    a.q_state = reinterpret_cast<SliceState *>(base + off_state);
-    a.y_head = a.q_tail + 4;
-    a.y_tail = a.q_tail + 5;
-    a.y_avail = reinterpret_cast<int *>(a.q_tail + 6);
-    a.y_seq = reinterpret_cast<unsigned int *>(base + off_yseq);
-    a.y_ids = reinterpret_cast<int *>(base + off_yids);
-    a.y_cap = (unsigned int)ycap;
-    a.npt_ctg_ws = ctg_bytes ? reinterpret_cast<double *>(base + off_ctg) : nullptr;
-    if (mig) { a.slice_its = wslice; a.slice_cycles = t->wave_slice_cycles; }
-    HIP_OK(hipMemsetAsync(base, 0, off_seq, (hipStream_t)stream));
-    if (cap) HIP_OK(hipMemsetAsync(a.q_seq, 0xFF, cap * 4, (hipStream_t)stream));
-    if (mig || t->is_npt) HIP_OK(hipMemsetAsync(a.q_state, 0, (size_t)B * sizeof(SliceState), (hipStream_t)stream));
-    if (ycap) HIP_OK(hipMemsetAsync(a.y_seq, 0, ycap * 4, (hipStream_t)stream));
+}
+
+// "the launch that used this slot last has completed" (gik_slots.h asks it under call_mutex)
+static bool event_done(hipEvent_t e) {
+  if (hipEventQuery(e) == hipSuccess) return true;
+  (void)hipGetLastError();      // (hipErrorNotReady of the query)
+  return false;
+}
+
+typedef gik::SlotLease<gik_template::CounterSlot> CounterLease;
+typedef gik::SlotLease<gik_template::SliceWs> WorkspaceLease;
+
+// a work-queue head of this call's own, zeroed on the stream behind the launch that used it last
+static int lease_counter(gik_template *mt, CounterLease &lease, gik::SolveArgs &a, hipStream_t stream) {
+  using namespace gik;
+  gik_template::CounterSlot &cs = lease.take(mt->counter_slot, mt->next_counter, (unsigned)mt->counter_ring, event_done);
+  a.work_counter = mt->d_counters + (&cs - mt->counter_slot.data());
+  if (!cs.done && hipEventCreateWithFlags(&cs.done, hipEventDisableTiming) != hipSuccess)
+    return fail("hipEventCreate failed");
+  if (cs.pending) HIP_OK(hipStreamWaitEvent(stream, cs.done, 0));   // ring wrapped: previous user first
+  HIP_OK(hipMemsetAsync(a.work_counter, 0, sizeof(unsigned int), stream));
+  return 0;
+}
+
+// a pooled workspace of at least the plan's size (grown outside the lock, behind its previous user), the queue
+// pointers of SolveArgs into it, and its memsets on the stream
+static int bind_workspace(gik_template *mt, WorkspaceLease &lease, const gik::SolvePlan &p, gik::SolveArgs &a,
+                          hipStream_t stream) {
+  using namespace gik;
+  gik_template::SliceWs *sw = &lease.take(mt->slice_ws, mt->next_slice, (unsigned)mt->slice_pool, event_done);
+  if (!sw->done && hipEventCreateWithFlags(&sw->done, hipEventDisableTiming) != hipSuccess)
+    return fail("hipEventCreate failed");
+  if (sw->bytes < p.bytes) {
+    if (sw->pending) (void)hipEventSynchronize(sw->done);
+    if (sw->base) (void)hipFree(sw->base);
+    sw->base = nullptr;
+    sw->bytes = 0;
+    if (hipMalloc(&sw->base, p.bytes) != hipSuccess) return fail("cannot allocate the time-slicing workspace");
+    sw->bytes = p.bytes;
+    sw->pending = false;
   }
-  // four planar problems per wavefront: from 12 problems per CU on (measured, planar-10, events around the call:
-  // 4..64 problems 158 against 95 us, 1024: 206 / 150, 4096: 259 / 282 -- below that every problem has a wavefront
-  // of its own anyway and the lone problem is faster there); debug_flags 16384: at any batch size
-  const bool quad = t->quad_solve && !(a.dbg & (1 | 8192)) && ((a.dbg & 16384) || B >= t->quad_min_batch);
-  if (quad) {
-    // a wavefront holds four problems: a quarter of the waves (at least one slot each), no slicing
-    int qw = t->quad_waves_per_cu;
-    if (t->wpc_override > 0) qw = t->wpc_override;
-    const int qgrid = std::max(1, std::min((B + QUAD_SLOTS - 1) / QUAD_SLOTS, t->n_cu * qw));
-    hipLaunchKernelGGL(t->quad_solve, dim3(qgrid), dim3(WAVE), t->quad_smem, (hipStream_t)stream, a);
-  } else if (t->is_npt) {
-    a.nt = t->nt;
-    hipLaunchKernelGGL(t->npt_variant->solve, dim3(grid), dim3(WAVE * t->npt_variant->NW), t->npt_smem, (hipStream_t)stream, a);
-  } else if (t->is_block) {
-    hipLaunchKernelGGL(t->kernels.block_solve, dim3(grid), dim3(BLOCK_NT), t->smem_bytes, (hipStream_t)stream, a, t->SL);
-  } else {
-    hipLaunchKernelGGL(mig ? t->kernels.solve_spread : t->kernels.solve, dim3(grid), dim3(WAVE), t->smem_bytes, (hipStream_t)stream, a);
+  if (sw->pending) HIP_OK(hipStreamWaitEvent(stream, sw->done, 0));
+  char *base = static_cast<char *>(sw->base);
+  a.q_tail = reinterpret_cast<unsigned int *>(base);
+  a.q_done = a.q_tail + 1;
+  a.q_head = a.q_tail + 2;
+  a.mig_credits = reinterpret_cast<int *>(a.q_tail + 3);
+  a.mig_simd_run = reinterpret_cast<int *>(base + p.off_simd);
+  a.q_seq = reinterpret_cast<unsigned int *>(base + p.off_seq);
+  a.q_ids = reinterpret_cast<int *>(base + p.off_ids);
+  a.q_state = reinterpret_cast<SliceState *>(base + p.off_state);
+  a.y_head = a.q_tail + 4;
+  a.y_tail = a.q_tail + 5;
+  a.y_avail = reinterpret_cast<int *>(a.q_tail + 6);
+  a.y_seq = reinterpret_cast<unsigned int *>(base + p.off_yseq);
+  a.y_ids = reinterpret_cast<int *>(base + p.off_yids);
+  a.y_cap = (unsigned int)p.ycap;
+  a.npt_ctg_ws = p.ctg_bytes ? reinterpret_cast<double *>(base + p.off_ctg) : nullptr;
+  HIP_OK(hipMemsetAsync(base, 0, p.zero_head, stream));
+  if (p.seq_fill) HIP_OK(hipMemsetAsync(a.q_seq, 0xFF, p.seq_fill, stream));
+  if (p.state_zero) HIP_OK(hipMemsetAsync(a.q_state, 0, p.state_zero, stream));
+  if (p.yseq_zero) HIP_OK(hipMemsetAsync(a.y_seq, 0, p.yseq_zero, stream));
+  return 0;
+}
+
+static void launch(const gik_template *t, const gik::SolvePlan &p, gik::SolveArgs &a, hipStream_t stream) {
+  using namespace gik;
+  const dim3 grid(p.launch_grid);
+  switch (p.launch) {
+    case Launch::QUAD:
+      hipLaunchKernelGGL(t->quad_solve, grid, dim3(WAVE), t->quad_smem, stream, a);
+      break;
+    case Launch::NPT:
+      a.nt = t->nt;
+      hipLaunchKernelGGL(t->npt_variant->solve, grid, dim3(WAVE * t->npt_variant->NW), t->npt_smem, stream, a);
+      break;
+    case Launch::BLOCK:
+      hipLaunchKernelGGL(t->kernels.block_solve, grid, dim3(BLOCK_NT), t->smem_bytes, stream, a, t->SL);
+      break;
+    case Launch::WAVE:
+      hipLaunchKernelGGL(t->kernels.solve, grid, dim3(WAVE), t->smem_bytes, stream, a);
+      break;
+    case Launch::WAVE_SPREAD:
+      hipLaunchKernelGGL(t->kernels.solve_spread, grid, dim3(WAVE), t->smem_bytes, stream, a);
+      break;
   }
+}
+
+int gik_solve_batch(const gik_template *t, const double *d_Y_init, const double *d_targets,
+                    int B, double *d_Y_out, gik_stats *d_stats, const gik_trace *trace,
+                    void *stream_) {
+  using namespace gik;
+  if (!t || B < 0) return fail("bad argument");
+  if (B == 0) return 0;
+  if (!d_Y_init || !d_targets || !d_Y_out || !d_stats) return fail("null buffer");
+  hipStream_t stream = (hipStream_t)stream_;
+  SolveArgs a;
+  fill_args(t, a, d_Y_init, d_targets, B, d_Y_out, d_stats, trace);
+  // Stream capture is refused: the slot protocol below queries, waits for and records events, grows workspaces
+  // (hipMalloc / hipFree) and resets a counter the kernel consumes -- none of which may happen under capture, and a
+  // replayed graph would reuse this call's counter slot and workspace behind the library's back.  A batch is ONE
+  // persistent launch; there is no launch overhead for a graph to remove.
+  if (refuse_capture("gik_solve_batch", stream_)) return -1;
+  const SolvePlan plan = plan_solve(t->f, B);
+  a.slice_its = plan.slice_its;
+  a.slice_cycles = plan.slice_cycles;
+  // The handle's mutable parts: the ring of work-queue heads and the time-slicing workspaces.  Each is leased
+  // under call_mutex (gik_slots.h) and held until the event that guards its reuse is recorded, so concurrent calls
+  // on one handle (any number of host threads and streams) are safe; every return hands the leases back.
+  gik_template *mt = const_cast<gik_template *>(t);
+  CounterLease counter(mt->call_mutex);
+  WorkspaceLease workspace(mt->call_mutex);
+  if (lease_counter(mt, counter, a, stream)) return -1;
+  if (plan.needs_ws && bind_workspace(mt, workspace, plan, a, stream)) return -1;
+  launch(t, plan, a, stream);
   HIP_OK(hipGetLastError());
   // The slots go back "pending" only behind an event that really covers this launch.  If a record fails,
   // nothing guards the counter / workspace against the next caller: wait for the kernel here and hand the
   // slots back idle instead.
-  const hipError_t e_cs = hipEventRecord(cs.done, (hipStream_t)stream);
-  const hipError_t e_sw = sw ? hipEventRecord(sw->done, (hipStream_t)stream) : hipSuccess;
+  const hipError_t e_cs = hipEventRecord(counter.get()->done, stream);
+  const hipError_t e_sw = workspace.get() ? hipEventRecord(workspace.get()->done, stream) : hipSuccess;
   if (e_cs != hipSuccess || e_sw != hipSuccess) {
-    (void)hipStreamSynchronize((hipStream_t)stream);
+    (void)hipStreamSynchronize(stream);
     return fail(std::string("hipEventRecord failed after the launch: ") + hipGetErrorString(e_cs != hipSuccess ? e_cs : e_sw));
   }
-  release.launched = true;
+  counter.covered_by_event();
+  workspace.covered_by_event();
   return 0;
 }
 
 int gik_template_get_info(const gik_template *t, gik_template_info *info) {
   if (!t || !info) return gik::fail("null argument");
   std::memset(info, 0, sizeof(*info));
-  info->is_block = t->is_block ? 1 : 0;
-  info->max_terms_per_node = t->is_block ? 0 : t->maxdeg;
+  info->is_block = t->f.is_block ? 1 : 0;
+  info->max_terms_per_node = t->f.is_block ? 0 : t->maxdeg;
   info->n_clique = t->bt.n_clq;
-  info->n_slot_terms = t->is_block ? t->bt.Tc : t->T;
+  info->n_slot_terms = t->f.is_block ? t->bt.Tc : t->T;
   info->slots_per_thread = t->SL;
-  info->waves_per_cu = t->waves_per_cu;
-  info->n_cu = t->n_cu;
+  info->waves_per_cu = t->f.waves_per_cu;
+  info->n_cu = t->f.n_cu;
   info->lds_bytes = (int32_t)t->smem_bytes;
   info->clique_closed_form = t->clique_mode;
-  info->hessian_form = (t->hess_per_edge || t->is_block) ? GIK_HESS_PER_EDGE : GIK_HESS_COLUMN;
+  info->hessian_form = (t->hess_per_edge || t->f.is_block) ? GIK_HESS_PER_EDGE : GIK_HESS_COLUMN;
   info->anchored = t->anchored ? 1 : 0;
   info->has_pipeline = t->has_pipe ? 1 : 0;
   info->prepare_is_block = t->prep_block ? 1 : 0;
-  info->node_per_lane = t->is_npt ? t->npt_variant->NW : 0;
+  info->node_per_lane = t->f.is_npt ? t->npt_variant->NW : 0;
   info->goals_per_wave = !t->has_pipe || t->prep_block ? 0 : (t->prep_quad ? gik::QUAD_SLOTS : 1);
-  info->problems_per_wave = t->is_block ? 0 : ((t->quad_solve && !(t->dbg & (1 | 8192))) ? gik::QUAD_SLOTS : 1);
-  if (t->is_npt) {
-    info->waves_per_cu = t->npt_waves_per_cu;
+  info->problems_per_wave = t->f.is_block ? 0 : ((t->quad_solve && !(t->f.dbg & (1 | 8192))) ? gik::QUAD_SLOTS : 1);
+  if (t->f.is_npt) {
+    info->waves_per_cu = t->f.npt_waves_per_cu;
     info->lds_bytes = (int32_t)t->npt_smem;
   }
   return 0;
@@ -1953,13 +1895,13 @@ double gik_debug_parts(const gik_template *t, int mode, int iters) {
   (void)hipEventCreate(&e0);
   (void)hipEventCreate(&e1);
   (void)hipEventRecord(e0, 0);
-  if (t->K == 3 && t->maxdeg == 9)
+  if (t->f.K == 3 && t->maxdeg == 9)
     hipLaunchKernelGGL((parts_kernel<3, 9>), dim3(1), dim3(WAVE), t->smem_bytes, 0, t->d_slot_meta,
                        t->N, t->T, mode % 100, iters, d);
-  else if (t->K == 3 && t->maxdeg == 10)
+  else if (t->f.K == 3 && t->maxdeg == 10)
     hipLaunchKernelGGL((parts_kernel<3, 10>), dim3(1), dim3(WAVE), t->smem_bytes, 0, t->d_slot_meta,
                        t->N, t->T, mode % 100, iters, d);
-  else if (t->K == 3)
+  else if (t->f.K == 3)
     return -1;
   else
     hipLaunchKernelGGL((parts_kernel<2, 6>), dim3(1), dim3(WAVE), t->smem_bytes, 0, t->d_slot_meta,

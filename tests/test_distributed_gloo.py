@@ -27,6 +27,7 @@ if rank == 0:
     assert mx == world and sm == total
 else:
     assert full is None
+gd.shutdown()      # (a rank that exits with gloo's threads still running can abort in their destructors)
 '''
 
 
@@ -218,6 +219,7 @@ if rank == 0:
     np.savez(os.environ["GIK_OUT"], q=q, Y=Y, q3=q3, Y3=Y3, it3=info3["iterations"], **info)
 else:
     assert q is None and Y is None and info is None and q2 is None and q3 is None
+gd.shutdown()      # (see WORKER)
 '''
 
 
