@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GIK_LIB_PATH") or os.path.join(_HERE, "lib", "libgraphik_amd.so")
 
 TERM_EQ, TERM_LOWER, TERM_UPPER = 1, 2, 3
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 
 class TemplateDesc(C.Structure):
@@ -124,6 +124,11 @@ SYMBOLS = {
     "gik_anchored_ws_doubles": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_int]),
     "gik_anchored_ik_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gik_anchored_seed_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gik_anchored_clearance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "gik_anchored_ik_batch_seeded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] +
+                                     7 * [C.c_void_p] + [C.c_void_p]),
     "gik_anchored_last_solve_ms": (C.c_double, [C.c_void_p]),
     "gik_template_destroy": (None, [C.c_void_p]),
     "gik_template_get_info": (C.c_int, [C.c_void_p, C.POINTER(TemplateInfo)]),

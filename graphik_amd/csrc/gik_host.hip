@@ -5,6 +5,7 @@
 #include "gik_kernels.hip.h"
 #include "gik_instances.h"
 #include "gik_retry.hip.h"
+#include "gik_anch_seed.hip.h"
 #include "gik_plan.h"
 #include "gik_slots.h"
 #include <memory>
@@ -123,6 +124,8 @@ struct gik_template {
   double *d_targets_const = nullptr;   // [T] template-constant targets of the free-free terms
   int full_N = 0, n_anchor = 0;
   int *d_free_full = nullptr, *d_anchor_full = nullptr;   // node index in the full robot graph
+  int *d_clear_full = nullptr;      // [n_clear] ... of the free nodes that carry the obstacle hinges (anch_clearance_kernel)
+  int n_clear = 0;
   double axis_length = 1.0;
   int solver;
   gik::CgParams cg;
@@ -778,8 +781,17 @@ static int upload_anchored(gik_template *t, const gik_anchored_desc *ad) {
     ++cnt[i];
   }
   unsigned long long mask = 0;
+  std::vector<int> clear_full;
   for (int i = 0; i < N && ad->obs_node_mask; ++i)
-    if (ad->obs_node_mask[i]) mask |= 1ull << i;
+    if (ad->obs_node_mask[i]) {
+      mask |= 1ull << i;
+      clear_full.push_back(ad->free_full_index[i]);
+    }
+  // rows of the full point matrix that the glue kernels read and write
+  for (int i = 0; i < N; ++i)
+    if (ad->free_full_index[i] < 0 || ad->free_full_index[i] >= ad->full_N) return fail("anchored templates: free_full_index out of range");
+  for (int r = 0; r < ad->n_anchor; ++r)
+    if (ad->anchor_full_index[r] < 0 || ad->anchor_full_index[r] >= ad->full_N) return fail("anchored templates: anchor_full_index out of range");
   AnchArgs &an = t->an;
   an.anch_const = ok ? upload(t, tab.data(), tab.size(), ok) : nullptr;
   an.pin_meta = upload(t, pm.data(), pm.size(), ok);
@@ -792,6 +804,8 @@ static int upload_anchored(gik_template *t, const gik_anchored_desc *ad) {
   t->d_targets_const = const_cast<double *>(upload(t, ad->term_target, (size_t)t->T, ok));
   t->d_free_full = const_cast<int *>(upload(t, ad->free_full_index, (size_t)N, ok));
   t->d_anchor_full = const_cast<int *>(upload(t, ad->anchor_full_index, (size_t)ad->n_anchor, ok));
+  t->d_clear_full = const_cast<int *>(upload(t, clear_full.data(), clear_full.size(), ok));
+  t->n_clear = (int)clear_full.size();
   t->full_N = ad->full_N;
   t->n_anchor = ad->n_anchor;
   t->axis_length = ad->axis_length;
@@ -1530,6 +1544,28 @@ size_t gik_anchored_ws_doubles(const gik_template *anch, const gik_template *bas
   return (size_t)B * ((size_t)base->T + (size_t)base->N * 3 + (size_t)anch->N * 3 + (size_t)anch->an.n_goal * 3);
 }
 
+// the arguments of the glue kernels between the robot-graph pipeline and the anchored solve
+static gik::AnchGlueArgs anch_glue_args(const gik_template *anch, const double *d_T_goal, int B, const double *Y_full_in,
+                                        double *Y_free, double *goal, double *Y_full_out) {
+  gik::AnchGlueArgs g;
+  g.T_goal = d_T_goal;
+  g.Y_full_in = Y_full_in;
+  g.Y_free = Y_free;
+  g.anchor_goal = goal;
+  g.Y_full_out = Y_full_out;
+  g.anch_const = anch->an.anch_const;
+  g.free_full = anch->d_free_full;
+  g.anchor_full = anch->d_anchor_full;
+  g.B = B;
+  g.Nf = anch->N;
+  g.full_N = anch->full_N;
+  g.n_anchor = anch->n_anchor;
+  g.n_goal = anch->an.n_goal;
+  g.goal_row0 = anch->an.goal_row0;
+  g.axis_length = anch->axis_length;
+  return g;
+}
+
 int gik_anchored_ik_batch(const gik_template *anch, const gik_template *base, const double *d_T_goal, int B,
                           double *d_ws, double *d_Y_full, gik_stats *d_stats, double *d_q,
                           double *d_pos_err, double *d_rot_err, void *stream) {
@@ -1546,22 +1582,7 @@ int gik_anchored_ik_batch(const gik_template *anch, const gik_template *base, co
   // initial point of the robot graph (bound smoothing + MDS, obstacles play no part in it) ...
   int rc = gik_prepare_batch(base, d_T_goal, B, tg_base, Y_full0, nullptr, stream);
   if (rc) return rc;
-  AnchGlueArgs g;
-  g.T_goal = d_T_goal;
-  g.Y_full_in = Y_full0;
-  g.Y_free = Y_free;
-  g.anchor_goal = goal;
-  g.Y_full_out = d_Y_full;
-  g.anch_const = anch->an.anch_const;
-  g.free_full = anch->d_free_full;
-  g.anchor_full = anch->d_anchor_full;
-  g.B = B;
-  g.Nf = anch->N;
-  g.full_N = anch->full_N;
-  g.n_anchor = anch->n_anchor;
-  g.n_goal = anch->an.n_goal;
-  g.goal_row0 = anch->an.goal_row0;
-  g.axis_length = anch->axis_length;
+  const AnchGlueArgs g = anch_glue_args(anch, d_T_goal, B, Y_full0, Y_free, goal, d_Y_full);
   // ... mapped onto the world frame by its anchors; free rows = anchored start point
   hipLaunchKernelGGL(anch_init_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, g);
   HIP_OK(hipGetLastError());
@@ -1582,6 +1603,105 @@ int gik_anchored_ik_batch(const gik_template *anch, const gik_template *base, co
   hipLaunchKernelGGL(anch_gather_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, g);
   HIP_OK(hipGetLastError());
   return gik_recover_batch(base, d_Y_full, d_T_goal, B, d_q, d_pos_err, d_rot_err, stream);
+}
+
+// ---- the anchored solve from joint-configuration seeds (gik_anch_seed.hip.h) --------------------------
+// what the seeded anchored calls refuse, before anything is queued
+static int anchored_seed_refusal(const char *entry, const gik_template *anch, const gik_template *base, const double *d_q_init,
+                                 int B, void *stream) {
+  using gik::fail;
+  const std::string e(entry);
+  if (!anch || !base || B < 0) return fail(e + ": bad argument");
+  if (!anch->anchored) return fail(e + ": the first handle must be a fixed-anchor template (gik_template_create_anchored)");
+  if (!base->has_pipe || base->f.K != 3 || base->N != anch->full_N)
+    return fail(e + ": the base template must be the robot graph (full_N nodes) with its pipeline attached");
+  if (!base->seed_ok) return fail(e + ": the base graph cannot be seeded on the device: " + base->seed_why);
+  if (refuse_capture(entry, stream)) return -1;
+  if (B > 0 && !d_q_init) return fail(e + ": null d_q_init (seed joint angles [B][n] are required)");
+  return 0;
+}
+
+// seed_kernel on the robot graph into the workspace, then the row gather + goal anchors
+static int anchored_seed_launch(const gik_template *anch, const gik_template *base, const double *d_T_goal,
+                                const double *d_q_init, int B, double *d_ws, double *Y_free, double *goal, void *stream) {
+  using namespace gik;
+  double *tg_base = d_ws;
+  double *Y_full0 = tg_base + (size_t)B * base->T;
+  const int rc = gik_seed_batch(base, d_T_goal, d_q_init, B, tg_base, Y_full0, stream);
+  if (rc) return rc;
+  const AnchGlueArgs g = anch_glue_args(anch, d_T_goal, B, Y_full0, Y_free, goal, nullptr);
+  const size_t n = (size_t)B * ((size_t)g.Nf + (size_t)g.n_goal) * 3;
+  hipLaunchKernelGGL(anch_scatter_kernel, dim3((unsigned)((n + ANCH_SCATTER_NT - 1) / ANCH_SCATTER_NT)), dim3(ANCH_SCATTER_NT),
+                     0, (hipStream_t)stream, g);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int gik_anchored_seed_batch(const gik_template *anch, const gik_template *base, const double *d_T_goal,
+                            const double *d_q_init, int B, double *d_ws, double *d_Y_free, double *d_goal, void *stream) {
+  if (anchored_seed_refusal("gik_anchored_seed_batch", anch, base, d_q_init, B, stream)) return -1;
+  if (B == 0) return 0;
+  if (!d_T_goal || !d_ws || !d_Y_free || !d_goal) return gik::fail("gik_anchored_seed_batch: null buffer");
+  return anchored_seed_launch(anch, base, d_T_goal, d_q_init, B, d_ws, d_Y_free, d_goal, stream);
+}
+
+static int anchored_clearance_launch(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance,
+                                     void *stream) {
+  using namespace gik;
+  AnchClearArgs c;
+  c.Y_full = d_Y_full;
+  c.obs = anch->an.obs;
+  c.node_full = anch->d_clear_full;
+  c.clearance = d_clearance;
+  c.B = B;
+  c.full_N = anch->full_N;
+  c.n_node = anch->n_clear;
+  c.n_obs = anch->an.n_obs;
+  hipLaunchKernelGGL(anch_clearance_kernel, dim3(std::min(B, anch->f.n_cu * 32)), dim3(WAVE), 0, (hipStream_t)stream, c);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int gik_anchored_clearance(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance, void *stream) {
+  using gik::fail;
+  if (!anch || B < 0) return fail("gik_anchored_clearance: bad argument");
+  if (!anch->anchored) return fail("gik_anchored_clearance: the handle must be a fixed-anchor template (gik_template_create_anchored)");
+  if (refuse_capture("gik_anchored_clearance", stream)) return -1;
+  if (B == 0) return 0;
+  if (!d_Y_full || !d_clearance) return fail("gik_anchored_clearance: null buffer");
+  return anchored_clearance_launch(anch, d_Y_full, B, d_clearance, stream);
+}
+
+int gik_anchored_ik_batch_seeded(const gik_template *anch, const gik_template *base, const double *d_T_goal,
+                                 const double *d_q_init, int B, double *d_ws, double *d_Y_full, gik_stats *d_stats,
+                                 double *d_q, double *d_pos_err, double *d_rot_err, double *d_clearance, void *stream) {
+  using namespace gik;
+  if (anchored_seed_refusal("gik_anchored_ik_batch_seeded", anch, base, d_q_init, B, stream)) return -1;
+  if (B == 0) return 0;
+  if (!d_T_goal || !d_ws || !d_Y_full || !d_stats || !d_q || !d_pos_err || !d_rot_err)
+    return fail("gik_anchored_ik_batch_seeded: null buffer");
+  double *Y_free = d_ws + (size_t)B * base->T + (size_t)B * base->N * 3;      // (the cold call's workspace layout)
+  double *goal = Y_free + (size_t)B * anch->N * 3;
+  // the seed angles are read here and nowhere later: d_q_init may be d_q
+  int rc = anchored_seed_launch(anch, base, d_T_goal, d_q_init, B, d_ws, Y_free, goal, stream);
+  if (rc) return rc;
+  gik_template *ma = const_cast<gik_template *>(anch);      // the event pair of gik_anchored_last_solve_ms, as the cold call
+  {
+    std::lock_guard<std::mutex> lock(ma->ev_mutex);
+    (void)hipEventRecord(ma->ev_solve0, (hipStream_t)stream);
+  }
+  rc = gik_solve_batch(anch, Y_free, goal, B, Y_free, d_stats, nullptr, stream);
+  if (rc) return rc;
+  {
+    std::lock_guard<std::mutex> lock(ma->ev_mutex);
+    (void)hipEventRecord(ma->ev_solve1, (hipStream_t)stream);
+  }
+  const AnchGlueArgs g = anch_glue_args(anch, d_T_goal, B, nullptr, Y_free, goal, d_Y_full);
+  hipLaunchKernelGGL(anch_gather_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, g);
+  HIP_OK(hipGetLastError());
+  rc = gik_recover_batch(base, d_Y_full, d_T_goal, B, d_q, d_pos_err, d_rot_err, stream);
+  if (rc || !d_clearance) return rc;
+  return anchored_clearance_launch(anch, d_Y_full, B, d_clearance, stream);
 }
 
 double gik_anchored_last_solve_ms(const gik_template *anch) {

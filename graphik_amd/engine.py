@@ -468,25 +468,86 @@ class Template:
         res.update(_decode_stats(out["stats"]))
         return res
 
-    def anchored_ik(self, base, T_goal):
-        """Whole pipeline through the fixed-anchor solve (gik_anchored_ik_batch): `base` is the
-        robot graph's Template (no obstacles) with its pipeline attached.  Returns device tensors:
-        x [B, full_N, 3] (all robot-graph nodes, anchors included), q, pos_err, rot_err + stats."""
-        assert self.anchored and base.has_pipeline
-        T, B = base._poses(T_goal)
+    def alloc_anchored_buffers(self, base, B, clearance=False):
+        """The buffers of one anchored_ik call of B goals (its `out`): the scratch "ws", the full point
+        matrix "Y" [B, full_N*3], "stats", "q", "pos_err", "rot_err" and, if asked for, "clearance"."""
         f64 = dict(dtype=torch.float64, device=self.device)
         nws = int(self.lib.gik_anchored_ws_doubles(self._h, base._h, B))
-        ws = torch.empty(max(nws, 1), **f64)
-        out = {"Y": torch.empty(B, self.full_N * 3, **f64), "stats": _alloc_stats(B, self.device),
-               "q": torch.empty(B, base.n_joints, **f64), "pos_err": torch.empty(B, **f64),
-               "rot_err": torch.empty(B, **f64)}
+        out = {"ws": torch.empty(max(nws, 1), **f64), "Y": torch.empty(B, self.full_N * 3, **f64),
+               "stats": _alloc_stats(B, self.device), "q": torch.empty(B, base.n_joints, **f64),
+               "pos_err": torch.empty(B, **f64), "rot_err": torch.empty(B, **f64)}
+        if clearance:
+            out["clearance"] = torch.empty(B, **f64)
+        return out
+
+    def anchored_seed(self, base, T_goal, q_init):
+        """Goal poses + seed joint angles [B,n] (or [n]) -> the anchored start point on the device
+        (gik_anchored_seed_batch): (Y_free [B,N,3], goal [B,n_goal*3]).  Y_free holds the free rows of
+        base.seed(T_goal, q_init)'s realization, copied; goal is computed from the goal poses."""
+        assert self.anchored and base.has_pipeline
+        T, B = base._poses(T_goal)
+        q = base._seed_angles(q_init, B)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        ws = torch.empty(max(int(self.lib.gik_anchored_ws_doubles(self._h, base._h, B)), 1), **f64)
+        Y_free = torch.empty(B, self.N * 3, **f64)
+        goal = torch.empty(B, self.n_goal_anchor * 3, **f64)
         with torch.cuda.device(self.device):
-            _ffi.check(self.lib.gik_anchored_ik_batch(self._h, base._h, T.data_ptr(), B, ws.data_ptr(),
-                                                      out["Y"].data_ptr(), out["stats"].data_ptr(),
-                                                      out["q"].data_ptr(), out["pos_err"].data_ptr(),
-                                                      out["rot_err"].data_ptr(), self._stream()))
+            _ffi.check(self.lib.gik_anchored_seed_batch(self._h, base._h, T.data_ptr(), q.data_ptr(), B, ws.data_ptr(),
+                                                        Y_free.data_ptr(), goal.data_ptr(), self._stream()))
+        return Y_free.reshape(B, self.N, 3), goal
+
+    def anchored_clearance(self, Y_full):
+        """Full point matrices [B, full_N, 3] -> clearance [B] on the device (gik_anchored_clearance): the
+        minimum of |Y_i - centre| - radius over the free nodes that carry the obstacle hinges and the
+        obstacles; +inf without obstacles."""
+        assert self.anchored
+        Y = _dev(Y_full, self.device)
+        if Y.dim() == 2:
+            Y = Y[None]
+        B = Y.shape[0]
+        assert Y.numel() == B * self.full_N * 3, (tuple(Y.shape), (B, self.full_N, 3))
+        Y = Y.reshape(B, self.full_N * 3).contiguous()
+        out = torch.empty(B, dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _ffi.check(self.lib.gik_anchored_clearance(self._h, Y.data_ptr(), B, out.data_ptr(), self._stream()))
+        return out
+
+    def anchored_ik(self, base, T_goal, q_init=None, out=None, clearance=False):
+        """Whole pipeline through the fixed-anchor solve: `base` is the robot graph's Template (no
+        obstacles) with its pipeline attached.  Without q_init the start point is the robot graph's bound
+        smoothing + MDS one fitted to the anchors (gik_anchored_ik_batch); with q_init (seed joint angles
+        [B,n] or [n]; a device tensor may be out["q"] itself) it is the realization of q_init
+        (gik_anchored_ik_batch_seeded).  clearance: also the device clearance of the answer.  `out`: the
+        buffers of alloc_anchored_buffers, to reuse between calls.  Returns device tensors: x [B, full_N, 3]
+        (all robot-graph nodes, anchors included), q, pos_err, rot_err (+ clearance) + stats."""
+        assert self.anchored and base.has_pipeline
+        T, B = base._poses(T_goal)
+        if out is None:
+            out = self.alloc_anchored_buffers(base, B, clearance)
+        ws = out["ws"]
+        assert ws.numel() >= int(self.lib.gik_anchored_ws_doubles(self._h, base._h, B))
+        cl = None
+        if clearance:
+            cl = out["clearance"] if "clearance" in out else torch.empty(B, dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            if q_init is None:
+                _ffi.check(self.lib.gik_anchored_ik_batch(self._h, base._h, T.data_ptr(), B, ws.data_ptr(),
+                                                          out["Y"].data_ptr(), out["stats"].data_ptr(),
+                                                          out["q"].data_ptr(), out["pos_err"].data_ptr(),
+                                                          out["rot_err"].data_ptr(), self._stream()))
+                if clearance:
+                    _ffi.check(self.lib.gik_anchored_clearance(self._h, out["Y"].data_ptr(), B, cl.data_ptr(),
+                                                               self._stream()))
+            else:
+                q0 = base._seed_angles(q_init, B)
+                _ffi.check(self.lib.gik_anchored_ik_batch_seeded(
+                    self._h, base._h, T.data_ptr(), q0.data_ptr(), B, ws.data_ptr(), out["Y"].data_ptr(),
+                    out["stats"].data_ptr(), out["q"].data_ptr(), out["pos_err"].data_ptr(), out["rot_err"].data_ptr(),
+                    None if cl is None else cl.data_ptr(), self._stream()))
         res = {"x": out["Y"].reshape(B, self.full_N, 3), "q": out["q"], "pos_err": out["pos_err"],
                "rot_err": out["rot_err"], "_ws": ws}
+        if clearance:
+            res["clearance"] = cl
         res.update(_decode_stats(out["stats"]))
         return res
 

@@ -566,9 +566,68 @@ class AnchoredProblem:
         """[B,4,4] -> [B, 2*3]: p_n, q_n world positions (graph_revolute.py:243-249)."""
         return self.base.goal_positions(T_goals).reshape(len(T_goals), -1)
 
-    def solve(self, T_goals):
-        """Goal poses -> dict of device tensors (x [B, N_robot, 3], q, pos_err, rot_err, stats)."""
-        return self.template.anchored_ik(self.base.template, np.asarray(T_goals, dtype=float))
+    def seed_points(self, q):
+        """Joint angles [B,n] (or [n]) -> the anchored start point [B, len(free), 3]: the free rows of
+        the robot graph's realization (BatchProblem.seed_points), which is already in the world frame.
+        The host mirror of gik_anchored_seed_batch's Y_free."""
+        return self.base.seed_points(q)[:, self.free]
+
+    def solve(self, T_goals, q_init=None, clearance=False):
+        """Goal poses -> dict of device tensors (x [B, N_robot, 3], q, pos_err, rot_err, stats).
+
+        q_init (warm start): joint angles [B,n] or [n]; the solve then starts from the realization of
+        its seed (gik_anchored_ik_batch_seeded) instead of bound smoothing + MDS, the goal nodes still
+        where the goal puts them.  clearance: add "clearance" [B], the device twin of
+        self.clearance(x) -- always there for a seeded solve."""
+        T = np.asarray(T_goals, dtype=float)
+        if q_init is None:
+            return self.template.anchored_ik(self.base.template, T, clearance=clearance)
+        q_init = _seed_angles(q_init, T.shape[0], self.robot.n)
+        return self.template.anchored_ik(self.base.template, T, q_init=q_init, clearance=True)
+
+    def solve_trajectory(self, T_path, q_start, return_Y=False):
+        """Path tracking among the obstacles: B paths of L waypoints, T_path [B, L, 4, 4].  Waypoint 0
+        is seeded by q_start ([B,n] or [n]), waypoint l by the joint angles recovered at waypoint l-1,
+        which never leave the device: L calls of gik_anchored_ik_batch_seeded on one stream, one
+        workspace, one synchronisation at the end.  A waypoint that fails still seeds the next one (no
+        retry): check info["stop"], info["f(x)"] and info["clearance"].
+
+        Returns q [B, L, n], Y [B, L, N_robot, 3] (None unless return_Y), and info with [B, L] arrays
+        iterations, inner_iterations, stop, f(x), gradnorm, pos_err, rot_err, clearance, plus
+        solve_time (seconds, whole path)."""
+        T = np.asarray(T_path, dtype=float)
+        B, L = T.shape[:2]
+        n = self.robot.n
+        q0 = _seed_angles(q_start, B, n, "q_start")
+        tpl, base = self.template, self.base.template
+        dev = tpl.device
+        f64 = dict(dtype=torch.float64, device=dev)
+        Tw = torch.from_numpy(np.ascontiguousarray(np.swapaxes(T, 0, 1))).to(dev)     # [L, B, 4, 4]: waypoint-major
+        q_all = torch.empty(L, B, n, **f64)
+        Y_all = torch.empty(L if return_Y else 1, B, tpl.full_N * 3, **f64)
+        stats = _alloc_stats(L * B, dev)
+        stats = stats.reshape(L, B, stats.shape[1])
+        pe, re, cl = (torch.empty(L, B, **f64) for _ in range(3))
+        ws = tpl.alloc_anchored_buffers(base, B)["ws"]
+        q_prev = torch.from_numpy(q0).to(dev)
+        torch.cuda.synchronize(dev)
+        t0 = time.time()
+        for l in range(L):
+            out = {"ws": ws, "Y": Y_all[l if return_Y else 0], "stats": stats[l], "q": q_all[l], "pos_err": pe[l],
+                   "rot_err": re[l], "clearance": cl[l]}
+            tpl.anchored_ik(base, Tw[l], q_init=q_prev, out=out, clearance=True)
+            q_prev = q_all[l]
+        torch.cuda.synchronize(dev)
+        dt = time.time() - t0
+        st = _decode_stats(stats.reshape(L * B, stats.shape[2]))
+        info = {"iterations": st["iterations"], "inner_iterations": st["inner_total"], "stop": st["stop"],
+                "f(x)": st["f"], "gradnorm": st["gradnorm"], "pos_err": pe.reshape(-1), "rot_err": re.reshape(-1),
+                "clearance": cl.reshape(-1)}
+        info = {key: v.reshape(L, B).T.cpu().numpy() for key, v in info.items()}
+        info["solve_time"] = dt
+        q = q_all.permute(1, 0, 2).cpu().numpy()
+        Y = Y_all.reshape(L, B, tpl.full_N, 3).permute(1, 0, 2, 3).cpu().numpy() if return_Y else None
+        return q, Y, info
 
     def clearance(self, Y_full, include_goal=False):
         """min over (p-node of the robot, obstacle) of |p - centre| - radius per goal (>= 0:

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define GIK_ABI_VERSION 7
+#define GIK_ABI_VERSION 8
 
 /* Residual-term kinds: one "term" per (index pair, kind) exactly as the loops of
  * costs.py:80-207 visit them: equality (omega != 0), lower hinge (psi_L != 0), upper hinge
@@ -147,7 +147,8 @@ enum {
  *   - anchored templates: the event pair read by gik_anchored_last_solve_ms (diagnostic; with
  *     concurrent callers it reports whichever call recorded last).
  * Because of that bookkeeping a batch call cannot be captured into a HIP graph: on a stream that is capturing
- * (hipStreamBeginCapture) gik_solve_batch / gik_ik_batch / gik_ik_batch_seeded / gik_anchored_ik_batch -- and gik_prepare_batch where it
+ * (hipStreamBeginCapture) gik_solve_batch / gik_ik_batch / gik_ik_batch_seeded / gik_anchored_ik_batch, the seeded anchored
+ * calls (gik_anchored_seed_batch, gik_anchored_ik_batch_seeded, gik_anchored_clearance) -- and gik_prepare_batch where it
  * uses the workgroup kernel -- return an error before touching the stream.  (A batch is one persistent launch; there
  * is no launch overhead for a graph to remove.)
  * Results never depend on that bookkeeping, on the stream, on the number of calls in flight or on how the problems of
@@ -481,8 +482,41 @@ int gik_anchored_ik_batch(const gik_template *anch, const gik_template *base, co
                           int B, double *d_ws, double *d_Y_full, gik_stats *d_stats, double *d_q,
                           double *d_pos_err, double *d_rot_err, void *stream);
 
+/* ---- the anchored solve from a joint-configuration seed; clearance ---------------------------
+ * The seed: joint angles d_q_init [B][n] (as gik_seed_batch takes them).  gik_seed_batch on `base` writes
+ * graph.realization(q_init) of the robot graph, which is already in the world frame with the base anchors
+ * at their positions; the anchored start point is a row gather of it -- Y_free[f] = Y_full[free_full_index[f]],
+ * copied bit for bit, no Procrustes fit.  The goal nodes do NOT come from the seed: they are constants of the
+ * goal here, so their seed rows are dropped and d_goal [B][n_goal*3] is computed from the goal pose (p_n = t,
+ * q_n = t + axis_length z), exactly as the cold call computes it.
+ *
+ * gik_anchored_seed_batch: the start point alone -- d_Y_free [B][N*3] and d_goal [B][n_goal*3], what
+ *   gik_solve_batch on `anch` takes.  d_ws: gik_anchored_ws_doubles(anch, base, B) doubles.
+ * gik_anchored_ik_batch_seeded: seed -> gather -> gik_solve_batch on `anch` -> full point matrix ->
+ *   gik_recover_batch on `base` -> clearance if d_clearance is not NULL; one stream, no host synchronisation.
+ *   The seed angles are read by the first kernel only, so d_q_init may alias d_q (path tracking: waypoint l
+ *   starts from waypoint l-1's answer in place).  The outputs are those of gik_anchored_ik_batch; the event
+ *   pair of gik_anchored_last_solve_ms is recorded around the solve kernel as there.
+ * gik_anchored_clearance: d_clearance [B] = min over (free node i with obs_node_mask[i] == 1, obstacle o) of
+ *   |Y_i - centre_o| - radius_o, read from a full point matrix d_Y_full [B][full_N*3] (radius_o is the square
+ *   root of the descriptor's squared radius).  >= 0: no masked node is inside a sphere.  Anchors are not
+ *   counted (the end effector sits where the goal puts it).  No obstacle, or no masked node: +infinity.  A NaN
+ *   coordinate of a masked node: NaN for that goal alone.
+ * Refused with a message before anything is queued: a capturing stream; an `anch` that is not a fixed-anchor
+ * template; a `base` without pipeline, with N != full_N, or that gik_seed_batch cannot seed (its reason is
+ * passed on); a null d_q_init or any other null buffer; B < 0.  B == 0 returns 0.                       */
+int gik_anchored_seed_batch(const gik_template *anch, const gik_template *base, const double *d_T_goal,
+                            const double *d_q_init, int B, double *d_ws, double *d_Y_free, double *d_goal,
+                            void *stream);
+int gik_anchored_clearance(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance,
+                           void *stream);
+int gik_anchored_ik_batch_seeded(const gik_template *anch, const gik_template *base, const double *d_T_goal,
+                                 const double *d_q_init, int B, double *d_ws, double *d_Y_full,
+                                 gik_stats *d_stats, double *d_q, double *d_pos_err, double *d_rot_err,
+                                 double *d_clearance /* may be NULL */, void *stream);
+
 /* Duration (ms, HIP events on the call's stream) of the anchored solve kernel inside the most
- * recent gik_anchored_ik_batch on this handle; waits for it.  < 0 if there was none.           */
+ * recent gik_anchored_ik_batch / gik_anchored_ik_batch_seeded on this handle; waits for it.  < 0 if there was none. */
 double gik_anchored_last_solve_ms(const gik_template *anch);
 
 #ifdef __cplusplus
