@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GIK_LIB_PATH") or os.path.join(_HERE, "lib", "libgraphik_amd.so")
 
 TERM_EQ, TERM_LOWER, TERM_UPPER = 1, 2, 3
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 
 class TemplateDesc(C.Structure):
@@ -107,6 +107,11 @@ class RetryOpts(C.Structure):
                 ("pos_tol", C.c_double), ("rot_tol", C.c_double), ("d_q_lo", C.c_void_p), ("d_q_hi", C.c_void_p)]
 
 
+class AnchoredRetryOpts(C.Structure):
+    """gik_anchored_retry_opts: gik_retry_opts + clear_tol, spread"""
+    _fields_ = RetryOpts._fields_ + [("clear_tol", C.c_double), ("spread", C.c_double)]
+
+
 class PrepareDiag(C.Structure):
     _fields_ = [("d_lb", C.c_void_p), ("d_ub", C.c_void_p), ("d_eig", C.c_void_p)]
 
@@ -130,6 +135,15 @@ SYMBOLS = {
     "gik_anchored_ik_batch_seeded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] +
                                      7 * [C.c_void_p] + [C.c_void_p]),
     "gik_anchored_last_solve_ms": (C.c_double, [C.c_void_p]),
+    "gik_anchored_retry_select": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double,
+                                            C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gik_anchored_retry_seeds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gik_anchored_retry_merge": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double,
+                                           C.c_double] + 13 * [C.c_void_p] + [C.c_void_p]),
+    "gik_anchored_retry_ws_bytes": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_int]),
+    "gik_anchored_ik_batch_retry": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                              C.POINTER(AnchoredRetryOpts)] + 8 * [C.c_void_p] + [C.c_void_p]),
     "gik_template_destroy": (None, [C.c_void_p]),
     "gik_template_get_info": (C.c_int, [C.c_void_p, C.POINTER(TemplateInfo)]),
     "gik_cost": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

@@ -6,6 +6,7 @@
 #include "gik_instances.h"
 #include "gik_retry.hip.h"
 #include "gik_anch_seed.hip.h"
+#include "gik_anch_retry.hip.h"
 #include "gik_plan.h"
 #include "gik_slots.h"
 #include <memory>
@@ -1702,6 +1703,215 @@ int gik_anchored_ik_batch_seeded(const gik_template *anch, const gik_template *b
   rc = gik_recover_batch(base, d_Y_full, d_T_goal, B, d_q, d_pos_err, d_rot_err, stream);
   if (rc || !d_clearance) return rc;
   return anchored_clearance_launch(anch, d_Y_full, B, d_clearance, stream);
+}
+
+// ---- restarts in the anchored solve, with a clearance rule (gik_anch_retry.hip.h) ------------------------
+int gik_anchored_retry_select(const gik_stats *d_stats, const double *d_pos_err, const double *d_rot_err,
+                              const double *d_clearance, int B, double pos_tol, double rot_tol, double clear_tol,
+                              int32_t *d_idx, int32_t *d_count, void *stream) {
+  using namespace gik;
+  if (B < 0) return fail("gik_anchored_retry_select: bad argument");
+  if (!d_idx || !d_count) return fail("gik_anchored_retry_select: null buffer");
+  HIP_OK(hipMemsetAsync(d_count, 0, sizeof(int32_t), (hipStream_t)stream));
+  if (B == 0) return 0;
+  if (!d_stats || !d_pos_err || !d_rot_err || !d_clearance) return fail("gik_anchored_retry_select: null buffer");
+  AnchRetrySelectArgs a;
+  a.stats = d_stats;
+  a.pos_err = d_pos_err;
+  a.rot_err = d_rot_err;
+  a.clearance = d_clearance;
+  a.tol = {pos_tol, rot_tol, clear_tol};
+  a.idx = d_idx;
+  a.count = d_count;
+  a.B = B;
+  hipLaunchKernelGGL(anch_retry_select_kernel, dim3((B + RETRY_WAVE - 1) / RETRY_WAVE), dim3(RETRY_WAVE), 0,
+                     (hipStream_t)stream, a);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int gik_anchored_retry_seeds(const gik_template *base, const double *d_T_goal, const int32_t *d_idx, int count,
+                             uint64_t seed, int attempt, const double *d_q_lo, const double *d_q_hi,
+                             const double *d_q_center, double spread, double *d_T_out, double *d_q_out, void *stream) {
+  using namespace gik;
+  if (!base || count < 0) return fail("gik_anchored_retry_seeds: bad argument");
+  if (!base->has_pipe) return fail("gik_anchored_retry_seeds: no pipeline attached to the base template (gik_pipeline_attach)");
+  if (attempt < 0 || attempt > 63) return fail("gik_anchored_retry_seeds: attempt must be within 0 .. 63");
+  if (!d_q_lo || !d_q_hi) return fail("gik_anchored_retry_seeds: null joint limits (d_q_lo / d_q_hi, [n] each, are required)");
+  if (!(spread >= 0.0)) return fail("gik_anchored_retry_seeds: spread must be at least 0");
+  if (spread > 0.0 && !d_q_center) return fail("gik_anchored_retry_seeds: spread > 0 needs the centre rows d_q_center [B][n]");
+  if (count == 0) return 0;
+  if (!d_T_goal || !d_idx || !d_T_out || !d_q_out) return fail("gik_anchored_retry_seeds: null buffer");
+  AnchRetrySeedArgs a;
+  a.T_goal = d_T_goal;
+  a.idx = d_idx;
+  a.q_lo = d_q_lo;
+  a.q_hi = d_q_hi;
+  a.q_center = d_q_center;
+  a.T_out = d_T_out;
+  a.q_out = d_q_out;
+  a.spread = spread;
+  a.seed = seed;
+  a.count = count;
+  a.pose_w = base->pc.n_ee * (base->f.K + 1) * (base->f.K + 1);
+  a.n = base->pc.n_joints;
+  a.attempt = attempt;
+  hipLaunchKernelGGL(anch_retry_seed_kernel, dim3(retry_grid(base, count)), dim3(RETRY_WAVE), 0, (hipStream_t)stream, a);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int gik_anchored_retry_merge(const gik_template *anch, const gik_template *base, const int32_t *d_idx, int count,
+                             int attempt, double pos_tol, double rot_tol, double clear_tol, const double *d_Y_r,
+                             const gik_stats *d_stats_r, const double *d_q_r, const double *d_pos_err_r,
+                             const double *d_rot_err_r, const double *d_clearance_r, double *d_Y_full, gik_stats *d_stats,
+                             double *d_q, double *d_pos_err, double *d_rot_err, double *d_clearance, int32_t *d_attempt,
+                             void *stream) {
+  using namespace gik;
+  if (!anch || !base || count < 0) return fail("gik_anchored_retry_merge: bad argument");
+  if (!anch->anchored) return fail("gik_anchored_retry_merge: the first handle must be a fixed-anchor template (gik_template_create_anchored)");
+  if (!base->has_pipe || base->N != anch->full_N)
+    return fail("gik_anchored_retry_merge: the base template must be the robot graph (full_N nodes) with its pipeline attached");
+  if (count == 0) return 0;
+  if (!d_idx || !d_Y_r || !d_stats_r || !d_q_r || !d_pos_err_r || !d_rot_err_r || !d_clearance_r || !d_Y_full || !d_stats ||
+      !d_q || !d_pos_err || !d_rot_err || !d_clearance || !d_attempt)
+    return fail("gik_anchored_retry_merge: null buffer");
+  AnchRetryMergeArgs a;
+  a.idx = d_idx;
+  a.Y_r = d_Y_r;
+  a.stats_r = d_stats_r;
+  a.q_r = d_q_r;
+  a.pos_r = d_pos_err_r;
+  a.rot_r = d_rot_err_r;
+  a.clear_r = d_clearance_r;
+  a.Y = d_Y_full;
+  a.stats = d_stats;
+  a.q = d_q;
+  a.pos_err = d_pos_err;
+  a.rot_err = d_rot_err;
+  a.clearance = d_clearance;
+  a.attempt = d_attempt;
+  a.tol = {pos_tol, rot_tol, clear_tol};
+  a.count = count;
+  a.row = anch->full_N * 3;
+  a.n = base->pc.n_joints;
+  a.attempt_no = attempt;
+  hipLaunchKernelGGL(anch_retry_merge_kernel, dim3(retry_grid(base, count)), dim3(RETRY_WAVE), 0, (hipStream_t)stream, a);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// The caller-owned workspace of gik_anchored_ik_batch_retry, every array sized for B failed goals:
+//   the scratch of one anchored call (gik_anchored_ws_doubles; attempt 0 and every restart use it in turn) |
+//   count (8 bytes) | idx [B] int32, padded to 8 bytes | poses | seed angles | centre angles | Y_full | stats | q |
+//   pos_err | rot_err | clearance
+namespace gik {
+struct AnchRetryWs {
+  double *scratch;
+  int32_t *count, *idx;
+  double *T, *q_seed, *q_center, *Y, *q, *pos_err, *rot_err, *clearance;
+  gik_stats *stats;
+  size_t bytes;
+};
+static AnchRetryWs anch_retry_ws(const gik_template *anch, const gik_template *base, int B, void *ws) {
+  const size_t b = (size_t)B, n = (size_t)base->pc.n_joints, pose_w = (size_t)base->pc.n_ee * (base->f.K + 1) * (base->f.K + 1);
+  const uintptr_t p = reinterpret_cast<uintptr_t>(ws);      // (null: gik_anchored_retry_ws_bytes only wants the size)
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    const uintptr_t at = p + off;
+    off += (bytes + 7) / 8 * 8;
+    return at;
+  };
+  AnchRetryWs w;
+  w.scratch = reinterpret_cast<double *>(take(gik_anchored_ws_doubles(anch, base, B) * sizeof(double)));
+  w.count = reinterpret_cast<int32_t *>(take(8));
+  w.idx = reinterpret_cast<int32_t *>(take(b * sizeof(int32_t)));
+  w.T = reinterpret_cast<double *>(take(b * pose_w * sizeof(double)));
+  w.q_seed = reinterpret_cast<double *>(take(b * n * sizeof(double)));
+  w.q_center = reinterpret_cast<double *>(take(b * n * sizeof(double)));
+  w.Y = reinterpret_cast<double *>(take(b * (size_t)anch->full_N * 3 * sizeof(double)));
+  w.stats = reinterpret_cast<gik_stats *>(take(b * sizeof(gik_stats)));
+  w.q = reinterpret_cast<double *>(take(b * n * sizeof(double)));
+  w.pos_err = reinterpret_cast<double *>(take(b * sizeof(double)));
+  w.rot_err = reinterpret_cast<double *>(take(b * sizeof(double)));
+  w.clearance = reinterpret_cast<double *>(take(b * sizeof(double)));
+  w.bytes = off;
+  return w;
+}
+}  // namespace gik
+
+size_t gik_anchored_retry_ws_bytes(const gik_template *anch, const gik_template *base, int B) {
+  if (!anch || !base || !anch->anchored || !base->has_pipe || base->N != anch->full_N || B < 0) return 0;
+  return gik::anch_retry_ws(anch, base, B, nullptr).bytes;
+}
+
+int gik_anchored_ik_batch_retry(const gik_template *anch, const gik_template *base, const double *d_T_goal,
+                                const double *d_q_init, int B, const gik_anchored_retry_opts *opts, void *d_ws,
+                                double *d_Y_full, gik_stats *d_stats, double *d_q, double *d_pos_err, double *d_rot_err,
+                                double *d_clearance, int32_t *d_attempt, void *stream) {
+  using namespace gik;
+  const std::string e("gik_anchored_ik_batch_retry");
+  // every refusal comes before anything is queued
+  if (!anch || !base || B < 0 || !opts) return fail(e + ": bad argument");
+  if (!anch->anchored) return fail(e + ": the first handle must be a fixed-anchor template (gik_template_create_anchored)");
+  if (!base->has_pipe || base->f.K != 3 || base->N != anch->full_N)
+    return fail(e + ": the base template must be the robot graph (full_N nodes) with its pipeline attached");
+  if (opts->retries < 0 || opts->retries > 63) return fail(e + ": retries must be within 0 .. 63");
+  if ((d_q_init || opts->retries > 0) && !base->seed_ok)
+    return fail(e + ": the base graph cannot be seeded on the device: " + base->seed_why);
+  if (opts->retries > 0) {
+    if (!opts->d_q_lo || !opts->d_q_hi)
+      return fail(e + ": null joint limits (opts->d_q_lo / d_q_hi, [n] each, are what the seeds are drawn from)");
+    if (!(opts->pos_tol > 0.0) || !(opts->rot_tol > 0.0)) return fail(e + ": pos_tol and rot_tol must be positive");
+    if (!(opts->clear_tol > 0.0)) return fail(e + ": clear_tol must be positive");
+    if (!(opts->spread >= 0.0)) return fail(e + ": spread must be at least 0 (radians; 0: uniform inside the limits)");
+    if (opts->spread > 0.0 && !d_q_init)
+      return fail(e + ": spread > 0 needs d_q_init, the centre the seeds are drawn around (a cold batch has none)");
+  }
+  if (refuse_capture("gik_anchored_ik_batch_retry", stream)) return -1;
+  if (B == 0) return 0;
+  if (!d_clearance || !d_attempt) return fail(e + ": null d_clearance or d_attempt");
+  if (!d_ws) return fail(e + ": null workspace (gik_anchored_retry_ws_bytes)");
+  if ((uintptr_t)d_ws % 8) return fail(e + ": the workspace must be 8-byte aligned");
+  if (!d_T_goal || !d_Y_full || !d_stats || !d_q || !d_pos_err || !d_rot_err) return fail(e + ": null buffer");
+  hipStream_t s = (hipStream_t)stream;
+  const AnchRetryWs w = anch_retry_ws(anch, base, B, d_ws);
+  const bool local = opts->retries > 0 && opts->spread > 0.0;
+  const size_t n = (size_t)base->pc.n_joints;
+  // the centre of local mode is what attempt 0 started from; d_q_init may be d_q, which attempt 0 overwrites
+  if (local) HIP_OK(hipMemcpyAsync(w.q_center, d_q_init, (size_t)B * n * sizeof(double), hipMemcpyDeviceToDevice, s));
+  HIP_OK(hipMemsetAsync(d_attempt, 0, (size_t)B * sizeof(int32_t), s));
+  int rc;
+  if (d_q_init) {
+    rc = gik_anchored_ik_batch_seeded(anch, base, d_T_goal, d_q_init, B, w.scratch, d_Y_full, d_stats, d_q, d_pos_err,
+                                      d_rot_err, d_clearance, stream);
+  } else {
+    rc = gik_anchored_ik_batch(anch, base, d_T_goal, B, w.scratch, d_Y_full, d_stats, d_q, d_pos_err, d_rot_err, stream);
+    if (!rc) rc = gik_anchored_clearance(anch, d_Y_full, B, d_clearance, stream);
+  }
+  if (rc) return rc;
+  for (int a = 1; a <= opts->retries; ++a) {
+    rc = gik_anchored_retry_select(d_stats, d_pos_err, d_rot_err, d_clearance, B, opts->pos_tol, opts->rot_tol,
+                                   opts->clear_tol, w.idx, w.count, stream);
+    if (rc) return rc;
+    // the solve kernels take their batch size from the host: the count comes back, the stream drains
+    int32_t count = 0;
+    HIP_OK(hipMemcpyAsync(&count, w.count, sizeof(count), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    if (count < 0 || count > B) return fail(e + ": the failed-goal count came back out of range");
+    if (count == 0) break;
+    rc = gik_anchored_retry_seeds(base, d_T_goal, w.idx, count, opts->seed, a, opts->d_q_lo, opts->d_q_hi,
+                                  local ? w.q_center : nullptr, local ? opts->spread : 0.0, w.T, w.q_seed, stream);
+    if (rc) return rc;
+    rc = gik_anchored_ik_batch_seeded(anch, base, w.T, w.q_seed, count, w.scratch, w.Y, w.stats, w.q, w.pos_err, w.rot_err,
+                                      w.clearance, stream);
+    if (rc) return rc;
+    rc = gik_anchored_retry_merge(anch, base, w.idx, count, a, opts->pos_tol, opts->rot_tol, opts->clear_tol, w.Y, w.stats,
+                                  w.q, w.pos_err, w.rot_err, w.clearance, d_Y_full, d_stats, d_q, d_pos_err, d_rot_err,
+                                  d_clearance, d_attempt, stream);
+    if (rc) return rc;
+  }
+  return 0;
 }
 
 double gik_anchored_last_solve_ms(const gik_template *anch) {

@@ -74,14 +74,23 @@ RETRY_MAX = 63          # attempts share 6 bits of the seed generator's counter 
 RETRY_MAX_JOINTS = 125
 
 
-def check_retry_args(retries, pos_tol, rot_tol, q_limits, n):
+def check_retry_args(retries, pos_tol, rot_tol, q_limits, n, clear_tol=None, retry_spread=0.0, has_center=True):
     """Arguments of a solve with restarts, checked on the host before any device call: retries within
     0 .. 63, positive tolerances, joint limits (q_lo [n], q_hi [n]) finite and ordered.  Returns
-    (retries, q_lo, q_hi) with the limits as contiguous float64 arrays; ValueError otherwise."""
+    (retries, q_lo, q_hi) with the limits as contiguous float64 arrays; ValueError otherwise.
+
+    The anchored solve adds clear_tol (positive; None: the rule has no clearance part) and retry_spread
+    (>= 0 radians; > 0 needs a centre: has_center says whether the call has a q_init)."""
     if int(retries) != retries or not 0 <= int(retries) <= RETRY_MAX:
         raise ValueError(f"retries must be an integer within 0 .. {RETRY_MAX}, got {retries!r}")
     if not (pos_tol > 0 and rot_tol > 0):
         raise ValueError("pos_tol and rot_tol must be positive")
+    if clear_tol is not None and not clear_tol > 0:
+        raise ValueError("clear_tol must be positive")
+    if not retry_spread >= 0:
+        raise ValueError(f"retry_spread must be at least 0 (radians), got {retry_spread!r}")
+    if retry_spread > 0 and not has_center:
+        raise ValueError("retry_spread > 0 needs q_init: local restarts are drawn around the seed, a cold solve has none")
     if n > RETRY_MAX_JOINTS:
         raise ValueError(f"restarts cover robots of at most {RETRY_MAX_JOINTS} joints")
     if q_limits is None:
@@ -512,15 +521,29 @@ class Template:
             _ffi.check(self.lib.gik_anchored_clearance(self._h, Y.data_ptr(), B, out.data_ptr(), self._stream()))
         return out
 
-    def anchored_ik(self, base, T_goal, q_init=None, out=None, clearance=False):
+    def anchored_ik(self, base, T_goal, q_init=None, out=None, clearance=False, retries=0, retry_seed=0, pos_tol=0.01,
+                    rot_tol=0.01, clear_tol=1e-4, retry_spread=0.0, q_limits=None):
         """Whole pipeline through the fixed-anchor solve: `base` is the robot graph's Template (no
         obstacles) with its pipeline attached.  Without q_init the start point is the robot graph's bound
         smoothing + MDS one fitted to the anchors (gik_anchored_ik_batch); with q_init (seed joint angles
         [B,n] or [n]; a device tensor may be out["q"] itself) it is the realization of q_init
         (gik_anchored_ik_batch_seeded).  clearance: also the device clearance of the answer.  `out`: the
         buffers of alloc_anchored_buffers, to reuse between calls.  Returns device tensors: x [B, full_N, 3]
-        (all robot-graph nodes, anchors included), q, pos_err, rot_err (+ clearance) + stats."""
+        (all robot-graph nodes, anchors included), q, pos_err, rot_err (+ clearance) + stats.
+
+        retries > 0 (gik_anchored_ik_batch_retry): goals that fail -- stop != 0, pos_err > pos_tol, rot_err >
+        rot_tol or clearance < -clear_tol -- are solved again, up to `retries` times, from joint angles drawn
+        inside q_limits = (q_lo [n], q_hi [n]) by the generator of Template.ik, keyed on (retry_seed, goal,
+        attempt): uniformly with retry_spread == 0, within retry_spread radians of q_init otherwise (which
+        q_init must then be there for).  The better answer is kept; "attempt" [B] int32 says which one each
+        goal holds, and "clearance" is always returned.  That call synchronises the stream once per attempt.
+        `out` may carry "attempt" [B] int32, "retry_ws" (gik_anchored_retry_ws_bytes) and "q_lo" / "q_hi"."""
         assert self.anchored and base.has_pipeline
+        if retries:      # (the clearance always comes back then: `clearance` is not read)
+            retries, lo, hi = check_retry_args(retries, pos_tol, rot_tol, q_limits, base.n_joints, clear_tol=clear_tol,
+                                               retry_spread=retry_spread, has_center=q_init is not None)
+            return self._anchored_ik_retry(base, T_goal, q_init, out, retries, lo, hi, retry_seed, pos_tol, rot_tol,
+                                           clear_tol, retry_spread)
         T, B = base._poses(T_goal)
         if out is None:
             out = self.alloc_anchored_buffers(base, B, clearance)
@@ -548,6 +571,37 @@ class Template:
                "rot_err": out["rot_err"], "_ws": ws}
         if clearance:
             res["clearance"] = cl
+        res.update(_decode_stats(out["stats"]))
+        return res
+
+    def _anchored_ik_retry(self, base, T_goal, q_init, out, retries, lo, hi, retry_seed, pos_tol, rot_tol, clear_tol,
+                           retry_spread):
+        """anchored_ik with retries > 0, its arguments already checked (check_retry_args: retries, lo, hi are what it
+        returns): one gik_anchored_ik_batch_retry call.  `out` needs no "ws": the restart workspace holds that scratch."""
+        T, B = base._poses(T_goal)
+        if out is None:
+            out = self.alloc_anchored_buffers(base, B, clearance=True)
+            del out["ws"]
+        dev = self.device
+        cl = out["clearance"] if "clearance" in out else torch.empty(B, dtype=torch.float64, device=dev)
+        attempt = out["attempt"] if "attempt" in out else torch.empty(B, dtype=torch.int32, device=dev)
+        ws = out.get("retry_ws")
+        nbytes = int(self.lib.gik_anchored_retry_ws_bytes(self._h, base._h, B))
+        if ws is None or ws.numel() * ws.element_size() < nbytes:
+            ws = torch.empty(max((nbytes + 7) // 8, 1), dtype=torch.float64, device=dev)
+        q_lo = out["q_lo"] if "q_lo" in out else _dev(lo, dev)
+        q_hi = out["q_hi"] if "q_hi" in out else _dev(hi, dev)
+        opts = _ffi.AnchoredRetryOpts(retries=retries, seed=int(retry_seed) & (2 ** 64 - 1), pos_tol=float(pos_tol),
+                                      rot_tol=float(rot_tol), d_q_lo=q_lo.data_ptr(), d_q_hi=q_hi.data_ptr(),
+                                      clear_tol=float(clear_tol), spread=float(retry_spread))
+        with torch.cuda.device(dev):
+            q0 = None if q_init is None else base._seed_angles(q_init, B)
+            _ffi.check(self.lib.gik_anchored_ik_batch_retry(
+                self._h, base._h, T.data_ptr(), None if q0 is None else q0.data_ptr(), B, C.byref(opts), ws.data_ptr(),
+                out["Y"].data_ptr(), out["stats"].data_ptr(), out["q"].data_ptr(), out["pos_err"].data_ptr(),
+                out["rot_err"].data_ptr(), cl.data_ptr(), attempt.data_ptr(), self._stream()))
+        res = {"x": out["Y"].reshape(B, self.full_N, 3), "q": out["q"], "pos_err": out["pos_err"],
+               "rot_err": out["rot_err"], "clearance": cl, "attempt": attempt, "_retry_ws": ws}
         res.update(_decode_stats(out["stats"]))
         return res
 

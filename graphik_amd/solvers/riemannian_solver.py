@@ -572,25 +572,50 @@ class AnchoredProblem:
         The host mirror of gik_anchored_seed_batch's Y_free."""
         return self.base.seed_points(q)[:, self.free]
 
-    def solve(self, T_goals, q_init=None, clearance=False):
+    def solve(self, T_goals, q_init=None, clearance=False, retries=0, retry_seed=0, pos_tol=0.01, rot_tol=0.01,
+              clear_tol=1e-4, retry_spread=0.0, q_limits=None):
         """Goal poses -> dict of device tensors (x [B, N_robot, 3], q, pos_err, rot_err, stats).
 
         q_init (warm start): joint angles [B,n] or [n]; the solve then starts from the realization of
         its seed (gik_anchored_ik_batch_seeded) instead of bound smoothing + MDS, the goal nodes still
         where the goal puts them.  clearance: add "clearance" [B], the device twin of
-        self.clearance(x) -- always there for a seeded solve."""
+        self.clearance(x) -- always there for a seeded solve and with retries > 0.
+
+        retries > 0 (gik_anchored_ik_batch_retry): a goal that fails -- stop != 0, pos_err > pos_tol, rot_err >
+        rot_tol or clearance < -clear_tol, so an answer on its goal with a link inside a sphere has failed -- is
+        solved again up to `retries` (<= 63) times from joint angles inside q_limits (default: the robot's
+        limits_arrays()), and the better answer is kept; "attempt" [B] int32 says which one each goal holds.
+        retry_spread == 0: the angles are uniform inside the limits, retry_seeds_host(retry_seed, [g], attempt,
+        lo, hi) are goal g's.  retry_spread > 0 (radians, needs q_init): they lie within retry_spread of q_init
+        (retry_seeds_host(..., center=q_init[g:g+1], spread=retry_spread)), for a tracked waypoint that
+        should stay on its IK branch."""
         T = np.asarray(T_goals, dtype=float)
+        if retries:      # checked here, before any device call, and once
+            q_limits = self.robot.limits_arrays() if q_limits is None else q_limits
+            retries, lo, hi = check_retry_args(retries, pos_tol, rot_tol, q_limits, self.robot.n, clear_tol=clear_tol,
+                                               retry_spread=retry_spread, has_center=q_init is not None)
+        if q_init is not None:
+            q_init = _seed_angles(q_init, T.shape[0], self.robot.n)
+        if retries:
+            return self.template._anchored_ik_retry(self.base.template, T, q_init, None, retries, lo, hi, retry_seed, pos_tol,
+                                                    rot_tol, clear_tol, retry_spread)
         if q_init is None:
             return self.template.anchored_ik(self.base.template, T, clearance=clearance)
-        q_init = _seed_angles(q_init, T.shape[0], self.robot.n)
         return self.template.anchored_ik(self.base.template, T, q_init=q_init, clearance=True)
 
-    def solve_trajectory(self, T_path, q_start, return_Y=False):
+    def solve_trajectory(self, T_path, q_start, return_Y=False, retries=0, retry_seed=0, pos_tol=0.01, rot_tol=0.01,
+                         clear_tol=1e-4, retry_spread=0.0, q_limits=None):
         """Path tracking among the obstacles: B paths of L waypoints, T_path [B, L, 4, 4].  Waypoint 0
         is seeded by q_start ([B,n] or [n]), waypoint l by the joint angles recovered at waypoint l-1,
         which never leave the device: L calls of gik_anchored_ik_batch_seeded on one stream, one
-        workspace, one synchronisation at the end.  A waypoint that fails still seeds the next one (no
-        retry): check info["stop"], info["f(x)"] and info["clearance"].
+        workspace, one synchronisation at the end.  With retries=0 a waypoint that fails still seeds the
+        next one (no retry): check info["stop"], info["f(x)"] and info["clearance"].
+
+        retries > 0: every waypoint is a solve(T[:, l], q_init=previous angles, retries=..., ...) -- a failed
+        waypoint (the rule of solve(), clearance included) is solved again before it seeds the next one, and
+        the rescued angles are what the next waypoint starts from.  retry_spread > 0 keeps the restarts within
+        that many radians of the previous waypoint's angles.  The stream then synchronises once per attempt
+        and waypoint; info["attempt"] [B, L] int32 says which attempt each waypoint holds.
 
         Returns q [B, L, n], Y [B, L, N_robot, 3] (None unless return_Y), and info with [B, L] arrays
         iterations, inner_iterations, stop, f(x), gradnorm, pos_err, rot_err, clearance, plus
@@ -599,6 +624,10 @@ class AnchoredProblem:
         B, L = T.shape[:2]
         n = self.robot.n
         q0 = _seed_angles(q_start, B, n, "q_start")
+        if retries:
+            q_limits = self.robot.limits_arrays() if q_limits is None else q_limits
+            retries, q_lo, q_hi = check_retry_args(retries, pos_tol, rot_tol, q_limits, n, clear_tol=clear_tol,
+                                                   retry_spread=retry_spread)
         tpl, base = self.template, self.base.template
         dev = tpl.device
         f64 = dict(dtype=torch.float64, device=dev)
@@ -608,14 +637,25 @@ class AnchoredProblem:
         stats = _alloc_stats(L * B, dev)
         stats = stats.reshape(L, B, stats.shape[1])
         pe, re, cl = (torch.empty(L, B, **f64) for _ in range(3))
-        ws = tpl.alloc_anchored_buffers(base, B)["ws"]
+        if retries:      # one restart workspace (it holds the anchored scratch too) and one copy of the limits for all waypoints
+            nbytes = int(tpl.lib.gik_anchored_retry_ws_bytes(tpl._h, base._h, B))
+            shared = {"retry_ws": torch.empty(max((nbytes + 7) // 8, 1), **f64), "q_lo": torch.from_numpy(q_lo).to(dev),
+                      "q_hi": torch.from_numpy(q_hi).to(dev)}
+            attempt = torch.empty(L, B, dtype=torch.int32, device=dev)
+        else:
+            shared = {"ws": tpl.alloc_anchored_buffers(base, B)["ws"]}
         q_prev = torch.from_numpy(q0).to(dev)
         torch.cuda.synchronize(dev)
         t0 = time.time()
         for l in range(L):
-            out = {"ws": ws, "Y": Y_all[l if return_Y else 0], "stats": stats[l], "q": q_all[l], "pos_err": pe[l],
-                   "rot_err": re[l], "clearance": cl[l]}
-            tpl.anchored_ik(base, Tw[l], q_init=q_prev, out=out, clearance=True)
+            out = {"Y": Y_all[l if return_Y else 0], "stats": stats[l], "q": q_all[l], "pos_err": pe[l],
+                   "rot_err": re[l], "clearance": cl[l], **shared}
+            if retries:
+                out["attempt"] = attempt[l]
+                tpl._anchored_ik_retry(base, Tw[l], q_prev, out, retries, q_lo, q_hi, retry_seed, pos_tol, rot_tol, clear_tol,
+                                       retry_spread)
+            else:
+                tpl.anchored_ik(base, Tw[l], q_init=q_prev, out=out, clearance=True)
             q_prev = q_all[l]
         torch.cuda.synchronize(dev)
         dt = time.time() - t0
@@ -623,6 +663,8 @@ class AnchoredProblem:
         info = {"iterations": st["iterations"], "inner_iterations": st["inner_total"], "stop": st["stop"],
                 "f(x)": st["f"], "gradnorm": st["gradnorm"], "pos_err": pe.reshape(-1), "rot_err": re.reshape(-1),
                 "clearance": cl.reshape(-1)}
+        if retries:
+            info["attempt"] = attempt.reshape(-1)
         info = {key: v.reshape(L, B).T.cpu().numpy() for key, v in info.items()}
         info["solve_time"] = dt
         q = q_all.permute(1, 0, 2).cpu().numpy()
@@ -723,13 +765,49 @@ def retry_uniform_host(seed, goals, attempt, n):
     return (z >> u64(11)).astype(np.float64) * 2.0 ** -53
 
 
-def retry_seeds_host(seed, goals, attempt, q_lo, q_hi):
+def retry_seeds_host(seed, goals, attempt, q_lo, q_hi, center=None, spread=0.0):
     """Host mirror of gik_retry_seeds: the joint angles [len(goals), n] that restart `attempt` of goals
     `goals` starts from, q = q_lo + u (q_hi - q_lo) with u from retry_uniform_host.  A function of
-    (seed, goal, attempt, joint) alone; the same bits as the device draws."""
+    (seed, goal, attempt, joint) alone; the same bits as the device draws.
+
+    spread > 0 (local mode of gik_anchored_retry_seeds): center [len(goals), n] holds the centre row of
+    each goal in `goals`, and q = min(max(center + spread (2u - 1), q_lo), q_hi) with the same u."""
     lo, hi = np.asarray(q_lo, dtype=np.float64), np.asarray(q_hi, dtype=np.float64)
     u = retry_uniform_host(seed, goals, attempt, len(lo))
-    return lo[None, :] + u * (hi - lo)[None, :]
+    if not spread >= 0:
+        raise ValueError("spread must be at least 0")
+    if spread == 0:
+        return lo[None, :] + u * (hi - lo)[None, :]
+    if center is None:
+        raise ValueError("spread > 0 needs the centre rows")
+    c = np.asarray(center, dtype=np.float64)
+    if c.shape != u.shape:
+        raise ValueError(f"center must have shape {list(u.shape)}, got {list(c.shape)}")
+    t = 2.0 * u - 1.0                                   # exact: u is a 53-bit fraction
+    return np.minimum(np.maximum(c + np.float64(spread) * t, lo[None, :]), hi[None, :])
+
+
+def anchored_retry_failed(stop, pos_err, rot_err, clearance, pos_tol=0.01, rot_tol=0.01, clear_tol=1e-4):
+    """Host mirror of the failure rule of gik_anchored_ik_batch_retry (include/graphik_amd.h), on arrays."""
+    stop, pos_err, rot_err, clearance = (np.asarray(a) for a in (stop, pos_err, rot_err, clearance))
+    with np.errstate(invalid="ignore"):
+        return (stop != 0) | ~(pos_err <= pos_tol) | ~(rot_err <= rot_tol) | ~(clearance >= -clear_tol)
+
+
+def anchored_retry_score(pos_err, rot_err, clearance, pos_tol=0.01, rot_tol=0.01, clear_tol=1e-4):
+    """... of the score: max(pos_err / pos_tol, rot_err / rot_tol, max(0, -clearance) / clear_tol), +inf for a NaN."""
+    pos_err, rot_err, clearance = (np.asarray(a, dtype=np.float64) for a in (pos_err, rot_err, clearance))
+    with np.errstate(invalid="ignore"):
+        s = np.maximum(np.maximum(pos_err / pos_tol, rot_err / rot_tol), np.maximum(0.0, -clearance) / clear_tol)
+    return np.where(np.isnan(s), np.inf, s)          # (np.maximum propagates NaN)
+
+
+def anchored_retry_better(new, old, pos_tol=0.01, rot_tol=0.01, clear_tol=1e-4):
+    """... of the merge order: new / old = (stop, pos_err, rot_err, clearance) arrays -> does `new` replace `old`?
+    A success beats a failure, within a class the smaller score wins, a NaN never wins, a tie keeps `old`."""
+    tol = (pos_tol, rot_tol, clear_tol)
+    ok_n, ok_o = ~anchored_retry_failed(*new, *tol), ~anchored_retry_failed(*old, *tol)
+    return (ok_n & ~ok_o) | ((ok_n == ok_o) & (anchored_retry_score(*new[1:], *tol) < anchored_retry_score(*old[1:], *tol)))
 
 
 def solve_batch(graph, T_goals, use_limits=True, params=None, device=None, Y_init=None, q_init=None,

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define GIK_ABI_VERSION 8
+#define GIK_ABI_VERSION 9
 
 /* Residual-term kinds: one "term" per (index pair, kind) exactly as the loops of
  * costs.py:80-207 visit them: equality (omega != 0), lower hinge (psi_L != 0), upper hinge
@@ -514,6 +514,85 @@ int gik_anchored_ik_batch_seeded(const gik_template *anch, const gik_template *b
                                  const double *d_q_init, int B, double *d_ws, double *d_Y_full,
                                  gik_stats *d_stats, double *d_q, double *d_pos_err, double *d_rot_err,
                                  double *d_clearance /* may be NULL */, void *stream);
+
+/* ---- restarts in the anchored solve, with a clearance rule (opt-in) -----------------------------
+ * The restarts of gik_ik_batch_retry for the fixed-anchor formulation.  The obstacle hinges are soft cost terms: an
+ * answer can stop on its gradient bar with the end effector on the goal and a link inside a sphere, which the rule
+ * of the plain restarts calls a success.  Here the rule also reads the answer's clearance (gik_anchored_clearance):
+ *
+ * failed(goal)  :=  stats.stop != 0  ||  !(pos_err <= pos_tol)  ||  !(rot_err <= rot_tol)  ||  !(clearance >= -clear_tol)
+ *                   -- a NaN clearance counts as failed; +infinity (no obstacle, no masked node) never fails a goal.
+ * score(goal)   :=  max(pos_err / pos_tol, rot_err / rot_tol, max(0, -clearance) / clear_tol);  +inf if any is NaN
+ * better(r, i)  :=  (r succeeds and i failed)  ||  (same success class  &&  score(r) < score(i))
+ *                   -- a NaN never wins, a tie keeps the incumbent.
+ *
+ * And the seeds have a second, local mode, for a goal that was itself seeded (a tracked waypoint): a seed drawn
+ * uniformly inside the limits usually lands on another IK branch, a joint jump; a seed drawn around the configuration
+ * the attempt started from stays near it.
+ *
+ * gik_anchored_retry_select: gik_retry_select with d_clearance [B] added and the rule above.
+ * gik_anchored_retry_seeds: the pose rows as gik_retry_seeds copies them (`base` gives their width and n), and
+ *   with spread == 0 (d_q_center is not read, may be NULL) the same angles, bit for bit:  q = lo + u (hi - lo).
+ *   With spread > 0, for goal g = d_idx[r] and the centre row c = d_q_center[g] (indexed by GOAL, [B][n]):
+ *       t = 2u - 1  (exact in fp64);   q = min(max(c + spread * t, lo), hi)      (one rounded product, one rounded sum)
+ *   with the same u(seed, g, attempt, j) as there.  A NaN centre gives a NaN seed.
+ *   graphik_amd.solvers.riemannian_solver.retry_seeds_host(..., center=, spread=) returns the same bits.
+ * gik_anchored_retry_merge: for compact slot r (one wavefront each), goal g = d_idx[r] (entries distinct): if the
+ *   restart's answer is better, the full point row (full_N * 3 doubles), the gik_stats record, the q row, pos_err,
+ *   rot_err and clearance of goal g are replaced together and d_attempt[g] = attempt; otherwise nothing of goal g
+ *   is written.
+ * gik_anchored_ik_batch_retry: attempt 0 is exactly gik_anchored_ik_batch followed by gik_anchored_clearance
+ *   (d_q_init NULL) or gik_anchored_ik_batch_seeded with the clearance output, on the caller's buffers, preceded by a
+ *   memset of d_attempt [B] to 0; with retries = 0 the call queues exactly that and nothing else.  Then for
+ *   a = 1 .. retries: select -> the 4-byte count is copied to the host -> stop if it is 0 -> seeds ->
+ *   gik_anchored_ik_batch_seeded with B' = count on compact buffers in d_ws, clearance included -> merge.
+ *   THIS CALL SYNCHRONISES ITS STREAM (hipStreamSynchronize) ONCE PER ATTEMPT after the first, as gik_ik_batch_retry
+ *   does and for its reason.  Synchronise the stream before reading the results.
+ *   Local mode (spread > 0): the centre is d_q_init.  d_q_init may alias d_q (path tracking), which attempt 0
+ *   overwrites, so the B n seed angles are copied into the workspace before attempt 0 and the seeds are centred on
+ *   the copy.
+ *   What comes back: the outputs of gik_anchored_ik_batch_seeded plus d_attempt[g] = the attempt whose answer goal g
+ *   holds.  The anchored solve runs on the wavefront kernel, whose bits do not depend on the batch, so a goal with
+ *   d_attempt[g] = a > 0 holds exactly what gik_anchored_ik_batch_seeded returns for that goal alone from the seed of
+ *   (seed, g, a).  gik_anchored_last_solve_ms reports the solve kernel of the LAST attempt that ran.
+ *   d_ws: caller-owned, gik_anchored_retry_ws_bytes(anch, base, B) bytes, 8-byte aligned: the scratch of one anchored
+ *   call (attempt 0 and the restarts use it in turn) plus compact buffers sized for the case that every goal fails.
+ *   It is needed with retries = 0 as well.
+ *   Refused, with a message, before anything is queued: what gik_anchored_ik_batch_seeded refuses (an `anch` that is
+ *   not a fixed-anchor template, a `base` without pipeline or with N != full_N, a capturing stream; a `base` that
+ *   cannot be seeded, if d_q_init is given or retries > 0); retries outside 0 .. 63; a null d_clearance, d_attempt or
+ *   workspace; and with retries > 0 null limits, a pos_tol, rot_tol or clear_tol that is not positive, a spread
+ *   that is negative or NaN, spread > 0 with a null d_q_init (a cold batch has no centre).  B == 0 returns 0.  */
+typedef struct {
+  int32_t retries;        /* further attempts for goals that failed: 0 .. 63                              */
+  int32_t reserved0;
+  uint64_t seed;          /* of the generator; the same seed gives the same answers                       */
+  double pos_tol;         /* a goal succeeds with stop == 0, pos_err <= pos_tol, rot_err <= rot_tol ...   */
+  double rot_tol;
+  const double *d_q_lo;   /* [n] device: the seeds stay inside [q_lo[j], q_hi[j]]                         */
+  const double *d_q_hi;   /* [n] device                                                                   */
+  double clear_tol;       /* ... and clearance >= -clear_tol (metres); must be positive                   */
+  double spread;          /* >= 0, radians.  0: seeds uniform inside the limits; > 0: within spread of d_q_init */
+} gik_anchored_retry_opts;
+
+int gik_anchored_retry_select(const gik_stats *d_stats, const double *d_pos_err, const double *d_rot_err,
+                              const double *d_clearance, int B, double pos_tol, double rot_tol, double clear_tol,
+                              int32_t *d_idx, int32_t *d_count, void *stream);
+int gik_anchored_retry_seeds(const gik_template *base, const double *d_T_goal, const int32_t *d_idx, int count,
+                             uint64_t seed, int attempt, const double *d_q_lo, const double *d_q_hi,
+                             const double *d_q_center /* [B][n]; may be NULL if spread == 0 */, double spread,
+                             double *d_T_out, double *d_q_out, void *stream);
+int gik_anchored_retry_merge(const gik_template *anch, const gik_template *base, const int32_t *d_idx, int count,
+                             int attempt, double pos_tol, double rot_tol, double clear_tol, const double *d_Y_r,
+                             const gik_stats *d_stats_r, const double *d_q_r, const double *d_pos_err_r,
+                             const double *d_rot_err_r, const double *d_clearance_r, double *d_Y_full,
+                             gik_stats *d_stats, double *d_q, double *d_pos_err, double *d_rot_err,
+                             double *d_clearance, int32_t *d_attempt, void *stream);
+size_t gik_anchored_retry_ws_bytes(const gik_template *anch, const gik_template *base, int B);
+int gik_anchored_ik_batch_retry(const gik_template *anch, const gik_template *base, const double *d_T_goal,
+                                const double *d_q_init /* may be NULL */, int B, const gik_anchored_retry_opts *opts,
+                                void *d_ws, double *d_Y_full, gik_stats *d_stats, double *d_q, double *d_pos_err,
+                                double *d_rot_err, double *d_clearance, int32_t *d_attempt, void *stream);
 
 /* Duration (ms, HIP events on the call's stream) of the anchored solve kernel inside the most
  * recent gik_anchored_ik_batch / gik_anchored_ik_batch_seeded on this handle; waits for it.  < 0 if there was none. */
