@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GIK_LIB_PATH") or os.path.join(_HERE, "lib", "libgraphik_amd.so")
 
 TERM_EQ, TERM_LOWER, TERM_UPPER = 1, 2, 3
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 
 class TemplateDesc(C.Structure):
@@ -103,13 +103,23 @@ class AnchoredDesc(C.Structure):
 
 class RetryOpts(C.Structure):
     """gik_retry_opts"""
-    _fields_ = [("retries", C.c_int32), ("reserved0", C.c_int32), ("seed", C.c_uint64),
+    _fields_ = [("retries", C.c_int32), ("clearance_mode", C.c_int32), ("seed", C.c_uint64),
                 ("pos_tol", C.c_double), ("rot_tol", C.c_double), ("d_q_lo", C.c_void_p), ("d_q_hi", C.c_void_p)]
 
 
 class AnchoredRetryOpts(C.Structure):
-    """gik_anchored_retry_opts: gik_retry_opts + clear_tol, spread"""
+    """gik_anchored_retry_opts: gik_retry_opts (whose clearance_mode is read here) + clear_tol, spread"""
     _fields_ = RetryOpts._fields_ + [("clear_tol", C.c_double), ("spread", C.c_double)]
+
+
+CLEARANCE_NODES, CLEARANCE_LINKS = 0, 1
+CLEARANCE_MODES = {"nodes": CLEARANCE_NODES, "links": CLEARANCE_LINKS}
+
+
+class LinkDesc(C.Structure):
+    """gik_link_desc"""
+    _fields_ = [("n_link", C.c_int32), ("reserved0", C.c_int32), ("link_a", C.POINTER(C.c_int32)),
+                ("link_b", C.POINTER(C.c_int32)), ("link_radius", C.POINTER(C.c_double))]
 
 
 class PrepareDiag(C.Structure):
@@ -132,6 +142,11 @@ SYMBOLS = {
     "gik_anchored_seed_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p]),
     "gik_anchored_clearance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "gik_anchored_attach_links": (C.c_int, [C.c_void_p, C.POINTER(LinkDesc)]),
+    "gik_anchored_link_clearance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "gik_anchored_sweep_ws_bytes": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "gik_anchored_sweep_clearance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                               C.c_void_p, C.c_void_p]),
     "gik_anchored_ik_batch_seeded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] +
                                      7 * [C.c_void_p] + [C.c_void_p]),
     "gik_anchored_last_solve_ms": (C.c_double, [C.c_void_p]),

@@ -1,7 +1,8 @@
 // graphik_amd/csrc/gik_anch_retry.hip.h -- restarts in the fixed-anchor (obstacle) solve, the device side.
 //
 // The restart kernels of gik_retry.hip.h with two additions: the failure rule reads the answer's clearance (an
-// answer that sits on its goal with a link inside a sphere has failed), and the seeds can be drawn around a centre
+// answer that sits on its goal with a joint point -- or, where the caller hands in the link clearance, any part of a
+// link -- inside a sphere has failed), and the seeds can be drawn around a centre
 // configuration instead of uniformly inside the joint limits.
 //
 //   anch_retry_select_kernel : one thread per goal: failed goals -> a compact index list (wave ballot, one atomic
@@ -20,7 +21,8 @@
 
 namespace gik {
 
-// failed: by the rule of the plain restarts, or a masked node deeper than clear_tol inside a sphere
+// failed: by the rule of the plain restarts, or deeper than clear_tol inside a sphere (a masked node, or a link: whichever
+// clearance the array holds)
 // (written so that a NaN clearance counts as failed; +inf -- no obstacle, no masked node -- never fails a goal)
 __host__ __device__ inline bool anch_retry_failed(int stop, double pos_err, double rot_err, double clearance, double pos_tol,
                                                   double rot_tol, double clear_tol) {

@@ -11,6 +11,14 @@
 //                           |Y_i - c_o| - r_o on a full point matrix.  Lanes stride over the pairs, then a wave
 //                           min-reduction by shuffles (no LDS, no atomics).  No pair: +inf.  A NaN coordinate of a
 //                           masked node: NaN for that goal.
+//   anch_link_clearance_kernel : the same wave, over (link l, obstacle o): the distance from the sphere's centre to the
+//                           SEGMENT between two rows of the point matrix, less the radius and the link's own
+//                           thickness (anch_link_pair).  A link can cross a sphere with both ends outside it, which
+//                           the node clearance does not see.  No pair: +inf.  A NaN coordinate of a link end: NaN.
+//   anch_sweep_interp_kernel / anch_sweep_min_kernel : the ends of gik_anchored_sweep_clearance -- the S + 1 joint
+//                           configurations between q_a and q_b (and the identity poses seed_kernel is handed with
+//                           them), one thread per double; and the minimum over the samples, one thread per goal.
+// anch_link_pair, anch_sweep_interp and anch_sweep_min are __host__ __device__, so that a host program can walk them.
 // Plain kernels, defined where GIK_DEFINE_ANCH_SEED_KERNELS is set (gik_k_anch_seed.hip); gik_host.hip sees prototypes.
 #pragma once
 
@@ -21,6 +29,7 @@
 namespace gik {
 
 constexpr int ANCH_SCATTER_NT = 256;
+constexpr int ANCH_MAXLINK = 64;   // links of gik_anchored_attach_links
 
 struct AnchClearArgs {
   const double *Y_full;      // [B][full_N*3]
@@ -29,6 +38,70 @@ struct AnchClearArgs {
   double *clearance;         // [B]
   int B, full_N, n_node, n_obs;
 };
+
+struct AnchLinkArgs {
+  const double *Y_full;      // [B][full_N*3]
+  const double *obs;         // [n_obs][4] x, y, z, r^2
+  const int *link_a, *link_b;   // [n_link] the ends of a link, as rows of the full point matrix
+  const double *link_rho;    // [n_link] capsule radius of a link, >= 0
+  double *clearance;         // [B]
+  int B, full_N, n_link, n_obs;
+};
+
+struct AnchSweepInterpArgs {
+  const double *q_a, *q_b;   // [B][n]
+  double *q_s;               // [S+1][B][n]  sample-major
+  double *T_id;              // [(S+1) B][pose_w] identity poses (seed_kernel's goal argument; nobody reads its targets)
+  int B, n, S, pose_w, D;    // D = 4: a pose is n_ee blocks of D x D
+};
+
+struct AnchSweepMinArgs {
+  const double *cl;          // [S+1][B]
+  double *clearance;         // [B]
+  int B, S;
+};
+
+// clearance of one (link, sphere) pair: a, b the link's ends, s = (centre, r^2), rho the link's radius.  The nearest
+// point of the segment is a + t (b - a), t clamped to [0, 1]; a zero-length link is its point.  Every product and sum
+// is rounded on its own (AnchoredProblem.link_clearance is the same operations in numpy).  A NaN in either end comes
+// out as NaN: one in b alone would otherwise be lost where L2 > 0 is false.
+__host__ __device__ inline double anch_link_pair(const double *a, const double *b, const double *s, double rho) {
+#pragma clang fp contract(off)
+  const double dx = b[0] - a[0], dy = b[1] - a[1], dz = b[2] - a[2];
+  const double L2 = dx * dx + dy * dy + dz * dz;
+  const double ux = s[0] - a[0], uy = s[1] - a[1], uz = s[2] - a[2];
+  double t = 0.0;
+  if (L2 > 0.0) {
+    t = (ux * dx + uy * dy + uz * dz) / L2;
+    t = t > 0.0 ? t : 0.0;
+    t = t < 1.0 ? t : 1.0;
+  }
+  const double vx = ux - t * dx, vy = uy - t * dy, vz = uz - t * dz;
+  const double v = sqrt(vx * vx + vy * vy + vz * vz) - sqrt(s[3]) - rho;
+  return L2 != L2 ? __builtin_nan("") : v;
+}
+
+// sample s of 0 .. S between two joint angles: two rounded products and one rounded sum, as the retry seeds are
+// written; s = 0 gives qa and s = S gives qb (finite angles; the sign of a zero aside)
+__host__ __device__ inline double anch_sweep_interp(double qa, double qb, int s, int S) {
+#pragma clang fp contract(off)
+  const double w = (double)s / (double)S;
+  const double pa = (1.0 - w) * qa;
+  const double pb = w * qb;
+  return pa + pb;
+}
+
+// min of n values `stride` apart; a NaN among them gives NaN (fmin would drop it)
+__host__ __device__ inline double anch_sweep_min(const double *c, int n, size_t stride) {
+  double m = __builtin_huge_val();
+  bool nan = false;
+  for (int s = 0; s < n; ++s) {
+    const double v = c[(size_t)s * stride];
+    nan |= v != v;
+    m = v < m ? v : m;
+  }
+  return nan ? __builtin_nan("") : m;
+}
 
 // (AnchGlueArgs: Y_full_in = seed_kernel's output, Y_free / anchor_goal out; Y_full_out unused)
 __global__ void __launch_bounds__(ANCH_SCATTER_NT) anch_scatter_kernel(AnchGlueArgs a)
@@ -75,6 +148,57 @@ __global__ void __launch_bounds__(WAVE) anch_clearance_kernel(AnchClearArgs a)
     if (__any(nan)) m = __builtin_nan("");
     if (lane == 0) a.clearance[b] = m;
   }
+}
+#endif
+
+__global__ void __launch_bounds__(WAVE) anch_link_clearance_kernel(AnchLinkArgs a)
+#ifndef GIK_DEFINE_ANCH_SEED_KERNELS
+    ;
+#else
+{
+  const int lane = threadIdx.x, pairs = a.n_link * a.n_obs;
+  for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
+    const double *Y = a.Y_full + (size_t)b * a.full_N * 3;
+    double m = __builtin_huge_val();
+    bool nan = false;
+    for (int p = lane; p < pairs; p += WAVE) {
+      const int l = p / a.n_obs, o = p - l * a.n_obs;
+      const double v = anch_link_pair(Y + a.link_a[l] * 3, Y + a.link_b[l] * 3, a.obs + o * 4, a.link_rho[l]);
+      nan |= v != v;
+      m = fmin(m, v);
+    }
+    for (int off = WAVE / 2; off > 0; off >>= 1) m = fmin(m, __shfl_xor(m, off));
+    if (__any(nan)) m = __builtin_nan("");
+    if (lane == 0) a.clearance[b] = m;
+  }
+}
+#endif
+
+__global__ void __launch_bounds__(ANCH_SCATTER_NT) anch_sweep_interp_kernel(AnchSweepInterpArgs a)
+#ifndef GIK_DEFINE_ANCH_SEED_KERNELS
+    ;
+#else
+{
+  const size_t row = (size_t)a.B * a.n, nQ = (size_t)(a.S + 1) * row, nT = (size_t)(a.S + 1) * a.B * a.pose_w;
+  const size_t t = (size_t)blockIdx.x * ANCH_SCATTER_NT + threadIdx.x;
+  if (t < nQ) {
+    const int s = (int)(t / row);
+    const size_t e = t - (size_t)s * row;
+    a.q_s[t] = anch_sweep_interp(a.q_a[e], a.q_b[e], s, a.S);
+  } else if (t - nQ < nT) {
+    const int e = (int)((t - nQ) % (size_t)(a.D * a.D));
+    a.T_id[t - nQ] = (e / a.D == e % a.D) ? 1.0 : 0.0;
+  }
+}
+#endif
+
+__global__ void __launch_bounds__(ANCH_SCATTER_NT) anch_sweep_min_kernel(AnchSweepMinArgs a)
+#ifndef GIK_DEFINE_ANCH_SEED_KERNELS
+    ;
+#else
+{
+  const size_t b = (size_t)blockIdx.x * ANCH_SCATTER_NT + threadIdx.x;
+  if (b < (size_t)a.B) a.clearance[b] = anch_sweep_min(a.cl + b, a.S + 1, (size_t)a.B);
 }
 #endif
 

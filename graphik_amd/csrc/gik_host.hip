@@ -9,6 +9,7 @@
 #include "gik_anch_retry.hip.h"
 #include "gik_plan.h"
 #include "gik_slots.h"
+#include <climits>
 #include <memory>
 
 namespace gik {
@@ -127,6 +128,10 @@ struct gik_template {
   int *d_free_full = nullptr, *d_anchor_full = nullptr;   // node index in the full robot graph
   int *d_clear_full = nullptr;      // [n_clear] ... of the free nodes that carry the obstacle hinges (anch_clearance_kernel)
   int n_clear = 0;
+  // the link set of gik_anchored_attach_links (anch_link_clearance_kernel); n_link < 0: none attached
+  int *d_link_a = nullptr, *d_link_b = nullptr;   // [n_link] rows of the full point matrix
+  double *d_link_rho = nullptr;                   // [n_link]
+  int n_link = -1;
   double axis_length = 1.0;
   int solver;
   gik::CgParams cg;
@@ -1673,6 +1678,139 @@ int gik_anchored_clearance(const gik_template *anch, const double *d_Y_full, int
   return anchored_clearance_launch(anch, d_Y_full, B, d_clearance, stream);
 }
 
+// ---- clearance of whole links, and its sweep between two configurations (gik_anch_seed.hip.h) -----------
+int gik_anchored_attach_links(gik_template *anch, const gik_link_desc *d) {
+  using namespace gik;
+  const std::string e("gik_anchored_attach_links");
+  if (!anch || !d) return fail(e + ": null argument");
+  if (!anch->anchored) return fail(e + ": the handle must be a fixed-anchor template (gik_template_create_anchored)");
+  if (anch->n_link >= 0) return fail(e + ": links already attached");
+  if (d->n_link < 0 || d->n_link > ANCH_MAXLINK) return fail(e + ": n_link must be within 0 .. 64");
+  if (d->n_link > 0 && (!d->link_a || !d->link_b || !d->link_radius)) return fail(e + ": null link array");
+  for (int l = 0; l < d->n_link; ++l) {
+    if (d->link_a[l] < 0 || d->link_a[l] >= anch->full_N || d->link_b[l] < 0 || d->link_b[l] >= anch->full_N)
+      return fail(e + ": link " + std::to_string(l) + " names a row outside [0, full_N)");
+    if (!(d->link_radius[l] >= 0.0) || d->link_radius[l] == __builtin_huge_val())
+      return fail(e + ": link_radius[" + std::to_string(l) + "] must be finite and at least 0");
+  }
+  bool ok = true;
+  int *la = const_cast<int *>(upload(anch, d->link_a, (size_t)d->n_link, ok));
+  int *lb = const_cast<int *>(upload(anch, d->link_b, (size_t)d->n_link, ok));
+  double *lr = const_cast<double *>(upload(anch, d->link_radius, (size_t)d->n_link, ok));
+  if (!ok) return fail(e + ": device upload failed");
+  anch->d_link_a = la;
+  anch->d_link_b = lb;
+  anch->d_link_rho = lr;
+  anch->n_link = d->n_link;
+  return 0;
+}
+
+static int anchored_link_clearance_launch(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance,
+                                          void *stream) {
+  using namespace gik;
+  AnchLinkArgs c;
+  c.Y_full = d_Y_full;
+  c.obs = anch->an.obs;
+  c.link_a = anch->d_link_a;
+  c.link_b = anch->d_link_b;
+  c.link_rho = anch->d_link_rho;
+  c.clearance = d_clearance;
+  c.B = B;
+  c.full_N = anch->full_N;
+  c.n_link = anch->n_link;
+  c.n_obs = anch->an.n_obs;
+  hipLaunchKernelGGL(anch_link_clearance_kernel, dim3(std::min(B, anch->f.n_cu * 32)), dim3(WAVE), 0, (hipStream_t)stream, c);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int gik_anchored_link_clearance(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance, void *stream) {
+  using gik::fail;
+  if (!anch || B < 0) return fail("gik_anchored_link_clearance: bad argument");
+  if (!anch->anchored) return fail("gik_anchored_link_clearance: the handle must be a fixed-anchor template (gik_template_create_anchored)");
+  if (anch->n_link < 0) return fail("gik_anchored_link_clearance: no links attached (gik_anchored_attach_links)");
+  if (refuse_capture("gik_anchored_link_clearance", stream)) return -1;
+  if (B == 0) return 0;
+  if (!d_Y_full || !d_clearance) return fail("gik_anchored_link_clearance: null buffer");
+  return anchored_link_clearance_launch(anch, d_Y_full, B, d_clearance, stream);
+}
+
+// The caller-owned workspace of gik_anchored_sweep_clearance, M = B (S + 1) configurations, all doubles:
+//   q_s [M][n] | identity poses [M][pose_w] | seed_kernel's targets [M][T_base] (not read) | Y [M][full_N*3] | clearance [M]
+namespace gik {
+struct AnchSweepWs {
+  double *q, *T, *targets, *Y, *cl;
+  size_t doubles;
+};
+static AnchSweepWs anch_sweep_ws(const gik_template *anch, const gik_template *base, int B, int S, double *ws) {
+  const size_t M = (size_t)B * ((size_t)S + 1), n = (size_t)base->pc.n_joints;
+  const size_t pose_w = (size_t)base->pc.n_ee * (base->f.K + 1) * (base->f.K + 1);
+  AnchSweepWs w;
+  w.q = ws;
+  w.T = w.q + M * n;
+  w.targets = w.T + M * pose_w;
+  w.Y = w.targets + M * (size_t)base->T;
+  w.cl = w.Y + M * (size_t)anch->full_N * 3;
+  w.doubles = M * (n + pose_w + (size_t)base->T + (size_t)anch->full_N * 3 + 1);
+  return w;
+}
+}  // namespace gik
+
+size_t gik_anchored_sweep_ws_bytes(const gik_template *anch, const gik_template *base, int B, int samples) {
+  if (!anch || !base || !anch->anchored || !base->has_pipe || base->N != anch->full_N || B < 0 || samples < 1 ||
+      (size_t)B * ((size_t)samples + 1) > (size_t)INT_MAX)
+    return 0;
+  return gik::anch_sweep_ws(anch, base, B, samples, nullptr).doubles * sizeof(double);
+}
+
+int gik_anchored_sweep_clearance(const gik_template *anch, const gik_template *base, const double *d_q_a,
+                                 const double *d_q_b, int B, int samples, double *d_ws, double *d_clearance, void *stream) {
+  using namespace gik;
+  const std::string e("gik_anchored_sweep_clearance");
+  if (!anch || !base || B < 0) return fail(e + ": bad argument");
+  if (!anch->anchored) return fail(e + ": the first handle must be a fixed-anchor template (gik_template_create_anchored)");
+  if (!base->has_pipe || base->f.K != 3 || base->N != anch->full_N)
+    return fail(e + ": the base template must be the robot graph (full_N nodes) with its pipeline attached");
+  if (!base->seed_ok) return fail(e + ": the base graph cannot be seeded on the device: " + base->seed_why);
+  if (anch->n_link < 0) return fail(e + ": no links attached (gik_anchored_attach_links)");
+  if (samples < 1) return fail(e + ": samples must be at least 1");
+  if ((size_t)B * ((size_t)samples + 1) > (size_t)INT_MAX) return fail(e + ": B (samples + 1) must fit an int");
+  if (refuse_capture("gik_anchored_sweep_clearance", stream)) return -1;
+  if (B == 0) return 0;
+  if (!d_q_a || !d_q_b || !d_ws || !d_clearance) return fail(e + ": null buffer");
+  const AnchSweepWs w = anch_sweep_ws(anch, base, B, samples, d_ws);
+  const int M = B * (samples + 1);
+  AnchSweepInterpArgs ia;
+  ia.q_a = d_q_a;
+  ia.q_b = d_q_b;
+  ia.q_s = w.q;
+  ia.T_id = w.T;
+  ia.B = B;
+  ia.n = base->pc.n_joints;
+  ia.S = samples;
+  ia.D = base->f.K + 1;
+  ia.pose_w = base->pc.n_ee * ia.D * ia.D;
+  const size_t nt = (size_t)M * ((size_t)ia.n + (size_t)ia.pose_w);
+  if ((nt + ANCH_SCATTER_NT - 1) / ANCH_SCATTER_NT > (size_t)INT_MAX) return fail(e + ": the batch is too large");
+  hipLaunchKernelGGL(anch_sweep_interp_kernel, dim3((unsigned)((nt + ANCH_SCATTER_NT - 1) / ANCH_SCATTER_NT)),
+                     dim3(ANCH_SCATTER_NT), 0, (hipStream_t)stream, ia);
+  HIP_OK(hipGetLastError());
+  // the realization of every sample: seed_kernel's joint-frame walk on the robot graph (its targets go unread)
+  int rc = gik_seed_batch(base, w.T, w.q, M, w.targets, w.Y, stream);
+  if (rc) return rc;
+  rc = anchored_link_clearance_launch(anch, w.Y, M, w.cl, stream);
+  if (rc) return rc;
+  AnchSweepMinArgs ma;
+  ma.cl = w.cl;
+  ma.clearance = d_clearance;
+  ma.B = B;
+  ma.S = samples;
+  hipLaunchKernelGGL(anch_sweep_min_kernel, dim3((B + ANCH_SCATTER_NT - 1) / ANCH_SCATTER_NT), dim3(ANCH_SCATTER_NT), 0,
+                     (hipStream_t)stream, ma);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
 int gik_anchored_ik_batch_seeded(const gik_template *anch, const gik_template *base, const double *d_T_goal,
                                  const double *d_q_init, int B, double *d_ws, double *d_Y_full, gik_stats *d_stats,
                                  double *d_q, double *d_pos_err, double *d_rot_err, double *d_clearance, void *stream) {
@@ -1857,6 +1995,10 @@ int gik_anchored_ik_batch_retry(const gik_template *anch, const gik_template *ba
   if (!base->has_pipe || base->f.K != 3 || base->N != anch->full_N)
     return fail(e + ": the base template must be the robot graph (full_N nodes) with its pipeline attached");
   if (opts->retries < 0 || opts->retries > 63) return fail(e + ": retries must be within 0 .. 63");
+  if (opts->clearance_mode != GIK_CLEARANCE_NODES && opts->clearance_mode != GIK_CLEARANCE_LINKS)
+    return fail(e + ": clearance_mode must be GIK_CLEARANCE_NODES (0) or GIK_CLEARANCE_LINKS (1)");
+  const bool links = opts->clearance_mode == GIK_CLEARANCE_LINKS;
+  if (links && anch->n_link < 0) return fail(e + ": clearance_mode = links, but no links attached (gik_anchored_attach_links)");
   if ((d_q_init || opts->retries > 0) && !base->seed_ok)
     return fail(e + ": the base graph cannot be seeded on the device: " + base->seed_why);
   if (opts->retries > 0) {
@@ -1884,11 +2026,13 @@ int gik_anchored_ik_batch_retry(const gik_template *anch, const gik_template *ba
   int rc;
   if (d_q_init) {
     rc = gik_anchored_ik_batch_seeded(anch, base, d_T_goal, d_q_init, B, w.scratch, d_Y_full, d_stats, d_q, d_pos_err,
-                                      d_rot_err, d_clearance, stream);
+                                      d_rot_err, links ? nullptr : d_clearance, stream);
   } else {
     rc = gik_anchored_ik_batch(anch, base, d_T_goal, B, w.scratch, d_Y_full, d_stats, d_q, d_pos_err, d_rot_err, stream);
-    if (!rc) rc = gik_anchored_clearance(anch, d_Y_full, B, d_clearance, stream);
+    if (!rc && !links) rc = gik_anchored_clearance(anch, d_Y_full, B, d_clearance, stream);
   }
+  // link mode: the rule below is the same, the array it reads holds the clearance of whole links
+  if (!rc && links) rc = anchored_link_clearance_launch(anch, d_Y_full, B, d_clearance, stream);
   if (rc) return rc;
   for (int a = 1; a <= opts->retries; ++a) {
     rc = gik_anchored_retry_select(d_stats, d_pos_err, d_rot_err, d_clearance, B, opts->pos_tol, opts->rot_tol,
@@ -1904,7 +2048,8 @@ int gik_anchored_ik_batch_retry(const gik_template *anch, const gik_template *ba
                                   local ? w.q_center : nullptr, local ? opts->spread : 0.0, w.T, w.q_seed, stream);
     if (rc) return rc;
     rc = gik_anchored_ik_batch_seeded(anch, base, w.T, w.q_seed, count, w.scratch, w.Y, w.stats, w.q, w.pos_err, w.rot_err,
-                                      w.clearance, stream);
+                                      links ? nullptr : w.clearance, stream);
+    if (!rc && links) rc = anchored_link_clearance_launch(anch, w.Y, count, w.clearance, stream);
     if (rc) return rc;
     rc = gik_anchored_retry_merge(anch, base, w.idx, count, a, opts->pos_tol, opts->rot_tol, opts->clear_tol, w.Y, w.stats,
                                   w.q, w.pos_err, w.rot_err, w.clearance, d_Y_full, d_stats, d_q, d_pos_err, d_rot_err,

@@ -105,6 +105,16 @@ def check_retry_args(retries, pos_tol, rot_tol, q_limits, n, clear_tol=None, ret
     return int(retries), lo, hi
 
 
+def check_clearance_mode(clearance_mode, has_links=True):
+    """clearance_mode of an anchored solve -> gik_anchored_retry_opts.clearance_mode (0 nodes, 1 links), checked on the
+    host before any device call: ValueError for another word, and for "links" where no links are attached."""
+    if clearance_mode not in _ffi.CLEARANCE_MODES:
+        raise ValueError(f"clearance_mode must be 'nodes' or 'links', got {clearance_mode!r}")
+    if clearance_mode == "links" and not has_links:
+        raise ValueError("clearance_mode='links' needs a link set: this problem was built without links")
+    return _ffi.CLEARANCE_MODES[clearance_mode]
+
+
 class Template:
     """Goal-independent part of an IK problem family, resident on one GPU."""
 
@@ -186,6 +196,7 @@ class Template:
                 self.n_goal_anchor, self.full_N = ad.n_goal_anchor, ad.full_N
                 _ffi.check(self.lib.gik_template_create_anchored(C.byref(d), C.byref(ad), C.byref(h)))
         self._h = h
+        self.n_link = None      # (attach_links)
         self._read_info()
         deg = np.bincount(np.concatenate([self.term_i, self.term_j]), minlength=self.N).max()
         # compiled slot count of the wavefront variant the library chose (or the raw degree: workgroup / node-per-lane paths)
@@ -521,8 +532,65 @@ class Template:
             _ffi.check(self.lib.gik_anchored_clearance(self._h, Y.data_ptr(), B, out.data_ptr(), self._stream()))
         return out
 
+    def attach_links(self, link_a, link_b, link_radius):
+        """The link set of an anchored template (gik_anchored_attach_links), once: link l is the segment between rows
+        link_a[l] and link_b[l] of the full point matrix, a capsule of radius link_radius[l] >= 0 (metres)."""
+        assert self.anchored
+        a = np.ascontiguousarray(link_a, dtype=np.int32).reshape(-1)
+        b = np.ascontiguousarray(link_b, dtype=np.int32).reshape(-1)
+        r = np.ascontiguousarray(link_radius, dtype=np.float64).reshape(-1)
+        if not len(a) == len(b) == len(r):
+            raise ValueError("link_a, link_b and link_radius must have one entry per link")
+        d = _ffi.LinkDesc(n_link=len(a), link_a=a.ctypes.data_as(C.POINTER(C.c_int32)),
+                          link_b=b.ctypes.data_as(C.POINTER(C.c_int32)),
+                          link_radius=r.ctypes.data_as(C.POINTER(C.c_double)))
+        with torch.cuda.device(self.device):
+            _ffi.check(self.lib.gik_anchored_attach_links(self._h, C.byref(d)))
+        self.n_link = len(a)
+
+    def anchored_link_clearance(self, Y_full):
+        """Full point matrices [B, full_N, 3] -> link clearance [B] on the device (gik_anchored_link_clearance): the
+        minimum over the attached links and the obstacles of the distance from the sphere to the link's capsule;
+        +inf without obstacles or links."""
+        assert self.anchored
+        Y = _dev(Y_full, self.device)
+        if Y.dim() == 2:
+            Y = Y[None]
+        B = Y.shape[0]
+        assert Y.numel() == B * self.full_N * 3, (tuple(Y.shape), (B, self.full_N, 3))
+        Y = Y.reshape(B, self.full_N * 3).contiguous()
+        out = torch.empty(B, dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _ffi.check(self.lib.gik_anchored_link_clearance(self._h, Y.data_ptr(), B, out.data_ptr(), self._stream()))
+        return out
+
+    def anchored_sweep_clearance(self, base, q_a, q_b, samples, out=None, ws=None):
+        """Joint angles q_a, q_b [B,n] (device tensors or arrays) -> [B]: the minimum link clearance over the samples + 1
+        configurations on the joint-space line from q_a to q_b (gik_anchored_sweep_clearance).  Sampled, not
+        conservative: pick `samples` from the joint step.  `out` [B] and `ws` (gik_anchored_sweep_ws_bytes, as float64)
+        may be handed in to reuse."""
+        assert self.anchored and base.has_pipeline
+        if int(samples) != samples or samples < 1:
+            raise ValueError(f"samples must be an integer of at least 1, got {samples!r}")
+        qa, qb = _dev(q_a, self.device), _dev(q_b, self.device)
+        n = base.n_joints
+        if qa.dim() != 2 or qa.shape[1] != n or qa.shape != qb.shape:
+            raise ValueError(f"q_a and q_b must both have shape [B, {n}], got {list(qa.shape)} and {list(qb.shape)}")
+        qa, qb = qa.contiguous(), qb.contiguous()
+        B, S = qa.shape[0], int(samples)
+        if out is None:
+            out = torch.empty(B, dtype=torch.float64, device=self.device)
+        nbytes = int(self.lib.gik_anchored_sweep_ws_bytes(self._h, base._h, B, S))
+        if ws is None or ws.numel() * ws.element_size() < nbytes:
+            ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=self.device)
+        assert out.is_contiguous() and out.numel() == B
+        with torch.cuda.device(self.device):
+            _ffi.check(self.lib.gik_anchored_sweep_clearance(self._h, base._h, qa.data_ptr(), qb.data_ptr(), B, S,
+                                                             ws.data_ptr(), out.data_ptr(), self._stream()))
+        return out      # (ws goes back to the allocator of this stream, behind the kernels that use it)
+
     def anchored_ik(self, base, T_goal, q_init=None, out=None, clearance=False, retries=0, retry_seed=0, pos_tol=0.01,
-                    rot_tol=0.01, clear_tol=1e-4, retry_spread=0.0, q_limits=None):
+                    rot_tol=0.01, clear_tol=1e-4, retry_spread=0.0, q_limits=None, clearance_mode="nodes"):
         """Whole pipeline through the fixed-anchor solve: `base` is the robot graph's Template (no
         obstacles) with its pipeline attached.  Without q_init the start point is the robot graph's bound
         smoothing + MDS one fitted to the anchors (gik_anchored_ik_batch); with q_init (seed joint angles
@@ -537,13 +605,18 @@ class Template:
         attempt): uniformly with retry_spread == 0, within retry_spread radians of q_init otherwise (which
         q_init must then be there for).  The better answer is kept; "attempt" [B] int32 says which one each
         goal holds, and "clearance" is always returned.  That call synchronises the stream once per attempt.
-        `out` may carry "attempt" [B] int32, "retry_ws" (gik_anchored_retry_ws_bytes) and "q_lo" / "q_hi"."""
+        `out` may carry "attempt" [B] int32, "retry_ws" (gik_anchored_retry_ws_bytes) and "q_lo" / "q_hi".
+
+        clearance_mode: "nodes" (the joint points, gik_anchored_clearance) or "links" (whole links,
+        gik_anchored_link_clearance; needs attach_links): which clearance comes back and the restart rule reads."""
         assert self.anchored and base.has_pipeline
+        mode = check_clearance_mode(clearance_mode, getattr(self, "n_link", None) is not None)
         if retries:      # (the clearance always comes back then: `clearance` is not read)
             retries, lo, hi = check_retry_args(retries, pos_tol, rot_tol, q_limits, base.n_joints, clear_tol=clear_tol,
                                                retry_spread=retry_spread, has_center=q_init is not None)
             return self._anchored_ik_retry(base, T_goal, q_init, out, retries, lo, hi, retry_seed, pos_tol, rot_tol,
-                                           clear_tol, retry_spread)
+                                           clear_tol, retry_spread, mode)
+        clear_fn = self.lib.gik_anchored_link_clearance if mode == _ffi.CLEARANCE_LINKS else self.lib.gik_anchored_clearance
         T, B = base._poses(T_goal)
         if out is None:
             out = self.alloc_anchored_buffers(base, B, clearance)
@@ -559,14 +632,16 @@ class Template:
                                                           out["q"].data_ptr(), out["pos_err"].data_ptr(),
                                                           out["rot_err"].data_ptr(), self._stream()))
                 if clearance:
-                    _ffi.check(self.lib.gik_anchored_clearance(self._h, out["Y"].data_ptr(), B, cl.data_ptr(),
-                                                               self._stream()))
+                    _ffi.check(clear_fn(self._h, out["Y"].data_ptr(), B, cl.data_ptr(), self._stream()))
             else:
                 q0 = base._seed_angles(q_init, B)
+                links = cl is not None and mode == _ffi.CLEARANCE_LINKS
                 _ffi.check(self.lib.gik_anchored_ik_batch_seeded(
                     self._h, base._h, T.data_ptr(), q0.data_ptr(), B, ws.data_ptr(), out["Y"].data_ptr(),
                     out["stats"].data_ptr(), out["q"].data_ptr(), out["pos_err"].data_ptr(), out["rot_err"].data_ptr(),
-                    None if cl is None else cl.data_ptr(), self._stream()))
+                    None if cl is None or links else cl.data_ptr(), self._stream()))
+                if links:
+                    _ffi.check(clear_fn(self._h, out["Y"].data_ptr(), B, cl.data_ptr(), self._stream()))
         res = {"x": out["Y"].reshape(B, self.full_N, 3), "q": out["q"], "pos_err": out["pos_err"],
                "rot_err": out["rot_err"], "_ws": ws}
         if clearance:
@@ -575,9 +650,10 @@ class Template:
         return res
 
     def _anchored_ik_retry(self, base, T_goal, q_init, out, retries, lo, hi, retry_seed, pos_tol, rot_tol, clear_tol,
-                           retry_spread):
+                           retry_spread, clearance_mode=_ffi.CLEARANCE_NODES):
         """anchored_ik with retries > 0, its arguments already checked (check_retry_args: retries, lo, hi are what it
-        returns): one gik_anchored_ik_batch_retry call.  `out` needs no "ws": the restart workspace holds that scratch."""
+        returns; check_clearance_mode: clearance_mode): one gik_anchored_ik_batch_retry call.  `out` needs no "ws": the
+        restart workspace holds that scratch."""
         T, B = base._poses(T_goal)
         if out is None:
             out = self.alloc_anchored_buffers(base, B, clearance=True)
@@ -591,7 +667,7 @@ class Template:
             ws = torch.empty(max((nbytes + 7) // 8, 1), dtype=torch.float64, device=dev)
         q_lo = out["q_lo"] if "q_lo" in out else _dev(lo, dev)
         q_hi = out["q_hi"] if "q_hi" in out else _dev(hi, dev)
-        opts = _ffi.AnchoredRetryOpts(retries=retries, seed=int(retry_seed) & (2 ** 64 - 1), pos_tol=float(pos_tol),
+        opts = _ffi.AnchoredRetryOpts(retries=retries, clearance_mode=int(clearance_mode), seed=int(retry_seed) & (2 ** 64 - 1), pos_tol=float(pos_tol),
                                       rot_tol=float(rot_tol), d_q_lo=q_lo.data_ptr(), d_q_hi=q_hi.data_ptr(),
                                       clear_tol=float(clear_tol), spread=float(retry_spread))
         with torch.cuda.device(dev):

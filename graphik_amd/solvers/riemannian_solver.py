@@ -16,7 +16,7 @@ import time
 import numpy as np
 import torch
 
-from ..engine import Template, _alloc_stats, _decode_stats, build_terms, check_retry_args
+from ..engine import Template, _alloc_stats, _decode_stats, build_terms, check_clearance_mode, check_retry_args
 from ..utils import dgp
 from ..utils.constants import POS
 from ..utils.lie import as_matrix
@@ -499,9 +499,14 @@ class AnchoredProblem:
     add_spherical_obstacle).  The initial point is the robot graph's own (bound smoothing + MDS
     without obstacles) fitted to the world frame by its anchors."""
 
-    def __init__(self, graph, params=None, device=None, host_only=False):
+    def __init__(self, graph, params=None, device=None, host_only=False, links=None, link_radius=0.0):
         """host_only: derive the term set only (no device handles) -- what tests/test_host_layer.py
-        compares with the reference's own edge construction (tests/golden/ur10_table_intended.npz)."""
+        compares with the reference's own edge construction (tests/golden/ur10_table_intended.npz).
+
+        links: the segments whose clearance link_clearance / clearance_mode="links" measure, as (name_a, name_b)
+        pairs of robot-graph nodes.  None: the chain's skeleton p0->p1, ..., p(n-1)->pn, base and end-effector rows
+        included (the last link is real geometry even though its end is a constant of the goal).  [] attaches none.
+        link_radius: the capsule radius of the links in metres, >= 0, a scalar or one entry per link."""
         import copy
         from ..utils.constants import OBSTACLE, ROBOT, TYPE, MAIN_PREFIX
         from .. import _ffi
@@ -551,6 +556,22 @@ class AnchoredProblem:
         self.free_names = names
         self.free_terms = (ti, tj, tk, target)
         self.obs_mask = np.array(mask, dtype=np.int32)
+        if links is None:
+            links = [(f"p{i}", f"p{i + 1}") for i in range(self.robot.n)]
+        links = [tuple(l) for l in links]
+        for l in links:
+            if len(l) != 2 or any(name not in bare.node_ids for name in l):
+                raise ValueError(f"link {l!r}: a link is a pair of node names of the robot graph")
+        self.link_names = links
+        self.link_rows = np.array([[bare.index(a), bare.index(b)] for a, b in links], dtype=np.int32).reshape(-1, 2)
+        rho = np.asarray(link_radius, dtype=np.float64)
+        if rho.ndim == 0:
+            rho = np.full(len(links), float(rho))
+        if rho.shape != (len(links),):
+            raise ValueError(f"link_radius must be a scalar or have one entry per link ({len(links)}), got shape {list(rho.shape)}")
+        if not np.all(np.isfinite(rho) & (rho >= 0)):
+            raise ValueError("link_radius must be finite and at least 0")
+        self.link_radius = np.ascontiguousarray(rho)
         if host_only:
             self.template = None
             return
@@ -561,6 +582,8 @@ class AnchoredProblem:
                           pin_kind=[p[2] for p in pin], pin_target=[p[3] for p in pin],
                           obs=obs, obs_node_mask=mask, full_N=N, free_full_index=free,
                           anchor_full_index=anchors, axis_length=graph.axis_length))
+        if len(links):
+            self.template.attach_links(self.link_rows[:, 0], self.link_rows[:, 1], self.link_radius)
 
     def goal_anchors(self, T_goals):
         """[B,4,4] -> [B, 2*3]: p_n, q_n world positions (graph_revolute.py:243-249)."""
@@ -573,7 +596,7 @@ class AnchoredProblem:
         return self.base.seed_points(q)[:, self.free]
 
     def solve(self, T_goals, q_init=None, clearance=False, retries=0, retry_seed=0, pos_tol=0.01, rot_tol=0.01,
-              clear_tol=1e-4, retry_spread=0.0, q_limits=None):
+              clear_tol=1e-4, retry_spread=0.0, q_limits=None, clearance_mode="nodes"):
         """Goal poses -> dict of device tensors (x [B, N_robot, 3], q, pos_err, rot_err, stats).
 
         q_init (warm start): joint angles [B,n] or [n]; the solve then starts from the realization of
@@ -581,15 +604,20 @@ class AnchoredProblem:
         where the goal puts them.  clearance: add "clearance" [B], the device twin of
         self.clearance(x) -- always there for a seeded solve and with retries > 0.
 
+        clearance_mode: "nodes" -- "clearance" is that of the joint points (self.clearance), which does not see a
+        link that crosses a sphere between two of them -- or "links": it is that of whole links
+        (self.link_clearance; the problem must have links), with retries=0 too.
+
         retries > 0 (gik_anchored_ik_batch_retry): a goal that fails -- stop != 0, pos_err > pos_tol, rot_err >
-        rot_tol or clearance < -clear_tol, so an answer on its goal with a link inside a sphere has failed -- is
-        solved again up to `retries` (<= 63) times from joint angles inside q_limits (default: the robot's
+        rot_tol or clearance < -clear_tol, so an answer on its goal with a joint point (clearance_mode="nodes") or
+        any part of a link ("links") inside a sphere has failed -- is solved again up to `retries` (<= 63) times from joint angles inside q_limits (default: the robot's
         limits_arrays()), and the better answer is kept; "attempt" [B] int32 says which one each goal holds.
         retry_spread == 0: the angles are uniform inside the limits, retry_seeds_host(retry_seed, [g], attempt,
         lo, hi) are goal g's.  retry_spread > 0 (radians, needs q_init): they lie within retry_spread of q_init
         (retry_seeds_host(..., center=q_init[g:g+1], spread=retry_spread)), for a tracked waypoint that
         should stay on its IK branch."""
         T = np.asarray(T_goals, dtype=float)
+        mode = check_clearance_mode(clearance_mode, len(self.link_names) > 0)
         if retries:      # checked here, before any device call, and once
             q_limits = self.robot.limits_arrays() if q_limits is None else q_limits
             retries, lo, hi = check_retry_args(retries, pos_tol, rot_tol, q_limits, self.robot.n, clear_tol=clear_tol,
@@ -598,13 +626,13 @@ class AnchoredProblem:
             q_init = _seed_angles(q_init, T.shape[0], self.robot.n)
         if retries:
             return self.template._anchored_ik_retry(self.base.template, T, q_init, None, retries, lo, hi, retry_seed, pos_tol,
-                                                    rot_tol, clear_tol, retry_spread)
+                                                    rot_tol, clear_tol, retry_spread, mode)
         if q_init is None:
-            return self.template.anchored_ik(self.base.template, T, clearance=clearance)
-        return self.template.anchored_ik(self.base.template, T, q_init=q_init, clearance=True)
+            return self.template.anchored_ik(self.base.template, T, clearance=clearance, clearance_mode=clearance_mode)
+        return self.template.anchored_ik(self.base.template, T, q_init=q_init, clearance=True, clearance_mode=clearance_mode)
 
     def solve_trajectory(self, T_path, q_start, return_Y=False, retries=0, retry_seed=0, pos_tol=0.01, rot_tol=0.01,
-                         clear_tol=1e-4, retry_spread=0.0, q_limits=None):
+                         clear_tol=1e-4, retry_spread=0.0, q_limits=None, clearance_mode="nodes", sweep=None):
         """Path tracking among the obstacles: B paths of L waypoints, T_path [B, L, 4, 4].  Waypoint 0
         is seeded by q_start ([B,n] or [n]), waypoint l by the joint angles recovered at waypoint l-1,
         which never leave the device: L calls of gik_anchored_ik_batch_seeded on one stream, one
@@ -617,6 +645,13 @@ class AnchoredProblem:
         that many radians of the previous waypoint's angles.  The stream then synchronises once per attempt
         and waypoint; info["attempt"] [B, L] int32 says which attempt each waypoint holds.
 
+        clearance_mode: as in solve() -- which clearance info["clearance"] holds and the rule reads.
+        sweep=S (an integer >= 1; the problem must have links): adds info["sweep_clearance"] [B, L], the minimum link
+        clearance over S + 1 joint-space samples between waypoint l-1's answer (q_start for waypoint 0) and waypoint
+        l's (sweep_clearance(q[:, l-1], q[:, l], S)), one gik_anchored_sweep_clearance call per waypoint on the rows
+        already on the device.  It is sampled, not conservative -- pick S from the joint step between waypoints --
+        and it is reported only: the restart rule does not read it.
+
         Returns q [B, L, n], Y [B, L, N_robot, 3] (None unless return_Y), and info with [B, L] arrays
         iterations, inner_iterations, stop, f(x), gradnorm, pos_err, rot_err, clearance, plus
         solve_time (seconds, whole path)."""
@@ -624,6 +659,11 @@ class AnchoredProblem:
         B, L = T.shape[:2]
         n = self.robot.n
         q0 = _seed_angles(q_start, B, n, "q_start")
+        mode = check_clearance_mode(clearance_mode, len(self.link_names) > 0)
+        if sweep is not None:
+            sweep = self._check_samples(sweep, "sweep")
+            if not len(self.link_names):
+                raise ValueError("sweep needs a link set: this problem was built without links")
         if retries:
             q_limits = self.robot.limits_arrays() if q_limits is None else q_limits
             retries, q_lo, q_hi = check_retry_args(retries, pos_tol, rot_tol, q_limits, n, clear_tol=clear_tol,
@@ -645,6 +685,9 @@ class AnchoredProblem:
         else:
             shared = {"ws": tpl.alloc_anchored_buffers(base, B)["ws"]}
         q_prev = torch.from_numpy(q0).to(dev)
+        if sweep:      # the start angles outlive waypoint 0's solve (it may write q_all[0] only), one workspace for all waypoints
+            sc = torch.empty(L, B, **f64)
+            sweep_ws = torch.empty(max(int(tpl.lib.gik_anchored_sweep_ws_bytes(tpl._h, base._h, B, sweep)) // 8, 1), **f64)
         torch.cuda.synchronize(dev)
         t0 = time.time()
         for l in range(L):
@@ -653,9 +696,11 @@ class AnchoredProblem:
             if retries:
                 out["attempt"] = attempt[l]
                 tpl._anchored_ik_retry(base, Tw[l], q_prev, out, retries, q_lo, q_hi, retry_seed, pos_tol, rot_tol, clear_tol,
-                                       retry_spread)
+                                       retry_spread, mode)
             else:
-                tpl.anchored_ik(base, Tw[l], q_init=q_prev, out=out, clearance=True)
+                tpl.anchored_ik(base, Tw[l], q_init=q_prev, out=out, clearance=True, clearance_mode=clearance_mode)
+            if sweep:
+                tpl.anchored_sweep_clearance(base, q_prev, q_all[l], sweep, out=sc[l], ws=sweep_ws)
             q_prev = q_all[l]
         torch.cuda.synchronize(dev)
         dt = time.time() - t0
@@ -665,15 +710,85 @@ class AnchoredProblem:
                 "clearance": cl.reshape(-1)}
         if retries:
             info["attempt"] = attempt.reshape(-1)
+        if sweep:
+            info["sweep_clearance"] = sc.reshape(-1)
         info = {key: v.reshape(L, B).T.cpu().numpy() for key, v in info.items()}
         info["solve_time"] = dt
         q = q_all.permute(1, 0, 2).cpu().numpy()
         Y = Y_all.reshape(L, B, tpl.full_N, 3).permute(1, 0, 2, 3).cpu().numpy() if return_Y else None
         return q, Y, info
 
+    @staticmethod
+    def _check_samples(samples, name="samples"):
+        if isinstance(samples, bool) or int(samples) != samples or samples < 1:
+            raise ValueError(f"{name} must be an integer of at least 1, got {samples!r}")
+        return int(samples)
+
+    def link_clearance(self, Y_full):
+        """min over (link, obstacle) of the distance from the sphere to the link's capsule per goal: the host mirror of
+        gik_anchored_link_clearance, the same operations in the same order.  Y_full [B, N_robot, 3] (numpy).  For a
+        link from a to b and a sphere (c, r):  d = b - a, L2 = d.d, u = c - a, t = L2 > 0 ? min(max(u.d / L2, 0), 1) : 0,
+        v = u - t d, value = |v| - r - link_radius.  >= 0: no part of a link is inside a sphere.  With radius 0 and the
+        skeleton it is <= clearance(Y_full, include_goal=True).  No link or no obstacle: +inf; a NaN coordinate of a
+        link end: NaN for that goal."""
+        Y = np.asarray(Y_full, dtype=np.float64)
+        if Y.ndim == 2:
+            Y = Y[None]
+        B = Y.shape[0]
+        if len(self.link_rows) == 0 or len(self.obstacles) == 0:
+            return np.full(B, np.inf)
+        a = Y[:, self.link_rows[:, 0], None, :]                    # [B, n_link, 1, 3]
+        b = Y[:, self.link_rows[:, 1], None, :]
+        c = self.obstacles[None, None, :, :3]                     # [1, 1, n_obs, 3]
+        r2 = self.obstacles[:, 3] ** 2                            # (what the template holds: the squared radius)
+        dot = lambda x, y: x[..., 0] * y[..., 0] + x[..., 1] * y[..., 1] + x[..., 2] * y[..., 2]   # noqa: E731
+        with np.errstate(invalid="ignore", divide="ignore"):
+            d = b - a
+            L2 = dot(d, d)                                        # [B, n_link, 1]
+            u = c - a
+            t = dot(u, d) / L2
+            t = np.where(t > 0.0, t, 0.0)
+            t = np.where(t < 1.0, t, 1.0)
+            t = np.where(L2 > 0.0, t, 0.0)
+            v = u - t[..., None] * d
+            val = np.sqrt(dot(v, v)) - np.sqrt(r2)[None, None, :] - self.link_radius[None, :, None]
+            val = np.where(np.isnan(L2), np.nan, val)
+        return np.where(np.isnan(val).any(axis=(1, 2)), np.nan, np.where(np.isnan(val), np.inf, val).min(axis=(1, 2)))
+
+    def sweep_points(self, q_a, q_b, samples):
+        """The samples + 1 configurations of a sweep, [samples + 1, B, n]: q_s = (1 - w) q_a + w q_b with w = s / samples
+        (two rounded products, one rounded sum -- the bits the device writes; s = 0 is q_a and s = samples is q_b)."""
+        S = self._check_samples(samples)
+        qa, qb = np.asarray(q_a, dtype=np.float64), np.asarray(q_b, dtype=np.float64)
+        if qa.ndim != 2 or qa.shape != qb.shape:
+            raise ValueError("q_a and q_b must both have shape [B, n]")
+        w = np.arange(S + 1, dtype=np.float64)[:, None, None] / np.float64(S)
+        return (1.0 - w) * qa[None] + w * qb[None]
+
+    def sweep_clearance_host(self, q_a, q_b, samples):
+        """The numpy mirror of sweep_clearance: link_clearance of BatchProblem.seed_points at every sample, the minimum
+        over the samples, NaN if any sample is NaN."""
+        qs = self.sweep_points(q_a, q_b, samples)
+        S1, B, n = qs.shape
+        cl = self.link_clearance(self.base.seed_points(qs.reshape(S1 * B, n))).reshape(S1, B)
+        return np.where(np.isnan(cl).any(axis=0), np.nan, np.where(np.isnan(cl), np.inf, cl).min(axis=0))
+
+    def sweep_clearance(self, q_a, q_b, samples):
+        """Joint angles q_a, q_b [B, n] -> device tensor [B]: the minimum link clearance over the samples + 1
+        configurations q_s = (1 - s / samples) q_a + (s / samples) q_b, s = 0 .. samples, each realized by forward
+        kinematics (gik_anchored_sweep_clearance; the problem must have links).  The sweep is SAMPLED, NOT
+        CONSERVATIVE: a link can pass through a sphere between two samples.  Pick `samples` from the joint step -- a
+        link of length L turning by dq moves its far end by about L dq, so samples >= L max|q_b - q_a| / tolerance
+        keeps what is missed below the tolerance.  sweep_clearance_host is the numpy mirror."""
+        S = self._check_samples(samples)
+        if not len(self.link_names):
+            raise ValueError("sweep_clearance needs a link set: this problem was built without links")
+        return self.template.anchored_sweep_clearance(self.base.template, q_a, q_b, S)
+
     def clearance(self, Y_full, include_goal=False):
-        """min over (p-node of the robot, obstacle) of |p - centre| - radius per goal (>= 0:
-        collision free in the sense of graph_base.py:205-211).  Y_full [B, N_robot, 3] (numpy).
+        """min over (p-node of the robot, obstacle) of |p - centre| - radius per goal (>= 0: no joint point
+        inside a sphere, the sense of graph_base.py:205-211; a link BETWEEN two joint points can still cross
+        one -- link_clearance).  Y_full [B, N_robot, 3] (numpy).
         The end effector p_n sits where the goal puts it (a constant of the problem), so it only
         counts with include_goal=True."""
         g = self.base.graph

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define GIK_ABI_VERSION 9
+#define GIK_ABI_VERSION 10
 
 /* Residual-term kinds: one "term" per (index pair, kind) exactly as the loops of
  * costs.py:80-207 visit them: equality (omega != 0), lower hinge (psi_L != 0), upper hinge
@@ -412,7 +412,8 @@ int gik_ik_batch_seeded(const gik_template *t, const double *d_T_goal, const dou
  *   a tolerance that is not positive, a null workspace.                                                       */
 typedef struct {
   int32_t retries;        /* further attempts for goals that failed: 0 .. 63                              */
-  int32_t reserved0;
+  int32_t clearance_mode; /* not read here (this rule has no clearance part); set 0.  Named as the field of
+                           * gik_anchored_retry_opts, whose first fields are this struct's                  */
   uint64_t seed;          /* of the generator; the same seed gives the same answers                       */
   double pos_tol;         /* a goal succeeds with stop == 0, pos_err <= pos_tol and rot_err <= rot_tol    */
   double rot_tol;
@@ -499,7 +500,8 @@ int gik_anchored_ik_batch(const gik_template *anch, const gik_template *base, co
  *   pair of gik_anchored_last_solve_ms is recorded around the solve kernel as there.
  * gik_anchored_clearance: d_clearance [B] = min over (free node i with obs_node_mask[i] == 1, obstacle o) of
  *   |Y_i - centre_o| - radius_o, read from a full point matrix d_Y_full [B][full_N*3] (radius_o is the square
- *   root of the descriptor's squared radius).  >= 0: no masked node is inside a sphere.  Anchors are not
+ *   root of the descriptor's squared radius).  >= 0: no masked node is inside a sphere -- which says nothing of
+ *   the links BETWEEN the nodes (gik_anchored_link_clearance below).  Anchors are not
  *   counted (the end effector sits where the goal puts it).  No obstacle, or no masked node: +infinity.  A NaN
  *   coordinate of a masked node: NaN for that goal alone.
  * Refused with a message before anything is queued: a capturing stream; an `anch` that is not a fixed-anchor
@@ -515,10 +517,56 @@ int gik_anchored_ik_batch_seeded(const gik_template *anch, const gik_template *b
                                  gik_stats *d_stats, double *d_q, double *d_pos_err, double *d_rot_err,
                                  double *d_clearance /* may be NULL */, void *stream);
 
+/* ---- clearance of whole links, and its sweep between two configurations -------------------------
+ * gik_anchored_clearance measures the joint points.  A link is the segment between two rows of the full point matrix
+ * (on a chain, consecutive p-nodes); it can pass through a sphere with both of its ends outside.
+ *
+ * gik_anchored_attach_links: the link set of an anchored template, attached once after creation (as
+ *   gik_pipeline_attach): link l runs from row link_a[l] to row link_b[l] of the full point matrix and is a capsule of
+ *   radius link_radius[l] >= 0 metres.  Any row may be named, anchors and goal rows included (the last link ends at the
+ *   end effector).  Refused with a message: a handle that is not a fixed-anchor template, n_link outside 0 .. 64, a row
+ *   outside [0, full_N), a radius that is negative, NaN or infinite, a second attach.
+ * gik_anchored_link_clearance: d_clearance [B] = min over (link l, obstacle o) of
+ *       d = b - a;  L2 = d.d;  u = c_o - a;   t = L2 > 0 ? min(max((u.d) / L2, 0), 1) : 0;   v = u - t d
+ *       |v| - radius_o - link_radius[l]
+ *   on d_Y_full [B][full_N*3]: the distance from the sphere to the capsule (a zero-length link is its point).  With
+ *   radius 0 and the chain's skeleton it is <= gik_anchored_clearance of the same points, since a segment holds its
+ *   ends.  No obstacle, or no link: +infinity.  A NaN coordinate of a link end: NaN for that goal alone.  One wavefront
+ *   per goal.  Refused: what gik_anchored_clearance refuses, and a template without links.  B == 0 returns 0.
+ * gik_anchored_sweep_clearance: d_clearance [B] = min over s = 0 .. samples of the link clearance of the robot at
+ *       q_s = (1 - w) q_a + w q_b,   w = s / samples      (two rounded products, one rounded sum; s = 0 is q_a, s = S is q_b)
+ *   for d_q_a, d_q_b [B][n]: the joint-space line between two configurations, realized by gik_seed_batch's walk on
+ *   `base` (every row comes from q_s, the end effector too).  A NaN at any sample gives NaN.
+ *   THE SWEEP IS SAMPLED, NOT CONSERVATIVE: a link can enter and leave a sphere between two samples.  The caller picks
+ *   `samples` from its joint step -- a link of length L turning by dq moves its far end by about L dq, so samples >=
+ *   L max|q_b - q_a| / (the penetration that matters) bounds what is missed.
+ *   One stream, four launches (interpolate, realize, link clearance of all B (samples + 1) configurations, minimum), no
+ *   host synchronisation.  d_ws: gik_anchored_sweep_ws_bytes(anch, base, B, samples) bytes, 8-byte aligned (0: bad
+ *   arguments).  Refused: what gik_anchored_seed_batch refuses of the handles and the stream, a template without
+ *   links, samples < 1, B (samples + 1) beyond an int, a null buffer.  B == 0 returns 0.                          */
+typedef struct {
+  int32_t n_link;               /* 0 .. 64                                                        */
+  int32_t reserved0;
+  const int32_t *link_a;        /* [n_link] row of the full point matrix where the link starts    */
+  const int32_t *link_b;        /* [n_link] ... and where it ends                                 */
+  const double *link_radius;    /* [n_link] capsule radius, metres, >= 0                          */
+} gik_link_desc;
+
+int gik_anchored_attach_links(gik_template *anch, const gik_link_desc *links);
+int gik_anchored_link_clearance(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance,
+                                void *stream);
+size_t gik_anchored_sweep_ws_bytes(const gik_template *anch, const gik_template *base, int B, int samples);
+int gik_anchored_sweep_clearance(const gik_template *anch, const gik_template *base, const double *d_q_a,
+                                 const double *d_q_b, int B, int samples, double *d_ws, double *d_clearance,
+                                 void *stream);
+
 /* ---- restarts in the anchored solve, with a clearance rule (opt-in) -----------------------------
  * The restarts of gik_ik_batch_retry for the fixed-anchor formulation.  The obstacle hinges are soft cost terms: an
- * answer can stop on its gradient bar with the end effector on the goal and a link inside a sphere, which the rule
- * of the plain restarts calls a success.  Here the rule also reads the answer's clearance (gik_anchored_clearance):
+ * answer can stop on its gradient bar with the end effector on the goal and a joint point inside a sphere, which the rule
+ * of the plain restarts calls a success.  Here the rule also reads the answer's clearance: that of the masked nodes
+ * (gik_anchored_clearance; clearance_mode = GIK_CLEARANCE_NODES, the default), which does not see a link that crosses a
+ * sphere between two nodes outside it, or that of whole links (gik_anchored_link_clearance; GIK_CLEARANCE_LINKS, for a
+ * template with links attached).  The rule is the same for both; only the array it reads differs:
  *
  * failed(goal)  :=  stats.stop != 0  ||  !(pos_err <= pos_tol)  ||  !(rot_err <= rot_tol)  ||  !(clearance >= -clear_tol)
  *                   -- a NaN clearance counts as failed; +infinity (no obstacle, no masked node) never fails a goal.
@@ -554,7 +602,9 @@ int gik_anchored_ik_batch_seeded(const gik_template *anch, const gik_template *b
  *   What comes back: the outputs of gik_anchored_ik_batch_seeded plus d_attempt[g] = the attempt whose answer goal g
  *   holds.  The anchored solve runs on the wavefront kernel, whose bits do not depend on the batch, so a goal with
  *   d_attempt[g] = a > 0 holds exactly what gik_anchored_ik_batch_seeded returns for that goal alone from the seed of
- *   (seed, g, a).  gik_anchored_last_solve_ms reports the solve kernel of the LAST attempt that ran.
+ *   (seed, g, a).  With clearance_mode = GIK_CLEARANCE_LINKS every clearance of the call -- attempt 0's in d_clearance,
+ *   each restart's on its compact batch, what the merge moves -- is gik_anchored_link_clearance of the same point
+ *   matrices instead; select, score and merge are unchanged.  gik_anchored_last_solve_ms reports the solve kernel of the LAST attempt that ran.
  *   d_ws: caller-owned, gik_anchored_retry_ws_bytes(anch, base, B) bytes, 8-byte aligned: the scratch of one anchored
  *   call (attempt 0 and the restarts use it in turn) plus compact buffers sized for the case that every goal fails.
  *   It is needed with retries = 0 as well.
@@ -562,10 +612,13 @@ int gik_anchored_ik_batch_seeded(const gik_template *anch, const gik_template *b
  *   not a fixed-anchor template, a `base` without pipeline or with N != full_N, a capturing stream; a `base` that
  *   cannot be seeded, if d_q_init is given or retries > 0); retries outside 0 .. 63; a null d_clearance, d_attempt or
  *   workspace; and with retries > 0 null limits, a pos_tol, rot_tol or clear_tol that is not positive, a spread
- *   that is negative or NaN, spread > 0 with a null d_q_init (a cold batch has no centre).  B == 0 returns 0.  */
+ *   that is negative or NaN, spread > 0 with a null d_q_init (a cold batch has no centre); a clearance_mode that is
+ *   neither 0 nor 1, and 1 on a template without links.  B == 0 returns 0.                                     */
+#define GIK_CLEARANCE_NODES 0
+#define GIK_CLEARANCE_LINKS 1
 typedef struct {
   int32_t retries;        /* further attempts for goals that failed: 0 .. 63                              */
-  int32_t reserved0;
+  int32_t clearance_mode; /* GIK_CLEARANCE_NODES (0) or GIK_CLEARANCE_LINKS (1): which clearance the rule reads */
   uint64_t seed;          /* of the generator; the same seed gives the same answers                       */
   double pos_tol;         /* a goal succeeds with stop == 0, pos_err <= pos_tol, rot_err <= rot_tol ...   */
   double rot_tol;
