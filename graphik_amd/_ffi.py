@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GIK_LIB_PATH") or os.path.join(_HERE, "lib", "libgraphik_amd.so")
 
 TERM_EQ, TERM_LOWER, TERM_UPPER = 1, 2, 3
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 class TemplateDesc(C.Structure):
@@ -43,7 +43,7 @@ class TemplateInfo(C.Structure):
                 ("n_cu", C.c_int32), ("lds_bytes", C.c_int32), ("clique_closed_form", C.c_int32),
                 ("anchored", C.c_int32), ("has_pipeline", C.c_int32), ("prepare_is_block", C.c_int32),
                 ("node_per_lane", C.c_int32), ("problems_per_wave", C.c_int32), ("goals_per_wave", C.c_int32),
-                ("hessian_form", C.c_int32)]
+                ("hessian_form", C.c_int32), ("claim_key_terms", C.c_int32)]
 
 
 SOLVER_TRUST_REGIONS, SOLVER_CONJUGATE_GRADIENT = 0, 1
@@ -161,6 +161,10 @@ SYMBOLS = {
                                               C.POINTER(AnchoredRetryOpts)] + 8 * [C.c_void_p] + [C.c_void_p]),
     "gik_template_destroy": (None, [C.c_void_p]),
     "gik_template_get_info": (C.c_int, [C.c_void_p, C.POINTER(TemplateInfo)]),
+    "gik_template_set_claim_key": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "gik_claim_order_max_batch": (C.c_int, []),
+    "gik_claim_order_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "gik_claim_order_sort": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "gik_cost": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "gik_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "gik_cost_and_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,

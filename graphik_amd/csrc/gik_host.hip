@@ -7,6 +7,7 @@
 #include "gik_retry.hip.h"
 #include "gik_anch_seed.hip.h"
 #include "gik_anch_retry.hip.h"
+#include "gik_order.hip.h"
 #include "gik_plan.h"
 #include "gik_slots.h"
 #include <climits>
@@ -16,6 +17,7 @@ namespace gik {
 GIK_ALL_KERNELS(GIK_EXTERN_TEMPLATE)
 static_assert(PLAN_MIG_SIMDS == MIG_SIMDS && PLAN_SLICE_STATE_BYTES == sizeof(SliceState) && PLAN_QUAD_SLOTS == QUAD_SLOTS,
               "gik_plan.h restates these constants of the kernel headers");
+static_assert(PLAN_CLAIM_KEY_MAX_TERMS == CLAIM_KEY_MAX_TERMS, "gik_plan.h restates this constant of gik_order.hip.h");
 
 // the compiled node-per-lane variants
 struct NptVariant {
@@ -146,6 +148,7 @@ struct gik_template {
     const void *occupancy = nullptr;                  // the kernel waves_per_cu was queried on
   } kernels;
   uint32_t *d_slot_meta = nullptr;
+  gik::ClaimKey claim_key;      // gik_template_set_claim_key (f.claim_terms = claim_key.n); n == 0: index order
   // Ring of work-queue heads, one per in-flight solve call.  A slot is handed out again only
   // behind the event recorded after the launch that used it last (the new call's stream waits for
   // it), so a wrap of the ring can never reset the counter of a kernel that is still running --
@@ -2193,6 +2196,7 @@ static void fill_args(const gik_template *t, gik::SolveArgs &a, const double *d_
   }
   a.dbg = t->f.dbg;
   a.dbg_buf = nullptr;
+  a.claim_order = nullptr;
 #ifdef GIK_DEV
   if (a.dbg & (4 | 8 | 4096)) a.dbg_buf = dev_debug_buffer();
 #endif
@@ -2226,6 +2230,14 @@ static int lease_counter(gik_template *mt, CounterLease &lease, gik::SolveArgs &
   if (cs.pending) HIP_OK(hipStreamWaitEvent(stream, cs.done, 0));   // ring wrapped: previous user first
   HIP_OK(hipMemsetAsync(a.work_counter, 0, sizeof(unsigned int), stream));
   return 0;
+}
+
+// key and rank kernels (gik_order.hip.h) on the stream: order[0 .. B) = the problems in ascending key order
+static void launch_claim_order(const gik::ClaimKey &k, const double *d_targets, int T, int B, float *d_key, int *d_order,
+                               hipStream_t stream) {
+  using namespace gik;
+  if (d_targets) hipLaunchKernelGGL(claim_key_kernel, dim3((B + 255) / 256), dim3(256), 0, stream, d_targets, T, B, k, d_key);
+  hipLaunchKernelGGL(claim_rank_kernel, dim3((B + ORDER_ROWS - 1) / ORDER_ROWS), dim3(ORDER_NT), 0, stream, d_key, B, d_order);
 }
 
 // a pooled workspace of at least the plan's size (grown outside the lock, behind its previous user), the queue
@@ -2262,10 +2274,18 @@ static int bind_workspace(gik_template *mt, WorkspaceLease &lease, const gik::So
   a.y_ids = reinterpret_cast<int *>(base + p.off_yids);
   a.y_cap = (unsigned int)p.ycap;
   a.npt_ctg_ws = p.ctg_bytes ? reinterpret_cast<double *>(base + p.off_ctg) : nullptr;
-  HIP_OK(hipMemsetAsync(base, 0, p.zero_head, stream));
+  if (p.zero_head) HIP_OK(hipMemsetAsync(base, 0, p.zero_head, stream));
   if (p.seq_fill) HIP_OK(hipMemsetAsync(a.q_seq, 0xFF, p.seq_fill, stream));
   if (p.state_zero) HIP_OK(hipMemsetAsync(a.q_state, 0, p.state_zero, stream));
   if (p.yseq_zero) HIP_OK(hipMemsetAsync(a.y_seq, 0, p.yseq_zero, stream));
+  if (p.order) {
+    // ticket -> problem, ascending in the template's key of THIS call's targets: two small launches in front of the solve
+    float *key = reinterpret_cast<float *>(base + p.off_key);
+    int *order = reinterpret_cast<int *>(base + p.off_order);
+    launch_claim_order(mt->claim_key, a.targets, a.T, a.B, key, order, stream);
+    HIP_OK(hipGetLastError());
+    a.claim_order = order;
+  }
   return 0;
 }
 
@@ -2334,6 +2354,55 @@ int gik_solve_batch(const gik_template *t, const double *d_Y_init, const double 
   return 0;
 }
 
+int gik_template_set_claim_key(gik_template *t, int n, const int32_t *terms, const double *weights) {
+  using namespace gik;
+  if (!t) return fail("null argument");
+  if (n > 0 && !weights) return fail("claim key: weights required");
+  if (!claim_key_ok(n, terms, t->T))
+    return fail("claim key: at most " + std::to_string(PLAN_CLAIM_KEY_MAX_TERMS) + " terms, each an index into the template's " +
+                std::to_string(t->T) + " terms");
+  // only the 3-D trust-region wavefront kernels order their claims: any other template takes the call and stays on
+  // index order (the caller need not know which kernels a graph got; gik_template_get_info says what is in effect)
+  if (t->anchored || t->f.is_block || t->f.K != 3 || t->f.cg) n = 0;
+  // GIK_CLAIM_ORDER=off (developer override, like GIK_DBG): every template stays on index order
+  if (const char *e = getenv("GIK_CLAIM_ORDER"))
+    if (!std::strcmp(e, "off") || !std::strcmp(e, "0")) n = 0;
+  ClaimKey k;
+  k.n = n;
+  for (int i = 0; i < n; ++i) {
+    k.term[i] = terms[i];
+    k.w[i] = weights[i];
+  }
+  std::lock_guard<std::mutex> lock(t->call_mutex);      // (calls in flight keep the plan they made)
+  t->claim_key = k;
+  t->f.claim_terms = n;
+  return 0;
+}
+
+int gik_claim_order_max_batch(void) { return gik::PLAN_CLAIM_ORDER_MAX_BATCH; }
+
+int gik_claim_order_keys(const gik_template *t, const double *d_targets, int B, float *d_keys, void *stream) {
+  using namespace gik;
+  if (!t || B < 0) return fail("bad argument");
+  if (t->claim_key.n == 0) return fail("the template has no claim key");
+  if (B == 0) return 0;
+  if (!d_targets || !d_keys) return fail("null buffer");
+  hipLaunchKernelGGL(claim_key_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_targets, t->T, B,
+                     t->claim_key, d_keys);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int gik_claim_order_sort(const float *d_keys, int B, int32_t *d_order, void *stream) {
+  using namespace gik;
+  if (B < 0 || B > PLAN_CLAIM_ORDER_MAX_BATCH) return fail("claim order: 0 .. " + std::to_string(PLAN_CLAIM_ORDER_MAX_BATCH) + " keys");
+  if (B == 0) return 0;
+  if (!d_keys || !d_order) return fail("null buffer");
+  launch_claim_order(ClaimKey(), nullptr, 0, B, const_cast<float *>(d_keys), d_order, (hipStream_t)stream);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
 int gik_template_get_info(const gik_template *t, gik_template_info *info) {
   if (!t || !info) return gik::fail("null argument");
   std::memset(info, 0, sizeof(*info));
@@ -2352,6 +2421,7 @@ int gik_template_get_info(const gik_template *t, gik_template_info *info) {
   info->prepare_is_block = t->prep_block ? 1 : 0;
   info->node_per_lane = t->f.is_npt ? t->npt_variant->NW : 0;
   info->goals_per_wave = !t->has_pipe || t->prep_block ? 0 : (t->prep_quad ? gik::QUAD_SLOTS : 1);
+  info->claim_key_terms = t->f.claim_terms;
   info->problems_per_wave = t->f.is_block ? 0 : ((t->quad_solve && !(t->f.dbg & (1 | 8192))) ? gik::QUAD_SLOTS : 1);
   if (t->f.is_npt) {
     info->waves_per_cu = t->f.npt_waves_per_cu;

@@ -114,6 +114,8 @@ struct SolveArgs {
   double *Y_out;              // [B][N*K]
   gik_stats *stats;           // [B]
   unsigned int *work_counter; // zeroed before launch; problems are claimed with atomicAdd
+  const int *claim_order = nullptr;   // [B] ticket -> problem (a permutation, gik_k_order.hip), null = index order; fresh claims of
+                              // rtr_wave_kernel only: likely-long problems get the early tickets (NOTEBOOK 21)
   gik_trace trace;
   int has_trace;
   int N, T, B;
@@ -330,6 +332,10 @@ __global__ void __launch_bounds__(WAVE, ANCH ? 1 : 2) rtr_wave_kernel(SolveArgs 
         b = __builtin_amdgcn_readlane(b, 0);  // lane 0 explicitly, independent of exec
         resumed = __builtin_amdgcn_readlane(resumed, 0);
       }
+      // a fresh claim's b is its ticket: with a claim order (a permutation of 0 .. B-1) ticket t stands for problem
+      // claim_order[t].  Looked up here, on the broadcast value: inside the lane-0 block above the load made the
+      // compiler wrap the solver's loops in exec masks (188 -> 207 instructions per tCG step of this build)
+      if (a.claim_order && !resumed && b >= 0) b = a.claim_order[b];
       tail = tail || resumed;
 #ifdef GIK_DEV
       dev_t_claim += (long long)__builtin_readcyclecounter() - dev_tc;
@@ -338,11 +344,18 @@ __global__ void __launch_bounds__(WAVE, ANCH ? 1 : 2) rtr_wave_kernel(SolveArgs 
 #endif
       if (UNI(b < 0)) break;
     } else {
+      // b is the ticket; with a claim order (a permutation of 0 .. B-1) ticket t stands for problem claim_order[t],
+      // tickets from B on stay as they are and end the loop.  (Here lane 0 looks it up before the broadcast: a lookup
+      // behind the exit test, as in the MIG branch, cost this build 0.7 % of a 4096-goal LWA4D batch in index order.)
       if (a.dbg & 1) {
         b = (int)blockIdx.x + pass * (int)gridDim.x;
         ++pass;
+        if (a.claim_order && b < a.B) b = a.claim_order[b];
       } else {
-        if (lane == 0) b = (int)atomicAdd(a.work_counter, 1u);
+        if (lane == 0) {
+          b = (int)atomicAdd(a.work_counter, 1u);
+          if (a.claim_order && b < a.B) b = a.claim_order[b];
+        }
         b = __builtin_amdgcn_readlane(b, 0);  // lane 0 explicitly, independent of exec
       }
       if (UNI(b >= a.B)) break;

@@ -13,6 +13,20 @@ namespace gik {
 constexpr int PLAN_MIG_SIMDS = 1 << 14;          // SIMD slots of the spread table (MIG_SIMDS)
 constexpr size_t PLAN_SLICE_STATE_BYTES = 32;    // sizeof(SliceState)
 constexpr int PLAN_QUAD_SLOTS = 4;               // problems per quad wavefront (QUAD_SLOTS)
+constexpr int PLAN_CLAIM_KEY_MAX_TERMS = 8;      // terms of a template's claim key (CLAIM_KEY_MAX_TERMS)
+// Largest batch whose claims are ordered.  The rank kernel compares every pair of keys: ~10 us at 4096 problems and
+// about 0.3 ms here, against a solve of several hundred ms; beyond it a batch is hundreds of problems deep per wave and
+// its time is throughput, not the start of one problem, so the plan keeps index order rather than pay B^2.
+constexpr int PLAN_CLAIM_ORDER_MAX_BATCH = 65536;
+
+// a claim key as gik_template_set_claim_key accepts it: at most PLAN_CLAIM_KEY_MAX_TERMS terms, each an index into the
+// template's T terms (n == 0: index order, always accepted)
+inline bool claim_key_ok(int n, const int *terms, int T) {
+  if (n < 0 || n > PLAN_CLAIM_KEY_MAX_TERMS || (n > 0 && !terms)) return false;
+  for (int i = 0; i < n; ++i)
+    if (terms[i] < 0 || terms[i] >= T) return false;
+  return true;
+}
 
 // What plan_solve reads from a handle: filled during template creation, constant afterwards.
 struct SolveFacts {
@@ -37,6 +51,7 @@ struct SolveFacts {
   int quad_min_batch = -1;     // smallest batch that runs it (GIK_QUAD_MIN_BATCH; else 12 problems per CU, set with quad_solve)
   int quad_waves_per_cu = 8;
   size_t ctg_doubles = 0;      // node-per-lane path: npt_variant->ctg(nt.n_pairs), else 0
+  int claim_terms = 0;         // terms of the claim key (gik_template_set_claim_key), 0 = index order
 };
 
 enum class Launch { QUAD, NPT, BLOCK, WAVE, WAVE_SPREAD };
@@ -49,11 +64,13 @@ struct SolvePlan {
   int slice_its, slice_cycles;   // SolveArgs::slice_its / slice_cycles
   bool mig;                      // the tail is spread
   size_t cap, ycap;              // entries of the re-queue ring and of the yield queue
+  bool order;                    // claims in ascending key order: key and rank kernels in front of the solve
   bool needs_ws;                 // everything below: only then
   size_t off_simd, off_seq, off_ids, off_state, off_yseq, off_yids, off_ctg, bytes;
   size_t ctg_bytes;              // of the clique-target region at off_ctg (0: none, SolveArgs::npt_ctg_ws stays null)
   // memsets: [0, zero_head) = 0; q_seq: seq_fill bytes of 0xFF; q_state: state_zero bytes of 0; y_seq: yseq_zero of 0
   size_t zero_head, seq_fill, state_zero, yseq_zero;
+  size_t off_key, off_order;     // order: [B] float keys, [B] int ticket -> problem
 };
 
 inline SolvePlan plan_solve(const SolveFacts &t, int B) {
@@ -96,7 +113,11 @@ inline SolvePlan plan_solve(const SolveFacts &t, int B) {
   p.grid = p.launch_grid = grid;
   p.slice_its = slice;
   p.mig = mig;
-  p.needs_ws = slice > 0 || mig || ctg_bytes;
+  // Claim order (NOTEBOOK 21): the 3-D trust-region wavefront kernels only, where the template has a key, and only
+  // where a problem can wait for a wave at all -- with a wave per problem every claim happens at once.
+  p.order = t.claim_terms > 0 && !t.is_block && !t.is_npt && t.K == 3 && !t.cg && B > grid && B <= PLAN_CLAIM_ORDER_MAX_BATCH;
+  const bool queues = slice > 0 || mig || ctg_bytes;
+  p.needs_ws = queues || p.order;
   if (p.needs_ws) {
     const size_t cap = mig ? (size_t)B + (size_t)grid + 64 : (slice > 0 ? (size_t)B * (size_t)(t.maxiter / slice + 1) : 0);
     // wavefront kernel: round-robin slicing (slice length: the handle's wave_slice_its)
@@ -120,7 +141,9 @@ inline SolvePlan plan_solve(const SolveFacts &t, int B) {
                  off_state = (off_ids + cap * 4 + 15) & ~(size_t)15,
                  off_yseq = off_state + (((size_t)B * PLAN_SLICE_STATE_BYTES + 15) & ~(size_t)15), off_yids = off_yseq + ycap * 4;
     const size_t off_ctg = (off_yids + ycap * 4 + 63) & ~(size_t)63;
-    const size_t bytes = off_ctg + ctg_bytes;
+    // (the order's buffers come last: a plan without them is laid out as it always was)
+    const size_t off_key = (off_ctg + ctg_bytes + 63) & ~(size_t)63, off_order = off_key + (p.order ? 4 * (size_t)B : 0);
+    const size_t bytes = p.order ? off_order + 4 * (size_t)B : off_ctg + ctg_bytes;
     if (mig) { p.slice_its = wslice; p.slice_cycles = t.wave_slice_cycles; }
     p.cap = cap;
     p.ycap = ycap;
@@ -133,7 +156,9 @@ inline SolvePlan plan_solve(const SolveFacts &t, int B) {
     p.off_ctg = off_ctg;
     p.ctg_bytes = ctg_bytes;
     p.bytes = bytes;
-    p.zero_head = off_seq;
+    p.off_key = off_key;
+    p.off_order = off_order;
+    p.zero_head = queues ? off_seq : 0;      // (no queue: nothing reads the head)
     p.seq_fill = cap * 4;
     p.state_zero = (mig || t.is_npt) ? (size_t)B * PLAN_SLICE_STATE_BYTES : 0;
     p.yseq_zero = ycap * 4;

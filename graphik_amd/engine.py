@@ -139,6 +139,9 @@ class Template:
         d = _ffi.TemplateDesc()
         params = dict(params or {})
         self.solver = params.pop("solver", "TrustRegions")
+        self.claim_order = params.pop("claim_order", "auto")      # "off": set_claim_key keeps index order
+        if self.claim_order not in ("auto", "on", "off"):
+            raise ValueError("params[\"claim_order\"] must be one of 'auto', 'on', 'off'")
         if self.solver == "ConjugateGradient":      # riemannian_solver.py:51-59
             self.lib.gik_default_cg_params(C.byref(d))
         elif self.solver == "TrustRegions":
@@ -221,6 +224,36 @@ class Template:
                 self._h = None
         except Exception:
             pass
+
+    def set_claim_key(self, terms, weights):
+        """The template's claim key (gik_template_set_claim_key): solves hand their problems out in ascending order of
+        sum_i weights[i] * targets[:, terms[i]].  No terms, or params["claim_order"] = "off": index order."""
+        terms = np.ascontiguousarray(terms, dtype=np.int32).reshape(-1)
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if len(terms) != len(w):
+            raise ValueError("one weight per term")
+        n = 0 if self.claim_order == "off" else len(terms)
+        with torch.cuda.device(self.device):
+            _ffi.check(self.lib.gik_template_set_claim_key(self._h, n, terms.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                           w.ctypes.data_as(C.POINTER(C.c_double))))
+        self._read_info()
+
+    def claim_order_of(self, keys):
+        """keys [B] float32 (device tensor or array) -> the indices in ascending key order as the solve would use them
+        (gik_claim_order_sort): stable, NaN last."""
+        k = torch.as_tensor(keys, dtype=torch.float32).to(self.device).contiguous()
+        order = torch.full((k.numel(),), -1, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            _ffi.check(self.lib.gik_claim_order_sort(k.data_ptr(), k.numel(), order.data_ptr(), self._stream()))
+        return order
+
+    def claim_keys(self, targets):
+        """targets [B,T] -> the claim keys [B] float32 of this template (gik_claim_order_keys)."""
+        t = _dev(targets, self.device)
+        keys = torch.empty(t.shape[0], dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _ffi.check(self.lib.gik_claim_order_keys(self._h, t.data_ptr(), t.shape[0], keys.data_ptr(), self._stream()))
+        return keys
 
     # -- helpers ------------------------------------------------------------------------------
     def targets_from_D(self, D_goal):

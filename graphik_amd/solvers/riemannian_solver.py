@@ -232,6 +232,25 @@ class BatchProblem:
         self.template = Template.from_matrices(self.omega, self.psi_L, self.psi_U, k=self.dim,
                                                use_limits=use_limits, device=device, params=params)
         self._attach_device_pipeline()
+        # claim order of the solve kernels (gik_template_set_claim_key): the robot's data names its key, params
+        # {"claim_order": "on" | "off"} overrides; the library decides per call whether it orders
+        mode = (params or {}).get("claim_order", "auto")
+        if mode == "on" or (mode == "auto" and getattr(self.robot, "claim_key", None) == "reach"):
+            terms = self.claim_key_terms()
+            if terms:
+                self.template.set_claim_key(terms, np.ones(len(terms)))
+
+    def claim_key_nodes(self):
+        """The goal nodes whose distance to the base origin p0 is the goal's reach: the end effectors' points p_e."""
+        return list(self.goal_nodes[0::2]) if self.dim == 3 else []
+
+    def claim_key_terms(self):
+        """Indices of the goal-dependent equality terms (p0, p_e) between the base anchor and the goal nodes of
+        claim_key_nodes: their targets are the squared reach of the goal."""
+        ti, tj, tk, _ = self.terms
+        p0 = self.graph.index("p0")
+        pairs = {(min(p0, g), max(p0, g)) for g in self.claim_key_nodes()}
+        return [t for t in range(len(ti)) if tk[t] == 1 and (int(ti[t]), int(tj[t])) in pairs]
 
     def _attach_device_pipeline(self):
         """Hand the goal-independent pre/post-processing data to the device handle."""

@@ -57,8 +57,18 @@ def _make(n, T_zero, limits, randomized_links=False, randomize_percentage=0.4):
     return robot, ProblemGraphRevolute(robot)
 
 
+def _claim_key(name):
+    """The packaged robot's claim-order key (graphik_amd.solvers.BatchProblem), or None: index order.  Only robots that
+    tools/claim_order_study.py supports carry one."""
+    with open(os.path.join(_DATA, name + ".json")) as f:
+        return json.load(f).get("claim_key")
+
+
 def load_schunk_lwa4d(limits=None, randomized_links=False, randomize_percentage=0.4):
-    return _make(*_packaged("lwa4d"), limits, randomized_links, randomize_percentage)
+    robot, graph = _make(*_packaged("lwa4d"), limits, randomized_links, randomize_percentage)
+    if not randomized_links:
+        robot.claim_key = _claim_key("lwa4d")
+    return robot, graph
 
 
 def load_ur10(limits=None, randomized_links=False, randomize_percentage=0.4):

@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define GIK_ABI_VERSION 10
+#define GIK_ABI_VERSION 11
 
 /* Residual-term kinds: one "term" per (index pair, kind) exactly as the loops of
  * costs.py:80-207 visit them: equality (omega != 0), lower hinge (psi_L != 0), upper hinge
@@ -242,8 +242,31 @@ typedef struct {
                                   (prep_quad_kernel); 1 = one (prep_wave_kernel); 0 = workgroup per goal / no pipeline */
   int32_t hessian_form;        /* what the solve kernel of this template does: GIK_HESS_PER_EDGE or GIK_HESS_COLUMN
                                   (never _AUTO; workgroup and node-per-lane kernels: always _PER_EDGE)              */
+  int32_t claim_key_terms;     /* terms of the claim key in effect (gik_template_set_claim_key); 0: index order        */
 } gik_template_info;
 int gik_template_get_info(const gik_template *t, gik_template_info *info);
+
+/* Claim order of gik_solve_batch (and the calls built on it).  The persistent solve kernels hand out problems by
+ * ticket, and a batch of a few problems per wave is as long as its longest problem plus the time that problem waited
+ * for a wave.  A template may carry a KEY -- a short linear form of each problem's targets,
+ *     key[b] = sum_i weights[i] * targets[b][terms[i]],   n <= 8 terms, each an index into the template's T terms --
+ * and the call then hands the tickets out in ascending key order (ties in index order, NaN last): two small kernels in
+ * front of the solve compute the keys and the permutation from THIS call's targets, in a leased workspace.  Which
+ * problems are likely long is a property of the robot: graphik_amd passes the squared reach of the goal (the targets of
+ * the terms between the base origin and the end effector's point) for robots whose goals close to the base are the
+ * slow ones (tools/claim_order_study.py).  n = 0 (the default of every template) keeps index order.
+ * Results never depend on it: problems are independent, the order only decides when each one starts.  It applies to
+ * the one-unknown-per-lane trust-region kernels of 3-D graphs (a template on other kernels accepts a valid key and stays
+ * on index order: gik_template_get_info().claim_key_terms reads 0), in batches of more problems than resident waves and
+ * of at most gik_claim_order_max_batch() problems; any other call keeps index order.  Not to be
+ * called while batch calls on the handle are being issued.  The environment variable GIK_CLAIM_ORDER=off makes this a
+ * no-op (developer override).                                                                                     */
+int gik_template_set_claim_key(gik_template *t, int n, const int32_t *terms, const double *weights);
+int gik_claim_order_max_batch(void);
+/* The two kernels on their own (tests, tools): d_keys [B] float from d_targets [B][T] by the template's key;
+ * d_order [B] = the indices 0 .. B-1 in ascending key order (stable, NaN last), B <= gik_claim_order_max_batch().   */
+int gik_claim_order_keys(const gik_template *t, const double *d_targets, int B, float *d_keys, void *stream);
+int gik_claim_order_sort(const float *d_keys, int B, int32_t *d_order, void *stream);
 
 /* costgrd twins, batched over B problems.  d_Y, d_W, d_out: [B][N*k]; d_targets: [B][T]
  * (squared goal distance for EQ terms, psi_L / psi_U for hinge terms); d_f: [B].          */
