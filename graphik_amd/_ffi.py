@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GIK_LIB_PATH") or os.path.join(_HERE, "lib", "libgraphik_amd.so")
 
 TERM_EQ, TERM_LOWER, TERM_UPPER = 1, 2, 3
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 
 class TemplateDesc(C.Structure):
@@ -118,7 +118,7 @@ CLEARANCE_MODES = {"nodes": CLEARANCE_NODES, "links": CLEARANCE_LINKS}
 
 class LinkDesc(C.Structure):
     """gik_link_desc"""
-    _fields_ = [("n_link", C.c_int32), ("reserved0", C.c_int32), ("link_a", C.POINTER(C.c_int32)),
+    _fields_ = [("n_link", C.c_int32), ("hinges", C.c_int32), ("link_a", C.POINTER(C.c_int32)),
                 ("link_b", C.POINTER(C.c_int32)), ("link_radius", C.POINTER(C.c_double))]
 
 

@@ -18,7 +18,8 @@
 //   anch_sweep_interp_kernel / anch_sweep_min_kernel : the ends of gik_anchored_sweep_clearance -- the S + 1 joint
 //                           configurations between q_a and q_b (and the identity poses seed_kernel is handed with
 //                           them), one thread per double; and the minimum over the samples, one thread per goal.
-// anch_link_pair, anch_sweep_interp and anch_sweep_min are __host__ __device__, so that a host program can walk them.
+// anch_link_pair, anch_link_foot (the pair function of the solve kernel's link hinges), anch_sweep_interp and
+// anch_sweep_min are __host__ __device__, so that a host program can walk them.
 // Plain kernels, defined where GIK_DEFINE_ANCH_SEED_KERNELS is set (gik_k_anch_seed.hip); gik_host.hip sees prototypes.
 #pragma once
 
@@ -79,6 +80,30 @@ __host__ __device__ inline double anch_link_pair(const double *a, const double *
   const double vx = ux - t * dx, vy = uy - t * dy, vz = uz - t * dz;
   const double v = sqrt(vx * vx + vy * vy + vz * vz) - sqrt(s[3]) - rho;
   return L2 != L2 ? __builtin_nan("") : v;
+}
+
+// The (link, sphere) pair as the solve kernel's link hinge reads it (WaveCtx<.., LINKS>, gik_wave.hip.h): the foot
+// parameter t of anch_link_pair, the vector m = (1 - t) a + t b - c from the sphere's centre to the foot, and d = m.m.
+// The hinge is  res = (r + rho)^2 - d > 0.  Every product and sum is rounded on its own
+// (AnchoredProblem.link_hinge_terms_host is the same operations in numpy); t = 0 gives m = a - c and t = 1 gives
+// m = b - c exactly, so a link that clamps to an end carries that end's node residual.
+__host__ __device__ inline void anch_link_foot(const double *a, const double *b, const double *s, double &t, double (&m)[3],
+                                               double &d) {
+#pragma clang fp contract(off)
+  const double dx = b[0] - a[0], dy = b[1] - a[1], dz = b[2] - a[2];
+  const double L2 = dx * dx + dy * dy + dz * dz;
+  const double ux = s[0] - a[0], uy = s[1] - a[1], uz = s[2] - a[2];
+  t = 0.0;
+  if (L2 > 0.0) {
+    t = (ux * dx + uy * dy + uz * dz) / L2;
+    t = t > 0.0 ? t : 0.0;
+    t = t < 1.0 ? t : 1.0;
+  }
+  const double w = 1.0 - t;
+  m[0] = (w * a[0] + t * b[0]) - s[0];
+  m[1] = (w * a[1] + t * b[1]) - s[1];
+  m[2] = (w * a[2] + t * b[2]) - s[2];
+  d = m[0] * m[0] + m[1] * m[1] + m[2] * m[2];
 }
 
 // sample s of 0 .. S between two joint angles: two rounded products and one rounded sum, as the retry seeds are

@@ -15,6 +15,7 @@
 
 namespace gik {
 GIK_ALL_KERNELS(GIK_EXTERN_TEMPLATE)
+GIK_KERNELS_ANCH_LINK(GIK_EXTERN_TEMPLATE)
 static_assert(PLAN_MIG_SIMDS == MIG_SIMDS && PLAN_SLICE_STATE_BYTES == sizeof(SliceState) && PLAN_QUAD_SLOTS == QUAD_SLOTS,
               "gik_plan.h restates these constants of the kernel headers");
 static_assert(PLAN_CLAIM_KEY_MAX_TERMS == CLAIM_KEY_MAX_TERMS, "gik_plan.h restates this constant of gik_order.hip.h");
@@ -97,6 +98,15 @@ static WaveRow anchored_row() {
   r.lds = WaveCtx<K, D, true>::lds_bytes;
   return r;
 }
+// the fixed-anchor kernels with link hinges (gik_anchored_attach_links, hinges = 1).  Not a row of kWaveRows: creation never
+// chooses it, the attach call re-resolves an anchored 9-slot template to it
+static WaveRow anchored_link_row() {
+  WaveRow r{3, 9, ANCHORED};
+  r.solve = rtr_wave_kernel<3, 9, true, true, false, false, true>;
+  r.kat = kat_wave_kernel<3, 9, true, false, true>;
+  r.lds = WaveCtx<3, 9, true, false, true>::lds_bytes;
+  return r;
+}
 // <3, 20> is compiled for anchored templates only: the free-free formulation with more than 10 terms at a node runs
 // on the workgroup kernels (the 20-slot wavefront variant needed 796 B of scratch per lane: measured on the
 // two-end-effector tree of tests/golden/tree5.npz, 13 terms, 144 k against 382 k solves/s;
@@ -134,6 +144,9 @@ struct gik_template {
   int *d_link_a = nullptr, *d_link_b = nullptr;   // [n_link] rows of the full point matrix
   double *d_link_rho = nullptr;                   // [n_link]
   int n_link = -1;
+  bool link_hinges = false;                       // ... attached with hinges = 1: the solve kernels are the LINKS builds
+  std::vector<int> h_free_full, h_anchor_full;    // host copies of d_free_full / d_anchor_full and of the slot table:
+  std::vector<uint32_t> h_slot_meta;              // what the attach call builds the per-node link records from
   double axis_length = 1.0;
   int solver;
   gik::CgParams cg;
@@ -815,6 +828,8 @@ static int upload_anchored(gik_template *t, const gik_anchored_desc *ad) {
   t->d_anchor_full = const_cast<int *>(upload(t, ad->anchor_full_index, (size_t)ad->n_anchor, ok));
   t->d_clear_full = const_cast<int *>(upload(t, clear_full.data(), clear_full.size(), ok));
   t->n_clear = (int)clear_full.size();
+  t->h_free_full.assign(ad->free_full_index, ad->free_full_index + N);
+  t->h_anchor_full.assign(ad->anchor_full_index, ad->anchor_full_index + ad->n_anchor);
   t->full_N = ad->full_N;
   t->n_anchor = ad->n_anchor;
   t->axis_length = ad->axis_length;
@@ -904,6 +919,7 @@ static int create_impl(const gik_template_desc *d, const gik_anchored_desc *ad, 
   int occ = 0;
   if (resolve_kernels(t.get(), d, row, block_lds) || device_setup(t.get(), d, bh.meta, occ)) return -1;
   if (ad && upload_anchored(t.get(), ad)) return -1;
+  if (ad) t->h_slot_meta = bh.meta;
   if (t->f.is_block) {
     bool ok = true;
     t->bt.nc_term = upload(t.get(), clq.nc_term.data(), clq.nc_term.size(), ok);
@@ -1682,12 +1698,68 @@ int gik_anchored_clearance(const gik_template *anch, const double *d_Y_full, int
 }
 
 // ---- clearance of whole links, and its sweep between two configurations (gik_anch_seed.hip.h) -----------
+// hinges = 1: the per-node link records of WaveCtx<.., LINKS> ([ANCH_LMAX][ANCH_LROWS], zero = no link), or a refusal.  A
+// link end is a free node or a row of the anchor table; a link with two constant ends carries no hinge (it is still measured).
+static int link_hinge_records(const gik_template *t, const gik_link_desc *d, std::vector<gik::AnchLinkRec> &recs) {
+  using namespace gik;
+  const std::string e("gik_anchored_attach_links");
+  if (t->maxdeg != 9)
+    return fail(e + ": hinges = 1 needs the 9-slot fixed-anchor kernel; this template runs the " + std::to_string(t->maxdeg) +
+                "-slot variant, which has no link hinges");
+  recs.assign((size_t)ANCH_LMAX * ANCH_LROWS, AnchLinkRec{0.0, 0u, 0u});
+  std::vector<int> cnt(t->N, 0);
+  // full row -> free node, or anchor row, or neither
+  auto find = [](const std::vector<int> &v, int row) {
+    for (size_t i = 0; i < v.size(); ++i)
+      if (v[i] == row) return (int)i;
+    return -1;
+  };
+  // the slot of free node i whose neighbour is free node j (a real term, not padding), or -1
+  auto slot_to = [&](int i, int j) {
+    for (int s = 0; s < t->maxdeg; ++s) {
+      const uint32_t m = t->h_slot_meta[(size_t)s * WAVE + i * 3];
+      if (((m >> 24) & 3u) != 0u && meta_j(m) == j) return s;
+    }
+    return -1;
+  };
+  for (int l = 0; l < d->n_link; ++l) {
+    const int row[2] = {d->link_a[l], d->link_b[l]};
+    int fr[2], an[2];
+    for (int q = 0; q < 2; ++q) {
+      fr[q] = find(t->h_free_full, row[q]);
+      an[q] = fr[q] < 0 ? find(t->h_anchor_full, row[q]) : -1;
+      if (fr[q] < 0 && an[q] < 0)
+        return fail(e + ": hinges = 1: link " + std::to_string(l) + " ends at row " + std::to_string(row[q]) +
+                    ", which is neither a free node nor an anchor row");
+    }
+    if (fr[0] < 0 && fr[1] < 0) continue;
+    int slot[2] = {0xff, 0xff};
+    if (fr[0] >= 0 && fr[1] >= 0) {
+      slot[0] = slot_to(fr[0], fr[1]);
+      slot[1] = slot_to(fr[1], fr[0]);
+      if (fr[0] == fr[1] || slot[0] < 0 || slot[1] < 0)
+        return fail(e + ": hinges = 1: the two free ends of link " + std::to_string(l) + " share no term");
+    }
+    for (int q = 0; q < 2; ++q) {
+      if (fr[q] < 0) continue;
+      if (cnt[fr[q]] >= ANCH_LMAX)
+        return fail(e + ": hinges = 1: more than " + std::to_string(ANCH_LMAX) + " hinge links at free node " + std::to_string(fr[q]));
+      const bool oc = fr[1 - q] < 0;
+      AnchLinkRec &r = recs[(size_t)cnt[fr[q]]++ * ANCH_LROWS + fr[q]];
+      r.rho = d->link_radius[l];
+      r.meta = link_meta_pack(q, oc ? 1 : 0, oc ? an[1 - q] : fr[1 - q], slot[q]);
+    }
+  }
+  return 0;
+}
+
 int gik_anchored_attach_links(gik_template *anch, const gik_link_desc *d) {
   using namespace gik;
   const std::string e("gik_anchored_attach_links");
   if (!anch || !d) return fail(e + ": null argument");
   if (!anch->anchored) return fail(e + ": the handle must be a fixed-anchor template (gik_template_create_anchored)");
   if (anch->n_link >= 0) return fail(e + ": links already attached");
+  if (d->hinges != 0 && d->hinges != 1) return fail(e + ": hinges must be 0 (measure only) or 1 (the solve carries link hinges)");
   if (d->n_link < 0 || d->n_link > ANCH_MAXLINK) return fail(e + ": n_link must be within 0 .. 64");
   if (d->n_link > 0 && (!d->link_a || !d->link_b || !d->link_radius)) return fail(e + ": null link array");
   for (int l = 0; l < d->n_link; ++l) {
@@ -1696,6 +1768,8 @@ int gik_anchored_attach_links(gik_template *anch, const gik_link_desc *d) {
     if (!(d->link_radius[l] >= 0.0) || d->link_radius[l] == __builtin_huge_val())
       return fail(e + ": link_radius[" + std::to_string(l) + "] must be finite and at least 0");
   }
+  std::vector<AnchLinkRec> recs;
+  if (d->hinges && link_hinge_records(anch, d, recs)) return -1;
   bool ok = true;
   int *la = const_cast<int *>(upload(anch, d->link_a, (size_t)d->n_link, ok));
   int *lb = const_cast<int *>(upload(anch, d->link_b, (size_t)d->n_link, ok));
@@ -1704,6 +1778,21 @@ int gik_anchored_attach_links(gik_template *anch, const gik_link_desc *d) {
   anch->d_link_a = la;
   anch->d_link_b = lb;
   anch->d_link_rho = lr;
+  if (d->hinges) {
+    // the template's solve and known-answer kernels become the LINKS builds, with their LDS bytes and occupancy
+    static const WaveRow row = anchored_link_row();
+    const AnchLinkRec *dr = upload(anch, recs.data(), recs.size(), ok);
+    int occ = 0;
+    if (!ok || hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)row.solve, WAVE, row.lds(anch->T)) != hipSuccess)
+      return fail(e + ": device upload failed");
+    anch->an.link_rec = dr;
+    anch->kernels.solve = row.solve;
+    anch->kernels.kat = row.kat;
+    anch->kernels.occupancy = (const void *)row.solve;
+    anch->smem_bytes = row.lds(anch->T);
+    anch->f.waves_per_cu = std::max(1, std::min(occ, 32));
+    anch->link_hinges = true;
+  }
   anch->n_link = d->n_link;
   return 0;
 }
@@ -2416,7 +2505,7 @@ int gik_template_get_info(const gik_template *t, gik_template_info *info) {
   info->lds_bytes = (int32_t)t->smem_bytes;
   info->clique_closed_form = t->clique_mode;
   info->hessian_form = (t->hess_per_edge || t->f.is_block) ? GIK_HESS_PER_EDGE : GIK_HESS_COLUMN;
-  info->anchored = t->anchored ? 1 : 0;
+  info->anchored = t->anchored ? (t->link_hinges ? 3 : 1) : 0;
   info->has_pipeline = t->has_pipe ? 1 : 0;
   info->prepare_is_block = t->prep_block ? 1 : 0;
   info->node_per_lane = t->f.is_npt ? t->npt_variant->NW : 0;

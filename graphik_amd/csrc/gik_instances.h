@@ -37,6 +37,11 @@
   X(void kat_wave_kernel<3, 9, true>(KatArgs))          \
   X(void rtr_wave_kernel<3, 20, true, true>(SolveArgs)) \
   X(void kat_wave_kernel<3, 20, true>(KatArgs))
+// ... with link hinges (gik_anchored_attach_links, hinges = 1).  Beside GIK_ALL_KERNELS, not inside it: gik_host.hip
+// expands this group on its own
+#define GIK_KERNELS_ANCH_LINK(X)                                          \
+  X(void rtr_wave_kernel<3, 9, true, true, false, false, true>(SolveArgs)) \
+  X(void kat_wave_kernel<3, 9, true, false, true>(KatArgs))
 // one unknown per lane, k = 2
 #define GIK_KERNELS_WAVE2(X)                       \
   X(void rtr_wave_kernel<2, 6, true>(SolveArgs))   \

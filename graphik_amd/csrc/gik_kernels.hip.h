@@ -105,6 +105,7 @@ struct AnchArgs {
   const double *obs;            // [n_obs][4] x, y, z, r^2
   unsigned long long obs_mask;  // bit i: free node i carries the obstacle hinges
   int n_obs, n_goal, goal_row0; // goal anchors occupy rows goal_row0 .. goal_row0 + n_goal - 1
+  const AnchLinkRec *link_rec = nullptr;   // [ANCH_LMAX][ANCH_LROWS] link hinges per free node (LINKS kernels only)
 };
 
 struct SolveArgs {
@@ -243,12 +244,15 @@ __device__ inline void stage_lds(double *tiles, uint32_t *meta, const uint32_t *
 // as well have that SIMD's whole register file -- at two waves per SIMD it spilled into the hot loop)
 // STRICT: the Hessian product term by term as costs.py:186-203 forms it (gik_wave_strict.hip.h;
 // gik_template_desc.hessian_form = GIK_HESS_PER_EDGE), k = 3 free-free graphs
-template <int K, int MAXDEG, bool THETA_ONE, bool ANCH = false, bool MIG = false, bool STRICT = false>
-__global__ void __launch_bounds__(WAVE, ANCH ? 1 : 2) rtr_wave_kernel(SolveArgs a) {
+// LINKS: link hinges in the fixed-anchor solve (WaveCtx<.., LINKS>, gik_anchored_attach_links with hinges = 1).
+// The kernel's text is this function; rtr_wave_kernel below is its two entry points.
+template <int K, int MAXDEG, bool THETA_ONE, bool ANCH, bool MIG, bool STRICT, bool LINKS>
+__device__ __forceinline__ void rtr_wave_run(const SolveArgs &a) {
+  static_assert(!LINKS || (ANCH && MAXDEG == 9), "link hinges: the 9-slot fixed-anchor kernel");
   static_assert(!ANCH || K == 3, "the fixed-anchor formulation is 3-D");
   static_assert(!MIG || !ANCH, "tail spreading: two waves per SIMD, i.e. not the anchored variant");
   static_assert(!STRICT || (K == 3 && !ANCH), "the per-edge product form: 3-D free-free graphs");
-  using Ctx = std::conditional_t<STRICT, WaveCtxStrict<MAXDEG>, WaveCtx<K, MAXDEG, ANCH>>;
+  using Ctx = std::conditional_t<STRICT, WaveCtxStrict<MAXDEG>, WaveCtx<K, MAXDEG, ANCH, false, LINKS>>;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int lane = threadIdx.x;
   const int NK = a.N * K;
@@ -263,6 +267,7 @@ __global__ void __launch_bounds__(WAVE, ANCH ? 1 : 2) rtr_wave_kernel(SolveArgs 
     // every target is a template constant here: records, pinned records and the constant rows of
     // the anchor table are staged once per wave; only the goal anchors change per problem
     cx.init_anchored(a.an.obs_mask, a.an.obs, a.an.n_obs, !(a.dbg & 128));
+    if constexpr (LINKS) cx.init_links(a.an.link_rec);
     for (int t = lane; t < a.T; t += WAVE) sh_tgt[t] = a.targets[t];
     for (int t = lane; t < 4 * ANCH_MAXA; t += WAVE) cx.sh_anch[t] = a.an.anch_const[t];
     __builtin_amdgcn_wave_barrier();
@@ -366,6 +371,7 @@ __global__ void __launch_bounds__(WAVE, ANCH ? 1 : 2) rtr_wave_kernel(SolveArgs 
         cx.sh_anch[(a.an.goal_row0 + lane / 3) * 4 + lane % 3] =
             a.an.anchor_goal[(size_t)b * 3 * a.an.n_goal + lane];
       cx.obs_reset();
+      if constexpr (LINKS) cx.links_reset();
     } else {
       for (int t = lane; t < a.T; t += WAVE) sh_tgt[t] = a.targets[(size_t)b * a.T + t];
       __builtin_amdgcn_wave_barrier();
@@ -459,6 +465,18 @@ __global__ void __launch_bounds__(WAVE, ANCH ? 1 : 2) rtr_wave_kernel(SolveArgs 
   }
 #endif
 }
+// Two templates of one name.  The six-parameter one is every kernel without link hinges, under the symbol names it has
+// always had (tools and tests find kernels in the code object by them); LINKS is the seventh parameter of an overload of
+// its own, so rtr_wave_kernel<3, 9, true, true, false, false, true> names the link build and nothing else moves.
+template <int K, int MAXDEG, bool THETA_ONE, bool ANCH = false, bool MIG = false, bool STRICT = false>
+__global__ void __launch_bounds__(WAVE, ANCH ? 1 : 2) rtr_wave_kernel(SolveArgs a) {
+  rtr_wave_run<K, MAXDEG, THETA_ONE, ANCH, MIG, STRICT, false>(a);
+}
+template <int K, int MAXDEG, bool THETA_ONE, bool ANCH, bool MIG, bool STRICT, bool LINKS>
+__global__ void __launch_bounds__(WAVE, ANCH ? 1 : 2) rtr_wave_kernel(SolveArgs a) {
+  static_assert(LINKS, "the seven-parameter form is the link build; every other kernel is rtr_wave_kernel<K, MAXDEG, THETA_ONE, ...>");
+  rtr_wave_run<K, MAXDEG, THETA_ONE, ANCH, MIG, STRICT, LINKS>(a);
+}
 
 // Riemannian conjugate gradients (the reference's alternative solver), same persistent scheme
 template <int K, int MAXDEG>
@@ -528,9 +546,9 @@ struct KatArgs {
   double *npt_ctg_ws = nullptr;   // see SolveArgs
 };
 
-template <int K, int MAXDEG, bool ANCH = false, bool STRICT = false>
+template <int K, int MAXDEG, bool ANCH = false, bool STRICT = false, bool LINKS = false>
 __global__ void __launch_bounds__(WAVE) kat_wave_kernel(KatArgs a) {
-  using Ctx = std::conditional_t<STRICT, WaveCtxStrict<MAXDEG>, WaveCtx<K, MAXDEG, ANCH>>;
+  using Ctx = std::conditional_t<STRICT, WaveCtxStrict<MAXDEG>, WaveCtx<K, MAXDEG, ANCH, false, LINKS>>;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int lane = threadIdx.x;
   const int b = blockIdx.x;
@@ -546,6 +564,7 @@ __global__ void __launch_bounds__(WAVE) kat_wave_kernel(KatArgs a) {
   cx.init(lane, a.N, sh_tiles, sh_tgt, sh_meta);
   if constexpr (ANCH) {
     cx.init_anchored(a.an.obs_mask, a.an.obs, a.an.n_obs, true);
+    if constexpr (LINKS) cx.init_links(a.an.link_rec);
     for (int t = lane; t < 4 * ANCH_MAXA; t += WAVE) cx.sh_anch[t] = a.an.anch_const[t];
     __builtin_amdgcn_wave_barrier();
     if (lane < 3 * a.an.n_goal)

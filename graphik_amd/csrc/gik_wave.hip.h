@@ -327,12 +327,43 @@ constexpr int ANCH_PMAX = 8;
 constexpr int ANCH_MAXA = 16;   // rows of the pinned-anchor table
 constexpr int ANCH_MAXOBS = 128; // obstacles (staged in LDS: 32 B each)
 
+// LINKS: link hinges on top (opt-in per template, gik_anchored_attach_links with hinges = 1).  A link l = (a, b, rho) is
+// the segment between two rows of the full point matrix -- free rows of Y, constant base anchors or the per-problem goal
+// anchors -- and a capsule radius.  Against a sphere (C, r) with R = r + rho and the foot parameter t of anch_link_pair:
+//     m = (1 - t) A + t B - C,   d = m.m,   res = R^2 - d,   active <=> res > 0,   c = d - R^2
+//     f += res^2,   G_A += (1 - t) 2 c m,   G_B += t 2 c m,
+//     H_A += (1 - t) Bh w,  H_B += t Bh w,   Bh = 2 (2 m m^T + c I),   w = (1 - t) W_A + t W_B    (W of a constant end: 0)
+// The gradient is exact: min_t |A + t u - C|^2 is C^1 in A and B, so differentiating with t frozen gives its gradient
+// (envelope theorem).  The Hessian is the FROZEN-t model on purpose: positive semidefinite up to the c I part, cheap, and
+// the trust-region ratio is taken on the true cost, so the model error costs iterations, never correctness.
+// The node hinges (obs_mask) stay as they are.  Where t clamps to a masked end of a link with rho = 0 the link's residual is
+// that node's residual counted once more: a heavier weight on the same zero set.
+// Since (1 - t) + t = 1,  (1 - t) Bh w = (1 - t) Bh W_A - t (1 - t) Bh (W_A - W_B): a diagonal block (into `ba` of
+// commit(), like the anchor terms) and a difference-form block that goes into bq[s] of the slot whose neighbour is the other
+// end -- on a chain consecutive p-nodes always share the link-length equality -- so ehess() runs unchanged.
+// Records are per NODE (the three lanes of a node share them), at most ANCH_LMAX links per free node.
+constexpr int ANCH_LMAX = 2;
+constexpr int ANCH_LROWS = 22;  // rows of the per-node link tables: 3 N <= 64 gives 21 free nodes, + one inert row for idle lanes
+struct AnchLinkRec {
+  double rho;      // capsule radius of the link
+  uint32_t meta;   // [0] valid, [1] this node is end b, [2] the other end is a row of sh_anch (constant), [15:8] the other
+                   // end's row (tile row of a free node / row of sh_anch), [23:16] the slot whose neighbour it is (0xff: none)
+  uint32_t pad;
+};
+__host__ __device__ inline uint32_t link_meta_pack(int is_b, int other_const, int other_row, int slot) {
+  return 1u | ((uint32_t)is_b << 1) | ((uint32_t)other_const << 2) | ((uint32_t)other_row << 8) | ((uint32_t)slot << 16);
+}
+// (gik_anch_seed.hip.h, next to anch_link_pair; a translation unit that instantiates LINKS includes it)
+__host__ __device__ inline void anch_link_foot(const double *a, const double *b, const double *s, double &t, double (&m)[3],
+                                               double &d);
+
 // SLIM: the layout of the per-edge product form (WaveCtxStrict, gik_wave_strict.hip.h): only the natural-order tile,
 // and slot metadata / slot records of the slots a lane OWNS (node slots comp, comp + 3, ...) -- 8.3 instead of 18.9 KB
 // of LDS per wavefront on a 7-DOF arm, which is what lets three wavefronts share a SIMD (153 VGPRs).
-template <int K, int MAXDEG, bool ANCH = false, bool SLIM = false>
+template <int K, int MAXDEG, bool ANCH = false, bool SLIM = false, bool LINKS = false>
 struct WaveCtx {
   static_assert(!SLIM || (K == 3 && !ANCH), "the slim layout belongs to the 3-D per-edge context");
+  static_assert(!LINKS || (ANCH && MAXDEG == 9), "link hinges: the 9-slot fixed-anchor context");
   static constexpr int RS = (K == 3) ? 6 : 2;  // LDS row stride in doubles (48 B / 16 B)
   static constexpr int NC = (K == 3) ? 3 : 1;  // independent entries of the skew matrix
   static constexpr int TILE = TILE_ROWS * RS;  // doubles per rotated tile
@@ -356,7 +387,8 @@ struct WaveCtx {
            sizeof(uint32_t) * (size_t)NSL * WAVE + sizeof(SlotRec) * (size_t)NSL * WAVE +
            (HAS_CK ? sizeof(double) * 4 * WAVE : 0) +
            (ANCH ? sizeof(double) * 4 * (ANCH_MAXA + ANCH_MAXOBS) + 16 * (size_t)ANCH_PMAX * WAVE +
-                       48 * (size_t)WAVE : 0);
+                       48 * (size_t)WAVE : 0) +
+           (LINKS ? sizeof(double) * ANCH_MAXOBS + (sizeof(AnchLinkRec) + sizeof(LinkObs)) * (size_t)ANCH_LMAX * ANCH_LROWS : 0);
   }
   // ---- fixed-anchor data (ANCH) ----
   // Everything per lane lives in LDS records (the 9-slot kernel has no VGPR to spare: per-lane
@@ -392,6 +424,138 @@ struct WaveCtx {
   static constexpr float OBS_TAU = 0.05f;
   ObsState *sh_ost;        // [64]
   bool obs_cull;
+  // ---- link hinges (LINKS) ----
+  // Near list of one (node, link record), the node scheme applied to the segment: from the last full walk with the ends at
+  // ref, the (at most 8) obstacles whose conservative float clearance |segment - C| - R is below OBS_TAU and the smallest
+  // clearance `slack` among the others.  A point of the segment moves no farther than the farther end (a constant end has
+  // moved 0), so while max(moved_a, moved_b) < slack every other obstacle contributes exactly zero.  Both ends of a link
+  // keep the same list (the same operations on the same numbers).
+  struct LinkObs {
+    double ref[6];         // ends a, b at the last full walk
+    double slack;          // <= 0: walk everything
+    uint32_t idx[2];
+    uint32_t cnt, pad;
+  };
+  double *sh_obr;          // [ANCH_MAXOBS] obstacle radii (sqrt of sh_obs[.][3], once per wave)
+  AnchLinkRec *sh_lrec;    // [ANCH_LMAX][ANCH_LROWS]
+  LinkObs *sh_lost;        // [ANCH_LMAX][ANCH_LROWS]
+  int lrow;                // this lane's row of the link tables
+  int anch_off;            // sh_anch - sh_tile (doubles): either kind of "other end" is an offset from sh_tile
+  __device__ inline void init_links(const AnchLinkRec *link_rec) {
+    sh_obr = reinterpret_cast<double *>(sh_ost + WAVE);
+    sh_lrec = reinterpret_cast<AnchLinkRec *>(sh_obr + ANCH_MAXOBS);
+    sh_lost = reinterpret_cast<LinkObs *>(sh_lrec + ANCH_LMAX * ANCH_LROWS);
+    lrow = active ? node : ANCH_LROWS - 1;
+    anch_off = (int)(sh_anch - sh_tile);
+    __builtin_amdgcn_wave_barrier();
+    for (int t = lane; t < n_obs; t += WAVE) sh_obr[t] = sqrt(sh_obs[4 * t + 3]);
+    if (lane < ANCH_LMAX * ANCH_LROWS) sh_lrec[lane] = link_rec[lane];
+    links_reset();
+  }
+  __device__ inline void links_reset() {
+    if (lane < ANCH_LMAX * ANCH_LROWS) {
+      LinkObs st = {{0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, -1.0, {0u, 0u}, 0u, 0u};
+      sh_lost[lane] = st;
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+  // where the other end of a link record lives, as a double offset from sh_tile (tile 0 is in natural component order)
+  __device__ inline int link_other(uint32_t meta) const {
+    const int row = (int)((meta >> 8) & 0xffu);
+    return (meta & 4u) ? anch_off + 4 * row : RS * row;
+  }
+  // true (wave-uniform) when both ends of every link are within the slack of its last full walk
+  __device__ inline bool links_near_only(const Row<K> &nat) const {
+    bool ok = true;
+#pragma unroll
+    for (int l = 0; l < ANCH_LMAX; ++l) {
+      const AnchLinkRec rc = sh_lrec[l * ANCH_LROWS + lrow];
+      const LinkObs &st = sh_lost[l * ANCH_LROWS + lrow];
+      const double *po = sh_tile + link_other(rc.meta);
+      const double *r_own = st.ref + ((rc.meta & 2u) ? 3 : 0), *r_oth = st.ref + ((rc.meta & 2u) ? 0 : 3);
+      const double a0 = nat.v[0] - r_own[0], a1 = nat.v[1] - r_own[1], a2 = nat.v[K - 1] - r_own[2];
+      const double b0 = po[0] - r_oth[0], b1 = po[1] - r_oth[1], b2 = po[2] - r_oth[2];
+      const double moved2 = fmax(fma(a2, a2, fma(a1, a1, a0 * a0)), fma(b2, b2, fma(b1, b1, b0 * b0)));
+      ok = ok && (!(rc.meta & 1u) || (st.slack > 0.0 && moved2 * (1.0 + 1e-9) < st.slack * st.slack));
+    }
+    return obs_cull && __builtin_amdgcn_ballot_w64(!ok) == 0ull;
+  }
+  // Link record l of this lane's node against the obstacles (all of them, or the near list).  Both ends of a link run
+  // this with a and b in the LINK's order and natural component order, so they carry the same bits of t, m and res (the
+  // reason is the one given for the one-residual-per-term rule in commit()).  Records are walked one after the other, each
+  // over the obstacles in ascending order, in the full and in the near walk alike: culling cannot change a sum.
+  //   cost (COMMIT = false): fl += res^2; a full walk renews the near list.
+  //   commit: G, the diagonal block `ba` ((1 - t) or t times the row of 2 m m^T + c I; its square where the other end is a
+  //   constant) and lk = sum of t (1 - t) rows, the difference-form block towards a free other end.
+  template <bool COMMIT>
+  __device__ inline void link_walk(const Row<K> &nat, int l, bool near_only, double &fl, double &G, double (&ba)[K],
+                                   double (&lk)[K]) {
+    const AnchLinkRec rc = sh_lrec[l * ANCH_LROWS + lrow];
+    const bool valid = rc.meta & 1u, is_b = rc.meta & 2u, oth_const = rc.meta & 4u;
+    const double *po = sh_tile + link_other(rc.meta);
+    double A[3], B[3];
+    A[0] = is_b ? po[0] : nat.v[0]; A[1] = is_b ? po[1] : nat.v[1]; A[2] = is_b ? po[2] : nat.v[K - 1];
+    B[0] = is_b ? nat.v[0] : po[0]; B[1] = is_b ? nat.v[1] : po[1]; B[2] = is_b ? nat.v[K - 1] : po[2];
+    LinkObs &st = sh_lost[l * ANCH_LROWS + lrow];
+    const uint32_t ncnt = (near_only && valid) ? st.cnt : 0u;
+    double slack = 1e30;
+    uint32_t idx[2] = {0u, 0u}, cnt = 0u;
+    const int walk = near_only ? 8 : n_obs;
+    for (int k0 = 0; k0 < walk; ++k0) {
+      if (near_only && __builtin_amdgcn_ballot_w64((uint32_t)k0 < ncnt) == 0ull) break;
+      const bool mine = near_only ? (uint32_t)k0 < ncnt : valid;
+      const int k = near_only ? (mine ? (int)((st.idx[k0 >> 2] >> (8u * (k0 & 3u))) & 0xffu) : 0) : k0;
+      const double4 o = *reinterpret_cast<const double4 *>(sh_obs + 4 * k);
+      const double C[3] = {o.x, o.y, o.z};
+      double t, m[3], d;
+      anch_link_foot(A, B, C, t, m, d);
+      const double R = sh_obr[k] + rc.rho;
+      if (!COMMIT && !near_only) {
+        const float clr = __builtin_sqrtf((float)d) * (1.0f - 1e-6f) - (float)R * (1.0f + 1e-6f) - 1e-6f;
+        if (clr < OBS_TAU) {
+          if (cnt < 8u) idx[cnt >> 2] |= (uint32_t)k << (8u * (cnt & 3u));
+          ++cnt;
+        } else {
+          slack = fmin(slack, (double)clr);
+        }
+      }
+      const double cl = mine ? fmax(R * R - d, 0.0) : 0.0;
+      if constexpr (!COMMIT) {
+        fl = fma(cl, cl, fl);
+      } else {
+        if (__builtin_amdgcn_ballot_w64(cl != 0.0) == 0ull) continue;   // nobody's link touches this obstacle
+        const double w_own = is_b ? t : 1.0 - t, w_oth = is_b ? 1.0 - t : t;
+        // (a constant other end has W = 0: its share - t (1 - t) Bh W_own stays on the diagonal, w_own - kap = w_own^2)
+        const double kap = oth_const ? 0.0 : w_own * w_oth;
+        const double wd = oth_const ? w_own * w_own : w_own;
+        double y[K];
+        rotate_nat(m, y);
+        const double c = -cl;
+        const double a2 = (cl != 0.0) ? 2.0 * y[0] : 0.0;
+#pragma unroll
+        for (int q = 0; q < K; ++q) {
+          const double blk = q == 0 ? fma(a2, y[0], c) : a2 * y[q];
+          ba[q] = fma(wd, blk, ba[q]);
+          lk[q] = fma(kap, blk, lk[q]);
+        }
+        G = fma(w_own * c, y[0], G);
+      }
+    }
+    if (!COMMIT && !near_only && active && comp == 0) {
+      LinkObs n;
+#pragma unroll
+      for (int q = 0; q < 3; ++q) {
+        n.ref[q] = A[q];
+        n.ref[3 + q] = B[q];
+      }
+      n.slack = cnt > 8u ? -1.0 : slack;
+      n.idx[0] = idx[0];
+      n.idx[1] = idx[1];
+      n.cnt = cnt > 8u ? 0u : cnt;
+      n.pad = 0u;
+      st = n;
+    }
+  }
   __device__ inline void init_anchored(const uint64_t obs_mask, const double *obs, int n_obs_, bool cull) {
     sh_anch = sh_ck + 4 * WAVE;
     sh_obs = sh_anch + 4 * ANCH_MAXA;
@@ -612,7 +776,9 @@ struct WaveCtx {
         const double cl = pin_residual(rc.tg, (int)((rc.meta >> 8) & 3u), d, eq);
         fa = fma(cl, cl, fa);
       }
-      if (obs_near_only(nat)) {
+      bool near_only = obs_near_only(nat);
+      if constexpr (LINKS) near_only = links_near_only(nat) && near_only;   // full walks of nodes and links happen together
+      if (near_only) {
         const ObsState &st = sh_ost[lane];
         const uint32_t cnt = obs_lane ? st.cnt : 0u;
         for (uint32_t q = 0; __builtin_amdgcn_ballot_w64(q < cnt) != 0ull; ++q) {
@@ -637,6 +803,18 @@ struct WaveCtx {
         obs_store(nat, slack, idx, cnt);
       }
       f = fma(2.0, fa, f);
+      if constexpr (LINKS) {
+        // a pair enters f once: a link between two free nodes is evaluated at both (halved below), one with a constant
+        // end at its free node alone (doubled first, like the anchor terms)
+        double G_ = 0.0, b_[K], k_[K];
+#pragma unroll 1
+        for (int l = 0; l < ANCH_LMAX; ++l) {
+          double fl = 0.0;
+          link_walk<false>(nat, l, near_only, fl, G_, b_, k_);
+          f += (sh_lrec[l * ANCH_LROWS + lrow].meta & 4u) ? 2.0 * fl : fl;
+        }
+        __builtin_amdgcn_wave_barrier();   // the near lists are written by one lane of a node and read by all three
+      }
     }
     return 0.5 * wave_sum((active && comp == 0) ? f : 0.0);
   }
@@ -712,7 +890,8 @@ struct WaveCtx {
         G = fma(c, y[0], G);
       }
       // (commit() follows cost() at the same point, so the near lists are fresh; it never refreshes)
-      const bool near_only = obs_near_only(nat);
+      bool near_only = obs_near_only(nat);
+      if constexpr (LINKS) near_only = links_near_only(nat) && near_only;
       const ObsState &st = sh_ost[lane];
       const uint32_t ncnt = (near_only && obs_lane) ? st.cnt : 0u;
       const int walk = near_only ? 8 : n_obs;
@@ -733,6 +912,23 @@ struct WaveCtx {
         for (int q = 0; q < K; ++q) ba[q] = fma(a2, y[q], ba[q]);
         ba[0] += c;
         G = fma(c, y[0], G);
+      }
+      if constexpr (LINKS) {
+#pragma unroll 1
+        for (int l = 0; l < ANCH_LMAX; ++l) {
+          double fl_ = 0.0, lk[K];
+#pragma unroll
+          for (int q = 0; q < K; ++q) lk[q] = 0.0;
+          link_walk<true>(nat, l, near_only, fl_, G, ba, lk);
+          // - t (1 - t) Bh towards the other end, in the slot that points at it (bq holds +2 B_ij rows here)
+          const int sl = (int)((sh_lrec[l * ANCH_LROWS + lrow].meta >> 16) & 0xffu);
+#pragma unroll
+          for (int s = 0; s < MAXDEG; ++s) {
+            const double w = sl == s ? -2.0 : 0.0;
+#pragma unroll
+            for (int q = 0; q < K; ++q) bq[s][q] = fma(w, lk[q], bq[s][q]);
+          }
+        }
       }
     }
 #pragma unroll

@@ -200,6 +200,7 @@ class Template:
                 _ffi.check(self.lib.gik_template_create_anchored(C.byref(d), C.byref(ad), C.byref(h)))
         self._h = h
         self.n_link = None      # (attach_links)
+        self.link_hinges = False
         self._read_info()
         deg = np.bincount(np.concatenate([self.term_i, self.term_j]), minlength=self.N).max()
         # compiled slot count of the wavefront variant the library chose (or the raw degree: workgroup / node-per-lane paths)
@@ -565,21 +566,28 @@ class Template:
             _ffi.check(self.lib.gik_anchored_clearance(self._h, Y.data_ptr(), B, out.data_ptr(), self._stream()))
         return out
 
-    def attach_links(self, link_a, link_b, link_radius):
+    def attach_links(self, link_a, link_b, link_radius, hinges=False):
         """The link set of an anchored template (gik_anchored_attach_links), once: link l is the segment between rows
-        link_a[l] and link_b[l] of the full point matrix, a capsule of radius link_radius[l] >= 0 (metres)."""
+        link_a[l] and link_b[l] of the full point matrix, a capsule of radius link_radius[l] >= 0 (metres).
+        hinges=True: the solve carries link hinges (gik_link_desc.hinges = 1) -- every later call on this template, the
+        known-answer entry points included, runs the link builds of its kernels; self.link_hinges and
+        self.info["anchored"] == 3 say so."""
+        if not isinstance(hinges, (bool, np.bool_)):
+            raise TypeError(f"hinges must be a bool, got {hinges!r}")
         assert self.anchored
         a = np.ascontiguousarray(link_a, dtype=np.int32).reshape(-1)
         b = np.ascontiguousarray(link_b, dtype=np.int32).reshape(-1)
         r = np.ascontiguousarray(link_radius, dtype=np.float64).reshape(-1)
         if not len(a) == len(b) == len(r):
             raise ValueError("link_a, link_b and link_radius must have one entry per link")
-        d = _ffi.LinkDesc(n_link=len(a), link_a=a.ctypes.data_as(C.POINTER(C.c_int32)),
+        d = _ffi.LinkDesc(n_link=len(a), hinges=int(hinges), link_a=a.ctypes.data_as(C.POINTER(C.c_int32)),
                           link_b=b.ctypes.data_as(C.POINTER(C.c_int32)),
                           link_radius=r.ctypes.data_as(C.POINTER(C.c_double)))
         with torch.cuda.device(self.device):
             _ffi.check(self.lib.gik_anchored_attach_links(self._h, C.byref(d)))
         self.n_link = len(a)
+        self.link_hinges = bool(hinges)
+        self._read_info()      # (hinges: other kernels, LDS bytes and occupancy)
 
     def anchored_link_clearance(self, Y_full):
         """Full point matrices [B, full_N, 3] -> link clearance [B] on the device (gik_anchored_link_clearance): the

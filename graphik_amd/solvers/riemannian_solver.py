@@ -518,19 +518,29 @@ class AnchoredProblem:
     add_spherical_obstacle).  The initial point is the robot graph's own (bound smoothing + MDS
     without obstacles) fitted to the world frame by its anchors."""
 
-    def __init__(self, graph, params=None, device=None, host_only=False, links=None, link_radius=0.0):
+    def __init__(self, graph, params=None, device=None, host_only=False, links=None, link_radius=0.0, link_hinges=False):
         """host_only: derive the term set only (no device handles) -- what tests/test_host_layer.py
         compares with the reference's own edge construction (tests/golden/ur10_table_intended.npz).
 
         links: the segments whose clearance link_clearance / clearance_mode="links" measure, as (name_a, name_b)
         pairs of robot-graph nodes.  None: the chain's skeleton p0->p1, ..., p(n-1)->pn, base and end-effector rows
         included (the last link is real geometry even though its end is a constant of the goal).  [] attaches none.
-        link_radius: the capsule radius of the links in metres, >= 0, a scalar or one entry per link."""
+        link_radius: the capsule radius of the links in metres, >= 0, a scalar or one entry per link.
+        link_hinges: False -- the links are measured only, the solve sees the joint points (the node hinges) -- or True:
+        the solve kernel also carries a hinge per (link, sphere) on the distance from the sphere's centre to the link's
+        SEGMENT (gik_anchored_attach_links with hinges = 1; link_hinge_terms_host is the numpy mirror of the terms), so
+        every solve, restart and tracked waypoint of this problem pushes whole links out of the spheres.  The node
+        hinges stay.  Needs a link set; chains on the 9-slot anchored kernel."""
         import copy
         from ..utils.constants import OBSTACLE, ROBOT, TYPE, MAIN_PREFIX
         from .. import _ffi
         if graph.dim != 3 or not graph.robot.is_chain:
             raise NotImplementedError("the fixed-anchor formulation covers 3-D chains")
+        if not isinstance(link_hinges, (bool, np.bool_)):      # (before any device call)
+            raise ValueError(f"link_hinges must be a bool, got {link_hinges!r}")
+        if link_hinges and links is not None and len(links) == 0:
+            raise ValueError("link_hinges=True needs a link set: links=[] attaches none")
+        self.link_hinges = bool(link_hinges)
         self.graph, self.robot = graph, graph.robot
         obstacles = [n for n in graph.node_ids if graph.nodes[n].get(TYPE) == OBSTACLE]
         bare = copy.deepcopy(graph)
@@ -572,6 +582,7 @@ class AnchoredProblem:
         pos = np.zeros((len(anchors), 3))
         pos[:len(bp.anchor_nodes)] = bp.anchor_pos
         self.free, self.anchors, self.pin = free, anchors, pin
+        self.anchor_pos, self.n_goal_anchor = pos, len(goal)      # (goal rows: zeros, filled per problem)
         self.free_names = names
         self.free_terms = (ti, tj, tk, target)
         self.obs_mask = np.array(mask, dtype=np.int32)
@@ -602,7 +613,7 @@ class AnchoredProblem:
                           obs=obs, obs_node_mask=mask, full_N=N, free_full_index=free,
                           anchor_full_index=anchors, axis_length=graph.axis_length))
         if len(links):
-            self.template.attach_links(self.link_rows[:, 0], self.link_rows[:, 1], self.link_radius)
+            self.template.attach_links(self.link_rows[:, 0], self.link_rows[:, 1], self.link_radius, hinges=self.link_hinges)
 
     def goal_anchors(self, T_goals):
         """[B,4,4] -> [B, 2*3]: p_n, q_n world positions (graph_revolute.py:243-249)."""
@@ -625,7 +636,9 @@ class AnchoredProblem:
 
         clearance_mode: "nodes" -- "clearance" is that of the joint points (self.clearance), which does not see a
         link that crosses a sphere between two of them -- or "links": it is that of whole links
-        (self.link_clearance; the problem must have links), with retries=0 too.
+        (self.link_clearance; the problem must have links), with retries=0 too.  On a problem built with
+        link_hinges=True the solve itself carries link hinges, so clearance_mode="links" then has hinges behind it: the
+        rule reads a clearance the cost acts on.
 
         retries > 0 (gik_anchored_ik_batch_retry): a goal that fails -- stop != 0, pos_err > pos_tol, rot_err >
         rot_tol or clearance < -clear_tol, so an answer on its goal with a joint point (clearance_mode="nodes") or
@@ -664,7 +677,8 @@ class AnchoredProblem:
         that many radians of the previous waypoint's angles.  The stream then synchronises once per attempt
         and waypoint; info["attempt"] [B, L] int32 says which attempt each waypoint holds.
 
-        clearance_mode: as in solve() -- which clearance info["clearance"] holds and the rule reads.
+        clearance_mode: as in solve() -- which clearance info["clearance"] holds and the rule reads; with
+        link_hinges=True clearance_mode="links" has hinges behind it at every waypoint.
         sweep=S (an integer >= 1; the problem must have links): adds info["sweep_clearance"] [B, L], the minimum link
         clearance over S + 1 joint-space samples between waypoint l-1's answer (q_start for waypoint 0) and waypoint
         l's (sweep_clearance(q[:, l-1], q[:, l], S)), one gik_anchored_sweep_clearance call per waypoint on the rows
@@ -773,6 +787,80 @@ class AnchoredProblem:
             val = np.sqrt(dot(v, v)) - np.sqrt(r2)[None, None, :] - self.link_radius[None, :, None]
             val = np.where(np.isnan(L2), np.nan, val)
         return np.where(np.isnan(val).any(axis=(1, 2)), np.nan, np.where(np.isnan(val), np.inf, val).min(axis=(1, 2)))
+
+    @staticmethod
+    def link_foot_host(a, b, c):
+        """One (link, sphere centre) pair -> (t, m, d): the foot parameter of link_clearance, m = (1 - t) a + t b - c and
+        d = m.m, in scalar doubles -- the operations of the device pair function (anch_link_foot) in its order."""
+        a, b, c = ([float(v) for v in x] for x in (a, b, c))
+        dx, dy, dz = b[0] - a[0], b[1] - a[1], b[2] - a[2]
+        L2 = dx * dx + dy * dy + dz * dz
+        ux, uy, uz = c[0] - a[0], c[1] - a[1], c[2] - a[2]
+        t = 0.0
+        if L2 > 0.0:
+            t = (ux * dx + uy * dy + uz * dz) / L2
+            t = t if t > 0.0 else 0.0
+            t = t if t < 1.0 else 1.0
+        w = 1.0 - t
+        m = np.array([(w * a[q] + t * b[q]) - c[q] for q in range(3)])
+        return t, m, float(m[0] * m[0] + m[1] * m[1] + m[2] * m[2])
+
+    def link_ends_host(self, Y_free, W, goal_anchor):
+        """Per link: ((A, W_A, i_A), (B, W_B, i_B)) -- position, direction and free-node index of either end at the point
+        Y_free [Nf, 3]; a constant end (base anchor, or goal anchor from goal_anchor [n_goal * 3]) has W = 0 and index None."""
+        Y, W = np.asarray(Y_free, dtype=np.float64), np.asarray(W, dtype=np.float64)
+        apos = np.array(self.anchor_pos, dtype=np.float64)
+        if self.n_goal_anchor:
+            apos[len(apos) - self.n_goal_anchor:] = np.asarray(goal_anchor, dtype=np.float64).reshape(-1, 3)
+        fidx = {n: f for f, n in enumerate(self.free)}
+        aidx = {n: r for r, n in enumerate(self.anchors)}
+        end = lambda r: (Y[fidx[r]], W[fidx[r]], fidx[r]) if r in fidx else (apos[aidx[r]], np.zeros(3), None)   # noqa: E731
+        return [(end(int(ra)), end(int(rb))) for ra, rb in self.link_rows]
+
+    def link_hinge_terms_host(self, Y_free, W, goal_anchor, frozen_t=None):
+        """(f, G, H) of the link hinges alone at one point: Y_free, W [Nf, 3], goal_anchor [n_goal * 3], in the
+        conventions of the anchored kernels' known answers (f = sum res^2, G = 1/2 grad f, H = 1/2 Hess f [W]).  Per
+        (link, sphere), with A, B the link's ends, R = r + rho and (t, m, d) of link_foot_host:
+            res = R^2 - d,  active <=> res > 0,  c = d - R^2
+            f += res^2;  G_A += (1 - t) 2 c m;  G_B += t 2 c m
+            w = (1 - t) W_A + t W_B;  H_A += (1 - t) 2 (2 (m.w) m + c w);  H_B += t 2 (2 (m.w) m + c w)
+        Contributions to a constant end are dropped; a link with two constant ends has no hinge.  The gradient is exact
+        (envelope theorem), H is the frozen-t model the solve kernel uses.  The full reference of a point is the
+        free-free and anchor terms plus this.  frozen_t: {(link, obstacle): t} to evaluate at instead of the foot
+        parameters of this point (what a finite difference of the frozen-t gradient needs); active pairs' t come back
+        in self.last_link_t."""
+        Y = np.asarray(Y_free, dtype=np.float64)
+        f, G, H = 0.0, np.zeros_like(Y), np.zeros_like(Y)
+        self.last_link_t = {}
+        for l, ((A, WA, ia), (B, WB, ib)) in enumerate(self.link_ends_host(Y, W, goal_anchor)):
+            if ia is None and ib is None:
+                continue
+            rho = float(self.link_radius[l])
+            for o, (cx, cy, cz, r) in enumerate(self.obstacles):
+                C = (cx, cy, cz)
+                t, m, d = self.link_foot_host(A, B, C)
+                if frozen_t is not None:
+                    if (l, o) not in frozen_t:
+                        continue
+                    t = frozen_t[(l, o)]
+                    m = ((1.0 - t) * A + t * B) - np.array(C)
+                    d = float(m[0] * m[0] + m[1] * m[1] + m[2] * m[2])
+                R = float(np.sqrt(r * r)) + rho      # (the template holds r^2)
+                res = R * R - d
+                if not res > 0.0 and frozen_t is None:
+                    continue
+                self.last_link_t[(l, o)] = t
+                c = -res
+                f += res * res
+                om = (1.0 - t) * WA + t * WB
+                hv = 2.0 * (2.0 * (m @ om) * m + c * om)
+                if ia is not None:
+                    G[ia] += (1.0 - t) * 2.0 * c * m
+                    H[ia] += (1.0 - t) * hv
+                if ib is not None:
+                    G[ib] += t * 2.0 * c * m
+                    H[ib] += t * hv
+        return f, G, H
 
     def sweep_points(self, q_a, q_b, samples):
         """The samples + 1 configurations of a sweep, [samples + 1, B, n]: q_s = (1 - w) q_a + w q_b with w = s / samples

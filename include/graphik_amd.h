@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define GIK_ABI_VERSION 11
+#define GIK_ABI_VERSION 12
 
 /* Residual-term kinds: one "term" per (index pair, kind) exactly as the loops of
  * costs.py:80-207 visit them: equality (omega != 0), lower hinge (psi_L != 0), upper hinge
@@ -227,7 +227,8 @@ typedef struct {
   int32_t n_cu;
   int32_t lds_bytes;           /* dynamic LDS per wavefront / workgroup of the solve kernel         */
   int32_t clique_closed_form;  /* GIK_CLIQUE_* in effect                                            */
-  int32_t anchored;
+  int32_t anchored;            /* bit 0: fixed-anchor template; bit 1: link hinges are on (gik_anchored_attach_links
+                                  with hinges = 1): 0, 1 or 3                                          */
   int32_t has_pipeline;
   int32_t prepare_is_block;    /* workgroup-per-goal prepare kernel                                 */
   int32_t node_per_lane;       /* != 0: an is_block graph solved by the node-per-lane kernel instead of the
@@ -549,6 +550,21 @@ int gik_anchored_ik_batch_seeded(const gik_template *anch, const gik_template *b
  *   radius link_radius[l] >= 0 metres.  Any row may be named, anchors and goal rows included (the last link ends at the
  *   end effector).  Refused with a message: a handle that is not a fixed-anchor template, n_link outside 0 .. 64, a row
  *   outside [0, full_N), a radius that is negative, NaN or infinite, a second attach.
+ *   hinges = 0: the links are measured only.  hinges = 1: the solve kernel also carries LINK HINGES -- per (link, sphere),
+ *   with A, B the link's ends, R = radius_o + link_radius[l] and the foot parameter t below,
+ *       m = (1 - t) A + t B - c_o;  d = m.m;  res = R^2 - d;  active <=> res > 0;  c = d - R^2
+ *       f += res^2;   G_A += (1 - t) 2 c m;   G_B += t 2 c m          (f = sum res^2, G = 1/2 grad f)
+ *       H_A += (1 - t) 2 (2 (m.w) m + c w);  H_B += t (...);   w = (1 - t) W_A + t W_B   (W of a constant end is 0)
+ *   on top of the node hinges of obs_node_mask, which stay (where t clamps to a masked end of a link of radius 0 that
+ *   node's residual is counted once more: the same zero set, a heavier weight).  The gradient is exact (the distance to a
+ *   segment is C^1; envelope theorem).  The Hessian is the frozen-t model on purpose; the trust-region ratio is taken on
+ *   the true cost, so its error costs iterations, not correctness.  The template's solve and known-answer kernels are
+ *   re-resolved to their link builds, so every call on the handle -- gik_anchored_ik_batch, _seeded, _retry,
+ *   gik_solve_batch, gik_cost / gik_grad / gik_cost_and_grad / gik_hess -- then runs them; gik_template_get_info reports
+ *   anchored = 3.  A link with two constant ends carries no hinge (it is still measured).  Refused with hinges = 1, each
+ *   with a message and before anything is uploaded: a value other than 0 or 1; a template on the 20-slot kernel variant;
+ *   more than 2 hinge links at one free node; a link whose two free ends share no term; a link end that is neither a free
+ *   node nor an anchor row.
  * gik_anchored_link_clearance: d_clearance [B] = min over (link l, obstacle o) of
  *       d = b - a;  L2 = d.d;  u = c_o - a;   t = L2 > 0 ? min(max((u.d) / L2, 0), 1) : 0;   v = u - t d
  *       |v| - radius_o - link_radius[l]
@@ -569,7 +585,7 @@ int gik_anchored_ik_batch_seeded(const gik_template *anch, const gik_template *b
  *   links, samples < 1, B (samples + 1) beyond an int, a null buffer.  B == 0 returns 0.                          */
 typedef struct {
   int32_t n_link;               /* 0 .. 64                                                        */
-  int32_t reserved0;
+  int32_t hinges;               /* 0: measure only; 1: the solve carries link hinges (see above)  */
   const int32_t *link_a;        /* [n_link] row of the full point matrix where the link starts    */
   const int32_t *link_b;        /* [n_link] ... and where it ends                                 */
   const double *link_radius;    /* [n_link] capsule radius, metres, >= 0                          */
