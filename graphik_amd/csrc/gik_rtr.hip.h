@@ -26,6 +26,36 @@ namespace gik {
 // so the structurizer never builds exec-masked loops around the reductions.
 #define UNI(cond) (__builtin_amdgcn_ballot_w64(cond) != 0ull)
 
+// The tCG step's "no exit" test on wave-uniform operands, accumulated in EXEC:
+//     (mv < mp) & (dHd > 0) & (j + 1 < maxinner) & (e < T) & (beta >= 1e-3) & !(rr <= t2hi)      (jmax_v = maxinner - 1)
+// Every operand is the same in all lanes, so each v_cmpx leaves EXEC whole or empty, and an empty EXEC stays empty:
+// the mask the last compare writes is the conjunction.  Six compares between a copy of EXEC and its restore, all
+// inside this one statement.  The compiler's rendering of the C expression is five v_cmp with five s_or_b64 chained
+// behind them, s_add / s_cmp / s_cselect for the integer test and an s_and with EXEC: eleven scalar instructions on
+// the serial path to the branch where this has four (NOTEBOOK 23).  Ordered compares are false on a NaN and
+// !(rr <= t2hi) is true on one, as in the C expression.  jmax_v must live in a vector register: a VALU instruction
+// reads one scalar operand, and that is j.
+// Hazards (LLVM's GCNHazardRecognizer, gfx940 rules): a DPP instruction needs five wait states after a VALU write of
+// EXEC.  None follows here -- the next DPP move of either caller path is a Hessian product or a reduction away -- and
+// tests/test_lone_wave_tail_isa.py measures that distance in the code object.  The scalar reads of the mask and of
+// EXEC behind the compares are interlocked by the hardware.
+__device__ inline bool plain_in_exec(double mv, double mp, double dHd, double e, double T, double beta, double rr,
+                                     double t2hi, int j, int jmax_v) {
+  unsigned long long ok, saved;
+  asm volatile("s_mov_b64 %1, exec\n\t"
+               "v_cmpx_lt_f64_e64 %0, %2, %3\n\t"
+               "v_cmpx_gt_f64_e64 %0, %4, 0\n\t"
+               "v_cmpx_gt_i32_e64 %0, %11, %10\n\t"
+               "v_cmpx_lt_f64_e64 %0, %5, %6\n\t"
+               "v_cmpx_ge_f64_e64 %0, %7, %8\n\t"
+               "v_cmpx_nle_f64_e64 %0, %9, %12\n\t"
+               "s_mov_b64 exec, %1"
+               : "=&s"(ok), "=&s"(saved)
+               : "s"(mv), "v"(mp), "s"(dHd), "v"(e), "v"(T), "v"(beta), "s"(1e-3), "v"(rr), "s"(j), "v"(jmax_v),
+                 "v"(t2hi));
+  return ok != 0ull;
+}
+
 struct RtrOut {
   double f, gradnorm;
   int iterations, inner_total, stop, n_accept;
@@ -156,6 +186,9 @@ __device__ inline void rtr_solve_one(Ctx &cx, const Params &p, const gik_trace &
   // MIG build is the one large batches run (two or three waves per SIMD, bound by the vector ALU, not by latency): it
   // keeps the one-piece product.  Same values either way.
   constexpr bool SPLIT = split_ehess<Ctx>::value && !MIG;
+  // The SPLIT builds for theta = 1 take the tCG exit test by hand (plain_in_exec).  The generic-theta ones keep the
+  // compiler's: they sit at 206 / 225 VGPRs and the vector register the hand-written test wants took the first to 207.
+  constexpr bool EXEC_TEST = SPLIT && THETA_ONE;
   const double Delta_bar = 10.0 + K;  // typicaldist (fixed_rank_psd_sym.py:71-73)
   const bool lead = cx.lead();
     double Delta = (SLICE && rs.resumed) ? rs.Delta : Delta_bar / 8.0;   // trust_region.py:134-135,164
@@ -304,6 +337,8 @@ __device__ inline void rtr_solve_one(Ctx &cx, const Params &p, const gik_trace &
         // the compiler has to assume one at the loop header it turns the first staged
         // s_waitcnt lgkmcnt(n) of every Hessian product into lgkmcnt(0).
         __builtin_amdgcn_s_waitcnt(0);
+        [[maybe_unused]] int maxinner_m1 = p.maxinner - 1;
+        if constexpr (EXEC_TEST) asm volatile("" : "+v"(maxinner_m1));   // (a vector register: see plain_in_exec)
         // One tCG iteration (:495-597).  (ec, hc, pc): current eta, Heta, <eta,eta>; (en, hn): the
         // previous eta, Heta on entry, the new ones on a plain return; pn: the new <eta,eta>.
         // Returns true when tCG ends (result in eta_l / Heta_l, or `bad`).
@@ -314,10 +349,24 @@ __device__ inline void rtr_solve_one(Ctx &cx, const Params &p, const gik_trace &
           else H = cx.ehess(delta);
           double v[8] = {cx.Q[0] * H, cx.Q[1] * H, cx.Q[2] * H,      delta * H,
                          w * H,       H * H,       ec * fma(0.5, hc, g), r * r};
-          cx.template sum_n<8>(v);
+          double Hd_Hd;
+          if constexpr (SPLIT) {
+            // |Hdelta|^2 is formed where <H, H> lives: on the still distributed sum, whose lanes 40-47 hold <H, H> and
+            // run exactly the chain below on it (the other lanes' results are never read), and only the result is read
+            // back.  With <H, H> uniform -- in scalar registers -- the first fma needs it next to v[0], a second scalar
+            // operand, which costs two v_mov_b32 in every step of the lone wavefront (NOTEBOOK 23).  Same three fmas on
+            // the same operands in the same order.
+            const double wd = wave_sum8_distributed(v);
+#pragma unroll
+            for (int q = 0; q < 8; ++q)
+              if (q != 5) v[q] = readlane_f64(wd, wave_sum8_lane(q));
+            Hd_Hd = readlane_f64(fma(-v[2], v[2], fma(-v[1], v[1], fma(-v[0], v[0], wd))), wave_sum8_lane(5));
+          } else {
+            cx.template sum_n<8>(v);
+            Hd_Hd = fma(-v[2], v[2], fma(-v[1], v[1], fma(-v[0], v[0], v[5])));
+          }
           const double Hdelta = fma(-cx.Q[2], v[2], fma(-cx.Q[1], v[1], fma(-cx.Q[0], v[0], H)));
           const double d_Hd = v[3];                // :500
-          const double Hd_Hd = fma(-v[2], v[2], fma(-v[1], v[1], fma(-v[0], v[0], v[5])));
           const double model_value = v[6];         // :551 evaluated at the current eta
           const double r_r = v[7];                 // :564 exact
           const double rho = frcp1(d_Hd);
@@ -348,12 +397,20 @@ __device__ inline void rtr_solve_one(Ctx &cx, const Params &p, const gik_trace &
           // and falls through with the same values; a NaN new_r_r still passes !(x <= t) as before.  Together with the
           // structurizer leaving uniform branches alone (build.py, UNIT_FLAGS) this takes 191 -> 185 instructions
           // out of the lone wavefront's step (NOTEBOOK 12); without that flag the same source is slower.
-          const bool rr_plain = SPLIT ? !(new_r_r <= target2_hi) : !((j >= p.mininner) & (new_r_r <= target2_hi));
-          const bool plain = (model_value < model_prev) & (d_Hd > 0.0) & (e_Pe_new < T_cur) &
-                             (beta_p >= 1e-3) & rr_plain & (j + 1 < p.maxinner);
+          // EXEC_TEST: the same conjunction from six v_cmpx and one scalar compare (plain_in_exec; NOTEBOOK 23).
+          bool leave;
+          if constexpr (EXEC_TEST) {
+            leave = !plain_in_exec(model_value, model_prev, d_Hd, e_Pe_new, T_cur, beta_p, new_r_r, target2_hi, j,
+                                   maxinner_m1);      // (already a scalar: no ballot)
+          } else {
+            const bool rr_plain = SPLIT ? !(new_r_r <= target2_hi) : !((j >= p.mininner) & (new_r_r <= target2_hi));
+            const bool plain = (model_value < model_prev) & (d_Hd > 0.0) & (e_Pe_new < T_cur) & (beta_p >= 1e-3) &
+                               rr_plain & (j + 1 < p.maxinner);
+            leave = UNI(!plain);
+          }
           double beta = beta_p;
           double rr_test = new_r_r;      // what the residual test sees (the recurrences keep the prediction)
-          if (__builtin_expect(UNI(!plain), 0)) {   // any exit, a NaN, or the accuracy guard
+          if (__builtin_expect(leave, 0)) {   // any exit, a NaN, or the accuracy guard
             if (!(d_Hd == d_Hd) || !(new_r_r == new_r_r) || !(model_value == model_value)) {
               bad = true;
               return true;

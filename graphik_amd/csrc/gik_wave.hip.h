@@ -228,12 +228,13 @@ __device__ inline double wave_sum8_distributed(double (&v)[8]) {
   w += dpp_f64<0x141>(w);  // row_half_mirror
   return w;
 }
+// first lane that holds value q of wave_sum8_distributed
+__device__ constexpr int wave_sum8_lane(int q) { return ((q & 1) ? 32 : 0) + ((q & 2) ? 16 : 0) + ((q & 4) ? 8 : 0); }
 template <>
 __device__ inline void wave_sum_n<8>(double (&v)[8]) {
   const double w = wave_sum8_distributed(v);
 #pragma unroll
-  for (int q = 0; q < 8; ++q)
-    v[q] = readlane_f64(w, ((q & 1) ? 32 : 0) + ((q & 2) ? 16 : 0) + ((q & 4) ? 8 : 0));
+  for (int q = 0; q < 8; ++q) v[q] = readlane_f64(w, wave_sum8_lane(q));
 }
 
 __device__ inline double wave_sum(double x) {
