@@ -6,7 +6,6 @@
 #include "gik_instances.h"
 #include "gik_retry.hip.h"
 #include "gik_anch_seed.hip.h"
-#include "gik_anch_retry.hip.h"
 #include "gik_order.hip.h"
 #include "gik_plan.h"
 #include "gik_slots.h"
@@ -50,6 +49,18 @@ static int fail(const std::string &m) {
     if (e_ != hipSuccess)                                                                 \
       return fail(std::string(#expr) + ": " + hipGetErrorString(e_));                     \
   } while (0)
+
+// Carves a caller-owned workspace into arrays, each padded to 8 bytes.  A null base only adds up the size.
+struct WsCarve {
+  uintptr_t base;
+  size_t off;
+  template <typename T>
+  T *take(size_t n) {
+    T *at = reinterpret_cast<T *>(base + off);
+    off += (n * sizeof(T) + 7) / 8 * 8;
+    return at;
+  }
+};
 
 typedef void (*solve_fn)(SolveArgs);
 typedef void (*kat_fn)(KatArgs);
@@ -1389,6 +1400,32 @@ int gik_ik_batch_seeded(const gik_template *t, const double *d_T_goal, const dou
 }
 
 // ---- restarts from random joint configurations (gik_retry.hip.h) --------------------------------------
+// The three launches behind gik_retry_* and gik_anchored_retry_*.  Those exports make their refusals and fill the arguments,
+// in the order of the structs; the plain ones have no clearance (null pointers: +inf, and any positive clear_tol), no centre
+// and spread 0.  t gives the grid (the anchored calls: the base template).
+static int retry_select_launch(const gik::RetrySelectArgs &a, void *stream) {
+  using namespace gik;
+  hipLaunchKernelGGL(retry_select_kernel, dim3((a.B + RETRY_WAVE - 1) / RETRY_WAVE), dim3(RETRY_WAVE), 0, (hipStream_t)stream, a);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+static int retry_grid(const gik_template *t, int count) { return std::min(count, t->f.n_cu * 8); }
+
+static int retry_seed_launch(const gik_template *t, const gik::RetrySeedArgs &a, void *stream) {
+  using namespace gik;
+  hipLaunchKernelGGL(retry_seed_kernel, dim3(retry_grid(t, a.count)), dim3(RETRY_WAVE), 0, (hipStream_t)stream, a);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+static int retry_merge_launch(const gik_template *t, const gik::RetryMergeArgs &a, void *stream) {
+  using namespace gik;
+  hipLaunchKernelGGL(retry_merge_kernel, dim3(retry_grid(t, a.count)), dim3(RETRY_WAVE), 0, (hipStream_t)stream, a);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
 int gik_retry_select(const gik_stats *d_stats, const double *d_pos_err, const double *d_rot_err, int B, double pos_tol,
                      double rot_tol, int32_t *d_idx, int32_t *d_count, void *stream) {
   using namespace gik;
@@ -1397,22 +1434,9 @@ int gik_retry_select(const gik_stats *d_stats, const double *d_pos_err, const do
   HIP_OK(hipMemsetAsync(d_count, 0, sizeof(int32_t), (hipStream_t)stream));
   if (B == 0) return 0;
   if (!d_stats || !d_pos_err || !d_rot_err) return fail("null buffer");
-  RetrySelectArgs a;
-  a.stats = d_stats;
-  a.pos_err = d_pos_err;
-  a.rot_err = d_rot_err;
-  a.pos_tol = pos_tol;
-  a.rot_tol = rot_tol;
-  a.idx = d_idx;
-  a.count = d_count;
-  a.B = B;
-  hipLaunchKernelGGL(retry_select_kernel, dim3((B + RETRY_WAVE - 1) / RETRY_WAVE), dim3(RETRY_WAVE), 0,
-                     (hipStream_t)stream, a);
-  HIP_OK(hipGetLastError());
-  return 0;
+  const RetrySelectArgs a = {d_stats, d_pos_err, d_rot_err, nullptr, {pos_tol, rot_tol, 1.0}, d_idx, d_count, B};
+  return retry_select_launch(a, stream);
 }
-
-static int retry_grid(const gik_template *t, int count) { return std::min(count, t->f.n_cu * 8); }
 
 int gik_retry_seeds(const gik_template *t, const double *d_T_goal, const int32_t *d_idx, int count, uint64_t seed,
                     int attempt, const double *d_q_lo, const double *d_q_hi, double *d_T_out, double *d_q_out,
@@ -1424,21 +1448,9 @@ int gik_retry_seeds(const gik_template *t, const double *d_T_goal, const int32_t
   if (!d_q_lo || !d_q_hi) return fail("gik_retry_seeds: null joint limits (d_q_lo / d_q_hi, [n] each, are required)");
   if (count == 0) return 0;
   if (!d_T_goal || !d_idx || !d_T_out || !d_q_out) return fail("null buffer");
-  RetrySeedArgs a;
-  a.T_goal = d_T_goal;
-  a.idx = d_idx;
-  a.q_lo = d_q_lo;
-  a.q_hi = d_q_hi;
-  a.T_out = d_T_out;
-  a.q_out = d_q_out;
-  a.seed = seed;
-  a.count = count;
-  a.pose_w = t->pc.n_ee * (t->f.K + 1) * (t->f.K + 1);
-  a.n = t->pc.n_joints;
-  a.attempt = attempt;
-  hipLaunchKernelGGL(retry_seed_kernel, dim3(retry_grid(t, count)), dim3(RETRY_WAVE), 0, (hipStream_t)stream, a);
-  HIP_OK(hipGetLastError());
-  return 0;
+  const RetrySeedArgs a = {d_T_goal, d_idx, d_q_lo, d_q_hi, nullptr, d_T_out, d_q_out, 0.0, seed,
+                           count, t->pc.n_ee * (t->f.K + 1) * (t->f.K + 1), t->pc.n_joints, attempt};
+  return retry_seed_launch(t, a, stream);
 }
 
 int gik_retry_merge(const gik_template *t, const int32_t *d_idx, int count, int attempt, double pos_tol, double rot_tol,
@@ -1452,33 +1464,16 @@ int gik_retry_merge(const gik_template *t, const int32_t *d_idx, int count, int 
   if (!d_idx || !d_Y_r || !d_stats_r || !d_q_r || !d_pos_err_r || !d_rot_err_r || !d_Y || !d_stats || !d_q ||
       !d_pos_err || !d_rot_err || !d_attempt)
     return fail("null buffer");
-  RetryMergeArgs a;
-  a.idx = d_idx;
-  a.Y_r = d_Y_r;
-  a.stats_r = d_stats_r;
-  a.q_r = d_q_r;
-  a.pos_r = d_pos_err_r;
-  a.rot_r = d_rot_err_r;
-  a.Y = d_Y;
-  a.stats = d_stats;
-  a.q = d_q;
-  a.pos_err = d_pos_err;
-  a.rot_err = d_rot_err;
-  a.attempt = d_attempt;
-  a.pos_tol = pos_tol;
-  a.rot_tol = rot_tol;
-  a.count = count;
-  a.row = t->N * t->f.K;
-  a.n = t->pc.n_joints;
-  a.attempt_no = attempt;
-  hipLaunchKernelGGL(retry_merge_kernel, dim3(retry_grid(t, count)), dim3(RETRY_WAVE), 0, (hipStream_t)stream, a);
-  HIP_OK(hipGetLastError());
-  return 0;
+  const RetryMergeArgs a = {d_idx,
+                            d_Y_r, d_stats_r, d_q_r, d_pos_err_r, d_rot_err_r, nullptr,
+                            d_Y, d_stats, d_q, d_pos_err, d_rot_err, nullptr, d_attempt,
+                            {pos_tol, rot_tol, 1.0}, count, t->N * t->f.K, t->pc.n_joints, attempt};
+  return retry_merge_launch(t, a, stream);
 }
 
+namespace gik {
 // The caller-owned workspace of gik_ik_batch_retry, every array sized for B failed goals:
 //   count (8 bytes) | idx [B] int32, padded to 8 bytes | poses | seed angles | targets | Y | stats | q | pos_err | rot_err
-namespace gik {
 struct RetryWs {
   int32_t *count, *idx;
   double *T, *q_seed, *targets, *Y, *q, *pos_err, *rot_err;
@@ -1487,26 +1482,28 @@ struct RetryWs {
 };
 static RetryWs retry_ws(const gik_template *t, int B, void *base) {
   const size_t b = (size_t)B, n = (size_t)t->pc.n_joints, pose_w = (size_t)t->pc.n_ee * (t->f.K + 1) * (t->f.K + 1);
-  const uintptr_t p = reinterpret_cast<uintptr_t>(base);      // (null: gik_retry_ws_bytes only wants the size)
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const uintptr_t at = p + off;
-    off += (bytes + 7) / 8 * 8;
-    return at;
-  };
+  WsCarve c = {reinterpret_cast<uintptr_t>(base), 0};
   RetryWs w;
-  w.count = reinterpret_cast<int32_t *>(take(8));
-  w.idx = reinterpret_cast<int32_t *>(take(b * sizeof(int32_t)));
-  w.T = reinterpret_cast<double *>(take(b * pose_w * sizeof(double)));
-  w.q_seed = reinterpret_cast<double *>(take(b * n * sizeof(double)));
-  w.targets = reinterpret_cast<double *>(take(b * (size_t)t->T * sizeof(double)));
-  w.Y = reinterpret_cast<double *>(take(b * (size_t)t->N * t->f.K * sizeof(double)));
-  w.stats = reinterpret_cast<gik_stats *>(take(b * sizeof(gik_stats)));
-  w.q = reinterpret_cast<double *>(take(b * n * sizeof(double)));
-  w.pos_err = reinterpret_cast<double *>(take(b * sizeof(double)));
-  w.rot_err = reinterpret_cast<double *>(take(b * sizeof(double)));
-  w.bytes = off;
+  w.count = c.take<int32_t>(2);
+  w.idx = c.take<int32_t>(b);
+  w.T = c.take<double>(b * pose_w);
+  w.q_seed = c.take<double>(b * n);
+  w.targets = c.take<double>(b * (size_t)t->T);
+  w.Y = c.take<double>(b * (size_t)t->N * t->f.K);
+  w.stats = c.take<gik_stats>(b);
+  w.q = c.take<double>(b * n);
+  w.pos_err = c.take<double>(b);
+  w.rot_err = c.take<double>(b);
+  w.bytes = c.off;
   return w;
+}
+
+// The solve kernels take their batch size from the host: the failed-goal count comes back, the stream drains.
+static int retry_read_count(const char *entry, const int32_t *d_count, int B, int32_t *count, hipStream_t s) {
+  HIP_OK(hipMemcpyAsync(count, d_count, sizeof(*count), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  if (*count < 0 || *count > B) return fail(std::string(entry) + ": the failed-goal count came back out of range");
+  return 0;
 }
 }  // namespace gik
 
@@ -1543,11 +1540,9 @@ int gik_ik_batch_retry(const gik_template *t, const double *d_T_goal, const doub
   for (int a = 1; a <= opts->retries; ++a) {
     rc = gik_retry_select(d_stats, d_pos_err, d_rot_err, B, opts->pos_tol, opts->rot_tol, w.idx, w.count, stream);
     if (rc) return rc;
-    // the solve kernels take their batch size from the host: the count comes back, the stream drains
     int32_t count = 0;
-    HIP_OK(hipMemcpyAsync(&count, w.count, sizeof(count), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
-    if (count < 0 || count > B) return fail("gik_ik_batch_retry: the failed-goal count came back out of range");
+    rc = retry_read_count("gik_ik_batch_retry", w.count, B, &count, s);
+    if (rc) return rc;
     if (count == 0) break;
     rc = gik_retry_seeds(t, d_T_goal, w.idx, count, opts->seed, a, opts->d_q_lo, opts->d_q_hi, w.T, w.q_seed, stream);
     if (rc) return rc;
@@ -1591,13 +1586,67 @@ static gik::AnchGlueArgs anch_glue_args(const gik_template *anch, const double *
   return g;
 }
 
+// What is wrong with the handle pair of an anchored call, or nothing: anch is a fixed-anchor template and base the robot
+// graph it was cut from, full_N nodes with its pipeline attached.  PAIR_3D: base is also 3-D; PAIR_SEEDABLE: and can be seeded
+// on the device.  Each entry names the terms it has always tested.  (Non-null handles.)
+enum { PAIR_3D = 1, PAIR_SEEDABLE = 2 };
+static std::string anchored_pair_fault(const gik_template *anch, const gik_template *base, int terms) {
+  if (!anch->anchored) return "the first handle must be a fixed-anchor template (gik_template_create_anchored)";
+  if (!base->has_pipe || ((terms & PAIR_3D) && base->f.K != 3) || base->N != anch->full_N)
+    return "the base template must be the robot graph (full_N nodes) with its pipeline attached";
+  if ((terms & PAIR_SEEDABLE) && !base->seed_ok) return "the base graph cannot be seeded on the device: " + base->seed_why;
+  return std::string();
+}
+
+static int anchored_clearance_launch(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance,
+                                     void *stream) {
+  using namespace gik;
+  AnchClearArgs c;
+  c.Y_full = d_Y_full;
+  c.obs = anch->an.obs;
+  c.node_full = anch->d_clear_full;
+  c.clearance = d_clearance;
+  c.B = B;
+  c.full_N = anch->full_N;
+  c.n_node = anch->n_clear;
+  c.n_obs = anch->an.n_obs;
+  hipLaunchKernelGGL(anch_clearance_kernel, dim3(std::min(B, anch->f.n_cu * 32)), dim3(WAVE), 0, (hipStream_t)stream, c);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// The end of the cold and the seeded anchored call: the solve from g.Y_free between the event pair of
+// gik_anchored_last_solve_ms, the gather into g.Y_full_out, the recovery and, where d_clearance is given, the node clearance.
+static int anchored_solve_tail(const gik_template *anch, const gik_template *base, const gik::AnchGlueArgs &g, gik_stats *d_stats,
+                               double *d_q, double *d_pos_err, double *d_rot_err, double *d_clearance, void *stream) {
+  using namespace gik;
+  // timing events around the solve (diagnostics only; created with the handle).  The pair is
+  // recorded under a lock so that gik_anchored_last_solve_ms never reads a half-recorded pair;
+  // with concurrent callers it reports whichever call recorded last.
+  gik_template *ma = const_cast<gik_template *>(anch);
+  {
+    std::lock_guard<std::mutex> lock(ma->ev_mutex);
+    (void)hipEventRecord(ma->ev_solve0, (hipStream_t)stream);
+  }
+  int rc = gik_solve_batch(anch, g.Y_free, g.anchor_goal, g.B, g.Y_free, d_stats, nullptr, stream);     // (not under ev_mutex:
+  if (rc) return rc;                                                                                   // other threads launch meanwhile)
+  {
+    std::lock_guard<std::mutex> lock(ma->ev_mutex);
+    (void)hipEventRecord(ma->ev_solve1, (hipStream_t)stream);
+  }
+  hipLaunchKernelGGL(anch_gather_kernel, dim3((g.B + 63) / 64), dim3(64), 0, (hipStream_t)stream, g);
+  HIP_OK(hipGetLastError());
+  rc = gik_recover_batch(base, g.Y_full_out, g.T_goal, g.B, d_q, d_pos_err, d_rot_err, stream);
+  if (rc || !d_clearance) return rc;
+  return anchored_clearance_launch(anch, g.Y_full_out, g.B, d_clearance, stream);
+}
+
 int gik_anchored_ik_batch(const gik_template *anch, const gik_template *base, const double *d_T_goal, int B,
                           double *d_ws, double *d_Y_full, gik_stats *d_stats, double *d_q,
                           double *d_pos_err, double *d_rot_err, void *stream) {
   using namespace gik;
   if (!anch || !base || !anch->anchored || B < 0) return fail("bad argument");
-  if (!base->has_pipe || base->f.K != 3 || base->N != anch->full_N)
-    return fail("the base template must be the robot graph (full_N nodes) with its pipeline attached");
+  if (const std::string why = anchored_pair_fault(anch, base, PAIR_3D); !why.empty()) return fail("gik_anchored_ik_batch: " + why);
   if (B == 0) return 0;
   if (!d_T_goal || !d_ws || !d_Y_full || !d_stats || !d_q || !d_pos_err || !d_rot_err) return fail("null buffer");
   double *tg_base = d_ws;
@@ -1611,23 +1660,7 @@ int gik_anchored_ik_batch(const gik_template *anch, const gik_template *base, co
   // ... mapped onto the world frame by its anchors; free rows = anchored start point
   hipLaunchKernelGGL(anch_init_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, g);
   HIP_OK(hipGetLastError());
-  // timing events around the solve (diagnostics only; created with the handle).  The pair is
-  // recorded under a lock so that gik_anchored_last_solve_ms never reads a half-recorded pair;
-  // with concurrent callers it reports whichever call recorded last.
-  gik_template *ma = const_cast<gik_template *>(anch);
-  {
-    std::lock_guard<std::mutex> lock(ma->ev_mutex);
-    (void)hipEventRecord(ma->ev_solve0, (hipStream_t)stream);
-  }
-  rc = gik_solve_batch(anch, Y_free, goal, B, Y_free, d_stats, nullptr, stream);     // (not under ev_mutex: other
-  if (rc) return rc;                                                                // threads launch meanwhile)
-  {
-    std::lock_guard<std::mutex> lock(ma->ev_mutex);
-    (void)hipEventRecord(ma->ev_solve1, (hipStream_t)stream);
-  }
-  hipLaunchKernelGGL(anch_gather_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, g);
-  HIP_OK(hipGetLastError());
-  return gik_recover_batch(base, d_Y_full, d_T_goal, B, d_q, d_pos_err, d_rot_err, stream);
+  return anchored_solve_tail(anch, base, g, d_stats, d_q, d_pos_err, d_rot_err, nullptr, stream);
 }
 
 // ---- the anchored solve from joint-configuration seeds (gik_anch_seed.hip.h) --------------------------
@@ -1637,10 +1670,7 @@ static int anchored_seed_refusal(const char *entry, const gik_template *anch, co
   using gik::fail;
   const std::string e(entry);
   if (!anch || !base || B < 0) return fail(e + ": bad argument");
-  if (!anch->anchored) return fail(e + ": the first handle must be a fixed-anchor template (gik_template_create_anchored)");
-  if (!base->has_pipe || base->f.K != 3 || base->N != anch->full_N)
-    return fail(e + ": the base template must be the robot graph (full_N nodes) with its pipeline attached");
-  if (!base->seed_ok) return fail(e + ": the base graph cannot be seeded on the device: " + base->seed_why);
+  if (const std::string why = anchored_pair_fault(anch, base, PAIR_3D | PAIR_SEEDABLE); !why.empty()) return fail(e + ": " + why);
   if (refuse_capture(entry, stream)) return -1;
   if (B > 0 && !d_q_init) return fail(e + ": null d_q_init (seed joint angles [B][n] are required)");
   return 0;
@@ -1668,23 +1698,6 @@ int gik_anchored_seed_batch(const gik_template *anch, const gik_template *base, 
   if (B == 0) return 0;
   if (!d_T_goal || !d_ws || !d_Y_free || !d_goal) return gik::fail("gik_anchored_seed_batch: null buffer");
   return anchored_seed_launch(anch, base, d_T_goal, d_q_init, B, d_ws, d_Y_free, d_goal, stream);
-}
-
-static int anchored_clearance_launch(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance,
-                                     void *stream) {
-  using namespace gik;
-  AnchClearArgs c;
-  c.Y_full = d_Y_full;
-  c.obs = anch->an.obs;
-  c.node_full = anch->d_clear_full;
-  c.clearance = d_clearance;
-  c.B = B;
-  c.full_N = anch->full_N;
-  c.n_node = anch->n_clear;
-  c.n_obs = anch->an.n_obs;
-  hipLaunchKernelGGL(anch_clearance_kernel, dim3(std::min(B, anch->f.n_cu * 32)), dim3(WAVE), 0, (hipStream_t)stream, c);
-  HIP_OK(hipGetLastError());
-  return 0;
 }
 
 int gik_anchored_clearance(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance, void *stream) {
@@ -1837,19 +1850,20 @@ struct AnchSweepWs {
 static AnchSweepWs anch_sweep_ws(const gik_template *anch, const gik_template *base, int B, int S, double *ws) {
   const size_t M = (size_t)B * ((size_t)S + 1), n = (size_t)base->pc.n_joints;
   const size_t pose_w = (size_t)base->pc.n_ee * (base->f.K + 1) * (base->f.K + 1);
+  WsCarve c = {reinterpret_cast<uintptr_t>(ws), 0};
   AnchSweepWs w;
-  w.q = ws;
-  w.T = w.q + M * n;
-  w.targets = w.T + M * pose_w;
-  w.Y = w.targets + M * (size_t)base->T;
-  w.cl = w.Y + M * (size_t)anch->full_N * 3;
-  w.doubles = M * (n + pose_w + (size_t)base->T + (size_t)anch->full_N * 3 + 1);
+  w.q = c.take<double>(M * n);
+  w.T = c.take<double>(M * pose_w);
+  w.targets = c.take<double>(M * (size_t)base->T);
+  w.Y = c.take<double>(M * (size_t)anch->full_N * 3);
+  w.cl = c.take<double>(M);
+  w.doubles = c.off / sizeof(double);
   return w;
 }
 }  // namespace gik
 
 size_t gik_anchored_sweep_ws_bytes(const gik_template *anch, const gik_template *base, int B, int samples) {
-  if (!anch || !base || !anch->anchored || !base->has_pipe || base->N != anch->full_N || B < 0 || samples < 1 ||
+  if (!anch || !base || !anchored_pair_fault(anch, base, 0).empty() || B < 0 || samples < 1 ||
       (size_t)B * ((size_t)samples + 1) > (size_t)INT_MAX)
     return 0;
   return gik::anch_sweep_ws(anch, base, B, samples, nullptr).doubles * sizeof(double);
@@ -1860,10 +1874,7 @@ int gik_anchored_sweep_clearance(const gik_template *anch, const gik_template *b
   using namespace gik;
   const std::string e("gik_anchored_sweep_clearance");
   if (!anch || !base || B < 0) return fail(e + ": bad argument");
-  if (!anch->anchored) return fail(e + ": the first handle must be a fixed-anchor template (gik_template_create_anchored)");
-  if (!base->has_pipe || base->f.K != 3 || base->N != anch->full_N)
-    return fail(e + ": the base template must be the robot graph (full_N nodes) with its pipeline attached");
-  if (!base->seed_ok) return fail(e + ": the base graph cannot be seeded on the device: " + base->seed_why);
+  if (const std::string why = anchored_pair_fault(anch, base, PAIR_3D | PAIR_SEEDABLE); !why.empty()) return fail(e + ": " + why);
   if (anch->n_link < 0) return fail(e + ": no links attached (gik_anchored_attach_links)");
   if (samples < 1) return fail(e + ": samples must be at least 1");
   if ((size_t)B * ((size_t)samples + 1) > (size_t)INT_MAX) return fail(e + ": B (samples + 1) must fit an int");
@@ -1916,26 +1927,11 @@ int gik_anchored_ik_batch_seeded(const gik_template *anch, const gik_template *b
   // the seed angles are read here and nowhere later: d_q_init may be d_q
   int rc = anchored_seed_launch(anch, base, d_T_goal, d_q_init, B, d_ws, Y_free, goal, stream);
   if (rc) return rc;
-  gik_template *ma = const_cast<gik_template *>(anch);      // the event pair of gik_anchored_last_solve_ms, as the cold call
-  {
-    std::lock_guard<std::mutex> lock(ma->ev_mutex);
-    (void)hipEventRecord(ma->ev_solve0, (hipStream_t)stream);
-  }
-  rc = gik_solve_batch(anch, Y_free, goal, B, Y_free, d_stats, nullptr, stream);
-  if (rc) return rc;
-  {
-    std::lock_guard<std::mutex> lock(ma->ev_mutex);
-    (void)hipEventRecord(ma->ev_solve1, (hipStream_t)stream);
-  }
-  const AnchGlueArgs g = anch_glue_args(anch, d_T_goal, B, nullptr, Y_free, goal, d_Y_full);
-  hipLaunchKernelGGL(anch_gather_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, g);
-  HIP_OK(hipGetLastError());
-  rc = gik_recover_batch(base, d_Y_full, d_T_goal, B, d_q, d_pos_err, d_rot_err, stream);
-  if (rc || !d_clearance) return rc;
-  return anchored_clearance_launch(anch, d_Y_full, B, d_clearance, stream);
+  return anchored_solve_tail(anch, base, anch_glue_args(anch, d_T_goal, B, nullptr, Y_free, goal, d_Y_full), d_stats, d_q, d_pos_err,
+                             d_rot_err, d_clearance, stream);
 }
 
-// ---- restarts in the anchored solve, with a clearance rule (gik_anch_retry.hip.h) ------------------------
+// ---- restarts in the anchored solve: the kernels of gik_retry.hip.h with a clearance in the rule -------------
 int gik_anchored_retry_select(const gik_stats *d_stats, const double *d_pos_err, const double *d_rot_err,
                               const double *d_clearance, int B, double pos_tol, double rot_tol, double clear_tol,
                               int32_t *d_idx, int32_t *d_count, void *stream) {
@@ -1945,19 +1941,8 @@ int gik_anchored_retry_select(const gik_stats *d_stats, const double *d_pos_err,
   HIP_OK(hipMemsetAsync(d_count, 0, sizeof(int32_t), (hipStream_t)stream));
   if (B == 0) return 0;
   if (!d_stats || !d_pos_err || !d_rot_err || !d_clearance) return fail("gik_anchored_retry_select: null buffer");
-  AnchRetrySelectArgs a;
-  a.stats = d_stats;
-  a.pos_err = d_pos_err;
-  a.rot_err = d_rot_err;
-  a.clearance = d_clearance;
-  a.tol = {pos_tol, rot_tol, clear_tol};
-  a.idx = d_idx;
-  a.count = d_count;
-  a.B = B;
-  hipLaunchKernelGGL(anch_retry_select_kernel, dim3((B + RETRY_WAVE - 1) / RETRY_WAVE), dim3(RETRY_WAVE), 0,
-                     (hipStream_t)stream, a);
-  HIP_OK(hipGetLastError());
-  return 0;
+  const RetrySelectArgs a = {d_stats, d_pos_err, d_rot_err, d_clearance, {pos_tol, rot_tol, clear_tol}, d_idx, d_count, B};
+  return retry_select_launch(a, stream);
 }
 
 int gik_anchored_retry_seeds(const gik_template *base, const double *d_T_goal, const int32_t *d_idx, int count,
@@ -1972,23 +1957,9 @@ int gik_anchored_retry_seeds(const gik_template *base, const double *d_T_goal, c
   if (spread > 0.0 && !d_q_center) return fail("gik_anchored_retry_seeds: spread > 0 needs the centre rows d_q_center [B][n]");
   if (count == 0) return 0;
   if (!d_T_goal || !d_idx || !d_T_out || !d_q_out) return fail("gik_anchored_retry_seeds: null buffer");
-  AnchRetrySeedArgs a;
-  a.T_goal = d_T_goal;
-  a.idx = d_idx;
-  a.q_lo = d_q_lo;
-  a.q_hi = d_q_hi;
-  a.q_center = d_q_center;
-  a.T_out = d_T_out;
-  a.q_out = d_q_out;
-  a.spread = spread;
-  a.seed = seed;
-  a.count = count;
-  a.pose_w = base->pc.n_ee * (base->f.K + 1) * (base->f.K + 1);
-  a.n = base->pc.n_joints;
-  a.attempt = attempt;
-  hipLaunchKernelGGL(anch_retry_seed_kernel, dim3(retry_grid(base, count)), dim3(RETRY_WAVE), 0, (hipStream_t)stream, a);
-  HIP_OK(hipGetLastError());
-  return 0;
+  const RetrySeedArgs a = {d_T_goal, d_idx, d_q_lo, d_q_hi, d_q_center, d_T_out, d_q_out, spread, seed,
+                           count, base->pc.n_ee * (base->f.K + 1) * (base->f.K + 1), base->pc.n_joints, attempt};
+  return retry_seed_launch(base, a, stream);
 }
 
 int gik_anchored_retry_merge(const gik_template *anch, const gik_template *base, const int32_t *d_idx, int count,
@@ -1999,36 +1970,16 @@ int gik_anchored_retry_merge(const gik_template *anch, const gik_template *base,
                              void *stream) {
   using namespace gik;
   if (!anch || !base || count < 0) return fail("gik_anchored_retry_merge: bad argument");
-  if (!anch->anchored) return fail("gik_anchored_retry_merge: the first handle must be a fixed-anchor template (gik_template_create_anchored)");
-  if (!base->has_pipe || base->N != anch->full_N)
-    return fail("gik_anchored_retry_merge: the base template must be the robot graph (full_N nodes) with its pipeline attached");
+  if (const std::string why = anchored_pair_fault(anch, base, 0); !why.empty()) return fail("gik_anchored_retry_merge: " + why);
   if (count == 0) return 0;
   if (!d_idx || !d_Y_r || !d_stats_r || !d_q_r || !d_pos_err_r || !d_rot_err_r || !d_clearance_r || !d_Y_full || !d_stats ||
       !d_q || !d_pos_err || !d_rot_err || !d_clearance || !d_attempt)
     return fail("gik_anchored_retry_merge: null buffer");
-  AnchRetryMergeArgs a;
-  a.idx = d_idx;
-  a.Y_r = d_Y_r;
-  a.stats_r = d_stats_r;
-  a.q_r = d_q_r;
-  a.pos_r = d_pos_err_r;
-  a.rot_r = d_rot_err_r;
-  a.clear_r = d_clearance_r;
-  a.Y = d_Y_full;
-  a.stats = d_stats;
-  a.q = d_q;
-  a.pos_err = d_pos_err;
-  a.rot_err = d_rot_err;
-  a.clearance = d_clearance;
-  a.attempt = d_attempt;
-  a.tol = {pos_tol, rot_tol, clear_tol};
-  a.count = count;
-  a.row = anch->full_N * 3;
-  a.n = base->pc.n_joints;
-  a.attempt_no = attempt;
-  hipLaunchKernelGGL(anch_retry_merge_kernel, dim3(retry_grid(base, count)), dim3(RETRY_WAVE), 0, (hipStream_t)stream, a);
-  HIP_OK(hipGetLastError());
-  return 0;
+  const RetryMergeArgs a = {d_idx,
+                            d_Y_r, d_stats_r, d_q_r, d_pos_err_r, d_rot_err_r, d_clearance_r,
+                            d_Y_full, d_stats, d_q, d_pos_err, d_rot_err, d_clearance, d_attempt,
+                            {pos_tol, rot_tol, clear_tol}, count, anch->full_N * 3, base->pc.n_joints, attempt};
+  return retry_merge_launch(base, a, stream);
 }
 
 // The caller-owned workspace of gik_anchored_ik_batch_retry, every array sized for B failed goals:
@@ -2045,33 +1996,27 @@ struct AnchRetryWs {
 };
 static AnchRetryWs anch_retry_ws(const gik_template *anch, const gik_template *base, int B, void *ws) {
   const size_t b = (size_t)B, n = (size_t)base->pc.n_joints, pose_w = (size_t)base->pc.n_ee * (base->f.K + 1) * (base->f.K + 1);
-  const uintptr_t p = reinterpret_cast<uintptr_t>(ws);      // (null: gik_anchored_retry_ws_bytes only wants the size)
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const uintptr_t at = p + off;
-    off += (bytes + 7) / 8 * 8;
-    return at;
-  };
+  WsCarve c = {reinterpret_cast<uintptr_t>(ws), 0};
   AnchRetryWs w;
-  w.scratch = reinterpret_cast<double *>(take(gik_anchored_ws_doubles(anch, base, B) * sizeof(double)));
-  w.count = reinterpret_cast<int32_t *>(take(8));
-  w.idx = reinterpret_cast<int32_t *>(take(b * sizeof(int32_t)));
-  w.T = reinterpret_cast<double *>(take(b * pose_w * sizeof(double)));
-  w.q_seed = reinterpret_cast<double *>(take(b * n * sizeof(double)));
-  w.q_center = reinterpret_cast<double *>(take(b * n * sizeof(double)));
-  w.Y = reinterpret_cast<double *>(take(b * (size_t)anch->full_N * 3 * sizeof(double)));
-  w.stats = reinterpret_cast<gik_stats *>(take(b * sizeof(gik_stats)));
-  w.q = reinterpret_cast<double *>(take(b * n * sizeof(double)));
-  w.pos_err = reinterpret_cast<double *>(take(b * sizeof(double)));
-  w.rot_err = reinterpret_cast<double *>(take(b * sizeof(double)));
-  w.clearance = reinterpret_cast<double *>(take(b * sizeof(double)));
-  w.bytes = off;
+  w.scratch = c.take<double>(gik_anchored_ws_doubles(anch, base, B));
+  w.count = c.take<int32_t>(2);
+  w.idx = c.take<int32_t>(b);
+  w.T = c.take<double>(b * pose_w);
+  w.q_seed = c.take<double>(b * n);
+  w.q_center = c.take<double>(b * n);
+  w.Y = c.take<double>(b * (size_t)anch->full_N * 3);
+  w.stats = c.take<gik_stats>(b);
+  w.q = c.take<double>(b * n);
+  w.pos_err = c.take<double>(b);
+  w.rot_err = c.take<double>(b);
+  w.clearance = c.take<double>(b);
+  w.bytes = c.off;
   return w;
 }
 }  // namespace gik
 
 size_t gik_anchored_retry_ws_bytes(const gik_template *anch, const gik_template *base, int B) {
-  if (!anch || !base || !anch->anchored || !base->has_pipe || base->N != anch->full_N || B < 0) return 0;
+  if (!anch || !base || !anchored_pair_fault(anch, base, 0).empty() || B < 0) return 0;
   return gik::anch_retry_ws(anch, base, B, nullptr).bytes;
 }
 
@@ -2083,9 +2028,7 @@ int gik_anchored_ik_batch_retry(const gik_template *anch, const gik_template *ba
   const std::string e("gik_anchored_ik_batch_retry");
   // every refusal comes before anything is queued
   if (!anch || !base || B < 0 || !opts) return fail(e + ": bad argument");
-  if (!anch->anchored) return fail(e + ": the first handle must be a fixed-anchor template (gik_template_create_anchored)");
-  if (!base->has_pipe || base->f.K != 3 || base->N != anch->full_N)
-    return fail(e + ": the base template must be the robot graph (full_N nodes) with its pipeline attached");
+  if (const std::string why = anchored_pair_fault(anch, base, PAIR_3D); !why.empty()) return fail(e + ": " + why);
   if (opts->retries < 0 || opts->retries > 63) return fail(e + ": retries must be within 0 .. 63");
   if (opts->clearance_mode != GIK_CLEARANCE_NODES && opts->clearance_mode != GIK_CLEARANCE_LINKS)
     return fail(e + ": clearance_mode must be GIK_CLEARANCE_NODES (0) or GIK_CLEARANCE_LINKS (1)");
@@ -2130,11 +2073,9 @@ int gik_anchored_ik_batch_retry(const gik_template *anch, const gik_template *ba
     rc = gik_anchored_retry_select(d_stats, d_pos_err, d_rot_err, d_clearance, B, opts->pos_tol, opts->rot_tol,
                                    opts->clear_tol, w.idx, w.count, stream);
     if (rc) return rc;
-    // the solve kernels take their batch size from the host: the count comes back, the stream drains
     int32_t count = 0;
-    HIP_OK(hipMemcpyAsync(&count, w.count, sizeof(count), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
-    if (count < 0 || count > B) return fail(e + ": the failed-goal count came back out of range");
+    rc = retry_read_count("gik_anchored_ik_batch_retry", w.count, B, &count, s);
+    if (rc) return rc;
     if (count == 0) break;
     rc = gik_anchored_retry_seeds(base, d_T_goal, w.idx, count, opts->seed, a, opts->d_q_lo, opts->d_q_hi,
                                   local ? w.q_center : nullptr, local ? opts->spread : 0.0, w.T, w.q_seed, stream);

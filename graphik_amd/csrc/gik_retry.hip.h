@@ -1,13 +1,20 @@
-// graphik_amd/csrc/gik_retry.hip.h -- restarts from random joint configurations, the device side.
+// graphik_amd/csrc/gik_retry.hip.h -- restarts from random joint configurations, the device side: the plain solve and
+// the fixed-anchor (obstacle) solve share one rule, one seed formula and one set of kernels.
 //
 //   retry_select_kernel : one thread per goal: failed goals -> a compact index list (wave ballot, one atomic
 //                         per wavefront; the order of the list is whatever the atomics make it).
-//   retry_seed_kernel   : one wavefront per compact slot: the goal's pose rows and n joint angles drawn
-//                         uniformly inside the joint limits by a counter-based generator -- a function of
-//                         (seed, goal, attempt, joint) only, mirrored bit for bit by
+//   retry_seed_kernel   : one wavefront per compact slot: the goal's pose rows and n joint angles drawn by a
+//                         counter-based generator -- a function of (seed, goal, attempt, joint) only.  spread == 0:
+//                         uniformly inside the joint limits.  spread > 0: q = clamp(c + spread (2u - 1), lo, hi) around
+//                         the centre row of the GOAL (not of the slot), same u.  Mirrored bit for bit by
 //                         graphik_amd.solvers.riemannian_solver.retry_seeds_host.
-//   retry_merge_kernel  : one wavefront per compact slot: the retry's answer replaces the goal's incumbent
-//                         if and only if it is better; rows that are not replaced are not written.
+//   retry_merge_kernel  : one wavefront per compact slot: the retry's answer -- point row, stats, q, both errors and,
+//                         where there is one, the clearance -- replaces the goal's incumbent if and only if it is
+//                         better; rows that are not replaced are not written.
+// The anchored solve adds the answer's clearance to the rule (an answer that sits on its goal with a joint point -- or,
+// where the caller hands in the link clearance, any part of a link -- inside a sphere has failed).  The plain solve has
+// no clearance: its kernels get null clearance pointers, which read as +inf, and +inf drops out of the rule.
+// The rule and the seed formula are __host__ __device__ functions, so that a host program can walk them.
 // Plain kernels, defined where GIK_DEFINE_RETRY_KERNELS is set (gik_k_retry.hip); gik_host.hip sees prototypes.
 #pragma once
 
@@ -20,24 +27,63 @@ namespace gik {
 
 constexpr int RETRY_WAVE = 64;
 
-// failed: the solver did not stop on its gradient bar, or an end-effector error is not within its tolerance
-// (written so that a NaN error counts as failed)
-__host__ __device__ inline bool retry_failed(int stop, double pos_err, double rot_err, double pos_tol, double rot_tol) {
-  return stop != 0 || !(pos_err <= pos_tol) || !(rot_err <= rot_tol);
+struct RetryTol {
+  double pos_tol, rot_tol, clear_tol;
+};
+
+// failed: the solver did not stop on its gradient bar, an end-effector error is not within its tolerance, or the answer is
+// deeper than clear_tol inside a sphere (a masked node, or a link: whichever clearance the array holds)
+// (written so that a NaN error or clearance counts as failed; +inf -- no obstacle, no masked node, no clearance at all --
+// never fails a goal)
+__host__ __device__ inline bool retry_failed(int stop, double pos_err, double rot_err, double clearance, RetryTol t) {
+  return stop != 0 || !(pos_err <= t.pos_tol) || !(rot_err <= t.rot_tol) || !(clearance >= -t.clear_tol);
 }
 
-// what the merge orders answers of one success class by; a NaN error scores +inf, so it never wins
-__host__ __device__ inline double retry_score(double pos_err, double rot_err, double pos_tol, double rot_tol) {
-  const double a = pos_err / pos_tol, b = rot_err / rot_tol;
-  if (a != a || b != b) return __builtin_huge_val();
-  return a > b ? a : b;
+// what the merge orders answers of one success class by: the larger of the pose errors in units of their tolerances and
+// the penetration depth in units of clear_tol; a NaN scores +inf, so it never wins.  clearance = +inf: the depth is 0 and
+// the score is max(pos_err / pos_tol, rot_err / rot_tol), for every pair of errors that is non-negative, +inf or NaN --
+// they are norms written by recover_kernel, so nothing else occurs.
+__host__ __device__ inline double retry_score(double pos_err, double rot_err, double clearance, RetryTol t) {
+  if (clearance != clearance) return __builtin_huge_val();
+  const double a = pos_err / t.pos_tol, b = rot_err / t.rot_tol;
+  const double s = a != a || b != b ? __builtin_huge_val() : a > b ? a : b;
+  const double depth = (clearance < 0.0 ? -clearance : 0.0) / t.clear_tol;
+  return s > depth ? s : depth;
+}
+
+// does the restart's answer (_r) replace the incumbent (_i)?  A success beats a failure; within one class the smaller
+// score wins and a tie keeps the incumbent.
+__host__ __device__ inline bool retry_better(int stop_r, double pos_r, double rot_r, double clear_r, int stop_i, double pos_i,
+                                             double rot_i, double clear_i, RetryTol t) {
+  const bool ok_r = !retry_failed(stop_r, pos_r, rot_r, clear_r, t);
+  const bool ok_i = !retry_failed(stop_i, pos_i, rot_i, clear_i, t);
+  return (ok_r && !ok_i) || (ok_r == ok_i && retry_score(pos_r, rot_r, clear_r, t) < retry_score(pos_i, rot_i, clear_i, t));
+}
+
+// one seed angle.  u = retry_uniform(seed, goal, attempt, joint).  spread == 0: lo + u (hi - lo), one rounded product and
+// one rounded sum, as numpy forms it.  spread > 0: t = 2u - 1 is exact (u is a 53-bit fraction), then one rounded product
+// and one rounded sum, clamped to the limits; a NaN centre passes both comparisons and comes out as NaN.
+__host__ __device__ inline double retry_seed_value(double u, double lo, double hi, double center, double spread) {
+#pragma clang fp contract(off)
+  if (!(spread > 0.0)) {
+    const double span = hi - lo;
+    const double step = u * span;
+    return lo + step;
+  }
+  const double t = 2.0 * u - 1.0;
+  const double step = spread * t;
+  double q = center + step;
+  q = q < lo ? lo : q;
+  q = q > hi ? hi : q;
+  return q;
 }
 
 struct RetrySelectArgs {
   const gik_stats *stats;   // [B]
   const double *pos_err;    // [B]
   const double *rot_err;    // [B]
-  double pos_tol, rot_tol;
+  const double *clearance;  // [B], or null: +inf
+  RetryTol tol;
   int *idx;                 // [B] out: the failed goals, compact
   int *count;               // [1] in: 0, out: how many
   int B;
@@ -47,8 +93,10 @@ struct RetrySeedArgs {
   const double *T_goal;     // [B][pose_w]  pose_w = n_ee (K+1)^2
   const int *idx;           // [count]
   const double *q_lo, *q_hi;   // [n]
+  const double *q_center;   // [B][n], indexed by goal; read only if spread > 0
   double *T_out;            // [count][pose_w]
   double *q_out;            // [count][n]
+  double spread;
   uint64_t seed;
   int count, pose_w, n, attempt;
 };
@@ -56,17 +104,19 @@ struct RetrySeedArgs {
 struct RetryMergeArgs {
   const int *idx;           // [count] distinct goals
   // the retry's answers, compact
-  const double *Y_r;        // [count][row]  row = N K
+  const double *Y_r;        // [count][row]  row = N K (anchored: full_N 3)
   const gik_stats *stats_r; // [count]
   const double *q_r;        // [count][n]
   const double *pos_r, *rot_r;   // [count]
+  const double *clear_r;    // [count], or null: +inf
   // the incumbents
   double *Y;                // [B][row]
   gik_stats *stats;         // [B]
   double *q;                // [B][n]
   double *pos_err, *rot_err;     // [B]
+  double *clearance;        // [B], or null: +inf, and never stored
   int *attempt;             // [B]
-  double pos_tol, rot_tol;
+  RetryTol tol;
   int count, row, n, attempt_no;
 };
 
@@ -89,7 +139,8 @@ __global__ void __launch_bounds__(RETRY_WAVE) retry_select_kernel(RetrySelectArg
 {
   const int b = blockIdx.x * RETRY_WAVE + threadIdx.x, lane = threadIdx.x;
   bool failed = false;
-  if (b < a.B) failed = retry_failed(a.stats[b].stop, a.pos_err[b], a.rot_err[b], a.pos_tol, a.rot_tol);
+  if (b < a.B)
+    failed = retry_failed(a.stats[b].stop, a.pos_err[b], a.rot_err[b], a.clearance ? a.clearance[b] : __builtin_huge_val(), a.tol);
   const unsigned long long mask = __ballot(failed);
   if (mask == 0) return;
   int base = 0;
@@ -104,8 +155,8 @@ __global__ void __launch_bounds__(RETRY_WAVE) retry_seed_kernel(RetrySeedArgs a)
     ;
 #else
 {
-#pragma clang fp contract(off)      // q = lo + u (hi - lo): one rounded product, one rounded sum, as numpy forms it
   const int lane = threadIdx.x;
+  const bool local = a.spread > 0.0;
   for (int r = blockIdx.x; r < a.count; r += gridDim.x) {
     const int g = a.idx[r];
     const double *src = a.T_goal + (size_t)g * a.pose_w;
@@ -113,9 +164,8 @@ __global__ void __launch_bounds__(RETRY_WAVE) retry_seed_kernel(RetrySeedArgs a)
     for (int e = lane; e < a.pose_w; e += RETRY_WAVE) dst[e] = src[e];
     for (int j = lane; j < a.n; j += RETRY_WAVE) {
       const double u = retry_uniform(a.seed, (uint64_t)g, a.attempt, j);
-      const double lo = a.q_lo[j], span = a.q_hi[j] - lo;
-      const double step = u * span;
-      a.q_out[(size_t)r * a.n + j] = lo + step;
+      const double c = local ? a.q_center[(size_t)g * a.n + j] : 0.0;
+      a.q_out[(size_t)r * a.n + j] = retry_seed_value(u, a.q_lo[j], a.q_hi[j], c, a.spread);
     }
   }
 }
@@ -130,11 +180,9 @@ __global__ void __launch_bounds__(RETRY_WAVE) retry_merge_kernel(RetryMergeArgs 
   for (int r = blockIdx.x; r < a.count; r += gridDim.x) {
     const int g = a.idx[r];
     // every lane takes the same decision from the same loads
-    const double pn = a.pos_r[r], rn = a.rot_r[r], po = a.pos_err[g], ro = a.rot_err[g];
-    const bool ok_new = !retry_failed(a.stats_r[r].stop, pn, rn, a.pos_tol, a.rot_tol);
-    const bool ok_old = !retry_failed(a.stats[g].stop, po, ro, a.pos_tol, a.rot_tol);
-    const bool better = (ok_new && !ok_old) ||
-                        (ok_new == ok_old && retry_score(pn, rn, a.pos_tol, a.rot_tol) < retry_score(po, ro, a.pos_tol, a.rot_tol));
+    const double pn = a.pos_r[r], rn = a.rot_r[r], cn = a.clear_r ? a.clear_r[r] : __builtin_huge_val();
+    const bool better = retry_better(a.stats_r[r].stop, pn, rn, cn, a.stats[g].stop, a.pos_err[g], a.rot_err[g],
+                                     a.clearance ? a.clearance[g] : __builtin_huge_val(), a.tol);
     __syncthreads();      // (the incumbent is read by all lanes before any lane overwrites it)
     if (!better) continue;
     const double *Ys = a.Y_r + (size_t)r * a.row;
@@ -149,6 +197,7 @@ __global__ void __launch_bounds__(RETRY_WAVE) retry_merge_kernel(RetryMergeArgs 
     if (lane == 0) {
       a.pos_err[g] = pn;
       a.rot_err[g] = rn;
+      if (a.clearance) a.clearance[g] = cn;
       a.attempt[g] = a.attempt_no;
     }
   }

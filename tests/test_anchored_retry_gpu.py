@@ -14,7 +14,8 @@ from test_anchored_seeded_gpu import _scene
 from test_anchored_seeded_host import collision_input, tracking_input
 from test_anchored_retry_host import TWIN_MAXITER, TWIN_SEED
 from test_retry_gpu import _failed as plain_failed
-from test_retry_gpu import _hip_runtime, _select_patterns, _stats_buffer
+from test_retry_gpu import _better as plain_better
+from test_retry_gpu import _hip_runtime, _merge_cases, _select_patterns, _stats_buffer
 
 pytestmark = pytest.mark.gpu
 
@@ -292,6 +293,112 @@ def test_merge_keeps_the_better_answer(torch_cuda):
         for B1, g in ((1, 0), (67, 66), (67, 0)):
             host, retry, got = _run_merge(torch, ap, one(old), one(new), B1, np.array([g], dtype=np.int32), rng, attempt_no=63)
             _check_merge(host, retry, got, [g], take[k:k + 1], attempt_no=63)
+
+
+# ---- 3b. one kernel set: with no clearance in sight the anchored entries are the plain ones ---------------------------
+@pytest.mark.parametrize("B", SIZES)
+def test_plain_and_anchored_entries_agree(torch_cuda, B):
+    """gik_retry_select / _seeds / _merge and their gik_anchored_* twins on the same inputs, every clearance +inf, spread 0
+    and no centre: the same failed goals, the same seeds and the same merged batch, bit for bit.  The base template is
+    3-D, so its row N K is the anchored row full_N 3 and the same buffers serve both calls."""
+    torch = torch_cuda
+    lib, _ffi = _lib()
+    robot, graph, ap = _problem()
+    tpl, base = ap.template, ap.base.template
+    row, n, pose_w = tpl.full_N * 3, base.n_joints, base.n_ee * 16
+    assert base.N * base.k == row
+    st = _stream(torch)
+    rng = np.random.RandomState(300 + B)
+    inf_B = torch.full((B,), np.inf, dtype=torch.float64, device="cuda")
+
+    # select: equal counts and equal index sets (the order of the list is unspecified)
+    for name, (stop, pos, rot) in _select_patterns(B).items():
+        assert not np.any(pos < 0) and not np.any(rot < 0)
+        stats = torch.from_numpy(_stats_buffer(torch, stop)).cuda()
+        d_pos, d_rot = torch.from_numpy(pos).cuda(), torch.from_numpy(rot).cuda()
+        idx = torch.full((2, B + 2), -7, dtype=torch.int32, device="cuda")        # a guard entry on either side
+        cnt = torch.tensor([[-7, 12345, -7]] * 2, dtype=torch.int32, device="cuda")
+        _ffi.check(lib.gik_retry_select(stats.data_ptr(), d_pos.data_ptr(), d_rot.data_ptr(), B, POS_TOL, ROT_TOL,
+                                        idx[0].data_ptr() + 4, cnt[0].data_ptr() + 4, st))
+        _ffi.check(lib.gik_anchored_retry_select(stats.data_ptr(), d_pos.data_ptr(), d_rot.data_ptr(), inf_B.data_ptr(), B,
+                                                 POS_TOL, ROT_TOL, CLEAR_TOL, idx[1].data_ptr() + 4, cnt[1].data_ptr() + 4, st))
+        torch.cuda.synchronize()
+        idx, cnt = idx.cpu().numpy(), cnt.cpu().numpy()
+        k = int(cnt[0, 1])
+        assert cnt[0].tolist() == cnt[1].tolist() == [-7, k, -7] and 0 <= k <= B, name
+        assert k == int(plain_failed(stop, pos, rot).sum()), name
+        assert np.array_equal(np.sort(idx[0, 1:1 + k]), np.sort(idx[1, 1:1 + k])), name
+        assert np.all(idx[:, 1 + k:] == -7) and np.all(idx[:, 0] == -7), name
+
+    count = B if B < 64 else B - 3                   # a shuffled subset: slots and goals differ
+    goals = rng.permutation(B)[:count].astype(np.int32)
+    d_goals = torch.from_numpy(goals).cuda()
+
+    # seeds: pose rows and angles bit-identical
+    lo, hi = robot.limits_arrays()
+    d_T = torch.from_numpy(rng.standard_normal((B, pose_w))).cuda()
+    d_lo, d_hi = torch.from_numpy(lo).cuda(), torch.from_numpy(hi).cuda()
+    T_out = torch.full((2, count + 2, pose_w), -7.0, dtype=torch.float64, device="cuda")
+    q_out = torch.full((2, count + 2, n), -7.0, dtype=torch.float64, device="cuda")
+    seed, attempt = 0xDEADBEEFCAFEF00D, 1 + B % 63
+    _ffi.check(lib.gik_retry_seeds(base._h, d_T.data_ptr(), d_goals.data_ptr(), count, seed, attempt, d_lo.data_ptr(),
+                                   d_hi.data_ptr(), T_out[0].data_ptr() + 8 * pose_w, q_out[0].data_ptr() + 8 * n, st))
+    _ffi.check(lib.gik_anchored_retry_seeds(base._h, d_T.data_ptr(), d_goals.data_ptr(), count, seed, attempt, d_lo.data_ptr(),
+                                            d_hi.data_ptr(), None, 0.0, T_out[1].data_ptr() + 8 * pose_w,
+                                            q_out[1].data_ptr() + 8 * n, st))
+    torch.cuda.synchronize()
+    for buf in (T_out.cpu().numpy(), q_out.cpu().numpy()):
+        assert np.array_equal(_bits(buf[0]), _bits(buf[1]))
+        assert np.all(buf[:, 0] == -7.0) and np.all(buf[:, -1] == -7.0) and not np.any(buf[:, 1:-1] == -7.0)
+
+    # merge: the drawn cells of the plain tests (NaN errors among them), no error negative
+    old, new = _merge_cases(count, seed=B)
+    assert all(not np.any(a < 0) for a in old[1:] + new[1:]) and (count == 1 or np.isnan(new[1]).any())
+    inc_stop = rng.choice([0, 1], B).astype(np.int32)
+    inc_pos, inc_rot = rng.uniform(0, 0.02, B), rng.uniform(0, 0.02, B)
+    inc_stop[goals], inc_pos[goals], inc_rot[goals] = old
+
+    def guarded(a):
+        g = np.full((1,) + a.shape[1:], -7, dtype=a.dtype)
+        return np.concatenate([g, a, g])
+
+    host = {"Y": guarded(rng.standard_normal((B, row))), "stats": guarded(_stats_buffer(torch, inc_stop, rng)),
+            "q": guarded(rng.standard_normal((B, n))), "pos": guarded(inc_pos), "rot": guarded(inc_rot),
+            "attempt": guarded(rng.randint(0, 3, B).astype(np.int32)), "clr": guarded(np.full(B, np.inf))}
+    retry = {"Y": rng.standard_normal((count, row)), "stats": _stats_buffer(torch, new[0], rng),
+             "q": rng.standard_normal((count, n)), "pos": new[1].copy(), "rot": new[2].copy(), "clr": np.full(count, np.inf)}
+    dre = {k: torch.from_numpy(v).cuda() for k, v in retry.items()}
+    plain = {k: torch.from_numpy(v).cuda() for k, v in host.items()}
+    anch = {k: torch.from_numpy(v).cuda() for k, v in host.items()}
+
+    def ptr(t):      # past the guard row
+        return t.data_ptr() + t.element_size() * (t.numel() // t.shape[0])
+
+    ATTEMPT = 5
+    _ffi.check(lib.gik_retry_merge(base._h, d_goals.data_ptr(), count, ATTEMPT, POS_TOL, ROT_TOL, dre["Y"].data_ptr(),
+                                   dre["stats"].data_ptr(), dre["q"].data_ptr(), dre["pos"].data_ptr(), dre["rot"].data_ptr(),
+                                   ptr(plain["Y"]), ptr(plain["stats"]), ptr(plain["q"]), ptr(plain["pos"]), ptr(plain["rot"]),
+                                   ptr(plain["attempt"]), st))
+    _ffi.check(lib.gik_anchored_retry_merge(tpl._h, base._h, d_goals.data_ptr(), count, ATTEMPT, POS_TOL, ROT_TOL, CLEAR_TOL,
+                                            dre["Y"].data_ptr(), dre["stats"].data_ptr(), dre["q"].data_ptr(),
+                                            dre["pos"].data_ptr(), dre["rot"].data_ptr(), dre["clr"].data_ptr(), ptr(anch["Y"]),
+                                            ptr(anch["stats"]), ptr(anch["q"]), ptr(anch["pos"]), ptr(anch["rot"]),
+                                            ptr(anch["clr"]), ptr(anch["attempt"]), st))
+    torch.cuda.synchronize()
+    take = plain_better(new, old)
+    want_attempt = host["attempt"].copy()
+    want_attempt[1 + goals[take]] = ATTEMPT
+    for k in host:
+        a = anch[k].cpu().numpy()
+        bits = np.int64 if a.dtype == np.float64 else np.int32
+        assert np.array_equal(a[[0, -1]].view(bits), host[k][[0, -1]].view(bits)), k      # the guard rows
+        if k == "clr":
+            assert np.array_equal(a, host[k])      # +inf everywhere still; the plain call has no such array
+            continue
+        p = plain[k].cpu().numpy()
+        assert np.array_equal(p.view(bits), a.view(bits)), k
+        if k == "attempt":
+            assert np.array_equal(p, want_attempt)
 
 
 # ---- 4-7. end to end -----------------------------------------------------------------------------------------

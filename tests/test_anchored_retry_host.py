@@ -199,9 +199,11 @@ def test_abi_carries_the_anchored_retry_entry_points():
 
 # ---- 4. the header's helpers in a program of their own, under the sanitizers -----------------------------------
 def test_header_helpers_walked_by_a_sanitized_host_program(tmp_path):
-    """tests/host/anch_retry_walk.cpp: host-only compile of gik_anch_retry.hip.h (no device code, nothing loaded into
+    """tests/host/anch_retry_walk.cpp: host-only compile of gik_retry.hip.h (no device code, nothing loaded into
     this interpreter), -fsanitize=address,undefined, run as a program.  It walks select / seed / merge over 389 random
-    slots on exactly sized heap arrays and prints the pinned local-mode value, which must be the mirror's."""
+    slots on exactly sized heap arrays and prints the pinned local-mode value, which must be the mirror's; then it holds
+    the helpers at clearance = +inf to the plain rule on every (stop, pos_err, rot_err) cell, restart answer x incumbent:
+    (5 * 6 * 6)^2 cells."""
     import shutil
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     assert os.path.exists(hipcc), "the HIP toolchain builds this project; it is needed here too"
@@ -219,6 +221,7 @@ def test_header_helpers_walked_by_a_sanitized_host_program(tmp_path):
     lines = r.stdout.strip().splitlines()
     assert lines[0].startswith("ok slots 389 ") and "FAILED" not in r.stdout
     assert lines[1].split() == ["pinned", "u", PINNED_U, "local", PINNED_LOCAL, "clipped", PINNED_CLIPPED]
+    assert lines[2] == "plain cells %d" % (5 * 6 * 6) ** 2
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
 
 
