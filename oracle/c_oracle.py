@@ -262,10 +262,11 @@ def rtr_solve_batch(Y_init, D_goal, omega, psi_L, psi_U, use_limits=True, nthrea
 
 
 def rtr_solve_anchored(Y_init, D_ff, omega_ff, psi_L_ff, psi_U_ff, at_node, at_pos, at_target, at_kind,
-                       traj_cap=0, **kw):
+                       traj_cap=0, fast=False, **kw):
     """Trust-region solve of the fixed-anchor formulation (gik_o_rtr_solve_anchored): Y_init
     [Nf,3] free nodes, dense free-free matrices, point-to-anchor terms (node, position, squared
-    target, kind)."""
+    target, kind).  fast: the -O3 / FMA build of the same source, a second rendering of the same
+    algorithm that differs in rounding only."""
     Y = _c(Y_init).copy()
     N, k = Y.shape
     omega, psi_L, psi_U = _c(omega_ff), _c(psi_L_ff), _c(psi_U_ff)
@@ -287,8 +288,8 @@ def rtr_solve_anchored(Y_init, D_ff, omega_ff, psi_L_ff, psi_U_ff, at_node, at_p
                              ("gradnorm_after", C.c_double, np.float64), ("accept", C.c_int, np.int32)):
             keep[name] = np.zeros(traj_cap, dtype=dt)
             setattr(tr, name, keep[name].ctypes.data_as(C.POINTER(ct)))
-    rc = lib().gik_o_rtr_solve_anchored(Y, _c(D_ff), omega, psi_L, psi_U, ii, jj, len(ii), N, k, C.byref(at),
-                                        C.byref(p), C.byref(res), C.byref(tr) if tr else None)
+    rc = lib(fast=fast).gik_o_rtr_solve_anchored(Y, _c(D_ff), omega, psi_L, psi_U, ii, jj, len(ii), N, k, C.byref(at),
+                                                 C.byref(p), C.byref(res), C.byref(tr) if tr else None)
     assert rc == 0
     info = {"x": Y, "f(x)": res.f, "gradnorm": res.gradnorm, "iterations": res.iterations,
             "inner_total": res.inner_total, "stop": res.stop}

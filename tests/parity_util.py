@@ -84,10 +84,11 @@ def anchored_terms(ap, goal_anchor):
     return np.array(node, dtype=np.int32), np.array(pos), np.array(tgt), np.array(kind, dtype=np.int32)
 
 
-def anchored_numpy(ap, Nf, Y, W, goal_anchor):
+def anchored_numpy_terms(free_terms, anchor_terms, Y, W):
     """Plain fp64 reference of the anchored cost, egrad (= 1/2 grad f, costs.py convention) and
-    ehess: free-free terms + point-to-anchor terms."""
-    ti, tj, tk, target = ap.free_terms
+    ehess from explicit term lists: free-free (i, j, kind, target) and point-to-anchor
+    (node, position, squared target, kind)."""
+    ti, tj, tk, target = free_terms
     f, G, H = 0.0, np.zeros_like(Y), np.zeros_like(Y)
 
     def term(yi, wi, yj, wj, tgt, kind):
@@ -102,8 +103,13 @@ def anchored_numpy(ap, Nf, Y, W, goal_anchor):
     for i, j, k_, t in zip(ti, tj, tk, target):
         df, dg, dh = term(Y[i], W[i], Y[j], W[j], t, k_)
         f += df; G[i] += dg; G[j] -= dg; H[i] += dh; H[j] -= dh
-    node, pos, tgt, kind = anchored_terms(ap, goal_anchor)
+    node, pos, tgt, kind = anchor_terms
     for i, a, t, k_ in zip(node, pos, tgt, kind):
         df, dg, dh = term(Y[i], W[i], a, 0 * a, t, k_)
         f += df; G[i] += dg; H[i] += dh
     return f, G, H
+
+
+def anchored_numpy(ap, Nf, Y, W, goal_anchor):
+    """anchored_numpy_terms on the term lists of an AnchoredProblem and one problem's goal anchors."""
+    return anchored_numpy_terms(ap.free_terms, anchored_terms(ap, goal_anchor), Y, W)
