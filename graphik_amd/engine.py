@@ -70,6 +70,16 @@ def _decode_stats(stats):
     return out
 
 
+def _result(out, x_shape, extras=()):
+    """What Template.ik / anchored_ik return, from the buffers `out` the call wrote: "x" (the point matrices "Y" as
+    x_shape = [B, rows, k]), "q", "pos_err", "rot_err", the call's extras (clearance, attempt, keep-alive entries) and
+    the decoded stats."""
+    res = {"x": out["Y"].reshape(x_shape), "q": out["q"], "pos_err": out["pos_err"], "rot_err": out["rot_err"]}
+    res.update(extras)
+    res.update(_decode_stats(out["stats"]))
+    return res
+
+
 RETRY_MAX = 63          # attempts share 6 bits of the seed generator's counter (include/graphik_amd.h)
 RETRY_MAX_JOINTS = 125
 
@@ -484,52 +494,48 @@ class Template:
         T, B = self._poses(T_goal)
         if out is None:
             out = self.alloc_ik_buffers(B)
+        q0 = None if q_init is None else self._seed_angles(q_init, B)
+        answer = [out[key].data_ptr() for key in ("targets", "Y", "stats", "q", "pos_err", "rot_err")]
+        extras = {}
         with torch.cuda.device(self.device):
             if retries:
-                q0 = None if q_init is None else self._seed_angles(q_init, B)
-                attempt = out.get("attempt")
-                if attempt is None:
-                    attempt = torch.empty(B, dtype=torch.int32, device=self.device)
-                ws = out.get("retry_ws")
-                nbytes = int(self.lib.gik_retry_ws_bytes(self._h, B))
-                if ws is None or ws.numel() * ws.element_size() < nbytes:
-                    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=self.device)
-                q_lo = out["q_lo"] if "q_lo" in out else _dev(lo, self.device)
-                q_hi = out["q_hi"] if "q_hi" in out else _dev(hi, self.device)
+                attempt, ws, q_lo, q_hi = self._retry_buffers(out, B, int(self.lib.gik_retry_ws_bytes(self._h, B)), lo, hi)
                 opts = _ffi.RetryOpts(retries=retries, seed=int(retry_seed) & (2 ** 64 - 1), pos_tol=float(pos_tol),
                                       rot_tol=float(rot_tol), d_q_lo=q_lo.data_ptr(), d_q_hi=q_hi.data_ptr())
                 _ffi.check(self.lib.gik_ik_batch_retry(self._h, T.data_ptr(), None if q0 is None else q0.data_ptr(), B,
-                                                       C.byref(opts), ws.data_ptr(), out["targets"].data_ptr(),
-                                                       out["Y"].data_ptr(), out["stats"].data_ptr(), out["q"].data_ptr(),
-                                                       out["pos_err"].data_ptr(), out["rot_err"].data_ptr(),
-                                                       attempt.data_ptr(), self._stream()))
-            elif q_init is None:
-                _ffi.check(self.lib.gik_ik_batch(self._h, T.data_ptr(), B, out["targets"].data_ptr(),
-                                                 out["Y"].data_ptr(), out["stats"].data_ptr(),
-                                                 out["q"].data_ptr(), out["pos_err"].data_ptr(),
-                                                 out["rot_err"].data_ptr(), self._stream()))
+                                                       C.byref(opts), ws.data_ptr(), *answer, attempt.data_ptr(),
+                                                       self._stream()))
+                extras = {"attempt": attempt, "_retry_ws": ws}      # (the workspace lives as long as the result)
+            elif q0 is None:
+                _ffi.check(self.lib.gik_ik_batch(self._h, T.data_ptr(), B, *answer, self._stream()))
             else:
-                q0 = self._seed_angles(q_init, B)
-                _ffi.check(self.lib.gik_ik_batch_seeded(self._h, T.data_ptr(), q0.data_ptr(), B,
-                                                        out["targets"].data_ptr(), out["Y"].data_ptr(),
-                                                        out["stats"].data_ptr(), out["q"].data_ptr(),
-                                                        out["pos_err"].data_ptr(), out["rot_err"].data_ptr(),
-                                                        self._stream()))
-        res = {"x": out["Y"].reshape(B, self.N, self.k), "q": out["q"], "pos_err": out["pos_err"],
-               "rot_err": out["rot_err"]}
-        if retries:
-            res["attempt"], res["_retry_ws"] = attempt, ws      # (the workspace lives as long as the result)
-        res.update(_decode_stats(out["stats"]))
-        return res
+                _ffi.check(self.lib.gik_ik_batch_seeded(self._h, T.data_ptr(), q0.data_ptr(), B, *answer, self._stream()))
+        return _result(out, (B, self.N, self.k), extras)
 
-    def alloc_anchored_buffers(self, base, B, clearance=False):
-        """The buffers of one anchored_ik call of B goals (its `out`): the scratch "ws", the full point
-        matrix "Y" [B, full_N*3], "stats", "q", "pos_err", "rot_err" and, if asked for, "clearance"."""
+    def _retry_buffers(self, out, B, nbytes, lo, hi):
+        """The restart buffers of one call with retries > 0, taken from `out` where it carries them: ("attempt" [B] int32,
+        "retry_ws" of at least nbytes -- what the call's gik_*retry_ws_bytes reported --, "q_lo", "q_hi" on the device);
+        a missing one is allocated, or uploaded from the checked limits lo / hi."""
+        attempt = out.get("attempt")
+        if attempt is None:
+            attempt = torch.empty(B, dtype=torch.int32, device=self.device)
+        ws = out.get("retry_ws")
+        if ws is None or ws.numel() * ws.element_size() < nbytes:
+            ws = torch.empty(max((nbytes + 7) // 8, 1), dtype=torch.float64, device=self.device)
+        q_lo = out["q_lo"] if "q_lo" in out else _dev(lo, self.device)
+        q_hi = out["q_hi"] if "q_hi" in out else _dev(hi, self.device)
+        return attempt, ws, q_lo, q_hi
+
+    def alloc_anchored_buffers(self, base, B, clearance=False, ws=True):
+        """The buffers of one anchored_ik call of B goals (its `out`): the scratch "ws" (ws=False leaves it out: a call
+        with retries > 0 keeps that scratch in its restart workspace), the full point matrix "Y" [B, full_N*3], "stats",
+        "q", "pos_err", "rot_err" and, if asked for, "clearance"."""
         f64 = dict(dtype=torch.float64, device=self.device)
-        nws = int(self.lib.gik_anchored_ws_doubles(self._h, base._h, B))
-        out = {"ws": torch.empty(max(nws, 1), **f64), "Y": torch.empty(B, self.full_N * 3, **f64),
+        out = {"Y": torch.empty(B, self.full_N * 3, **f64),
                "stats": _alloc_stats(B, self.device), "q": torch.empty(B, base.n_joints, **f64),
                "pos_err": torch.empty(B, **f64), "rot_err": torch.empty(B, **f64)}
+        if ws:
+            out["ws"] = torch.empty(max(int(self.lib.gik_anchored_ws_doubles(self._h, base._h, B)), 1), **f64)
         if clearance:
             out["clearance"] = torch.empty(B, **f64)
         return out
@@ -555,6 +561,10 @@ class Template:
         minimum of |Y_i - centre| - radius over the free nodes that carry the obstacle hinges and the
         obstacles; +inf without obstacles."""
         assert self.anchored
+        return self._clearance_of(self.lib.gik_anchored_clearance, Y_full)
+
+    def _clearance_of(self, clear_fn, Y_full):
+        """Full point matrices [B, full_N, 3] (or [full_N, 3]) as a contiguous [B, full_N*3] buffer -> clear_fn's [B]."""
         Y = _dev(Y_full, self.device)
         if Y.dim() == 2:
             Y = Y[None]
@@ -563,7 +573,7 @@ class Template:
         Y = Y.reshape(B, self.full_N * 3).contiguous()
         out = torch.empty(B, dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
-            _ffi.check(self.lib.gik_anchored_clearance(self._h, Y.data_ptr(), B, out.data_ptr(), self._stream()))
+            _ffi.check(clear_fn(self._h, Y.data_ptr(), B, out.data_ptr(), self._stream()))
         return out
 
     def attach_links(self, link_a, link_b, link_radius, hinges=False):
@@ -594,16 +604,7 @@ class Template:
         minimum over the attached links and the obstacles of the distance from the sphere to the link's capsule;
         +inf without obstacles or links."""
         assert self.anchored
-        Y = _dev(Y_full, self.device)
-        if Y.dim() == 2:
-            Y = Y[None]
-        B = Y.shape[0]
-        assert Y.numel() == B * self.full_N * 3, (tuple(Y.shape), (B, self.full_N, 3))
-        Y = Y.reshape(B, self.full_N * 3).contiguous()
-        out = torch.empty(B, dtype=torch.float64, device=self.device)
-        with torch.cuda.device(self.device):
-            _ffi.check(self.lib.gik_anchored_link_clearance(self._h, Y.data_ptr(), B, out.data_ptr(), self._stream()))
-        return out
+        return self._clearance_of(self.lib.gik_anchored_link_clearance, Y_full)
 
     def anchored_sweep_clearance(self, base, q_a, q_b, samples, out=None, ws=None):
         """Joint angles q_a, q_b [B,n] (device tensors or arrays) -> [B]: the minimum link clearance over the samples + 1
@@ -646,81 +647,51 @@ class Template:
         attempt): uniformly with retry_spread == 0, within retry_spread radians of q_init otherwise (which
         q_init must then be there for).  The better answer is kept; "attempt" [B] int32 says which one each
         goal holds, and "clearance" is always returned.  That call synchronises the stream once per attempt.
-        `out` may carry "attempt" [B] int32, "retry_ws" (gik_anchored_retry_ws_bytes) and "q_lo" / "q_hi".
+        `out` may carry "attempt" [B] int32, "retry_ws" (gik_anchored_retry_ws_bytes) and "q_lo" / "q_hi", and needs
+        no "ws": the restart workspace holds that scratch.
 
         clearance_mode: "nodes" (the joint points, gik_anchored_clearance) or "links" (whole links,
         gik_anchored_link_clearance; needs attach_links): which clearance comes back and the restart rule reads."""
         assert self.anchored and base.has_pipeline
         mode = check_clearance_mode(clearance_mode, getattr(self, "n_link", None) is not None)
-        if retries:      # (the clearance always comes back then: `clearance` is not read)
+        if retries:      # (the clearance always comes back then, whatever `clearance` says)
             retries, lo, hi = check_retry_args(retries, pos_tol, rot_tol, q_limits, base.n_joints, clear_tol=clear_tol,
                                                retry_spread=retry_spread, has_center=q_init is not None)
-            return self._anchored_ik_retry(base, T_goal, q_init, out, retries, lo, hi, retry_seed, pos_tol, rot_tol,
-                                           clear_tol, retry_spread, mode)
-        clear_fn = self.lib.gik_anchored_link_clearance if mode == _ffi.CLEARANCE_LINKS else self.lib.gik_anchored_clearance
+            clearance = True
         T, B = base._poses(T_goal)
-        if out is None:
-            out = self.alloc_anchored_buffers(base, B, clearance)
-        ws = out["ws"]
-        assert ws.numel() >= int(self.lib.gik_anchored_ws_doubles(self._h, base._h, B))
+        if out is None:      # (with retries the restart workspace holds the scratch "ws")
+            out = self.alloc_anchored_buffers(base, B, clearance, ws=not retries)
+        q0 = None if q_init is None else base._seed_angles(q_init, B)
         cl = None
         if clearance:
             cl = out["clearance"] if "clearance" in out else torch.empty(B, dtype=torch.float64, device=self.device)
+        answer = [out[key].data_ptr() for key in ("Y", "stats", "q", "pos_err", "rot_err")]
         with torch.cuda.device(self.device):
-            if q_init is None:
-                _ffi.check(self.lib.gik_anchored_ik_batch(self._h, base._h, T.data_ptr(), B, ws.data_ptr(),
-                                                          out["Y"].data_ptr(), out["stats"].data_ptr(),
-                                                          out["q"].data_ptr(), out["pos_err"].data_ptr(),
-                                                          out["rot_err"].data_ptr(), self._stream()))
-                if clearance:
-                    _ffi.check(clear_fn(self._h, out["Y"].data_ptr(), B, cl.data_ptr(), self._stream()))
-            else:
-                q0 = base._seed_angles(q_init, B)
-                links = cl is not None and mode == _ffi.CLEARANCE_LINKS
+            if retries:
+                nbytes = int(self.lib.gik_anchored_retry_ws_bytes(self._h, base._h, B))
+                attempt, ws, q_lo, q_hi = self._retry_buffers(out, B, nbytes, lo, hi)
+                opts = _ffi.AnchoredRetryOpts(retries=retries, clearance_mode=mode, seed=int(retry_seed) & (2 ** 64 - 1),
+                                              pos_tol=float(pos_tol), rot_tol=float(rot_tol), d_q_lo=q_lo.data_ptr(),
+                                              d_q_hi=q_hi.data_ptr(), clear_tol=float(clear_tol), spread=float(retry_spread))
+                _ffi.check(self.lib.gik_anchored_ik_batch_retry(
+                    self._h, base._h, T.data_ptr(), None if q0 is None else q0.data_ptr(), B, C.byref(opts), ws.data_ptr(),
+                    *answer, cl.data_ptr(), attempt.data_ptr(), self._stream()))
+                return _result(out, (B, self.full_N, 3), {"clearance": cl, "attempt": attempt, "_retry_ws": ws})
+            ws = out["ws"]
+            assert ws.numel() >= int(self.lib.gik_anchored_ws_doubles(self._h, base._h, B))
+            if q0 is None:
+                _ffi.check(self.lib.gik_anchored_ik_batch(self._h, base._h, T.data_ptr(), B, ws.data_ptr(), *answer,
+                                                          self._stream()))
+                after = clearance
+            else:      # (the seeded call measures the joint points itself; whole links are measured after it)
+                after = clearance and mode == _ffi.CLEARANCE_LINKS
                 _ffi.check(self.lib.gik_anchored_ik_batch_seeded(
-                    self._h, base._h, T.data_ptr(), q0.data_ptr(), B, ws.data_ptr(), out["Y"].data_ptr(),
-                    out["stats"].data_ptr(), out["q"].data_ptr(), out["pos_err"].data_ptr(), out["rot_err"].data_ptr(),
-                    None if cl is None or links else cl.data_ptr(), self._stream()))
-                if links:
-                    _ffi.check(clear_fn(self._h, out["Y"].data_ptr(), B, cl.data_ptr(), self._stream()))
-        res = {"x": out["Y"].reshape(B, self.full_N, 3), "q": out["q"], "pos_err": out["pos_err"],
-               "rot_err": out["rot_err"], "_ws": ws}
-        if clearance:
-            res["clearance"] = cl
-        res.update(_decode_stats(out["stats"]))
-        return res
-
-    def _anchored_ik_retry(self, base, T_goal, q_init, out, retries, lo, hi, retry_seed, pos_tol, rot_tol, clear_tol,
-                           retry_spread, clearance_mode=_ffi.CLEARANCE_NODES):
-        """anchored_ik with retries > 0, its arguments already checked (check_retry_args: retries, lo, hi are what it
-        returns; check_clearance_mode: clearance_mode): one gik_anchored_ik_batch_retry call.  `out` needs no "ws": the
-        restart workspace holds that scratch."""
-        T, B = base._poses(T_goal)
-        if out is None:
-            out = self.alloc_anchored_buffers(base, B, clearance=True)
-            del out["ws"]
-        dev = self.device
-        cl = out["clearance"] if "clearance" in out else torch.empty(B, dtype=torch.float64, device=dev)
-        attempt = out["attempt"] if "attempt" in out else torch.empty(B, dtype=torch.int32, device=dev)
-        ws = out.get("retry_ws")
-        nbytes = int(self.lib.gik_anchored_retry_ws_bytes(self._h, base._h, B))
-        if ws is None or ws.numel() * ws.element_size() < nbytes:
-            ws = torch.empty(max((nbytes + 7) // 8, 1), dtype=torch.float64, device=dev)
-        q_lo = out["q_lo"] if "q_lo" in out else _dev(lo, dev)
-        q_hi = out["q_hi"] if "q_hi" in out else _dev(hi, dev)
-        opts = _ffi.AnchoredRetryOpts(retries=retries, clearance_mode=int(clearance_mode), seed=int(retry_seed) & (2 ** 64 - 1), pos_tol=float(pos_tol),
-                                      rot_tol=float(rot_tol), d_q_lo=q_lo.data_ptr(), d_q_hi=q_hi.data_ptr(),
-                                      clear_tol=float(clear_tol), spread=float(retry_spread))
-        with torch.cuda.device(dev):
-            q0 = None if q_init is None else base._seed_angles(q_init, B)
-            _ffi.check(self.lib.gik_anchored_ik_batch_retry(
-                self._h, base._h, T.data_ptr(), None if q0 is None else q0.data_ptr(), B, C.byref(opts), ws.data_ptr(),
-                out["Y"].data_ptr(), out["stats"].data_ptr(), out["q"].data_ptr(), out["pos_err"].data_ptr(),
-                out["rot_err"].data_ptr(), cl.data_ptr(), attempt.data_ptr(), self._stream()))
-        res = {"x": out["Y"].reshape(B, self.full_N, 3), "q": out["q"], "pos_err": out["pos_err"],
-               "rot_err": out["rot_err"], "clearance": cl, "attempt": attempt, "_retry_ws": ws}
-        res.update(_decode_stats(out["stats"]))
-        return res
+                    self._h, base._h, T.data_ptr(), q0.data_ptr(), B, ws.data_ptr(), *answer,
+                    None if cl is None or after else cl.data_ptr(), self._stream()))
+            if after:
+                clear_fn = self.lib.gik_anchored_link_clearance if mode == _ffi.CLEARANCE_LINKS else self.lib.gik_anchored_clearance
+                _ffi.check(clear_fn(self._h, out["Y"].data_ptr(), B, cl.data_ptr(), self._stream()))
+        return _result(out, (B, self.full_N, 3), {"_ws": ws, "clearance": cl} if clearance else {"_ws": ws})
 
     def alloc_ik_buffers(self, B):
         f64 = dict(dtype=torch.float64, device=self.device)

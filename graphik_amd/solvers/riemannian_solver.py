@@ -649,19 +649,23 @@ class AnchoredProblem:
         (retry_seeds_host(..., center=q_init[g:g+1], spread=retry_spread)), for a tracked waypoint that
         should stay on its IK branch."""
         T = np.asarray(T_goals, dtype=float)
-        mode = check_clearance_mode(clearance_mode, len(self.link_names) > 0)
-        if retries:      # checked here, before any device call, and once
-            q_limits = self.robot.limits_arrays() if q_limits is None else q_limits
-            retries, lo, hi = check_retry_args(retries, pos_tol, rot_tol, q_limits, self.robot.n, clear_tol=clear_tol,
-                                               retry_spread=retry_spread, has_center=q_init is not None)
+        check_clearance_mode(clearance_mode, len(self.link_names) > 0)
+        retry = self._retry_args(retries, retry_seed, pos_tol, rot_tol, clear_tol, retry_spread, q_limits, q_init is not None)
         if q_init is not None:
             q_init = _seed_angles(q_init, T.shape[0], self.robot.n)
-        if retries:
-            return self.template._anchored_ik_retry(self.base.template, T, q_init, None, retries, lo, hi, retry_seed, pos_tol,
-                                                    rot_tol, clear_tol, retry_spread, mode)
-        if q_init is None:
-            return self.template.anchored_ik(self.base.template, T, clearance=clearance, clearance_mode=clearance_mode)
-        return self.template.anchored_ik(self.base.template, T, q_init=q_init, clearance=True, clearance_mode=clearance_mode)
+        return self.template.anchored_ik(self.base.template, T, q_init=q_init, clearance=clearance or q_init is not None,
+                                         clearance_mode=clearance_mode, **retry)
+
+    def _retry_args(self, retries, retry_seed, pos_tol, rot_tol, clear_tol, retry_spread, q_limits, has_center=True):
+        """The restart arguments of solve / solve_trajectory, checked here before any device call, as the keywords
+        Template.anchored_ik takes ({} with retries == 0); q_limits defaults to the robot's limits_arrays()."""
+        if not retries:
+            return {}
+        q_limits = self.robot.limits_arrays() if q_limits is None else q_limits
+        retries, lo, hi = check_retry_args(retries, pos_tol, rot_tol, q_limits, self.robot.n, clear_tol=clear_tol,
+                                           retry_spread=retry_spread, has_center=has_center)
+        return dict(retries=retries, retry_seed=retry_seed, pos_tol=pos_tol, rot_tol=rot_tol, clear_tol=clear_tol,
+                    retry_spread=retry_spread, q_limits=(lo, hi))
 
     def solve_trajectory(self, T_path, q_start, return_Y=False, retries=0, retry_seed=0, pos_tol=0.01, rot_tol=0.01,
                          clear_tol=1e-4, retry_spread=0.0, q_limits=None, clearance_mode="nodes", sweep=None):
@@ -689,67 +693,32 @@ class AnchoredProblem:
         iterations, inner_iterations, stop, f(x), gradnorm, pos_err, rot_err, clearance, plus
         solve_time (seconds, whole path)."""
         T = np.asarray(T_path, dtype=float)
-        B, L = T.shape[:2]
-        n = self.robot.n
-        q0 = _seed_angles(q_start, B, n, "q_start")
-        mode = check_clearance_mode(clearance_mode, len(self.link_names) > 0)
+        B = T.shape[0]
+        q0 = _seed_angles(q_start, B, self.robot.n, "q_start")
+        check_clearance_mode(clearance_mode, len(self.link_names) > 0)
         if sweep is not None:
             sweep = self._check_samples(sweep, "sweep")
             if not len(self.link_names):
                 raise ValueError("sweep needs a link set: this problem was built without links")
-        if retries:
-            q_limits = self.robot.limits_arrays() if q_limits is None else q_limits
-            retries, q_lo, q_hi = check_retry_args(retries, pos_tol, rot_tol, q_limits, n, clear_tol=clear_tol,
-                                                   retry_spread=retry_spread)
+        retry = self._retry_args(retries, retry_seed, pos_tol, rot_tol, clear_tol, retry_spread, q_limits)
         tpl, base = self.template, self.base.template
-        dev = tpl.device
-        f64 = dict(dtype=torch.float64, device=dev)
-        Tw = torch.from_numpy(np.ascontiguousarray(np.swapaxes(T, 0, 1))).to(dev)     # [L, B, 4, 4]: waypoint-major
-        q_all = torch.empty(L, B, n, **f64)
-        Y_all = torch.empty(L if return_Y else 1, B, tpl.full_N * 3, **f64)
-        stats = _alloc_stats(L * B, dev)
-        stats = stats.reshape(L, B, stats.shape[1])
-        pe, re, cl = (torch.empty(L, B, **f64) for _ in range(3))
-        if retries:      # one restart workspace (it holds the anchored scratch too) and one copy of the limits for all waypoints
+        planes, shared, nbytes = ["clearance"], {}, None
+        if retry:      # (the restart workspace holds the anchored scratch too)
+            planes.append("attempt")
             nbytes = int(tpl.lib.gik_anchored_retry_ws_bytes(tpl._h, base._h, B))
-            shared = {"retry_ws": torch.empty(max((nbytes + 7) // 8, 1), **f64), "q_lo": torch.from_numpy(q_lo).to(dev),
-                      "q_hi": torch.from_numpy(q_hi).to(dev)}
-            attempt = torch.empty(L, B, dtype=torch.int32, device=dev)
         else:
-            shared = {"ws": tpl.alloc_anchored_buffers(base, B)["ws"]}
-        q_prev = torch.from_numpy(q0).to(dev)
-        if sweep:      # the start angles outlive waypoint 0's solve (it may write q_all[0] only), one workspace for all waypoints
-            sc = torch.empty(L, B, **f64)
-            sweep_ws = torch.empty(max(int(tpl.lib.gik_anchored_sweep_ws_bytes(tpl._h, base._h, B, sweep)) // 8, 1), **f64)
-        torch.cuda.synchronize(dev)
-        t0 = time.time()
-        for l in range(L):
-            out = {"Y": Y_all[l if return_Y else 0], "stats": stats[l], "q": q_all[l], "pos_err": pe[l],
-                   "rot_err": re[l], "clearance": cl[l], **shared}
-            if retries:
-                out["attempt"] = attempt[l]
-                tpl._anchored_ik_retry(base, Tw[l], q_prev, out, retries, q_lo, q_hi, retry_seed, pos_tol, rot_tol, clear_tol,
-                                       retry_spread, mode)
-            else:
-                tpl.anchored_ik(base, Tw[l], q_init=q_prev, out=out, clearance=True, clearance_mode=clearance_mode)
+            shared["ws"] = tpl.alloc_anchored_buffers(base, B)["ws"]
+        if sweep:      # one workspace for all waypoints
+            planes.append("sweep_clearance")
+            sweep_ws = torch.empty(max(int(tpl.lib.gik_anchored_sweep_ws_bytes(tpl._h, base._h, B, sweep)) // 8, 1),
+                                   dtype=torch.float64, device=tpl.device)
+
+        def step(T_l, q_prev, out):
+            tpl.anchored_ik(base, T_l, q_init=q_prev, out=out, clearance=True, clearance_mode=clearance_mode, **retry)
             if sweep:
-                tpl.anchored_sweep_clearance(base, q_prev, q_all[l], sweep, out=sc[l], ws=sweep_ws)
-            q_prev = q_all[l]
-        torch.cuda.synchronize(dev)
-        dt = time.time() - t0
-        st = _decode_stats(stats.reshape(L * B, stats.shape[2]))
-        info = {"iterations": st["iterations"], "inner_iterations": st["inner_total"], "stop": st["stop"],
-                "f(x)": st["f"], "gradnorm": st["gradnorm"], "pos_err": pe.reshape(-1), "rot_err": re.reshape(-1),
-                "clearance": cl.reshape(-1)}
-        if retries:
-            info["attempt"] = attempt.reshape(-1)
-        if sweep:
-            info["sweep_clearance"] = sc.reshape(-1)
-        info = {key: v.reshape(L, B).T.cpu().numpy() for key, v in info.items()}
-        info["solve_time"] = dt
-        q = q_all.permute(1, 0, 2).cpu().numpy()
-        Y = Y_all.reshape(L, B, tpl.full_N, 3).permute(1, 0, 2, 3).cpu().numpy() if return_Y else None
-        return q, Y, info
+                tpl.anchored_sweep_clearance(base, q_prev, out["q"], sweep, out=out["sweep_clearance"], ws=sweep_ws)
+
+        return _track(tpl, T, q0, (tpl.full_N, 3), return_Y, planes, step, shared, nbytes, retry.get("q_limits"))
 
     @staticmethod
     def _check_samples(samples, name="samples"):
@@ -1066,51 +1035,28 @@ def solve_batch(graph, T_goals, use_limits=True, params=None, device=None, Y_ini
     prob = _problem_for(graph, use_limits, params, device)
     if retries and not prob.device_pipeline:
         raise ValueError("retries > 0 needs the device pipeline, which this graph is outside of")
+    tpl = prob.template
+    on_device = prob.device_pipeline and Y_init is None
     t0 = time.time()
-    attempt = None
-    if retries:
-        res = prob.template.ik(T, q_init=q_init, **retry)      # gik_ik_batch_retry
-        torch.cuda.synchronize(prob.template.device)
-        dt = time.time() - t0
-        Y = res["x"].cpu().numpy()
-        q = res["q"].cpu().numpy()
-        pos, rot = res["pos_err"].cpu().numpy(), res["rot_err"].cpu().numpy()
-        attempt = res["attempt"].cpu().numpy()
-    elif q_init is not None:
-        if prob.device_pipeline:
-            res = prob.template.ik(T, q_init=q_init)      # seed -> solve -> recover (gik_ik_batch_seeded)
-            torch.cuda.synchronize(prob.template.device)
-            dt = time.time() - t0
-            Y = res["x"].cpu().numpy()
-            q = res["q"].cpu().numpy()
-            pos, rot = res["pos_err"].cpu().numpy(), res["rot_err"].cpu().numpy()
-        else:
-            targets = prob.targets_from_D(prob.assemble(T)[0])
-            Y0 = prob.seed_points(q_init)
-            t0 = time.time()
-            res = prob.template.solve(Y0, targets)
-            torch.cuda.synchronize(prob.template.device)
-            dt = time.time() - t0
-            Y = res["x"].cpu().numpy()
-            q = prob.joint_variables(Y, T)
-            pos, rot = prob.pose_errors(q, T)
-    elif prob.device_pipeline and Y_init is None:
-        # everything on the device: prepare -> solve -> recover (gik_ik_batch)
-        res = prob.template.ik(T)
-        torch.cuda.synchronize(prob.template.device)
-        dt = time.time() - t0
-        Y = res["x"].cpu().numpy()
-        q = res["q"].cpu().numpy()
-        pos, rot = res["pos_err"].cpu().numpy(), res["rot_err"].cpu().numpy()
+    if on_device:
+        # everything on the device: prepare or seed -> solve (with restarts) -> recover (gik_ik_batch[_seeded | _retry])
+        res = tpl.ik(T, q_init=q_init, **retry)
     else:
-        targets, Y0 = prob.prepare(T)
-        if Y_init is not None:
-            Y0 = np.asarray(Y_init, dtype=float)
+        # the host prepares and recovers around the device solve; the clock starts after the preparation
+        if q_init is not None:
+            targets, Y0 = prob.targets_from_D(prob.assemble(T)[0]), prob.seed_points(q_init)
+        else:
+            targets, Y0 = prob.prepare(T)
+            if Y_init is not None:
+                Y0 = np.asarray(Y_init, dtype=float)
         t0 = time.time()
-        res = prob.template.solve(Y0, targets)
-        torch.cuda.synchronize(prob.template.device)
-        dt = time.time() - t0
-        Y = res["x"].cpu().numpy()
+        res = tpl.solve(Y0, targets)
+    torch.cuda.synchronize(tpl.device)
+    dt = time.time() - t0
+    Y = res["x"].cpu().numpy()
+    if on_device:
+        q, pos, rot = (res[key].cpu().numpy() for key in ("q", "pos_err", "rot_err"))
+    else:
         q = prob.joint_variables(Y, T)
         pos, rot = prob.pose_errors(q, T)
     info = {"x": Y, "f(x)": res["f"].cpu().numpy(), "gradnorm": res["gradnorm"].cpu().numpy(),
@@ -1118,7 +1064,7 @@ def solve_batch(graph, T_goals, use_limits=True, params=None, device=None, Y_ini
             "inner_iterations": res["inner_total"].cpu().numpy(),
             "stop": res["stop"].cpu().numpy(), "time": np.full(len(Y), dt / max(len(Y), 1)),
             "solve_time": dt, "pos_err": pos, "rot_err": rot,
-            "attempt": attempt if attempt is not None else np.zeros(len(Y), dtype=np.int32)}
+            "attempt": res["attempt"].cpu().numpy() if retries else np.zeros(len(Y), dtype=np.int32)}
     return q, Y, info
 
 
@@ -1164,39 +1110,58 @@ def solve_trajectory(graph, T_path, q_start, use_limits=True, params=None, devic
         out["solve_time"] = dt
         return np.stack(qs, axis=1), (np.stack(Ys, axis=1) if return_Y else None), out
     tpl = prob.template
+    shared = {"targets": torch.empty(B, tpl.T, dtype=torch.float64, device=tpl.device)}
+    nbytes = None
+    if retries:
+        retry["q_limits"] = (q_lo, q_hi)
+        nbytes = int(tpl.lib.gik_retry_ws_bytes(tpl._h, B))
+
+    def step(T_l, q_prev, out):
+        tpl.ik(T_l, out=out, q_init=q_prev, **retry)
+
+    return _track(tpl, T, q0, (tpl.N, tpl.k), return_Y, ["attempt"], step, shared, nbytes, retry.get("q_limits"))
+
+
+def _track(tpl, T, q0, Y_shape, return_Y, planes, step, shared, retry_ws_bytes=None, q_limits=None):
+    """The tracking loop of both solve_trajectory functions: B paths of L waypoints T [B, L, ...] from the start angles
+    q0 [B, n], on tpl's device.  step(T_l, q_prev, out) makes waypoint l's calls: goal poses T_l [B, ...], the angles
+    q_prev [B, n] that seed it (q0, then waypoint l-1's answer -- they never leave the device), and `out`, its rows of
+    the result storage: "Y" (row 0 every time unless return_Y), "stats", "q", "pos_err", "rot_err", one [B] row per
+    name in `planes` ("attempt": int32, zero where no call writes it; the others float64) and what the waypoints
+    share: `shared` and, with retry_ws_bytes (the caller's gik_*retry_ws_bytes) and q_limits = (q_lo, q_hi), one
+    restart workspace "retry_ws" and one upload of the limits "q_lo" / "q_hi".  One synchronisation after the last
+    waypoint.  Returns q [B, L, n], Y [B, L, *Y_shape] (None unless return_Y) and info: [B, L] arrays of the stats
+    and the planes, plus solve_time."""
+    B, L = T.shape[:2]
     dev = tpl.device
     f64 = dict(dtype=torch.float64, device=dev)
     Tw = torch.from_numpy(np.ascontiguousarray(np.swapaxes(T, 0, 1))).to(dev)     # [L, B, ...]: waypoint-major
-    q_all = torch.empty(L, B, n, **f64)
-    Y_all = torch.empty(L if return_Y else 1, B, tpl.N * tpl.k, **f64)
-    stats = _alloc_stats(L * B, dev).reshape(L, B, -1)
-    pe, re = torch.empty(L, B, **f64), torch.empty(L, B, **f64)
-    targets = torch.empty(B, tpl.T, **f64)
-    q_prev = torch.from_numpy(q0).to(dev)
-    attempt = torch.zeros(L, B, dtype=torch.int32, device=dev)
-    shared = {}
-    if retries:      # one restart workspace and one copy of the limits for all waypoints
-        nbytes = int(tpl.lib.gik_retry_ws_bytes(tpl._h, B))
-        shared = {"retry_ws": torch.empty((nbytes + 7) // 8, **f64), "q_lo": torch.from_numpy(q_lo).to(dev),
-                  "q_hi": torch.from_numpy(q_hi).to(dev)}
-        retry["q_limits"] = (q_lo, q_hi)
+    q_all = torch.empty(L, B, q0.shape[1], **f64)
+    Y_all = torch.empty(L if return_Y else 1, B, Y_shape[0] * Y_shape[1], **f64)
+    stats = _alloc_stats(L * B, dev)
+    stats = stats.reshape(L, B, stats.shape[1])      # (no -1: B may be 0)
+    rows ={name: torch.zeros(L, B, dtype=torch.int32, device=dev) if name == "attempt" else torch.empty(L, B, **f64)
+            for name in ("pos_err", "rot_err", *planes)}
+    shared = dict(shared)
+    if retry_ws_bytes is not None:
+        shared.update(retry_ws=torch.empty(max((retry_ws_bytes + 7) // 8, 1), **f64),
+                      q_lo=torch.from_numpy(q_limits[0]).to(dev), q_hi=torch.from_numpy(q_limits[1]).to(dev))
+    q_prev = torch.from_numpy(q0).to(dev)      # (its own tensor: the start angles outlive waypoint 0's solve)
     torch.cuda.synchronize(dev)
     t0 = time.time()
     for l in range(L):
-        out = {"targets": targets, "Y": Y_all[l if return_Y else 0], "stats": stats[l], "q": q_all[l],
-               "pos_err": pe[l], "rot_err": re[l], "attempt": attempt[l], **shared}
-        tpl.ik(Tw[l], out=out, q_init=q_prev, **retry)
+        step(Tw[l], q_prev, {"Y": Y_all[l if return_Y else 0], "stats": stats[l], "q": q_all[l],
+                             **{name: plane[l] for name, plane in rows.items()}, **shared})
         q_prev = q_all[l]
     torch.cuda.synchronize(dev)
     dt = time.time() - t0
-    st = _decode_stats(stats.reshape(L * B, -1))
+    st = _decode_stats(stats.reshape(L * B, stats.shape[2]))
     info = {"iterations": st["iterations"], "inner_iterations": st["inner_total"], "stop": st["stop"],
-            "f(x)": st["f"], "gradnorm": st["gradnorm"], "pos_err": pe.reshape(-1), "rot_err": re.reshape(-1),
-            "attempt": attempt.reshape(-1)}
+            "f(x)": st["f"], "gradnorm": st["gradnorm"], **{name: plane.reshape(-1) for name, plane in rows.items()}}
     info = {key: v.reshape(L, B).T.cpu().numpy() for key, v in info.items()}
     info["solve_time"] = dt
     q = q_all.permute(1, 0, 2).cpu().numpy()
-    Y = Y_all.reshape(L, B, tpl.N, tpl.k).permute(1, 0, 2, 3).cpu().numpy() if return_Y else None
+    Y = Y_all.reshape(L, B, *Y_shape).permute(1, 0, 2, 3).cpu().numpy() if return_Y else None
     return q, Y, info
 
 
