@@ -18,6 +18,9 @@ GIK_KERNELS_ANCH_LINK(GIK_EXTERN_TEMPLATE)
 static_assert(PLAN_MIG_SIMDS == MIG_SIMDS && PLAN_SLICE_STATE_BYTES == sizeof(SliceState) && PLAN_QUAD_SLOTS == QUAD_SLOTS,
               "gik_plan.h restates these constants of the kernel headers");
 static_assert(PLAN_CLAIM_KEY_MAX_TERMS == CLAIM_KEY_MAX_TERMS, "gik_plan.h restates this constant of gik_order.hip.h");
+static_assert(PLAN_PREP_MAXN == PREP_MAXN && PLAN_PREP_BIGN == PREP_BIGN && PLAN_PREPQ_MAXN == PREPQ_MAXN &&
+                  PLAN_PREPQ_VEC_STRIDE == PREPQ_VEC_STRIDE && PLAN_PREP_NT == PREP_NT && PLAN_WAVE == WAVE,
+              "gik_plan.h restates these constants of gik_prep.hip.h and gik_prep_quad.hip.h");
 
 // the compiled node-per-lane variants
 struct NptVariant {
@@ -49,18 +52,6 @@ static int fail(const std::string &m) {
     if (e_ != hipSuccess)                                                                 \
       return fail(std::string(#expr) + ": " + hipGetErrorString(e_));                     \
   } while (0)
-
-// Carves a caller-owned workspace into arrays, each padded to 8 bytes.  A null base only adds up the size.
-struct WsCarve {
-  uintptr_t base;
-  size_t off;
-  template <typename T>
-  T *take(size_t n) {
-    T *at = reinterpret_cast<T *>(base + off);
-    off += (n * sizeof(T) + 7) / 8 * 8;
-    return at;
-  }
-};
 
 typedef void (*solve_fn)(SolveArgs);
 typedef void (*kat_fn)(KatArgs);
@@ -222,20 +213,15 @@ struct gik_template {
   bool has_pipe = false;
   gik::PipeConst pc = {};
   std::vector<void *> pipe_allocs;
-  size_t prep_smem;
-  int prep_waves_per_cu = 8;   // resident prepare waves (workgroups on the block variant) per CU
-  bool prep_block = false;
-  bool prep_quad = false;      // four goals per wavefront (prep_quad_kernel: graphs of at most 16 nodes)
-  size_t prep_quad_smem = 0;
-  int prep_quad_waves_per_cu = 8;
-  bool prep_a_lds = false;     // block variant: work matrix in LDS
-  bool prep_big = false;       // block variant for graphs of 129 .. 255 nodes (work matrix in the slab, always compressed)
-  bool prep_no_compress = false;   // block variant: full N x N Jacobi even where the Gram matrix is rank deficient
-  double *prep_ws = nullptr;   // [n_cu * prep_waves_per_cu][5][N*N] (block variant)
-  hipEvent_t prep_done = nullptr;   // block variant: launches share prep_ws, so each one waits
-  std::mutex prep_mutex;            // for the previous one (whatever stream it ran on)
-  bool prep_pending = false;
-  int sweeps;
+  // the prepare kernel of this template, resolved once at attach (plan_prepare, gik_plan.h), and what a block variant needs
+  struct Prepare {
+    gik::PrepPlan plan;
+    int sweeps = 10;
+    double *ws = nullptr;        // the slab, plan.slab_bytes
+    hipEvent_t done = nullptr;   // launches share the slab, so each one waits for the
+    std::mutex mutex;            // previous one (whatever stream it ran on)
+    bool pending = false;
+  } prep;
   // joint-configuration seeds (gik_seed_batch): FK tables built at attach; seed_ok is false (and seed_why says why)
   // for a graph with a node that neither a frame nor an anchor places
   gik::SeedConst sc = {};
@@ -244,6 +230,8 @@ struct gik_template {
   std::string seed_why;
 };
 static constexpr int kCounterRing = 256;
+// doubles of one goal: a (K+1) x (K+1) pose per end effector
+static int pose_width(const gik_template *t) { return t->pc.n_ee * (t->f.K + 1) * (t->f.K + 1); }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a property of the kernel, not of a launch: several
 // templates share a kernel, so the allowance is only ever raised (a later, smaller template must
@@ -1034,7 +1022,7 @@ void gik_template_destroy(gik_template *t) {
   for (void *p : t->pipe_allocs) (void)hipFree(p);
   if (t->ev_solve0) (void)hipEventDestroy(t->ev_solve0);
   if (t->ev_solve1) (void)hipEventDestroy(t->ev_solve1);
-  if (t->prep_done) (void)hipEventDestroy(t->prep_done);
+  if (t->prep.done) (void)hipEventDestroy(t->prep.done);
   for (auto &c : t->counter_slot)
     if (c.done) (void)hipEventDestroy(c.done);
   for (auto &w : t->slice_ws) {
@@ -1126,8 +1114,9 @@ static bool seed_tables(gik_template *t, const gik_pipeline_desc *d, const std::
   return true;
 }
 
-int gik_pipeline_attach(gik_template *t, const gik_pipeline_desc *d) {
-  using namespace gik;
+namespace gik {      // ---- gik_pipeline_attach, step by step ----
+
+static int validate_pipeline(const gik_template *t, const gik_pipeline_desc *d) {
   if (!t || !d) return fail("null argument");
   if (t->has_pipe) return fail("pipeline already attached");
   const int N = t->N, K = t->f.K, n = d->n_joints;
@@ -1139,9 +1128,13 @@ int gik_pipeline_attach(gik_template *t, const gik_pipeline_desc *d) {
       !d->anchor_pos || !d->pair_i || !d->pair_j || !d->term_src || !d->term_static)
     return fail("null pipeline array");
   if (K == 3 && !d->q_index) return fail("q_index required for k=3");
+  return 0;
+}
+
+// the descriptor's arrays on the device and its scalars (uploads stay in pipe_allocs for gik_template_destroy)
+static int upload_pipe_const(gik_template *t, const gik_pipeline_desc *d, PipeConst &pc) {
+  const int N = t->N, K = t->f.K, n = d->n_joints, DD = (K + 1) * (K + 1);
   bool ok = true;
-  PipeConst pc;
-  const int DD = (K + 1) * (K + 1);
   pc.T0 = upload(t, d->T0, (size_t)(n + 1) * DD, ok);
   pc.p_idx = upload(t, d->p_index, n + 1, ok);
   pc.q_idx = (K == 3) ? upload(t, d->q_index, n + 1, ok) : pc.p_idx;
@@ -1162,7 +1155,19 @@ int gik_pipeline_attach(gik_template *t, const gik_pipeline_desc *d) {
   pc.n_joints = n;
   pc.goal0 = d->goal_node0;
   pc.goal1 = d->goal_node1;
-  // end effectors: a chain is one path 0..n with goal nodes (goal_node0, goal_node1)
+  pc.x_idx = d->x_index;
+  pc.y_idx = d->y_index;
+  pc.goal_len = d->goal_len;
+  pc.axis_length = d->axis_length;
+  pc.last_along_z = d->last_link_along_z;
+  return 0;
+}
+
+// end effectors: a chain is one path 0..n with goal nodes (goal_node0, goal_node1).  path: [n_ee][n + 1], -1 past an end
+static int end_effector_paths(gik_template *t, const gik_pipeline_desc *d, PipeConst &pc, std::vector<int> &path,
+                              bool &inert_goal_slot) {
+  const int N = t->N, K = t->f.K, n = d->n_joints;
+  bool ok = true;
   const int n_ee = d->n_ee > 1 ? d->n_ee : 1;
   if (n_ee > PREP_MAX_EE) return fail("at most 8 end effectors");
   if (n_ee > 1 && (!d->ee_goal_nodes || !d->ee_path || d->n_goal_pairs < 0 || (K == 2 && !d->ee_goal_len) ||
@@ -1170,8 +1175,7 @@ int gik_pipeline_attach(gik_template *t, const gik_pipeline_desc *d) {
     return fail("several end effectors: ee_goal_nodes / ee_path / goal pairs (k = 2: ee_goal_len) required");
   pc.n_ee = n_ee;
   pc.n_gg = n_ee > 1 ? d->n_goal_pairs : 0;
-  std::vector<int> path((size_t)n_ee * (n + 1), -1);
-  bool inert_goal_slot = false;
+  path.assign((size_t)n_ee * (n + 1), -1);
   for (int e = 0; e < PREP_MAX_EE; ++e) pc.ee_len[e] = (n_ee > 1 && K == 2 && e < n_ee) ? d->ee_goal_len[e] : d->goal_len;
   if (n_ee > 1) {
     for (int g = 0; g < 2 * n_ee; ++g) {
@@ -1198,72 +1202,75 @@ int gik_pipeline_attach(gik_template *t, const gik_pipeline_desc *d) {
   pc.gg_b = pc.n_gg ? upload(t, d->goal_pair_b, pc.n_gg, ok) : nullptr;
   if (2 * n_ee * d->n_anchor + pc.n_gg > 2 * PREP_MAXA + 16) return fail("too many anchor-goal pairs");
   if (!ok) return fail("device upload failed");
-  pc.x_idx = d->x_index;
-  pc.y_idx = d->y_index;
-  pc.goal_len = d->goal_len;
-  pc.axis_length = d->axis_length;
-  pc.last_along_z = d->last_link_along_z;
-  t->pc = pc;
-  t->sweeps = d->jacobi_sweeps > 0 ? d->jacobi_sweeps : 10;
-  t->prep_smem = sizeof(double) * ((size_t)5 * N * N + 2 * n_ee * d->n_anchor + pc.n_gg + 96) +
-                 sizeof(int) * (48 + (size_t)((N + 1) / 2) * ((N | 1) + (N + 1) / 2 + 1));   // (+ jacobi_lds's pair tables)
-  // graphs beyond one wavefront's LDS: workgroup-per-goal kernel with its matrices in a global slab
-  t->prep_block = N > 32 || d->n_anchor > 32 || d->force_block_prepare != 0 ||
-                  getenv("GIK_PREP_FORCE_BLOCK") != nullptr;
-  t->prep_no_compress = getenv("GIK_PREP_NO_COMPRESS") != nullptr;   // (developer A/B switch, read once, here)
-  t->prep_big = N > PREP_MAXN;      // graphs of 129 .. 255 nodes: prep_block_kernel<false, PREP_BIGN>, six matrices per slab
-  if (t->prep_block) {
-    int occ = 0;
-    // work matrix in LDS when it fits next to the kernel's static arrays (N <= 123), one workgroup per CU
-    t->prep_a_lds = false;
-    const size_t a_bytes = sizeof(double) * (size_t)N * N;
-    if (t->prep_big) {
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, prep_block_kernel<false, PREP_BIGN>, PREP_NT, 0) != hipSuccess)
-        occ = 1;
-    } else if (!getenv("GIK_PREP_A_GLOBAL") &&
-        raise_dynamic_lds((const void *)prep_block_kernel<true>, a_bytes) == hipSuccess &&
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, prep_block_kernel<true>, PREP_NT, a_bytes) == hipSuccess &&
-        occ >= 1)
-      t->prep_a_lds = true;
-    else
-      (void)hipGetLastError();
-    if (!t->prep_a_lds && !t->prep_big &&
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, prep_block_kernel<false>, PREP_NT, 0) != hipSuccess)
-      occ = 1;
-    occ = std::max(1, std::min(occ, 2));   // 5 N^2 doubles per workgroup: keep the slabs cache-resident
-    if (const char *e = getenv("GIK_PREP_WAVES_PER_CU")) occ = std::max(1, atoi(e));
-    t->prep_waves_per_cu = occ;
-    const size_t bytes = sizeof(double) * (t->prep_big ? 6 : 5) * (size_t)N * N * (size_t)t->f.n_cu * occ;
-    void *ws = nullptr;
-    if (hipMalloc(&ws, bytes) != hipSuccess) return fail("cannot allocate the prepare workspace");
-    t->pipe_allocs.push_back(ws);
-    t->prep_ws = static_cast<double *>(ws);
-    if (hipEventCreateWithFlags(&t->prep_done, hipEventDisableTiming) != hipSuccess)
-      return fail("hipEventCreate failed");
-  } else {
-    // the prepare kernel is latency-bound (dependent Jacobi chains, LDS round trips): run as many
-    // resident waves per CU as its registers and LDS allow (a fixed 8 per CU left half of them
-    // unused: planar-10 prepare 2.3 -> see NOTEBOOK 4.2)
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, prep_wave_kernel, WAVE, t->prep_smem) != hipSuccess)
-      occ = 8;
-    if (const char *e = getenv("GIK_PREP_WAVES_PER_CU")) occ = atoi(e);   // developer override
-    t->prep_waves_per_cu = std::max(1, std::min(occ, 32));
-    if (N <= PREPQ_MAXN && !inert_goal_slot && !getenv("GIK_NO_PREP_QUAD")) {   // (inert slots: prep_wave_kernel skips them)
-      t->prep_quad_smem = prep_quad_lds_bytes(N, 2 * n_ee * d->n_anchor + pc.n_gg);
-      int qocc = 0;
-      if (t->prep_quad_smem <= 40 * 1024 &&
-          hipOccupancyMaxActiveBlocksPerMultiprocessor(&qocc, N == 13 ? prep_quad_kernel<13> : prep_quad_kernel<0>, WAVE,
-                                                       t->prep_quad_smem) == hipSuccess &&
-          qocc >= 1) {
-        t->prep_quad = true;
-        if (const char *e = getenv("GIK_PREP_WAVES_PER_CU")) qocc = atoi(e);
-        t->prep_quad_waves_per_cu = std::max(1, std::min(qocc, 32));
-      } else {
-        (void)hipGetLastError();
-      }
-    }
+  return 0;
+}
+
+// the kernel of a prepare variant: the one place that names the six
+static const void *prep_kernel(Prep v) {
+  switch (v) {
+    case Prep::QUAD13: return (const void *)prep_quad_kernel<13>;
+    case Prep::QUAD: return (const void *)prep_quad_kernel<0>;
+    case Prep::WAVE: return (const void *)prep_wave_kernel;
+    case Prep::BLOCK_LDS: return (const void *)prep_block_kernel<true>;
+    case Prep::BLOCK: return (const void *)prep_block_kernel<false>;
+    case Prep::BLOCK_BIG: return (const void *)prep_block_kernel<false, PREP_BIGN>;
   }
+  return nullptr;
+}
+
+// plan_prepare's occupancy answer: resident workgroups per CU, -1 where the query -- for the LDS variant, raising the
+// kernel's allowance first -- failed
+static int prep_occupancy(Prep v, int threads, size_t lds) {
+  int occ = 0;
+  if ((v != Prep::BLOCK_LDS || raise_dynamic_lds(prep_kernel(v), lds) == hipSuccess) &&
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, prep_kernel(v), threads, lds) == hipSuccess)
+    return occ;
+  (void)hipGetLastError();
+  return -1;
+}
+
+// the prepare kernel of this template (plan_prepare), and the slab and the event of a block variant.  The developer
+// switches of the environment are read once, here.
+static int plan_and_acquire_prepare(gik_template *t, const gik_pipeline_desc *d, bool inert_goal_slot) {
+  PrepFacts f;
+  f.N = t->N;
+  f.K = t->f.K;
+  f.n_anchor = d->n_anchor;
+  f.n_ee = t->pc.n_ee;
+  f.n_gg = t->pc.n_gg;
+  f.inert_goal_slot = inert_goal_slot;
+  f.force_block_prepare = d->force_block_prepare != 0;
+  f.env_force_block = getenv("GIK_PREP_FORCE_BLOCK") != nullptr;
+  f.env_no_compress = getenv("GIK_PREP_NO_COMPRESS") != nullptr;
+  f.env_a_global = getenv("GIK_PREP_A_GLOBAL") != nullptr;
+  f.env_no_quad = getenv("GIK_NO_PREP_QUAD") != nullptr;
+  if (const char *e = getenv("GIK_PREP_WAVES_PER_CU")) {
+    f.env_waves_set = true;
+    f.env_waves = atoi(e);
+  }
+  f.n_cu = t->f.n_cu;
+  t->prep.sweeps = d->jacobi_sweeps > 0 ? d->jacobi_sweeps : 10;
+  t->prep.plan = plan_prepare(f, prep_occupancy);
+  if (!t->prep.plan.block()) return 0;
+  void *ws = nullptr;
+  if (hipMalloc(&ws, t->prep.plan.slab_bytes) != hipSuccess) return fail("cannot allocate the prepare workspace");
+  t->pipe_allocs.push_back(ws);
+  t->prep.ws = static_cast<double *>(ws);
+  if (hipEventCreateWithFlags(&t->prep.done, hipEventDisableTiming) != hipSuccess) return fail("hipEventCreate failed");
+  return 0;
+}
+
+}  // namespace gik
+
+int gik_pipeline_attach(gik_template *t, const gik_pipeline_desc *d) {
+  using namespace gik;
+  if (validate_pipeline(t, d)) return -1;
+  PipeConst pc;
+  std::vector<int> path;
+  bool inert_goal_slot = false;
+  if (upload_pipe_const(t, d, pc) || end_effector_paths(t, d, pc, path, inert_goal_slot)) return -1;
+  t->pc = pc;
+  if (plan_and_acquire_prepare(t, d, inert_goal_slot)) return -1;
   if (!seed_tables(t, d, path, pc.n_ee)) return fail("device upload failed");
   t->has_pipe = true;
   return 0;
@@ -1274,6 +1281,25 @@ int gik_prepare_batch(const gik_template *t, const double *d_T_goal, int B, doub
   return gik_prepare_batch_debug(t, d_T_goal, B, d_targets, d_Y_init, d_K_out, nullptr, stream);
 }
 
+// One prepare launch.  The block variants share the slab: each launch waits for the one before it, whatever stream that ran on.
+static int launch_prepare(const gik_template *t, const gik::PrepPlan &p, gik::PrepArgs a, hipStream_t s) {
+  using namespace gik;
+  gik_template::Prepare &m = const_cast<gik_template *>(t)->prep;   // the workspace hand-over is the mutable part
+  std::unique_lock<std::mutex> lock(m.mutex, std::defer_lock);
+  if (p.block()) {
+    lock.lock();
+    if (m.pending) HIP_OK(hipStreamWaitEvent(s, m.done, 0));
+  }
+  void *args[] = {&a, &m.ws};      // (the wavefront kernels take the first only)
+  (void)hipLaunchKernel(prep_kernel(p.variant), dim3(p.launch_grid(a.B)), dim3(p.threads()), args, p.lds, s);
+  if (p.block()) {
+    HIP_OK(hipEventRecord(m.done, s));
+    m.pending = true;
+  }
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
 int gik_prepare_batch_debug(const gik_template *t, const double *d_T_goal, int B, double *d_targets,
                             double *d_Y_init, int32_t *d_K_out, const gik_prepare_diag *diag,
                             void *stream) {
@@ -1282,7 +1308,7 @@ int gik_prepare_batch_debug(const gik_template *t, const double *d_T_goal, int B
   if (!t->has_pipe) return fail("no pipeline attached (gik_pipeline_attach)");
   if (B == 0) return 0;
   if (!d_T_goal || !d_targets || !d_Y_init) return fail("null buffer");
-  if (t->prep_block && refuse_capture("gik_prepare_batch", stream)) return -1;      // (the workgroup variant chains its launches by an event)
+  if (t->prep.plan.block() && refuse_capture("gik_prepare_batch", stream)) return -1;      // (the block variants chain their launches by an event)
   PrepArgs a;
   a.pc = t->pc;
   a.T_goal = d_T_goal;
@@ -1294,38 +1320,14 @@ int gik_prepare_batch_debug(const gik_template *t, const double *d_T_goal, int B
   a.dbg_eig = diag ? diag->d_eig : nullptr;
   if ((a.dbg_lb == nullptr) != (a.dbg_ub == nullptr)) return fail("d_lb and d_ub go together");
   a.B = B;
-  a.sweeps = t->sweeps;
+  a.sweeps = t->prep.sweeps;
   a.stop_phase = 0;
-  a.no_compress = t->prep_no_compress ? 1 : 0;
+  a.no_compress = t->prep.plan.no_compress ? 1 : 0;
 #ifdef GIK_DEV
   if (const char *e = getenv("GIK_PREP_STOP")) a.stop_phase = atoi(e);   // developer build: timing of the phases
 #endif
-  const int grid = std::min(B, t->f.n_cu * t->prep_waves_per_cu);
-  if (t->prep_block) {
-    gik_template *mt = const_cast<gik_template *>(t);   // the workspace hand-over is the mutable part
-    std::lock_guard<std::mutex> lock(mt->prep_mutex);
-    if (mt->prep_pending) HIP_OK(hipStreamWaitEvent((hipStream_t)stream, mt->prep_done, 0));
-    if (t->prep_big)
-      hipLaunchKernelGGL((prep_block_kernel<false, PREP_BIGN>), dim3(grid), dim3(PREP_NT), 0, (hipStream_t)stream, a,
-                         t->prep_ws);
-    else if (t->prep_a_lds)
-      hipLaunchKernelGGL(prep_block_kernel<true>, dim3(grid), dim3(PREP_NT),
-                         sizeof(double) * (size_t)t->N * t->N, (hipStream_t)stream, a, t->prep_ws);
-    else
-      hipLaunchKernelGGL(prep_block_kernel<false>, dim3(grid), dim3(PREP_NT), 0, (hipStream_t)stream, a,
-                         t->prep_ws);
-    HIP_OK(hipEventRecord(mt->prep_done, (hipStream_t)stream));
-    mt->prep_pending = true;
-  } else if (t->prep_quad && !a.dbg_lb && !a.dbg_eig) {
-    // (the diagnostics -- bounds and spectra of gik_prepare_batch_debug -- come from the one-goal-per-wavefront kernel)
-    const int qgrid = std::min((B + QUAD_SLOTS - 1) / QUAD_SLOTS, t->f.n_cu * t->prep_quad_waves_per_cu);
-    hipLaunchKernelGGL(t->N == 13 ? prep_quad_kernel<13> : prep_quad_kernel<0>, dim3(qgrid), dim3(WAVE), t->prep_quad_smem,
-                       (hipStream_t)stream, a);
-  } else
-    hipLaunchKernelGGL(prep_wave_kernel, dim3(grid), dim3(WAVE), t->prep_smem, (hipStream_t)stream,
-                       a);
-  HIP_OK(hipGetLastError());
-  return 0;
+  // (the diagnostics -- bounds and spectra -- come from the one-goal-per-wavefront kernel)
+  return launch_prepare(t, (a.dbg_lb || a.dbg_eig) ? t->prep.plan.diagnostics() : t->prep.plan, a, (hipStream_t)stream);
 }
 
 int gik_recover_batch(const gik_template *t, const double *d_Y, const double *d_T_goal, int B,
@@ -1449,7 +1451,7 @@ int gik_retry_seeds(const gik_template *t, const double *d_T_goal, const int32_t
   if (count == 0) return 0;
   if (!d_T_goal || !d_idx || !d_T_out || !d_q_out) return fail("null buffer");
   const RetrySeedArgs a = {d_T_goal, d_idx, d_q_lo, d_q_hi, nullptr, d_T_out, d_q_out, 0.0, seed,
-                           count, t->pc.n_ee * (t->f.K + 1) * (t->f.K + 1), t->pc.n_joints, attempt};
+                           count, pose_width(t), t->pc.n_joints, attempt};
   return retry_seed_launch(t, a, stream);
 }
 
@@ -1481,7 +1483,7 @@ struct RetryWs {
   size_t bytes;
 };
 static RetryWs retry_ws(const gik_template *t, int B, void *base) {
-  const size_t b = (size_t)B, n = (size_t)t->pc.n_joints, pose_w = (size_t)t->pc.n_ee * (t->f.K + 1) * (t->f.K + 1);
+  const size_t b = (size_t)B, n = (size_t)t->pc.n_joints, pose_w = (size_t)pose_width(t);
   WsCarve c = {reinterpret_cast<uintptr_t>(base), 0};
   RetryWs w;
   w.count = c.take<int32_t>(2);
@@ -1559,9 +1561,14 @@ int gik_ik_batch_retry(const gik_template *t, const double *d_T_goal, const doub
   return 0;
 }
 
+// the scratch of one anchored call over d_ws (gik_plan.h), or with a null d_ws its size
+static gik::AnchWs anch_ws(const gik_template *anch, const gik_template *base, int B, double *d_ws) {
+  return gik::anch_ws(base->T, base->N, anch->N, anch->an.n_goal, B, d_ws);
+}
+
 size_t gik_anchored_ws_doubles(const gik_template *anch, const gik_template *base, int B) {
   if (!anch || !base || !anch->anchored || B < 0) return 0;
-  return (size_t)B * ((size_t)base->T + (size_t)base->N * 3 + (size_t)anch->N * 3 + (size_t)anch->an.n_goal * 3);
+  return anch_ws(anch, base, B, nullptr).doubles;
 }
 
 // the arguments of the glue kernels between the robot-graph pipeline and the anchored solve
@@ -1649,14 +1656,11 @@ int gik_anchored_ik_batch(const gik_template *anch, const gik_template *base, co
   if (const std::string why = anchored_pair_fault(anch, base, PAIR_3D); !why.empty()) return fail("gik_anchored_ik_batch: " + why);
   if (B == 0) return 0;
   if (!d_T_goal || !d_ws || !d_Y_full || !d_stats || !d_q || !d_pos_err || !d_rot_err) return fail("null buffer");
-  double *tg_base = d_ws;
-  double *Y_full0 = tg_base + (size_t)B * base->T;
-  double *Y_free = Y_full0 + (size_t)B * base->N * 3;
-  double *goal = Y_free + (size_t)B * anch->N * 3;
+  const AnchWs w = anch_ws(anch, base, B, d_ws);
   // initial point of the robot graph (bound smoothing + MDS, obstacles play no part in it) ...
-  int rc = gik_prepare_batch(base, d_T_goal, B, tg_base, Y_full0, nullptr, stream);
+  int rc = gik_prepare_batch(base, d_T_goal, B, w.targets, w.Y_full0, nullptr, stream);
   if (rc) return rc;
-  const AnchGlueArgs g = anch_glue_args(anch, d_T_goal, B, Y_full0, Y_free, goal, d_Y_full);
+  const AnchGlueArgs g = anch_glue_args(anch, d_T_goal, B, w.Y_full0, w.Y_free, w.goal, d_Y_full);
   // ... mapped onto the world frame by its anchors; free rows = anchored start point
   hipLaunchKernelGGL(anch_init_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, g);
   HIP_OK(hipGetLastError());
@@ -1680,11 +1684,10 @@ static int anchored_seed_refusal(const char *entry, const gik_template *anch, co
 static int anchored_seed_launch(const gik_template *anch, const gik_template *base, const double *d_T_goal,
                                 const double *d_q_init, int B, double *d_ws, double *Y_free, double *goal, void *stream) {
   using namespace gik;
-  double *tg_base = d_ws;
-  double *Y_full0 = tg_base + (size_t)B * base->T;
-  const int rc = gik_seed_batch(base, d_T_goal, d_q_init, B, tg_base, Y_full0, stream);
+  const AnchWs w = anch_ws(anch, base, B, d_ws);      // (its head: Y_free and goal may be the caller's own arrays)
+  const int rc = gik_seed_batch(base, d_T_goal, d_q_init, B, w.targets, w.Y_full0, stream);
   if (rc) return rc;
-  const AnchGlueArgs g = anch_glue_args(anch, d_T_goal, B, Y_full0, Y_free, goal, nullptr);
+  const AnchGlueArgs g = anch_glue_args(anch, d_T_goal, B, w.Y_full0, Y_free, goal, nullptr);
   const size_t n = (size_t)B * ((size_t)g.Nf + (size_t)g.n_goal) * 3;
   hipLaunchKernelGGL(anch_scatter_kernel, dim3((unsigned)((n + ANCH_SCATTER_NT - 1) / ANCH_SCATTER_NT)), dim3(ANCH_SCATTER_NT),
                      0, (hipStream_t)stream, g);
@@ -1849,7 +1852,7 @@ struct AnchSweepWs {
 };
 static AnchSweepWs anch_sweep_ws(const gik_template *anch, const gik_template *base, int B, int S, double *ws) {
   const size_t M = (size_t)B * ((size_t)S + 1), n = (size_t)base->pc.n_joints;
-  const size_t pose_w = (size_t)base->pc.n_ee * (base->f.K + 1) * (base->f.K + 1);
+  const size_t pose_w = (size_t)pose_width(base);
   WsCarve c = {reinterpret_cast<uintptr_t>(ws), 0};
   AnchSweepWs w;
   w.q = c.take<double>(M * n);
@@ -1892,7 +1895,7 @@ int gik_anchored_sweep_clearance(const gik_template *anch, const gik_template *b
   ia.n = base->pc.n_joints;
   ia.S = samples;
   ia.D = base->f.K + 1;
-  ia.pose_w = base->pc.n_ee * ia.D * ia.D;
+  ia.pose_w = pose_width(base);
   const size_t nt = (size_t)M * ((size_t)ia.n + (size_t)ia.pose_w);
   if ((nt + ANCH_SCATTER_NT - 1) / ANCH_SCATTER_NT > (size_t)INT_MAX) return fail(e + ": the batch is too large");
   hipLaunchKernelGGL(anch_sweep_interp_kernel, dim3((unsigned)((nt + ANCH_SCATTER_NT - 1) / ANCH_SCATTER_NT)),
@@ -1922,13 +1925,12 @@ int gik_anchored_ik_batch_seeded(const gik_template *anch, const gik_template *b
   if (B == 0) return 0;
   if (!d_T_goal || !d_ws || !d_Y_full || !d_stats || !d_q || !d_pos_err || !d_rot_err)
     return fail("gik_anchored_ik_batch_seeded: null buffer");
-  double *Y_free = d_ws + (size_t)B * base->T + (size_t)B * base->N * 3;      // (the cold call's workspace layout)
-  double *goal = Y_free + (size_t)B * anch->N * 3;
+  const AnchWs w = anch_ws(anch, base, B, d_ws);
   // the seed angles are read here and nowhere later: d_q_init may be d_q
-  int rc = anchored_seed_launch(anch, base, d_T_goal, d_q_init, B, d_ws, Y_free, goal, stream);
+  int rc = anchored_seed_launch(anch, base, d_T_goal, d_q_init, B, d_ws, w.Y_free, w.goal, stream);
   if (rc) return rc;
-  return anchored_solve_tail(anch, base, anch_glue_args(anch, d_T_goal, B, nullptr, Y_free, goal, d_Y_full), d_stats, d_q, d_pos_err,
-                             d_rot_err, d_clearance, stream);
+  return anchored_solve_tail(anch, base, anch_glue_args(anch, d_T_goal, B, nullptr, w.Y_free, w.goal, d_Y_full), d_stats, d_q,
+                             d_pos_err, d_rot_err, d_clearance, stream);
 }
 
 // ---- restarts in the anchored solve: the kernels of gik_retry.hip.h with a clearance in the rule -------------
@@ -1958,7 +1960,7 @@ int gik_anchored_retry_seeds(const gik_template *base, const double *d_T_goal, c
   if (count == 0) return 0;
   if (!d_T_goal || !d_idx || !d_T_out || !d_q_out) return fail("gik_anchored_retry_seeds: null buffer");
   const RetrySeedArgs a = {d_T_goal, d_idx, d_q_lo, d_q_hi, d_q_center, d_T_out, d_q_out, spread, seed,
-                           count, base->pc.n_ee * (base->f.K + 1) * (base->f.K + 1), base->pc.n_joints, attempt};
+                           count, pose_width(base), base->pc.n_joints, attempt};
   return retry_seed_launch(base, a, stream);
 }
 
@@ -1995,7 +1997,7 @@ struct AnchRetryWs {
   size_t bytes;
 };
 static AnchRetryWs anch_retry_ws(const gik_template *anch, const gik_template *base, int B, void *ws) {
-  const size_t b = (size_t)B, n = (size_t)base->pc.n_joints, pose_w = (size_t)base->pc.n_ee * (base->f.K + 1) * (base->f.K + 1);
+  const size_t b = (size_t)B, n = (size_t)base->pc.n_joints, pose_w = (size_t)pose_width(base);
   WsCarve c = {reinterpret_cast<uintptr_t>(ws), 0};
   AnchRetryWs w;
   w.scratch = c.take<double>(gik_anchored_ws_doubles(anch, base, B));
@@ -2448,9 +2450,9 @@ int gik_template_get_info(const gik_template *t, gik_template_info *info) {
   info->hessian_form = (t->hess_per_edge || t->f.is_block) ? GIK_HESS_PER_EDGE : GIK_HESS_COLUMN;
   info->anchored = t->anchored ? (t->link_hinges ? 3 : 1) : 0;
   info->has_pipeline = t->has_pipe ? 1 : 0;
-  info->prepare_is_block = t->prep_block ? 1 : 0;
+  info->prepare_is_block = t->prep.plan.block() ? 1 : 0;
   info->node_per_lane = t->f.is_npt ? t->npt_variant->NW : 0;
-  info->goals_per_wave = !t->has_pipe || t->prep_block ? 0 : (t->prep_quad ? gik::QUAD_SLOTS : 1);
+  info->goals_per_wave = !t->has_pipe || t->prep.plan.block() ? 0 : (t->prep.plan.quad() ? gik::QUAD_SLOTS : 1);
   info->claim_key_terms = t->f.claim_terms;
   info->problems_per_wave = t->f.is_block ? 0 : ((t->quad_solve && !(t->f.dbg & (1 | 8192))) ? gik::QUAD_SLOTS : 1);
   if (t->f.is_npt) {

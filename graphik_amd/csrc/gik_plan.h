@@ -1,11 +1,14 @@
 // graphik_amd/csrc/gik_plan.h -- the scheduling decisions of one batch call (gik_solve_batch): which kernel runs,
 // its grid, the time slice, whether the tail is spread, the queue capacities and the layout of the pooled workspace.
-// Integer arithmetic over facts that are fixed at template creation, plus the batch size: plain C++17, no HIP, so
-// that tests/host/solve_plan_table.cpp can tabulate it without a device.
+// Below it the same for the device prepare (gik_pipeline_attach: which of the six prepare kernels, its LDS bytes, waves per
+// CU, slab and grids) and the layout of the anchored calls' scratch.
+// Integer arithmetic over facts that are fixed at template creation or at attach, plus the batch size: plain C++17, no
+// HIP, so that tests/host/solve_plan_table.cpp and prep_plan_table.cpp can tabulate it without a device.
 #pragma once
 
 #include <algorithm>
 #include <cstddef>
+#include <cstdint>
 
 namespace gik {
 
@@ -181,6 +184,156 @@ inline SolvePlan plan_solve(const SolveFacts &t, int B) {
     p.launch = mig ? Launch::WAVE_SPREAD : Launch::WAVE;
   }
   return p;
+}
+
+// ---- the device prepare (gik_pipeline_attach, gik_prepare_batch): which of the six prepare kernels a template runs, its
+// dynamic LDS bytes, resident waves per CU, slab and grids.  Decided once, at attach.
+constexpr int PLAN_PREP_MAXN = 128;          // nodes of the workgroup kernels' small LDS arrays (PREP_MAXN) ...
+constexpr int PLAN_PREP_BIGN = 256;          // ... and of the build for 129 .. 255 nodes (PREP_BIGN)
+constexpr int PLAN_PREPQ_MAXN = 16;          // nodes of a goal of the quad kernel (PREPQ_MAXN)
+constexpr int PLAN_PREPQ_VEC_STRIDE = 104;   // doubles of a goal slot's small arrays (PREPQ_VEC_STRIDE)
+constexpr int PLAN_PREP_NT = 512;            // threads of a workgroup kernel (PREP_NT)
+constexpr int PLAN_WAVE = 64;
+
+// prep_quad_lds_bytes of gik_prep_quad.hip.h (tests/golden/prep_plan.json pins the two equal)
+constexpr size_t plan_prep_quad_lds_bytes(int N, int n_gd) {
+  const int NS = N * (N | 1), stride = NS + ((16 - NS % 32) + 32) % 32;
+  return sizeof(double) * ((size_t)12 * stride + 4 * (size_t)((n_gd + 1) & ~1) + 4 * PLAN_PREPQ_VEC_STRIDE);
+}
+
+// What plan_prepare reads: the graph and the pipeline descriptor, and the developer switches of the environment, which
+// gik_pipeline_attach reads once.
+struct PrepFacts {
+  int N = 0, K = 0;      // (no rule reads K: the 2-D and the 3-D pipeline plan alike)
+  int n_anchor = 0, n_ee = 1, n_gg = 0;
+  bool inert_goal_slot = false;       // an ee_goal_nodes entry of -1 (prep_wave_kernel skips it, the quad kernel cannot)
+  bool force_block_prepare = false;   // gik_pipeline_desc::force_block_prepare
+  bool env_force_block = false;       // GIK_PREP_FORCE_BLOCK
+  bool env_no_compress = false;       // GIK_PREP_NO_COMPRESS
+  bool env_a_global = false;          // GIK_PREP_A_GLOBAL
+  bool env_no_quad = false;           // GIK_NO_PREP_QUAD
+  bool env_waves_set = false;         // GIK_PREP_WAVES_PER_CU ...
+  int env_waves = 0;                  // ... and its atoi
+  int n_cu = 0;
+};
+
+// QUAD13 / QUAD: prep_quad_kernel<13> / <0>; WAVE: prep_wave_kernel; BLOCK_LDS / BLOCK / BLOCK_BIG: prep_block_kernel<true> /
+// <false> / <false, PREP_BIGN>
+enum class Prep { QUAD13, QUAD, WAVE, BLOCK_LDS, BLOCK, BLOCK_BIG };
+
+struct PrepPlan {
+  Prep variant = Prep::WAVE;
+  size_t lds = 0;       // dynamic LDS bytes of its launch
+  int wpc = 8;          // resident prepare waves (workgroups on the block variants) per CU
+  // prep_wave_kernel: a quad template runs the diagnostics of gik_prepare_batch_debug on it (WAVE: lds and wpc again)
+  size_t wave_lds = 0;
+  int wave_wpc = 8;
+  bool no_compress = false;   // block variants: full N x N Jacobi even where the Gram matrix is rank deficient
+  size_t slab_bytes = 0;      // block variants: [n_cu * wpc][5 (BLOCK_BIG: 6)][N * N] doubles of global workspace
+  int n_cu = 0;
+  bool block() const { return variant >= Prep::BLOCK_LDS; }
+  bool quad() const { return variant <= Prep::QUAD; }
+  int threads() const { return block() ? PLAN_PREP_NT : PLAN_WAVE; }
+  int launch_grid(int B) const {
+    return std::min(quad() ? (B + PLAN_QUAD_SLOTS - 1) / PLAN_QUAD_SLOTS : B, n_cu * wpc);
+  }
+  // the plan of a launch with diagnostics (gik_prepare_batch_debug): the quad kernel has none, prep_wave_kernel runs instead
+  PrepPlan diagnostics() const {
+    PrepPlan p = *this;
+    if (quad()) {
+      p.variant = Prep::WAVE;
+      p.lds = wave_lds;
+      p.wpc = wave_wpc;
+    }
+    return p;
+  }
+};
+
+// occupancy(variant, threads, lds): resident workgroups of that kernel per CU, below 0 where the query failed.  For
+// BLOCK_LDS it raises the kernel's LDS allowance first, and a refusal there is a failed query too.
+template <typename Occupancy>
+inline PrepPlan plan_prepare(const PrepFacts &f, Occupancy occupancy) {
+  PrepPlan p;
+  const size_t NN = (size_t)f.N * f.N;
+  const int N = f.N, n_gd = 2 * f.n_ee * f.n_anchor + f.n_gg;
+  p.n_cu = f.n_cu;
+  p.no_compress = f.env_no_compress;
+  p.wave_lds = sizeof(double) * ((size_t)5 * N * N + n_gd + 96) +
+               sizeof(int) * (48 + (size_t)((N + 1) / 2) * ((N | 1) + (N + 1) / 2 + 1));   // (+ jacobi_lds's pair tables)
+  // graphs beyond one wavefront's LDS: workgroup-per-goal kernel with its matrices in a global slab
+  if (N > 32 || f.n_anchor > 32 || f.force_block_prepare || f.env_force_block) {
+    int occ = 0;
+    if (N > PLAN_PREP_MAXN) {      // graphs of 129 .. 255 nodes: six matrices per slab
+      p.variant = Prep::BLOCK_BIG;
+      if ((occ = occupancy(p.variant, PLAN_PREP_NT, p.lds)) < 0) occ = 1;
+    } else {
+      // work matrix in LDS when it fits next to the kernel's static arrays (N <= 123), one workgroup per CU
+      p.variant = Prep::BLOCK_LDS;
+      p.lds = sizeof(double) * NN;
+      if (f.env_a_global || (occ = occupancy(p.variant, PLAN_PREP_NT, p.lds)) < 1) {
+        p.variant = Prep::BLOCK;
+        p.lds = 0;
+        if ((occ = occupancy(p.variant, PLAN_PREP_NT, p.lds)) < 0) occ = 1;
+      }
+    }
+    occ = std::max(1, std::min(occ, 2));   // 5 N^2 doubles per workgroup: keep the slabs cache-resident
+    if (f.env_waves_set) occ = std::max(1, f.env_waves);
+    p.wpc = occ;
+    p.slab_bytes = sizeof(double) * (p.variant == Prep::BLOCK_BIG ? 6 : 5) * NN * (size_t)f.n_cu * occ;
+    return p;
+  }
+  // the prepare kernel is latency-bound (dependent Jacobi chains, LDS round trips): run as many
+  // resident waves per CU as its registers and LDS allow (a fixed 8 per CU left half of them
+  // unused: planar-10 prepare 2.3 -> see NOTEBOOK 4.2)
+  int occ = occupancy(Prep::WAVE, PLAN_WAVE, p.wave_lds);
+  if (occ < 0) occ = 8;
+  if (f.env_waves_set) occ = f.env_waves;   // developer override
+  p.lds = p.wave_lds;
+  p.wpc = p.wave_wpc = std::max(1, std::min(occ, 32));
+  if (N <= PLAN_PREPQ_MAXN && !f.inert_goal_slot && !f.env_no_quad) {
+    const Prep quad = N == 13 ? Prep::QUAD13 : Prep::QUAD;
+    const size_t quad_lds = plan_prep_quad_lds_bytes(N, n_gd);
+    int qocc = 0;
+    if (quad_lds <= 40 * 1024 && (qocc = occupancy(quad, PLAN_WAVE, quad_lds)) >= 1) {
+      if (f.env_waves_set) qocc = f.env_waves;
+      p.variant = quad;
+      p.lds = quad_lds;
+      p.wpc = std::max(1, std::min(qocc, 32));
+    }
+  }
+  return p;
+}
+
+// ---- caller-owned workspaces
+// Carves a caller-owned workspace into arrays, each padded to 8 bytes.  A null base only adds up the size.
+struct WsCarve {
+  uintptr_t base;
+  size_t off;
+  template <typename T>
+  T *take(size_t n) {
+    T *at = reinterpret_cast<T *>(base + off);
+    off += (n * sizeof(T) + 7) / 8 * 8;
+    return at;
+  }
+};
+
+// The scratch of one anchored call (gik_anchored_ws_doubles), B goals: what the robot graph's prepare or seed kernel
+// writes, then the start point and the goal anchors of the fixed-anchor solve
+//   targets [B][T_base] | Y_full0 [B][N_base * 3] | Y_free [B][N_free * 3] | goal [B][n_goal * 3]
+struct AnchWs {
+  double *targets, *Y_full0, *Y_free, *goal;
+  size_t doubles;
+};
+inline AnchWs anch_ws(int base_T, int base_N, int free_N, int n_goal, int B, double *ws) {
+  const size_t b = (size_t)B;
+  WsCarve c = {reinterpret_cast<uintptr_t>(ws), 0};
+  AnchWs w;
+  w.targets = c.take<double>(b * (size_t)base_T);
+  w.Y_full0 = c.take<double>(b * (size_t)base_N * 3);
+  w.Y_free = c.take<double>(b * (size_t)free_N * 3);
+  w.goal = c.take<double>(b * (size_t)n_goal * 3);
+  w.doubles = c.off / sizeof(double);
+  return w;
 }
 
 }  // namespace gik
