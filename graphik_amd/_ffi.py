@@ -122,6 +122,15 @@ class LinkDesc(C.Structure):
                 ("link_b", C.POINTER(C.c_int32)), ("link_radius", C.POINTER(C.c_double))]
 
 
+class SceneSet(C.Structure):
+    """gik_scene_set: per-goal obstacle scenes of the anchored solve, device pointers"""
+    _fields_ = [("n_scene", C.c_int32), ("stride", C.c_int32), ("d_obs", C.c_void_p), ("d_n_obs", C.c_void_p),
+                ("d_scene_id", C.c_void_p)]
+
+
+SCENE_MAX_SPHERES = 128
+
+
 class PrepareDiag(C.Structure):
     _fields_ = [("d_lb", C.c_void_p), ("d_ub", C.c_void_p), ("d_eig", C.c_void_p)]
 
@@ -159,6 +168,16 @@ SYMBOLS = {
     "gik_anchored_retry_ws_bytes": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_int]),
     "gik_anchored_ik_batch_retry": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                               C.POINTER(AnchoredRetryOpts)] + 8 * [C.c_void_p] + [C.c_void_p]),
+    "gik_solve_batch_scenes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.POINTER(Trace), C.POINTER(SceneSet), C.c_void_p]),
+    "gik_anchored_ik_batch_scenes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(SceneSet)] +
+                                     7 * [C.c_void_p] + [C.c_int, C.c_void_p]),
+    "gik_anchored_clearance_scenes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(SceneSet), C.c_void_p, C.c_void_p]),
+    "gik_anchored_link_clearance_scenes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(SceneSet), C.c_void_p,
+                                                     C.c_void_p]),
+    "gik_anchored_ik_batch_retry_scenes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                     C.POINTER(AnchoredRetryOpts), C.POINTER(SceneSet)] + 8 * [C.c_void_p] +
+                                           [C.c_void_p]),
     "gik_template_destroy": (None, [C.c_void_p]),
     "gik_template_get_info": (C.c_int, [C.c_void_p, C.POINTER(TemplateInfo)]),
     "gik_template_set_claim_key": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),

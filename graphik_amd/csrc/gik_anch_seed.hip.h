@@ -18,6 +18,8 @@
 //   anch_sweep_interp_kernel / anch_sweep_min_kernel : the ends of gik_anchored_sweep_clearance -- the S + 1 joint
 //                           configurations between q_a and q_b (and the identity poses seed_kernel is handed with
 //                           them), one thread per double; and the minimum over the samples, one thread per goal.
+//   anch_clearance_scene_kernel / anch_link_clearance_scene_kernel / scene_gather_kernel : the two clearance kernels with
+//                           the obstacle rows of a per-goal scene (gik_scene_set), and the scene ids of a compact batch.
 // anch_link_pair, anch_link_foot (the pair function of the solve kernel's link hinges), anch_sweep_interp and
 // anch_sweep_min are __host__ __device__, so that a host program can walk them.
 // Plain kernels, defined where GIK_DEFINE_ANCH_SEED_KERNELS is set (gik_k_anch_seed.hip); gik_host.hip sees prototypes.
@@ -26,6 +28,7 @@
 #include <hip/hip_runtime.h>
 
 #include "gik_prep.hip.h"
+#include "gik_scenes.h"
 
 namespace gik {
 
@@ -196,6 +199,82 @@ __global__ void __launch_bounds__(WAVE) anch_link_clearance_kernel(AnchLinkArgs 
     if (__any(nan)) m = __builtin_nan("");
     if (lane == 0) a.clearance[b] = m;
   }
+}
+#endif
+
+// ---- per-goal obstacle scenes (gik_scene_set) ----
+// The two clearance kernels above with the obstacle rows looked up per goal: a.obs is [n_scene][stride][4] and a.n_obs is
+// not read; goal b is measured against the first n_obs[s] rows of scene s = scene_id[b] (null: scene 0), id and count
+// clamped as the solve kernel clamps them (SceneArgs, gik_scenes.h).  The same pairs through the same expressions; a minimum does not depend on the
+// order of its terms.
+__device__ inline const double *anch_scene_rows(const SceneArgs &sc, const double *obs, int b, int &n) {
+  const int s = scene_clamp_id(sc.scene_id ? sc.scene_id[b] : 0, sc.n_scene);
+  n = scene_clamp_count(sc.n_obs[s], sc.stride);
+  return obs + (size_t)s * (size_t)sc.stride * 4;
+}
+
+__global__ void __launch_bounds__(WAVE) anch_clearance_scene_kernel(AnchClearArgs a, SceneArgs sc)
+#ifndef GIK_DEFINE_ANCH_SEED_KERNELS
+    ;
+#else
+{
+  const int lane = threadIdx.x;
+  for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
+    int n_obs;
+    const double *obs = anch_scene_rows(sc, a.obs, b, n_obs);
+    const int pairs = a.n_node * n_obs;
+    const double *Y = a.Y_full + (size_t)b * a.full_N * 3;
+    double m = __builtin_huge_val();
+    bool nan = false;
+    for (int p = lane; p < pairs; p += WAVE) {
+      const int i = p / n_obs, o = p - i * n_obs;
+      const double *y = Y + a.node_full[i] * 3, *s = obs + o * 4;
+      const double dx = y[0] - s[0], dy = y[1] - s[1], dz = y[2] - s[2];
+      const double v = sqrt(dx * dx + dy * dy + dz * dz) - sqrt(s[3]);
+      nan |= v != v;
+      m = fmin(m, v);
+    }
+    for (int off = WAVE / 2; off > 0; off >>= 1) m = fmin(m, __shfl_xor(m, off));
+    if (__any(nan)) m = __builtin_nan("");
+    if (lane == 0) a.clearance[b] = m;
+  }
+}
+#endif
+
+__global__ void __launch_bounds__(WAVE) anch_link_clearance_scene_kernel(AnchLinkArgs a, SceneArgs sc)
+#ifndef GIK_DEFINE_ANCH_SEED_KERNELS
+    ;
+#else
+{
+  const int lane = threadIdx.x;
+  for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
+    int n_obs;
+    const double *obs = anch_scene_rows(sc, a.obs, b, n_obs);
+    const int pairs = a.n_link * n_obs;
+    const double *Y = a.Y_full + (size_t)b * a.full_N * 3;
+    double m = __builtin_huge_val();
+    bool nan = false;
+    for (int p = lane; p < pairs; p += WAVE) {
+      const int l = p / n_obs, o = p - l * n_obs;
+      const double v = anch_link_pair(Y + a.link_a[l] * 3, Y + a.link_b[l] * 3, obs + o * 4, a.link_rho[l]);
+      nan |= v != v;
+      m = fmin(m, v);
+    }
+    for (int off = WAVE / 2; off > 0; off >>= 1) m = fmin(m, __shfl_xor(m, off));
+    if (__any(nan)) m = __builtin_nan("");
+    if (lane == 0) a.clearance[b] = m;
+  }
+}
+#endif
+
+// the scene ids of a restart's compact batch: out[r] = scene_id[idx[r]], one thread per slot
+__global__ void __launch_bounds__(ANCH_SCATTER_NT) scene_gather_kernel(const int *scene_id, const int *idx, int count, int *out)
+#ifndef GIK_DEFINE_ANCH_SEED_KERNELS
+    ;
+#else
+{
+  const int r = blockIdx.x * ANCH_SCATTER_NT + threadIdx.x;
+  if (r < count) out[r] = scene_id[idx[r]];
 }
 #endif
 

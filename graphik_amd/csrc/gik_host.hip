@@ -16,6 +16,7 @@
 namespace gik {
 GIK_ALL_KERNELS(GIK_EXTERN_TEMPLATE)
 GIK_KERNELS_ANCH_LINK(GIK_EXTERN_TEMPLATE)
+GIK_KERNELS_ANCH_SCENE(GIK_EXTERN_TEMPLATE)
 static_assert(PLAN_MIG_SIMDS == MIG_SIMDS && PLAN_SLICE_STATE_BYTES == sizeof(SliceState) && PLAN_QUAD_SLOTS == QUAD_SLOTS,
               "gik_plan.h restates these constants of the kernel headers");
 static_assert(PLAN_CLAIM_KEY_MAX_TERMS == CLAIM_KEY_MAX_TERMS, "gik_plan.h restates this constant of gik_order.hip.h");
@@ -55,6 +56,7 @@ static int fail(const std::string &m) {
   } while (0)
 
 typedef void (*solve_fn)(SolveArgs);
+typedef void (*scene_fn)(SolveArgs, SceneArgs);
 typedef void (*kat_fn)(KatArgs);
 typedef size_t (*lds_fn)(int);
 
@@ -69,6 +71,7 @@ struct WaveRow {
   solve_fn solve_theta = nullptr;   // any theta
   solve_fn solve_cg = nullptr;      // ConjugateGradient
   solve_fn solve_spread = nullptr;  // theta == 1 with tail spreading (MigCtl)
+  scene_fn solve_scene = nullptr;   // ANCHORED: the scene build of `solve` (gik_solve_batch_scenes)
   kat_fn kat = nullptr;
   lds_fn lds = nullptr;
 };
@@ -97,6 +100,7 @@ template <int K, int D>
 static WaveRow anchored_row() {
   WaveRow r{K, D, ANCHORED};
   r.solve = rtr_wave_kernel<K, D, true, true>;
+  r.solve_scene = rtr_wave_scene_kernel<D, false>;
   r.kat = kat_wave_kernel<K, D, true>;
   r.lds = WaveCtx<K, D, true>::lds_bytes;
   return r;
@@ -106,6 +110,7 @@ static WaveRow anchored_row() {
 static WaveRow anchored_link_row() {
   WaveRow r{3, 9, ANCHORED};
   r.solve = rtr_wave_kernel<3, 9, true, true, false, false, true>;
+  r.solve_scene = rtr_wave_scene_kernel<9, true>;
   r.kat = kat_wave_kernel<3, 9, true, false, true>;
   r.lds = WaveCtx<3, 9, true, false, true>::lds_bytes;
   return r;
@@ -158,6 +163,7 @@ struct gik_template {
   struct Kernels {
     void (*solve)(gik::SolveArgs) = nullptr;          // wavefront path: the solve kernel ...
     void (*solve_spread)(gik::SolveArgs) = nullptr;   // ... its tail-spreading build, or null: none compiled for this solver / theta / form
+    void (*solve_scene)(gik::SolveArgs, gik::SceneArgs) = nullptr;   // ... its scene build (anchored templates), same LDS bytes
     void (*kat)(gik::KatArgs) = nullptr;              // ... and the known-answer kernel
     void (*block_solve)(gik::SolveArgs, int) = nullptr;   // workgroup path
     void (*block_kat)(gik::KatArgs, int) = nullptr;
@@ -392,6 +398,7 @@ static int resolve_kernels(gik_template *t, const gik_template_desc *d, const Wa
   const WaveRow *r = t->hess_per_edge ? pe : row;
   kn.solve = cg ? r->solve_cg : (theta1 ? r->solve : r->solve_theta);
   kn.solve_spread = (cg || !theta1) ? nullptr : r->solve_spread;
+  kn.solve_scene = r->solve_scene;
   kn.kat = r->kat;
   // occupancy: of the build large batches run -- the small-batch build trades registers for latency, gik_rtr.hip.h SPLIT.  (Per-edge
   // form: the tail-spreading build where there is one; column form: always the theta == 1 build.  The grids were tuned on these.)
@@ -1194,27 +1201,57 @@ static std::string anchored_pair_fault(const gik_template *anch, const gik_templ
   return std::string();
 }
 
+// What is wrong with the scene set of a scene call on `t`, as a refusal with the entry's name, or 0 (gik_scenes.h holds
+// the host-checkable part; the contents of d_n_obs and d_scene_id are the caller's precondition)
+static int scene_refusal(const char *entry, const gik_template *t, const gik_scene_set *sc) {
+  using gik::fail;
+  const std::string e(entry);
+  if (!t->anchored || !t->kernels.solve_scene)
+    return fail(e + ": the handle must be a fixed-anchor template (gik_template_create_anchored): scenes replace its obstacles");
+  if (!sc) return fail(e + ": null scene set");
+  if (const char *why = gik::scene_set_fault(sc->n_scene, sc->stride, sc->d_obs, sc->d_n_obs, sc->d_scene_id))
+    return fail(e + ": " + why);
+  return 0;
+}
+static gik::SceneArgs scene_args(const gik_scene_set *sc) {
+  gik::SceneArgs a;
+  a.scene_id = sc->d_scene_id;
+  a.n_obs = sc->d_n_obs;
+  a.n_scene = sc->n_scene;
+  a.stride = sc->stride;
+  return a;
+}
+
+// (scenes: a checked scene set, or null: the template's own obstacles)
 static int anchored_clearance_launch(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance,
-                                     void *stream) {
+                                     void *stream, const gik_scene_set *scenes = nullptr) {
   using namespace gik;
   AnchClearArgs c;
   c.Y_full = d_Y_full;
-  c.obs = anch->an.obs;
+  c.obs = scenes ? scenes->d_obs : anch->an.obs;
   c.node_full = anch->d_clear_full;
   c.clearance = d_clearance;
   c.B = B;
   c.full_N = anch->full_N;
   c.n_node = anch->n_clear;
-  c.n_obs = anch->an.n_obs;
-  hipLaunchKernelGGL(anch_clearance_kernel, dim3(std::min(B, anch->f.n_cu * 32)), dim3(WAVE), 0, (hipStream_t)stream, c);
+  c.n_obs = scenes ? 0 : anch->an.n_obs;
+  const dim3 grid(std::min(B, anch->f.n_cu * 32));
+  if (scenes)
+    hipLaunchKernelGGL(anch_clearance_scene_kernel, grid, dim3(WAVE), 0, (hipStream_t)stream, c, scene_args(scenes));
+  else
+    hipLaunchKernelGGL(anch_clearance_kernel, grid, dim3(WAVE), 0, (hipStream_t)stream, c);
   HIP_OK(hipGetLastError());
   return 0;
 }
+static int anchored_link_clearance_launch(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance,
+                                          void *stream, const gik_scene_set *scenes = nullptr);
 
 // The end of the cold and the seeded anchored call: the solve from g.Y_free between the event pair of
-// gik_anchored_last_solve_ms, the gather into g.Y_full_out, the recovery and, where d_clearance is given, the node clearance.
+// gik_anchored_last_solve_ms, the gather into g.Y_full_out, the recovery and, where d_clearance is given, the clearance: of the
+// masked nodes, or with link_clear of whole links.  scenes: a checked scene set for the solve and the clearance, or null.
 static int anchored_solve_tail(const gik_template *anch, const gik_template *base, const gik::AnchGlueArgs &g, gik_stats *d_stats,
-                               double *d_q, double *d_pos_err, double *d_rot_err, double *d_clearance, void *stream) {
+                               double *d_q, double *d_pos_err, double *d_rot_err, double *d_clearance, void *stream,
+                               const gik_scene_set *scenes = nullptr, bool link_clear = false) {
   using namespace gik;
   // timing events around the solve (diagnostics only; created with the handle).  The pair is
   // recorded under a lock so that gik_anchored_last_solve_ms never reads a half-recorded pair;
@@ -1224,7 +1261,8 @@ static int anchored_solve_tail(const gik_template *anch, const gik_template *bas
     std::lock_guard<std::mutex> lock(ma->ev_mutex);
     (void)hipEventRecord(ma->ev_solve0, (hipStream_t)stream);
   }
-  int rc = gik_solve_batch(anch, g.Y_free, g.anchor_goal, g.B, g.Y_free, d_stats, nullptr, stream);     // (not under ev_mutex:
+  int rc = scenes ? gik_solve_batch_scenes(anch, g.Y_free, g.anchor_goal, g.B, g.Y_free, d_stats, nullptr, scenes, stream)
+                  : gik_solve_batch(anch, g.Y_free, g.anchor_goal, g.B, g.Y_free, d_stats, nullptr, stream);     // (not under ev_mutex:
   if (rc) return rc;                                                                                   // other threads launch meanwhile)
   {
     std::lock_guard<std::mutex> lock(ma->ev_mutex);
@@ -1234,8 +1272,16 @@ static int anchored_solve_tail(const gik_template *anch, const gik_template *bas
   HIP_OK(hipGetLastError());
   rc = gik_recover_batch(base, g.Y_full_out, g.T_goal, g.B, d_q, d_pos_err, d_rot_err, stream);
   if (rc || !d_clearance) return rc;
-  return anchored_clearance_launch(anch, g.Y_full_out, g.B, d_clearance, stream);
+  return link_clear ? anchored_link_clearance_launch(anch, g.Y_full_out, g.B, d_clearance, stream, scenes)
+                    : anchored_clearance_launch(anch, g.Y_full_out, g.B, d_clearance, stream, scenes);
 }
+
+// One anchored solve on checked arguments, cold (d_q_init null: prepare + Procrustes fit) or seeded, with the clearance of
+// the answer where d_clearance is given; scenes as above.  What gik_anchored_ik_batch / _seeded queue, through one door:
+// the restart loop and the scene entry use it.
+static int anchored_attempt(const gik_template *anch, const gik_template *base, const double *d_T_goal, const double *d_q_init,
+                            int B, const gik_scene_set *scenes, double *d_ws, double *d_Y_full, gik_stats *d_stats, double *d_q,
+                            double *d_pos_err, double *d_rot_err, double *d_clearance, bool link_clear, void *stream);
 
 int gik_anchored_ik_batch(const gik_template *anch, const gik_template *base, const double *d_T_goal, int B,
                           double *d_ws, double *d_Y_full, gik_stats *d_stats, double *d_q,
@@ -1340,6 +1386,7 @@ int gik_anchored_attach_links(gik_template *anch, const gik_link_desc *d) {
       return fail(e + ": device upload failed");
     anch->an.link_rec = dr;
     anch->kernels.solve = row.solve;
+    anch->kernels.solve_scene = row.solve_scene;
     anch->kernels.kat = row.kat;
     anch->kernels.occupancy = (const void *)row.solve;
     anch->smem_bytes = row.lds(anch->T);
@@ -1351,11 +1398,11 @@ int gik_anchored_attach_links(gik_template *anch, const gik_link_desc *d) {
 }
 
 static int anchored_link_clearance_launch(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance,
-                                          void *stream) {
+                                          void *stream, const gik_scene_set *scenes) {
   using namespace gik;
   AnchLinkArgs c;
   c.Y_full = d_Y_full;
-  c.obs = anch->an.obs;
+  c.obs = scenes ? scenes->d_obs : anch->an.obs;
   c.link_a = anch->d_link_a;
   c.link_b = anch->d_link_b;
   c.link_rho = anch->d_link_rho;
@@ -1363,8 +1410,12 @@ static int anchored_link_clearance_launch(const gik_template *anch, const double
   c.B = B;
   c.full_N = anch->full_N;
   c.n_link = anch->n_link;
-  c.n_obs = anch->an.n_obs;
-  hipLaunchKernelGGL(anch_link_clearance_kernel, dim3(std::min(B, anch->f.n_cu * 32)), dim3(WAVE), 0, (hipStream_t)stream, c);
+  c.n_obs = scenes ? 0 : anch->an.n_obs;
+  const dim3 grid(std::min(B, anch->f.n_cu * 32));
+  if (scenes)
+    hipLaunchKernelGGL(anch_link_clearance_scene_kernel, grid, dim3(WAVE), 0, (hipStream_t)stream, c, scene_args(scenes));
+  else
+    hipLaunchKernelGGL(anch_link_clearance_kernel, grid, dim3(WAVE), 0, (hipStream_t)stream, c);
   HIP_OK(hipGetLastError());
   return 0;
 }
@@ -1378,6 +1429,30 @@ int gik_anchored_link_clearance(const gik_template *anch, const double *d_Y_full
   if (B == 0) return 0;
   if (!d_Y_full || !d_clearance) return fail("gik_anchored_link_clearance: null buffer");
   return anchored_link_clearance_launch(anch, d_Y_full, B, d_clearance, stream);
+}
+
+// ---- per-goal obstacle scenes: the two clearances (the solve: gik_solve_batch_scenes) ----
+int gik_anchored_clearance_scenes(const gik_template *anch, const double *d_Y_full, int B, const gik_scene_set *scenes,
+                                  double *d_clearance, void *stream) {
+  using gik::fail;
+  if (!anch || B < 0) return fail("gik_anchored_clearance_scenes: bad argument");
+  if (scene_refusal("gik_anchored_clearance_scenes", anch, scenes)) return -1;
+  if (refuse_capture("gik_anchored_clearance_scenes", stream)) return -1;
+  if (B == 0) return 0;
+  if (!d_Y_full || !d_clearance) return fail("gik_anchored_clearance_scenes: null buffer");
+  return anchored_clearance_launch(anch, d_Y_full, B, d_clearance, stream, scenes);
+}
+
+int gik_anchored_link_clearance_scenes(const gik_template *anch, const double *d_Y_full, int B, const gik_scene_set *scenes,
+                                       double *d_clearance, void *stream) {
+  using gik::fail;
+  if (!anch || B < 0) return fail("gik_anchored_link_clearance_scenes: bad argument");
+  if (scene_refusal("gik_anchored_link_clearance_scenes", anch, scenes)) return -1;
+  if (anch->n_link < 0) return fail("gik_anchored_link_clearance_scenes: no links attached (gik_anchored_attach_links)");
+  if (refuse_capture("gik_anchored_link_clearance_scenes", stream)) return -1;
+  if (B == 0) return 0;
+  if (!d_Y_full || !d_clearance) return fail("gik_anchored_link_clearance_scenes: null buffer");
+  return anchored_link_clearance_launch(anch, d_Y_full, B, d_clearance, stream, scenes);
 }
 
 // The caller-owned workspace of gik_anchored_sweep_clearance, M = B (S + 1) configurations, all doubles:
@@ -1470,6 +1545,47 @@ int gik_anchored_ik_batch_seeded(const gik_template *anch, const gik_template *b
                              d_pos_err, d_rot_err, d_clearance, stream);
 }
 
+static int anchored_attempt(const gik_template *anch, const gik_template *base, const double *d_T_goal, const double *d_q_init,
+                            int B, const gik_scene_set *scenes, double *d_ws, double *d_Y_full, gik_stats *d_stats, double *d_q,
+                            double *d_pos_err, double *d_rot_err, double *d_clearance, bool link_clear, void *stream) {
+  using namespace gik;
+  const AnchWs w = anch_ws(anch, base, B, d_ws);
+  AnchGlueArgs g;
+  if (d_q_init) {      // (read here and nowhere later: d_q_init may be d_q)
+    const int rc = anchored_seed_launch(anch, base, d_T_goal, d_q_init, B, d_ws, w.Y_free, w.goal, stream);
+    if (rc) return rc;
+    g = anch_glue_args(anch, d_T_goal, B, nullptr, w.Y_free, w.goal, d_Y_full);
+  } else {
+    const int rc = gik_prepare_batch(base, d_T_goal, B, w.targets, w.Y_full0, nullptr, stream);
+    if (rc) return rc;
+    g = anch_glue_args(anch, d_T_goal, B, w.Y_full0, w.Y_free, w.goal, d_Y_full);
+    hipLaunchKernelGGL(anch_init_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, g);
+    HIP_OK(hipGetLastError());
+  }
+  return anchored_solve_tail(anch, base, g, d_stats, d_q, d_pos_err, d_rot_err, d_clearance, stream, scenes, link_clear);
+}
+
+int gik_anchored_ik_batch_scenes(const gik_template *anch, const gik_template *base, const double *d_T_goal,
+                                 const double *d_q_init, int B, const gik_scene_set *scenes, double *d_ws, double *d_Y_full,
+                                 gik_stats *d_stats, double *d_q, double *d_pos_err, double *d_rot_err, double *d_clearance,
+                                 int clearance_mode, void *stream) {
+  using namespace gik;
+  const std::string e("gik_anchored_ik_batch_scenes");
+  if (!anch || !base || B < 0) return fail(e + ": bad argument");
+  if (const std::string why = anchored_pair_fault(anch, base, PAIR_3D | (d_q_init ? PAIR_SEEDABLE : 0)); !why.empty())
+    return fail(e + ": " + why);
+  if (scene_refusal("gik_anchored_ik_batch_scenes", anch, scenes)) return -1;
+  if (clearance_mode != GIK_CLEARANCE_NODES && clearance_mode != GIK_CLEARANCE_LINKS)
+    return fail(e + ": clearance_mode must be GIK_CLEARANCE_NODES (0) or GIK_CLEARANCE_LINKS (1)");
+  const bool links = clearance_mode == GIK_CLEARANCE_LINKS;
+  if (links && anch->n_link < 0) return fail(e + ": clearance_mode = links, but no links attached (gik_anchored_attach_links)");
+  if (refuse_capture("gik_anchored_ik_batch_scenes", stream)) return -1;
+  if (B == 0) return 0;
+  if (!d_T_goal || !d_ws || !d_Y_full || !d_stats || !d_q || !d_pos_err || !d_rot_err) return fail(e + ": null buffer");
+  return anchored_attempt(anch, base, d_T_goal, d_q_init, B, scenes, d_ws, d_Y_full, d_stats, d_q, d_pos_err, d_rot_err,
+                          d_clearance, links, stream);
+}
+
 // ---- restarts in the anchored solve: the kernels of gik_retry.hip.h with a clearance in the rule -------------
 int gik_anchored_retry_select(const gik_stats *d_stats, const double *d_pos_err, const double *d_rot_err,
                               const double *d_clearance, int B, double pos_tol, double rot_tol, double clear_tol,
@@ -1559,15 +1675,18 @@ size_t gik_anchored_retry_ws_bytes(const gik_template *anch, const gik_template 
   return gik::anch_retry_ws(anch, base, B, nullptr).bytes;
 }
 
-int gik_anchored_ik_batch_retry(const gik_template *anch, const gik_template *base, const double *d_T_goal,
-                                const double *d_q_init, int B, const gik_anchored_retry_opts *opts, void *d_ws,
-                                double *d_Y_full, gik_stats *d_stats, double *d_q, double *d_pos_err, double *d_rot_err,
-                                double *d_clearance, int32_t *d_attempt, void *stream) {
+// The restart loop of gik_anchored_ik_batch_retry and, with a scene set, of gik_anchored_ik_batch_retry_scenes: the scene
+// goes through attempt 0, every compact batch (ids gathered behind the workspace's plain layout) and every clearance.
+static int anchored_retry_impl(const char *entry, const gik_template *anch, const gik_template *base, const double *d_T_goal,
+                               const double *d_q_init, int B, const gik_anchored_retry_opts *opts, const gik_scene_set *scenes,
+                               bool with_scenes, void *d_ws, double *d_Y_full, gik_stats *d_stats, double *d_q, double *d_pos_err,
+                               double *d_rot_err, double *d_clearance, int32_t *d_attempt, void *stream) {
   using namespace gik;
-  const std::string e("gik_anchored_ik_batch_retry");
+  const std::string e(entry);
   // every refusal comes before anything is queued
   if (!anch || !base || B < 0 || !opts) return fail(e + ": bad argument");
   if (const std::string why = anchored_pair_fault(anch, base, PAIR_3D); !why.empty()) return fail(e + ": " + why);
+  if (with_scenes && scene_refusal(entry, anch, scenes)) return -1;
   if (opts->retries < 0 || opts->retries > 63) return fail(e + ": retries must be within 0 .. 63");
   if (opts->clearance_mode != GIK_CLEARANCE_NODES && opts->clearance_mode != GIK_CLEARANCE_LINKS)
     return fail(e + ": clearance_mode must be GIK_CLEARANCE_NODES (0) or GIK_CLEARANCE_LINKS (1)");
@@ -1584,7 +1703,7 @@ int gik_anchored_ik_batch_retry(const gik_template *anch, const gik_template *ba
     if (opts->spread > 0.0 && !d_q_init)
       return fail(e + ": spread > 0 needs d_q_init, the centre the seeds are drawn around (a cold batch has none)");
   }
-  if (refuse_capture("gik_anchored_ik_batch_retry", stream)) return -1;
+  if (refuse_capture(entry, stream)) return -1;
   if (B == 0) return 0;
   if (!d_clearance || !d_attempt) return fail(e + ": null d_clearance or d_attempt");
   if (!d_ws) return fail(e + ": null workspace (gik_anchored_retry_ws_bytes)");
@@ -1597,31 +1716,35 @@ int gik_anchored_ik_batch_retry(const gik_template *anch, const gik_template *ba
   // the centre of local mode is what attempt 0 started from; d_q_init may be d_q, which attempt 0 overwrites
   if (local) HIP_OK(hipMemcpyAsync(w.q_center, d_q_init, (size_t)B * n * sizeof(double), hipMemcpyDeviceToDevice, s));
   HIP_OK(hipMemsetAsync(d_attempt, 0, (size_t)B * sizeof(int32_t), s));
-  int rc;
-  if (d_q_init) {
-    rc = gik_anchored_ik_batch_seeded(anch, base, d_T_goal, d_q_init, B, w.scratch, d_Y_full, d_stats, d_q, d_pos_err,
-                                      d_rot_err, links ? nullptr : d_clearance, stream);
-  } else {
-    rc = gik_anchored_ik_batch(anch, base, d_T_goal, B, w.scratch, d_Y_full, d_stats, d_q, d_pos_err, d_rot_err, stream);
-    if (!rc && !links) rc = gik_anchored_clearance(anch, d_Y_full, B, d_clearance, stream);
+  // the scene ids of a compact batch: [B] int32 behind the plain layout (the scene entry's workspace is that much longer)
+  int32_t *ids_r = reinterpret_cast<int32_t *>(static_cast<char *>(d_ws) + ((w.bytes + 7) & ~(size_t)7));
+  gik_scene_set compact;
+  if (scenes) {
+    compact = *scenes;
+    if (scenes->d_scene_id) compact.d_scene_id = ids_r;
   }
   // link mode: the rule below is the same, the array it reads holds the clearance of whole links
-  if (!rc && links) rc = anchored_link_clearance_launch(anch, d_Y_full, B, d_clearance, stream);
+  int rc = anchored_attempt(anch, base, d_T_goal, d_q_init, B, scenes, w.scratch, d_Y_full, d_stats, d_q, d_pos_err, d_rot_err,
+                            d_clearance, links, stream);
   if (rc) return rc;
   for (int a = 1; a <= opts->retries; ++a) {
     rc = gik_anchored_retry_select(d_stats, d_pos_err, d_rot_err, d_clearance, B, opts->pos_tol, opts->rot_tol,
                                    opts->clear_tol, w.idx, w.count, stream);
     if (rc) return rc;
     int32_t count = 0;
-    rc = retry_read_count("gik_anchored_ik_batch_retry", w.count, B, &count, s);
+    rc = retry_read_count(entry, w.count, B, &count, s);
     if (rc) return rc;
     if (count == 0) break;
     rc = gik_anchored_retry_seeds(base, d_T_goal, w.idx, count, opts->seed, a, opts->d_q_lo, opts->d_q_hi,
                                   local ? w.q_center : nullptr, local ? opts->spread : 0.0, w.T, w.q_seed, stream);
     if (rc) return rc;
-    rc = gik_anchored_ik_batch_seeded(anch, base, w.T, w.q_seed, count, w.scratch, w.Y, w.stats, w.q, w.pos_err, w.rot_err,
-                                      links ? nullptr : w.clearance, stream);
-    if (!rc && links) rc = anchored_link_clearance_launch(anch, w.Y, count, w.clearance, stream);
+    if (scenes && scenes->d_scene_id) {
+      hipLaunchKernelGGL(scene_gather_kernel, dim3((count + ANCH_SCATTER_NT - 1) / ANCH_SCATTER_NT), dim3(ANCH_SCATTER_NT), 0, s,
+                         scenes->d_scene_id, w.idx, count, ids_r);
+      HIP_OK(hipGetLastError());
+    }
+    rc = anchored_attempt(anch, base, w.T, w.q_seed, count, scenes ? &compact : nullptr, w.scratch, w.Y, w.stats, w.q, w.pos_err,
+                          w.rot_err, w.clearance, links, stream);
     if (rc) return rc;
     rc = gik_anchored_retry_merge(anch, base, w.idx, count, a, opts->pos_tol, opts->rot_tol, opts->clear_tol, w.Y, w.stats,
                                   w.q, w.pos_err, w.rot_err, w.clearance, d_Y_full, d_stats, d_q, d_pos_err, d_rot_err,
@@ -1629,6 +1752,22 @@ int gik_anchored_ik_batch_retry(const gik_template *anch, const gik_template *ba
     if (rc) return rc;
   }
   return 0;
+}
+
+int gik_anchored_ik_batch_retry(const gik_template *anch, const gik_template *base, const double *d_T_goal,
+                                const double *d_q_init, int B, const gik_anchored_retry_opts *opts, void *d_ws,
+                                double *d_Y_full, gik_stats *d_stats, double *d_q, double *d_pos_err, double *d_rot_err,
+                                double *d_clearance, int32_t *d_attempt, void *stream) {
+  return anchored_retry_impl("gik_anchored_ik_batch_retry", anch, base, d_T_goal, d_q_init, B, opts, nullptr, false, d_ws, d_Y_full,
+                             d_stats, d_q, d_pos_err, d_rot_err, d_clearance, d_attempt, stream);
+}
+
+int gik_anchored_ik_batch_retry_scenes(const gik_template *anch, const gik_template *base, const double *d_T_goal,
+                                       const double *d_q_init, int B, const gik_anchored_retry_opts *opts,
+                                       const gik_scene_set *scenes, void *d_ws, double *d_Y_full, gik_stats *d_stats, double *d_q,
+                                       double *d_pos_err, double *d_rot_err, double *d_clearance, int32_t *d_attempt, void *stream) {
+  return anchored_retry_impl("gik_anchored_ik_batch_retry_scenes", anch, base, d_T_goal, d_q_init, B, opts, scenes, true, d_ws,
+                             d_Y_full, d_stats, d_q, d_pos_err, d_rot_err, d_clearance, d_attempt, stream);
 }
 
 double gik_anchored_last_solve_ms(const gik_template *anch) {
@@ -1858,9 +1997,15 @@ static int bind_workspace(gik_template *mt, WorkspaceLease &lease, const gik::So
   return 0;
 }
 
-static void launch(const gik_template *t, const gik::SolvePlan &p, gik::SolveArgs &a, hipStream_t stream) {
+// `scenes`: the scene build of the wavefront kernel instead (anchored templates, whose plan is always Launch::WAVE)
+static void launch(const gik_template *t, const gik::SolvePlan &p, gik::SolveArgs &a, const gik::SceneArgs *scenes,
+                   hipStream_t stream) {
   using namespace gik;
   const dim3 grid(p.launch_grid);
+  if (scenes) {
+    hipLaunchKernelGGL(t->kernels.solve_scene, grid, dim3(WAVE), t->smem_bytes, stream, a, *scenes);
+    return;
+  }
   switch (p.launch) {
     case Launch::QUAD:
       hipLaunchKernelGGL(t->quad_solve, grid, dim3(WAVE), t->quad_smem, stream, a);
@@ -1881,22 +2026,29 @@ static void launch(const gik_template *t, const gik::SolvePlan &p, gik::SolveArg
   }
 }
 
-int gik_solve_batch(const gik_template *t, const double *d_Y_init, const double *d_targets,
-                    int B, double *d_Y_out, gik_stats *d_stats, const gik_trace *trace,
-                    void *stream_) {
+// gik_solve_batch, and with a (checked) scene set gik_solve_batch_scenes
+static int solve_batch_impl(const char *entry, const gik_template *t, const double *d_Y_init, const double *d_targets,
+                            int B, double *d_Y_out, gik_stats *d_stats, const gik_trace *trace, const gik_scene_set *scenes,
+                            void *stream_) {
   using namespace gik;
-  if (!t || B < 0) return fail("bad argument");
   if (B == 0) return 0;
   if (!d_Y_init || !d_targets || !d_Y_out || !d_stats) return fail("null buffer");
   hipStream_t stream = (hipStream_t)stream_;
   SolveArgs a;
   fill_args(t, a, d_Y_init, d_targets, B, d_Y_out, d_stats, trace);
+  SceneArgs sa;
+  if (scenes) {      // the template's own spheres play no part: the kernel walks the rows of each problem's scene
+    sa = scene_args(scenes);
+    a.an.obs = scenes->d_obs;
+    a.an.n_obs = 0;
+  }
   // Stream capture is refused: the slot protocol below queries, waits for and records events, grows workspaces
   // (hipMalloc / hipFree) and resets a counter the kernel consumes -- none of which may happen under capture, and a
   // replayed graph would reuse this call's counter slot and workspace behind the library's back.  A batch is ONE
   // persistent launch; there is no launch overhead for a graph to remove.
-  if (refuse_capture("gik_solve_batch", stream_)) return -1;
+  if (refuse_capture(entry, stream_)) return -1;
   const SolvePlan plan = plan_solve(t->f, B);
+  if (scenes && plan.launch != Launch::WAVE) return fail(std::string(entry) + ": the template's plan is not the wavefront kernel");
   a.slice_its = plan.slice_its;
   a.slice_cycles = plan.slice_cycles;
   // The handle's mutable parts: the ring of work-queue heads and the time-slicing workspaces.  Each is leased
@@ -1907,7 +2059,7 @@ int gik_solve_batch(const gik_template *t, const double *d_Y_init, const double 
   WorkspaceLease workspace(mt->call_mutex);
   if (lease_counter(mt, counter, a, stream)) return -1;
   if (plan.needs_ws && bind_workspace(mt, workspace, plan, a, stream)) return -1;
-  launch(t, plan, a, stream);
+  launch(t, plan, a, scenes ? &sa : nullptr, stream);
   HIP_OK(hipGetLastError());
   // The slots go back "pending" only behind an event that really covers this launch.  If a record fails,
   // nothing guards the counter / workspace against the next caller: wait for the kernel here and hand the
@@ -1921,6 +2073,20 @@ int gik_solve_batch(const gik_template *t, const double *d_Y_init, const double 
   counter.covered_by_event();
   workspace.covered_by_event();
   return 0;
+}
+
+int gik_solve_batch(const gik_template *t, const double *d_Y_init, const double *d_targets,
+                    int B, double *d_Y_out, gik_stats *d_stats, const gik_trace *trace,
+                    void *stream_) {
+  if (!t || B < 0) return gik::fail("bad argument");
+  return solve_batch_impl("gik_solve_batch", t, d_Y_init, d_targets, B, d_Y_out, d_stats, trace, nullptr, stream_);
+}
+
+int gik_solve_batch_scenes(const gik_template *t, const double *d_Y_init, const double *d_targets, int B, double *d_Y_out,
+                           gik_stats *d_stats, const gik_trace *trace, const gik_scene_set *scenes, void *stream_) {
+  if (!t || B < 0) return gik::fail("gik_solve_batch_scenes: bad argument");
+  if (scene_refusal("gik_solve_batch_scenes", t, scenes) || refuse_capture("gik_solve_batch_scenes", stream_)) return -1;
+  return solve_batch_impl("gik_solve_batch_scenes", t, d_Y_init, d_targets, B, d_Y_out, d_stats, trace, scenes, stream_);
 }
 
 int gik_template_set_claim_key(gik_template *t, int n, const int32_t *terms, const double *weights) {

@@ -42,6 +42,12 @@
 #define GIK_KERNELS_ANCH_LINK(X)                                          \
   X(void rtr_wave_kernel<3, 9, true, true, false, false, true>(SolveArgs)) \
   X(void kat_wave_kernel<3, 9, true, false, true>(KatArgs))
+// ... with per-goal obstacle scenes (gik_solve_batch_scenes): the scene builds of the three solve kernels above, <slots,
+// link hinges>.  Beside GIK_ALL_KERNELS like the link group
+#define GIK_KERNELS_ANCH_SCENE(X)                                 \
+  X(void rtr_wave_scene_kernel<9, false>(SolveArgs, SceneArgs))   \
+  X(void rtr_wave_scene_kernel<20, false>(SolveArgs, SceneArgs))  \
+  X(void rtr_wave_scene_kernel<9, true>(SolveArgs, SceneArgs))
 // one unknown per lane, k = 2
 #define GIK_KERNELS_WAVE2(X)                       \
   X(void rtr_wave_kernel<2, 6, true>(SolveArgs))   \

@@ -245,9 +245,17 @@ __device__ inline void stage_lds(double *tiles, uint32_t *meta, const uint32_t *
 // STRICT: the Hessian product term by term as costs.py:186-203 forms it (gik_wave_strict.hip.h;
 // gik_template_desc.hessian_form = GIK_HESS_PER_EDGE), k = 3 free-free graphs
 // LINKS: link hinges in the fixed-anchor solve (WaveCtx<.., LINKS>, gik_anchored_attach_links with hinges = 1).
-// The kernel's text is this function; rtr_wave_kernel below is its two entry points.
-template <int K, int MAXDEG, bool THETA_ONE, bool ANCH, bool MIG, bool STRICT, bool LINKS>
-__device__ __forceinline__ void rtr_wave_run(const SolveArgs &a) {
+// SCENES: per-goal obstacle scenes in the fixed-anchor solve (gik_solve_batch_scenes).  The scene set is a second kernel
+// argument (SceneArgs, gik_scenes.h; SolveArgs and with it every other kernel stay as they are): a.an.obs is then the
+// caller's [n_scene][stride][4] array and a.an.n_obs is not read; problem b walks the first n_obs[s] rows of scene
+// s = scene_id[b] (null: scene 0), and the obstacle table in LDS is restaged whenever a claimed problem's scene differs
+// from the staged one.  The anchored builds are not
+// time-sliced and reset their near lists per problem anyway, and the near lists are exact, so a problem's bits are those
+// of a template created with its scene's spheres, whatever the wave staged before.
+// The kernel's text is this function; rtr_wave_kernel and rtr_wave_scene_kernel below are its entry points.
+template <int K, int MAXDEG, bool THETA_ONE, bool ANCH, bool MIG, bool STRICT, bool LINKS, bool SCENES = false>
+__device__ __forceinline__ void rtr_wave_run(const SolveArgs &a, const SceneArgs &sc = SceneArgs()) {
+  static_assert(!SCENES || ANCH, "scenes: the fixed-anchor kernels");
   static_assert(!LINKS || (ANCH && MAXDEG == 9), "link hinges: the 9-slot fixed-anchor kernel");
   static_assert(!ANCH || K == 3, "the fixed-anchor formulation is 3-D");
   static_assert(!MIG || !ANCH, "tail spreading: two waves per SIMD, i.e. not the anchored variant");
@@ -266,7 +274,8 @@ __device__ __forceinline__ void rtr_wave_run(const SolveArgs &a) {
   if constexpr (ANCH) {
     // every target is a template constant here: records, pinned records and the constant rows of
     // the anchor table are staged once per wave; only the goal anchors change per problem
-    cx.init_anchored(a.an.obs_mask, a.an.obs, a.an.n_obs, !(a.dbg & 128));
+    // (a scene build starts with no obstacle staged: the first claimed problem brings its scene)
+    cx.init_anchored(a.an.obs_mask, a.an.obs, SCENES ? 0 : a.an.n_obs, !(a.dbg & 128));
     if constexpr (LINKS) cx.init_links(a.an.link_rec);
     for (int t = lane; t < a.T; t += WAVE) sh_tgt[t] = a.targets[t];
     for (int t = lane; t < 4 * ANCH_MAXA; t += WAVE) cx.sh_anch[t] = a.an.anch_const[t];
@@ -280,6 +289,7 @@ __device__ __forceinline__ void rtr_wave_run(const SolveArgs &a) {
                 (int)gridDim.x, a.slice_cycles};
   bool tail = false;
   bool owns_entry = false;    // (lane 0) this wave has just pushed a yielded problem
+  int staged_scene = -1;      // (SCENES) the scene whose rows sh_obs holds
   if constexpr (MIG) mig.sid = hw_simd_id();
 #ifdef GIK_DEV
   long long dev_t_start = (long long)__builtin_readcyclecounter(), dev_t_solve = 0, dev_t_claim = 0;
@@ -370,6 +380,16 @@ __device__ __forceinline__ void rtr_wave_run(const SolveArgs &a) {
       if (lane < 3 * a.an.n_goal)
         cx.sh_anch[(a.an.goal_row0 + lane / 3) * 4 + lane % 3] =
             a.an.anchor_goal[(size_t)b * 3 * a.an.n_goal + lane];
+      if constexpr (SCENES) {
+        // b is wave-uniform (readlane), so id and count are scalar loads and stay in scalar registers.  Both are clamped:
+        // a bad id or count in the caller's arrays reads a wrong scene, never memory outside the scene set or the table.
+        const int s = uniform_i32(scene_clamp_id(sc.scene_id ? sc.scene_id[b] : 0, sc.n_scene));
+        if (UNI(s != staged_scene)) {
+          const int n = uniform_i32(scene_clamp_count(sc.n_obs[s], sc.stride));
+          cx.stage_scene(a.an.obs + (size_t)s * (size_t)sc.stride * 4, n);
+          staged_scene = s;
+        }
+      }
       cx.obs_reset();
       if constexpr (LINKS) cx.links_reset();
     } else {
@@ -476,6 +496,12 @@ template <int K, int MAXDEG, bool THETA_ONE, bool ANCH, bool MIG, bool STRICT, b
 __global__ void __launch_bounds__(WAVE, ANCH ? 1 : 2) rtr_wave_kernel(SolveArgs a) {
   static_assert(LINKS, "the seven-parameter form is the link build; every other kernel is rtr_wave_kernel<K, MAXDEG, THETA_ONE, ...>");
   rtr_wave_run<K, MAXDEG, THETA_ONE, ANCH, MIG, STRICT, LINKS>(a);
+}
+// The scene builds of the three fixed-anchor solve kernels (9 slots, 20 slots, 9 slots with link hinges), under a name of
+// their own: the templates above keep their parameter lists and their symbols.
+template <int MAXDEG, bool LINKS>
+__global__ void __launch_bounds__(WAVE, 1) rtr_wave_scene_kernel(SolveArgs a, SceneArgs sc) {
+  rtr_wave_run<3, MAXDEG, true, true, false, false, LINKS, true>(a, sc);
 }
 
 // Riemannian conjugate gradients (the reference's alternative solver), same persistent scheme

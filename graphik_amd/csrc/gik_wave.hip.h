@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "graphik_amd.h"
+#include "gik_scenes.h"
 
 namespace gik {
 
@@ -327,6 +328,7 @@ struct Row {
 constexpr int ANCH_PMAX = 8;
 constexpr int ANCH_MAXA = 16;   // rows of the pinned-anchor table
 constexpr int ANCH_MAXOBS = 128; // obstacles (staged in LDS: 32 B each)
+static_assert(SCENE_MAX_SPHERES == ANCH_MAXOBS, "gik_scenes.h restates this constant");
 
 // LINKS: link hinges on top (opt-in per template, gik_anchored_attach_links with hinges = 1).  A link l = (a, b, rho) is
 // the segment between two rows of the full point matrix -- free rows of Y, constant base anchors or the per-problem goal
@@ -567,6 +569,20 @@ struct WaveCtx {
     obs_lane = active && ((obs_mask >> node) & 1ull);
     for (int t = lane; t < 4 * n_obs_; t += WAVE) sh_obs[t] = obs[t];
     obs_reset();
+  }
+  // Per-goal scenes (the scene builds of rtr_wave_kernel): replace the staged obstacle table by `n` rows of a scene, and
+  // with LINKS the radii, by the expressions init_anchored / init_links stage the template's own with -- a problem's bits
+  // are those of a template created with these rows.  Rows from n up keep whatever an earlier scene left: nothing reads
+  // them (every walk stops at n_obs, every near list holds indices below it).  `n` is wave-uniform; the caller runs
+  // obs_reset / links_reset next.
+  __device__ inline void stage_scene(const double *obs, int n) {
+    __builtin_amdgcn_wave_barrier();
+    n_obs = n;
+    for (int t = lane; t < 4 * n; t += WAVE) sh_obs[t] = obs[t];
+    if constexpr (LINKS) {
+      __builtin_amdgcn_wave_barrier();
+      for (int t = lane; t < n; t += WAVE) sh_obr[t] = sqrt(sh_obs[4 * t + 3]);
+    }
   }
   // per problem: forget the near lists
   __device__ inline void obs_reset() {

@@ -125,6 +125,93 @@ def check_clearance_mode(clearance_mode, has_links=True):
     return _ffi.CLEARANCE_MODES[clearance_mode]
 
 
+def pack_scenes(scenes, stride=None):
+    """A sequence of [m_s, 4] arrays of (centre x, y, z, radius), numpy or torch -> what gik_scene_set points at, on the
+    host: (obs [S, stride, 4] float64 with the radius SQUARED -- one rounded product, the bits of AnchoredProblem's own
+    obs[:, 3] ** 2 -- and NaN in the padding rows, which no kernel reads; n_obs [S] int32; stride).  stride defaults to
+    the largest count.  ValueError, before any device call: no scene, more than 128 spheres in one, a shape that is not
+    [m, 4], a centre that is not finite, a radius that is negative or not finite, a stride below a count or above 128."""
+    rows = []
+    for s, sc in enumerate(scenes):
+        a = sc.detach().cpu().numpy() if isinstance(sc, torch.Tensor) else np.asarray(sc)
+        a = np.asarray(a, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != 4:
+            raise ValueError(f"scene {s}: expected an array of shape [m, 4] (centre x, y, z, radius), got {list(a.shape)}")
+        if a.shape[0] > _ffi.SCENE_MAX_SPHERES:
+            raise ValueError(f"scene {s}: {a.shape[0]} spheres, at most {_ffi.SCENE_MAX_SPHERES} per scene")
+        if not np.all(np.isfinite(a[:, :3])):
+            raise ValueError(f"scene {s}: a centre is not finite")
+        if not np.all(np.isfinite(a[:, 3]) & (a[:, 3] >= 0)):
+            raise ValueError(f"scene {s}: a radius is negative or not finite")
+        rows.append(a)
+    if not rows:
+        raise ValueError("a scene set needs at least one scene (an empty scene is an array of shape [0, 4])")
+    n_obs = np.array([len(a) for a in rows], dtype=np.int32)
+    if stride is None:
+        stride = int(n_obs.max())
+    if int(stride) != stride or not int(n_obs.max()) <= stride <= _ffi.SCENE_MAX_SPHERES:
+        raise ValueError(f"stride must be an integer within {int(n_obs.max())} (the largest scene) .. {_ffi.SCENE_MAX_SPHERES}, got {stride!r}")
+    obs = np.full((len(rows), int(stride), 4), np.nan)
+    for s, a in enumerate(rows):
+        obs[s, :len(a), :3] = a[:, :3]
+        obs[s, :len(a), 3] = a[:, 3] ** 2
+    return obs, n_obs, int(stride)
+
+
+class SceneSet:
+    """Per-goal obstacle scenes of the anchored solve (gik_scene_set), uploaded once: `scenes` is a sequence of [m_s, 4]
+    arrays of (centre, radius).  Holds the device tensors obs [S, stride, 4] (squared radii) and n_obs [S] int32, and on
+    the host scenes (the arrays as given, float64), obs_host, counts, stride, n_scene.  An argument of
+    Template.solve / anchored_ik and of AnchoredProblem.solve / solve_trajectory, together with scene_id."""
+
+    def __init__(self, scenes, device, stride=None):
+        scenes = list(scenes)
+        self.obs_host, self.counts, self.stride = pack_scenes(scenes, stride)
+        self.n_scene = len(self.counts)
+        self.scenes = [np.asarray(sc.detach().cpu().numpy() if isinstance(sc, torch.Tensor) else sc, dtype=np.float64).reshape(-1, 4)
+                       for sc in scenes]
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device(f"cuda:{torch.cuda.current_device()}")
+        self.obs = torch.from_numpy(self.obs_host).to(self.device)
+        self.n_obs = torch.from_numpy(self.counts).to(self.device)
+
+    def ids(self, scene_id, shape, checked=False):
+        """scene_id -> a contiguous int32 device tensor of `shape` ([B], or [B, L]), or None where there is one scene and
+        no ids (every goal uses scene 0).  ValueError for a missing id array with several scenes, a wrong shape, an id
+        that is not an integer or lies outside [0, n_scene); a device tensor is checked with one reduction.
+        checked: scene_id is what an earlier ids() returned, or a row of it -- nothing is looked at again."""
+        if checked:
+            return scene_id
+        if scene_id is None:
+            if self.n_scene != 1:
+                raise ValueError(f"scene_id is required with {self.n_scene} scenes: [B] ints, the scene of each goal")
+            return None
+        if isinstance(scene_id, torch.Tensor) and scene_id.device.type != "cpu":
+            t = scene_id
+            if t.dtype not in (torch.int32, torch.int64):
+                raise ValueError("scene_id must hold integers")
+            if tuple(t.shape) != tuple(shape):
+                raise ValueError(f"scene_id must have shape {list(shape)}, got {list(t.shape)}")
+            if t.numel() and bool(((t < 0) | (t >= self.n_scene)).any()):
+                raise ValueError(f"scene_id has entries outside [0, {self.n_scene})")
+            return t.to(device=self.device, dtype=torch.int32).contiguous()
+        a = np.asarray(scene_id.numpy() if isinstance(scene_id, torch.Tensor) else scene_id)
+        if a.dtype.kind not in "iu":
+            if a.dtype.kind != "f" or not np.all(a == np.floor(a)):
+                raise ValueError("scene_id must hold integers")
+        if tuple(a.shape) != tuple(shape):
+            raise ValueError(f"scene_id must have shape {list(shape)}, got {list(a.shape)}")
+        if a.size and (a.min() < 0 or a.max() >= self.n_scene):
+            raise ValueError(f"scene_id has entries outside [0, {self.n_scene})")
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)
+
+    def desc(self, ids):
+        """The gik_scene_set of one call: ids [B] int32 on the device (from ids()), or None."""
+        return _ffi.SceneSet(n_scene=self.n_scene, stride=self.stride, d_obs=self.obs.data_ptr() if self.stride else None,
+                             d_n_obs=self.n_obs.data_ptr(), d_scene_id=None if ids is None else ids.data_ptr())
+
+
 class Template:
     """Goal-independent part of an IK problem family, resident on one GPU."""
 
@@ -556,25 +643,47 @@ class Template:
                                                         Y_free.data_ptr(), goal.data_ptr(), self._stream()))
         return Y_free.reshape(B, self.N, 3), goal
 
-    def anchored_clearance(self, Y_full):
+    def anchored_clearance(self, Y_full, scenes=None, scene_id=None):
         """Full point matrices [B, full_N, 3] -> clearance [B] on the device (gik_anchored_clearance): the
         minimum of |Y_i - centre| - radius over the free nodes that carry the obstacle hinges and the
-        obstacles; +inf without obstacles."""
+        obstacles; +inf without obstacles.  scenes (a SceneSet) / scene_id [B]: goal b against the spheres of its
+        scene instead of the template's own (gik_anchored_clearance_scenes)."""
         assert self.anchored
-        return self._clearance_of(self.lib.gik_anchored_clearance, Y_full)
+        return self._clearance_of(self.lib.gik_anchored_clearance, self.lib.gik_anchored_clearance_scenes, Y_full, scenes, scene_id)
 
-    def _clearance_of(self, clear_fn, Y_full):
-        """Full point matrices [B, full_N, 3] (or [full_N, 3]) as a contiguous [B, full_N*3] buffer -> clear_fn's [B]."""
+    def _clearance_of(self, clear_fn, scene_fn, Y_full, scenes=None, scene_id=None):
+        """Full point matrices [B, full_N, 3] (or [full_N, 3]) as a contiguous [B, full_N*3] buffer -> clear_fn's [B], or
+        with a scene set scene_fn's."""
         Y = _dev(Y_full, self.device)
         if Y.dim() == 2:
             Y = Y[None]
         B = Y.shape[0]
         assert Y.numel() == B * self.full_N * 3, (tuple(Y.shape), (B, self.full_N, 3))
+        sc, ids = self._scene_desc(scenes, scene_id, B)
         Y = Y.reshape(B, self.full_N * 3).contiguous()
         out = torch.empty(B, dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
-            _ffi.check(clear_fn(self._h, Y.data_ptr(), B, out.data_ptr(), self._stream()))
+            if sc is None:
+                _ffi.check(clear_fn(self._h, Y.data_ptr(), B, out.data_ptr(), self._stream()))
+            else:
+                _ffi.check(scene_fn(self._h, Y.data_ptr(), B, C.byref(sc), out.data_ptr(), self._stream()))
         return out
+
+    def _scene_desc(self, scenes, scene_id, B, checked=False):
+        """(gik_scene_set, ids tensor) of a call of B goals -- checked on the host before any device call -- or
+        (None, None) without scenes.  The caller keeps `ids` alive until its call is queued."""
+        if scenes is None:
+            if scene_id is not None:
+                raise ValueError("scene_id needs scenes=")
+            return None, None
+        if not isinstance(scenes, SceneSet):
+            raise TypeError("scenes must be a SceneSet (AnchoredProblem.scene_set, engine.SceneSet)")
+        if not self.anchored:
+            raise ValueError("scenes belong to the fixed-anchor solve: this template is not anchored")
+        if scenes.device != self.device:
+            raise ValueError(f"the scene set lives on {scenes.device}, the template on {self.device}")
+        ids = scenes.ids(scene_id, (B,), checked)
+        return scenes.desc(ids), ids
 
     def attach_links(self, link_a, link_b, link_radius, hinges=False):
         """The link set of an anchored template (gik_anchored_attach_links), once: link l is the segment between rows
@@ -599,12 +708,13 @@ class Template:
         self.link_hinges = bool(hinges)
         self._read_info()      # (hinges: other kernels, LDS bytes and occupancy)
 
-    def anchored_link_clearance(self, Y_full):
+    def anchored_link_clearance(self, Y_full, scenes=None, scene_id=None):
         """Full point matrices [B, full_N, 3] -> link clearance [B] on the device (gik_anchored_link_clearance): the
         minimum over the attached links and the obstacles of the distance from the sphere to the link's capsule;
-        +inf without obstacles or links."""
+        +inf without obstacles or links.  scenes / scene_id: as anchored_clearance (gik_anchored_link_clearance_scenes)."""
         assert self.anchored
-        return self._clearance_of(self.lib.gik_anchored_link_clearance, Y_full)
+        return self._clearance_of(self.lib.gik_anchored_link_clearance, self.lib.gik_anchored_link_clearance_scenes, Y_full,
+                                  scenes, scene_id)
 
     def anchored_sweep_clearance(self, base, q_a, q_b, samples, out=None, ws=None):
         """Joint angles q_a, q_b [B,n] (device tensors or arrays) -> [B]: the minimum link clearance over the samples + 1
@@ -632,7 +742,8 @@ class Template:
         return out      # (ws goes back to the allocator of this stream, behind the kernels that use it)
 
     def anchored_ik(self, base, T_goal, q_init=None, out=None, clearance=False, retries=0, retry_seed=0, pos_tol=0.01,
-                    rot_tol=0.01, clear_tol=1e-4, retry_spread=0.0, q_limits=None, clearance_mode="nodes"):
+                    rot_tol=0.01, clear_tol=1e-4, retry_spread=0.0, q_limits=None, clearance_mode="nodes", scenes=None,
+                    scene_id=None, scene_id_checked=False):
         """Whole pipeline through the fixed-anchor solve: `base` is the robot graph's Template (no
         obstacles) with its pipeline attached.  Without q_init the start point is the robot graph's bound
         smoothing + MDS one fitted to the anchors (gik_anchored_ik_batch); with q_init (seed joint angles
@@ -651,7 +762,12 @@ class Template:
         no "ws": the restart workspace holds that scratch.
 
         clearance_mode: "nodes" (the joint points, gik_anchored_clearance) or "links" (whole links,
-        gik_anchored_link_clearance; needs attach_links): which clearance comes back and the restart rule reads."""
+        gik_anchored_link_clearance; needs attach_links): which clearance comes back and the restart rule reads.
+
+        scenes (a SceneSet) with scene_id ([B] ints; optional with one scene): goal b is solved among the spheres of
+        scene scene_id[b] instead of the template's own, and its clearance is measured against them
+        (gik_anchored_ik_batch_scenes, gik_anchored_ik_batch_retry_scenes); everything else combines with it unchanged.
+        scene_id_checked: scene_id is a row of an id array SceneSet.ids() has already checked (solve_trajectory)."""
         assert self.anchored and base.has_pipeline
         mode = check_clearance_mode(clearance_mode, getattr(self, "n_link", None) is not None)
         if retries:      # (the clearance always comes back then, whatever `clearance` says)
@@ -659,6 +775,7 @@ class Template:
                                                retry_spread=retry_spread, has_center=q_init is not None)
             clearance = True
         T, B = base._poses(T_goal)
+        sc, ids = self._scene_desc(scenes, scene_id, B, scene_id_checked)
         if out is None:      # (with retries the restart workspace holds the scratch "ws")
             out = self.alloc_anchored_buffers(base, B, clearance, ws=not retries)
         q0 = None if q_init is None else base._seed_angles(q_init, B)
@@ -669,16 +786,30 @@ class Template:
         with torch.cuda.device(self.device):
             if retries:
                 nbytes = int(self.lib.gik_anchored_retry_ws_bytes(self._h, base._h, B))
+                if sc is not None:      # (the compact batch's scene ids sit behind the plain layout)
+                    nbytes = (nbytes + 7) // 8 * 8 + 4 * B
                 attempt, ws, q_lo, q_hi = self._retry_buffers(out, B, nbytes, lo, hi)
                 opts = _ffi.AnchoredRetryOpts(retries=retries, clearance_mode=mode, seed=int(retry_seed) & (2 ** 64 - 1),
                                               pos_tol=float(pos_tol), rot_tol=float(rot_tol), d_q_lo=q_lo.data_ptr(),
                                               d_q_hi=q_hi.data_ptr(), clear_tol=float(clear_tol), spread=float(retry_spread))
-                _ffi.check(self.lib.gik_anchored_ik_batch_retry(
-                    self._h, base._h, T.data_ptr(), None if q0 is None else q0.data_ptr(), B, C.byref(opts), ws.data_ptr(),
-                    *answer, cl.data_ptr(), attempt.data_ptr(), self._stream()))
-                return _result(out, (B, self.full_N, 3), {"clearance": cl, "attempt": attempt, "_retry_ws": ws})
+                seed_ptr = None if q0 is None else q0.data_ptr()
+                if sc is None:
+                    _ffi.check(self.lib.gik_anchored_ik_batch_retry(
+                        self._h, base._h, T.data_ptr(), seed_ptr, B, C.byref(opts), ws.data_ptr(),
+                        *answer, cl.data_ptr(), attempt.data_ptr(), self._stream()))
+                else:
+                    _ffi.check(self.lib.gik_anchored_ik_batch_retry_scenes(
+                        self._h, base._h, T.data_ptr(), seed_ptr, B, C.byref(opts), C.byref(sc), ws.data_ptr(),
+                        *answer, cl.data_ptr(), attempt.data_ptr(), self._stream()))
+                return _result(out, (B, self.full_N, 3), {"clearance": cl, "attempt": attempt, "_retry_ws": ws, "_scene_id": ids})
             ws = out["ws"]
             assert ws.numel() >= int(self.lib.gik_anchored_ws_doubles(self._h, base._h, B))
+            if sc is not None:      # one call: cold or seeded, the clearance of either mode behind it
+                _ffi.check(self.lib.gik_anchored_ik_batch_scenes(
+                    self._h, base._h, T.data_ptr(), None if q0 is None else q0.data_ptr(), B, C.byref(sc), ws.data_ptr(),
+                    *answer, None if cl is None else cl.data_ptr(), mode, self._stream()))
+                extras = {"_ws": ws, "_scene_id": ids}
+                return _result(out, (B, self.full_N, 3), {**extras, "clearance": cl} if clearance else extras)
             if q0 is None:
                 _ffi.check(self.lib.gik_anchored_ik_batch(self._h, base._h, T.data_ptr(), B, ws.data_ptr(), *answer,
                                                           self._stream()))
@@ -700,11 +831,14 @@ class Template:
                 "pos_err": torch.empty(B, **f64), "rot_err": torch.empty(B, **f64)}
 
     # -- trust-region solve -------------------------------------------------------------------
-    def solve(self, Y_init, targets, trace_cap=0):
+    def solve(self, Y_init, targets, trace_cap=0, scenes=None, scene_id=None):
         """Batched TrustRegions.solve.  Returns dict of device tensors:
-        x [B,N,k], f, gradnorm, iterations, inner_total, stop, n_accept (+ trace arrays)."""
+        x [B,N,k], f, gradnorm, iterations, inner_total, stop, n_accept (+ trace arrays).
+        scenes (a SceneSet) / scene_id [B], anchored templates: problem b among the spheres of its scene instead of the
+        template's own (gik_solve_batch_scenes)."""
         Y, B = self._vec(Y_init)
         t = self._tg(targets, B)
+        sc, ids = self._scene_desc(scenes, scene_id, B)
         out = torch.empty_like(Y)
         stats = _alloc_stats(B, self.device)
         tr = None
@@ -719,11 +853,18 @@ class Template:
                 keep[name] = torch.full((B, trace_cap), fill, dtype=dt, device=self.device)
                 setattr(tr, "d_" + name, keep[name].data_ptr())
         with torch.cuda.device(self.device):
-            _ffi.check(self.lib.gik_solve_batch(self._h, Y.data_ptr(), t.data_ptr(), B,
-                                                out.data_ptr(), stats.data_ptr(),
-                                                C.byref(tr) if tr is not None else None,
-                                                self._stream()))
+            if sc is None:
+                _ffi.check(self.lib.gik_solve_batch(self._h, Y.data_ptr(), t.data_ptr(), B,
+                                                    out.data_ptr(), stats.data_ptr(),
+                                                    C.byref(tr) if tr is not None else None,
+                                                    self._stream()))
+            else:
+                _ffi.check(self.lib.gik_solve_batch_scenes(self._h, Y.data_ptr(), t.data_ptr(), B, out.data_ptr(),
+                                                           stats.data_ptr(), C.byref(tr) if tr is not None else None,
+                                                           C.byref(sc), self._stream()))
         res = {"x": out.reshape(B, self.N, self.k)}
+        if ids is not None:
+            res["_scene_id"] = ids      # (read by the kernel: lives as long as the result)
         res.update(_decode_stats(stats))
         if tr is not None:
             res["trace"] = keep

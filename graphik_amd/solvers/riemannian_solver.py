@@ -625,8 +625,23 @@ class AnchoredProblem:
         The host mirror of gik_anchored_seed_batch's Y_free."""
         return self.base.seed_points(q)[:, self.free]
 
+    def scene_set(self, scenes):
+        """Per-goal obstacle scenes for solve(..., scenes=) and solve_trajectory: a sequence of [m_s, 4] arrays of
+        (centre x, y, z, radius), numpy or torch, at most 128 spheres each; an empty scene is an array of shape [0, 4].
+        They are uploaded once; the returned engine.SceneSet holds the device tensors (obs with the radii squared by one
+        rounded product, the bits of this problem's own obs[:, 3] ** 2; n_obs), the counts, the stride and the host
+        copies.  ValueError before any device call: more than 128 spheres in a scene, a radius that is negative or not
+        finite, a centre that is not finite, a shape that is not [m, 4].  The problem's own obstacles play no part in a
+        solve that is given scenes; its masked nodes, links and link radii apply to every scene."""
+        from ..engine import SceneSet, pack_scenes
+        scenes = list(scenes)
+        pack_scenes(scenes)      # (the checks, before the template -- a device object -- is touched)
+        if self.template is None:
+            raise ValueError("a host-only problem has no device to upload scenes to")
+        return SceneSet(scenes, self.template.device)
+
     def solve(self, T_goals, q_init=None, clearance=False, retries=0, retry_seed=0, pos_tol=0.01, rot_tol=0.01,
-              clear_tol=1e-4, retry_spread=0.0, q_limits=None, clearance_mode="nodes"):
+              clear_tol=1e-4, retry_spread=0.0, q_limits=None, clearance_mode="nodes", scenes=None, scene_id=None):
         """Goal poses -> dict of device tensors (x [B, N_robot, 3], q, pos_err, rot_err, stats).
 
         q_init (warm start): joint angles [B,n] or [n]; the solve then starts from the realization of
@@ -647,14 +662,19 @@ class AnchoredProblem:
         retry_spread == 0: the angles are uniform inside the limits, retry_seeds_host(retry_seed, [g], attempt,
         lo, hi) are goal g's.  retry_spread > 0 (radians, needs q_init): they lie within retry_spread of q_init
         (retry_seeds_host(..., center=q_init[g:g+1], spread=retry_spread)), for a tracked waypoint that
-        should stay on its IK branch."""
+        should stay on its IK branch.
+
+        scenes (scene_set(...)) with scene_id ([B] ints within [0, S), numpy or a device tensor; optional with one
+        scene): goal b is solved among the spheres of scene scene_id[b] instead of the problem's own -- one launch over
+        the whole batch, whatever the mix -- and "clearance" is measured against them.  Every other keyword combines with
+        it.  Goal b's answer is, bit for bit, that of an AnchoredProblem built with scene scene_id[b]'s spheres."""
         T = np.asarray(T_goals, dtype=float)
         check_clearance_mode(clearance_mode, len(self.link_names) > 0)
         retry = self._retry_args(retries, retry_seed, pos_tol, rot_tol, clear_tol, retry_spread, q_limits, q_init is not None)
         if q_init is not None:
             q_init = _seed_angles(q_init, T.shape[0], self.robot.n)
         return self.template.anchored_ik(self.base.template, T, q_init=q_init, clearance=clearance or q_init is not None,
-                                         clearance_mode=clearance_mode, **retry)
+                                         clearance_mode=clearance_mode, scenes=scenes, scene_id=scene_id, **retry)
 
     def _retry_args(self, retries, retry_seed, pos_tol, rot_tol, clear_tol, retry_spread, q_limits, has_center=True):
         """The restart arguments of solve / solve_trajectory, checked here before any device call, as the keywords
@@ -668,7 +688,8 @@ class AnchoredProblem:
                     retry_spread=retry_spread, q_limits=(lo, hi))
 
     def solve_trajectory(self, T_path, q_start, return_Y=False, retries=0, retry_seed=0, pos_tol=0.01, rot_tol=0.01,
-                         clear_tol=1e-4, retry_spread=0.0, q_limits=None, clearance_mode="nodes", sweep=None):
+                         clear_tol=1e-4, retry_spread=0.0, q_limits=None, clearance_mode="nodes", sweep=None, scenes=None,
+                         scene_id=None):
         """Path tracking among the obstacles: B paths of L waypoints, T_path [B, L, 4, 4].  Waypoint 0
         is seeded by q_start ([B,n] or [n]), waypoint l by the joint angles recovered at waypoint l-1,
         which never leave the device: L calls of gik_anchored_ik_batch_seeded on one stream, one
@@ -689,6 +710,10 @@ class AnchoredProblem:
         already on the device.  It is sampled, not conservative -- pick S from the joint step between waypoints --
         and it is reported only: the restart rule does not read it.
 
+        scenes (scene_set(...)) with scene_id: [B] ints -- a scene per path -- or [B, L] -- a scene per waypoint, which
+        is a moving obstacle: waypoint l of path b is solved among the spheres of scene scene_id[b, l].  Optional with
+        one scene.  sweep= together with scenes= is refused (the sweep clearance reads the problem's own obstacles).
+
         Returns q [B, L, n], Y [B, L, N_robot, 3] (None unless return_Y), and info with [B, L] arrays
         iterations, inner_iterations, stop, f(x), gradnorm, pos_err, rot_err, clearance, plus
         solve_time (seconds, whole path)."""
@@ -696,6 +721,18 @@ class AnchoredProblem:
         B = T.shape[0]
         q0 = _seed_angles(q_start, B, self.robot.n, "q_start")
         check_clearance_mode(clearance_mode, len(self.link_names) > 0)
+        if sweep is not None and scenes is not None:
+            raise ValueError("sweep= with scenes= is not supported: the sweep clearance measures the problem's own obstacles")
+        ids = None      # [L, B] int32 on the device: waypoint-major, a row per step
+        if scenes is not None:
+            L = T.shape[1]
+            shape = np.shape(scene_id) if scene_id is not None else ()
+            per_waypoint = len(shape) == 2
+            ids = scenes.ids(scene_id, (B, L) if per_waypoint else (B,))
+            if ids is not None:
+                ids = ids.T.contiguous() if per_waypoint else ids[None].expand(L, B).contiguous()
+        elif scene_id is not None:
+            raise ValueError("scene_id needs scenes=")
         if sweep is not None:
             sweep = self._check_samples(sweep, "sweep")
             if not len(self.link_names):
@@ -703,9 +740,11 @@ class AnchoredProblem:
         retry = self._retry_args(retries, retry_seed, pos_tol, rot_tol, clear_tol, retry_spread, q_limits)
         tpl, base = self.template, self.base.template
         planes, shared, nbytes = ["clearance"], {}, None
-        if retry:      # (the restart workspace holds the anchored scratch too)
+        if retry:      # (the restart workspace holds the anchored scratch too; with scenes, a compact batch's ids behind it)
             planes.append("attempt")
             nbytes = int(tpl.lib.gik_anchored_retry_ws_bytes(tpl._h, base._h, B))
+            if scenes is not None:
+                nbytes = (nbytes + 7) // 8 * 8 + 4 * B
         else:
             shared["ws"] = tpl.alloc_anchored_buffers(base, B)["ws"]
         if sweep:      # one workspace for all waypoints
@@ -713,8 +752,12 @@ class AnchoredProblem:
             sweep_ws = torch.empty(max(int(tpl.lib.gik_anchored_sweep_ws_bytes(tpl._h, base._h, B, sweep)) // 8, 1),
                                    dtype=torch.float64, device=tpl.device)
 
+        waypoint = iter(range(T.shape[1]))
+
         def step(T_l, q_prev, out):
-            tpl.anchored_ik(base, T_l, q_init=q_prev, out=out, clearance=True, clearance_mode=clearance_mode, **retry)
+            l = next(waypoint)
+            tpl.anchored_ik(base, T_l, q_init=q_prev, out=out, clearance=True, clearance_mode=clearance_mode, scenes=scenes,
+                            scene_id=None if ids is None else ids[l], scene_id_checked=True, **retry)
             if sweep:
                 tpl.anchored_sweep_clearance(base, q_prev, out["q"], sweep, out=out["sweep_clearance"], ws=sweep_ws)
 
@@ -726,23 +769,25 @@ class AnchoredProblem:
             raise ValueError(f"{name} must be an integer of at least 1, got {samples!r}")
         return int(samples)
 
-    def link_clearance(self, Y_full):
+    def link_clearance(self, Y_full, obstacles=None):
         """min over (link, obstacle) of the distance from the sphere to the link's capsule per goal: the host mirror of
         gik_anchored_link_clearance, the same operations in the same order.  Y_full [B, N_robot, 3] (numpy).  For a
         link from a to b and a sphere (c, r):  d = b - a, L2 = d.d, u = c - a, t = L2 > 0 ? min(max(u.d / L2, 0), 1) : 0,
         v = u - t d, value = |v| - r - link_radius.  >= 0: no part of a link is inside a sphere.  With radius 0 and the
         skeleton it is <= clearance(Y_full, include_goal=True).  No link or no obstacle: +inf; a NaN coordinate of a
-        link end: NaN for that goal."""
+        link end: NaN for that goal.  obstacles: [m, 4] (centre, radius) to measure against instead of the problem's own
+        (a scene of scene_set)."""
         Y = np.asarray(Y_full, dtype=np.float64)
         if Y.ndim == 2:
             Y = Y[None]
         B = Y.shape[0]
-        if len(self.link_rows) == 0 or len(self.obstacles) == 0:
+        obstacles = self.obstacles if obstacles is None else np.asarray(obstacles, dtype=np.float64).reshape(-1, 4)
+        if len(self.link_rows) == 0 or len(obstacles) == 0:
             return np.full(B, np.inf)
         a = Y[:, self.link_rows[:, 0], None, :]                    # [B, n_link, 1, 3]
         b = Y[:, self.link_rows[:, 1], None, :]
-        c = self.obstacles[None, None, :, :3]                     # [1, 1, n_obs, 3]
-        r2 = self.obstacles[:, 3] ** 2                            # (what the template holds: the squared radius)
+        c = obstacles[None, None, :, :3]                          # [1, 1, n_obs, 3]
+        r2 = obstacles[:, 3] ** 2                                 # (what the template holds: the squared radius)
         dot = lambda x, y: x[..., 0] * y[..., 0] + x[..., 1] * y[..., 1] + x[..., 2] * y[..., 2]   # noqa: E731
         with np.errstate(invalid="ignore", divide="ignore"):
             d = b - a
@@ -861,17 +906,24 @@ class AnchoredProblem:
             raise ValueError("sweep_clearance needs a link set: this problem was built without links")
         return self.template.anchored_sweep_clearance(self.base.template, q_a, q_b, S)
 
-    def clearance(self, Y_full, include_goal=False):
+    def clearance(self, Y_full, include_goal=False, obstacles=None):
         """min over (p-node of the robot, obstacle) of |p - centre| - radius per goal (>= 0: no joint point
         inside a sphere, the sense of graph_base.py:205-211; a link BETWEEN two joint points can still cross
         one -- link_clearance).  Y_full [B, N_robot, 3] (numpy).
         The end effector p_n sits where the goal puts it (a constant of the problem), so it only
-        counts with include_goal=True."""
+        counts with include_goal=True.  obstacles: [m, 4] (centre, radius) to measure against instead of the problem's
+        own (a scene of scene_set); none: +inf."""
         g = self.base.graph
         pn = [g.index(f"p{i}") for i in range(1, self.robot.n + (1 if include_goal else 0))]
         P = np.asarray(Y_full)[:, pn]                                            # [B, n, 3]
-        d = np.linalg.norm(P[:, :, None, :] - self.obstacles[None, None, :, :3], axis=-1)
-        return (d - self.obstacles[None, None, :, 3]).min(axis=(1, 2))
+        if obstacles is None:
+            obstacles = self.obstacles
+        else:
+            obstacles = np.asarray(obstacles, dtype=np.float64).reshape(-1, 4)
+            if len(obstacles) == 0:
+                return np.full(len(P), np.inf)
+        d = np.linalg.norm(P[:, :, None, :] - obstacles[None, None, :, :3], axis=-1)
+        return (d - obstacles[None, None, :, 3]).min(axis=(1, 2))
 
 
 # BatchProblem objects (device handles) of recent solve_batch / solve_with_riemannian calls.  The

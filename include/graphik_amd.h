@@ -686,6 +686,62 @@ int gik_anchored_ik_batch_retry(const gik_template *anch, const gik_template *ba
                                 void *d_ws, double *d_Y_full, gik_stats *d_stats, double *d_q, double *d_pos_err,
                                 double *d_rot_err, double *d_clearance, int32_t *d_attempt, void *stream);
 
+/* ---- per-goal obstacle scenes in the fixed-anchor solve (opt-in) --------------------------------
+ * An anchored template holds ONE set of spheres, the same for every goal.  A scene call takes the spheres as an ARGUMENT
+ * instead, caller-owned device memory like the goals: n_scene sets of at most 128 spheres and, per goal, which set it
+ * is solved in.  The handle stays immutable (any number of scene calls with any scene sets may be in flight on any
+ * number of streams), and the batch stays one persistent launch however many scenes it mixes: a wave restages its
+ * 4 KB obstacle table when the problem it claims names another scene than the one it holds.
+ *   - The template's own spheres are ignored by a scene call.  Its obs_node_mask, its links, their radii and hinges
+ *     apply to every scene.  gik_cost .. gik_hess keep the template's own spheres.
+ *   - The order of the spheres in a walk is the order of the scene's rows, and rows from d_n_obs[s] up to the stride are
+ *     never read.  The solve kernels' near lists are exact, so a goal solved under scene s holds, BIT FOR BIT, what the
+ *     plain call returns for it on a template created with the d_n_obs[s] rows of scene s -- whatever the other goals of
+ *     the batch use.
+ *   - d_n_obs and d_scene_id live on the device: that their entries are within 0 .. stride and 0 .. n_scene - 1 is the
+ *     CALLER'S PRECONDITION, as the distinct entries of d_idx are for a merge.  The kernels clamp what they read (an id into
+ *     [0, n_scene), a count into [0, min(stride, 128)]), so a bad entry gives a wrong answer, never an access outside
+ *     the set.  The arrays are read while the call's kernels run: keep them unchanged until the stream has passed them.
+ *
+ * gik_solve_batch_scenes: gik_solve_batch on an anchored template, with the scene builds of its solve kernel.
+ * gik_anchored_ik_batch_scenes: gik_anchored_ik_batch (d_q_init NULL: the cold start) or gik_anchored_ik_batch_seeded with
+ *   the scene solve and, where d_clearance is given, the scene clearance of the answer: that of the masked nodes
+ *   (clearance_mode = GIK_CLEARANCE_NODES) or of whole links (GIK_CLEARANCE_LINKS; links attached).
+ * gik_anchored_clearance_scenes / gik_anchored_link_clearance_scenes: the two clearances with goal b measured against
+ *   scene d_scene_id[b].  A scene without spheres: +infinity.
+ * gik_anchored_ik_batch_retry_scenes: gik_anchored_ik_batch_retry with the scene carried through attempt 0, every
+ *   compact batch (its ids are d_scene_id[d_idx[r]], gathered into the workspace) and every clearance; the rule, the
+ *   seeds and the merge are the same.  d_ws: gik_anchored_retry_ws_bytes(anch, base, B) bytes PLUS 4 B bytes (rounded
+ *   up to a multiple of 8) for the gathered ids, 8-byte aligned.
+ * Each refuses, with a message and before anything is queued: what its plain sibling refuses (a capturing stream
+ * included), a handle that is not a fixed-anchor template, a null scene set, n_scene < 1, a stride outside 0 .. 128,
+ * a null d_n_obs, a null d_obs with stride > 0, a null d_scene_id with n_scene != 1.  B == 0 returns 0.           */
+typedef struct {
+  int32_t n_scene;            /* >= 1 */
+  int32_t stride;             /* rows per scene in d_obs, 0 .. 128 */
+  const double  *d_obs;       /* [n_scene][stride][4] centre x, y, z and SQUARED radius (as gik_anchored_desc.obs) */
+  const int32_t *d_n_obs;     /* [n_scene] spheres of each scene, 0 .. stride */
+  const int32_t *d_scene_id;  /* [B] scene of each goal; NULL: every goal uses scene 0 (n_scene must be 1) */
+} gik_scene_set;
+
+int gik_solve_batch_scenes(const gik_template *t, const double *d_Y_init, const double *d_targets, int B,
+                           double *d_Y_out, gik_stats *d_stats, const gik_trace *trace /* may be NULL */,
+                           const gik_scene_set *scenes, void *stream);
+int gik_anchored_ik_batch_scenes(const gik_template *anch, const gik_template *base, const double *d_T_goal,
+                                 const double *d_q_init /* may be NULL: cold */, int B, const gik_scene_set *scenes,
+                                 double *d_ws, double *d_Y_full, gik_stats *d_stats, double *d_q, double *d_pos_err,
+                                 double *d_rot_err, double *d_clearance /* may be NULL */, int clearance_mode,
+                                 void *stream);
+int gik_anchored_clearance_scenes(const gik_template *anch, const double *d_Y_full, int B,
+                                  const gik_scene_set *scenes, double *d_clearance, void *stream);
+int gik_anchored_link_clearance_scenes(const gik_template *anch, const double *d_Y_full, int B,
+                                       const gik_scene_set *scenes, double *d_clearance, void *stream);
+int gik_anchored_ik_batch_retry_scenes(const gik_template *anch, const gik_template *base, const double *d_T_goal,
+                                       const double *d_q_init /* may be NULL */, int B,
+                                       const gik_anchored_retry_opts *opts, const gik_scene_set *scenes, void *d_ws,
+                                       double *d_Y_full, gik_stats *d_stats, double *d_q, double *d_pos_err,
+                                       double *d_rot_err, double *d_clearance, int32_t *d_attempt, void *stream);
+
 /* Duration (ms, HIP events on the call's stream) of the anchored solve kernel inside the most
  * recent gik_anchored_ik_batch / gik_anchored_ik_batch_seeded on this handle; waits for it.  < 0 if there was none. */
 double gik_anchored_last_solve_ms(const gik_template *anch);
