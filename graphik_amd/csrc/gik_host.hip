@@ -1069,45 +1069,23 @@ int gik_retry_merge(const gik_template *t, const int32_t *d_idx, int count, int 
   return retry_merge_launch(t, a, stream);
 }
 
-namespace gik {
-// The caller-owned workspace of gik_ik_batch_retry, every array sized for B failed goals:
-//   count (8 bytes) | idx [B] int32, padded to 8 bytes | poses | seed angles | targets | Y | stats | q | pos_err | rot_err
-struct RetryWs {
-  int32_t *count, *idx;
-  double *T, *q_seed, *targets, *Y, *q, *pos_err, *rot_err;
-  gik_stats *stats;
-  size_t bytes;
-};
-static RetryWs retry_ws(const gik_template *t, int B, void *base) {
-  const size_t b = (size_t)B, n = (size_t)t->pc.n_joints, pose_w = (size_t)pose_width(t);
-  WsCarve c = {reinterpret_cast<uintptr_t>(base), 0};
-  RetryWs w;
-  w.count = c.take<int32_t>(2);
-  w.idx = c.take<int32_t>(b);
-  w.T = c.take<double>(b * pose_w);
-  w.q_seed = c.take<double>(b * n);
-  w.targets = c.take<double>(b * (size_t)t->T);
-  w.Y = c.take<double>(b * (size_t)t->N * t->f.K);
-  w.stats = c.take<gik_stats>(b);
-  w.q = c.take<double>(b * n);
-  w.pos_err = c.take<double>(b);
-  w.rot_err = c.take<double>(b);
-  w.bytes = c.off;
-  return w;
+// the caller-owned workspace of gik_ik_batch_retry over d_ws (gik_plan.h), or with a null d_ws its size
+static gik::RetryWs retry_ws(const gik_template *t, int B, void *d_ws) {
+  return gik::retry_ws(t->pc.n_joints, pose_width(t), t->T, t->N, t->f.K, B, d_ws);
 }
 
 // The solve kernels take their batch size from the host: the failed-goal count comes back, the stream drains.
 static int retry_read_count(const char *entry, const int32_t *d_count, int B, int32_t *count, hipStream_t s) {
+  using gik::fail;
   HIP_OK(hipMemcpyAsync(count, d_count, sizeof(*count), hipMemcpyDeviceToHost, s));
   HIP_OK(hipStreamSynchronize(s));
   if (*count < 0 || *count > B) return fail(std::string(entry) + ": the failed-goal count came back out of range");
   return 0;
 }
-}  // namespace gik
 
 size_t gik_retry_ws_bytes(const gik_template *t, int B) {
   if (!t || !t->has_pipe || B < 0) return 0;
-  return gik::retry_ws(t, B, nullptr).bytes;
+  return retry_ws(t, B, nullptr).bytes;
 }
 
 int gik_ik_batch_retry(const gik_template *t, const double *d_T_goal, const double *d_q_init, int B,
@@ -1156,6 +1134,13 @@ int gik_ik_batch_retry(const gik_template *t, const double *d_T_goal, const doub
   }
   return 0;
 }
+
+// ---- the fixed-anchor (obstacle) solve on the robot graph's pipeline -------------------------------------------------
+// Every solve entry -- cold, seeded, with scenes, and each attempt of the two restart loops -- refuses what it has always
+// refused, under its own name, and then queues its work through anchored_attempt, the one place that writes the launch
+// sequence.  The four clearance exports are anchored_clearance_entry with two booleans; clearance_mode_refusal is the mode
+// check of the scene entry and the restart loops.  The helpers stand in order of use.  The layouts of the caller-owned
+// workspaces are gik_plan.h's; the wrappers here read their integers off the handles.
 
 // the scratch of one anchored call over d_ws (gik_plan.h), or with a null d_ws its size
 static gik::AnchWs anch_ws(const gik_template *anch, const gik_template *base, int B, double *d_ws) {
@@ -1243,16 +1228,71 @@ static int anchored_clearance_launch(const gik_template *anch, const double *d_Y
   HIP_OK(hipGetLastError());
   return 0;
 }
-static int anchored_link_clearance_launch(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance,
-                                          void *stream, const gik_scene_set *scenes = nullptr);
 
-// The end of the cold and the seeded anchored call: the solve from g.Y_free between the event pair of
-// gik_anchored_last_solve_ms, the gather into g.Y_full_out, the recovery and, where d_clearance is given, the clearance: of the
-// masked nodes, or with link_clear of whole links.  scenes: a checked scene set for the solve and the clearance, or null.
-static int anchored_solve_tail(const gik_template *anch, const gik_template *base, const gik::AnchGlueArgs &g, gik_stats *d_stats,
-                               double *d_q, double *d_pos_err, double *d_rot_err, double *d_clearance, void *stream,
-                               const gik_scene_set *scenes = nullptr, bool link_clear = false) {
+// the same of whole links (gik_anchored_attach_links; gik_anch_seed.hip.h)
+static int anchored_link_clearance_launch(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance,
+                                          void *stream, const gik_scene_set *scenes = nullptr) {
   using namespace gik;
+  AnchLinkArgs c;
+  c.Y_full = d_Y_full;
+  c.obs = scenes ? scenes->d_obs : anch->an.obs;
+  c.link_a = anch->d_link_a;
+  c.link_b = anch->d_link_b;
+  c.link_rho = anch->d_link_rho;
+  c.clearance = d_clearance;
+  c.B = B;
+  c.full_N = anch->full_N;
+  c.n_link = anch->n_link;
+  c.n_obs = scenes ? 0 : anch->an.n_obs;
+  const dim3 grid(std::min(B, anch->f.n_cu * 32));
+  if (scenes)
+    hipLaunchKernelGGL(anch_link_clearance_scene_kernel, grid, dim3(WAVE), 0, (hipStream_t)stream, c, scene_args(scenes));
+  else
+    hipLaunchKernelGGL(anch_link_clearance_kernel, grid, dim3(WAVE), 0, (hipStream_t)stream, c);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// the start point from joint-configuration seeds (gik_anch_seed.hip.h): seed_kernel on the robot graph into the workspace,
+// then the row gather + goal anchors
+static int anchored_seed_launch(const gik_template *anch, const gik_template *base, const double *d_T_goal,
+                                const double *d_q_init, int B, double *d_ws, double *Y_free, double *goal, void *stream) {
+  using namespace gik;
+  const AnchWs w = anch_ws(anch, base, B, d_ws);      // (its head: Y_free and goal may be the caller's own arrays)
+  const int rc = gik_seed_batch(base, d_T_goal, d_q_init, B, w.targets, w.Y_full0, stream);
+  if (rc) return rc;
+  const AnchGlueArgs g = anch_glue_args(anch, d_T_goal, B, w.Y_full0, Y_free, goal, nullptr);
+  const size_t n = (size_t)B * ((size_t)g.Nf + (size_t)g.n_goal) * 3;
+  hipLaunchKernelGGL(anch_scatter_kernel, dim3((unsigned)((n + ANCH_SCATTER_NT - 1) / ANCH_SCATTER_NT)), dim3(ANCH_SCATTER_NT),
+                     0, (hipStream_t)stream, g);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// One anchored solve on checked arguments, B > 0: what every solve entry and every restart queues.  The start point, cold
+// (d_q_init null: the robot graph's prepare, fitted to the anchors) or seeded; the solve between the event pair of
+// gik_anchored_last_solve_ms; the gather into d_Y_full; the recovery; and, where d_clearance is given, the clearance of the
+// answer: of the masked nodes, or with link_clear of whole links.  scenes: a checked scene set for the solve and the
+// clearance, or null: the template's own obstacles.
+static int anchored_attempt(const gik_template *anch, const gik_template *base, const double *d_T_goal, const double *d_q_init,
+                            int B, const gik_scene_set *scenes, double *d_ws, double *d_Y_full, gik_stats *d_stats, double *d_q,
+                            double *d_pos_err, double *d_rot_err, double *d_clearance, bool link_clear, void *stream) {
+  using namespace gik;
+  const AnchWs w = anch_ws(anch, base, B, d_ws);
+  AnchGlueArgs g;
+  if (d_q_init) {      // (read here and nowhere later: d_q_init may be d_q)
+    const int rc = anchored_seed_launch(anch, base, d_T_goal, d_q_init, B, d_ws, w.Y_free, w.goal, stream);
+    if (rc) return rc;
+    g = anch_glue_args(anch, d_T_goal, B, nullptr, w.Y_free, w.goal, d_Y_full);
+  } else {
+    // initial point of the robot graph (bound smoothing + MDS, obstacles play no part in it) ...
+    const int rc = gik_prepare_batch(base, d_T_goal, B, w.targets, w.Y_full0, nullptr, stream);
+    if (rc) return rc;
+    g = anch_glue_args(anch, d_T_goal, B, w.Y_full0, w.Y_free, w.goal, d_Y_full);
+    // ... mapped onto the world frame by its anchors; free rows = anchored start point
+    hipLaunchKernelGGL(anch_init_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, g);
+    HIP_OK(hipGetLastError());
+  }
   // timing events around the solve (diagnostics only; created with the handle).  The pair is
   // recorded under a lock so that gik_anchored_last_solve_ms never reads a half-recorded pair;
   // with concurrent callers it reports whichever call recorded last.
@@ -1276,13 +1316,6 @@ static int anchored_solve_tail(const gik_template *anch, const gik_template *bas
                     : anchored_clearance_launch(anch, g.Y_full_out, g.B, d_clearance, stream, scenes);
 }
 
-// One anchored solve on checked arguments, cold (d_q_init null: prepare + Procrustes fit) or seeded, with the clearance of
-// the answer where d_clearance is given; scenes as above.  What gik_anchored_ik_batch / _seeded queue, through one door:
-// the restart loop and the scene entry use it.
-static int anchored_attempt(const gik_template *anch, const gik_template *base, const double *d_T_goal, const double *d_q_init,
-                            int B, const gik_scene_set *scenes, double *d_ws, double *d_Y_full, gik_stats *d_stats, double *d_q,
-                            double *d_pos_err, double *d_rot_err, double *d_clearance, bool link_clear, void *stream);
-
 int gik_anchored_ik_batch(const gik_template *anch, const gik_template *base, const double *d_T_goal, int B,
                           double *d_ws, double *d_Y_full, gik_stats *d_stats, double *d_q,
                           double *d_pos_err, double *d_rot_err, void *stream) {
@@ -1291,18 +1324,10 @@ int gik_anchored_ik_batch(const gik_template *anch, const gik_template *base, co
   if (const std::string why = anchored_pair_fault(anch, base, PAIR_3D); !why.empty()) return fail("gik_anchored_ik_batch: " + why);
   if (B == 0) return 0;
   if (!d_T_goal || !d_ws || !d_Y_full || !d_stats || !d_q || !d_pos_err || !d_rot_err) return fail("null buffer");
-  const AnchWs w = anch_ws(anch, base, B, d_ws);
-  // initial point of the robot graph (bound smoothing + MDS, obstacles play no part in it) ...
-  int rc = gik_prepare_batch(base, d_T_goal, B, w.targets, w.Y_full0, nullptr, stream);
-  if (rc) return rc;
-  const AnchGlueArgs g = anch_glue_args(anch, d_T_goal, B, w.Y_full0, w.Y_free, w.goal, d_Y_full);
-  // ... mapped onto the world frame by its anchors; free rows = anchored start point
-  hipLaunchKernelGGL(anch_init_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, g);
-  HIP_OK(hipGetLastError());
-  return anchored_solve_tail(anch, base, g, d_stats, d_q, d_pos_err, d_rot_err, nullptr, stream);
+  return anchored_attempt(anch, base, d_T_goal, nullptr, B, nullptr, d_ws, d_Y_full, d_stats, d_q, d_pos_err, d_rot_err, nullptr,
+                          false, stream);
 }
 
-// ---- the anchored solve from joint-configuration seeds (gik_anch_seed.hip.h) --------------------------
 // what the seeded anchored calls refuse, before anything is queued
 static int anchored_seed_refusal(const char *entry, const gik_template *anch, const gik_template *base, const double *d_q_init,
                                  int B, void *stream) {
@@ -1315,21 +1340,6 @@ static int anchored_seed_refusal(const char *entry, const gik_template *anch, co
   return 0;
 }
 
-// seed_kernel on the robot graph into the workspace, then the row gather + goal anchors
-static int anchored_seed_launch(const gik_template *anch, const gik_template *base, const double *d_T_goal,
-                                const double *d_q_init, int B, double *d_ws, double *Y_free, double *goal, void *stream) {
-  using namespace gik;
-  const AnchWs w = anch_ws(anch, base, B, d_ws);      // (its head: Y_free and goal may be the caller's own arrays)
-  const int rc = gik_seed_batch(base, d_T_goal, d_q_init, B, w.targets, w.Y_full0, stream);
-  if (rc) return rc;
-  const AnchGlueArgs g = anch_glue_args(anch, d_T_goal, B, w.Y_full0, Y_free, goal, nullptr);
-  const size_t n = (size_t)B * ((size_t)g.Nf + (size_t)g.n_goal) * 3;
-  hipLaunchKernelGGL(anch_scatter_kernel, dim3((unsigned)((n + ANCH_SCATTER_NT - 1) / ANCH_SCATTER_NT)), dim3(ANCH_SCATTER_NT),
-                     0, (hipStream_t)stream, g);
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
 int gik_anchored_seed_batch(const gik_template *anch, const gik_template *base, const double *d_T_goal,
                             const double *d_q_init, int B, double *d_ws, double *d_Y_free, double *d_goal, void *stream) {
   if (anchored_seed_refusal("gik_anchored_seed_batch", anch, base, d_q_init, B, stream)) return -1;
@@ -1338,17 +1348,81 @@ int gik_anchored_seed_batch(const gik_template *anch, const gik_template *base, 
   return anchored_seed_launch(anch, base, d_T_goal, d_q_init, B, d_ws, d_Y_free, d_goal, stream);
 }
 
-int gik_anchored_clearance(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance, void *stream) {
-  using gik::fail;
-  if (!anch || B < 0) return fail("gik_anchored_clearance: bad argument");
-  if (!anch->anchored) return fail("gik_anchored_clearance: the handle must be a fixed-anchor template (gik_template_create_anchored)");
-  if (refuse_capture("gik_anchored_clearance", stream)) return -1;
+int gik_anchored_ik_batch_seeded(const gik_template *anch, const gik_template *base, const double *d_T_goal,
+                                 const double *d_q_init, int B, double *d_ws, double *d_Y_full, gik_stats *d_stats,
+                                 double *d_q, double *d_pos_err, double *d_rot_err, double *d_clearance, void *stream) {
+  if (anchored_seed_refusal("gik_anchored_ik_batch_seeded", anch, base, d_q_init, B, stream)) return -1;
   if (B == 0) return 0;
-  if (!d_Y_full || !d_clearance) return fail("gik_anchored_clearance: null buffer");
-  return anchored_clearance_launch(anch, d_Y_full, B, d_clearance, stream);
+  if (!d_T_goal || !d_ws || !d_Y_full || !d_stats || !d_q || !d_pos_err || !d_rot_err)
+    return gik::fail("gik_anchored_ik_batch_seeded: null buffer");
+  return anchored_attempt(anch, base, d_T_goal, d_q_init, B, nullptr, d_ws, d_Y_full, d_stats, d_q, d_pos_err, d_rot_err,
+                          d_clearance, false, stream);
 }
 
-// ---- clearance of whole links, and its sweep between two configurations (gik_anch_seed.hip.h) -----------
+// what a call that takes a clearance_mode refuses about it, under the entry's name e
+static int clearance_mode_refusal(const std::string &e, const gik_template *anch, int clearance_mode) {
+  using gik::fail;
+  if (clearance_mode != GIK_CLEARANCE_NODES && clearance_mode != GIK_CLEARANCE_LINKS)
+    return fail(e + ": clearance_mode must be GIK_CLEARANCE_NODES (0) or GIK_CLEARANCE_LINKS (1)");
+  if (clearance_mode == GIK_CLEARANCE_LINKS && anch->n_link < 0)
+    return fail(e + ": clearance_mode = links, but no links attached (gik_anchored_attach_links)");
+  return 0;
+}
+
+// ---- per-goal obstacle scenes: the solve entry (the solve kernel's: gik_solve_batch_scenes) ----
+int gik_anchored_ik_batch_scenes(const gik_template *anch, const gik_template *base, const double *d_T_goal,
+                                 const double *d_q_init, int B, const gik_scene_set *scenes, double *d_ws, double *d_Y_full,
+                                 gik_stats *d_stats, double *d_q, double *d_pos_err, double *d_rot_err, double *d_clearance,
+                                 int clearance_mode, void *stream) {
+  using namespace gik;
+  const std::string e("gik_anchored_ik_batch_scenes");
+  if (!anch || !base || B < 0) return fail(e + ": bad argument");
+  if (const std::string why = anchored_pair_fault(anch, base, PAIR_3D | (d_q_init ? PAIR_SEEDABLE : 0)); !why.empty())
+    return fail(e + ": " + why);
+  if (scene_refusal("gik_anchored_ik_batch_scenes", anch, scenes)) return -1;
+  if (clearance_mode_refusal(e, anch, clearance_mode)) return -1;
+  if (refuse_capture("gik_anchored_ik_batch_scenes", stream)) return -1;
+  if (B == 0) return 0;
+  if (!d_T_goal || !d_ws || !d_Y_full || !d_stats || !d_q || !d_pos_err || !d_rot_err) return fail(e + ": null buffer");
+  return anchored_attempt(anch, base, d_T_goal, d_q_init, B, scenes, d_ws, d_Y_full, d_stats, d_q, d_pos_err, d_rot_err,
+                          d_clearance, clearance_mode == GIK_CLEARANCE_LINKS, stream);
+}
+
+// ---- the clearance of an answer: of the masked nodes or of whole links, against the template's obstacles or per-goal scenes ----
+static int anchored_clearance_entry(const char *entry, const gik_template *anch, bool links, bool with_scenes,
+                                    const gik_scene_set *scenes, const double *d_Y_full, int B, double *d_clearance, void *stream) {
+  using gik::fail;
+  const std::string e(entry);
+  if (!anch || B < 0) return fail(e + ": bad argument");
+  if (with_scenes) {
+    if (scene_refusal(entry, anch, scenes)) return -1;
+  } else if (!anch->anchored) {
+    return fail(e + ": the handle must be a fixed-anchor template (gik_template_create_anchored)");
+  }
+  if (links && anch->n_link < 0) return fail(e + ": no links attached (gik_anchored_attach_links)");
+  if (refuse_capture(entry, stream)) return -1;
+  if (B == 0) return 0;
+  if (!d_Y_full || !d_clearance) return fail(e + ": null buffer");
+  return links ? anchored_link_clearance_launch(anch, d_Y_full, B, d_clearance, stream, scenes)      // (scenes: null without)
+               : anchored_clearance_launch(anch, d_Y_full, B, d_clearance, stream, scenes);
+}
+
+int gik_anchored_clearance(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance, void *stream) {
+  return anchored_clearance_entry("gik_anchored_clearance", anch, false, false, nullptr, d_Y_full, B, d_clearance, stream);
+}
+int gik_anchored_link_clearance(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance, void *stream) {
+  return anchored_clearance_entry("gik_anchored_link_clearance", anch, true, false, nullptr, d_Y_full, B, d_clearance, stream);
+}
+int gik_anchored_clearance_scenes(const gik_template *anch, const double *d_Y_full, int B, const gik_scene_set *scenes,
+                                  double *d_clearance, void *stream) {
+  return anchored_clearance_entry("gik_anchored_clearance_scenes", anch, false, true, scenes, d_Y_full, B, d_clearance, stream);
+}
+int gik_anchored_link_clearance_scenes(const gik_template *anch, const double *d_Y_full, int B, const gik_scene_set *scenes,
+                                       double *d_clearance, void *stream) {
+  return anchored_clearance_entry("gik_anchored_link_clearance_scenes", anch, true, true, scenes, d_Y_full, B, d_clearance, stream);
+}
+
+// ---- the links of the link clearance, and its sweep between two configurations (gik_anch_seed.hip.h) -----------
 int gik_anchored_attach_links(gik_template *anch, const gik_link_desc *d) {
   using namespace gik;
   const std::string e("gik_anchored_attach_links");
@@ -1397,91 +1471,16 @@ int gik_anchored_attach_links(gik_template *anch, const gik_link_desc *d) {
   return 0;
 }
 
-static int anchored_link_clearance_launch(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance,
-                                          void *stream, const gik_scene_set *scenes) {
-  using namespace gik;
-  AnchLinkArgs c;
-  c.Y_full = d_Y_full;
-  c.obs = scenes ? scenes->d_obs : anch->an.obs;
-  c.link_a = anch->d_link_a;
-  c.link_b = anch->d_link_b;
-  c.link_rho = anch->d_link_rho;
-  c.clearance = d_clearance;
-  c.B = B;
-  c.full_N = anch->full_N;
-  c.n_link = anch->n_link;
-  c.n_obs = scenes ? 0 : anch->an.n_obs;
-  const dim3 grid(std::min(B, anch->f.n_cu * 32));
-  if (scenes)
-    hipLaunchKernelGGL(anch_link_clearance_scene_kernel, grid, dim3(WAVE), 0, (hipStream_t)stream, c, scene_args(scenes));
-  else
-    hipLaunchKernelGGL(anch_link_clearance_kernel, grid, dim3(WAVE), 0, (hipStream_t)stream, c);
-  HIP_OK(hipGetLastError());
-  return 0;
+// the caller-owned workspace of gik_anchored_sweep_clearance over d_ws (gik_plan.h), or with a null d_ws its size
+static gik::AnchSweepWs anch_sweep_ws(const gik_template *anch, const gik_template *base, int B, int S, double *d_ws) {
+  return gik::anch_sweep_ws(base->pc.n_joints, pose_width(base), base->T, anch->full_N, B, S, d_ws);
 }
-
-int gik_anchored_link_clearance(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance, void *stream) {
-  using gik::fail;
-  if (!anch || B < 0) return fail("gik_anchored_link_clearance: bad argument");
-  if (!anch->anchored) return fail("gik_anchored_link_clearance: the handle must be a fixed-anchor template (gik_template_create_anchored)");
-  if (anch->n_link < 0) return fail("gik_anchored_link_clearance: no links attached (gik_anchored_attach_links)");
-  if (refuse_capture("gik_anchored_link_clearance", stream)) return -1;
-  if (B == 0) return 0;
-  if (!d_Y_full || !d_clearance) return fail("gik_anchored_link_clearance: null buffer");
-  return anchored_link_clearance_launch(anch, d_Y_full, B, d_clearance, stream);
-}
-
-// ---- per-goal obstacle scenes: the two clearances (the solve: gik_solve_batch_scenes) ----
-int gik_anchored_clearance_scenes(const gik_template *anch, const double *d_Y_full, int B, const gik_scene_set *scenes,
-                                  double *d_clearance, void *stream) {
-  using gik::fail;
-  if (!anch || B < 0) return fail("gik_anchored_clearance_scenes: bad argument");
-  if (scene_refusal("gik_anchored_clearance_scenes", anch, scenes)) return -1;
-  if (refuse_capture("gik_anchored_clearance_scenes", stream)) return -1;
-  if (B == 0) return 0;
-  if (!d_Y_full || !d_clearance) return fail("gik_anchored_clearance_scenes: null buffer");
-  return anchored_clearance_launch(anch, d_Y_full, B, d_clearance, stream, scenes);
-}
-
-int gik_anchored_link_clearance_scenes(const gik_template *anch, const double *d_Y_full, int B, const gik_scene_set *scenes,
-                                       double *d_clearance, void *stream) {
-  using gik::fail;
-  if (!anch || B < 0) return fail("gik_anchored_link_clearance_scenes: bad argument");
-  if (scene_refusal("gik_anchored_link_clearance_scenes", anch, scenes)) return -1;
-  if (anch->n_link < 0) return fail("gik_anchored_link_clearance_scenes: no links attached (gik_anchored_attach_links)");
-  if (refuse_capture("gik_anchored_link_clearance_scenes", stream)) return -1;
-  if (B == 0) return 0;
-  if (!d_Y_full || !d_clearance) return fail("gik_anchored_link_clearance_scenes: null buffer");
-  return anchored_link_clearance_launch(anch, d_Y_full, B, d_clearance, stream, scenes);
-}
-
-// The caller-owned workspace of gik_anchored_sweep_clearance, M = B (S + 1) configurations, all doubles:
-//   q_s [M][n] | identity poses [M][pose_w] | seed_kernel's targets [M][T_base] (not read) | Y [M][full_N*3] | clearance [M]
-namespace gik {
-struct AnchSweepWs {
-  double *q, *T, *targets, *Y, *cl;
-  size_t doubles;
-};
-static AnchSweepWs anch_sweep_ws(const gik_template *anch, const gik_template *base, int B, int S, double *ws) {
-  const size_t M = (size_t)B * ((size_t)S + 1), n = (size_t)base->pc.n_joints;
-  const size_t pose_w = (size_t)pose_width(base);
-  WsCarve c = {reinterpret_cast<uintptr_t>(ws), 0};
-  AnchSweepWs w;
-  w.q = c.take<double>(M * n);
-  w.T = c.take<double>(M * pose_w);
-  w.targets = c.take<double>(M * (size_t)base->T);
-  w.Y = c.take<double>(M * (size_t)anch->full_N * 3);
-  w.cl = c.take<double>(M);
-  w.doubles = c.off / sizeof(double);
-  return w;
-}
-}  // namespace gik
 
 size_t gik_anchored_sweep_ws_bytes(const gik_template *anch, const gik_template *base, int B, int samples) {
   if (!anch || !base || !anchored_pair_fault(anch, base, 0).empty() || B < 0 || samples < 1 ||
       (size_t)B * ((size_t)samples + 1) > (size_t)INT_MAX)
     return 0;
-  return gik::anch_sweep_ws(anch, base, B, samples, nullptr).doubles * sizeof(double);
+  return anch_sweep_ws(anch, base, B, samples, nullptr).doubles * sizeof(double);
 }
 
 int gik_anchored_sweep_clearance(const gik_template *anch, const gik_template *base, const double *d_q_a,
@@ -1527,63 +1526,6 @@ int gik_anchored_sweep_clearance(const gik_template *anch, const gik_template *b
                      (hipStream_t)stream, ma);
   HIP_OK(hipGetLastError());
   return 0;
-}
-
-int gik_anchored_ik_batch_seeded(const gik_template *anch, const gik_template *base, const double *d_T_goal,
-                                 const double *d_q_init, int B, double *d_ws, double *d_Y_full, gik_stats *d_stats,
-                                 double *d_q, double *d_pos_err, double *d_rot_err, double *d_clearance, void *stream) {
-  using namespace gik;
-  if (anchored_seed_refusal("gik_anchored_ik_batch_seeded", anch, base, d_q_init, B, stream)) return -1;
-  if (B == 0) return 0;
-  if (!d_T_goal || !d_ws || !d_Y_full || !d_stats || !d_q || !d_pos_err || !d_rot_err)
-    return fail("gik_anchored_ik_batch_seeded: null buffer");
-  const AnchWs w = anch_ws(anch, base, B, d_ws);
-  // the seed angles are read here and nowhere later: d_q_init may be d_q
-  int rc = anchored_seed_launch(anch, base, d_T_goal, d_q_init, B, d_ws, w.Y_free, w.goal, stream);
-  if (rc) return rc;
-  return anchored_solve_tail(anch, base, anch_glue_args(anch, d_T_goal, B, nullptr, w.Y_free, w.goal, d_Y_full), d_stats, d_q,
-                             d_pos_err, d_rot_err, d_clearance, stream);
-}
-
-static int anchored_attempt(const gik_template *anch, const gik_template *base, const double *d_T_goal, const double *d_q_init,
-                            int B, const gik_scene_set *scenes, double *d_ws, double *d_Y_full, gik_stats *d_stats, double *d_q,
-                            double *d_pos_err, double *d_rot_err, double *d_clearance, bool link_clear, void *stream) {
-  using namespace gik;
-  const AnchWs w = anch_ws(anch, base, B, d_ws);
-  AnchGlueArgs g;
-  if (d_q_init) {      // (read here and nowhere later: d_q_init may be d_q)
-    const int rc = anchored_seed_launch(anch, base, d_T_goal, d_q_init, B, d_ws, w.Y_free, w.goal, stream);
-    if (rc) return rc;
-    g = anch_glue_args(anch, d_T_goal, B, nullptr, w.Y_free, w.goal, d_Y_full);
-  } else {
-    const int rc = gik_prepare_batch(base, d_T_goal, B, w.targets, w.Y_full0, nullptr, stream);
-    if (rc) return rc;
-    g = anch_glue_args(anch, d_T_goal, B, w.Y_full0, w.Y_free, w.goal, d_Y_full);
-    hipLaunchKernelGGL(anch_init_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, g);
-    HIP_OK(hipGetLastError());
-  }
-  return anchored_solve_tail(anch, base, g, d_stats, d_q, d_pos_err, d_rot_err, d_clearance, stream, scenes, link_clear);
-}
-
-int gik_anchored_ik_batch_scenes(const gik_template *anch, const gik_template *base, const double *d_T_goal,
-                                 const double *d_q_init, int B, const gik_scene_set *scenes, double *d_ws, double *d_Y_full,
-                                 gik_stats *d_stats, double *d_q, double *d_pos_err, double *d_rot_err, double *d_clearance,
-                                 int clearance_mode, void *stream) {
-  using namespace gik;
-  const std::string e("gik_anchored_ik_batch_scenes");
-  if (!anch || !base || B < 0) return fail(e + ": bad argument");
-  if (const std::string why = anchored_pair_fault(anch, base, PAIR_3D | (d_q_init ? PAIR_SEEDABLE : 0)); !why.empty())
-    return fail(e + ": " + why);
-  if (scene_refusal("gik_anchored_ik_batch_scenes", anch, scenes)) return -1;
-  if (clearance_mode != GIK_CLEARANCE_NODES && clearance_mode != GIK_CLEARANCE_LINKS)
-    return fail(e + ": clearance_mode must be GIK_CLEARANCE_NODES (0) or GIK_CLEARANCE_LINKS (1)");
-  const bool links = clearance_mode == GIK_CLEARANCE_LINKS;
-  if (links && anch->n_link < 0) return fail(e + ": clearance_mode = links, but no links attached (gik_anchored_attach_links)");
-  if (refuse_capture("gik_anchored_ik_batch_scenes", stream)) return -1;
-  if (B == 0) return 0;
-  if (!d_T_goal || !d_ws || !d_Y_full || !d_stats || !d_q || !d_pos_err || !d_rot_err) return fail(e + ": null buffer");
-  return anchored_attempt(anch, base, d_T_goal, d_q_init, B, scenes, d_ws, d_Y_full, d_stats, d_q, d_pos_err, d_rot_err,
-                          d_clearance, links, stream);
 }
 
 // ---- restarts in the anchored solve: the kernels of gik_retry.hip.h with a clearance in the rule -------------
@@ -1637,46 +1579,18 @@ int gik_anchored_retry_merge(const gik_template *anch, const gik_template *base,
   return retry_merge_launch(base, a, stream);
 }
 
-// The caller-owned workspace of gik_anchored_ik_batch_retry, every array sized for B failed goals:
-//   the scratch of one anchored call (gik_anchored_ws_doubles; attempt 0 and every restart use it in turn) |
-//   count (8 bytes) | idx [B] int32, padded to 8 bytes | poses | seed angles | centre angles | Y_full | stats | q |
-//   pos_err | rot_err | clearance
-namespace gik {
-struct AnchRetryWs {
-  double *scratch;
-  int32_t *count, *idx;
-  double *T, *q_seed, *q_center, *Y, *q, *pos_err, *rot_err, *clearance;
-  gik_stats *stats;
-  size_t bytes;
-};
-static AnchRetryWs anch_retry_ws(const gik_template *anch, const gik_template *base, int B, void *ws) {
-  const size_t b = (size_t)B, n = (size_t)base->pc.n_joints, pose_w = (size_t)pose_width(base);
-  WsCarve c = {reinterpret_cast<uintptr_t>(ws), 0};
-  AnchRetryWs w;
-  w.scratch = c.take<double>(gik_anchored_ws_doubles(anch, base, B));
-  w.count = c.take<int32_t>(2);
-  w.idx = c.take<int32_t>(b);
-  w.T = c.take<double>(b * pose_w);
-  w.q_seed = c.take<double>(b * n);
-  w.q_center = c.take<double>(b * n);
-  w.Y = c.take<double>(b * (size_t)anch->full_N * 3);
-  w.stats = c.take<gik_stats>(b);
-  w.q = c.take<double>(b * n);
-  w.pos_err = c.take<double>(b);
-  w.rot_err = c.take<double>(b);
-  w.clearance = c.take<double>(b);
-  w.bytes = c.off;
-  return w;
+// the caller-owned workspace of the anchored restart loops over d_ws (gik_plan.h), or with a null d_ws its size
+static gik::AnchRetryWs anch_retry_ws(const gik_template *anch, const gik_template *base, int B, void *d_ws) {
+  return gik::anch_retry_ws(base->pc.n_joints, pose_width(base), base->T, base->N, anch->N, anch->an.n_goal, anch->full_N, B, d_ws);
 }
-}  // namespace gik
 
 size_t gik_anchored_retry_ws_bytes(const gik_template *anch, const gik_template *base, int B) {
   if (!anch || !base || !anchored_pair_fault(anch, base, 0).empty() || B < 0) return 0;
-  return gik::anch_retry_ws(anch, base, B, nullptr).bytes;
+  return anch_retry_ws(anch, base, B, nullptr).bytes;      // (without the scene entry's ids)
 }
 
 // The restart loop of gik_anchored_ik_batch_retry and, with a scene set, of gik_anchored_ik_batch_retry_scenes: the scene
-// goes through attempt 0, every compact batch (ids gathered behind the workspace's plain layout) and every clearance.
+// goes through attempt 0, every compact batch (its ids gathered into the workspace's last array) and every clearance.
 static int anchored_retry_impl(const char *entry, const gik_template *anch, const gik_template *base, const double *d_T_goal,
                                const double *d_q_init, int B, const gik_anchored_retry_opts *opts, const gik_scene_set *scenes,
                                bool with_scenes, void *d_ws, double *d_Y_full, gik_stats *d_stats, double *d_q, double *d_pos_err,
@@ -1688,10 +1602,8 @@ static int anchored_retry_impl(const char *entry, const gik_template *anch, cons
   if (const std::string why = anchored_pair_fault(anch, base, PAIR_3D); !why.empty()) return fail(e + ": " + why);
   if (with_scenes && scene_refusal(entry, anch, scenes)) return -1;
   if (opts->retries < 0 || opts->retries > 63) return fail(e + ": retries must be within 0 .. 63");
-  if (opts->clearance_mode != GIK_CLEARANCE_NODES && opts->clearance_mode != GIK_CLEARANCE_LINKS)
-    return fail(e + ": clearance_mode must be GIK_CLEARANCE_NODES (0) or GIK_CLEARANCE_LINKS (1)");
+  if (clearance_mode_refusal(e, anch, opts->clearance_mode)) return -1;
   const bool links = opts->clearance_mode == GIK_CLEARANCE_LINKS;
-  if (links && anch->n_link < 0) return fail(e + ": clearance_mode = links, but no links attached (gik_anchored_attach_links)");
   if ((d_q_init || opts->retries > 0) && !base->seed_ok)
     return fail(e + ": the base graph cannot be seeded on the device: " + base->seed_why);
   if (opts->retries > 0) {
@@ -1716,12 +1628,10 @@ static int anchored_retry_impl(const char *entry, const gik_template *anch, cons
   // the centre of local mode is what attempt 0 started from; d_q_init may be d_q, which attempt 0 overwrites
   if (local) HIP_OK(hipMemcpyAsync(w.q_center, d_q_init, (size_t)B * n * sizeof(double), hipMemcpyDeviceToDevice, s));
   HIP_OK(hipMemsetAsync(d_attempt, 0, (size_t)B * sizeof(int32_t), s));
-  // the scene ids of a compact batch: [B] int32 behind the plain layout (the scene entry's workspace is that much longer)
-  int32_t *ids_r = reinterpret_cast<int32_t *>(static_cast<char *>(d_ws) + ((w.bytes + 7) & ~(size_t)7));
-  gik_scene_set compact;
+  gik_scene_set compact;      // the scene set of a compact batch: its ids are gathered into w.ids
   if (scenes) {
     compact = *scenes;
-    if (scenes->d_scene_id) compact.d_scene_id = ids_r;
+    if (scenes->d_scene_id) compact.d_scene_id = w.ids;
   }
   // link mode: the rule below is the same, the array it reads holds the clearance of whole links
   int rc = anchored_attempt(anch, base, d_T_goal, d_q_init, B, scenes, w.scratch, d_Y_full, d_stats, d_q, d_pos_err, d_rot_err,
@@ -1740,7 +1650,7 @@ static int anchored_retry_impl(const char *entry, const gik_template *anch, cons
     if (rc) return rc;
     if (scenes && scenes->d_scene_id) {
       hipLaunchKernelGGL(scene_gather_kernel, dim3((count + ANCH_SCATTER_NT - 1) / ANCH_SCATTER_NT), dim3(ANCH_SCATTER_NT), 0, s,
-                         scenes->d_scene_id, w.idx, count, ids_r);
+                         scenes->d_scene_id, w.idx, count, w.ids);
       HIP_OK(hipGetLastError());
     }
     rc = anchored_attempt(anch, base, w.T, w.q_seed, count, scenes ? &compact : nullptr, w.scratch, w.Y, w.stats, w.q, w.pos_err,

@@ -1,14 +1,17 @@
 // graphik_amd/csrc/gik_plan.h -- the scheduling decisions of one batch call (gik_solve_batch): which kernel runs,
 // its grid, the time slice, whether the tail is spread, the queue capacities and the layout of the pooled workspace.
 // Below it the same for the device prepare (gik_pipeline_attach: which of the six prepare kernels, its LDS bytes, waves per
-// CU, slab and grids) and the layout of the anchored calls' scratch.
+// CU, slab and grids) and the layouts of the caller-owned workspaces: the anchored calls' scratch, the two restart loops'
+// and the sweep's.
 // Integer arithmetic over facts that are fixed at template creation or at attach, plus the batch size: plain C++17, no
-// HIP, so that tests/host/solve_plan_table.cpp and prep_plan_table.cpp can tabulate it without a device.
+// HIP, so that tests/host/solve_plan_table.cpp, prep_plan_table.cpp and ws_layout_table.cpp can tabulate it without a device.
 #pragma once
 
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+
+#include "../../include/graphik_amd.h"      // (gik_stats, 48 bytes, in the restart workspaces; after <cstddef>: it uses size_t)
 
 namespace gik {
 
@@ -333,6 +336,88 @@ inline AnchWs anch_ws(int base_T, int base_N, int free_N, int n_goal, int B, dou
   w.Y_free = c.take<double>(b * (size_t)free_N * 3);
   w.goal = c.take<double>(b * (size_t)n_goal * 3);
   w.doubles = c.off / sizeof(double);
+  return w;
+}
+
+// The workspace of gik_ik_batch_retry (gik_retry_ws_bytes), every array sized for B failed goals; n joints, pose_w doubles
+// per goal pose, the template's T terms and N nodes in K dimensions:
+//   count (8 bytes) | idx [B] int32, padded to 8 bytes | poses | seed angles | targets | Y | stats | q | pos_err | rot_err
+struct RetryWs {
+  int32_t *count, *idx;
+  double *T, *q_seed, *targets, *Y, *q, *pos_err, *rot_err;
+  gik_stats *stats;
+  size_t bytes;
+};
+inline RetryWs retry_ws(int n_joints, int pose_w, int T, int N, int K, int B, void *base) {
+  const size_t b = (size_t)B, n = (size_t)n_joints;
+  WsCarve c = {reinterpret_cast<uintptr_t>(base), 0};
+  RetryWs w;
+  w.count = c.take<int32_t>(2);
+  w.idx = c.take<int32_t>(b);
+  w.T = c.take<double>(b * (size_t)pose_w);
+  w.q_seed = c.take<double>(b * n);
+  w.targets = c.take<double>(b * (size_t)T);
+  w.Y = c.take<double>(b * (size_t)N * (size_t)K);
+  w.stats = c.take<gik_stats>(b);
+  w.q = c.take<double>(b * n);
+  w.pos_err = c.take<double>(b);
+  w.rot_err = c.take<double>(b);
+  w.bytes = c.off;
+  return w;
+}
+
+// The workspace of gik_anchored_sweep_clearance (gik_anchored_sweep_ws_bytes), M = B (S + 1) configurations, all doubles:
+//   q_s [M][n] | identity poses [M][pose_w] | seed_kernel's targets [M][T_base] (not read) | Y [M][full_N*3] | clearance [M]
+struct AnchSweepWs {
+  double *q, *T, *targets, *Y, *cl;
+  size_t doubles;
+};
+inline AnchSweepWs anch_sweep_ws(int n_joints, int pose_w, int base_T, int full_N, int B, int S, double *ws) {
+  const size_t M = (size_t)B * ((size_t)S + 1);
+  WsCarve c = {reinterpret_cast<uintptr_t>(ws), 0};
+  AnchSweepWs w;
+  w.q = c.take<double>(M * (size_t)n_joints);
+  w.T = c.take<double>(M * (size_t)pose_w);
+  w.targets = c.take<double>(M * (size_t)base_T);
+  w.Y = c.take<double>(M * (size_t)full_N * 3);
+  w.cl = c.take<double>(M);
+  w.doubles = c.off / sizeof(double);
+  return w;
+}
+
+// The workspace of gik_anchored_ik_batch_retry (gik_anchored_retry_ws_bytes = bytes), every array sized for B failed goals:
+//   the scratch of one anchored call (AnchWs; attempt 0 and every restart use it in turn) |
+//   count (8 bytes) | idx [B] int32, padded to 8 bytes | poses | seed angles | centre angles | Y_full | stats | q |
+//   pos_err | rot_err | clearance
+// and behind those bytes, for gik_anchored_ik_batch_retry_scenes alone, whose workspace is that much longer:
+//   ids [B] int32, the scene ids of a compact batch
+struct AnchRetryWs {
+  double *scratch;
+  int32_t *count, *idx;
+  double *T, *q_seed, *q_center, *Y, *q, *pos_err, *rot_err, *clearance;
+  gik_stats *stats;
+  size_t bytes;
+  int32_t *ids;
+};
+inline AnchRetryWs anch_retry_ws(int n_joints, int pose_w, int base_T, int base_N, int free_N, int n_goal, int full_N, int B,
+                                 void *ws) {
+  const size_t b = (size_t)B, n = (size_t)n_joints;
+  WsCarve c = {reinterpret_cast<uintptr_t>(ws), 0};
+  AnchRetryWs w;
+  w.scratch = c.take<double>(anch_ws(base_T, base_N, free_N, n_goal, B, nullptr).doubles);
+  w.count = c.take<int32_t>(2);
+  w.idx = c.take<int32_t>(b);
+  w.T = c.take<double>(b * (size_t)pose_w);
+  w.q_seed = c.take<double>(b * n);
+  w.q_center = c.take<double>(b * n);
+  w.Y = c.take<double>(b * (size_t)full_N * 3);
+  w.stats = c.take<gik_stats>(b);
+  w.q = c.take<double>(b * n);
+  w.pos_err = c.take<double>(b);
+  w.rot_err = c.take<double>(b);
+  w.clearance = c.take<double>(b);
+  w.bytes = c.off;
+  w.ids = c.take<int32_t>(b);
   return w;
 }
 

@@ -613,6 +613,13 @@ class Template:
         q_hi = out["q_hi"] if "q_hi" in out else _dev(hi, self.device)
         return attempt, ws, q_lo, q_hi
 
+    def anchored_retry_ws_bytes(self, base, B, scenes=False):
+        """Bytes of the restart workspace ("retry_ws") of one anchored_ik call of B goals with retries > 0:
+        gik_anchored_retry_ws_bytes, a multiple of 8, and with a scene set behind it the compact batch's scene ids,
+        [B] int32 (gik_anchored_ik_batch_retry_scenes)."""
+        nbytes = int(self.lib.gik_anchored_retry_ws_bytes(self._h, base._h, B))
+        return (nbytes + 7) // 8 * 8 + 4 * B if scenes else nbytes
+
     def alloc_anchored_buffers(self, base, B, clearance=False, ws=True):
         """The buffers of one anchored_ik call of B goals (its `out`): the scratch "ws" (ws=False leaves it out: a call
         with retries > 0 keeps that scratch in its restart workspace), the full point matrix "Y" [B, full_N*3], "stats",
@@ -785,9 +792,7 @@ class Template:
         answer = [out[key].data_ptr() for key in ("Y", "stats", "q", "pos_err", "rot_err")]
         with torch.cuda.device(self.device):
             if retries:
-                nbytes = int(self.lib.gik_anchored_retry_ws_bytes(self._h, base._h, B))
-                if sc is not None:      # (the compact batch's scene ids sit behind the plain layout)
-                    nbytes = (nbytes + 7) // 8 * 8 + 4 * B
+                nbytes = self.anchored_retry_ws_bytes(base, B, scenes=sc is not None)
                 attempt, ws, q_lo, q_hi = self._retry_buffers(out, B, nbytes, lo, hi)
                 opts = _ffi.AnchoredRetryOpts(retries=retries, clearance_mode=mode, seed=int(retry_seed) & (2 ** 64 - 1),
                                               pos_tol=float(pos_tol), rot_tol=float(rot_tol), d_q_lo=q_lo.data_ptr(),

@@ -742,9 +742,7 @@ class AnchoredProblem:
         planes, shared, nbytes = ["clearance"], {}, None
         if retry:      # (the restart workspace holds the anchored scratch too; with scenes, a compact batch's ids behind it)
             planes.append("attempt")
-            nbytes = int(tpl.lib.gik_anchored_retry_ws_bytes(tpl._h, base._h, B))
-            if scenes is not None:
-                nbytes = (nbytes + 7) // 8 * 8 + 4 * B
+            nbytes = tpl.anchored_retry_ws_bytes(base, B, scenes=scenes is not None)
         else:
             shared["ws"] = tpl.alloc_anchored_buffers(base, B)["ws"]
         if sweep:      # one workspace for all waypoints

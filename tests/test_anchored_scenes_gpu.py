@@ -313,7 +313,7 @@ def test_refusals(torch_cuda):
     Yf = Yf.reshape(B, -1).contiguous()
     Yo = torch.full_like(Yf, -7.0)
     stats = torch.zeros(B, _ffi.STATS_BYTES // 8, dtype=torch.float64, device="cuda")
-    rws = torch.empty(int(lib.gik_anchored_retry_ws_bytes(tpl._h, base._h, B)) // 8 + B + 2, dtype=torch.float64, device="cuda")
+    rws = torch.empty(tpl.anchored_retry_ws_bytes(base, B, scenes=True) // 8 + B + 2, dtype=torch.float64, device="cuda")
     attempt = torch.full((B,), -7, dtype=torch.int32, device="cuda")
     lo, hi = (torch.from_numpy(a).cuda() for a in robot.limits_arrays())
     opts = _ffi.AnchoredRetryOpts(retries=1, clearance_mode=0, seed=1, pos_tol=0.01, rot_tol=0.01, d_q_lo=lo.data_ptr(),
