@@ -1,16 +1,15 @@
 // graphik_amd/csrc/gik_host.hip -- host side of the library: template creation (the path, the kernels, the uploads; the
-// tables themselves are built by gik_tables.hip.h), the scheduling slots of a batch call, pipeline attach and the C ABI of
-// include/graphik_amd.h.  No device code is compiled here: the kernels live in gik_k_*.hip (gik_instances.h).
+// tables themselves are built by gik_tables.hip.h; gik_anchored_attach_links, which re-resolves them), pipeline attach,
+// prepare / recover / seed, the known-answer entries, the solve with the scheduling slots of a batch call, the claim order
+// and the info call: the core of the C ABI of include/graphik_amd.h.  The restarts and the fixed-anchor entries are a
+// client of these exports in a unit of their own, gik_host_anch.hip; the handle and the helpers both units call are
+// gik_handle.h's, defined here.  No device code is compiled here: the kernels live in gik_k_*.hip (gik_instances.h).
 
-#include "gik_kernels.hip.h"
+#include "gik_handle.h"
 #include "gik_instances.h"
-#include "gik_retry.hip.h"
 #include "gik_anch_seed.hip.h"
-#include "gik_order.hip.h"
-#include "gik_plan.h"
 #include "gik_slots.h"
 #include "gik_tables.hip.h"
-#include <climits>
 #include <memory>
 
 namespace gik {
@@ -44,16 +43,10 @@ thread_local std::string g_err;
 #ifdef GIK_DEV
 static double *g_dbg_buf = nullptr;
 #endif
-static int fail(const std::string &m) {
+int fail(const std::string &m) {
   g_err = m;
   return -1;
 }
-#define HIP_OK(expr)                                                                      \
-  do {                                                                                    \
-    hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess)                                                                 \
-      return fail(std::string(#expr) + ": " + hipGetErrorString(e_));                     \
-  } while (0)
 
 typedef void (*solve_fn)(SolveArgs);
 typedef void (*scene_fn)(SolveArgs, SceneArgs);
@@ -136,109 +129,7 @@ static const WaveRow *find_row(int K, Form form, int slots) {
 
 }  // namespace gik
 
-struct gik_template {
-  int N, T, maxdeg;
-  gik::SolveFacts f;   // what the launch plan of a batch call reads (gik_plan.h); complete at the end of creation
-  // fixed-anchor formulation (gik_template_create_anchored)
-  bool anchored = false;
-  hipEvent_t ev_solve0 = nullptr, ev_solve1 = nullptr;   // around the solve kernel of the last gik_anchored_ik_batch
-  gik::AnchArgs an = {};            // device pointers + counts (anchor_goal filled per call)
-  double *d_targets_const = nullptr;   // [T] template-constant targets of the free-free terms
-  int full_N = 0, n_anchor = 0;
-  int *d_free_full = nullptr, *d_anchor_full = nullptr;   // node index in the full robot graph
-  int *d_clear_full = nullptr;      // [n_clear] ... of the free nodes that carry the obstacle hinges (anch_clearance_kernel)
-  int n_clear = 0;
-  // the link set of gik_anchored_attach_links (anch_link_clearance_kernel); n_link < 0: none attached
-  int *d_link_a = nullptr, *d_link_b = nullptr;   // [n_link] rows of the full point matrix
-  double *d_link_rho = nullptr;                   // [n_link]
-  int n_link = -1;
-  bool link_hinges = false;                       // ... attached with hinges = 1: the solve kernels are the LINKS builds
-  std::vector<int> h_free_full, h_anchor_full;    // host copies of d_free_full / d_anchor_full and of the slot table:
-  std::vector<uint32_t> h_slot_meta;              // what the attach call builds the per-node link records from
-  double axis_length = 1.0;
-  int solver;
-  gik::CgParams cg;
-  gik::Params p;
-  // the kernels of this template, resolved once at creation (resolve_kernels)
-  struct Kernels {
-    void (*solve)(gik::SolveArgs) = nullptr;          // wavefront path: the solve kernel ...
-    void (*solve_spread)(gik::SolveArgs) = nullptr;   // ... its tail-spreading build, or null: none compiled for this solver / theta / form
-    void (*solve_scene)(gik::SolveArgs, gik::SceneArgs) = nullptr;   // ... its scene build (anchored templates), same LDS bytes
-    void (*kat)(gik::KatArgs) = nullptr;              // ... and the known-answer kernel
-    void (*block_solve)(gik::SolveArgs, int) = nullptr;   // workgroup path
-    void (*block_kat)(gik::KatArgs, int) = nullptr;
-    const void *occupancy = nullptr;                  // the kernel waves_per_cu was queried on
-  } kernels;
-  uint32_t *d_slot_meta = nullptr;
-  gik::ClaimKey claim_key;      // gik_template_set_claim_key (f.claim_terms = claim_key.n); n == 0: index order
-  // Ring of work-queue heads, one per in-flight solve call.  A slot is handed out again only
-  // behind the event recorded after the launch that used it last (the new call's stream waits for
-  // it), so a wrap of the ring can never reset the counter of a kernel that is still running --
-  // whatever the number of calls in flight.
-  unsigned int *d_counters = nullptr;
-  struct CounterSlot {
-    hipEvent_t done = nullptr;
-    bool pending = false;
-    bool in_use = false;     // handed to a call that has not recorded `done` yet
-  };
-  std::vector<CounterSlot> counter_slot;   // [kCounterRing]
-  unsigned next_counter = 0;
-  int counter_ring = 256;   // slots in use (GIK_COUNTER_RING at creation: tests shrink it to force wraps)
-  std::mutex call_mutex;    // counter ring + time-slicing pool: held for the slot hand-out and the hand-back only
-                            // (a slot marked in_use belongs to its call: blocking work happens outside the lock)
-  std::mutex ev_mutex;      // ev_solve0 / ev_solve1 (anchored templates)
-  int clique_mode = 0;      // gik_template_desc::clique_closed_form as resolved at creation
-  bool hess_per_edge = false;   // the wavefront kernel (k = 3) runs the per-edge product form (gik_template_desc::hessian_form)
-  // time-slicing workspaces (re-queue ring + paused state), a small pool handed out round-robin;
-  // a launch that gets a slot still in use by an earlier launch waits for it on its stream
-  struct SliceWs {
-    void *base = nullptr;
-    size_t bytes = 0;
-    hipEvent_t done = nullptr;
-    bool pending = false;
-    bool in_use = false;     // handed to a call that has not recorded `done` yet (only its owner touches the slot)
-  };
-  static constexpr int kSlicePool = 32;
-  SliceWs slice_ws[kSlicePool];
-  unsigned next_slice = 0;
-  int slice_pool = kSlicePool;   // slots in use (GIK_SLICE_POOL at creation: tests shrink it to force reuse)
-  int device;
-  size_t smem_bytes;
-  int SL;         // slots per thread on the block path
-  gik::BlockTabs bt = {nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, 0, 0};
-  // node-per-lane path (rtr_npt_kernel): trust-region solves and the known-answer entry points of
-  // 3-D graphs beyond one wavefront's 64 unknowns; the workgroup tables above stay (ConjugateGradient)
-  gik::NptTabs nt = {};
-  const gik::NptVariant *npt_variant = nullptr;
-  size_t npt_smem = 0;
-  // four-problems-per-wavefront path (rtr_quad_kernel): trust-region solves of planar graphs with at most
-  // 16 nodes and 6 terms per node; everything else of such a template stays on the wavefront kernels
-  void (*quad_solve)(gik::SolveArgs) = nullptr;
-  size_t quad_smem = 0;
-  bool no_npt = false, no_quad = false;   // GIK_NO_NPT / GIK_NO_QUAD: creation leaves these kernels out
-  // device pre/post-processing (gik_pipeline_attach)
-  bool has_pipe = false;
-  gik::PipeConst pc = {};
-  std::vector<void *> pipe_allocs;
-  // the prepare kernel of this template, resolved once at attach (plan_prepare, gik_plan.h), and what a block variant needs
-  struct Prepare {
-    gik::PrepPlan plan;
-    int sweeps = 10;
-    double *ws = nullptr;        // the slab, plan.slab_bytes
-    hipEvent_t done = nullptr;   // launches share the slab, so each one waits for the
-    std::mutex mutex;            // previous one (whatever stream it ran on)
-    bool pending = false;
-  } prep;
-  // joint-configuration seeds (gik_seed_batch): FK tables built at attach; seed_ok is false (and seed_why says why)
-  // for a graph with a node that neither a frame nor an anchor places
-  gik::SeedConst sc = {};
-  size_t seed_smem = 0;
-  bool seed_ok = false;
-  std::string seed_why;
-};
 static constexpr int kCounterRing = 256;
-// doubles of one goal: a (K+1) x (K+1) pose per end effector
-static int pose_width(const gik_template *t) { return t->pc.n_ee * (t->f.K + 1) * (t->f.K + 1); }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a property of the kernel, not of a launch: several
 // templates share a kernel, so the allowance is only ever raised (a later, smaller template must
@@ -272,9 +163,30 @@ static bool capturing_stream(void *stream) {
   return st != hipStreamCaptureStatusNone;
 }
 // the refusal of an entry point whose bookkeeping (events, workspaces, counters) cannot happen under capture
-static int refuse_capture(const char *entry, void *stream) {
+int refuse_capture(const char *entry, void *stream) {
   if (!capturing_stream(stream)) return 0;
   return gik::fail(std::string(entry) + ": the stream is capturing (hipStreamBeginCapture); batch calls cannot be captured into a graph");
+}
+
+// What is wrong with the scene set of a scene call on `t`, as a refusal with the entry's name, or 0 (gik_scenes.h holds
+// the host-checkable part; the contents of d_n_obs and d_scene_id are the caller's precondition)
+int scene_refusal(const char *entry, const gik_template *t, const gik_scene_set *sc) {
+  using gik::fail;
+  const std::string e(entry);
+  if (!t->anchored || !t->kernels.solve_scene)
+    return fail(e + ": the handle must be a fixed-anchor template (gik_template_create_anchored): scenes replace its obstacles");
+  if (!sc) return fail(e + ": null scene set");
+  if (const char *why = gik::scene_set_fault(sc->n_scene, sc->stride, sc->d_obs, sc->d_n_obs, sc->d_scene_id))
+    return fail(e + ": " + why);
+  return 0;
+}
+gik::SceneArgs scene_args(const gik_scene_set *sc) {
+  gik::SceneArgs a;
+  a.scene_id = sc->d_scene_id;
+  a.n_obs = sc->d_n_obs;
+  a.n_scene = sc->n_scene;
+  a.stride = sc->stride;
+  return a;
 }
 
 template <typename T>
@@ -668,6 +580,55 @@ int gik_template_create_anchored(const gik_template_desc *d, const gik_anchored_
   return create_impl(d, ad, out);
 }
 
+// the links of the link clearance; with hinges = 1 the template's kernels are resolved again (anchored_link_row)
+int gik_anchored_attach_links(gik_template *anch, const gik_link_desc *d) {
+  using namespace gik;
+  const std::string e("gik_anchored_attach_links");
+  if (!anch || !d) return fail(e + ": null argument");
+  if (!anch->anchored) return fail(e + ": the handle must be a fixed-anchor template (gik_template_create_anchored)");
+  if (anch->n_link >= 0) return fail(e + ": links already attached");
+  if (d->hinges != 0 && d->hinges != 1) return fail(e + ": hinges must be 0 (measure only) or 1 (the solve carries link hinges)");
+  if (d->n_link < 0 || d->n_link > ANCH_MAXLINK) return fail(e + ": n_link must be within 0 .. 64");
+  if (d->n_link > 0 && (!d->link_a || !d->link_b || !d->link_radius)) return fail(e + ": null link array");
+  for (int l = 0; l < d->n_link; ++l) {
+    if (d->link_a[l] < 0 || d->link_a[l] >= anch->full_N || d->link_b[l] < 0 || d->link_b[l] >= anch->full_N)
+      return fail(e + ": link " + std::to_string(l) + " names a row outside [0, full_N)");
+    if (!(d->link_radius[l] >= 0.0) || d->link_radius[l] == __builtin_huge_val())
+      return fail(e + ": link_radius[" + std::to_string(l) + "] must be finite and at least 0");
+  }
+  std::vector<AnchLinkRec> recs;
+  if (d->hinges) {
+    const std::string why = link_hinge_records(anch->N, anch->maxdeg, anch->h_slot_meta, anch->h_free_full, anch->h_anchor_full, d, recs);
+    if (!why.empty()) return fail(e + ": " + why);
+  }
+  bool ok = true;
+  int *la = const_cast<int *>(upload(anch, d->link_a, (size_t)d->n_link, ok));
+  int *lb = const_cast<int *>(upload(anch, d->link_b, (size_t)d->n_link, ok));
+  double *lr = const_cast<double *>(upload(anch, d->link_radius, (size_t)d->n_link, ok));
+  if (!ok) return fail(e + ": device upload failed");
+  anch->d_link_a = la;
+  anch->d_link_b = lb;
+  anch->d_link_rho = lr;
+  if (d->hinges) {
+    // the template's solve and known-answer kernels become the LINKS builds, with their LDS bytes and occupancy
+    static const WaveRow row = anchored_link_row();
+    const AnchLinkRec *dr = upload(anch, recs.data(), recs.size(), ok);
+    int occ = 0;
+    if (!ok || hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)row.solve, WAVE, row.lds(anch->T)) != hipSuccess)
+      return fail(e + ": device upload failed");
+    anch->an.link_rec = dr;
+    anch->kernels.solve = row.solve;
+    anch->kernels.solve_scene = row.solve_scene;
+    anch->kernels.kat = row.kat;
+    anch->kernels.occupancy = (const void *)row.solve;
+    anch->smem_bytes = row.lds(anch->T);
+    anch->f.waves_per_cu = std::max(1, std::min(occ, 32));
+    anch->link_hinges = true;
+  }
+  anch->n_link = d->n_link;
+  return 0;
+}
+
 void gik_template_destroy(gik_template *t) {
   if (!t) return;
   if (t->d_slot_meta) (void)hipFree(t->d_slot_meta);
@@ -995,705 +956,6 @@ int gik_ik_batch_seeded(const gik_template *t, const double *d_T_goal, const dou
   rc = gik_solve_batch(t, d_Y, d_targets, B, d_Y, d_stats, nullptr, stream);
   if (rc) return rc;
   return gik_recover_batch(t, d_Y, d_T_goal, B, d_q, d_pos_err, d_rot_err, stream);
-}
-
-// ---- restarts from random joint configurations (gik_retry.hip.h) --------------------------------------
-// The three launches behind gik_retry_* and gik_anchored_retry_*.  Those exports make their refusals and fill the arguments,
-// in the order of the structs; the plain ones have no clearance (null pointers: +inf, and any positive clear_tol), no centre
-// and spread 0.  t gives the grid (the anchored calls: the base template).
-static int retry_select_launch(const gik::RetrySelectArgs &a, void *stream) {
-  using namespace gik;
-  hipLaunchKernelGGL(retry_select_kernel, dim3((a.B + RETRY_WAVE - 1) / RETRY_WAVE), dim3(RETRY_WAVE), 0, (hipStream_t)stream, a);
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-static int retry_grid(const gik_template *t, int count) { return std::min(count, t->f.n_cu * 8); }
-
-static int retry_seed_launch(const gik_template *t, const gik::RetrySeedArgs &a, void *stream) {
-  using namespace gik;
-  hipLaunchKernelGGL(retry_seed_kernel, dim3(retry_grid(t, a.count)), dim3(RETRY_WAVE), 0, (hipStream_t)stream, a);
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-static int retry_merge_launch(const gik_template *t, const gik::RetryMergeArgs &a, void *stream) {
-  using namespace gik;
-  hipLaunchKernelGGL(retry_merge_kernel, dim3(retry_grid(t, a.count)), dim3(RETRY_WAVE), 0, (hipStream_t)stream, a);
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-int gik_retry_select(const gik_stats *d_stats, const double *d_pos_err, const double *d_rot_err, int B, double pos_tol,
-                     double rot_tol, int32_t *d_idx, int32_t *d_count, void *stream) {
-  using namespace gik;
-  if (B < 0) return fail("bad argument");
-  if (!d_idx || !d_count) return fail("null buffer");
-  HIP_OK(hipMemsetAsync(d_count, 0, sizeof(int32_t), (hipStream_t)stream));
-  if (B == 0) return 0;
-  if (!d_stats || !d_pos_err || !d_rot_err) return fail("null buffer");
-  const RetrySelectArgs a = {d_stats, d_pos_err, d_rot_err, nullptr, {pos_tol, rot_tol, 1.0}, d_idx, d_count, B};
-  return retry_select_launch(a, stream);
-}
-
-int gik_retry_seeds(const gik_template *t, const double *d_T_goal, const int32_t *d_idx, int count, uint64_t seed,
-                    int attempt, const double *d_q_lo, const double *d_q_hi, double *d_T_out, double *d_q_out,
-                    void *stream) {
-  using namespace gik;
-  if (!t || count < 0) return fail("bad argument");
-  if (!t->has_pipe) return fail("no pipeline attached (gik_pipeline_attach)");
-  if (attempt < 0 || attempt > 63) return fail("gik_retry_seeds: attempt must be within 0 .. 63");
-  if (!d_q_lo || !d_q_hi) return fail("gik_retry_seeds: null joint limits (d_q_lo / d_q_hi, [n] each, are required)");
-  if (count == 0) return 0;
-  if (!d_T_goal || !d_idx || !d_T_out || !d_q_out) return fail("null buffer");
-  const RetrySeedArgs a = {d_T_goal, d_idx, d_q_lo, d_q_hi, nullptr, d_T_out, d_q_out, 0.0, seed,
-                           count, pose_width(t), t->pc.n_joints, attempt};
-  return retry_seed_launch(t, a, stream);
-}
-
-int gik_retry_merge(const gik_template *t, const int32_t *d_idx, int count, int attempt, double pos_tol, double rot_tol,
-                    const double *d_Y_r, const gik_stats *d_stats_r, const double *d_q_r, const double *d_pos_err_r,
-                    const double *d_rot_err_r, double *d_Y, gik_stats *d_stats, double *d_q, double *d_pos_err,
-                    double *d_rot_err, int32_t *d_attempt, void *stream) {
-  using namespace gik;
-  if (!t || count < 0) return fail("bad argument");
-  if (!t->has_pipe) return fail("no pipeline attached (gik_pipeline_attach)");
-  if (count == 0) return 0;
-  if (!d_idx || !d_Y_r || !d_stats_r || !d_q_r || !d_pos_err_r || !d_rot_err_r || !d_Y || !d_stats || !d_q ||
-      !d_pos_err || !d_rot_err || !d_attempt)
-    return fail("null buffer");
-  const RetryMergeArgs a = {d_idx,
-                            d_Y_r, d_stats_r, d_q_r, d_pos_err_r, d_rot_err_r, nullptr,
-                            d_Y, d_stats, d_q, d_pos_err, d_rot_err, nullptr, d_attempt,
-                            {pos_tol, rot_tol, 1.0}, count, t->N * t->f.K, t->pc.n_joints, attempt};
-  return retry_merge_launch(t, a, stream);
-}
-
-// the caller-owned workspace of gik_ik_batch_retry over d_ws (gik_plan.h), or with a null d_ws its size
-static gik::RetryWs retry_ws(const gik_template *t, int B, void *d_ws) {
-  return gik::retry_ws(t->pc.n_joints, pose_width(t), t->T, t->N, t->f.K, B, d_ws);
-}
-
-// The solve kernels take their batch size from the host: the failed-goal count comes back, the stream drains.
-static int retry_read_count(const char *entry, const int32_t *d_count, int B, int32_t *count, hipStream_t s) {
-  using gik::fail;
-  HIP_OK(hipMemcpyAsync(count, d_count, sizeof(*count), hipMemcpyDeviceToHost, s));
-  HIP_OK(hipStreamSynchronize(s));
-  if (*count < 0 || *count > B) return fail(std::string(entry) + ": the failed-goal count came back out of range");
-  return 0;
-}
-
-size_t gik_retry_ws_bytes(const gik_template *t, int B) {
-  if (!t || !t->has_pipe || B < 0) return 0;
-  return retry_ws(t, B, nullptr).bytes;
-}
-
-int gik_ik_batch_retry(const gik_template *t, const double *d_T_goal, const double *d_q_init, int B,
-                       const gik_retry_opts *opts, void *d_ws, double *d_targets, double *d_Y, gik_stats *d_stats,
-                       double *d_q, double *d_pos_err, double *d_rot_err, int32_t *d_attempt, void *stream) {
-  using namespace gik;
-  // every refusal comes before anything is queued
-  if (!t || B < 0 || !opts) return fail("bad argument");
-  if (!t->has_pipe) return fail("gik_ik_batch_retry: no pipeline attached (gik_pipeline_attach)");
-  if (opts->retries < 0 || opts->retries > 63) return fail("gik_ik_batch_retry: retries must be within 0 .. 63");
-  if (opts->retries > 0) {
-    if (!t->seed_ok) return fail("gik_ik_batch_retry: this graph cannot be seeded on the device: " + t->seed_why);
-    if (!opts->d_q_lo || !opts->d_q_hi)
-      return fail("gik_ik_batch_retry: null joint limits (opts->d_q_lo / d_q_hi, [n] each, are what the seeds are drawn from)");
-    if (!(opts->pos_tol > 0.0) || !(opts->rot_tol > 0.0)) return fail("gik_ik_batch_retry: pos_tol and rot_tol must be positive");
-    if (!d_ws && B > 0) return fail("gik_ik_batch_retry: null workspace (gik_retry_ws_bytes)");
-    if ((uintptr_t)d_ws % 8) return fail("gik_ik_batch_retry: the workspace must be 8-byte aligned");
-  }
-  if (refuse_capture("gik_ik_batch_retry", stream)) return -1;
-  if (B == 0) return 0;
-  if (!d_T_goal || !d_targets || !d_Y || !d_stats || !d_q || !d_pos_err || !d_rot_err || !d_attempt) return fail("null buffer");
-  hipStream_t s = (hipStream_t)stream;
-  HIP_OK(hipMemsetAsync(d_attempt, 0, (size_t)B * sizeof(int32_t), s));
-  int rc = d_q_init ? gik_ik_batch_seeded(t, d_T_goal, d_q_init, B, d_targets, d_Y, d_stats, d_q, d_pos_err, d_rot_err, stream)
-                    : gik_ik_batch(t, d_T_goal, B, d_targets, d_Y, d_stats, d_q, d_pos_err, d_rot_err, stream);
-  if (rc) return rc;
-  const RetryWs w = retry_ws(t, B, d_ws);
-  for (int a = 1; a <= opts->retries; ++a) {
-    rc = gik_retry_select(d_stats, d_pos_err, d_rot_err, B, opts->pos_tol, opts->rot_tol, w.idx, w.count, stream);
-    if (rc) return rc;
-    int32_t count = 0;
-    rc = retry_read_count("gik_ik_batch_retry", w.count, B, &count, s);
-    if (rc) return rc;
-    if (count == 0) break;
-    rc = gik_retry_seeds(t, d_T_goal, w.idx, count, opts->seed, a, opts->d_q_lo, opts->d_q_hi, w.T, w.q_seed, stream);
-    if (rc) return rc;
-    rc = gik_seed_batch(t, w.T, w.q_seed, count, w.targets, w.Y, stream);
-    if (rc) return rc;
-    rc = gik_solve_batch(t, w.Y, w.targets, count, w.Y, w.stats, nullptr, stream);
-    if (rc) return rc;
-    rc = gik_recover_batch(t, w.Y, w.T, count, w.q, w.pos_err, w.rot_err, stream);
-    if (rc) return rc;
-    rc = gik_retry_merge(t, w.idx, count, a, opts->pos_tol, opts->rot_tol, w.Y, w.stats, w.q, w.pos_err, w.rot_err, d_Y,
-                         d_stats, d_q, d_pos_err, d_rot_err, d_attempt, stream);
-    if (rc) return rc;
-  }
-  return 0;
-}
-
-// ---- the fixed-anchor (obstacle) solve on the robot graph's pipeline -------------------------------------------------
-// Every solve entry -- cold, seeded, with scenes, and each attempt of the two restart loops -- refuses what it has always
-// refused, under its own name, and then queues its work through anchored_attempt, the one place that writes the launch
-// sequence.  The four clearance exports are anchored_clearance_entry with two booleans; clearance_mode_refusal is the mode
-// check of the scene entry and the restart loops.  The helpers stand in order of use.  The layouts of the caller-owned
-// workspaces are gik_plan.h's; the wrappers here read their integers off the handles.
-
-// the scratch of one anchored call over d_ws (gik_plan.h), or with a null d_ws its size
-static gik::AnchWs anch_ws(const gik_template *anch, const gik_template *base, int B, double *d_ws) {
-  return gik::anch_ws(base->T, base->N, anch->N, anch->an.n_goal, B, d_ws);
-}
-
-size_t gik_anchored_ws_doubles(const gik_template *anch, const gik_template *base, int B) {
-  if (!anch || !base || !anch->anchored || B < 0) return 0;
-  return anch_ws(anch, base, B, nullptr).doubles;
-}
-
-// the arguments of the glue kernels between the robot-graph pipeline and the anchored solve
-static gik::AnchGlueArgs anch_glue_args(const gik_template *anch, const double *d_T_goal, int B, const double *Y_full_in,
-                                        double *Y_free, double *goal, double *Y_full_out) {
-  gik::AnchGlueArgs g;
-  g.T_goal = d_T_goal;
-  g.Y_full_in = Y_full_in;
-  g.Y_free = Y_free;
-  g.anchor_goal = goal;
-  g.Y_full_out = Y_full_out;
-  g.anch_const = anch->an.anch_const;
-  g.free_full = anch->d_free_full;
-  g.anchor_full = anch->d_anchor_full;
-  g.B = B;
-  g.Nf = anch->N;
-  g.full_N = anch->full_N;
-  g.n_anchor = anch->n_anchor;
-  g.n_goal = anch->an.n_goal;
-  g.goal_row0 = anch->an.goal_row0;
-  g.axis_length = anch->axis_length;
-  return g;
-}
-
-// What is wrong with the handle pair of an anchored call, or nothing: anch is a fixed-anchor template and base the robot
-// graph it was cut from, full_N nodes with its pipeline attached.  PAIR_3D: base is also 3-D; PAIR_SEEDABLE: and can be seeded
-// on the device.  Each entry names the terms it has always tested.  (Non-null handles.)
-enum { PAIR_3D = 1, PAIR_SEEDABLE = 2 };
-static std::string anchored_pair_fault(const gik_template *anch, const gik_template *base, int terms) {
-  if (!anch->anchored) return "the first handle must be a fixed-anchor template (gik_template_create_anchored)";
-  if (!base->has_pipe || ((terms & PAIR_3D) && base->f.K != 3) || base->N != anch->full_N)
-    return "the base template must be the robot graph (full_N nodes) with its pipeline attached";
-  if ((terms & PAIR_SEEDABLE) && !base->seed_ok) return "the base graph cannot be seeded on the device: " + base->seed_why;
-  return std::string();
-}
-
-// What is wrong with the scene set of a scene call on `t`, as a refusal with the entry's name, or 0 (gik_scenes.h holds
-// the host-checkable part; the contents of d_n_obs and d_scene_id are the caller's precondition)
-static int scene_refusal(const char *entry, const gik_template *t, const gik_scene_set *sc) {
-  using gik::fail;
-  const std::string e(entry);
-  if (!t->anchored || !t->kernels.solve_scene)
-    return fail(e + ": the handle must be a fixed-anchor template (gik_template_create_anchored): scenes replace its obstacles");
-  if (!sc) return fail(e + ": null scene set");
-  if (const char *why = gik::scene_set_fault(sc->n_scene, sc->stride, sc->d_obs, sc->d_n_obs, sc->d_scene_id))
-    return fail(e + ": " + why);
-  return 0;
-}
-static gik::SceneArgs scene_args(const gik_scene_set *sc) {
-  gik::SceneArgs a;
-  a.scene_id = sc->d_scene_id;
-  a.n_obs = sc->d_n_obs;
-  a.n_scene = sc->n_scene;
-  a.stride = sc->stride;
-  return a;
-}
-
-// (scenes: a checked scene set, or null: the template's own obstacles)
-static int anchored_clearance_launch(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance,
-                                     void *stream, const gik_scene_set *scenes = nullptr) {
-  using namespace gik;
-  AnchClearArgs c;
-  c.Y_full = d_Y_full;
-  c.obs = scenes ? scenes->d_obs : anch->an.obs;
-  c.node_full = anch->d_clear_full;
-  c.clearance = d_clearance;
-  c.B = B;
-  c.full_N = anch->full_N;
-  c.n_node = anch->n_clear;
-  c.n_obs = scenes ? 0 : anch->an.n_obs;
-  const dim3 grid(std::min(B, anch->f.n_cu * 32));
-  if (scenes)
-    hipLaunchKernelGGL(anch_clearance_scene_kernel, grid, dim3(WAVE), 0, (hipStream_t)stream, c, scene_args(scenes));
-  else
-    hipLaunchKernelGGL(anch_clearance_kernel, grid, dim3(WAVE), 0, (hipStream_t)stream, c);
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-// the same of whole links (gik_anchored_attach_links; gik_anch_seed.hip.h)
-static int anchored_link_clearance_launch(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance,
-                                          void *stream, const gik_scene_set *scenes = nullptr) {
-  using namespace gik;
-  AnchLinkArgs c;
-  c.Y_full = d_Y_full;
-  c.obs = scenes ? scenes->d_obs : anch->an.obs;
-  c.link_a = anch->d_link_a;
-  c.link_b = anch->d_link_b;
-  c.link_rho = anch->d_link_rho;
-  c.clearance = d_clearance;
-  c.B = B;
-  c.full_N = anch->full_N;
-  c.n_link = anch->n_link;
-  c.n_obs = scenes ? 0 : anch->an.n_obs;
-  const dim3 grid(std::min(B, anch->f.n_cu * 32));
-  if (scenes)
-    hipLaunchKernelGGL(anch_link_clearance_scene_kernel, grid, dim3(WAVE), 0, (hipStream_t)stream, c, scene_args(scenes));
-  else
-    hipLaunchKernelGGL(anch_link_clearance_kernel, grid, dim3(WAVE), 0, (hipStream_t)stream, c);
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-// the start point from joint-configuration seeds (gik_anch_seed.hip.h): seed_kernel on the robot graph into the workspace,
-// then the row gather + goal anchors
-static int anchored_seed_launch(const gik_template *anch, const gik_template *base, const double *d_T_goal,
-                                const double *d_q_init, int B, double *d_ws, double *Y_free, double *goal, void *stream) {
-  using namespace gik;
-  const AnchWs w = anch_ws(anch, base, B, d_ws);      // (its head: Y_free and goal may be the caller's own arrays)
-  const int rc = gik_seed_batch(base, d_T_goal, d_q_init, B, w.targets, w.Y_full0, stream);
-  if (rc) return rc;
-  const AnchGlueArgs g = anch_glue_args(anch, d_T_goal, B, w.Y_full0, Y_free, goal, nullptr);
-  const size_t n = (size_t)B * ((size_t)g.Nf + (size_t)g.n_goal) * 3;
-  hipLaunchKernelGGL(anch_scatter_kernel, dim3((unsigned)((n + ANCH_SCATTER_NT - 1) / ANCH_SCATTER_NT)), dim3(ANCH_SCATTER_NT),
-                     0, (hipStream_t)stream, g);
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-// One anchored solve on checked arguments, B > 0: what every solve entry and every restart queues.  The start point, cold
-// (d_q_init null: the robot graph's prepare, fitted to the anchors) or seeded; the solve between the event pair of
-// gik_anchored_last_solve_ms; the gather into d_Y_full; the recovery; and, where d_clearance is given, the clearance of the
-// answer: of the masked nodes, or with link_clear of whole links.  scenes: a checked scene set for the solve and the
-// clearance, or null: the template's own obstacles.
-static int anchored_attempt(const gik_template *anch, const gik_template *base, const double *d_T_goal, const double *d_q_init,
-                            int B, const gik_scene_set *scenes, double *d_ws, double *d_Y_full, gik_stats *d_stats, double *d_q,
-                            double *d_pos_err, double *d_rot_err, double *d_clearance, bool link_clear, void *stream) {
-  using namespace gik;
-  const AnchWs w = anch_ws(anch, base, B, d_ws);
-  AnchGlueArgs g;
-  if (d_q_init) {      // (read here and nowhere later: d_q_init may be d_q)
-    const int rc = anchored_seed_launch(anch, base, d_T_goal, d_q_init, B, d_ws, w.Y_free, w.goal, stream);
-    if (rc) return rc;
-    g = anch_glue_args(anch, d_T_goal, B, nullptr, w.Y_free, w.goal, d_Y_full);
-  } else {
-    // initial point of the robot graph (bound smoothing + MDS, obstacles play no part in it) ...
-    const int rc = gik_prepare_batch(base, d_T_goal, B, w.targets, w.Y_full0, nullptr, stream);
-    if (rc) return rc;
-    g = anch_glue_args(anch, d_T_goal, B, w.Y_full0, w.Y_free, w.goal, d_Y_full);
-    // ... mapped onto the world frame by its anchors; free rows = anchored start point
-    hipLaunchKernelGGL(anch_init_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, g);
-    HIP_OK(hipGetLastError());
-  }
-  // timing events around the solve (diagnostics only; created with the handle).  The pair is
-  // recorded under a lock so that gik_anchored_last_solve_ms never reads a half-recorded pair;
-  // with concurrent callers it reports whichever call recorded last.
-  gik_template *ma = const_cast<gik_template *>(anch);
-  {
-    std::lock_guard<std::mutex> lock(ma->ev_mutex);
-    (void)hipEventRecord(ma->ev_solve0, (hipStream_t)stream);
-  }
-  int rc = scenes ? gik_solve_batch_scenes(anch, g.Y_free, g.anchor_goal, g.B, g.Y_free, d_stats, nullptr, scenes, stream)
-                  : gik_solve_batch(anch, g.Y_free, g.anchor_goal, g.B, g.Y_free, d_stats, nullptr, stream);     // (not under ev_mutex:
-  if (rc) return rc;                                                                                   // other threads launch meanwhile)
-  {
-    std::lock_guard<std::mutex> lock(ma->ev_mutex);
-    (void)hipEventRecord(ma->ev_solve1, (hipStream_t)stream);
-  }
-  hipLaunchKernelGGL(anch_gather_kernel, dim3((g.B + 63) / 64), dim3(64), 0, (hipStream_t)stream, g);
-  HIP_OK(hipGetLastError());
-  rc = gik_recover_batch(base, g.Y_full_out, g.T_goal, g.B, d_q, d_pos_err, d_rot_err, stream);
-  if (rc || !d_clearance) return rc;
-  return link_clear ? anchored_link_clearance_launch(anch, g.Y_full_out, g.B, d_clearance, stream, scenes)
-                    : anchored_clearance_launch(anch, g.Y_full_out, g.B, d_clearance, stream, scenes);
-}
-
-int gik_anchored_ik_batch(const gik_template *anch, const gik_template *base, const double *d_T_goal, int B,
-                          double *d_ws, double *d_Y_full, gik_stats *d_stats, double *d_q,
-                          double *d_pos_err, double *d_rot_err, void *stream) {
-  using namespace gik;
-  if (!anch || !base || !anch->anchored || B < 0) return fail("bad argument");
-  if (const std::string why = anchored_pair_fault(anch, base, PAIR_3D); !why.empty()) return fail("gik_anchored_ik_batch: " + why);
-  if (B == 0) return 0;
-  if (!d_T_goal || !d_ws || !d_Y_full || !d_stats || !d_q || !d_pos_err || !d_rot_err) return fail("null buffer");
-  return anchored_attempt(anch, base, d_T_goal, nullptr, B, nullptr, d_ws, d_Y_full, d_stats, d_q, d_pos_err, d_rot_err, nullptr,
-                          false, stream);
-}
-
-// what the seeded anchored calls refuse, before anything is queued
-static int anchored_seed_refusal(const char *entry, const gik_template *anch, const gik_template *base, const double *d_q_init,
-                                 int B, void *stream) {
-  using gik::fail;
-  const std::string e(entry);
-  if (!anch || !base || B < 0) return fail(e + ": bad argument");
-  if (const std::string why = anchored_pair_fault(anch, base, PAIR_3D | PAIR_SEEDABLE); !why.empty()) return fail(e + ": " + why);
-  if (refuse_capture(entry, stream)) return -1;
-  if (B > 0 && !d_q_init) return fail(e + ": null d_q_init (seed joint angles [B][n] are required)");
-  return 0;
-}
-
-int gik_anchored_seed_batch(const gik_template *anch, const gik_template *base, const double *d_T_goal,
-                            const double *d_q_init, int B, double *d_ws, double *d_Y_free, double *d_goal, void *stream) {
-  if (anchored_seed_refusal("gik_anchored_seed_batch", anch, base, d_q_init, B, stream)) return -1;
-  if (B == 0) return 0;
-  if (!d_T_goal || !d_ws || !d_Y_free || !d_goal) return gik::fail("gik_anchored_seed_batch: null buffer");
-  return anchored_seed_launch(anch, base, d_T_goal, d_q_init, B, d_ws, d_Y_free, d_goal, stream);
-}
-
-int gik_anchored_ik_batch_seeded(const gik_template *anch, const gik_template *base, const double *d_T_goal,
-                                 const double *d_q_init, int B, double *d_ws, double *d_Y_full, gik_stats *d_stats,
-                                 double *d_q, double *d_pos_err, double *d_rot_err, double *d_clearance, void *stream) {
-  if (anchored_seed_refusal("gik_anchored_ik_batch_seeded", anch, base, d_q_init, B, stream)) return -1;
-  if (B == 0) return 0;
-  if (!d_T_goal || !d_ws || !d_Y_full || !d_stats || !d_q || !d_pos_err || !d_rot_err)
-    return gik::fail("gik_anchored_ik_batch_seeded: null buffer");
-  return anchored_attempt(anch, base, d_T_goal, d_q_init, B, nullptr, d_ws, d_Y_full, d_stats, d_q, d_pos_err, d_rot_err,
-                          d_clearance, false, stream);
-}
-
-// what a call that takes a clearance_mode refuses about it, under the entry's name e
-static int clearance_mode_refusal(const std::string &e, const gik_template *anch, int clearance_mode) {
-  using gik::fail;
-  if (clearance_mode != GIK_CLEARANCE_NODES && clearance_mode != GIK_CLEARANCE_LINKS)
-    return fail(e + ": clearance_mode must be GIK_CLEARANCE_NODES (0) or GIK_CLEARANCE_LINKS (1)");
-  if (clearance_mode == GIK_CLEARANCE_LINKS && anch->n_link < 0)
-    return fail(e + ": clearance_mode = links, but no links attached (gik_anchored_attach_links)");
-  return 0;
-}
-
-// ---- per-goal obstacle scenes: the solve entry (the solve kernel's: gik_solve_batch_scenes) ----
-int gik_anchored_ik_batch_scenes(const gik_template *anch, const gik_template *base, const double *d_T_goal,
-                                 const double *d_q_init, int B, const gik_scene_set *scenes, double *d_ws, double *d_Y_full,
-                                 gik_stats *d_stats, double *d_q, double *d_pos_err, double *d_rot_err, double *d_clearance,
-                                 int clearance_mode, void *stream) {
-  using namespace gik;
-  const std::string e("gik_anchored_ik_batch_scenes");
-  if (!anch || !base || B < 0) return fail(e + ": bad argument");
-  if (const std::string why = anchored_pair_fault(anch, base, PAIR_3D | (d_q_init ? PAIR_SEEDABLE : 0)); !why.empty())
-    return fail(e + ": " + why);
-  if (scene_refusal("gik_anchored_ik_batch_scenes", anch, scenes)) return -1;
-  if (clearance_mode_refusal(e, anch, clearance_mode)) return -1;
-  if (refuse_capture("gik_anchored_ik_batch_scenes", stream)) return -1;
-  if (B == 0) return 0;
-  if (!d_T_goal || !d_ws || !d_Y_full || !d_stats || !d_q || !d_pos_err || !d_rot_err) return fail(e + ": null buffer");
-  return anchored_attempt(anch, base, d_T_goal, d_q_init, B, scenes, d_ws, d_Y_full, d_stats, d_q, d_pos_err, d_rot_err,
-                          d_clearance, clearance_mode == GIK_CLEARANCE_LINKS, stream);
-}
-
-// ---- the clearance of an answer: of the masked nodes or of whole links, against the template's obstacles or per-goal scenes ----
-static int anchored_clearance_entry(const char *entry, const gik_template *anch, bool links, bool with_scenes,
-                                    const gik_scene_set *scenes, const double *d_Y_full, int B, double *d_clearance, void *stream) {
-  using gik::fail;
-  const std::string e(entry);
-  if (!anch || B < 0) return fail(e + ": bad argument");
-  if (with_scenes) {
-    if (scene_refusal(entry, anch, scenes)) return -1;
-  } else if (!anch->anchored) {
-    return fail(e + ": the handle must be a fixed-anchor template (gik_template_create_anchored)");
-  }
-  if (links && anch->n_link < 0) return fail(e + ": no links attached (gik_anchored_attach_links)");
-  if (refuse_capture(entry, stream)) return -1;
-  if (B == 0) return 0;
-  if (!d_Y_full || !d_clearance) return fail(e + ": null buffer");
-  return links ? anchored_link_clearance_launch(anch, d_Y_full, B, d_clearance, stream, scenes)      // (scenes: null without)
-               : anchored_clearance_launch(anch, d_Y_full, B, d_clearance, stream, scenes);
-}
-
-int gik_anchored_clearance(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance, void *stream) {
-  return anchored_clearance_entry("gik_anchored_clearance", anch, false, false, nullptr, d_Y_full, B, d_clearance, stream);
-}
-int gik_anchored_link_clearance(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance, void *stream) {
-  return anchored_clearance_entry("gik_anchored_link_clearance", anch, true, false, nullptr, d_Y_full, B, d_clearance, stream);
-}
-int gik_anchored_clearance_scenes(const gik_template *anch, const double *d_Y_full, int B, const gik_scene_set *scenes,
-                                  double *d_clearance, void *stream) {
-  return anchored_clearance_entry("gik_anchored_clearance_scenes", anch, false, true, scenes, d_Y_full, B, d_clearance, stream);
-}
-int gik_anchored_link_clearance_scenes(const gik_template *anch, const double *d_Y_full, int B, const gik_scene_set *scenes,
-                                       double *d_clearance, void *stream) {
-  return anchored_clearance_entry("gik_anchored_link_clearance_scenes", anch, true, true, scenes, d_Y_full, B, d_clearance, stream);
-}
-
-// ---- the links of the link clearance, and its sweep between two configurations (gik_anch_seed.hip.h) -----------
-int gik_anchored_attach_links(gik_template *anch, const gik_link_desc *d) {
-  using namespace gik;
-  const std::string e("gik_anchored_attach_links");
-  if (!anch || !d) return fail(e + ": null argument");
-  if (!anch->anchored) return fail(e + ": the handle must be a fixed-anchor template (gik_template_create_anchored)");
-  if (anch->n_link >= 0) return fail(e + ": links already attached");
-  if (d->hinges != 0 && d->hinges != 1) return fail(e + ": hinges must be 0 (measure only) or 1 (the solve carries link hinges)");
-  if (d->n_link < 0 || d->n_link > ANCH_MAXLINK) return fail(e + ": n_link must be within 0 .. 64");
-  if (d->n_link > 0 && (!d->link_a || !d->link_b || !d->link_radius)) return fail(e + ": null link array");
-  for (int l = 0; l < d->n_link; ++l) {
-    if (d->link_a[l] < 0 || d->link_a[l] >= anch->full_N || d->link_b[l] < 0 || d->link_b[l] >= anch->full_N)
-      return fail(e + ": link " + std::to_string(l) + " names a row outside [0, full_N)");
-    if (!(d->link_radius[l] >= 0.0) || d->link_radius[l] == __builtin_huge_val())
-      return fail(e + ": link_radius[" + std::to_string(l) + "] must be finite and at least 0");
-  }
-  std::vector<AnchLinkRec> recs;
-  if (d->hinges) {
-    const std::string why = link_hinge_records(anch->N, anch->maxdeg, anch->h_slot_meta, anch->h_free_full, anch->h_anchor_full, d, recs);
-    if (!why.empty()) return fail(e + ": " + why);
-  }
-  bool ok = true;
-  int *la = const_cast<int *>(upload(anch, d->link_a, (size_t)d->n_link, ok));
-  int *lb = const_cast<int *>(upload(anch, d->link_b, (size_t)d->n_link, ok));
-  double *lr = const_cast<double *>(upload(anch, d->link_radius, (size_t)d->n_link, ok));
-  if (!ok) return fail(e + ": device upload failed");
-  anch->d_link_a = la;
-  anch->d_link_b = lb;
-  anch->d_link_rho = lr;
-  if (d->hinges) {
-    // the template's solve and known-answer kernels become the LINKS builds, with their LDS bytes and occupancy
-    static const WaveRow row = anchored_link_row();
-    const AnchLinkRec *dr = upload(anch, recs.data(), recs.size(), ok);
-    int occ = 0;
-    if (!ok || hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)row.solve, WAVE, row.lds(anch->T)) != hipSuccess)
-      return fail(e + ": device upload failed");
-    anch->an.link_rec = dr;
-    anch->kernels.solve = row.solve;
-    anch->kernels.solve_scene = row.solve_scene;
-    anch->kernels.kat = row.kat;
-    anch->kernels.occupancy = (const void *)row.solve;
-    anch->smem_bytes = row.lds(anch->T);
-    anch->f.waves_per_cu = std::max(1, std::min(occ, 32));
-    anch->link_hinges = true;
-  }
-  anch->n_link = d->n_link;
-  return 0;
-}
-
-// the caller-owned workspace of gik_anchored_sweep_clearance over d_ws (gik_plan.h), or with a null d_ws its size
-static gik::AnchSweepWs anch_sweep_ws(const gik_template *anch, const gik_template *base, int B, int S, double *d_ws) {
-  return gik::anch_sweep_ws(base->pc.n_joints, pose_width(base), base->T, anch->full_N, B, S, d_ws);
-}
-
-size_t gik_anchored_sweep_ws_bytes(const gik_template *anch, const gik_template *base, int B, int samples) {
-  if (!anch || !base || !anchored_pair_fault(anch, base, 0).empty() || B < 0 || samples < 1 ||
-      (size_t)B * ((size_t)samples + 1) > (size_t)INT_MAX)
-    return 0;
-  return anch_sweep_ws(anch, base, B, samples, nullptr).doubles * sizeof(double);
-}
-
-int gik_anchored_sweep_clearance(const gik_template *anch, const gik_template *base, const double *d_q_a,
-                                 const double *d_q_b, int B, int samples, double *d_ws, double *d_clearance, void *stream) {
-  using namespace gik;
-  const std::string e("gik_anchored_sweep_clearance");
-  if (!anch || !base || B < 0) return fail(e + ": bad argument");
-  if (const std::string why = anchored_pair_fault(anch, base, PAIR_3D | PAIR_SEEDABLE); !why.empty()) return fail(e + ": " + why);
-  if (anch->n_link < 0) return fail(e + ": no links attached (gik_anchored_attach_links)");
-  if (samples < 1) return fail(e + ": samples must be at least 1");
-  if ((size_t)B * ((size_t)samples + 1) > (size_t)INT_MAX) return fail(e + ": B (samples + 1) must fit an int");
-  if (refuse_capture("gik_anchored_sweep_clearance", stream)) return -1;
-  if (B == 0) return 0;
-  if (!d_q_a || !d_q_b || !d_ws || !d_clearance) return fail(e + ": null buffer");
-  const AnchSweepWs w = anch_sweep_ws(anch, base, B, samples, d_ws);
-  const int M = B * (samples + 1);
-  AnchSweepInterpArgs ia;
-  ia.q_a = d_q_a;
-  ia.q_b = d_q_b;
-  ia.q_s = w.q;
-  ia.T_id = w.T;
-  ia.B = B;
-  ia.n = base->pc.n_joints;
-  ia.S = samples;
-  ia.D = base->f.K + 1;
-  ia.pose_w = pose_width(base);
-  const size_t nt = (size_t)M * ((size_t)ia.n + (size_t)ia.pose_w);
-  if ((nt + ANCH_SCATTER_NT - 1) / ANCH_SCATTER_NT > (size_t)INT_MAX) return fail(e + ": the batch is too large");
-  hipLaunchKernelGGL(anch_sweep_interp_kernel, dim3((unsigned)((nt + ANCH_SCATTER_NT - 1) / ANCH_SCATTER_NT)),
-                     dim3(ANCH_SCATTER_NT), 0, (hipStream_t)stream, ia);
-  HIP_OK(hipGetLastError());
-  // the realization of every sample: seed_kernel's joint-frame walk on the robot graph (its targets go unread)
-  int rc = gik_seed_batch(base, w.T, w.q, M, w.targets, w.Y, stream);
-  if (rc) return rc;
-  rc = anchored_link_clearance_launch(anch, w.Y, M, w.cl, stream);
-  if (rc) return rc;
-  AnchSweepMinArgs ma;
-  ma.cl = w.cl;
-  ma.clearance = d_clearance;
-  ma.B = B;
-  ma.S = samples;
-  hipLaunchKernelGGL(anch_sweep_min_kernel, dim3((B + ANCH_SCATTER_NT - 1) / ANCH_SCATTER_NT), dim3(ANCH_SCATTER_NT), 0,
-                     (hipStream_t)stream, ma);
-  HIP_OK(hipGetLastError());
-  return 0;
-}
-
-// ---- restarts in the anchored solve: the kernels of gik_retry.hip.h with a clearance in the rule -------------
-int gik_anchored_retry_select(const gik_stats *d_stats, const double *d_pos_err, const double *d_rot_err,
-                              const double *d_clearance, int B, double pos_tol, double rot_tol, double clear_tol,
-                              int32_t *d_idx, int32_t *d_count, void *stream) {
-  using namespace gik;
-  if (B < 0) return fail("gik_anchored_retry_select: bad argument");
-  if (!d_idx || !d_count) return fail("gik_anchored_retry_select: null buffer");
-  HIP_OK(hipMemsetAsync(d_count, 0, sizeof(int32_t), (hipStream_t)stream));
-  if (B == 0) return 0;
-  if (!d_stats || !d_pos_err || !d_rot_err || !d_clearance) return fail("gik_anchored_retry_select: null buffer");
-  const RetrySelectArgs a = {d_stats, d_pos_err, d_rot_err, d_clearance, {pos_tol, rot_tol, clear_tol}, d_idx, d_count, B};
-  return retry_select_launch(a, stream);
-}
-
-int gik_anchored_retry_seeds(const gik_template *base, const double *d_T_goal, const int32_t *d_idx, int count,
-                             uint64_t seed, int attempt, const double *d_q_lo, const double *d_q_hi,
-                             const double *d_q_center, double spread, double *d_T_out, double *d_q_out, void *stream) {
-  using namespace gik;
-  if (!base || count < 0) return fail("gik_anchored_retry_seeds: bad argument");
-  if (!base->has_pipe) return fail("gik_anchored_retry_seeds: no pipeline attached to the base template (gik_pipeline_attach)");
-  if (attempt < 0 || attempt > 63) return fail("gik_anchored_retry_seeds: attempt must be within 0 .. 63");
-  if (!d_q_lo || !d_q_hi) return fail("gik_anchored_retry_seeds: null joint limits (d_q_lo / d_q_hi, [n] each, are required)");
-  if (!(spread >= 0.0)) return fail("gik_anchored_retry_seeds: spread must be at least 0");
-  if (spread > 0.0 && !d_q_center) return fail("gik_anchored_retry_seeds: spread > 0 needs the centre rows d_q_center [B][n]");
-  if (count == 0) return 0;
-  if (!d_T_goal || !d_idx || !d_T_out || !d_q_out) return fail("gik_anchored_retry_seeds: null buffer");
-  const RetrySeedArgs a = {d_T_goal, d_idx, d_q_lo, d_q_hi, d_q_center, d_T_out, d_q_out, spread, seed,
-                           count, pose_width(base), base->pc.n_joints, attempt};
-  return retry_seed_launch(base, a, stream);
-}
-
-int gik_anchored_retry_merge(const gik_template *anch, const gik_template *base, const int32_t *d_idx, int count,
-                             int attempt, double pos_tol, double rot_tol, double clear_tol, const double *d_Y_r,
-                             const gik_stats *d_stats_r, const double *d_q_r, const double *d_pos_err_r,
-                             const double *d_rot_err_r, const double *d_clearance_r, double *d_Y_full, gik_stats *d_stats,
-                             double *d_q, double *d_pos_err, double *d_rot_err, double *d_clearance, int32_t *d_attempt,
-                             void *stream) {
-  using namespace gik;
-  if (!anch || !base || count < 0) return fail("gik_anchored_retry_merge: bad argument");
-  if (const std::string why = anchored_pair_fault(anch, base, 0); !why.empty()) return fail("gik_anchored_retry_merge: " + why);
-  if (count == 0) return 0;
-  if (!d_idx || !d_Y_r || !d_stats_r || !d_q_r || !d_pos_err_r || !d_rot_err_r || !d_clearance_r || !d_Y_full || !d_stats ||
-      !d_q || !d_pos_err || !d_rot_err || !d_clearance || !d_attempt)
-    return fail("gik_anchored_retry_merge: null buffer");
-  const RetryMergeArgs a = {d_idx,
-                            d_Y_r, d_stats_r, d_q_r, d_pos_err_r, d_rot_err_r, d_clearance_r,
-                            d_Y_full, d_stats, d_q, d_pos_err, d_rot_err, d_clearance, d_attempt,
-                            {pos_tol, rot_tol, clear_tol}, count, anch->full_N * 3, base->pc.n_joints, attempt};
-  return retry_merge_launch(base, a, stream);
-}
-
-// the caller-owned workspace of the anchored restart loops over d_ws (gik_plan.h), or with a null d_ws its size
-static gik::AnchRetryWs anch_retry_ws(const gik_template *anch, const gik_template *base, int B, void *d_ws) {
-  return gik::anch_retry_ws(base->pc.n_joints, pose_width(base), base->T, base->N, anch->N, anch->an.n_goal, anch->full_N, B, d_ws);
-}
-
-size_t gik_anchored_retry_ws_bytes(const gik_template *anch, const gik_template *base, int B) {
-  if (!anch || !base || !anchored_pair_fault(anch, base, 0).empty() || B < 0) return 0;
-  return anch_retry_ws(anch, base, B, nullptr).bytes;      // (without the scene entry's ids)
-}
-
-// The restart loop of gik_anchored_ik_batch_retry and, with a scene set, of gik_anchored_ik_batch_retry_scenes: the scene
-// goes through attempt 0, every compact batch (its ids gathered into the workspace's last array) and every clearance.
-static int anchored_retry_impl(const char *entry, const gik_template *anch, const gik_template *base, const double *d_T_goal,
-                               const double *d_q_init, int B, const gik_anchored_retry_opts *opts, const gik_scene_set *scenes,
-                               bool with_scenes, void *d_ws, double *d_Y_full, gik_stats *d_stats, double *d_q, double *d_pos_err,
-                               double *d_rot_err, double *d_clearance, int32_t *d_attempt, void *stream) {
-  using namespace gik;
-  const std::string e(entry);
-  // every refusal comes before anything is queued
-  if (!anch || !base || B < 0 || !opts) return fail(e + ": bad argument");
-  if (const std::string why = anchored_pair_fault(anch, base, PAIR_3D); !why.empty()) return fail(e + ": " + why);
-  if (with_scenes && scene_refusal(entry, anch, scenes)) return -1;
-  if (opts->retries < 0 || opts->retries > 63) return fail(e + ": retries must be within 0 .. 63");
-  if (clearance_mode_refusal(e, anch, opts->clearance_mode)) return -1;
-  const bool links = opts->clearance_mode == GIK_CLEARANCE_LINKS;
-  if ((d_q_init || opts->retries > 0) && !base->seed_ok)
-    return fail(e + ": the base graph cannot be seeded on the device: " + base->seed_why);
-  if (opts->retries > 0) {
-    if (!opts->d_q_lo || !opts->d_q_hi)
-      return fail(e + ": null joint limits (opts->d_q_lo / d_q_hi, [n] each, are what the seeds are drawn from)");
-    if (!(opts->pos_tol > 0.0) || !(opts->rot_tol > 0.0)) return fail(e + ": pos_tol and rot_tol must be positive");
-    if (!(opts->clear_tol > 0.0)) return fail(e + ": clear_tol must be positive");
-    if (!(opts->spread >= 0.0)) return fail(e + ": spread must be at least 0 (radians; 0: uniform inside the limits)");
-    if (opts->spread > 0.0 && !d_q_init)
-      return fail(e + ": spread > 0 needs d_q_init, the centre the seeds are drawn around (a cold batch has none)");
-  }
-  if (refuse_capture(entry, stream)) return -1;
-  if (B == 0) return 0;
-  if (!d_clearance || !d_attempt) return fail(e + ": null d_clearance or d_attempt");
-  if (!d_ws) return fail(e + ": null workspace (gik_anchored_retry_ws_bytes)");
-  if ((uintptr_t)d_ws % 8) return fail(e + ": the workspace must be 8-byte aligned");
-  if (!d_T_goal || !d_Y_full || !d_stats || !d_q || !d_pos_err || !d_rot_err) return fail(e + ": null buffer");
-  hipStream_t s = (hipStream_t)stream;
-  const AnchRetryWs w = anch_retry_ws(anch, base, B, d_ws);
-  const bool local = opts->retries > 0 && opts->spread > 0.0;
-  const size_t n = (size_t)base->pc.n_joints;
-  // the centre of local mode is what attempt 0 started from; d_q_init may be d_q, which attempt 0 overwrites
-  if (local) HIP_OK(hipMemcpyAsync(w.q_center, d_q_init, (size_t)B * n * sizeof(double), hipMemcpyDeviceToDevice, s));
-  HIP_OK(hipMemsetAsync(d_attempt, 0, (size_t)B * sizeof(int32_t), s));
-  gik_scene_set compact;      // the scene set of a compact batch: its ids are gathered into w.ids
-  if (scenes) {
-    compact = *scenes;
-    if (scenes->d_scene_id) compact.d_scene_id = w.ids;
-  }
-  // link mode: the rule below is the same, the array it reads holds the clearance of whole links
-  int rc = anchored_attempt(anch, base, d_T_goal, d_q_init, B, scenes, w.scratch, d_Y_full, d_stats, d_q, d_pos_err, d_rot_err,
-                            d_clearance, links, stream);
-  if (rc) return rc;
-  for (int a = 1; a <= opts->retries; ++a) {
-    rc = gik_anchored_retry_select(d_stats, d_pos_err, d_rot_err, d_clearance, B, opts->pos_tol, opts->rot_tol,
-                                   opts->clear_tol, w.idx, w.count, stream);
-    if (rc) return rc;
-    int32_t count = 0;
-    rc = retry_read_count(entry, w.count, B, &count, s);
-    if (rc) return rc;
-    if (count == 0) break;
-    rc = gik_anchored_retry_seeds(base, d_T_goal, w.idx, count, opts->seed, a, opts->d_q_lo, opts->d_q_hi,
-                                  local ? w.q_center : nullptr, local ? opts->spread : 0.0, w.T, w.q_seed, stream);
-    if (rc) return rc;
-    if (scenes && scenes->d_scene_id) {
-      hipLaunchKernelGGL(scene_gather_kernel, dim3((count + ANCH_SCATTER_NT - 1) / ANCH_SCATTER_NT), dim3(ANCH_SCATTER_NT), 0, s,
-                         scenes->d_scene_id, w.idx, count, w.ids);
-      HIP_OK(hipGetLastError());
-    }
-    rc = anchored_attempt(anch, base, w.T, w.q_seed, count, scenes ? &compact : nullptr, w.scratch, w.Y, w.stats, w.q, w.pos_err,
-                          w.rot_err, w.clearance, links, stream);
-    if (rc) return rc;
-    rc = gik_anchored_retry_merge(anch, base, w.idx, count, a, opts->pos_tol, opts->rot_tol, opts->clear_tol, w.Y, w.stats,
-                                  w.q, w.pos_err, w.rot_err, w.clearance, d_Y_full, d_stats, d_q, d_pos_err, d_rot_err,
-                                  d_clearance, d_attempt, stream);
-    if (rc) return rc;
-  }
-  return 0;
-}
-
-int gik_anchored_ik_batch_retry(const gik_template *anch, const gik_template *base, const double *d_T_goal,
-                                const double *d_q_init, int B, const gik_anchored_retry_opts *opts, void *d_ws,
-                                double *d_Y_full, gik_stats *d_stats, double *d_q, double *d_pos_err, double *d_rot_err,
-                                double *d_clearance, int32_t *d_attempt, void *stream) {
-  return anchored_retry_impl("gik_anchored_ik_batch_retry", anch, base, d_T_goal, d_q_init, B, opts, nullptr, false, d_ws, d_Y_full,
-                             d_stats, d_q, d_pos_err, d_rot_err, d_clearance, d_attempt, stream);
-}
-
-int gik_anchored_ik_batch_retry_scenes(const gik_template *anch, const gik_template *base, const double *d_T_goal,
-                                       const double *d_q_init, int B, const gik_anchored_retry_opts *opts,
-                                       const gik_scene_set *scenes, void *d_ws, double *d_Y_full, gik_stats *d_stats, double *d_q,
-                                       double *d_pos_err, double *d_rot_err, double *d_clearance, int32_t *d_attempt, void *stream) {
-  return anchored_retry_impl("gik_anchored_ik_batch_retry_scenes", anch, base, d_T_goal, d_q_init, B, opts, scenes, true, d_ws,
-                             d_Y_full, d_stats, d_q, d_pos_err, d_rot_err, d_clearance, d_attempt, stream);
-}
-
-double gik_anchored_last_solve_ms(const gik_template *anch) {
-  if (!anch || !anch->ev_solve0) return -1.0;
-  float ms = -1.0f;
-  hipEvent_t e0, e1;
-  {   // the handles under the lock (a record in another thread is not interleaved with this read), the wait outside it
-    std::lock_guard<std::mutex> lock(const_cast<gik_template *>(anch)->ev_mutex);
-    e0 = anch->ev_solve0;
-    e1 = anch->ev_solve1;
-  }
-  if (hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) {
-    (void)hipGetLastError();      // (a pair recorded by two different concurrent calls has no defined duration)
-    return -1.0;
-  }
-  return (double)ms;
 }
 
 static int launch_kat(const gik_template *t, int mode, const double *d_Y, const double *d_W,
