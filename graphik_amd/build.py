@@ -52,10 +52,26 @@ def source_digest(extra=()):
     return h.hexdigest()
 
 
+def _unit_headers(src, extra):
+    """The headers ONE translation unit includes, transitively, as the compiler lists them (-MM: it only preprocesses);
+    every header where it cannot say."""
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    inc = ["-I" + os.path.join(REPO, "include"), "-I" + SRC]
+    cmd = [hipcc] + FLAGS + UNIT_FLAGS.get(src, []) + list(extra) + inc + ["--cuda-host-only", "-MM", os.path.join(SRC, src)]
+    try:
+        r = subprocess.run(cmd, capture_output=True, text=True)
+    except OSError:
+        return headers()
+    seen = {os.path.realpath(w) for w in r.stdout.replace("\\\n", " ").split()}
+    mine = [h for h in headers() if os.path.realpath(h) in seen]
+    return mine if r.returncode == 0 and mine else headers()
+
+
 def _unit_digest(src, extra):
-    """... of ONE translation unit: its own text, every header, the flags."""
+    """... of ONE translation unit: its own text, the headers it includes, the flags.  Only the object cache reads it:
+    whether the library is stale is source_digest's to say, which hashes every file."""
     h = hashlib.sha256(" ".join(FLAGS + UNIT_FLAGS.get(src, []) + list(extra)).encode())
-    for d in [os.path.join(SRC, src)] + headers():
+    for d in [os.path.join(SRC, src)] + _unit_headers(src, extra):
         h.update(os.path.relpath(d, REPO).encode())
         h.update(open(d, "rb").read())
     return h.hexdigest()

@@ -22,12 +22,14 @@
 //                           the obstacle rows of a per-goal scene (gik_scene_set), and the scene ids of a compact batch.
 // anch_link_pair, anch_link_foot (the pair function of the solve kernel's link hinges), anch_sweep_interp and
 // anch_sweep_min are __host__ __device__, so that a host program can walk them.
-// Plain kernels, defined where GIK_DEFINE_ANCH_SEED_KERNELS is set (gik_k_anch_seed.hip); gik_host.hip sees prototypes.
+// Plain kernels, defined where GIK_DEFINE_ANCH_SEED_KERNELS is set (gik_k_anch_seed.hip); every other unit that includes
+// this header -- the two host units, which launch them -- sees prototypes.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
-#include "gik_prep.hip.h"
+#include "gik_anch_glue.hip.h"      // (anchor_world)
+#include "gik_args.h"
 #include "gik_scenes.h"
 
 namespace gik {

@@ -31,6 +31,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gik_args.h"
 #include "gik_wave.hip.h"
 
 namespace gik {
@@ -41,20 +42,6 @@ constexpr int BLOCK_MAXN = BLOCK_NT / 4;  // 128 nodes
 constexpr int CLQ_M = BLOCK_MAXN / 4;     // clique partners per thread (row 4m + part, m < CLQ_M)
 constexpr int CLQ_NCQ = 12;               // per accepted point: Syy (3 x 3, row-major), tr Syy, n, pad
 constexpr int CLQ_NMOM = 27;              // Sw[3], M[3][3], T3[3], U3[3] (Euclidean targets: U3 - R3), P[3][3]
-
-// launch-invariant tables of the workgroup-per-problem path (device pointers; gik_template_create)
-struct BlockTabs {
-  const int *nc_term;      // [Tc] index in the caller's target row of each slot-table term; null = identity
-  const int *clq_term;     // [M][512] target index of clique pair (row tid >> 2, row 4m + (tid & 3)); -1 = none
-  const int *clq_pair_term;        // [n_pairs] target index of clique pair p (each pair once)
-  const unsigned short *clq_pid_t; // [M][512] pair id of (row tid >> 2, row 4m + (tid & 3)), like clq_term; 0xffff = none
-  int n_pairs;
-  const int *node_of_row;  // [128] node (the caller's numbering) of each LDS row; null = identity
-  const int *wave_sl;      // [8][2] slot-loop bounds {SLE, SL} of each wavefront
-  int Tc;                  // terms kept in the slot tables
-  int n_clq;               // clique size (rows 0..n_clq-1), 0 = none
-  int clq_euclid;          // 1: look for point coordinates behind the clique's target distances
-};
 
 template <int K>
 struct BlockCtx {

@@ -3,7 +3,13 @@
 // belongs here.
 #pragma once
 
-#include "gik_kernels.hip.h"
+#include <hip/hip_runtime.h>
+
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "gik_args.h"
 #include "gik_order.hip.h"
 #include "gik_plan.h"
 #define GIK_INTERNAL __attribute__((visibility("hidden")))      // shared between the two units, not an export

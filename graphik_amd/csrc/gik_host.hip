@@ -6,22 +6,24 @@
 // gik_handle.h's, defined here.  No device code is compiled here: the kernels live in gik_k_*.hip (gik_instances.h).
 
 #include "gik_handle.h"
+#include "gik_kernels.hip.h"
 #include "gik_instances.h"
 #include "gik_anch_seed.hip.h"
 #include "gik_slots.h"
 #include "gik_tables.hip.h"
+#include <algorithm>
+#include <atomic>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
 #include <memory>
+#include <thread>
 
 namespace gik {
 GIK_ALL_KERNELS(GIK_EXTERN_TEMPLATE)
 GIK_KERNELS_ANCH_LINK(GIK_EXTERN_TEMPLATE)
 GIK_KERNELS_ANCH_SCENE(GIK_EXTERN_TEMPLATE)
-static_assert(PLAN_MIG_SIMDS == MIG_SIMDS && PLAN_SLICE_STATE_BYTES == sizeof(SliceState) && PLAN_QUAD_SLOTS == QUAD_SLOTS,
-              "gik_plan.h restates these constants of the kernel headers");
-static_assert(PLAN_CLAIM_KEY_MAX_TERMS == CLAIM_KEY_MAX_TERMS, "gik_plan.h restates this constant of gik_order.hip.h");
-static_assert(PLAN_PREP_MAXN == PREP_MAXN && PLAN_PREP_BIGN == PREP_BIGN && PLAN_PREPQ_MAXN == PREPQ_MAXN &&
-                  PLAN_PREPQ_VEC_STRIDE == PREPQ_VEC_STRIDE && PLAN_PREP_NT == PREP_NT && PLAN_WAVE == WAVE,
-              "gik_plan.h restates these constants of gik_prep.hip.h and gik_prep_quad.hip.h");
 
 // the compiled node-per-lane variants
 struct NptVariant {

@@ -1,14 +1,16 @@
 // graphik_amd/csrc/gik_host_anch.hip -- the second host unit: the restarts and the fixed-anchor (obstacle) solve, with
 // their part of the C ABI of include/graphik_amd.h.  A client of gik_host.hip: it reaches templates and the prepare / seed /
 // solve / recover path only through the library's exports and the helpers of gik_handle.h (gik_anchored_attach_links is
-// creation and lives there).  It launches the plain kernels of gik_retry.hip.h, gik_anch_seed.hip.h and gik_prep.hip.h by
-// their prototypes: no device code is compiled here.
+// creation and lives there).  It launches the plain kernels of gik_retry.hip.h, gik_anch_seed.hip.h and gik_anch_glue.hip.h
+// by their prototypes: no device code is compiled here, and no solve kernel's header is seen.
 
 #include "gik_handle.h"
 #include "gik_retry.hip.h"
+#include "gik_anch_glue.hip.h"
 #include "gik_anch_seed.hip.h"
 #include "gik_plan.h"
 #include "gik_scenes.h"
+#include <algorithm>
 #include <climits>
 
 // doubles of one goal: a (K+1) x (K+1) pose per end effector

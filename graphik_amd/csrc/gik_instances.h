@@ -3,8 +3,10 @@
 // GIK_KERNELS_<GROUP>(X) calls X(<function signature>) for every instantiation of the group; gik_k_<group>.hip expands
 // it with GIK_INSTANTIATE, gik_host.hip expands all groups with GIK_EXTERN_TEMPLATE (so that taking a kernel's address
 // there -- the variant tables, hipLaunchKernelGGL -- refers to the other file's symbol instead of compiling the kernel
-// a second time).  The five non-template kernels (prep_wave_kernel, recover_kernel, seed_kernel, anch_init_kernel,
-// anch_gather_kernel) are defined where GIK_DEFINE_PLAIN_KERNELS is set: gik_k_prep.hip.
+// a second time).  The five non-template kernels (prep_wave_kernel of gik_prep.hip.h; recover_kernel, seed_kernel of
+// gik_recover_seed.hip.h; anch_init_kernel, anch_gather_kernel of gik_anch_glue.hip.h) are defined where
+// GIK_DEFINE_PLAIN_KERNELS is set, gik_k_prep.hip; every other unit that includes one of those headers -- both host units
+// do -- sees their prototypes.  This header names kernels and argument types only: include the family's header first.
 #pragma once
 
 #define GIK_INSTANTIATE(...) template __global__ __VA_ARGS__;
@@ -91,7 +93,7 @@
   X(void kat_quad_kernel<6>(KatArgs))       \
   X(void prep_quad_kernel<13>(PrepArgs))    \
   X(void prep_quad_kernel<0>(PrepArgs))
-// prepare (workgroup per goal); the plain kernels of gik_prep.hip.h are defined next to these
+// prepare (workgroup per goal); the five plain kernels are defined next to these
 #define GIK_KERNELS_PREP(X)                            \
   X(void prep_block_kernel<true>(PrepArgs, double *))  \
   X(void prep_block_kernel<false>(PrepArgs, double *)) \

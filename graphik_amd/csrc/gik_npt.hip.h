@@ -32,32 +32,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gik_args.h"
 #include "gik_wave.hip.h"
 
 namespace gik {
 
 constexpr int NPT_MAXN = 2 * WAVE;     // rows
 constexpr int NPT_RS = 4;              // LDS row stride (doubles)
-
-// launch-invariant tables (device pointers; gik_template_create)
-struct NptTabs {
-  const int *node_of_row;          // [128] the caller's node held by thread slot NS * thread + s, -1 = none
-  const unsigned char *prow_of_slot;   // [128] its row in the point table sh_P (clique nodes: cbase + rank)
-  const int *clq_pair_term;        // [n_pairs] target index of clique pair (a < b: clique ranks), p = a n - a (a + 1) / 2 + b - a - 1
-  const uint32_t *term_rec;        // [TL][64] row_i | row_j << 8 | kind << 16 | wslot_i << 18 | wslot_j << 25; kind 0 = padding
-  const int *term_tgt;             // [TL][64] target index of the lane's term, -1 = padding
-  const unsigned short *gather;    // [DEG0 + DEG1][threads] row of the +-t table the thread adds: 2 slot (+t) or 2 slot + 1 (-t);
-                                   // padding = the zero row 2 * n_terms
-  const unsigned char *wslot_of_row;   // [128] (per thread slot) row of the compact direction table that publishes the node, 255 = none
-  int n_clq, n_pairs, DEG0, DEG1, n_wrows, TL;
-  int clq_euclid;                  // 1: look for point coordinates behind the clique's target distances
-  int cbase;                       // first row of the clique (its nodes take rows cbase .. cbase + n_clq - 1, rank = row - cbase)
-  int n_rows;                      // rows in use (even)
-  int n_terms;                     // slot terms (the first n_terms of the TL * 64 term slots, all evaluated by wavefront 0)
-  int term_sync;                   // two waves per problem: 1 = end nodes of slot terms sit in both wavefronts
-  int n_helped;                    // one node per lane: lanes 2 i (i < n_helped) hold the busiest nodes, lane 2 i + 1 gathers the
-                                   // second half of lane 2 i's list (the gather is as long as the longest list of any lane)
-};
 
 // Sum 24 independent per-lane values over the wavefront by transposing exchanges (the scheme of
 // wave_sum_n<8>, five levels deep): each level pairs the registers, a lane keeps one value of the

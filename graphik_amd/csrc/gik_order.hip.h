@@ -10,15 +10,16 @@
 //                       B^2 comparisons on LDS broadcasts -- 64 problems x 4 quarters of the key array per workgroup,
 //                       ~10 us at 4096 problems, a few hundred at PLAN_CLAIM_ORDER_MAX_BATCH, beyond which the plan
 //                       keeps index order (gik_plan.h).
-// Plain kernels, defined where GIK_DEFINE_ORDER_KERNELS is set (gik_k_order.hip); gik_host.hip sees prototypes.
+// Plain kernels, defined where GIK_DEFINE_ORDER_KERNELS is set (gik_k_order.hip); the host units see prototypes.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gik_args.h"
+
 namespace gik {
 
-constexpr int CLAIM_KEY_MAX_TERMS = 8;
 constexpr int ORDER_ROWS = 64;                      // problems per workgroup of claim_rank_kernel
 constexpr int ORDER_PARTS = 4;                      // ... each against a quarter of the keys per wavefront
 constexpr int ORDER_NT = ORDER_ROWS * ORDER_PARTS;

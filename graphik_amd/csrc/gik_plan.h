@@ -12,14 +12,11 @@
 #include <cstdint>
 
 #include "../../include/graphik_amd.h"      // (gik_stats, 48 bytes, in the restart workspaces; after <cstddef>: it uses size_t)
+#include "gik_args.h"      // what the plan knows of the kernels' data: their constants and sizeof(SliceState)
 
 namespace gik {
 
-// what the plan knows of the kernels' data (gik_host.hip static_asserts them against the kernel headers)
-constexpr int PLAN_MIG_SIMDS = 1 << 14;          // SIMD slots of the spread table (MIG_SIMDS)
-constexpr size_t PLAN_SLICE_STATE_BYTES = 32;    // sizeof(SliceState)
-constexpr int PLAN_QUAD_SLOTS = 4;               // problems per quad wavefront (QUAD_SLOTS)
-constexpr int PLAN_CLAIM_KEY_MAX_TERMS = 8;      // terms of a template's claim key (CLAIM_KEY_MAX_TERMS)
+constexpr int PLAN_CLAIM_KEY_MAX_TERMS = CLAIM_KEY_MAX_TERMS;      // (the name tests/host/claim_order_plan.cpp checks)
 // Largest batch whose claims are ordered.  The rank kernel compares every pair of keys: ~10 us at 4096 problems and
 // about 0.3 ms here, against a solve of several hundred ms; beyond it a batch is hundreds of problems deep per wave and
 // its time is throughput, not the start of one problem, so the plan keeps index order rather than pay B^2.
@@ -143,9 +140,9 @@ inline SolvePlan plan_solve(const SolveFacts &t, int B) {
     const size_t ycap = wslice > 0 ? std::min((size_t)B * (size_t)(t.maxiter / wslice + 2), (size_t)16 * B + 8192) +
                                          2 * (size_t)grid + 256
                                    : 0;      // (very short slices: the queue fills and the problems stop yielding)
-    const size_t off_simd = 32, off_seq = off_simd + (mig ? sizeof(int) * PLAN_MIG_SIMDS : 0), off_ids = off_seq + cap * 4,
+    const size_t off_simd = 32, off_seq = off_simd + (mig ? sizeof(int) * MIG_SIMDS : 0), off_ids = off_seq + cap * 4,
                  off_state = (off_ids + cap * 4 + 15) & ~(size_t)15,
-                 off_yseq = off_state + (((size_t)B * PLAN_SLICE_STATE_BYTES + 15) & ~(size_t)15), off_yids = off_yseq + ycap * 4;
+                 off_yseq = off_state + (((size_t)B * sizeof(SliceState) + 15) & ~(size_t)15), off_yids = off_yseq + ycap * 4;
     const size_t off_ctg = (off_yids + ycap * 4 + 63) & ~(size_t)63;
     // (the order's buffers come last: a plan without them is laid out as it always was)
     const size_t off_key = (off_ctg + ctg_bytes + 63) & ~(size_t)63, off_order = off_key + (p.order ? 4 * (size_t)B : 0);
@@ -166,7 +163,7 @@ inline SolvePlan plan_solve(const SolveFacts &t, int B) {
     p.off_order = off_order;
     p.zero_head = queues ? off_seq : 0;      // (no queue: nothing reads the head)
     p.seq_fill = cap * 4;
-    p.state_zero = (mig || t.is_npt) ? (size_t)B * PLAN_SLICE_STATE_BYTES : 0;
+    p.state_zero = (mig || t.is_npt) ? (size_t)B * sizeof(SliceState) : 0;
     p.yseq_zero = ycap * 4;
   }
   // four planar problems per wavefront: from 12 problems per CU on (measured, planar-10, events around the call:
@@ -177,7 +174,7 @@ inline SolvePlan plan_solve(const SolveFacts &t, int B) {
     // a wavefront holds four problems: a quarter of the waves (at least one slot each), no slicing
     int qw = t.quad_waves_per_cu;
     if (t.wpc_override > 0) qw = t.wpc_override;
-    p.launch_grid = std::max(1, std::min((B + PLAN_QUAD_SLOTS - 1) / PLAN_QUAD_SLOTS, t.n_cu * qw));
+    p.launch_grid = std::max(1, std::min((B + QUAD_SLOTS - 1) / QUAD_SLOTS, t.n_cu * qw));
     p.launch = Launch::QUAD;
   } else if (t.is_npt) {
     p.launch = Launch::NPT;
@@ -191,17 +188,11 @@ inline SolvePlan plan_solve(const SolveFacts &t, int B) {
 
 // ---- the device prepare (gik_pipeline_attach, gik_prepare_batch): which of the six prepare kernels a template runs, its
 // dynamic LDS bytes, resident waves per CU, slab and grids.  Decided once, at attach.
-constexpr int PLAN_PREP_MAXN = 128;          // nodes of the workgroup kernels' small LDS arrays (PREP_MAXN) ...
-constexpr int PLAN_PREP_BIGN = 256;          // ... and of the build for 129 .. 255 nodes (PREP_BIGN)
-constexpr int PLAN_PREPQ_MAXN = 16;          // nodes of a goal of the quad kernel (PREPQ_MAXN)
-constexpr int PLAN_PREPQ_VEC_STRIDE = 104;   // doubles of a goal slot's small arrays (PREPQ_VEC_STRIDE)
-constexpr int PLAN_PREP_NT = 512;            // threads of a workgroup kernel (PREP_NT)
-constexpr int PLAN_WAVE = 64;
 
 // prep_quad_lds_bytes of gik_prep_quad.hip.h (tests/golden/prep_plan.json pins the two equal)
 constexpr size_t plan_prep_quad_lds_bytes(int N, int n_gd) {
   const int NS = N * (N | 1), stride = NS + ((16 - NS % 32) + 32) % 32;
-  return sizeof(double) * ((size_t)12 * stride + 4 * (size_t)((n_gd + 1) & ~1) + 4 * PLAN_PREPQ_VEC_STRIDE);
+  return sizeof(double) * ((size_t)12 * stride + 4 * (size_t)((n_gd + 1) & ~1) + 4 * PREPQ_VEC_STRIDE);
 }
 
 // What plan_prepare reads: the graph and the pipeline descriptor, and the developer switches of the environment, which
@@ -236,9 +227,9 @@ struct PrepPlan {
   int n_cu = 0;
   bool block() const { return variant >= Prep::BLOCK_LDS; }
   bool quad() const { return variant <= Prep::QUAD; }
-  int threads() const { return block() ? PLAN_PREP_NT : PLAN_WAVE; }
+  int threads() const { return block() ? PREP_NT : WAVE; }
   int launch_grid(int B) const {
-    return std::min(quad() ? (B + PLAN_QUAD_SLOTS - 1) / PLAN_QUAD_SLOTS : B, n_cu * wpc);
+    return std::min(quad() ? (B + QUAD_SLOTS - 1) / QUAD_SLOTS : B, n_cu * wpc);
   }
   // the plan of a launch with diagnostics (gik_prepare_batch_debug): the quad kernel has none, prep_wave_kernel runs instead
   PrepPlan diagnostics() const {
@@ -266,17 +257,17 @@ inline PrepPlan plan_prepare(const PrepFacts &f, Occupancy occupancy) {
   // graphs beyond one wavefront's LDS: workgroup-per-goal kernel with its matrices in a global slab
   if (N > 32 || f.n_anchor > 32 || f.force_block_prepare || f.env_force_block) {
     int occ = 0;
-    if (N > PLAN_PREP_MAXN) {      // graphs of 129 .. 255 nodes: six matrices per slab
+    if (N > PREP_MAXN) {      // graphs of 129 .. 255 nodes: six matrices per slab
       p.variant = Prep::BLOCK_BIG;
-      if ((occ = occupancy(p.variant, PLAN_PREP_NT, p.lds)) < 0) occ = 1;
+      if ((occ = occupancy(p.variant, PREP_NT, p.lds)) < 0) occ = 1;
     } else {
       // work matrix in LDS when it fits next to the kernel's static arrays (N <= 123), one workgroup per CU
       p.variant = Prep::BLOCK_LDS;
       p.lds = sizeof(double) * NN;
-      if (f.env_a_global || (occ = occupancy(p.variant, PLAN_PREP_NT, p.lds)) < 1) {
+      if (f.env_a_global || (occ = occupancy(p.variant, PREP_NT, p.lds)) < 1) {
         p.variant = Prep::BLOCK;
         p.lds = 0;
-        if ((occ = occupancy(p.variant, PLAN_PREP_NT, p.lds)) < 0) occ = 1;
+        if ((occ = occupancy(p.variant, PREP_NT, p.lds)) < 0) occ = 1;
       }
     }
     occ = std::max(1, std::min(occ, 2));   // 5 N^2 doubles per workgroup: keep the slabs cache-resident
@@ -288,16 +279,16 @@ inline PrepPlan plan_prepare(const PrepFacts &f, Occupancy occupancy) {
   // the prepare kernel is latency-bound (dependent Jacobi chains, LDS round trips): run as many
   // resident waves per CU as its registers and LDS allow (a fixed 8 per CU left half of them
   // unused: planar-10 prepare 2.3 -> see NOTEBOOK 4.2)
-  int occ = occupancy(Prep::WAVE, PLAN_WAVE, p.wave_lds);
+  int occ = occupancy(Prep::WAVE, WAVE, p.wave_lds);
   if (occ < 0) occ = 8;
   if (f.env_waves_set) occ = f.env_waves;   // developer override
   p.lds = p.wave_lds;
   p.wpc = p.wave_wpc = std::max(1, std::min(occ, 32));
-  if (N <= PLAN_PREPQ_MAXN && !f.inert_goal_slot && !f.env_no_quad) {
+  if (N <= PREPQ_MAXN && !f.inert_goal_slot && !f.env_no_quad) {
     const Prep quad = N == 13 ? Prep::QUAD13 : Prep::QUAD;
     const size_t quad_lds = plan_prep_quad_lds_bytes(N, n_gd);
     int qocc = 0;
-    if (quad_lds <= 40 * 1024 && (qocc = occupancy(quad, PLAN_WAVE, quad_lds)) >= 1) {
+    if (quad_lds <= 40 * 1024 && (qocc = occupancy(quad, WAVE, quad_lds)) >= 1) {
       if (f.env_waves_set) qocc = f.env_waves;
       p.variant = quad;
       p.lds = quad_lds;

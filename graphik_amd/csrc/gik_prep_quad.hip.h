@@ -33,18 +33,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "gik_prep.hip.h"
-#include "gik_quad.hip.h"
+#include "gik_args.h"
+#include "gik_goal.hip.h"
+#include "gik_prep.hip.h"      // (desc_rank; the Jacobi and the Sturm count are this header's own renderings)
 
 namespace gik {
-
-constexpr int PREPQ_MAXN = QUAD_NODES;
-// The small per-goal arrays -- ev, sg, hv, hw (16 doubles each), the rotations (c, s) (16 double2) and the ranks (16
-// ints) -- form ONE block of 104 doubles per goal slot.  104 = 8 mod 32: what the four goals of a half-wave read at
-// the same index (broadcast reads, most of the traffic to these arrays; for the rotations a ds_read_b128) falls into
-// four different bank groups.  Until round 5 every array had a slot stride of 16 or 32 doubles: the four goals' (c, s)
-// sat on the SAME banks (every read of a rotation 4-way conflicted), the others two by two.
-constexpr int PREPQ_VEC_STRIDE = 104;
 
 // sum over the 16 lanes of a goal (a DPP row); every lane gets the total, bit-identical in all 16 (each level adds
 // two partial sums that are equal in the lanes exchanging them)

@@ -14,14 +14,10 @@
 
 #include <hip/hip_runtime.h>
 
+#include "gik_args.h"
 #include "gik_rtr.hip.h"
 
 namespace gik {
-
-struct CgParams {
-  double mingradnorm, minstepsize, orth_value;
-  int maxiter, beta_type, planar_proj_exact;
-};
 
 enum { CG_FLETCHER_REEVES = 0, CG_POLAK_RIBIERE = 1, CG_HESTENES_STIEFEL = 2, CG_HAGER_ZHANG = 3 };
 

@@ -15,7 +15,7 @@
 // where the caller hands in the link clearance, any part of a link -- inside a sphere has failed).  The plain solve has
 // no clearance: its kernels get null clearance pointers, which read as +inf, and +inf drops out of the rule.
 // The rule and the seed formula are __host__ __device__ functions, so that a host program can walk them.
-// Plain kernels, defined where GIK_DEFINE_RETRY_KERNELS is set (gik_k_retry.hip); gik_host.hip sees prototypes.
+// Plain kernels, defined where GIK_DEFINE_RETRY_KERNELS is set (gik_k_retry.hip); gik_host_anch.hip, which launches them, sees prototypes.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -130,7 +130,6 @@ struct MigCtl {
   int slice_cycles;             // shortest slice in cycles of the shader clock counter
 };
 enum { PAUSE_NONE = 0, PAUSE_DONATE = 1, PAUSE_YIELD = 2 };
-constexpr int MIG_SIMDS = 1 << 14;
 
 template <typename Ctx>
 __device__ inline bool mig_poll(const Ctx &cx, const MigCtl &m) {

@@ -28,11 +28,10 @@
 #include <stdint.h>
 
 #include "graphik_amd.h"
+#include "gik_args.h"
 #include "gik_scenes.h"
 
 namespace gik {
-
-constexpr int WAVE = 64;
 
 constexpr int TILE_ROWS = 33;  // 32 nodes max + one dump row for idle lanes
 
@@ -294,12 +293,6 @@ __device__ inline void vertical_basis(double a, double b, double c, double d, do
   Q[2] = fma(-l21, Q[1], fma(-l20, Q[0], pk[2])) * i22;
 }
 
-// ---- solver parameters handed to the kernels ----------------------------------------------
-struct Params {
-  double mingradnorm, theta, kappa, rho_prime, rho_regularization;
-  int maxiter, maxinner, mininner, planar_proj_exact;
-};
-
 enum {
   TCG_NEGATIVE_CURVATURE = 0,
   TCG_EXCEEDED_TR = 1,
@@ -325,10 +318,6 @@ struct Row {
 // An anchor does not move, so these terms touch cost(), commit() and the diagonal blocks `bsum` of
 // the Hessian only -- the Hessian-vector product costs what it costs without obstacles.  Anchors
 // fix the gauge: the search space is Euclidean (no horizontal projection, Q = 0).
-constexpr int ANCH_PMAX = 8;
-constexpr int ANCH_MAXA = 16;   // rows of the pinned-anchor table
-constexpr int ANCH_MAXOBS = 128; // obstacles (staged in LDS: 32 B each)
-static_assert(SCENE_MAX_SPHERES == ANCH_MAXOBS, "gik_scenes.h restates this constant");
 
 // LINKS: link hinges on top (opt-in per template, gik_anchored_attach_links with hinges = 1).  A link l = (a, b, rho) is
 // the segment between two rows of the full point matrix -- free rows of Y, constant base anchors or the per-problem goal
@@ -345,14 +334,6 @@ static_assert(SCENE_MAX_SPHERES == ANCH_MAXOBS, "gik_scenes.h restates this cons
 // commit(), like the anchor terms) and a difference-form block that goes into bq[s] of the slot whose neighbour is the other
 // end -- on a chain consecutive p-nodes always share the link-length equality -- so ehess() runs unchanged.
 // Records are per NODE (the three lanes of a node share them), at most ANCH_LMAX links per free node.
-constexpr int ANCH_LMAX = 2;
-constexpr int ANCH_LROWS = 22;  // rows of the per-node link tables: 3 N <= 64 gives 21 free nodes, + one inert row for idle lanes
-struct AnchLinkRec {
-  double rho;      // capsule radius of the link
-  uint32_t meta;   // [0] valid, [1] this node is end b, [2] the other end is a row of sh_anch (constant), [15:8] the other
-                   // end's row (tile row of a free node / row of sh_anch), [23:16] the slot whose neighbour it is (0xff: none)
-  uint32_t pad;
-};
 __host__ __device__ inline uint32_t link_meta_pack(int is_b, int other_const, int other_row, int slot) {
   return 1u | ((uint32_t)is_b << 1) | ((uint32_t)other_const << 2) | ((uint32_t)other_row << 8) | ((uint32_t)slot << 16);
 }
