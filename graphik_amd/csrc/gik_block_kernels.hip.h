@@ -71,15 +71,7 @@ __global__ void __launch_bounds__(BLOCK_NT) rtr_block_kernel(SolveArgs a, int SL
     if (cx.active) a.Y_out[(size_t)b * NK + cx.gnode * K + cx.part] = x;
     if (UNI(ro.paused)) {
       if (tid == 0) {
-        SliceState st;
-        st.Delta = ro.Delta;
-        st.kiter = ro.iterations;
-        st.inner_total = ro.inner_total;
-        st.inner_exec = ro.inner_executed;
-        st.n_accept = ro.n_accept;
-        st.resumes = rs.resumes + 1;
-        st.pad = 0;
-        a.q_state[b] = st;
+        a.q_state[b] = slice_state_of(ro, rs.resumes + 1);
       }
       __threadfence();
       __syncthreads();
@@ -87,17 +79,7 @@ __global__ void __launch_bounds__(BLOCK_NT) rtr_block_kernel(SolveArgs a, int SL
       continue;
     }
     if (tid == 0) {
-      gik_stats s;
-      s.f = ro.f;
-      s.gradnorm = ro.gradnorm;
-      s.iterations = ro.iterations;
-      s.inner_total = ro.inner_total;
-      s.stop = ro.stop;
-      s.n_accept = ro.n_accept;
-      s.inner_executed = ro.inner_executed;
-      s.flags = cx.lowrank ? 1 : 0;
-      s.stepsize = ro.Delta;
-      a.stats[b] = s;
+      a.stats[b] = stats_of(ro, cx.lowrank ? 1 : 0);
       if (a.slice_its > 0) __hip_atomic_fetch_add(a.q_done, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
@@ -124,17 +106,7 @@ __global__ void __launch_bounds__(BLOCK_NT) rcg_block_kernel(SolveArgs a, int SL
     rcg_solve_one<K>(cx, a.cg, a.trace, a.has_trace, b, x, ro);
     if (cx.active) a.Y_out[(size_t)b * NK + cx.gnode * K + cx.part] = x;
     if (tid == 0) {
-      gik_stats s;
-      s.f = ro.f;
-      s.gradnorm = ro.gradnorm;
-      s.iterations = ro.iterations;
-      s.inner_total = ro.inner_total;
-      s.stop = ro.stop;
-      s.n_accept = ro.n_accept;
-      s.inner_executed = ro.inner_executed;
-      s.flags = cx.lowrank ? 1 : 0;
-      s.stepsize = ro.Delta;
-      a.stats[b] = s;
+      a.stats[b] = stats_of(ro, cx.lowrank ? 1 : 0);
     }
   }
 }

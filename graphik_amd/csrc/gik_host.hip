@@ -22,8 +22,6 @@
 
 namespace gik {
 GIK_ALL_KERNELS(GIK_EXTERN_TEMPLATE)
-GIK_KERNELS_ANCH_LINK(GIK_EXTERN_TEMPLATE)
-GIK_KERNELS_ANCH_SCENE(GIK_EXTERN_TEMPLATE)
 
 // the compiled node-per-lane variants
 struct NptVariant {
@@ -56,9 +54,11 @@ typedef void (*kat_fn)(KatArgs);
 typedef size_t (*lds_fn)(int);
 
 // The compiled one-unknown-per-lane builds: one row per (K, slots, form), exactly what gik_instances.h instantiates.
-// A build a form does not have stays null: only the functions below fill a row, each with what its form compiles.
-// (PER_EDGE: hessian_form = GIK_HESS_PER_EDGE, k = 3, TrustRegions; ANCHORED: the fixed-anchor formulation, k = 3, theta == 1)
-enum Form { COLUMN, PER_EDGE, ANCHORED };
+// A build a form does not have stays null.
+// (PER_EDGE: hessian_form = GIK_HESS_PER_EDGE, k = 3, TrustRegions; ANCHORED: the fixed-anchor formulation, k = 3, theta == 1;
+// ANCHORED_LINK: ... with link hinges.  Creation never asks for that form: gik_anchored_attach_links with hinges = 1
+// re-resolves an anchored 9-slot template to it)
+enum Form { COLUMN, PER_EDGE, ANCHORED, ANCHORED_LINK };
 struct WaveRow {
   int K, slots;
   Form form;
@@ -66,48 +66,24 @@ struct WaveRow {
   solve_fn solve_theta = nullptr;   // any theta
   solve_fn solve_cg = nullptr;      // ConjugateGradient
   solve_fn solve_spread = nullptr;  // theta == 1 with tail spreading (MigCtl)
-  scene_fn solve_scene = nullptr;   // ANCHORED: the scene build of `solve` (gik_solve_batch_scenes)
+  scene_fn solve_scene = nullptr;   // anchored forms: the scene build of `solve` (gik_solve_batch_scenes)
   kat_fn kat = nullptr;
   lds_fn lds = nullptr;
 };
-template <int K, int D>
-static WaveRow column_row(solve_fn solve_spread = nullptr) {
-  WaveRow r{K, D, COLUMN};
-  r.solve = rtr_wave_kernel<K, D, true>;
-  r.solve_theta = rtr_wave_kernel<K, D, false>;
-  r.solve_cg = rcg_wave_kernel<K, D>;
-  r.solve_spread = solve_spread;
-  r.kat = kat_wave_kernel<K, D>;
-  r.lds = WaveCtx<K, D>::lds_bytes;
-  return r;
-}
-template <int K, int D>
-static WaveRow per_edge_row() {
-  WaveRow r{K, D, PER_EDGE};
-  r.solve = rtr_wave_kernel<K, D, true, false, false, true>;
-  r.solve_theta = rtr_wave_kernel<K, D, false, false, false, true>;
-  r.solve_spread = rtr_wave_kernel<K, D, true, false, true, true>;
-  r.kat = kat_wave_kernel<K, D, false, true>;
-  r.lds = WaveCtxStrict<D>::lds_bytes;
-  return r;
-}
-template <int K, int D>
-static WaveRow anchored_row() {
-  WaveRow r{K, D, ANCHORED};
-  r.solve = rtr_wave_kernel<K, D, true, true>;
-  r.solve_scene = rtr_wave_scene_kernel<D, false>;
-  r.kat = kat_wave_kernel<K, D, true>;
-  r.lds = WaveCtx<K, D, true>::lds_bytes;
-  return r;
-}
-// the fixed-anchor kernels with link hinges (gik_anchored_attach_links, hinges = 1).  Not a row of kWaveRows: creation never
-// chooses it, the attach call re-resolves an anchored 9-slot template to it
-static WaveRow anchored_link_row() {
-  WaveRow r{3, 9, ANCHORED};
-  r.solve = rtr_wave_kernel<3, 9, true, true, false, false, true>;
-  r.solve_scene = rtr_wave_scene_kernel<9, true>;
-  r.kat = kat_wave_kernel<3, 9, true, false, true>;
-  r.lds = WaveCtx<3, 9, true, false, true>::lds_bytes;
+// Every kernel of a row, named by the form's flag bits (WaveBuild).  The free-free forms compile an any-theta build, the
+// column form ConjugateGradient, the anchored forms a scene entry; MORE: W_SPREAD where the form has a tail-spreading
+// build -- the per-edge form always, the column form at <3, 9> only.
+template <int K, int D, Form F, unsigned MORE = (F == PER_EDGE ? W_SPREAD : 0u)>
+static WaveRow wave_row() {
+  constexpr unsigned B = F == PER_EDGE ? W_PER_EDGE : F == ANCHORED ? W_ANCH : F == ANCHORED_LINK ? W_ANCH | W_LINKS : 0u;
+  WaveRow r{K, D, F};
+  r.solve = rtr_wave_kernel<K, D, B | W_THETA1>;
+  if constexpr ((B & W_ANCH) == 0) r.solve_theta = rtr_wave_kernel<K, D, B>;
+  if constexpr (F == COLUMN) r.solve_cg = rcg_wave_kernel<K, D>;
+  if constexpr ((MORE & W_SPREAD) != 0) r.solve_spread = rtr_wave_kernel<K, D, B | W_THETA1 | W_SPREAD>;
+  if constexpr ((B & W_ANCH) != 0) r.solve_scene = rtr_wave_scene_kernel<K, D, B | W_THETA1>;
+  r.kat = kat_wave_kernel<K, D, B>;
+  r.lds = WaveBuildCtx<K, D, B>::lds_bytes;
   return r;
 }
 // <3, 20> is compiled for anchored templates only: the free-free formulation with more than 10 terms at a node runs
@@ -116,10 +92,10 @@ static WaveRow anchored_link_row() {
 // tools/gpu_variants.py.  <3,10> 48 B: -1.3 % against <3,9>; <2,16> 168 B: 5x faster than the
 // workgroup kernels on the planar trees -- both stay)
 static const WaveRow kWaveRows[] = {
-    column_row<3, 9>(rtr_wave_kernel<3, 9, true, false, true>), per_edge_row<3, 9>(), anchored_row<3, 9>(),
-    column_row<3, 10>(), per_edge_row<3, 10>(),
-    anchored_row<3, 20>(),
-    column_row<2, 6>(), column_row<2, 16>(), column_row<2, 31>()};
+    wave_row<3, 9, COLUMN, W_SPREAD>(), wave_row<3, 9, PER_EDGE>(), wave_row<3, 9, ANCHORED>(), wave_row<3, 9, ANCHORED_LINK>(),
+    wave_row<3, 10, COLUMN>(), wave_row<3, 10, PER_EDGE>(),
+    wave_row<3, 20, ANCHORED>(),
+    wave_row<2, 6, COLUMN>(), wave_row<2, 16, COLUMN>(), wave_row<2, 31, COLUMN>()};
 
 // the row of (K, form) with the fewest slots that hold `slots` terms per node, or null
 static const WaveRow *find_row(int K, Form form, int slots) {
@@ -287,10 +263,24 @@ static void read_params(gik_template *t, const gik_template_desc *d) {
   if (const char *e = getenv("GIK_QUAD_MIN_BATCH")) t->f.quad_min_batch = std::max(0, atoi(e));
 }
 
+// A row's kernels on a template, by its solver and theta, with the LDS bytes of a launch.
+// occupancy: of the build large batches run -- the small-batch build trades registers for latency, gik_rtr.hip.h SPLIT.  (Per-edge
+// form: the tail-spreading build where there is one; every other form: always the theta == 1 build.  The grids were tuned on these.)
+static void install_row(gik_template *t, const WaveRow *r) {
+  const bool cg = t->solver == GIK_SOLVER_CONJUGATE_GRADIENT, theta1 = t->p.theta == 1.0;
+  gik_template::Kernels &kn = t->kernels;
+  kn.solve = cg ? r->solve_cg : (theta1 ? r->solve : r->solve_theta);
+  kn.solve_spread = (cg || !theta1) ? nullptr : r->solve_spread;
+  kn.solve_scene = r->solve_scene;
+  kn.kat = r->kat;
+  kn.occupancy = (const void *)(r->form == PER_EDGE ? (kn.solve_spread ? kn.solve_spread : kn.solve) : (cg ? r->solve_cg : r->solve));
+  t->smem_bytes = r->lds(t->T);
+}
+
 // The kernels this template launches, chosen once from path, solver, theta, anchored and Hessian form; with them
 // hess_per_edge and the LDS bytes of a launch.  `row`: the wavefront path's table row (column form or anchored).
 static int resolve_kernels(gik_template *t, const gik_template_desc *d, const WaveRow *row, size_t block_lds) {
-  const bool cg = d->solver == GIK_SOLVER_CONJUGATE_GRADIENT, k3 = d->k == 3, theta1 = d->theta == 1.0;
+  const bool cg = d->solver == GIK_SOLVER_CONJUGATE_GRADIENT, k3 = d->k == 3;
   gik_template::Kernels &kn = t->kernels;
   if (t->f.is_block) {
     kn.block_solve = cg ? (k3 ? rcg_block_kernel<3> : rcg_block_kernel<2>) : (k3 ? rtr_block_kernel<3> : rtr_block_kernel<2>);
@@ -309,15 +299,7 @@ static int resolve_kernels(gik_template *t, const gik_template_desc *d, const Wa
       return fail("hessian_form = GIK_HESS_PER_EDGE: wavefront kernel of 3-D free-free graphs, TrustRegions only");
     t->hess_per_edge = have;
   }
-  const WaveRow *r = t->hess_per_edge ? pe : row;
-  kn.solve = cg ? r->solve_cg : (theta1 ? r->solve : r->solve_theta);
-  kn.solve_spread = (cg || !theta1) ? nullptr : r->solve_spread;
-  kn.solve_scene = r->solve_scene;
-  kn.kat = r->kat;
-  // occupancy: of the build large batches run -- the small-batch build trades registers for latency, gik_rtr.hip.h SPLIT.  (Per-edge
-  // form: the tail-spreading build where there is one; column form: always the theta == 1 build.  The grids were tuned on these.)
-  kn.occupancy = (const void *)(t->hess_per_edge ? (kn.solve_spread ? kn.solve_spread : kn.solve) : (cg ? r->solve_cg : r->solve));
-  t->smem_bytes = r->lds(t->T);
+  install_row(t, t->hess_per_edge ? pe : row);
   return 0;
 }
 
@@ -582,7 +564,7 @@ int gik_template_create_anchored(const gik_template_desc *d, const gik_anchored_
   return create_impl(d, ad, out);
 }
 
-// the links of the link clearance; with hinges = 1 the template's kernels are resolved again (anchored_link_row)
+// the links of the link clearance; with hinges = 1 the template's kernels are resolved again (the ANCHORED_LINK row)
 int gik_anchored_attach_links(gik_template *anch, const gik_link_desc *d) {
   using namespace gik;
   const std::string e("gik_anchored_attach_links");
@@ -612,18 +594,14 @@ int gik_anchored_attach_links(gik_template *anch, const gik_link_desc *d) {
   anch->d_link_b = lb;
   anch->d_link_rho = lr;
   if (d->hinges) {
-    // the template's solve and known-answer kernels become the LINKS builds, with their LDS bytes and occupancy
-    static const WaveRow row = anchored_link_row();
+    // the template's solve and known-answer kernels become the link row's, with their LDS bytes and occupancy
+    const WaveRow *row = find_row(3, ANCHORED_LINK, 9);
     const AnchLinkRec *dr = upload(anch, recs.data(), recs.size(), ok);
     int occ = 0;
-    if (!ok || hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)row.solve, WAVE, row.lds(anch->T)) != hipSuccess)
+    if (!ok || hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)row->solve, WAVE, row->lds(anch->T)) != hipSuccess)
       return fail(e + ": device upload failed");
     anch->an.link_rec = dr;
-    anch->kernels.solve = row.solve;
-    anch->kernels.solve_scene = row.solve_scene;
-    anch->kernels.kat = row.kat;
-    anch->kernels.occupancy = (const void *)row.solve;
-    anch->smem_bytes = row.lds(anch->T);
+    install_row(anch, row);
     anch->f.waves_per_cu = std::max(1, std::min(occ, 32));
     anch->link_hinges = true;
   }

@@ -12,57 +12,56 @@
 #define GIK_INSTANTIATE(...) template __global__ __VA_ARGS__;
 #define GIK_EXTERN_TEMPLATE(...) extern template __global__ __VA_ARGS__;
 
-// one unknown per lane, k = 3: column-form product (+ ConjugateGradient, known answers, tail spreading)
+// one unknown per lane (rtr_wave_kernel<K, slots, flag word>, WaveBuild of gik_wave_kernels.hip.h), k = 3: column-form
+// product (+ ConjugateGradient, known answers, tail spreading)
 #define GIK_KERNELS_WAVE3(X)                                   \
-  X(void rtr_wave_kernel<3, 9, true>(SolveArgs))               \
-  X(void rtr_wave_kernel<3, 9, false>(SolveArgs))              \
-  X(void rtr_wave_kernel<3, 9, true, false, true>(SolveArgs))  \
+  X(void rtr_wave_kernel<3, 9, W_THETA1>(SolveArgs))           \
+  X(void rtr_wave_kernel<3, 9, 0>(SolveArgs))                  \
+  X(void rtr_wave_kernel<3, 9, W_THETA1 | W_SPREAD>(SolveArgs)) \
   X(void rcg_wave_kernel<3, 9>(SolveArgs))                     \
   X(void kat_wave_kernel<3, 9>(KatArgs))                       \
-  X(void rtr_wave_kernel<3, 10, true>(SolveArgs))              \
-  X(void rtr_wave_kernel<3, 10, false>(SolveArgs))             \
+  X(void rtr_wave_kernel<3, 10, W_THETA1>(SolveArgs))          \
+  X(void rtr_wave_kernel<3, 10, 0>(SolveArgs))                 \
   X(void rcg_wave_kernel<3, 10>(SolveArgs))                    \
   X(void kat_wave_kernel<3, 10>(KatArgs))
 // ... per-edge product form (gik_wave_strict.hip.h)
-#define GIK_KERNELS_WAVE3_STRICT(X)                                  \
-  X(void rtr_wave_kernel<3, 9, true, false, false, true>(SolveArgs)) \
-  X(void rtr_wave_kernel<3, 9, true, false, true, true>(SolveArgs))  \
-  X(void rtr_wave_kernel<3, 9, false, false, false, true>(SolveArgs)) \
-  X(void kat_wave_kernel<3, 9, false, true>(KatArgs))                \
-  X(void rtr_wave_kernel<3, 10, true, false, false, true>(SolveArgs)) \
-  X(void rtr_wave_kernel<3, 10, true, false, true, true>(SolveArgs)) \
-  X(void rtr_wave_kernel<3, 10, false, false, false, true>(SolveArgs)) \
-  X(void kat_wave_kernel<3, 10, false, true>(KatArgs))
+#define GIK_KERNELS_WAVE3_STRICT(X)                                         \
+  X(void rtr_wave_kernel<3, 9, W_THETA1 | W_PER_EDGE>(SolveArgs))           \
+  X(void rtr_wave_kernel<3, 9, W_THETA1 | W_SPREAD | W_PER_EDGE>(SolveArgs)) \
+  X(void rtr_wave_kernel<3, 9, W_PER_EDGE>(SolveArgs))                      \
+  X(void kat_wave_kernel<3, 9, W_PER_EDGE>(KatArgs))                        \
+  X(void rtr_wave_kernel<3, 10, W_THETA1 | W_PER_EDGE>(SolveArgs))          \
+  X(void rtr_wave_kernel<3, 10, W_THETA1 | W_SPREAD | W_PER_EDGE>(SolveArgs)) \
+  X(void rtr_wave_kernel<3, 10, W_PER_EDGE>(SolveArgs))                     \
+  X(void kat_wave_kernel<3, 10, W_PER_EDGE>(KatArgs))
 // ... fixed-anchor formulation
-#define GIK_KERNELS_ANCH(X)                             \
-  X(void rtr_wave_kernel<3, 9, true, true>(SolveArgs))  \
-  X(void kat_wave_kernel<3, 9, true>(KatArgs))          \
-  X(void rtr_wave_kernel<3, 20, true, true>(SolveArgs)) \
-  X(void kat_wave_kernel<3, 20, true>(KatArgs))
-// ... with link hinges (gik_anchored_attach_links, hinges = 1).  Beside GIK_ALL_KERNELS, not inside it: gik_host.hip
-// expands this group on its own
-#define GIK_KERNELS_ANCH_LINK(X)                                          \
-  X(void rtr_wave_kernel<3, 9, true, true, false, false, true>(SolveArgs)) \
-  X(void kat_wave_kernel<3, 9, true, false, true>(KatArgs))
-// ... with per-goal obstacle scenes (gik_solve_batch_scenes): the scene builds of the three solve kernels above, <slots,
-// link hinges>.  Beside GIK_ALL_KERNELS like the link group
-#define GIK_KERNELS_ANCH_SCENE(X)                                 \
-  X(void rtr_wave_scene_kernel<9, false>(SolveArgs, SceneArgs))   \
-  X(void rtr_wave_scene_kernel<20, false>(SolveArgs, SceneArgs))  \
-  X(void rtr_wave_scene_kernel<9, true>(SolveArgs, SceneArgs))
+#define GIK_KERNELS_ANCH(X)                                    \
+  X(void rtr_wave_kernel<3, 9, W_THETA1 | W_ANCH>(SolveArgs))  \
+  X(void kat_wave_kernel<3, 9, W_ANCH>(KatArgs))               \
+  X(void rtr_wave_kernel<3, 20, W_THETA1 | W_ANCH>(SolveArgs)) \
+  X(void kat_wave_kernel<3, 20, W_ANCH>(KatArgs))
+// ... with link hinges (gik_anchored_attach_links, hinges = 1)
+#define GIK_KERNELS_ANCH_LINK(X)                                        \
+  X(void rtr_wave_kernel<3, 9, W_THETA1 | W_ANCH | W_LINKS>(SolveArgs)) \
+  X(void kat_wave_kernel<3, 9, W_ANCH | W_LINKS>(KatArgs))
+// ... with per-goal obstacle scenes (gik_solve_batch_scenes): the scene builds of the three solve kernels above
+#define GIK_KERNELS_ANCH_SCENE(X)                                                        \
+  X(void rtr_wave_scene_kernel<3, 9, W_THETA1 | W_ANCH>(SolveArgs, SceneArgs))           \
+  X(void rtr_wave_scene_kernel<3, 20, W_THETA1 | W_ANCH>(SolveArgs, SceneArgs))          \
+  X(void rtr_wave_scene_kernel<3, 9, W_THETA1 | W_ANCH | W_LINKS>(SolveArgs, SceneArgs))
 // one unknown per lane, k = 2
-#define GIK_KERNELS_WAVE2(X)                       \
-  X(void rtr_wave_kernel<2, 6, true>(SolveArgs))   \
-  X(void rtr_wave_kernel<2, 6, false>(SolveArgs))  \
-  X(void rcg_wave_kernel<2, 6>(SolveArgs))         \
-  X(void kat_wave_kernel<2, 6>(KatArgs))           \
-  X(void rtr_wave_kernel<2, 16, true>(SolveArgs))  \
-  X(void rtr_wave_kernel<2, 16, false>(SolveArgs)) \
-  X(void rcg_wave_kernel<2, 16>(SolveArgs))        \
-  X(void kat_wave_kernel<2, 16>(KatArgs))          \
-  X(void rtr_wave_kernel<2, 31, true>(SolveArgs))  \
-  X(void rtr_wave_kernel<2, 31, false>(SolveArgs)) \
-  X(void rcg_wave_kernel<2, 31>(SolveArgs))        \
+#define GIK_KERNELS_WAVE2(X)                          \
+  X(void rtr_wave_kernel<2, 6, W_THETA1>(SolveArgs))  \
+  X(void rtr_wave_kernel<2, 6, 0>(SolveArgs))         \
+  X(void rcg_wave_kernel<2, 6>(SolveArgs))            \
+  X(void kat_wave_kernel<2, 6>(KatArgs))              \
+  X(void rtr_wave_kernel<2, 16, W_THETA1>(SolveArgs)) \
+  X(void rtr_wave_kernel<2, 16, 0>(SolveArgs))        \
+  X(void rcg_wave_kernel<2, 16>(SolveArgs))           \
+  X(void kat_wave_kernel<2, 16>(KatArgs))             \
+  X(void rtr_wave_kernel<2, 31, W_THETA1>(SolveArgs)) \
+  X(void rtr_wave_kernel<2, 31, 0>(SolveArgs))        \
+  X(void rcg_wave_kernel<2, 31>(SolveArgs))           \
   X(void kat_wave_kernel<2, 31>(KatArgs))
 // workgroup per problem
 #define GIK_KERNELS_BLOCK(X)                    \
@@ -99,6 +98,6 @@
   X(void prep_block_kernel<false>(PrepArgs, double *)) \
   X(void prep_block_kernel<false, PREP_BIGN>(PrepArgs, double *))
 
-#define GIK_ALL_KERNELS(X)                                                                             \
-  GIK_KERNELS_WAVE3(X) GIK_KERNELS_WAVE3_STRICT(X) GIK_KERNELS_ANCH(X) GIK_KERNELS_WAVE2(X) GIK_KERNELS_BLOCK(X) \
-  GIK_KERNELS_NPT(X) GIK_KERNELS_NPT4(X) GIK_KERNELS_QUAD(X) GIK_KERNELS_PREP(X)
+#define GIK_ALL_KERNELS(X)                                                                                      \
+  GIK_KERNELS_WAVE3(X) GIK_KERNELS_WAVE3_STRICT(X) GIK_KERNELS_ANCH(X) GIK_KERNELS_ANCH_LINK(X) GIK_KERNELS_ANCH_SCENE(X) \
+  GIK_KERNELS_WAVE2(X) GIK_KERNELS_BLOCK(X) GIK_KERNELS_NPT(X) GIK_KERNELS_NPT4(X) GIK_KERNELS_QUAD(X) GIK_KERNELS_PREP(X)

@@ -50,6 +50,31 @@ __device__ inline RtrResume load_slice_state(const SliceState *st) {
   rs.resumed = 1;
   return rs;
 }
+// ... what a paused problem leaves there (resumes: counting this pause), and what a finished one reports
+__device__ __forceinline__ SliceState slice_state_of(const RtrOut &ro, int resumes) {
+  SliceState st;
+  st.Delta = ro.Delta;
+  st.kiter = ro.iterations;
+  st.inner_total = ro.inner_total;
+  st.inner_exec = ro.inner_executed;
+  st.n_accept = ro.n_accept;
+  st.resumes = resumes;
+  st.pad = 0;
+  return st;
+}
+__device__ __forceinline__ gik_stats stats_of(const RtrOut &ro, int flags) {
+  gik_stats s;
+  s.f = ro.f;
+  s.gradnorm = ro.gradnorm;
+  s.iterations = ro.iterations;
+  s.inner_total = ro.inner_total;
+  s.stop = ro.stop;
+  s.n_accept = ro.n_accept;
+  s.inner_executed = ro.inner_executed;
+  s.flags = flags;
+  s.stepsize = ro.Delta;
+  return s;
+}
 
 // publish a paused problem (one thread; the state stores of all threads must be complete and
 // fenced before the call)

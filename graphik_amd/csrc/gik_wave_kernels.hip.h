@@ -54,10 +54,22 @@ __device__ inline void stage_lds(double *tiles, uint32_t *meta, const uint32_t *
 // XCDs idle behind a few stragglers; the queue keeps every SIMD busy until the end.
 // (the fixed-anchor variant holds 34 KB of LDS per wave: four waves per CU, one per SIMD, so it may
 // as well have that SIMD's whole register file -- at two waves per SIMD it spilled into the hot loop)
-// STRICT: the Hessian product term by term as costs.py:186-203 forms it (gik_wave_strict.hip.h;
-// gik_template_desc.hessian_form = GIK_HESS_PER_EDGE), k = 3 free-free graphs
-// LINKS: link hinges in the fixed-anchor solve (WaveCtx<.., LINKS>, gik_anchored_attach_links with hinges = 1).
-// SCENES: per-goal obstacle scenes in the fixed-anchor solve (gik_solve_batch_scenes).  The scene set is a second kernel
+// A build is named by one flag word (rtr_wave_kernel<K, SLOTS, BUILD>, kat_wave_kernel<K, SLOTS, BUILD>):
+enum WaveBuild : unsigned {
+  W_THETA1 = 1,    // theta == 1, the reference default (without it: any theta)
+  W_ANCH = 2,      // the fixed-anchor formulation, k = 3
+  W_SPREAD = 4,    // tail spreading (MigCtl): two waves per SIMD, i.e. not the anchored builds
+  // the Hessian product term by term as costs.py:186-203 forms it (gik_wave_strict.hip.h;
+  // gik_template_desc.hessian_form = GIK_HESS_PER_EDGE), k = 3 free-free graphs
+  W_PER_EDGE = 8,
+  W_LINKS = 16,    // link hinges in the fixed-anchor solve (WaveCtx<.., LINKS>, gik_anchored_attach_links with hinges = 1)
+};
+// the context a build runs on
+template <int K, int MAXDEG, unsigned BUILD>
+using WaveBuildCtx = std::conditional_t<(BUILD & W_PER_EDGE) != 0, WaveCtxStrict<MAXDEG>,
+                                        WaveCtx<K, MAXDEG, (BUILD & W_ANCH) != 0, false, (BUILD & W_LINKS) != 0>>;
+// SCENES is not a bit but an entry point, rtr_wave_scene_kernel: per-goal obstacle scenes in the fixed-anchor solve
+// (gik_solve_batch_scenes).  The scene set is a second kernel
 // argument (SceneArgs, gik_scenes.h; SolveArgs and with it every other kernel stay as they are): a.an.obs is then the
 // caller's [n_scene][stride][4] array and a.an.n_obs is not read; problem b walks the first n_obs[s] rows of scene
 // s = scene_id[b] (null: scene 0), and the obstacle table in LDS is restaged whenever a claimed problem's scene differs
@@ -65,14 +77,16 @@ __device__ inline void stage_lds(double *tiles, uint32_t *meta, const uint32_t *
 // time-sliced and reset their near lists per problem anyway, and the near lists are exact, so a problem's bits are those
 // of a template created with its scene's spheres, whatever the wave staged before.
 // The kernel's text is this function; rtr_wave_kernel and rtr_wave_scene_kernel below are its entry points.
-template <int K, int MAXDEG, bool THETA_ONE, bool ANCH, bool MIG, bool STRICT, bool LINKS, bool SCENES = false>
+template <int K, int MAXDEG, unsigned BUILD, bool SCENES = false>
 __device__ __forceinline__ void rtr_wave_run(const SolveArgs &a, const SceneArgs &sc = SceneArgs()) {
+  constexpr bool THETA_ONE = BUILD & W_THETA1, ANCH = BUILD & W_ANCH, MIG = BUILD & W_SPREAD, STRICT = BUILD & W_PER_EDGE,
+                 LINKS = BUILD & W_LINKS;
   static_assert(!SCENES || ANCH, "scenes: the fixed-anchor kernels");
   static_assert(!LINKS || (ANCH && MAXDEG == 9), "link hinges: the 9-slot fixed-anchor kernel");
   static_assert(!ANCH || K == 3, "the fixed-anchor formulation is 3-D");
   static_assert(!MIG || !ANCH, "tail spreading: two waves per SIMD, i.e. not the anchored variant");
   static_assert(!STRICT || (K == 3 && !ANCH), "the per-edge product form: 3-D free-free graphs");
-  using Ctx = std::conditional_t<STRICT, WaveCtxStrict<MAXDEG>, WaveCtx<K, MAXDEG, ANCH, false, LINKS>>;
+  using Ctx = WaveBuildCtx<K, MAXDEG, BUILD>;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int lane = threadIdx.x;
   const int NK = a.N * K;
@@ -233,15 +247,7 @@ __device__ __forceinline__ void rtr_wave_run(const SolveArgs &a, const SceneArgs
       if (cx.active) a.Y_out[(size_t)b * NK + lane] = x;
       if (UNI(ro.paused)) {
         if (lane == 0) {
-          SliceState st;
-          st.Delta = ro.Delta;
-          st.kiter = ro.iterations;
-          st.inner_total = ro.inner_total;
-          st.inner_exec = ro.inner_executed;
-          st.n_accept = ro.n_accept;
-          st.resumes = rs.resumes + 1;
-          st.pad = 0;
-          a.q_state[b] = st;
+          a.q_state[b] = slice_state_of(ro, rs.resumes + 1);
         }
         __threadfence();
 #ifdef GIK_DEV
@@ -268,17 +274,7 @@ __device__ __forceinline__ void rtr_wave_run(const SolveArgs &a, const SceneArgs
       if (cx.active) a.Y_out[(size_t)b * NK + lane] = x;
     }
     if (lane == 0) {
-      gik_stats s;
-      s.f = ro.f;
-      s.gradnorm = ro.gradnorm;
-      s.iterations = ro.iterations;
-      s.inner_total = ro.inner_total;
-      s.stop = ro.stop;
-      s.n_accept = ro.n_accept;
-      s.inner_executed = ro.inner_executed;
-      s.flags = (MIG && resumed) ? (2 | (rs_resumes << 8)) : 0;
-      s.stepsize = ro.Delta;
-      a.stats[b] = s;
+      a.stats[b] = stats_of(ro, (MIG && resumed) ? (2 | (rs_resumes << 8)) : 0);
 #ifdef GIK_DEV
       if (MIG && (a.dbg & 4096) && a.dbg_buf) dev_log(a.dbg_buf, 4, b);
 #endif
@@ -297,23 +293,14 @@ __device__ __forceinline__ void rtr_wave_run(const SolveArgs &a, const SceneArgs
   }
 #endif
 }
-// Two templates of one name.  The six-parameter one is every kernel without link hinges, under the symbol names it has
-// always had (tools and tests find kernels in the code object by them); LINKS is the seventh parameter of an overload of
-// its own, so rtr_wave_kernel<3, 9, true, true, false, false, true> names the link build and nothing else moves.
-template <int K, int MAXDEG, bool THETA_ONE, bool ANCH = false, bool MIG = false, bool STRICT = false>
-__global__ void __launch_bounds__(WAVE, ANCH ? 1 : 2) rtr_wave_kernel(SolveArgs a) {
-  rtr_wave_run<K, MAXDEG, THETA_ONE, ANCH, MIG, STRICT, false>(a);
+template <int K, int MAXDEG, unsigned BUILD>
+__global__ void __launch_bounds__(WAVE, (BUILD & W_ANCH) ? 1 : 2) rtr_wave_kernel(SolveArgs a) {
+  rtr_wave_run<K, MAXDEG, BUILD>(a);
 }
-template <int K, int MAXDEG, bool THETA_ONE, bool ANCH, bool MIG, bool STRICT, bool LINKS>
-__global__ void __launch_bounds__(WAVE, ANCH ? 1 : 2) rtr_wave_kernel(SolveArgs a) {
-  static_assert(LINKS, "the seven-parameter form is the link build; every other kernel is rtr_wave_kernel<K, MAXDEG, THETA_ONE, ...>");
-  rtr_wave_run<K, MAXDEG, THETA_ONE, ANCH, MIG, STRICT, LINKS>(a);
-}
-// The scene builds of the three fixed-anchor solve kernels (9 slots, 20 slots, 9 slots with link hinges), under a name of
-// their own: the templates above keep their parameter lists and their symbols.
-template <int MAXDEG, bool LINKS>
+// the scene builds of the three fixed-anchor solve kernels (9 slots, 20 slots, 9 slots with link hinges)
+template <int K, int MAXDEG, unsigned BUILD>
 __global__ void __launch_bounds__(WAVE, 1) rtr_wave_scene_kernel(SolveArgs a, SceneArgs sc) {
-  rtr_wave_run<3, MAXDEG, true, true, false, false, LINKS, true>(a, sc);
+  rtr_wave_run<K, MAXDEG, BUILD, true>(a, sc);
 }
 
 // Riemannian conjugate gradients (the reference's alternative solver), same persistent scheme
@@ -353,24 +340,16 @@ __global__ void __launch_bounds__(WAVE, 2) rcg_wave_kernel(SolveArgs a) {
     rcg_solve_one<K>(cx, a.cg, a.trace, a.has_trace, b, x, ro);
     if (cx.active) a.Y_out[(size_t)b * NK + lane] = x;
     if (lane == 0) {
-      gik_stats s;
-      s.f = ro.f;
-      s.gradnorm = ro.gradnorm;
-      s.iterations = ro.iterations;
-      s.inner_total = ro.inner_total;
-      s.stop = ro.stop;
-      s.n_accept = ro.n_accept;
-      s.inner_executed = ro.inner_executed;
-      s.flags = 0;
-      s.stepsize = ro.Delta;
-      a.stats[b] = s;
+      a.stats[b] = stats_of(ro, 0);
     }
   }
 }
 
-template <int K, int MAXDEG, bool ANCH = false, bool STRICT = false, bool LINKS = false>
+template <int K, int MAXDEG, unsigned BUILD = 0>
 __global__ void __launch_bounds__(WAVE) kat_wave_kernel(KatArgs a) {
-  using Ctx = std::conditional_t<STRICT, WaveCtxStrict<MAXDEG>, WaveCtx<K, MAXDEG, ANCH, false, LINKS>>;
+  static_assert(!(BUILD & ~(W_ANCH | W_PER_EDGE | W_LINKS)), "known answers: the anchored, per-edge and link builds");
+  constexpr bool ANCH = BUILD & W_ANCH, LINKS = BUILD & W_LINKS;
+  using Ctx = WaveBuildCtx<K, MAXDEG, BUILD>;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int lane = threadIdx.x;
   const int b = blockIdx.x;

@@ -1,5 +1,5 @@
 """Seeded synthetic fixed-anchor problems at the compiled limits of the anchored wavefront kernels
-(rtr_wave_kernel<3, 9 | 20, true, true>, kat_wave_kernel<3, 9 | 20, true>): 21 free nodes, 16 anchor rows, 8 pinned
+(rtr_wave_kernel<3, 9 | 20, W_THETA1 | W_ANCH>, kat_wave_kernel<3, 9 | 20, W_ANCH>): 21 free nodes, 16 anchor rows, 8 pinned
 terms at a node, 128 obstacles, 8 / 9 spheres on a near list, and the shapes gik_template_create_anchored refuses.
 
 Plain module (numpy only at import), the anchored sibling of tests/synth_graphs.py: tests/test_anchored_limits_host.py
@@ -33,11 +33,11 @@ FAR_CLEAR = 0.09                # ... and of every other sphere at the nodes who
 
 
 def _solve9():
-    return ["rtr_wave_kernel<3,9,true,true>", "kat_wave_kernel<3,9,true>"]
+    return ["rtr_wave_kernel<3,9,W_THETA1|W_ANCH>", "kat_wave_kernel<3,9,W_ANCH>"]
 
 
 def _solve20():
-    return ["rtr_wave_kernel<3,20,true,true>", "kat_wave_kernel<3,20,true>"]
+    return ["rtr_wave_kernel<3,20,W_THETA1|W_ANCH>", "kat_wave_kernel<3,20,W_ANCH>"]
 
 
 # id -> shape.  N free nodes, `busiest` free-free terms at the hub, n_anchor rows of which the last n_goal are per-goal,

@@ -187,11 +187,11 @@ def _info(kind, **kw):
 
 
 def _strict(D):
-    return [f"rtr_wave_kernel<3,{D},true,false,false,true>", f"kat_wave_kernel<3,{D},false,true>"]
+    return [f"rtr_wave_kernel<3,{D},W_THETA1|W_PER_EDGE>", f"kat_wave_kernel<3,{D},W_PER_EDGE>"]
 
 
 def _column(D):
-    return [f"rtr_wave_kernel<3,{D},true>", f"kat_wave_kernel<3,{D}>"]
+    return [f"rtr_wave_kernel<3,{D},W_THETA1>", f"kat_wave_kernel<3,{D}>"]
 
 
 CASES = {}
@@ -213,10 +213,10 @@ for D in (9, 10):
           params={"solver": "ConjugateGradient"}, counts=dict(busiest=D))
     for th, ka, tag in ((0.5, 0.2, "theta05"), (2.0, 0.5, "theta2")):
         _case(f"w3_d{D}_{tag}", 3, 21, dict(busiest=D, seed=3), _info("wave3", **mt),
-              [f"rtr_wave_kernel<3,{D},false,false,false,true>", f"kat_wave_kernel<3,{D},false,true>"],
+              [f"rtr_wave_kernel<3,{D},W_PER_EDGE>", f"kat_wave_kernel<3,{D},W_PER_EDGE>"],
               params={"theta": th, "kappa": ka}, counts=dict(busiest=D))
         _case(f"w3_d{D}_column_{tag}", 3, 21, dict(busiest=D, seed=3), _info("wave3c", **mt),
-              [f"rtr_wave_kernel<3,{D},false>", f"kat_wave_kernel<3,{D}>"],
+              [f"rtr_wave_kernel<3,{D},0>", f"kat_wave_kernel<3,{D}>"],
               params={"theta": th, "kappa": ka, "hessian_form": "column"}, counts=dict(busiest=D))
 _case("w3_n21_d9_scaled", 3, 21, dict(busiest=9, scaled=True, seed=5), _info("wave3", max_terms_per_node=9), _strict(9),
       counts=dict(busiest=9))
@@ -269,40 +269,40 @@ _case("npt_force1", 3, 100, dict(_NPL, outside=64), _info("block", n_clique=40),
 # k = 2: N * k <= 64 and N <= 32; slot counts 6 / 16 / 31 (32: the workgroup kernels); the four-problem kernel up to 16 nodes
 for D, slots, N in ((6, 6, 17), (7, 16, 24), (16, 16, 24), (17, 31, 32), (31, 31, 32)):
     _case(f"w2_d{D}", 2, N, dict(busiest=D), _info("wave2", max_terms_per_node=slots),
-          [f"rtr_wave_kernel<2,{slots},true>", f"kat_wave_kernel<2,{slots}>"], counts=dict(busiest=D))
+          [f"rtr_wave_kernel<2,{slots},W_THETA1>", f"kat_wave_kernel<2,{slots}>"], counts=dict(busiest=D))
 _case("w2_d32", 2, 32, dict(busiest=32), _info("block"), ["rtr_block_kernel<2>", "kat_block_kernel<2>"], counts=dict(busiest=32))
-_case("w2_n32", 2, 32, dict(busiest=6), _info("wave2", max_terms_per_node=6), ["rtr_wave_kernel<2,6,true>", "kat_wave_kernel<2,6>"],
+_case("w2_n32", 2, 32, dict(busiest=6), _info("wave2", max_terms_per_node=6), ["rtr_wave_kernel<2,6,W_THETA1>", "kat_wave_kernel<2,6>"],
       counts=dict(busiest=6))
 _case("w2_n33", 2, 33, dict(busiest=6), _info("block"), ["rtr_block_kernel<2>", "kat_block_kernel<2>"], counts=dict(busiest=6))
 _case("w2_n33_cg", 2, 33, dict(busiest=6), _info("block"), ["rcg_block_kernel<2>", "kat_block_kernel<2>"],
       params={"solver": "ConjugateGradient"}, counts=dict(busiest=6))
 _case("w2_n16_quad", 2, 16, dict(busiest=6), _info("quad", max_terms_per_node=6), ["rtr_quad_kernel<6>", "kat_quad_kernel<6>"],
       params={"debug_flags": 16384}, counts=dict(busiest=6))
-_case("w2_n16_wave", 2, 16, dict(busiest=6), _info("wave2", max_terms_per_node=6), ["rtr_wave_kernel<2,6,true>", "kat_wave_kernel<2,6>"],
+_case("w2_n16_wave", 2, 16, dict(busiest=6), _info("wave2", max_terms_per_node=6), ["rtr_wave_kernel<2,6,W_THETA1>", "kat_wave_kernel<2,6>"],
       params={"debug_flags": 8192}, counts=dict(busiest=6))
 _case("w2_d16_scaled", 2, 24, dict(busiest=16, scaled=True, seed=5), _info("wave2", max_terms_per_node=16),
-      ["rtr_wave_kernel<2,16,true>", "kat_wave_kernel<2,16>"], counts=dict(busiest=16))
+      ["rtr_wave_kernel<2,16,W_THETA1>", "kat_wave_kernel<2,16>"], counts=dict(busiest=16))
 for D, N in ((6, 17), (16, 24), (31, 32)):
     mt = dict(max_terms_per_node=D)
     _case(f"w2_d{D}_cg", 2, N, dict(busiest=D), _info("wave2", **mt), [f"rcg_wave_kernel<2,{D}>", f"kat_wave_kernel<2,{D}>"],
           params={"solver": "ConjugateGradient"}, counts=dict(busiest=D))
     for th, ka, tag in ((0.5, 0.2, "theta05"), (2.0, 0.5, "theta2")):
         _case(f"w2_d{D}_{tag}", 2, N, dict(busiest=D, seed=3), _info("wave2", **mt),
-              [f"rtr_wave_kernel<2,{D},false>", f"kat_wave_kernel<2,{D}>"], params={"theta": th, "kappa": ka},
+              [f"rtr_wave_kernel<2,{D},0>", f"kat_wave_kernel<2,{D}>"], params={"theta": th, "kappa": ka},
               counts=dict(busiest=D))
 
 # ragged batches, every sampled problem against itself alone.  Tail spreading (the *_mig builds): more problems than
 # resident waves at more than four waves per CU -- waves_per_cu = 8, B = 8 * n_cu + 37; debug_flags 512 turns it off.
 # The four-problem kernel: below / above its batch-size switch (12 problems per CU).
 BATCH_CASES = {
-    "mig_d9": dict(graph="w3_n21_d9", params={}, reaches=["rtr_wave_kernel<3,9,true,false,true,true>"], mig=True),
+    "mig_d9": dict(graph="w3_n21_d9", params={}, reaches=["rtr_wave_kernel<3,9,W_THETA1|W_SPREAD|W_PER_EDGE>"], mig=True),
     "mig_d9_column": dict(graph="w3_n21_d9_column", params={"hessian_form": "column"},
-                          reaches=["rtr_wave_kernel<3,9,true,false,true>"], mig=True),
-    "mig_d10": dict(graph="w3_n21_d10", params={}, reaches=["rtr_wave_kernel<3,10,true,false,true,true>"], mig=True),
+                          reaches=["rtr_wave_kernel<3,9,W_THETA1|W_SPREAD>"], mig=True),
+    "mig_d10": dict(graph="w3_n21_d10", params={}, reaches=["rtr_wave_kernel<3,10,W_THETA1|W_SPREAD|W_PER_EDGE>"], mig=True),
     # (<3, 10> has no column-form tail-spreading build: the same batch runs on the plain one, nothing moves)
     "mig_d10_column": dict(graph="w3_n21_d10_column", params={"hessian_form": "column"}, reaches=_column(10)[:1], mig=False),
     "mig_d10_off": dict(graph="w3_n21_d10", params={"debug_flags": 512}, reaches=_strict(10)[:1], mig=False),
-    "quad_below": dict(graph="w2_n16_quad", params={}, reaches=["rtr_wave_kernel<2,6,true>"], quad=-1),
+    "quad_below": dict(graph="w2_n16_quad", params={}, reaches=["rtr_wave_kernel<2,6,W_THETA1>"], quad=-1),
     "quad_above": dict(graph="w2_n16_quad", params={}, reaches=["rtr_quad_kernel<6>"], quad=3),
 }
 
@@ -329,9 +329,20 @@ REFUSED = {
 
 # instantiations that the existing suite reaches (anchored formulation, prepare kernels): named, not re-tested
 EXISTING = {
-    "rtr_wave_kernel<3,9,true,true>": ["tests/test_hip_gpu.py::test_anchored_trajectory_against_oracle",
-                                       "tests/test_hip_gpu.py::test_anchored_pipeline"],
-    "kat_wave_kernel<3,9,true>": ["tests/test_hip_gpu.py::test_anchored_kernel_known_answers"],
+    "rtr_wave_kernel<3,9,W_THETA1|W_ANCH>": ["tests/test_hip_gpu.py::test_anchored_trajectory_against_oracle",
+                                             "tests/test_hip_gpu.py::test_anchored_pipeline"],
+    "kat_wave_kernel<3,9,W_ANCH>": ["tests/test_hip_gpu.py::test_anchored_kernel_known_answers"],
+    # ... with link hinges (UR10 + table, AnchoredProblem(link_hinges=True))
+    "rtr_wave_kernel<3,9,W_THETA1|W_ANCH|W_LINKS>": ["tests/test_anchored_link_hinges_gpu.py::test_the_blind_spot_closes",
+                                                     "tests/test_anchored_link_hinges_gpu.py::test_the_new_kernel_group_is_what_the_hinge_template_runs"],
+    "kat_wave_kernel<3,9,W_ANCH|W_LINKS>": ["tests/test_anchored_link_hinges_gpu.py::test_link_hinge_known_answers"],
+    # ... the scene entries: the synthetic cases near9 / a20_full of tests/synth_anchored_scenes.py (9 and 20 slots, asserted
+    # there through info), and UR10 with hinges
+    "rtr_wave_scene_kernel<3,9,W_THETA1|W_ANCH>": ["tests/test_anchored_scenes_gpu.py::test_template_level_bit_identity",
+                                                   "tests/test_anchored_scenes_gpu.py::test_a_wave_changes_scene_between_problems"],
+    "rtr_wave_scene_kernel<3,20,W_THETA1|W_ANCH>": ["tests/test_anchored_scenes_gpu.py::test_template_level_bit_identity",
+                                                    "tests/test_anchored_scenes_gpu.py::test_a_wave_changes_scene_between_problems"],
+    "rtr_wave_scene_kernel<3,9,W_THETA1|W_ANCH|W_LINKS>": ["tests/test_anchored_scenes_gpu.py::test_ur10_three_scenes"],
     "prep_block_kernel<true>": ["tests/test_hip_gpu.py::test_block_prepare_kernel_equals_wave_kernel"],
     "prep_block_kernel<false>": ["tests/test_hip_gpu.py::test_block_prepare_kernel_equals_wave_kernel"],
     "prep_block_kernel<false,PREP_BIGN>": ["tests/test_hip_gpu.py::test_scene_with_200_spheres_beyond_128_nodes"],
@@ -365,7 +376,7 @@ def coverage():
 
 def compiled_instances(text=None):
     """The instantiations GIK_ALL_KERNELS expands to (gik_instances.h), without blanks:
-    'rtr_wave_kernel<3,9,true>' etc."""
+    'rtr_wave_kernel<3,9,W_THETA1>' etc."""
     if text is None:
         with open(INSTANCES_H) as f:
             text = f.read()

@@ -1,7 +1,7 @@
 """The fixed-anchor wavefront kernels at every compiled limit on the MI355X, template-level calls only (Template.cost /
 grad / hess / cost_and_grad / solve on the synthetic problems of tests/synth_anchored.py, batches of 8): which kernel ran,
 known answers against the plain numpy reference, the solve against its CPU twin, near lists against the full walk bit for
-bit, and the refused shapes.  The 20-slot build (rtr_wave_kernel<3, 20, true, true>, kat_wave_kernel<3, 20, true>) runs in
+bit, and the refused shapes.  The 20-slot build (rtr_wave_kernel<3, 20, W_THETA1 | W_ANCH>, kat_wave_kernel<3, 20, W_ANCH>) runs in
 the cases a10 and a20_full.  Every condition on the inputs is a test of tests/test_anchored_limits_host.py."""
 import functools
 
@@ -42,8 +42,8 @@ def test_which_kernel_ran(torch_cuda, cid):
     info = _template(cid).info
     assert info["max_terms_per_node"] == sa.CASES[cid]["slots"], info
     assert info["anchored"] == 1 and not info["is_block"], info
-    assert sa.CASES[cid]["reaches"] == [f"rtr_wave_kernel<3,{info['max_terms_per_node']},true,true>",
-                                        f"kat_wave_kernel<3,{info['max_terms_per_node']},true>"]
+    assert sa.CASES[cid]["reaches"] == [f"rtr_wave_kernel<3,{info['max_terms_per_node']},W_THETA1|W_ANCH>",
+                                        f"kat_wave_kernel<3,{info['max_terms_per_node']},W_ANCH>"]
 
 
 # ---- 2. known answers ----------------------------------------------------------------------------------------------

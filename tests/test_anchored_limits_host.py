@@ -362,7 +362,7 @@ def test_twin_converges_from_every_start_point(cid):
 # ---- 5. coverage -------------------------------------------------------------------------------------------------------
 def test_the_case_table_covers_the_anchored_kernels():
     cov = sg.coverage()
-    assert not any("ANCH" in k or re.search(r"wave_kernel<3,\d+,true,true>|kat_wave_kernel<3,\d+,true>", k) for k in sg.OUT_OF_SCOPE)
+    assert not any("ANCH" in k or re.search(r"wave_kernel<3,\d+,[^>]*W_ANCH", k) for k in sg.OUT_OF_SCOPE)
     assert all(why for why in sg.OUT_OF_SCOPE.values())
     with open(sg.INSTANCES_H) as f:
         text = f.read()
@@ -374,5 +374,7 @@ def test_the_case_table_covers_the_anchored_kernels():
         assert by_case, inst
         slots = int(inst.split(",")[1])
         assert all(sa.CASES[c.split(":")[1]]["slots"] == slots for c in by_case)
-    # the link-hinge group stays beside the table
-    assert not any(inst in cov for inst in ("rtr_wave_kernel<3,9,true,true,false,false,true>", "kat_wave_kernel<3,9,true,false,true>"))
+    # the link-hinge group is in the table and covered
+    compiled = sg.compiled_instances()
+    for inst in ("rtr_wave_kernel<3,9,W_THETA1|W_ANCH|W_LINKS>", "kat_wave_kernel<3,9,W_ANCH|W_LINKS>"):
+        assert compiled.count(inst) == 1 and cov.get(inst), inst

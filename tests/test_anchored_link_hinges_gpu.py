@@ -292,7 +292,8 @@ def test_refusals_of_attach_with_hinges(torch_cuda):
 
 # ---- 8. the compiled kernels of the new group are the ones that ran ------------------------------------------------
 def test_the_new_kernel_group_is_what_the_hinge_template_runs(torch_cuda):
-    """GIK_KERNELS_ANCH_LINK (gik_instances.h) holds two instantiations, the solve and the known-answer kernel; the hinge
+    """GIK_KERNELS_ANCH_LINK (gik_instances.h, a group of GIK_ALL_KERNELS) holds two instantiations, the solve and the
+    known-answer kernel, both in the coverage table of tests/synth_graphs.py; the hinge
     template of the tests above reports them through gik_template_get_info: 3-D, 9 slots, anchored with link hinges
     (anchored = 3), at the LDS bytes of the link context and four waves per CU."""
     text = open(os.path.join(REPO, "graphik_amd", "csrc", "gik_instances.h")).read()
@@ -300,13 +301,17 @@ def test_the_new_kernel_group_is_what_the_hinge_template_runs(torch_cuda):
     assert m, "GIK_KERNELS_ANCH_LINK not found"
     group = {re.sub(r"\s+", "", s) for s in re.findall(r"X\(\s*void\s+(\w+\s*<[^>]*>)\s*\(", m.group(1))}
     all_k = re.search(r"#define\s+GIK_ALL_KERNELS\(X\)((?:[^\n]*\\\n)*[^\n]*)", text).group(1)
-    assert "GIK_KERNELS_ANCH_LINK" not in all_k      # (beside the table of tests/synth_graphs.py, not in it)
+    # in the table of tests/synth_graphs.py, and covered there by a test that exists
+    assert "GIK_KERNELS_ANCH_LINK(X)" in all_k
+    import synth_graphs as sg
+    cov, compiled = sg.coverage(), sg.compiled_instances()
+    assert group <= set(compiled) and all(cov.get(inst) for inst in group)
     robot, graph, on = _table(True)
     _, _, off = _table(False)
     info, base = on.template.info, off.template.info
     assert not info["is_block"] and info["anchored"] == 3 and base["anchored"] == 1
     slots = info["max_terms_per_node"]
-    ran = {f"rtr_wave_kernel<3,{slots},true,true,false,false,true>", f"kat_wave_kernel<3,{slots},true,false,true>"}
+    ran = {f"rtr_wave_kernel<3,{slots},W_THETA1|W_ANCH|W_LINKS>", f"kat_wave_kernel<3,{slots},W_ANCH|W_LINKS>"}
     assert ran == group
     # radii [128] + per-node link records and near lists [2][22] x (16 + 72) bytes on top of the anchored context
     assert info["lds_bytes"] - base["lds_bytes"] == 128 * 8 + 2 * 22 * (16 + 72)

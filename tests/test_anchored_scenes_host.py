@@ -212,32 +212,44 @@ def test_header_prototypes_equal_the_binding():
 
 
 # ---- 4. where the kernels sit ------------------------------------------------------------------------------------------
-ANCH_GROUP = """#define GIK_KERNELS_ANCH(X)                             \\
-  X(void rtr_wave_kernel<3, 9, true, true>(SolveArgs))  \\
-  X(void kat_wave_kernel<3, 9, true>(KatArgs))          \\
-  X(void rtr_wave_kernel<3, 20, true, true>(SolveArgs)) \\
-  X(void kat_wave_kernel<3, 20, true>(KatArgs))
+ANCH_GROUP = """#define GIK_KERNELS_ANCH(X)                                    \\
+  X(void rtr_wave_kernel<3, 9, W_THETA1 | W_ANCH>(SolveArgs))  \\
+  X(void kat_wave_kernel<3, 9, W_ANCH>(KatArgs))               \\
+  X(void rtr_wave_kernel<3, 20, W_THETA1 | W_ANCH>(SolveArgs)) \\
+  X(void kat_wave_kernel<3, 20, W_ANCH>(KatArgs))
 """
-ANCH_LINK_GROUP = """#define GIK_KERNELS_ANCH_LINK(X)                                          \\
-  X(void rtr_wave_kernel<3, 9, true, true, false, false, true>(SolveArgs)) \\
-  X(void kat_wave_kernel<3, 9, true, false, true>(KatArgs))
+ANCH_LINK_GROUP = """#define GIK_KERNELS_ANCH_LINK(X)                                        \\
+  X(void rtr_wave_kernel<3, 9, W_THETA1 | W_ANCH | W_LINKS>(SolveArgs)) \\
+  X(void kat_wave_kernel<3, 9, W_ANCH | W_LINKS>(KatArgs))
 """
+SCENE_GROUP = ["rtr_wave_scene_kernel<3,9,W_THETA1|W_ANCH>", "rtr_wave_scene_kernel<3,20,W_THETA1|W_ANCH>",
+               "rtr_wave_scene_kernel<3,9,W_THETA1|W_ANCH|W_LINKS>"]
 
 
-def test_scene_kernels_sit_beside_the_table():
+def test_scene_kernels_sit_in_the_table():
     from graphik_amd import build
+    import synth_graphs as sg
     text = open(INSTANCES_H).read()
-    assert ANCH_GROUP in text and ANCH_LINK_GROUP in text          # the existing anchored instantiations, textually unchanged
+    assert ANCH_GROUP in text and ANCH_LINK_GROUP in text          # the anchored groups: exactly these members, in this order
     m = re.search(r"#define\s+GIK_KERNELS_ANCH_SCENE\(X\)((?:[^\n]*\\\n)*[^\n]*)", text)
     group = [re.sub(r"\s+", "", s) for s in re.findall(r"X\(\s*void\s+(\w+\s*<[^>]*>)\s*\(", m.group(1))]
-    assert group == ["rtr_wave_scene_kernel<9,false>", "rtr_wave_scene_kernel<20,false>", "rtr_wave_scene_kernel<9,true>"]
+    assert group == SCENE_GROUP
+    # one table: every anchored group is in GIK_ALL_KERNELS, the host unit expands that and no group on its own, and every
+    # scene build is covered by a test that exists
     all_k = re.search(r"#define\s+GIK_ALL_KERNELS\(X\)((?:[^\n]*\\\n)*[^\n]*)", text).group(1)
-    assert "GIK_KERNELS_ANCH(X)" in all_k and "ANCH_SCENE" not in all_k and "ANCH_LINK" not in all_k
+    assert all(g in all_k for g in ("GIK_KERNELS_ANCH(X)", "GIK_KERNELS_ANCH_SCENE(X)", "GIK_KERNELS_ANCH_LINK(X)"))
+    compiled, cov = sg.compiled_instances(), sg.coverage()
+    for inst in SCENE_GROUP:
+        assert compiled.count(inst) == 1 and cov.get(inst), inst
+        assert all("::" in ref for ref in cov[inst]), cov[inst]
+        for ref in cov[inst]:
+            path, name = ref.split("::")
+            assert re.search(r"^def %s\(" % re.escape(name.split("[")[0]), open(os.path.join(REPO, path)).read(), flags=re.M), ref
     assert "gik_k_anch_scene.hip" in build.SOURCES
     unit = open(os.path.join(REPO, "graphik_amd", "csrc", "gik_k_anch_scene.hip")).read()
     assert "GIK_KERNELS_ANCH_SCENE(GIK_INSTANTIATE)" in unit
     host = open(os.path.join(REPO, "graphik_amd", "csrc", "gik_host.hip")).read()
-    assert "GIK_KERNELS_ANCH_SCENE(GIK_EXTERN_TEMPLATE)" in host
+    assert re.findall(r"GIK_\w+\(GIK_EXTERN_TEMPLATE\)", host) == ["GIK_ALL_KERNELS(GIK_EXTERN_TEMPLATE)"]
 
 
 # ---- 5. the host validation, walked by a stand-alone program -----------------------------------------------------------

@@ -1,4 +1,4 @@
-"""The lone-wavefront build of the per-edge kernel (rtr_wave_kernel<3, 9, true, false, false, true>, the SPLIT product of
+"""The lone-wavefront build of the per-edge kernel (rtr_wave_kernel<3, 9, W_THETA1 | W_PER_EDGE>, the SPLIT product of
 gik_rtr.hip.h) from its code object: the instruction count of one tCG step (what tools/isa_loop.py counts) and the
 register budget (at most 256 VGPRs, no scratch: two waves per SIMD stay possible).  CPU only; skips without the
 toolchain or a built library."""
@@ -14,7 +14,7 @@ from conftest import REPO
 
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-KERNEL = "_ZN3gik15rtr_wave_kernelILi3ELi9ELb1ELb0ELb0ELb1EEEvNS_9SolveArgsE"
+KERNEL = "_ZN3gik15rtr_wave_kernelILi3ELi9ELj%dEEEvNS_9SolveArgsE" % (1 | 8)      # W_THETA1 | W_PER_EDGE (gik_wave_kernels.hip.h)
 MAX_STEP_INSTRUCTIONS = 185     # 191 before the SPLIT exit test and the per-unit structurizer flag (NOTEBOOK 12)
 
 

@@ -15,16 +15,23 @@ from conftest import REPO
 
 OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
-NAME = "_ZN3gik15rtr_wave_kernelILi3ELi%dELb%dELb0ELb%dELb1EEEvNS_9SolveArgsE"      # <3, slots, theta one, false, spread, true>
-KERNEL = NAME % (9, 1, 0)
+W_THETA1, W_SPREAD, W_PER_EDGE = 1, 4, 8      # the bits of WaveBuild (gik_wave_kernels.hip.h) these six builds differ in
+
+
+def name(slots, theta_one, spread):
+    """rtr_wave_kernel<3, slots, flag word> of a per-edge build, mangled."""
+    return "_ZN3gik15rtr_wave_kernelILi3ELi%dELj%dEEEvNS_9SolveArgsE" % (slots, W_THETA1 * theta_one | W_SPREAD * spread | W_PER_EDGE)
+
+
+KERNEL = name(9, 1, 0)
 MAX_STEP_INSTRUCTIONS = 179     # 185 in the parent; 183 with |Hdelta|^2 on the distributed sum alone
 # (vgpr, agpr, sgpr, scratch bytes, spilled vgprs) of the other five, read from the parent commit's code object
 PARENT_FIGURES = {
-    NAME % (9, 1, 1): (153, 0, 106, 0, 0),
-    NAME % (9, 0, 0): (206, 0, 106, 0, 0),
-    NAME % (10, 1, 0): (187, 0, 106, 0, 0),
-    NAME % (10, 1, 1): (168, 0, 106, 0, 0),
-    NAME % (10, 0, 0): (225, 0, 106, 0, 0),
+    name(9, 1, 1): (153, 0, 106, 0, 0),
+    name(9, 0, 0): (206, 0, 106, 0, 0),
+    name(10, 1, 0): (187, 0, 106, 0, 0),
+    name(10, 1, 1): (168, 0, 106, 0, 0),
+    name(10, 0, 0): (225, 0, 106, 0, 0),
 }
 DPP_WAIT_STATES_AFTER_VALU_EXEC_WRITE = 5      # GCNHazardRecognizer::checkDPPHazards
 
@@ -108,7 +115,7 @@ def test_no_dpp_in_the_shadow_of_the_exec_write(code_object, slots):
     every group, down the fall-through path and down every branch taken from it.  Every instruction counts as one
     wait state (s_nop N as N + 1)."""
     _, txt = code_object
-    body = body_of(txt, NAME % (slots, 1, 0))
+    body = body_of(txt, name(slots, 1, 0))
     addr = [int(re.search(r"//\s*([0-9A-Fa-f]+):", l).group(1), 16) for l in body]
     base = addr[0]
     last = [i for i, l in enumerate(body) if l.split()[0].startswith("v_cmpx_")

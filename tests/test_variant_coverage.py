@@ -29,11 +29,11 @@ def test_every_instantiation_has_a_case():
 def test_a_new_instantiation_without_a_case_fails():
     with open(sg.INSTANCES_H) as f:
         text = f.read()
-    extra = "  X(void rtr_wave_kernel<2, 7, true>(SolveArgs))  \\\n"
-    anchor = "#define GIK_KERNELS_WAVE2(X)                       \\\n"
+    extra = "  X(void rtr_wave_kernel<2, 7, W_THETA1>(SolveArgs))  \\\n"
+    anchor = "#define GIK_KERNELS_WAVE2(X)                          \\\n"
     assert anchor in text
     missing, stale = _gaps(text.replace(anchor, anchor + extra))
-    assert missing == ["rtr_wave_kernel<2,7,true>"] and not stale
+    assert missing == ["rtr_wave_kernel<2,7,W_THETA1>"] and not stale
     dropped = re.sub(r"[^\n]*X\(void rcg_wave_kernel<2, 31>\(SolveArgs\)\)[^\n]*\n", "", text)
     assert dropped != text
     missing, stale = _gaps(dropped)
