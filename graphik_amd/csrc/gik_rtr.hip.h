@@ -167,6 +167,16 @@ struct split_ehess : std::false_type {};
 template <typename Ctx>
 struct split_ehess<Ctx, std::enable_if_t<Ctx::SPLIT_EHESS>> : std::true_type {};
 
+// The build whose tCG loop keeps its cold block outside the hot loop and waits once per owned slot for the product's
+// gathers (rtr_solve_one, LONE_LOOP): the nine-slot lone wavefront's, rtr_wave_kernel<3, 9, W_THETA1 | W_PER_EDGE>,
+// which is a small batch's critical path.  Every other build compiles the text it compiled before, token for token
+// (merely declaring the step's scalars outside `step` reschedules all of them); the register figures of the other
+// per-edge builds are pinned (tests/test_lone_wave_tail_isa.py).
+template <typename Ctx, bool EXEC_TEST, typename = void>
+struct lone_loop : std::false_type {};
+template <typename Ctx>
+struct lone_loop<Ctx, true, std::enable_if_t<Ctx::NSH == 3>> : std::true_type {};
+
 // THETA_ONE: compiled for the reference default theta = 1 (trust_region.py:92), where
 // norm_r0 ** theta needs no pow().  The generic build evaluates pow() when theta != 1; inlined, its
 // polynomial constants are hoisted to the per-problem setup and spilled to scratch by every problem
@@ -188,6 +198,7 @@ __device__ inline void rtr_solve_one(Ctx &cx, const Params &p, const gik_trace &
   // The SPLIT builds for theta = 1 take the tCG exit test by hand (plain_in_exec).  The generic-theta ones keep the
   // compiler's: they sit at 206 / 225 VGPRs and the vector register the hand-written test wants took the first to 207.
   constexpr bool EXEC_TEST = SPLIT && THETA_ONE;
+  constexpr bool LONE_LOOP = lone_loop<Ctx, EXEC_TEST>::value;
   const double Delta_bar = 10.0 + K;  // typicaldist (fixed_rank_psd_sym.py:71-73)
   const bool lead = cx.lead();
     double Delta = (SLICE && rs.resumed) ? rs.Delta : Delta_bar / 8.0;   // trust_region.py:134-135,164
@@ -341,6 +352,8 @@ __device__ inline void rtr_solve_one(Ctx &cx, const Params &p, const gik_trace &
         // One tCG iteration (:495-597).  (ec, hc, pc): current eta, Heta, <eta,eta>; (en, hn): the
         // previous eta, Heta on entry, the new ones on a plain return; pn: the new <eta,eta>.
         // Returns true when tCG ends (result in eta_l / Heta_l, or `bad`).
+        // (The nine-slot lone wavefront runs a second copy of these statements, in three parts: LONE_LOOP, below.  A
+        //  change to the step goes there as well; tests/test_lone_wave_loop_gpu.py compares the two bit for bit.)
         auto step = [&](const double ec, const double hc, const double pc, double &en, double &hn,
                         double &pn) __attribute__((always_inline)) -> bool {
           double H;                                // :497
@@ -527,7 +540,171 @@ __device__ inline void rtr_solve_one(Ctx &cx, const Params &p, const gik_trace &
         if constexpr (SPLIT) {
           if (p.maxinner > 0) cx.ehess_begin(delta);
         }
-        if (p.maxinner > 0)
+        if constexpr (LONE_LOOP) {
+          // The hot loop holds plain steps only and its one way out is a step's own `leave` branch; the cold block runs
+          // outside it and either ends tCG or finishes the step and enters the loop again.  With the cold block inside
+          // (`step`) the loop has an exit in every `return true` and a way back into the step, and the compiler joins
+          // them through a flag that every plain step sets and tests (s_mov / s_and / s_cbranch), and through register
+          // copies where the cold block's re-summed beta and <r', r'> meet the hot path's.  With ehess_end_slotwise:
+          // 179 -> 172 / 173 instructions in the two steps (NOTEBOOK 34).  The loop is always entered in the first role: a
+          // step that left it in the second swaps the two register sets on the way out (moves on the cold path, about
+          // twice per tCG solve), and so does the step finished out here.  Same operations on the same operands.
+          (void)step;
+          // One step's scalars, shared by its three parts below: `step` (above) in pieces, the same statements in the same
+          // order; its comments are not repeated here.
+          double Hdelta, d_Hd, model_value, r_r, alpha, e_Pe_new, beta_p, new_r_r, beta, rr_test;
+          // the product, the reduction and the test: true when the step is anything but a plain one
+          auto step_test = [&](const double ec, const double hc, const double pc) __attribute__((always_inline)) -> bool {
+            const double H = cx.ehess_end_slotwise();   // :497
+            double v[8] = {cx.Q[0] * H, cx.Q[1] * H, cx.Q[2] * H,      delta * H,
+                           w * H,       H * H,       ec * fma(0.5, hc, g), r * r};
+            const double wd = wave_sum8_distributed(v);
+#pragma unroll
+            for (int q = 0; q < 8; ++q)
+              if (q != 5) v[q] = readlane_f64(wd, wave_sum8_lane(q));
+            const double Hd_Hd = readlane_f64(fma(-v[2], v[2], fma(-v[1], v[1], fma(-v[0], v[0], wd))), wave_sum8_lane(5));
+            Hdelta = fma(-cx.Q[2], v[2], fma(-cx.Q[1], v[1], fma(-cx.Q[0], v[0], H)));
+            d_Hd = v[3];                             // :500
+            model_value = v[6];                      // :551 evaluated at the current eta
+            r_r = v[7];                              // :564 exact
+            const double rho = frcp1(d_Hd);
+            alpha = r_r * rho;                       // :503
+            e_Pe_new = fma(alpha, fma(alpha, d_Pd, e_Pd2), pc);                          // :506
+            beta_p = fma(fma(alpha, Hd_Hd, -(v[4] + v[4])), rho, 1.0);                   // :592 predicted
+            new_r_r = beta_p * r_r;                                                      // :564 predicted
+            beta = beta_p;
+            rr_test = new_r_r;
+            return !plain_in_exec(model_value, model_prev, d_Hd, e_Pe_new, T_cur, beta_p, new_r_r, target2_hi, j, maxinner_m1);
+          };
+          // the cold block behind it: true when tCG ends (result in eta_l / Heta_l, or `bad`), false when the step turns out
+          // to be a plain one after all (beta and new_r_r may have been re-summed)
+          auto step_cold = [&](const double ec, const double hc, const double pc, const double en,
+                               const double hn) __attribute__((always_inline)) -> bool {
+            if (!(d_Hd == d_Hd) || !(new_r_r == new_r_r) || !(model_value == model_value)) {
+              bad = true;
+              return true;
+            }
+            if (model_value >= model_prev) {                    // :552 of step j-1
+              eta_l = en;
+              Heta_l = hn;
+              e_Pe_end = pc;
+              stop_tCG = TCG_MODEL_INCREASED;
+              extra = 1;
+              j = j - 1;
+              return true;
+            }
+            if constexpr (RETRACE) {
+              if (!ck_set && (d_Hd <= 0.0 || e_Pe_new >= Tq)) {   // first meeting with radius / 4
+                cx.ck_put(0, ec);
+                cx.ck_put(1, hc);
+                cx.ck_put(2, delta);
+                cx.ck_put(3, Hdelta);
+                ck_e_Pe = pc;
+                ck_e_Pd2 = e_Pd2;
+                ck_d_Pd = d_Pd;
+                ck_j = j;
+                ck_neg = d_Hd <= 0.0;
+                ck_T = Tq;
+                ck_set = true;
+                T_cur = Delta2;
+              }
+            }
+            if (d_Hd <= 0.0 || e_Pe_new >= Delta2) {           // :509
+              const double tau = boundary_tau(e_Pd2, d_Pd, Delta2, pc);             // :514
+              eta_l = fma(tau, delta, ec);                      // :516
+              Heta_l = fma(tau, Hdelta, hc);                    // :521
+              e_Pe_end = pc;
+              stop_tCG = (d_Hd <= 0.0) ? TCG_NEGATIVE_CURVATURE : TCG_EXCEEDED_TR;  // :531-534
+              return true;
+            }
+            // the step's new vectors, for this block only: formed from an opaque copy of alpha so
+            // that they are not merged with (and hoisted above the branch for) the hot path's
+            double alpha_c = alpha;
+            asm volatile("" : "+v"(alpha_c));
+            if (beta_p < 1e-3) {
+              const double new_r = fma(alpha_c, Hdelta, r);     // :561
+              new_r_r = cx.sum1(new_r * new_r);
+              beta = new_r_r / r_r;
+              rr_test = new_r_r;
+            } else if (j >= p.mininner && new_r_r >= target2_lo && new_r_r <= target2_hi) {
+              const double new_r = fma(alpha_c, Hdelta, r);     // :561: a near tie is decided on the sum itself (:564)
+              rr_test = cx.sum1(new_r * new_r);
+            }
+            if (j >= p.mininner && rr_test <= target2) {        // :572
+              e_Pe_end = e_Pe_new;   // this step passed the radius test (what a rerun has to pass again)
+              // the reference tests the model of this step first (:552)
+              const double new_eta = fma(alpha_c, delta, ec);   // :538
+              const double new_Heta = fma(alpha_c, Hdelta, hc); // :542
+              const double model_new = cx.sum1(new_eta * fma(0.5, new_Heta, g));
+              if (model_new >= model_value) {
+                eta_l = ec;
+                Heta_l = hc;
+                stop_tCG = TCG_MODEL_INCREASED;
+              } else {
+                eta_l = new_eta;
+                Heta_l = new_Heta;
+                stop_tCG = (p.kappa < nr0_theta) ? TCG_REACHED_TARGET_LINEAR
+                                                 : TCG_REACHED_TARGET_SUPERLINEAR;
+              }
+              return true;
+            }
+            if (j + 1 >= p.maxinner) {
+              // inner iterations exhausted (:495) with the model test of this last step pending:
+              // take the step and reduce its model value on the spot
+              e_Pe_end = e_Pe_new;
+              const double new_eta = fma(alpha_c, delta, ec);   // :538
+              const double new_Heta = fma(alpha_c, Hdelta, hc); // :542
+              const double model_last = cx.sum1(new_eta * fma(0.5, new_Heta, g));
+              if (model_last >= model_value) {
+                eta_l = ec;
+                Heta_l = hc;
+                stop_tCG = TCG_MODEL_INCREASED;
+              } else {
+                eta_l = new_eta;
+                Heta_l = new_Heta;
+              }
+              j = p.maxinner;
+              return true;
+            }
+            return false;
+          };
+          // a plain step's updates
+          auto step_update = [&](const double ec, const double hc, double &en, double &hn, double &pn)
+                                 __attribute__((always_inline)) {
+            ++j;
+            pn = e_Pe_new;                                    // :537
+            model_prev = model_value;
+            en = fma(alpha, delta, ec);                       // :538 (reads the old delta)
+            w = fma(-alpha, Hdelta, w);
+            delta = fma(beta, delta, w);                      // :593
+            cx.ehess_begin(delta);
+            __builtin_amdgcn_sched_barrier(0);
+            hn = fma(alpha, Hdelta, hc);                      // :542
+            r = fma(alpha, Hdelta, r);                        // :561
+            e_Pd2 = beta * fma(alpha + alpha, d_Pd, e_Pd2);   // :596 (carried as 2 <eta, delta>)
+            d_Pd = fma(beta * beta, d_Pd, new_r_r);           // :597
+          };
+          auto swap_sets = [&]() __attribute__((always_inline)) {
+            double t;
+            t = ea, ea = eb, eb = t;
+            t = ha, ha = hb, hb = t;
+            t = pa, pa = pb, pb = t;
+          };
+          if (p.maxinner > 0)
+            for (;;) {
+              bool second;
+              for (;;) {                             // :495
+                if (__builtin_expect(step_test(ea, ha, pa), 0)) { second = false; break; }
+                step_update(ea, ha, eb, hb, pb);
+                if (__builtin_expect(step_test(eb, hb, pb), 0)) { second = true; break; }
+                step_update(eb, hb, ea, ha, pa);
+              }
+              if (second) swap_sets();
+              if (step_cold(ea, ha, pa, eb, hb)) break;
+              step_update(ea, ha, eb, hb, pb);
+              swap_sets();
+            }
+        } else if (p.maxinner > 0)
           for (;;) {                               // :495
             if (step(ea, ha, pa, eb, hb, pb)) break;
             if (step(eb, hb, pb, ea, ha, pa)) break;

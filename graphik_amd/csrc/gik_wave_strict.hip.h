@@ -137,6 +137,23 @@ struct WaveCtxStrict : WaveCtx<3, MAXDEG, false, true> {
     }
     return triple_sum(p);
   }
+  // ehess_end with one s_waitcnt per owned slot instead of two: a slot's third component -- the later of its two reads,
+  // and LDS reads return in order -- is taken first, and the scheduler keeps the rest of the slot behind it.  The same
+  // operations on the same operands.  Only the nine-slot lone wavefront calls it (rtr_solve_one, LONE_LOOP).
+  __device__ inline double ehess_end_slotwise() {
+    double p[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int k = 0; k < NSH; ++k) {
+      const double u2 = wn_.v[2] - rw_[k].v[2];
+      __builtin_amdgcn_sched_barrier(0);
+      const double u0 = wn_.v[0] - rw_[k].v[0], u1 = wn_.v[1] - rw_[k].v[1];
+      const double s = fma(ysn[k][2], u2, fma(ysn[k][1], u1, ysn[k][0] * u0));
+      p[0] = fma(s, ysn[k][0], fma(cc[k], u0, p[0]));
+      p[1] = fma(s, ysn[k][1], fma(cc[k], u1, p[1]));
+      p[2] = fma(s, ysn[k][2], fma(cc[k], u2, p[2]));
+    }
+    return triple_sum(p);
+  }
   __device__ inline double ehess(double W) {
     ehess_begin(W);
     return ehess_end();
