@@ -82,7 +82,7 @@ class PipelineDesc(C.Structure):
         ("last_link_along_z", C.c_int32), ("jacobi_sweeps", C.c_int32),
         ("force_block_prepare", C.c_int32), ("n_ee", C.c_int32),
         ("ee_goal_nodes", C.POINTER(C.c_int32)), ("ee_path", C.POINTER(C.c_int32)),
-        ("n_goal_pairs", C.c_int32), ("reserved1", C.c_int32),
+        ("n_goal_pairs", C.c_int32), ("position_goal_mask", C.c_int32),
         ("goal_pair_a", C.POINTER(C.c_int32)), ("goal_pair_b", C.POINTER(C.c_int32)),
         ("ee_goal_len", C.POINTER(C.c_double)),
     ]
@@ -194,6 +194,7 @@ SYMBOLS = {
     "gik_solve_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                   C.c_void_p, C.POINTER(Trace), C.c_void_p]),
     "gik_pipeline_attach": (C.c_int, [C.c_void_p, C.POINTER(PipelineDesc)]),
+    "gik_pipeline_set_point_axis": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double]),
     "gik_prepare_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     "gik_prepare_batch_debug": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,

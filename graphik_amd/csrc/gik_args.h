@@ -211,10 +211,19 @@ struct PipeConst {
   // and arithmetic of the single-end-effector kernels, bit for bit).
   int n_ee, n_gg;
   int goal_node[2 * 8];       // graph node of goal node g; -1: inert slot (k = 2 trees: a parent that an earlier
-                              // end effector's pose already pins -- graph_planar.py:136-145 through BatchProblem)
+                              // end effector's pose already pins -- graph_planar.py:136-145 through BatchProblem; the
+                              // odd slot of a position goal)
+  int pos_goal_mask;          // bit e: end effector e is a POSITION goal (graph.from_pos({p_e: xyz})): only p_e is pinned,
+                              // no T_final correction, no rotation error.  (In the padding in front of ee_len: no other
+                              // member moved when it was added.)
   double ee_len[8];           // goal_len per end effector: axis_length (k = 3), |parent(e) e| (k = 2)
   const int *gg_a, *gg_b;     // [n_gg] goal-node slots of each pair
   const int *ee_path;         // [n_ee][n+1] joints from the root to end effector e, -1 padded
+  // k = 3, a position goal whose last link lies along z (gik_pipeline_set_point_axis): the x, y of qs_0 that the point
+  // formula of its last joint uses instead of forming them from T0.  There they are round-off residues of the frame
+  // product, and their direction alone decides the angle (graph_revolute.py:308 without the T_final correction).
+  double pos_qs0[8][2];
+  int pos_qs0_mask;           // bit e: pos_qs0[e] is set
 };
 
 struct PrepArgs {

@@ -701,8 +701,9 @@ static int upload_pipe_const(gik_template *t, const gik_pipeline_desc *d, PipeCo
 }
 
 // end effectors: a chain is one path 0..n with goal nodes (goal_node0, goal_node1).  path: [n_ee][n + 1], -1 past an end
+// inert_goal_slot: a goal slot of -1; position_goals: every such slot is the odd slot of a position end effector
 static int end_effector_paths(gik_template *t, const gik_pipeline_desc *d, PipeConst &pc, std::vector<int> &path,
-                              bool &inert_goal_slot) {
+                              bool &inert_goal_slot, bool &position_goals) {
   const int N = t->N, K = t->f.K, n = d->n_joints;
   bool ok = true;
   const int n_ee = d->n_ee > 1 ? d->n_ee : 1;
@@ -710,6 +711,16 @@ static int end_effector_paths(gik_template *t, const gik_pipeline_desc *d, PipeC
   if (n_ee > 1 && (!d->ee_goal_nodes || !d->ee_path || d->n_goal_pairs < 0 || (K == 2 && !d->ee_goal_len) ||
                    (d->n_goal_pairs > 0 && (!d->goal_pair_a || !d->goal_pair_b))))
     return fail("several end effectors: ee_goal_nodes / ee_path / goal pairs (k = 2: ee_goal_len) required");
+  // position goals: one bit per end effector, its odd slot inert, no T_final correction
+  const uint32_t mask = (uint32_t)d->position_goal_mask;
+  if (mask >> n_ee) return fail("position_goal_mask: a bit at or beyond n_ee");
+  if (mask & (uint32_t)d->last_link_along_z)
+    return fail("position_goal_mask: a position goal takes no T_final correction; clear its bit of last_link_along_z");
+  const char *odd_slot = "position_goal_mask: the odd goal slot of a position goal (goal_node1, ee_goal_nodes[2 e + 1]) must be -1";
+  pc.pos_goal_mask = (int)mask;
+  pc.pos_qs0_mask = 0;
+  for (auto &xy : pc.pos_qs0) xy[0] = xy[1] = 0.0;
+  bool inert_other = false;
   pc.n_ee = n_ee;
   pc.n_gg = n_ee > 1 ? d->n_goal_pairs : 0;
   path.assign((size_t)n_ee * (n + 1), -1);
@@ -717,10 +728,13 @@ static int end_effector_paths(gik_template *t, const gik_pipeline_desc *d, PipeC
   if (n_ee > 1) {
     for (int g = 0; g < 2 * n_ee; ++g) {
       pc.goal_node[g] = d->ee_goal_nodes[g];
-      // -1: a planar tree's parent node that an earlier end effector's pose pins already (odd slots only)
-      if (pc.goal_node[g] < 0 && !(K == 2 && (g & 1))) return fail("bad ee_goal_nodes");
+      const bool pos_odd = (g & 1) && ((mask >> (g >> 1)) & 1);      // the odd slot of a position goal
+      // -1: a planar tree's parent node that an earlier end effector's pose pins already, or a position goal (odd slots only)
+      if (pc.goal_node[g] < 0 && !((K == 2 && (g & 1)) || pos_odd)) return fail("bad ee_goal_nodes");
       if (pc.goal_node[g] >= N) return fail("bad ee_goal_nodes");
+      if (pos_odd && pc.goal_node[g] >= 0) return fail(odd_slot);
       inert_goal_slot = inert_goal_slot || pc.goal_node[g] < 0;
+      inert_other = inert_other || (pc.goal_node[g] < 0 && !pos_odd);
     }
     for (size_t t = 0; t < path.size(); ++t) path[t] = d->ee_path[t];
     for (int e = 0; e < n_ee; ++e)
@@ -731,8 +745,13 @@ static int end_effector_paths(gik_template *t, const gik_pipeline_desc *d, PipeC
   } else {
     pc.goal_node[0] = d->goal_node0;
     pc.goal_node[1] = d->goal_node1;
+    if (mask & 1) {
+      if (d->goal_node1 >= 0) return fail(odd_slot);
+      inert_goal_slot = true;
+    }
     for (int k = 0; k <= n; ++k) path[k] = k;
   }
+  position_goals = inert_goal_slot && !inert_other;
   pc.ee_path = upload(t, path.data(), path.size(), ok);
 
   pc.gg_a = pc.n_gg ? upload(t, d->goal_pair_a, pc.n_gg, ok) : nullptr;
@@ -768,7 +787,7 @@ static int prep_occupancy(Prep v, int threads, size_t lds) {
 
 // the prepare kernel of this template (plan_prepare), and the slab and the event of a block variant.  The developer
 // switches of the environment are read once, here.
-static int plan_and_acquire_prepare(gik_template *t, const gik_pipeline_desc *d, bool inert_goal_slot) {
+static int plan_and_acquire_prepare(gik_template *t, const gik_pipeline_desc *d, bool inert_goal_slot, bool position_goals) {
   PrepFacts f;
   f.N = t->N;
   f.K = t->f.K;
@@ -776,6 +795,7 @@ static int plan_and_acquire_prepare(gik_template *t, const gik_pipeline_desc *d,
   f.n_ee = t->pc.n_ee;
   f.n_gg = t->pc.n_gg;
   f.inert_goal_slot = inert_goal_slot;
+  f.position_goals = position_goals;
   f.force_block_prepare = d->force_block_prepare != 0;
   f.env_force_block = getenv("GIK_PREP_FORCE_BLOCK") != nullptr;
   f.env_no_compress = getenv("GIK_PREP_NO_COMPRESS") != nullptr;
@@ -804,12 +824,26 @@ int gik_pipeline_attach(gik_template *t, const gik_pipeline_desc *d) {
   if (validate_pipeline(t, d)) return -1;
   PipeConst pc;
   std::vector<int> path;
-  bool inert_goal_slot = false;
-  if (upload_pipe_const(t, d, pc) || end_effector_paths(t, d, pc, path, inert_goal_slot)) return -1;
+  bool inert_goal_slot = false, position_goals = false;
+  if (upload_pipe_const(t, d, pc) || end_effector_paths(t, d, pc, path, inert_goal_slot, position_goals)) return -1;
   t->pc = pc;
-  if (plan_and_acquire_prepare(t, d, inert_goal_slot)) return -1;
+  if (plan_and_acquire_prepare(t, d, inert_goal_slot, position_goals)) return -1;
   if (!seed_tables(t, d, path, pc.n_ee)) return fail("device upload failed");
   t->has_pipe = true;
+  return 0;
+}
+
+int gik_pipeline_set_point_axis(gik_template *t, int ee, double x, double y) {
+  using namespace gik;
+  if (!t) return fail("gik_pipeline_set_point_axis: bad argument");
+  if (!t->has_pipe) return fail("gik_pipeline_set_point_axis: no pipeline attached (gik_pipeline_attach)");
+  if (t->f.K != 3) return fail("gik_pipeline_set_point_axis: k = 3 only");
+  if (ee < 0 || ee >= t->pc.n_ee || !((t->pc.pos_goal_mask >> ee) & 1))
+    return fail("gik_pipeline_set_point_axis: ee must be an end effector with a position goal (position_goal_mask)");
+  if (!std::isfinite(x) || !std::isfinite(y)) return fail("gik_pipeline_set_point_axis: x and y must be finite");
+  t->pc.pos_qs0[ee][0] = x;
+  t->pc.pos_qs0[ee][1] = y;
+  t->pc.pos_qs0_mask |= 1 << ee;
   return 0;
 }
 

@@ -210,6 +210,8 @@ static std::string anchored_pair_fault(const gik_template *anch, const gik_templ
   if (!anch->anchored) return "the first handle must be a fixed-anchor template (gik_template_create_anchored)";
   if (!base->has_pipe || ((terms & PAIR_3D) && base->f.K != 3) || base->N != anch->full_N)
     return "the base template must be the robot graph (full_N nodes) with its pipeline attached";
+  if (base->pc.pos_goal_mask)
+    return "the base template has position goals (position_goal_mask); the fixed-anchor formulation takes pose goals";
   if ((terms & PAIR_SEEDABLE) && !base->seed_ok) return "the base graph cannot be seeded on the device: " + base->seed_why;
   return std::string();
 }
@@ -501,6 +503,9 @@ int gik_anchored_retry_seeds(const gik_template *base, const double *d_T_goal, c
   using namespace gik;
   if (!base || count < 0) return fail("gik_anchored_retry_seeds: bad argument");
   if (!base->has_pipe) return fail("gik_anchored_retry_seeds: no pipeline attached to the base template (gik_pipeline_attach)");
+  if (base->pc.pos_goal_mask)
+    return fail("gik_anchored_retry_seeds: the base template has position goals (position_goal_mask); the fixed-anchor "
+                "formulation takes pose goals");
   if (attempt < 0 || attempt > 63) return fail("gik_anchored_retry_seeds: attempt must be within 0 .. 63");
   if (!d_q_lo || !d_q_hi) return fail("gik_anchored_retry_seeds: null joint limits (d_q_lo / d_q_hi, [n] each, are required)");
   if (!(spread >= 0.0)) return fail("gik_anchored_retry_seeds: spread must be at least 0");

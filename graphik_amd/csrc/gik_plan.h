@@ -200,7 +200,10 @@ constexpr size_t plan_prep_quad_lds_bytes(int N, int n_gd) {
 struct PrepFacts {
   int N = 0, K = 0;      // (no rule reads K: the 2-D and the 3-D pipeline plan alike)
   int n_anchor = 0, n_ee = 1, n_gg = 0;
-  bool inert_goal_slot = false;       // an ee_goal_nodes entry of -1 (prep_wave_kernel skips it, the quad kernel cannot)
+  bool inert_goal_slot = false;       // a goal slot of -1 (every prepare kernel skips it)
+  bool position_goals = false;        // ... and every one of them is the odd slot of a position end effector
+                                      // (position_goal_mask).  A planar tree's parent slot that an earlier pose pins keeps
+                                      // prep_wave_kernel, as it always has: the recorded plans (tests/golden/prep_plan.json)
   bool force_block_prepare = false;   // gik_pipeline_desc::force_block_prepare
   bool env_force_block = false;       // GIK_PREP_FORCE_BLOCK
   bool env_no_compress = false;       // GIK_PREP_NO_COMPRESS
@@ -284,7 +287,7 @@ inline PrepPlan plan_prepare(const PrepFacts &f, Occupancy occupancy) {
   if (f.env_waves_set) occ = f.env_waves;   // developer override
   p.lds = p.wave_lds;
   p.wpc = p.wave_wpc = std::max(1, std::min(occ, 32));
-  if (N <= PREPQ_MAXN && !f.inert_goal_slot && !f.env_no_quad) {
+  if (N <= PREPQ_MAXN && (!f.inert_goal_slot || f.position_goals) && !f.env_no_quad) {
     const Prep quad = N == 13 ? Prep::QUAD13 : Prep::QUAD;
     const size_t quad_lds = plan_prep_quad_lds_bytes(N, n_gd);
     int qocc = 0;

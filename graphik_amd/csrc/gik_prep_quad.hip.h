@@ -407,8 +407,10 @@ __global__ void __launch_bounds__(WAVE, 2) prep_quad_kernel(PrepArgs a) {
       int an, gn;
       const double d = goal_distance(pc, Tg, idx, an, gn);
       gd[idx] = d;
-      U[an * S + gn] = U[gn * S + an] = d;
-      L[an * S + gn] = L[gn * S + an] = d;
+      if (an >= 0 && gn >= 0) {      // (an inert goal slot pins nothing; no term reads its gd)
+        U[an * S + gn] = U[gn * S + an] = d;
+        L[an * S + gn] = L[gn * S + an] = d;
+      }
     }
     __builtin_amdgcn_wave_barrier();
     // per-term targets: squared goal distances for the goal edges, template constants otherwise

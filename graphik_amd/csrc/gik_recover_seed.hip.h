@@ -1,7 +1,8 @@
 // graphik_amd/csrc/gik_recover_seed.hip.h -- joint angles out of a point matrix, and a point matrix out of joint angles.
 //
 //   recover_kernel   : one thread per goal: joint_variables (graph_revolute.py:251-318 /
-//       graph_planar.py:147-176) + forward kinematics of the recovered angles -> EE pose error.
+//       graph_planar.py:147-176) + forward kinematics of the recovered angles -> EE pose error.  An end effector of
+//       PipeConst::pos_goal_mask is a position goal: no T_final correction, its rotation error is not counted (0.0).
 //   seed_kernel      : one wavefront per goal: the targets of a goal and the realization of q_init (see below).
 // Plain kernels, defined where GIK_DEFINE_PLAIN_KERNELS is set (gik_k_prep.hip); every other unit sees prototypes.
 #pragma once
@@ -84,6 +85,10 @@ __global__ void __launch_bounds__(64) recover_kernel(RecoverArgs a)
         // qs_0 = (T_prev_0^-1 T_0 trans_z(a)).trans
         double qs0[2];
         for (int t = 0; t < 2; ++t) qs0[t] = Trel[t * 4 + 3] + Trel[t * 4 + 2] * pc.axis_length;
+        if (k == last && ((pc.pos_qs0_mask >> e) & 1)) {      // (a position goal behind a link along z: see PipeConst)
+          qs0[0] = pc.pos_qs0[e][0];
+          qs0[1] = pc.pos_qs0[e][1];
+        }
         const double *pc_ = P + pc.p_idx[cur] * 3, *qc = P + pc.q_idx[cur] * 3;
         double dq[3], nr = 0.0;
         for (int t = 0; t < 3; ++t) {
@@ -114,7 +119,8 @@ __global__ void __launch_bounds__(64) recover_kernel(RecoverArgs a)
         mat4_mul(Tp, Rz, tmp);
         mat4_mul(tmp, Trel, Tee);
       }
-      if ((pc.last_along_z >> e) & 1) {  // :314-316
+      const bool pos_goal = (pc.pos_goal_mask >> e) & 1;   // a position goal: no T_final, no rotation error
+      if (((pc.last_along_z >> e) & 1) && !pos_goal) {  // :314-316
         // T_final expressed in the recovered base frame is the goal itself (T_base = identity
         // re-basing happened at load time); T_th = T[ee]^-1 T_final
         mat4_inv_rigid(Tee, inv);
@@ -134,7 +140,7 @@ __global__ void __launch_bounds__(64) recover_kernel(RecoverArgs a)
         for (int u = 0; u < 3; ++u) tr += Tg[t * 4 + u] * Tee[t * 4 + u];  // trace(Rg Rs^T)
       }
       worst_p = fmax(worst_p, sqrt(dp));
-      worst_r = fmax(worst_r, acos(fmin(1.0, fmax(-1.0, 0.5 * tr - 0.5))));
+      if (!pos_goal) worst_r = fmax(worst_r, acos(fmin(1.0, fmax(-1.0, 0.5 * tr - 0.5))));
     }
     a.pos_err[b] = worst_p;     // (several end effectors: the worst of them)
     a.rot_err[b] = worst_r;
@@ -206,7 +212,7 @@ __global__ void __launch_bounds__(64) recover_kernel(RecoverArgs a)
       const double dx = Te[2] - px, dy = Te[5] - py;
       worst_p = fmax(worst_p, sqrt(dx * dx + dy * dy));
       const double gphi = atan2(Te[3], Te[0]);
-      worst_r = fmax(worst_r, fabs(wrap_pi(gphi - phi)));
+      if (!((pc.pos_goal_mask >> e) & 1)) worst_r = fmax(worst_r, fabs(wrap_pi(gphi - phi)));   // (a position goal has none)
     }
     a.pos_err[b] = worst_p;
     a.rot_err[b] = worst_r;

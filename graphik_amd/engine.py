@@ -439,9 +439,12 @@ class Template:
                         goal_len, base_lower, base_upper, anchor_index, anchor_pos, pair_i, pair_j,
                         term_src, term_static, last_link_along_z, jacobi_sweeps=0,
                         force_block_prepare=False, ee_goal_nodes=None, ee_path=None,
-                        goal_pair_a=(), goal_pair_b=(), ee_goal_len=None):
+                        goal_pair_a=(), goal_pair_b=(), ee_goal_len=None, position_goal_mask=0, point_axis=None):
         """Give the handle what it needs to run from_pose + bound_smoothing +
-        generate_initialization and joint_variables on the device (gik_pipeline_attach)."""
+        generate_initialization and joint_variables on the device (gik_pipeline_attach).
+        position_goal_mask: bit e -- end effector e has a position goal (gik_pipeline_desc::position_goal_mask): its odd
+        goal slot (goal_nodes[1], ee_goal_nodes[2 e + 1]) is -1 and its bit of last_link_along_z clear.
+        point_axis: {e: (x, y)} for gik_pipeline_set_point_axis (position goals behind a last link along z)."""
         keep = {}
 
         def arr(name, a, dt):
@@ -470,6 +473,7 @@ class Template:
         d.term_src = arr("ts", term_src, np.int32)
         d.term_static = arr("tv", term_static, np.float64)
         d.last_link_along_z = int(last_link_along_z)       # one bit per end effector
+        d.position_goal_mask = int(position_goal_mask)     # likewise
         d.jacobi_sweeps = int(jacobi_sweeps)
         d.force_block_prepare = int(bool(force_block_prepare))
         self.n_ee = 1
@@ -485,6 +489,8 @@ class Template:
                 d.ee_goal_len = arr("el", ee_goal_len, np.float64)
         with torch.cuda.device(self.device):
             _ffi.check(self.lib.gik_pipeline_attach(self._h, C.byref(d)))
+            for e, (x, y) in (point_axis or {}).items():
+                _ffi.check(self.lib.gik_pipeline_set_point_axis(self._h, int(e), float(x), float(y)))
         self.n_joints = int(d.n_joints)
         self.has_pipeline = True
         self._read_info()

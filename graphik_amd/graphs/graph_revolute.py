@@ -180,6 +180,20 @@ class ProblemGraphRevolute(ProblemGraph):
         return T.dot(trans_axis(self.axis_length, "z")) if query_node[0] == AUX_PREFIX else T
 
 
+def point_axis_offset(graph, ee):
+    """qs_0 of the last joint of end effector `ee` (graph_revolute.py:292-297) by the reference's own sequence of
+    operations -- T_prev_0.inv().dot(T_0.dot(trans_z(axis_length))).trans -- when the last link lies along z
+    (:314), else None.  There x and y of qs_0 are round-off residues of that product, and without a T_final to
+    correct it the DIRECTION of the residue is the last angle the point formula (:308) returns: to give the
+    reference's angle it has to be formed as the reference forms it."""
+    robot = graph.robot
+    k_map = robot.kinematic_map[ROOT][ee]
+    T_prev_0, T_0 = robot.nodes[k_map[-2]]["T0"], robot.nodes[k_map[-1]]["T0"]
+    if np.linalg.norm(np.cross(T_prev_0.inv().dot(T_0).trans, [0, 0, 1])) >= 1e-10:
+        return None
+    return np.asarray(T_prev_0.inv().dot(T_0.dot(trans_axis(graph.axis_length, "z"))).trans, dtype=float)
+
+
 def joint_variables_revolute_batch(graph, P, T_final=None, tol=1e-10):
     """Vectorised restatement of ProblemGraphRevolute.joint_variables over B realisations.
     P [B,N,3] (node order of `graph`); T_final: [B,4,4] poses of the (first) end effector, a dict
@@ -210,6 +224,9 @@ def joint_variables_revolute_batch(graph, P, T_final=None, tol=1e-10):
             inv_prev0 = np.linalg.inv(T0_prev)
             T_rel = inv_prev0 @ T0_cur
             qs_0 = (inv_prev0 @ T0_cur @ Tz)[:3, 3]
+            if idx == len(k_map) - 1 and (T_final is None or ee not in T_final):
+                ref_qs_0 = point_axis_offset(graph, ee)      # no T_final will correct this angle: the reference's residues
+                qs_0 = qs_0 if ref_qs_0 is None else ref_qs_0
             pc, qc = P[:, ix(cur)], P[:, ix(AUX_PREFIX + cur[1:])]
             qn = to_base(pc + unit(qc - pc))
             T_prev = T[pred]

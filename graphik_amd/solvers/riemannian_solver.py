@@ -176,14 +176,60 @@ class RiemannianSolver:
 
 
 # ---------------------------------------------------------------------------------------------
+GOAL_KINDS = ("pose", "position")
+
+
+def goal_kinds(goal, n_ee):
+    """The goal= argument -> one kind per end effector: "pose" or "position", or a sequence of those with one entry
+    per robot.end_effectors.  ValueError for anything else."""
+    kinds = (goal,) * n_ee if isinstance(goal, str) else tuple(goal) if isinstance(goal, (list, tuple, np.ndarray)) else None
+    if kinds is None:
+        raise ValueError(f"goal must be 'pose', 'position' or a sequence of those, got {goal!r}")
+    if len(kinds) != n_ee:
+        raise ValueError(f"goal has {len(kinds)} entries for {n_ee} end effector{'s' if n_ee != 1 else ''}")
+    for kind in kinds:
+        if not isinstance(kind, str) or kind not in GOAL_KINDS:
+            raise ValueError(f"unknown goal kind {kind!r}: a goal is 'pose' or 'position'")
+    return tuple(str(kind) for kind in kinds)
+
+
+def goal_poses(goals, kinds, dim, lead=1):
+    """The goal array of a problem with position goals as pose arrays, the layout of the device buffers.  `lead` leading
+    axes ([B], or [B, L] of a path).  When every end effector is a position: positions [..., d] or [..., n_ee, d], packed
+    into identity-rotation poses; pose arrays [..., d+1, d+1] / [..., n_ee, d+1, d+1] are taken as they are (of a position
+    end effector's pose only the translation column is read).  ValueError for any other shape."""
+    G = np.asarray(goals, dtype=float)
+    n_ee, d = len(kinds), dim
+    head, tail = G.shape[:lead], G.shape[lead:]
+    pose_tails = [(n_ee, d + 1, d + 1)] + ([(d + 1, d + 1)] if n_ee == 1 else [])
+    if G.ndim >= lead and tail in pose_tails:
+        return G
+    if all(kind == "position" for kind in kinds):
+        if G.ndim >= lead and tail in [(n_ee, d)] + ([(d,)] if n_ee == 1 else []):
+            P = G.reshape(head + (n_ee, d))
+            T = np.broadcast_to(np.identity(d + 1), head + (n_ee, d + 1, d + 1)).copy()
+            T[..., :d, d] = P
+            return T if len(tail) == 2 else T[..., 0, :, :]
+    axes = "B, L, " if lead == 2 else "B, "
+    want = f"poses [{axes}{f'{n_ee}, ' if n_ee > 1 else ''}{d + 1}, {d + 1}]"
+    if all(kind == "position" for kind in kinds):
+        want = f"positions [{axes}{d}] or [{axes}{n_ee}, {d}], or " + want
+    raise ValueError(f"goal array of shape {list(G.shape)}: expected {want}")
+
+
 class BatchProblem:
     """Goal-independent data of solve_with_riemannian for one problem graph, prepared once:
     edge template, which squared distances depend on the goal, anchors, limits."""
 
     def __init__(self, graph, use_limits=True, params=None, device=None, force_block_prepare=False,
-                 host_only=False):
+                 host_only=False, goal="pose"):
         """host_only: only the goal-independent host data (edge pattern, anchors, limits); no device
-        handle is created (term-set construction can then be inspected without a GPU)."""
+        handle is created (term-set construction can then be inspected without a GPU).
+
+        goal: "pose" -- a goal pins p_e and q_e (planar: the end effector and its parent), graph.from_pose -- or
+        "position": it pins the point p_e alone, the reference's graph.from_pos({p_e: xyz}); the orientation is free,
+        no T_final correction applies to that end effector's last angle and its rotation error is reported as 0.  A
+        sequence with one entry per robot.end_effectors mixes the kinds on a tree."""
         self.force_block_prepare = force_block_prepare
         self.graph = graph
         self.robot = graph.robot
@@ -193,18 +239,21 @@ class BatchProblem:
         n = self.robot.n
         self.end_effectors = list(self.robot.end_effectors)
         self.multi_ee = len(self.end_effectors) > 1
+        self.goal_kinds = goal_kinds(goal, len(self.end_effectors))
+        is_pose = [kind == "pose" for kind in self.goal_kinds]
         ee = self.end_effectors[0]
         # goal nodes and how their positions follow from the goal pose (_pose_goal); a robot with
         # several end effectors (3-D trees) has a (p, q) pair per end effector and takes goals
-        # [B, n_ee, 4, 4] in the order of robot.end_effectors
+        # [B, n_ee, 4, 4] in the order of robot.end_effectors.  A position goal pins p_e only.
         if self.dim == 3:
-            self.goal_nodes = [graph.index(c + e[1:]) for e in self.end_effectors for c in "pq"]
+            self.goal_nodes = [graph.index(c + e[1:]) for e, pose in zip(self.end_effectors, is_pose) for c in ("pq" if pose else "p")]
+            self._goal_keep = [2 * e_i + s for e_i, pose in enumerate(is_pose) for s in ((0, 1) if pose else (0,))]
         else:
             # planar (graph_planar.py:136-145): a goal pose pins its end effector and the end effector's
             # parent; two end effectors of a tree may share that parent (one goal node then)
             self.goal_nodes, self._goal_src = [], []
             for e_i, e in enumerate(self.end_effectors):
-                for is_parent, name in ((0, e), (1, self.robot.parent[e])):
+                for is_parent, name in ((0, e), (1, self.robot.parent[e]))[:2 if is_pose[e_i] else 1]:
                     if graph.index(name) not in self.goal_nodes:
                         self.goal_nodes.append(graph.index(name))
                         self._goal_src.append((e_i, is_parent, graph.dist[graph.index(self.robot.parent[e]),
@@ -215,7 +264,14 @@ class BatchProblem:
                                    dtype=float)
         # a goal instance with a dummy pose gives the complete edge pattern (omega)
         q0 = self.robot.zero_configuration()
-        G0 = graph.from_pose({e: self.robot.pose(q0, e) for e in self.end_effectors})
+        if all(is_pose):
+            G0 = graph.from_pose({e: self.robot.pose(q0, e) for e in self.end_effectors})
+        else:      # from_pos of what the goals pin: (p_e, q_e) of a pose, p_e of a position
+            pinned = {}
+            for e, pose in zip(self.end_effectors, is_pose):
+                T_e = self.robot.pose(q0, e)
+                pinned.update(graph._pose_goal({e: T_e}) if pose else {e: as_matrix(T_e)[:self.dim, self.dim]})
+            G0 = graph.from_pos(pinned)
         self.omega = dgp.adjacency_matrix_from_graph(G0)
         self.base_D = dgp.distance_matrix_from_graph(G0)
         self.base_lower = np.where(G0.edge, G0.lower, np.nan)
@@ -242,7 +298,7 @@ class BatchProblem:
 
     def claim_key_nodes(self):
         """The goal nodes whose distance to the base origin p0 is the goal's reach: the end effectors' points p_e."""
-        return list(self.goal_nodes[0::2]) if self.dim == 3 else []
+        return [self.graph.index(e) for e in self.end_effectors] if self.dim == 3 else []
 
     def claim_key_terms(self):
         """Indices of the goal-dependent equality terms (p0, p_e) between the base anchor and the goal nodes of
@@ -263,16 +319,20 @@ class BatchProblem:
             return
         # Device goal slots: two per end effector.  3-D: (p_e, q_e) = self.goal_nodes in order.  Planar (round 6: trees
         # too): (the end effector, its parent); a parent that an earlier end effector's pose pins already gets an inert
-        # slot (-1) -- _pose_goal / BatchProblem keep the first definition.
+        # slot (-1) -- _pose_goal / BatchProblem keep the first definition.  A position goal: (p_e, -1) in either dimension.
+        is_pose = [kind == "pose" for kind in self.goal_kinds]
+        position_mask = sum(1 << e for e, pose in enumerate(is_pose) if not pose)
         if self.dim == 3:
-            dev_slots = list(self.goal_nodes)
+            dev_slots = [g.index(c + e[1:]) if c == "p" or pose else -1 for e, pose in zip(self.end_effectors, is_pose) for c in "pq"]
         else:
             dev_slots, seen = [], set()
-            for e in self.end_effectors:
+            for e, pose in zip(self.end_effectors, is_pose):
                 for name in (e, self.robot.parent[e]):
                     node = g.index(name)
-                    dev_slots.append(node if node not in seen else -1)
-                    seen.add(node)
+                    pinned = pose or name == e
+                    dev_slots.append(node if pinned and node not in seen else -1)
+                    if pinned:
+                        seen.add(node)
             if any(dev_slots[2 * e] < 0 for e in range(len(self.end_effectors))):
                 self.device_pipeline = False       # (an end effector that is another one's parent: host path)
                 return
@@ -312,7 +372,7 @@ class BatchProblem:
         for e, ee in enumerate(self.end_effectors):
             path = [int(name[1:]) for name in self.robot.kinematic_map["p0"][ee]]
             ee_path[e, :len(path)] = path
-        ee_len = None
+        ee_len, point_axis = None, {}
         if self.dim == 3:
             p_idx = [g.index(f"p{i}") for i in range(n + 1)]
             q_idx = [g.index(f"q{i}") for i in range(n + 1)]
@@ -320,28 +380,38 @@ class BatchProblem:
             for e, ee in enumerate(self.end_effectors):
                 path = [int(name[1:]) for name in self.robot.kinematic_map["p0"][ee]]
                 rel_last = np.linalg.inv(T0[path[-2]]) @ T0[path[-1]]
-                if np.linalg.norm(np.cross(rel_last[:3, 3], [0, 0, 1])) < 1e-10:
-                    along_z |= 1 << e
+                if is_pose[e] and np.linalg.norm(np.cross(rel_last[:3, 3], [0, 0, 1])) < 1e-10:
+                    along_z |= 1 << e      # (a position goal has no T_final: the correction does not apply)
             goal_len = g.axis_length
+            # a position goal behind a last link along z: the residues the point formula takes its angle from (point_axis_offset)
+            from ..graphs.graph_revolute import point_axis_offset
+            for e, ee in enumerate(self.end_effectors):
+                if not is_pose[e] and point_axis_offset(g, ee) is not None:
+                    point_axis[e] = point_axis_offset(g, ee)[:2]
         else:
             p_idx = [g.index(f"p{i}") for i in range(n + 1)]
             q_idx = None
             along_z = 0
-            goal_len = g.dist[self.goal_nodes[1], self.goal_nodes[0]]
             ee_len = [g.dist[g.index(self.robot.parent[e]), g.index(e)] for e in self.end_effectors]
+            goal_len = ee_len[0]
         T.attach_pipeline(T0=T0, p_index=p_idx, q_index=q_idx, x_index=g.index("x"),
                           y_index=g.index("y"), axis_length=g.axis_length,
-                          goal_nodes=self.goal_nodes, goal_len=goal_len, base_lower=lower,
+                          goal_nodes=dev_slots[:2], goal_len=goal_len, base_lower=lower,
                           base_upper=upper, anchor_index=self.anchor_nodes,
                           anchor_pos=self.anchor_pos, pair_i=I, pair_j=J, term_src=term_src,
-                          term_static=static, last_link_along_z=along_z,
+                          term_static=static, last_link_along_z=along_z, position_goal_mask=position_mask, point_axis=point_axis,
                           force_block_prepare=self.force_block_prepare,
                           ee_goal_nodes=dev_slots if self.multi_ee else None, ee_path=ee_path, ee_goal_len=ee_len,
                           goal_pair_a=[a for a, _ in pairs], goal_pair_b=[b for _, b in pairs])
         self.device_pipeline = True
 
+    def goal_poses(self, goals, lead=1):
+        """Goal arrays as this problem's entries take them -> pose arrays (goal_poses above): positions, where every
+        end effector has a position goal, are packed into identity-rotation poses."""
+        return goal_poses(goals, self.goal_kinds, self.dim, lead)
+
     def goal_positions(self, T_goals):
-        """[B,d+1,d+1] poses -> positions of the goal nodes [B,2,d]  (_pose_goal)."""
+        """[B,d+1,d+1] poses -> positions of the goal nodes [B,2,d]  (_pose_goal; a position goal: p_e alone)."""
         T = np.asarray(T_goals, dtype=float)
         d = self.dim
         if d == 3:
@@ -349,7 +419,8 @@ class BatchProblem:
                 T = T[:, None]                           # one end effector
             p = T[:, :, :3, 3]
             q = p + T[:, :, :3, 2] * self.graph.axis_length
-            return np.stack((p, q), axis=2).reshape(T.shape[0], -1, 3)   # p_e, q_e per end effector
+            gp = np.stack((p, q), axis=2).reshape(T.shape[0], -1, 3)   # p_e, q_e per end effector
+            return gp if len(self._goal_keep) == gp.shape[1] else gp[:, self._goal_keep]
         if T.ndim == 3:
             T = T[:, None]                               # one end effector
         return np.stack([T[:, e_i, :2, 2] - (T[:, e_i, :2, 0] * dist if is_parent else 0.0)
@@ -477,7 +548,10 @@ class BatchProblem:
         from ..graphs.graph_planar import joint_variables_planar_batch
         if self.dim == 3:
             T = np.asarray(T_goals, dtype=float)
-            if T.ndim == 4:
+            if "position" in self.goal_kinds:      # T_final only for the end effectors whose goal is a pose
+                T = T if T.ndim == 4 else T[:, None]
+                T = {e: T[:, i] for i, e in enumerate(self.end_effectors) if self.goal_kinds[i] == "pose"} or None
+            elif T.ndim == 4:
                 T = {e: T[:, i] for i, e in enumerate(self.end_effectors)}
             return joint_variables_revolute_batch(self.graph, Y, T)
         return joint_variables_planar_batch(self.graph, Y)
@@ -486,6 +560,12 @@ class BatchProblem:
         """EE position / rotation error of FK(q) against the goals (the metric of
         experiments/simple_ik_examples/test_chain_2d_new.py:62-66)."""
         T_goals = np.asarray(T_goals, dtype=float)
+        if "position" in self.goal_kinds:      # a position goal has no rotation error: 0, and no part in the maximum
+            T4 = T_goals if T_goals.ndim == 4 else T_goals[:, None]
+            errs = [BatchProblem._pose_err(self.robot.fk_batch(q, int(e[1:])), T4[:, i], self.dim)
+                    for i, e in enumerate(self.end_effectors)]
+            rot = [r for (_, r), kind in zip(errs, self.goal_kinds) if kind == "pose"]
+            return np.max([e[0] for e in errs], axis=0), np.max(rot, axis=0) if rot else np.zeros(len(T4))
         if T_goals.ndim == 4:        # several end effectors: the worst of them
             errs = [BatchProblem._pose_err(self.robot.fk_batch(q, int(e[1:])), T_goals[:, i], self.dim)
                     for i, e in enumerate(self.end_effectors)]
@@ -518,7 +598,8 @@ class AnchoredProblem:
     add_spherical_obstacle).  The initial point is the robot graph's own (bound smoothing + MDS
     without obstacles) fitted to the world frame by its anchors."""
 
-    def __init__(self, graph, params=None, device=None, host_only=False, links=None, link_radius=0.0, link_hinges=False):
+    def __init__(self, graph, params=None, device=None, host_only=False, links=None, link_radius=0.0, link_hinges=False,
+                 goal="pose"):
         """host_only: derive the term set only (no device handles) -- what tests/test_host_layer.py
         compares with the reference's own edge construction (tests/golden/ur10_table_intended.npz).
 
@@ -536,6 +617,9 @@ class AnchoredProblem:
         from .. import _ffi
         if graph.dim != 3 or not graph.robot.is_chain:
             raise NotImplementedError("the fixed-anchor formulation covers 3-D chains")
+        if goal_kinds(goal, len(graph.robot.end_effectors)) != ("pose",):
+            # (q_n is a constant row of the goal there; with a position goal it would become a free node)
+            raise NotImplementedError("the fixed-anchor formulation takes pose goals: goal='position' is not supported")
         if not isinstance(link_hinges, (bool, np.bool_)):      # (before any device call)
             raise ValueError(f"link_hinges must be a bool, got {link_hinges!r}")
         if link_hinges and links is not None and len(links) == 0:
@@ -953,12 +1037,13 @@ def graph_fingerprint(graph):
     return h.hexdigest()
 
 
-def _problem_for(graph, use_limits=True, params=None, device=None):
+def _problem_for(graph, use_limits=True, params=None, device=None, goal="pose"):
+    kinds = goal_kinds(goal, len(graph.robot.end_effectors))
     key = (graph_fingerprint(graph), bool(use_limits),
-           None if not params else tuple(sorted(params.items())), None if device is None else str(device))
+           None if not params else tuple(sorted(params.items())), None if device is None else str(device), kinds)
     prob = _PROBLEM_CACHE.get(key)
     if prob is None:
-        prob = _PROBLEM_CACHE[key] = BatchProblem(graph, use_limits, params, device)
+        prob = _PROBLEM_CACHE[key] = BatchProblem(graph, use_limits, params, device, goal=kinds)
         while len(_PROBLEM_CACHE) > _PROBLEM_CACHE_MAX:
             _PROBLEM_CACHE.popitem(last=False)
     else:
@@ -1052,9 +1137,16 @@ def anchored_retry_better(new, old, pos_tol=0.01, rot_tol=0.01, clear_tol=1e-4):
 
 
 def solve_batch(graph, T_goals, use_limits=True, params=None, device=None, Y_init=None, q_init=None,
-                retries=0, retry_seed=0, pos_tol=0.01, rot_tol=0.01):
+                retries=0, retry_seed=0, pos_tol=0.01, rot_tol=0.01, goal="pose"):
     """Batched solve_with_riemannian.  T_goals: [B,d+1,d+1] array or list of poses.
     Returns (q [B,n], Y [B,N,k], info dict of arrays).
+
+    goal: "pose" (the default), "position", or a sequence of those with one entry per robot.end_effectors.  A position
+    goal pins the end effector's point and leaves its orientation free -- the reference's graph.from_pos({p_e: xyz}) with
+    joint_variables(G_sol) without T_final; info["rot_err"] leaves such an end effector out (0.0 when all are
+    positions), so the restart rule's rot_tol never fires for it.  When every end effector is a position, T_goals holds
+    positions [B, d] or [B, n_ee, d] (pose arrays are accepted too: only their translations are read); with mixed kinds
+    it holds poses as for "pose".  q_init, retries and every other argument combine with it unchanged.
 
     q_init (warm start): joint angles [B,n] or [n] (one seed for all goals), columns in
     robot.q_to_array order.  Each solve then starts from the realization of its seed -- the
@@ -1071,6 +1163,8 @@ def solve_batch(graph, T_goals, use_limits=True, params=None, device=None, Y_ini
     cannot be combined with retries, and a graph off the device pipeline has none: ValueError."""
     T = np.stack([as_matrix(t) for t in T_goals]) if not isinstance(T_goals, np.ndarray) \
         else np.asarray(T_goals, dtype=float)
+    if not (isinstance(goal, str) and goal == "pose"):
+        T = goal_poses(T, goal_kinds(goal, len(graph.robot.end_effectors)), graph.dim)
     if q_init is not None:
         if Y_init is not None:
             raise ValueError("pass Y_init or q_init, not both")
@@ -1082,7 +1176,7 @@ def solve_batch(graph, T_goals, use_limits=True, params=None, device=None, Y_ini
         check_retry_args(retries, pos_tol, rot_tol, graph.robot.limits_arrays(), graph.robot.n)
         retry = dict(retries=retries, retry_seed=retry_seed, pos_tol=pos_tol, rot_tol=rot_tol,
                      q_limits=graph.robot.limits_arrays())
-    prob = _problem_for(graph, use_limits, params, device)
+    prob = _problem_for(graph, use_limits, params, device, goal)
     if retries and not prob.device_pipeline:
         raise ValueError("retries > 0 needs the device pipeline, which this graph is outside of")
     tpl = prob.template
@@ -1119,7 +1213,7 @@ def solve_batch(graph, T_goals, use_limits=True, params=None, device=None, Y_ini
 
 
 def solve_trajectory(graph, T_path, q_start, use_limits=True, params=None, device=None, return_Y=False,
-                     retries=0, retry_seed=0, pos_tol=0.01, rot_tol=0.01):
+                     retries=0, retry_seed=0, pos_tol=0.01, rot_tol=0.01, goal="pose"):
     """Path tracking: B paths of L waypoints, each waypoint a warm-started solve_batch.
 
     T_path: [B, L, d+1, d+1] goal poses ([B, L, n_ee, 4, 4] for robots with several end effectors).
@@ -1129,6 +1223,8 @@ def solve_trajectory(graph, T_path, q_start, use_limits=True, params=None, devic
     waypoint whose solve fails (stop != 0, or a large pos_err) still seeds the next one; by default
     there is no retry -- check info["stop"] / info["pos_err"].
 
+    goal: as in solve_batch; with position goals T_path holds positions [B, L, d] or [B, L, n_ee, d].
+
     retries > 0: every waypoint is a solve_batch(..., q_init=previous angles, retries=...) -- a failed
     waypoint is solved again from random joint angles (see solve_batch), and a rescued waypoint seeds
     the next one with its rescued angles.  Each waypoint then synchronises the stream once per attempt.
@@ -1137,6 +1233,8 @@ def solve_trajectory(graph, T_path, q_start, use_limits=True, params=None, devic
     iterations, inner_iterations, stop, f(x), gradnorm, pos_err, rot_err, attempt, plus solve_time
     (seconds, whole path)."""
     T = np.asarray(T_path, dtype=float)
+    if not (isinstance(goal, str) and goal == "pose"):
+        T = goal_poses(T, goal_kinds(goal, len(graph.robot.end_effectors)), graph.dim, lead=2)
     B, L = T.shape[:2]
     n = graph.robot.n
     q0 = _seed_angles(q_start, B, n, "q_start")
@@ -1144,12 +1242,12 @@ def solve_trajectory(graph, T_path, q_start, use_limits=True, params=None, devic
     if retries:
         _, q_lo, q_hi = check_retry_args(retries, pos_tol, rot_tol, graph.robot.limits_arrays(), n)
         retry = dict(retries=retries, retry_seed=retry_seed, pos_tol=pos_tol, rot_tol=rot_tol)
-    prob = _problem_for(graph, use_limits, params, device)
+    prob = _problem_for(graph, use_limits, params, device, goal)
     if not prob.device_pipeline:
         qs, Ys, infos, dt = [], [], [], 0.0
         q_prev = q0
         for l in range(L):
-            q_prev, Y, info = solve_batch(graph, T[:, l], use_limits, params, device, q_init=q_prev, **retry)
+            q_prev, Y, info = solve_batch(graph, T[:, l], use_limits, params, device, q_init=q_prev, goal=goal, **retry)
             qs.append(q_prev)
             Ys.append(Y)
             infos.append(info)

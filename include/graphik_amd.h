@@ -302,7 +302,8 @@ typedef struct {
   int32_t x_index, y_index;  /* base anchor nodes "x", "y"                                 */
   double axis_length;        /* graph.axis_length                                          */
   int32_t goal_node0;        /* node pinned at the goal position (p_n)                     */
-  int32_t goal_node1;        /* q_n (k=3: p_n + axis_length*z) or p_{n-1} (k=2: p_n - len*x) */
+  int32_t goal_node1;        /* q_n (k=3: p_n + axis_length*z) or p_{n-1} (k=2: p_n - len*x);
+                                -1 for a position goal (position_goal_mask bit 0)            */
   double goal_len;           /* axis_length (k=3) / DIST(p_{n-1}, p_n) (k=2)               */
   const double *base_lower;  /* [N*N] LOWER of the goal-independent edges, NaN = no edge   */
   const double *base_upper;  /* [N*N] UPPER                                                */
@@ -326,12 +327,29 @@ typedef struct {
   int32_t n_ee;
   const int32_t *ee_goal_nodes; /* [2 * n_ee] graph nodes pinned by goal pose e: (p_e, q_e); k = 2: (the end effector,
                                    its parent -- or -1 where an earlier end effector's pose pins that parent already:
-                                   graph_planar.py:136-145 keeps the first)                      */
+                                   graph_planar.py:136-145 keeps the first); either k: (p_e, -1) for a position goal
+                                   (position_goal_mask)                                          */
   const int32_t *ee_path;       /* [n_ee][n + 1] joint numbers from the root to end effector e
                                    (path[0] = 0), -1 padded; a parent's number precedes its
                                    children's nowhere assumed                                   */
   int32_t n_goal_pairs;         /* goal-node pairs of DIFFERENT end effectors tied by an edge   */
-  int32_t reserved1;
+  int32_t position_goal_mask;   /* bit e: end effector e has a POSITION goal -- the reference's graph.from_pos({p_e: xyz})
+                                   (graph_base.py:146-165): p_e alone is pinned and its orientation is free.  0: every goal
+                                   is a pose, the behaviour of every earlier build (the field was reserved1, zero).
+                                   Where bit e is set:
+                                   - goal_node1 (a chain) or ee_goal_nodes[2 e + 1] must be -1: the odd slot is inert, no
+                                     term_src may name it, and base_lower / base_upper / term_static hold what the graph
+                                     holds between q_e (k = 2: the parent) and the anchors;
+                                   - of pose e in d_T_goal only the translation column is read (pack a point into an
+                                     identity-rotation pose);
+                                   - no T_final correction applies to it (graph_revolute.py:314-316 runs only for an end
+                                     effector with a T_final entry): bit e of last_link_along_z must be clear, and the last
+                                     angle of such an arm is what the point formula gives, as in the reference;
+                                   - gik_recover_batch's rot_err excludes it: 0.0 when every goal is a position, else the
+                                     worst of the pose end effectors.  The restart rule rot_err > rot_tol then never fires.
+                                   gik_pipeline_attach refuses a set bit with a non-negative odd slot, a bit at or beyond
+                                   n_ee, and a bit that last_link_along_z also has.  Every gik_anchored_* entry that takes a
+                                   `base` template refuses one with a non-zero mask.                              */
   const int32_t *goal_pair_a, *goal_pair_b;  /* [n_goal_pairs] slots into ee_goal_nodes; term_src
                                    of such a term = 2 n_ee n_anchor + pair; of an anchor<->goal
                                    term = anchor_slot * 2 n_ee + goal slot                     */
@@ -339,6 +357,17 @@ typedef struct {
 } gik_pipeline_desc;
 
 int gik_pipeline_attach(gik_template *t, const gik_pipeline_desc *desc);
+
+/* k = 3, after gik_pipeline_attach and before the first gik_recover_batch, optional.  End effector `ee` has a position goal
+ * and its last link lies along its joint's z axis.  joint_variables' point formula (graph_revolute.py:308) takes the last
+ * angle from atan2 of qs_0 = (T0[pred]^-1 T0[ee] trans_z(axis_length)).trans against the recovered point, and with no
+ * T_final to correct it (:314-316) that is the answer.  For such a link the x, y of qs_0 are round-off residues of the frame
+ * product: their DIRECTION alone decides the angle, and it depends on the order of the operations that formed them.  (x, y)
+ * replaces what gik_recover_batch forms from T0, so that a caller who mirrors a host implementation -- the Python layer
+ * passes the residues of the reference's own operations -- gets that implementation's angle.  Any angle is a solution: the
+ * joint turns about an axis through the goal point.  Errors: no pipeline, k = 2, ee without a position goal, a non-finite
+ * value.                                                                                                              */
+int gik_pipeline_set_point_axis(gik_template *t, int ee, double x, double y);
 
 /* goal poses [B][n_ee][(k+1)^2] (row-major homogeneous matrices) -> per-term targets [B][T] and the
  * initial point [B][N*k] (from_pose + bound_smoothing + generate_initialization).
