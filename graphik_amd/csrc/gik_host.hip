@@ -806,7 +806,11 @@ static int plan_and_acquire_prepare(gik_template *t, const gik_pipeline_desc *d,
     f.env_waves = atoi(e);
   }
   f.n_cu = t->f.n_cu;
-  t->prep.sweeps = d->jacobi_sweeps > 0 ? d->jacobi_sweeps : 10;
+  // The Jacobi loops stop by themselves, after the first sweep without a rotation; this is the bound behind that rule.
+  // A bound of 10 was the reason to stop on full-rank Gram matrices from about 50 rows on (planar chains: 11 sweeps at
+  // N = 47, up to 13 at N = 66 and 15 at N = 123 .. 128, where the spectrum was left at 2e-9 instead of 1e-14 and
+  // Gram(Y_init) at 3e-6; NOTEBOOK 36).  Graphs of one wavefront keep 10, and with it every bit of their results.
+  t->prep.sweeps = d->jacobi_sweeps > 0 ? d->jacobi_sweeps : (t->N <= 32 ? 10 : 30);
   t->prep.plan = plan_prepare(f, prep_occupancy);
   if (!t->prep.plan.block()) return 0;
   void *ws = nullptr;

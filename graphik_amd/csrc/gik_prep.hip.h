@@ -407,14 +407,15 @@ __global__ void __launch_bounds__(WAVE) prep_wave_kernel(PrepArgs a)
       sg[lane] = sgn;
     }
     __builtin_amdgcn_wave_barrier();
-    // Y = X * W, W = the K eigenvectors of largest eigenvalue
-    if (lane < N * K) {
-      const int r = lane / K, dcol = lane - r * K;
+    // Y = X * W, W = the K eigenvectors of largest eigenvalue (N K entries: up to 96 on a 3-D graph of 32 nodes, more
+    // than the wavefront has lanes)
+    for (int t = lane; t < N * K; t += WAVE) {
+      const int r = t / K, dcol = t - r * K;
       int col = 0;
       for (int c = 0; c < N; ++c) col = (rk[c] == dcol) ? c : col;
       double s = 0.0;
       for (int c = 0; c < N; ++c) s += X[r * N + c] * V[c * N + col];
-      a.Y_init[(size_t)b * N * K + lane] = s * sg[col];
+      a.Y_init[(size_t)b * N * K + t] = s * sg[col];
     }
     __builtin_amdgcn_wave_barrier();
   }

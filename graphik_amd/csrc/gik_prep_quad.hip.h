@@ -22,9 +22,10 @@
 // graph_base.py:146-180, dgp.py:124-147; bound smoothing, dgp.py:192-231;
 // RiemannianSolver.generate_initialization, riemannian_solver.py:67-75), with differences that stay at
 // round-off: the per-goal sums of the Jacobi threshold and of the Householder reflectors are taken in
-// another order; the K x K Jacobi of linear_projection runs the round-robin schedule of the LARGEST K
-// among the wavefront's four goals (a goal with a smaller K sees extra pairs whose off-diagonal entry
-// is exactly zero: skipped); and where the matrix size is a compile-time constant a round forms
+// another order; the K x K Jacobi of linear_projection runs the round-robin schedule of quad_schedule_size(K),
+// a size that depends on the goal alone (up to 8: the schedule of 8, where a smaller K sees extra pairs whose
+// off-diagonal entry is exactly zero: skipped), so that a goal's result does not depend on the goals it
+// shares the wavefront with; and where the matrix size is a compile-time constant a round forms
 // (J^T A) J from rows held in registers instead of J^T (A J) in LDS (quad_jacobi_fixed).  Three
 // matrices per goal instead of five (each phase overwrites what the previous one no longer needs):
 // 19.6 KB of LDS per wavefront at N = 13, eight wavefronts per CU.
@@ -62,28 +63,6 @@ __device__ inline unsigned lds_addr(const void *p) {
 // load and a separate wait -- nothing can be scheduled into the middle of a single statement.
 template <int N>
 __device__ inline void lds_read_row(double (&v)[N], const double *row);      // written out below for the sizes in use
-template <>
-__device__ inline void lds_read_row<6>(double (&v)[6], const double *row) {
-  const unsigned a = lds_addr(row);
-  asm volatile(
-      "ds_read_b64 %0, %6\n\tds_read_b64 %1, %6 offset:8\n\tds_read_b64 %2, %6 offset:16\n\t"
-      "ds_read_b64 %3, %6 offset:24\n\tds_read_b64 %4, %6 offset:32\n\tds_read_b64 %5, %6 offset:40\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5])
-      : "v"(a)
-      : "memory");
-}
-template <>
-__device__ inline void lds_read_row<7>(double (&v)[7], const double *row) {
-  const unsigned a = lds_addr(row);
-  asm volatile(
-      "ds_read_b64 %0, %7\n\tds_read_b64 %1, %7 offset:8\n\tds_read_b64 %2, %7 offset:16\n\t"
-      "ds_read_b64 %3, %7 offset:24\n\tds_read_b64 %4, %7 offset:32\n\tds_read_b64 %5, %7 offset:40\n\t"
-      "ds_read_b64 %6, %7 offset:48\n\ts_waitcnt lgkmcnt(0)"
-      : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(v[6])
-      : "v"(a)
-      : "memory");
-}
 template <>
 __device__ inline void lds_read_row<8>(double (&v)[8], const double *row) {
   const unsigned a = lds_addr(row);
@@ -148,15 +127,24 @@ __device__ inline bool quad_rotation(double app, double aqq, double apq, double 
   return true;
 }
 
+// Size of the K x K Jacobi's schedule for a scatter matrix that is non-zero in its leading Kc x Kc block, of an N-node
+// graph: a function of the goal alone.  Blocks up to 8 share the schedule of 8 (the round-robin of 7 IS that of 8 with
+// index 7 as the bye; the usual chain has K = 6 .. 8), larger ones take their own.
+__device__ inline int quad_schedule_size(int Kc, int N) {
+  const int n2 = Kc > 1 ? Kc : 2;
+  return n2 <= 8 ? (N < 8 ? N : 8) : n2;
+}
+
 // Cyclic Jacobi (see jacobi_lds) on the leading n x n block of this goal's symmetric matrix A (row
 // stride S), V accumulates the eigenvectors as columns.  n is wave-uniform; a goal whose matrix is
 // non-zero in a smaller leading block only passes the larger n as well.  Lane `i` is row / column i
-// of its goal; cs: (c, s) of this goal's pairs.
-__device__ inline void quad_jacobi(double *A, double *V, int S, int n, int sweeps, double2 *cs, int slot, int i) {
+// of its goal; cs: (c, s) of this goal's pairs.  on (the same in a goal's 16 lanes): this goal takes part -- the
+// matrices of the others are neither read nor written.
+__device__ inline void quad_jacobi(double *A, double *V, int S, int n, int sweeps, double2 *cs, int slot, int i, bool on = true) {
   const int ne = n + (n & 1), np = ne / 2;
   __builtin_amdgcn_wave_barrier();
   double fro = 0.0;
-  if (i < n)
+  if (on && i < n)
     for (int j = 0; j < n; ++j) fro = fma(A[i * S + j], A[i * S + j], fro);
   const double thr = 1e-16 * sqrt(goal_sum(fro));
   const unsigned long long mine = 0xFFFFull << (16 * slot);
@@ -164,7 +152,7 @@ __device__ inline void quad_jacobi(double *A, double *V, int S, int n, int sweep
     bool rotated = false;
     for (int r = 0; r < ne - 1; ++r) {
       bool sig = false;
-      if (i < np) {
+      if (on && i < np) {
         const int p = quad_rr_p(ne, r, i), q = quad_rr_q(ne, r, i);
         double c = 1.0, s = 0.0;
         if (q < n) sig = quad_rotation(A[p * S + p], A[q * S + q], A[p * S + q], thr, c, s);
@@ -180,7 +168,7 @@ __device__ inline void quad_jacobi(double *A, double *V, int S, int n, int sweep
         if (q >= n) continue;
         const double2 r2 = cs[m];
         const double c = r2.x, s = r2.y;
-        if (i < n) {
+        if (on && i < n) {
           const double ap = A[i * S + p], aq = A[i * S + q];
           A[i * S + p] = c * ap - s * aq;
           A[i * S + q] = s * ap + c * aq;
@@ -195,7 +183,7 @@ __device__ inline void quad_jacobi(double *A, double *V, int S, int n, int sweep
         if (q >= n) continue;
         const double2 r2 = cs[m];
         const double c = r2.x, s = r2.y;
-        if (i < n) {
+        if (on && i < n) {
           const double ap = A[p * S + i], aq = A[q * S + i];
           A[p * S + i] = c * ap - s * aq;
           A[q * S + i] = s * ap + c * aq;
@@ -219,13 +207,14 @@ __device__ inline void quad_jacobi(double *A, double *V, int S, int n, int sweep
 //   own' = c own -/+ s partner -> own' J in registers,
 // 19 KB of LDS traffic per wavefront and round.  A' = (J^T A) J where jacobi_lds forms J^T (A J): the same
 // matrix up to round-off.
+// on: as in quad_jacobi (a goal that sits the call out holds zeros for rows, rotates nothing and stores nothing).
 template <int N, int S>
-__device__ inline void quad_jacobi_fixed(double *A, double *V, int sweeps, double2 *cs, int slot, int i) {   // (i by value: made opaque per round)
+__device__ inline void quad_jacobi_fixed(double *A, double *V, int sweeps, double2 *cs, int slot, int i, bool on = true) {   // (i by value: made opaque per round)
   constexpr int NE = N + (N & 1), NP = NE / 2;
   __builtin_amdgcn_wave_barrier();
   double ar[N], vr[N];
   {
-    const bool row = i < N;
+    const bool row = on && i < N;
     const double *Ar = A + i * S;
 #pragma unroll
     for (int j = 0; j < N; ++j) {
@@ -250,7 +239,7 @@ __device__ inline void quad_jacobi_fixed(double *A, double *V, int sweeps, doubl
       //  addresses -- is then recomputed there, a dozen integer instructions, instead of being hoisted out of the
       //  sweep loop for all 13 rounds at once and spilled: round 4's build kept 123 VGPRs in scratch)
       asm volatile("" : "+v"(i));
-      const bool row = i < N;
+      const bool row = on && i < N;
       double *Ar = A + i * S;
       int j = 2 * r - i;
       j = j < 0 ? j + (NE - 1) : j;
@@ -307,7 +296,7 @@ __device__ inline void quad_jacobi_fixed(double *A, double *V, int sweeps, doubl
     if (__builtin_amdgcn_ballot_w64(rotated) == 0ull) break;
   }
   __builtin_amdgcn_wave_barrier();
-  if (i < N) {
+  if (on && i < N) {
     double *Ar = A + i * S, *Vr = V + i * S;
 #pragma unroll
     for (int j = 0; j < N; ++j) {
@@ -538,17 +527,24 @@ __global__ void __launch_bounds__(WAVE, 2) prep_quad_kernel(PrepArgs a) {
 #ifdef GIK_DEV
     if (a.stop_phase == 8) continue;
 #endif
-    // the largest block among the four goals sets the schedule (wave-uniform)
-    const int n2 = Kc > 1 ? Kc : 2;
-    const int n2max = max(max(__builtin_amdgcn_readlane(n2, 0), __builtin_amdgcn_readlane(n2, 16)),
-                          max(__builtin_amdgcn_readlane(n2, 32), __builtin_amdgcn_readlane(n2, 48)));
-    if constexpr (NT >= 8) {   // (the usual block sizes of a chain: K = 6..8)
-      if (n2max == 7) quad_jacobi_fixed<7, (NT | 1)>(A, V, a.sweeps, cs, slot, i);
-      else if (n2max == 8) quad_jacobi_fixed<8, (NT | 1)>(A, V, a.sweeps, cs, slot, i);
-      else if (n2max == 6) quad_jacobi_fixed<6, (NT | 1)>(A, V, a.sweeps, cs, slot, i);
-      else quad_jacobi(A, V, S, n2max, a.sweeps, cs, slot, i);
-    } else {
-      quad_jacobi(A, V, S, n2max, a.sweeps, cs, slot, i);
+    // The schedule of a goal's Jacobi follows from its own block size (quad_schedule_size), whatever the other three
+    // goals of the wavefront are: goals of equal schedule size run together, the others sit that pass out.  (Until the
+    // boundary tests of the prepare kernels the LARGEST block of the four set the schedule of all, and a goal's Y_init
+    // moved in its last bits with the column counts of its neighbours.)  The usual chain has K = 6 .. 8 throughout:
+    // one pass, on the unrolled schedule of 8.
+    const int ns = quad_schedule_size(Kc, N);
+    unsigned long long todo = ~0ull;      // lanes whose goal has not run (wave-uniform)
+#pragma unroll 1
+    while (todo != 0ull) {
+      const int n = __builtin_amdgcn_readlane(ns, (int)__builtin_ctzll(todo));
+      const bool on = ns == n;
+      todo &= ~__builtin_amdgcn_ballot_w64(on);
+      if constexpr (NT >= 8) {
+        if (n == 8) quad_jacobi_fixed<8, (NT | 1)>(A, V, a.sweeps, cs, slot, i, on);
+        else quad_jacobi(A, V, S, n, a.sweeps, cs, slot, i, on);
+      } else {
+        quad_jacobi(A, V, S, n, a.sweeps, cs, slot, i, on);
+      }
     }
 #ifdef GIK_DEV
     if (a.stop_phase == 9) continue;

@@ -317,7 +317,7 @@ typedef struct {
   const int32_t *term_src;   /* [T] -1: term_static[t]; else anchor_slot*2 + goal_slot     */
   const double *term_static; /* [T] psi_L / psi_U / goal-independent squared distances     */
   int32_t last_link_along_z; /* the T_final correction of graph_revolute.py:314-316 applies */
-  int32_t jacobi_sweeps;     /* 0 = default (10)                                           */
+  int32_t jacobi_sweeps;     /* 0 = default (10; graphs of more than 32 nodes: 30)          */
   int32_t force_block_prepare; /* 1: workgroup-per-goal prepare kernel even for small graphs
                                 (tests; GIK_PREP_FORCE_BLOCK is read once, at attach)         */
   /* Robots with several end effectors (k = 3 trees, robot_base.py:29-41; round 6: planar trees,

@@ -328,6 +328,8 @@ REFUSED = {
 }
 
 # instantiations that the existing suite reaches (anchored formulation, prepare kernels): named, not re-tested
+_PREP_HOST = "tests/test_prepare_boundaries_gpu.py::test_prepare_against_the_host"
+_PREP_MULTI = "tests/test_prepare_boundaries_gpu.py::test_a_workgroup_that_takes_more_than_one_goal"
 EXISTING = {
     "rtr_wave_kernel<3,9,W_THETA1|W_ANCH>": ["tests/test_hip_gpu.py::test_anchored_trajectory_against_oracle",
                                              "tests/test_hip_gpu.py::test_anchored_pipeline"],
@@ -343,11 +345,15 @@ EXISTING = {
     "rtr_wave_scene_kernel<3,20,W_THETA1|W_ANCH>": ["tests/test_anchored_scenes_gpu.py::test_template_level_bit_identity",
                                                     "tests/test_anchored_scenes_gpu.py::test_a_wave_changes_scene_between_problems"],
     "rtr_wave_scene_kernel<3,9,W_THETA1|W_ANCH|W_LINKS>": ["tests/test_anchored_scenes_gpu.py::test_ur10_three_scenes"],
-    "prep_block_kernel<true>": ["tests/test_hip_gpu.py::test_block_prepare_kernel_equals_wave_kernel"],
-    "prep_block_kernel<false>": ["tests/test_hip_gpu.py::test_block_prepare_kernel_equals_wave_kernel"],
-    "prep_block_kernel<false,PREP_BIGN>": ["tests/test_hip_gpu.py::test_scene_with_200_spheres_beyond_128_nodes"],
-    "prep_quad_kernel<13>": ["tests/test_hip_gpu.py::test_quad_prepare_kernel_against_wave_kernel"],
-    "prep_quad_kernel<0>": ["tests/test_hip_gpu.py::test_planar_chains_of_other_sizes_on_the_quad_kernels"],
+    # the prepare kernels: against the host restatement at every size boundary (the case table of tests/synth_prepare.py,
+    # tests/test_prepare_boundaries_host.py keeps it complete), and the older kernel-against-kernel comparisons
+    "prep_block_kernel<true>": [_PREP_HOST, _PREP_MULTI, "tests/test_hip_gpu.py::test_block_prepare_kernel_equals_wave_kernel"],
+    "prep_block_kernel<false>": [_PREP_HOST, _PREP_MULTI, "tests/test_hip_gpu.py::test_block_prepare_kernel_equals_wave_kernel"],
+    "prep_block_kernel<false,PREP_BIGN>": [_PREP_HOST, _PREP_MULTI,
+                                           "tests/test_hip_gpu.py::test_scene_with_200_spheres_beyond_128_nodes"],
+    "prep_quad_kernel<13>": [_PREP_HOST, _PREP_MULTI, "tests/test_hip_gpu.py::test_quad_prepare_kernel_against_wave_kernel"],
+    "prep_quad_kernel<0>": [_PREP_HOST, _PREP_MULTI,
+                            "tests/test_hip_gpu.py::test_planar_chains_of_other_sizes_on_the_quad_kernels"],
 }
 # compiled but outside this matrix on purpose, with the reason (none at present: the 20-slot anchored kernels are
 # reached through tests/synth_anchored.py's case table)

@@ -948,7 +948,7 @@ def test_quad_prepare_kernel_against_wave_kernel(torch_cuda, monkeypatch, name):
     """Four goals per wavefront (prep_quad_kernel, the default for graphs of at most 16 nodes) against one
     (prep_wave_kernel, GIK_NO_PREP_QUAD read at attach): targets bit for bit (no inner product in them), MDS
     column counts equal, initial points to round-off (the Jacobi threshold and the Householder reflectors sum in
-    another order; the K x K Jacobi runs the schedule of the wavefront's largest K) -- for batch sizes that leave
+    another order; the K x K Jacobi runs the schedule of 8 for blocks up to 8) -- for batch sizes that leave
     slots of the last wavefront empty, and the solves that start from either end on the same iteration."""
     from graphik_amd.solvers.riemannian_solver import BatchProblem
     robot, graph = make_graph(name)

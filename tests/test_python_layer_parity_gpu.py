@@ -10,7 +10,9 @@ by key (sha256 over dtype, shape and bytes; not hashed: time, solve_time, inner_
 with "_") and compared with tests/golden/python_layer_parent.json, which tools/python_layer_digest.py recorded on the
 MI355X from a checkout of the parent commit with this table.  The recording refuses a file in which a restart scenario
 improved no goal (attempt all zero) or a clearance scenario has no finite clearance; the test checks the same of the
-file it reads, so no scenario passes on a path that did nothing.
+file it reads, so no scenario passes on a path that did nothing.  (planar_cold was recorded again when prep_quad_kernel's
+K x K Jacobi schedule became a function of the goal alone, docs/NOTEBOOK.md 36: the floating-point arrays moved in their
+last bits, every count stayed; the entry says so.)
 
 Shapes: B = 5 goals (a multiple of nothing), trajectories of L = 3 waypoints for B = 4 paths.  Inputs: conftest.make_graph
 and the inputs of the anchored host tests (collision_input, tracking_input, TWIN_MAXITER, TWIN_SEED); fixed seeds."""
