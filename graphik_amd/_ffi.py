@@ -112,8 +112,9 @@ class AnchoredRetryOpts(C.Structure):
     _fields_ = RetryOpts._fields_ + [("clear_tol", C.c_double), ("spread", C.c_double)]
 
 
-CLEARANCE_NODES, CLEARANCE_LINKS = 0, 1
-CLEARANCE_MODES = {"nodes": CLEARANCE_NODES, "links": CLEARANCE_LINKS}
+CLEARANCE_NODES, CLEARANCE_LINKS, CLEARANCE_LINKS_SELF = 0, 1, 2
+CLEARANCE_MODES = {"nodes": CLEARANCE_NODES, "links": CLEARANCE_LINKS, "links+self": CLEARANCE_LINKS_SELF}
+SELF_MAX_PAIRS = 2016      # every pair of 64 links
 
 
 class LinkDesc(C.Structure):
@@ -156,6 +157,10 @@ SYMBOLS = {
     "gik_anchored_sweep_ws_bytes": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
     "gik_anchored_sweep_clearance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                                C.c_void_p, C.c_void_p]),
+    "gik_anchored_attach_self_pairs": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "gik_anchored_self_clearance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "gik_anchored_sweep_clearances": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]),
     "gik_anchored_ik_batch_seeded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] +
                                      7 * [C.c_void_p] + [C.c_void_p]),
     "gik_anchored_last_solve_ms": (C.c_double, [C.c_void_p]),

@@ -20,8 +20,12 @@
 //                           them), one thread per double; and the minimum over the samples, one thread per goal.
 //   anch_clearance_scene_kernel / anch_link_clearance_scene_kernel / scene_gather_kernel : the two clearance kernels with
 //                           the obstacle rows of a per-goal scene (gik_scene_set), and the scene ids of a compact batch.
-// anch_link_pair, anch_link_foot (the pair function of the solve kernel's link hinges), anch_sweep_interp and
-// anch_sweep_min are __host__ __device__, so that a host program can walk them.
+//   anch_self_clearance_kernel : link against link: min over the attached pairs (l, m) of the distance between the two
+//                           SEGMENTS less both radii (anch_self_pair), optionally merged into the value already there.
+//                           Up to 16 pairs: four goals per wavefront, lane 16 g + p on pair p of goal slot g, the
+//                           minimum and the NaN flag per 16-lane row.  More: one wavefront per goal, as the link kernel.
+// anch_link_pair, anch_self_pair, anch_link_foot (the pair function of the solve kernel's link hinges), anch_sweep_interp
+// and anch_sweep_min are __host__ __device__, so that a host program can walk them.
 // Plain kernels, defined where GIK_DEFINE_ANCH_SEED_KERNELS is set (gik_k_anch_seed.hip); every other unit that includes
 // this header -- the two host units, which launch them -- sees prototypes.
 #pragma once
@@ -36,6 +40,8 @@ namespace gik {
 
 constexpr int ANCH_SCATTER_NT = 256;
 constexpr int ANCH_MAXLINK = 64;   // links of gik_anchored_attach_links
+constexpr int ANCH_MAXSELF = ANCH_MAXLINK * (ANCH_MAXLINK - 1) / 2;   // pairs of gik_anchored_attach_self_pairs: 2016
+constexpr int ANCH_SELF_ROW = 16;  // anch_self_clearance_kernel: up to this many pairs, a goal per 16-lane row
 
 struct AnchClearArgs {
   const double *Y_full;      // [B][full_N*3]
@@ -52,6 +58,16 @@ struct AnchLinkArgs {
   const double *link_rho;    // [n_link] capsule radius of a link, >= 0
   double *clearance;         // [B]
   int B, full_N, n_link, n_obs;
+};
+
+struct AnchSelfArgs {
+  const double *Y_full;      // [B][full_N*3]
+  const int *link_a, *link_b;   // [n_link] as AnchLinkArgs
+  const double *link_rho;    // [n_link]
+  const int *pair_l, *pair_m;   // [n_pair] the two links of a pair, indices into the link arrays
+  double *clearance;         // [B]
+  int B, full_N, n_pair;
+  int merge;                 // 0: clearance[b] = the minimum; 1: the NaN-propagating minimum of it and clearance[b]
 };
 
 struct AnchSweepInterpArgs {
@@ -85,6 +101,56 @@ __host__ __device__ inline double anch_link_pair(const double *a, const double *
   const double vx = ux - t * dx, vy = uy - t * dy, vz = uz - t * dz;
   const double v = sqrt(vx * vx + vy * vy + vz * vz) - sqrt(s[3]) - rho;
   return L2 != L2 ? __builtin_nan("") : v;
+}
+
+// clearance of one (link, link) pair: the distance between the segments a1 -> b1 and a2 -> b2 less the two radii.  The
+// closest points are a1 + s d1 and a2 + t d2: s from the unconstrained minimum clamped to [0, 1], t from s, and where t
+// leaves [0, 1] it is clamped and s taken again for that end.  A zero-length link is its point (a == 0: s = 0 and t is
+// the foot of that point; e == 0: t = 0 and s is; both: the distance of the two points); parallel links (den == 0) take s = 0 and the
+// clamps; crossing links give -rho1 - rho2.  Every product and sum is rounded on its own (AnchoredProblem.self_clearance
+// is the same operations in numpy).  A NaN in any end comes out as NaN: every coordinate enters a or e.
+__host__ __device__ inline double anch_self_pair(const double *a1, const double *b1, const double *a2, const double *b2,
+                                                 double rho1, double rho2) {
+#pragma clang fp contract(off)
+  const double d1x = b1[0] - a1[0], d1y = b1[1] - a1[1], d1z = b1[2] - a1[2];
+  const double d2x = b2[0] - a2[0], d2y = b2[1] - a2[1], d2z = b2[2] - a2[2];
+  const double rx = a1[0] - a2[0], ry = a1[1] - a2[1], rz = a1[2] - a2[2];
+  const double a = d1x * d1x + d1y * d1y + d1z * d1z;
+  const double e = d2x * d2x + d2y * d2y + d2z * d2z;
+  const double f = d2x * rx + d2y * ry + d2z * rz;
+  const double c = d1x * rx + d1y * ry + d1z * rz;
+  const double b = d1x * d2x + d1y * d2y + d1z * d2z;
+  const double den = a * e - b * b;
+  double s = 0.0;
+  if (a > 0.0 && den > 0.0) {
+    s = (b * f - c * e) / den;
+    s = s > 0.0 ? s : 0.0;
+    s = s < 1.0 ? s : 1.0;
+  }
+  // (a zero-length second link has no t to solve for: it takes the t = 0 branch, whose s is the foot of its point)
+  double t = e > 0.0 ? (b * s + f) / e : -1.0;
+  if (t < 0.0) {
+    t = 0.0;
+    s = 0.0;
+    if (a > 0.0) {
+      s = -c / a;
+      s = s > 0.0 ? s : 0.0;
+      s = s < 1.0 ? s : 1.0;
+    }
+  } else if (t > 1.0) {
+    t = 1.0;
+    s = 0.0;
+    if (a > 0.0) {
+      s = (b - c) / a;
+      s = s > 0.0 ? s : 0.0;
+      s = s < 1.0 ? s : 1.0;
+    }
+  }
+  const double vx = (a1[0] + s * d1x) - (a2[0] + t * d2x);
+  const double vy = (a1[1] + s * d1y) - (a2[1] + t * d2y);
+  const double vz = (a1[2] + s * d1z) - (a2[2] + t * d2z);
+  const double v = sqrt(vx * vx + vy * vy + vz * vz) - rho1 - rho2;
+  return (a != a || e != e) ? __builtin_nan("") : v;
 }
 
 // The (link, sphere) pair as the solve kernel's link hinge reads it (WaveCtx<.., LINKS>, gik_wave.hip.h): the foot
@@ -200,6 +266,62 @@ __global__ void __launch_bounds__(WAVE) anch_link_clearance_kernel(AnchLinkArgs 
     for (int off = WAVE / 2; off > 0; off >>= 1) m = fmin(m, __shfl_xor(m, off));
     if (__any(nan)) m = __builtin_nan("");
     if (lane == 0) a.clearance[b] = m;
+  }
+}
+#endif
+
+// pair p of one goal's point matrix (anch_self_clearance_kernel)
+__device__ inline double anch_self_value(const AnchSelfArgs &a, const double *Y, int p) {
+  const int l = a.pair_l[p], m = a.pair_m[p];
+  return anch_self_pair(Y + a.link_a[l] * 3, Y + a.link_b[l] * 3, Y + a.link_a[m] * 3, Y + a.link_b[m] * 3, a.link_rho[l],
+                        a.link_rho[m]);
+}
+
+// what anch_self_clearance_kernel stores for a goal: its minimum m, or with merge the NaN-propagating minimum of m and
+// the value already there (the link clearance of the same point: clearance_mode = GIK_CLEARANCE_LINKS_SELF)
+__device__ inline void anch_self_store(const AnchSelfArgs &a, int b, double m) {
+  if (a.merge) {
+    const double old = a.clearance[b];
+    m = (old != old || m != m) ? __builtin_nan("") : (old < m ? old : m);
+  }
+  a.clearance[b] = m;
+}
+
+__global__ void __launch_bounds__(WAVE) anch_self_clearance_kernel(AnchSelfArgs a)
+#ifndef GIK_DEFINE_ANCH_SEED_KERNELS
+    ;
+#else
+{
+  const int lane = threadIdx.x;
+  if (a.n_pair <= ANCH_SELF_ROW) {
+    // four goals per wavefront: lane 16 g + p takes pair p of goal slot g; the trip count is the wavefront's, so every
+    // lane reaches the exchanges; a slot beyond B computes and writes nothing
+    const int g = lane / ANCH_SELF_ROW, p = lane % ANCH_SELF_ROW;
+    for (int b0 = blockIdx.x * 4; b0 < a.B; b0 += gridDim.x * 4) {
+      const int b = b0 + g;
+      double v = __builtin_huge_val();
+      if (b < a.B && p < a.n_pair) v = anch_self_value(a, a.Y_full + (size_t)b * a.full_N * 3, p);
+      const bool nan = v != v;
+      double m = fmin(__builtin_huge_val(), v);
+      for (int off = ANCH_SELF_ROW / 2; off > 0; off >>= 1) m = fmin(m, __shfl_xor(m, off, ANCH_SELF_ROW));
+      // the NaN flag of this goal's row alone: a NaN goal must not poison its three neighbours
+      if ((__ballot(nan) >> (g * ANCH_SELF_ROW)) & 0xffffull) m = __builtin_nan("");
+      if (p == 0 && b < a.B) anch_self_store(a, b, m);
+    }
+    return;
+  }
+  for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
+    const double *Y = a.Y_full + (size_t)b * a.full_N * 3;
+    double m = __builtin_huge_val();
+    bool nan = false;
+    for (int p = lane; p < a.n_pair; p += WAVE) {
+      const double v = anch_self_value(a, Y, p);
+      nan |= v != v;
+      m = fmin(m, v);
+    }
+    for (int off = WAVE / 2; off > 0; off >>= 1) m = fmin(m, __shfl_xor(m, off));
+    if (__any(nan)) m = __builtin_nan("");
+    if (lane == 0) anch_self_store(a, b, m);
   }
 }
 #endif

@@ -42,6 +42,9 @@ struct gik_template {
   double *d_link_rho = nullptr;                   // [n_link]
   int n_link = -1;
   bool link_hinges = false;                       // ... attached with hinges = 1: the solve kernels are the LINKS builds
+  // the link pairs of gik_anchored_attach_self_pairs (anch_self_clearance_kernel); n_self < 0: none attached
+  int *d_self_l = nullptr, *d_self_m = nullptr;   // [n_self] indices into the link arrays
+  int n_self = -1;
   std::vector<int> h_free_full, h_anchor_full;    // host copies of d_free_full / d_anchor_full and of the slot table:
   std::vector<uint32_t> h_slot_meta;              // what the attach call builds the per-node link records from
   double axis_length = 1.0;

@@ -609,6 +609,31 @@ int gik_anchored_attach_links(gik_template *anch, const gik_link_desc *d) {
   return 0;
 }
 
+// the link pairs of the self clearance: indices into the attached link set, once, after the links
+int gik_anchored_attach_self_pairs(gik_template *anch, int n_pair, const int32_t *pair_l, const int32_t *pair_m) {
+  using namespace gik;
+  const std::string e("gik_anchored_attach_self_pairs");
+  if (!anch) return fail(e + ": null argument");
+  if (!anch->anchored) return fail(e + ": the handle must be a fixed-anchor template (gik_template_create_anchored)");
+  if (anch->n_link < 0) return fail(e + ": no links attached (gik_anchored_attach_links comes first)");
+  if (anch->n_self >= 0) return fail(e + ": self pairs already attached");
+  if (n_pair < 0 || n_pair > ANCH_MAXSELF) return fail(e + ": n_pair must be within 0 .. 2016");
+  if (n_pair > 0 && (!pair_l || !pair_m)) return fail(e + ": null pair array");
+  for (int p = 0; p < n_pair; ++p) {
+    if (pair_l[p] < 0 || pair_l[p] >= anch->n_link || pair_m[p] < 0 || pair_m[p] >= anch->n_link)
+      return fail(e + ": pair " + std::to_string(p) + " names a link outside [0, n_link)");
+    if (pair_l[p] == pair_m[p]) return fail(e + ": pair " + std::to_string(p) + " names one link twice");
+  }
+  bool ok = true;
+  int *pl = const_cast<int *>(upload(anch, pair_l, (size_t)n_pair, ok));
+  int *pm = const_cast<int *>(upload(anch, pair_m, (size_t)n_pair, ok));
+  if (!ok) return fail(e + ": device upload failed");
+  anch->d_self_l = pl;
+  anch->d_self_m = pm;
+  anch->n_self = n_pair;
+  return 0;
+}
+
 void gik_template_destroy(gik_template *t) {
   if (!t) return;
   if (t->d_slot_meta) (void)hipFree(t->d_slot_meta);

@@ -166,7 +166,7 @@ int gik_ik_batch_retry(const gik_template *t, const double *d_T_goal, const doub
 // ---- the fixed-anchor (obstacle) solve on the robot graph's pipeline -------------------------------------------------
 // Every solve entry -- cold, seeded, with scenes, and each attempt of the restart loop -- refuses what it has always
 // refused, under its own name, and then queues its work through anchored_attempt, the one place that writes the launch
-// sequence.  The four clearance exports are anchored_clearance_entry with two booleans; clearance_mode_refusal is the mode
+// sequence.  The four obstacle clearance exports are anchored_clearance_entry with two booleans; clearance_mode_refusal is the mode
 // check of the scene entry and the restart entries.  The helpers stand in order of use.  The layouts of the caller-owned
 // workspaces are gik_plan.h's; the wrappers here read their integers off the handles.
 
@@ -262,6 +262,39 @@ static int anchored_link_clearance_launch(const gik_template *anch, const double
   return 0;
 }
 
+// link against link (gik_anchored_attach_self_pairs; gik_anch_seed.hip.h): up to 16 pairs four goals share a wavefront.
+// merge: the minimum with what d_clearance holds, the link clearance of the same points queued before it on the stream.
+static int anchored_self_clearance_launch(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance,
+                                          bool merge, void *stream) {
+  using namespace gik;
+  AnchSelfArgs c;
+  c.Y_full = d_Y_full;
+  c.link_a = anch->d_link_a;
+  c.link_b = anch->d_link_b;
+  c.link_rho = anch->d_link_rho;
+  c.pair_l = anch->d_self_l;
+  c.pair_m = anch->d_self_m;
+  c.clearance = d_clearance;
+  c.B = B;
+  c.full_N = anch->full_N;
+  c.n_pair = anch->n_self;
+  c.merge = merge ? 1 : 0;
+  const int waves = c.n_pair <= ANCH_SELF_ROW ? (B + 3) / 4 : B;
+  hipLaunchKernelGGL(anch_self_clearance_kernel, dim3(std::min(waves, anch->f.n_cu * 32)), dim3(WAVE), 0, (hipStream_t)stream, c);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// the clearance of one clearance_mode (checked: clearance_mode_refusal) of B point matrices.  GIK_CLEARANCE_LINKS_SELF:
+// the link launch, then the self kernel merging into its output -- the self clearance does not depend on the scene.
+static int anchored_mode_clearance_launch(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance, int mode,
+                                          void *stream, const gik_scene_set *scenes) {
+  if (mode == GIK_CLEARANCE_NODES) return anchored_clearance_launch(anch, d_Y_full, B, d_clearance, stream, scenes);
+  const int rc = anchored_link_clearance_launch(anch, d_Y_full, B, d_clearance, stream, scenes);
+  if (rc || mode == GIK_CLEARANCE_LINKS) return rc;
+  return anchored_self_clearance_launch(anch, d_Y_full, B, d_clearance, true, stream);
+}
+
 // the start point from joint-configuration seeds (gik_anch_seed.hip.h): seed_kernel on the robot graph into the workspace,
 // then the row gather + goal anchors
 static int anchored_seed_launch(const gik_template *anch, const gik_template *base, const double *d_T_goal,
@@ -281,11 +314,11 @@ static int anchored_seed_launch(const gik_template *anch, const gik_template *ba
 // One anchored solve on checked arguments, B > 0: what every solve entry and every restart queues.  The start point, cold
 // (d_q_init null: the robot graph's prepare, fitted to the anchors) or seeded; the solve between the event pair of
 // gik_anchored_last_solve_ms; the gather into d_Y_full; the recovery; and, where d_clearance is given, the clearance of the
-// answer: of the masked nodes, or with link_clear of whole links.  scenes: a checked scene set for the solve and the
+// answer in the call's clearance_mode (`mode`: nodes, whole links, or links and self pairs).  scenes: a checked scene set for the solve and the
 // clearance, or null: the template's own obstacles.
 static int anchored_attempt(const gik_template *anch, const gik_template *base, const double *d_T_goal, const double *d_q_init,
                             int B, const gik_scene_set *scenes, double *d_ws, double *d_Y_full, gik_stats *d_stats, double *d_q,
-                            double *d_pos_err, double *d_rot_err, double *d_clearance, bool link_clear, void *stream) {
+                            double *d_pos_err, double *d_rot_err, double *d_clearance, int mode, void *stream) {
   using namespace gik;
   const AnchWs w = anch_ws(anch, base, B, d_ws);
   AnchGlueArgs g;
@@ -321,8 +354,7 @@ static int anchored_attempt(const gik_template *anch, const gik_template *base, 
   HIP_OK(hipGetLastError());
   rc = gik_recover_batch(base, g.Y_full_out, g.T_goal, g.B, d_q, d_pos_err, d_rot_err, stream);
   if (rc || !d_clearance) return rc;
-  return link_clear ? anchored_link_clearance_launch(anch, g.Y_full_out, g.B, d_clearance, stream, scenes)
-                    : anchored_clearance_launch(anch, g.Y_full_out, g.B, d_clearance, stream, scenes);
+  return anchored_mode_clearance_launch(anch, g.Y_full_out, g.B, d_clearance, mode, stream, scenes);
 }
 
 int gik_anchored_ik_batch(const gik_template *anch, const gik_template *base, const double *d_T_goal, int B,
@@ -334,7 +366,7 @@ int gik_anchored_ik_batch(const gik_template *anch, const gik_template *base, co
   if (B == 0) return 0;
   if (!d_T_goal || !d_ws || !d_Y_full || !d_stats || !d_q || !d_pos_err || !d_rot_err) return fail("null buffer");
   return anchored_attempt(anch, base, d_T_goal, nullptr, B, nullptr, d_ws, d_Y_full, d_stats, d_q, d_pos_err, d_rot_err, nullptr,
-                          false, stream);
+                          GIK_CLEARANCE_NODES, stream);
 }
 
 // what the seeded anchored calls refuse, before anything is queued
@@ -365,14 +397,19 @@ int gik_anchored_ik_batch_seeded(const gik_template *anch, const gik_template *b
   if (!d_T_goal || !d_ws || !d_Y_full || !d_stats || !d_q || !d_pos_err || !d_rot_err)
     return gik::fail("gik_anchored_ik_batch_seeded: null buffer");
   return anchored_attempt(anch, base, d_T_goal, d_q_init, B, nullptr, d_ws, d_Y_full, d_stats, d_q, d_pos_err, d_rot_err,
-                          d_clearance, false, stream);
+                          d_clearance, GIK_CLEARANCE_NODES, stream);
 }
 
 // what a call that takes a clearance_mode refuses about it, under the entry's name e
 static int clearance_mode_refusal(const std::string &e, const gik_template *anch, int clearance_mode) {
   using gik::fail;
-  if (clearance_mode != GIK_CLEARANCE_NODES && clearance_mode != GIK_CLEARANCE_LINKS)
-    return fail(e + ": clearance_mode must be GIK_CLEARANCE_NODES (0) or GIK_CLEARANCE_LINKS (1)");
+  // (GIK_CLEARANCE_LINKS_SELF is a value only where self pairs are attached: on every other template the call is
+  // refused in the words it has always been refused in)
+  const bool has_self = anch->n_self >= 0;
+  if (clearance_mode != GIK_CLEARANCE_NODES && clearance_mode != GIK_CLEARANCE_LINKS &&
+      !(has_self && clearance_mode == GIK_CLEARANCE_LINKS_SELF))
+    return fail(e + ": clearance_mode must be GIK_CLEARANCE_NODES (0) or GIK_CLEARANCE_LINKS (1)" +
+                (has_self ? " or GIK_CLEARANCE_LINKS_SELF (2)" : ""));
   if (clearance_mode == GIK_CLEARANCE_LINKS && anch->n_link < 0)
     return fail(e + ": clearance_mode = links, but no links attached (gik_anchored_attach_links)");
   return 0;
@@ -394,7 +431,7 @@ int gik_anchored_ik_batch_scenes(const gik_template *anch, const gik_template *b
   if (B == 0) return 0;
   if (!d_T_goal || !d_ws || !d_Y_full || !d_stats || !d_q || !d_pos_err || !d_rot_err) return fail(e + ": null buffer");
   return anchored_attempt(anch, base, d_T_goal, d_q_init, B, scenes, d_ws, d_Y_full, d_stats, d_q, d_pos_err, d_rot_err,
-                          d_clearance, clearance_mode == GIK_CLEARANCE_LINKS, stream);
+                          d_clearance, clearance_mode, stream);
 }
 
 // ---- the clearance of an answer: of the masked nodes or of whole links, against the template's obstacles or per-goal scenes ----
@@ -431,6 +468,20 @@ int gik_anchored_link_clearance_scenes(const gik_template *anch, const double *d
   return anchored_clearance_entry("gik_anchored_link_clearance_scenes", anch, true, true, scenes, d_Y_full, B, d_clearance, stream);
 }
 
+// link against link: the pairs of gik_anchored_attach_self_pairs (none: +infinity, as the kernel leaves it)
+int gik_anchored_self_clearance(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance, void *stream) {
+  using gik::fail;
+  const std::string e("gik_anchored_self_clearance");
+  if (!anch || B < 0) return fail(e + ": bad argument");
+  if (!anch->anchored) return fail(e + ": the handle must be a fixed-anchor template (gik_template_create_anchored)");
+  if (anch->n_link < 0) return fail(e + ": no links attached (gik_anchored_attach_links)");
+  if (anch->n_self < 0) return fail(e + ": no self pairs attached (gik_anchored_attach_self_pairs)");
+  if (refuse_capture("gik_anchored_self_clearance", stream)) return -1;
+  if (B == 0) return 0;
+  if (!d_Y_full || !d_clearance) return fail(e + ": null buffer");
+  return anchored_self_clearance_launch(anch, d_Y_full, B, d_clearance, false, stream);
+}
+
 // ---- the sweep of the link clearance between two configurations (gik_anch_seed.hip.h) -----------
 // the caller-owned workspace of gik_anchored_sweep_clearance over d_ws (gik_plan.h), or with a null d_ws its size
 static gik::AnchSweepWs anch_sweep_ws(const gik_template *anch, const gik_template *base, int B, int S, double *d_ws) {
@@ -444,18 +495,24 @@ size_t gik_anchored_sweep_ws_bytes(const gik_template *anch, const gik_template 
   return anch_sweep_ws(anch, base, B, samples, nullptr).doubles * sizeof(double);
 }
 
-int gik_anchored_sweep_clearance(const gik_template *anch, const gik_template *base, const double *d_q_a,
-                                 const double *d_q_b, int B, int samples, double *d_ws, double *d_clearance, void *stream) {
+// gik_anchored_sweep_clearance (d_link_out is its d_clearance) and gik_anchored_sweep_clearances (two_outputs: either may
+// be null): one interpolate launch, one realization, then per output the clearance of all M configurations into the one
+// [S+1][B] array and its minimum over the samples.
+static int anchored_sweep_impl(const char *entry, bool two_outputs, const gik_template *anch, const gik_template *base,
+                               const double *d_q_a, const double *d_q_b, int B, int samples, double *d_ws, double *d_link_out,
+                               double *d_self_out, void *stream) {
   using namespace gik;
-  const std::string e("gik_anchored_sweep_clearance");
+  const std::string e(entry);
   if (!anch || !base || B < 0) return fail(e + ": bad argument");
   if (const std::string why = anchored_pair_fault(anch, base, PAIR_3D | PAIR_SEEDABLE); !why.empty()) return fail(e + ": " + why);
   if (anch->n_link < 0) return fail(e + ": no links attached (gik_anchored_attach_links)");
   if (samples < 1) return fail(e + ": samples must be at least 1");
   if ((size_t)B * ((size_t)samples + 1) > (size_t)INT_MAX) return fail(e + ": B (samples + 1) must fit an int");
-  if (refuse_capture("gik_anchored_sweep_clearance", stream)) return -1;
+  if (two_outputs && !d_link_out && !d_self_out) return fail(e + ": both outputs are null (d_link_out, d_self_out: one at least)");
+  if (d_self_out && anch->n_self < 0) return fail(e + ": d_self_out given, but no self pairs attached (gik_anchored_attach_self_pairs)");
+  if (refuse_capture(entry, stream)) return -1;
   if (B == 0) return 0;
-  if (!d_q_a || !d_q_b || !d_ws || !d_clearance) return fail(e + ": null buffer");
+  if (!d_q_a || !d_q_b || !d_ws || (!two_outputs && !d_link_out)) return fail(e + ": null buffer");
   const AnchSweepWs w = anch_sweep_ws(anch, base, B, samples, d_ws);
   const int M = B * (samples + 1);
   AnchSweepInterpArgs ia;
@@ -476,17 +533,35 @@ int gik_anchored_sweep_clearance(const gik_template *anch, const gik_template *b
   // the realization of every sample: seed_kernel's joint-frame walk on the robot graph (its targets go unread)
   int rc = gik_seed_batch(base, w.T, w.q, M, w.targets, w.Y, stream);
   if (rc) return rc;
-  rc = anchored_link_clearance_launch(anch, w.Y, M, w.cl, stream);
-  if (rc) return rc;
-  AnchSweepMinArgs ma;
-  ma.cl = w.cl;
-  ma.clearance = d_clearance;
-  ma.B = B;
-  ma.S = samples;
-  hipLaunchKernelGGL(anch_sweep_min_kernel, dim3((B + ANCH_SCATTER_NT - 1) / ANCH_SCATTER_NT), dim3(ANCH_SCATTER_NT), 0,
-                     (hipStream_t)stream, ma);
-  HIP_OK(hipGetLastError());
+  for (int k = 0; k < 2; ++k) {      // (one stream: the second clearance overwrites w.cl behind the first minimum)
+    double *out = k == 0 ? d_link_out : d_self_out;
+    if (!out) continue;
+    rc = k == 0 ? anchored_link_clearance_launch(anch, w.Y, M, w.cl, stream)
+                : anchored_self_clearance_launch(anch, w.Y, M, w.cl, false, stream);
+    if (rc) return rc;
+    AnchSweepMinArgs ma;
+    ma.cl = w.cl;
+    ma.clearance = out;
+    ma.B = B;
+    ma.S = samples;
+    hipLaunchKernelGGL(anch_sweep_min_kernel, dim3((B + ANCH_SCATTER_NT - 1) / ANCH_SCATTER_NT), dim3(ANCH_SCATTER_NT), 0,
+                       (hipStream_t)stream, ma);
+    HIP_OK(hipGetLastError());
+  }
   return 0;
+}
+
+int gik_anchored_sweep_clearance(const gik_template *anch, const gik_template *base, const double *d_q_a,
+                                 const double *d_q_b, int B, int samples, double *d_ws, double *d_clearance, void *stream) {
+  return anchored_sweep_impl("gik_anchored_sweep_clearance", false, anch, base, d_q_a, d_q_b, B, samples, d_ws, d_clearance, nullptr,
+                             stream);
+}
+
+int gik_anchored_sweep_clearances(const gik_template *anch, const gik_template *base, const double *d_q_a,
+                                  const double *d_q_b, int B, int samples, double *d_ws, double *d_link_out,
+                                  double *d_self_out, void *stream) {
+  return anchored_sweep_impl("gik_anchored_sweep_clearances", true, anch, base, d_q_a, d_q_b, B, samples, d_ws, d_link_out, d_self_out,
+                             stream);
 }
 
 // ---- restarts in the anchored solve: the kernels of gik_retry.hip.h with a clearance in the rule -------------
@@ -561,7 +636,7 @@ static int anchored_retry_impl(const char *entry, const gik_template *anch, cons
   if (with_scenes && scene_refusal(entry, anch, scenes)) return -1;
   if (opts->retries < 0 || opts->retries > 63) return fail(e + ": retries must be within 0 .. 63");
   if (clearance_mode_refusal(e, anch, opts->clearance_mode)) return -1;
-  const bool links = opts->clearance_mode == GIK_CLEARANCE_LINKS;
+  const int mode = opts->clearance_mode;
   if ((d_q_init || opts->retries > 0) && !base->seed_ok)
     return fail(e + ": the base graph cannot be seeded on the device: " + base->seed_why);
   if (opts->retries > 0) {
@@ -591,9 +666,10 @@ static int anchored_retry_impl(const char *entry, const gik_template *anch, cons
     compact = *scenes;
     if (scenes->d_scene_id) compact.d_scene_id = w.ids;
   }
-  // link mode: the rule below is the same, the array it reads holds the clearance of whole links
+  // link modes: the rule below is the same, the array it reads holds the clearance of whole links, or the minimum of
+  // that and the self clearance
   const int rc = anchored_attempt(anch, base, d_T_goal, d_q_init, B, scenes, w.scratch, d_Y_full, d_stats, d_q, d_pos_err,
-                                  d_rot_err, d_clearance, links, stream);
+                                  d_rot_err, d_clearance, mode, stream);
   if (rc) return rc;
   const RetryTol tol = {opts->pos_tol, opts->rot_tol, opts->clear_tol};
   const RetrySelectArgs select = {d_stats, d_pos_err, d_rot_err, d_clearance, tol, w.idx, w.count, B};
@@ -608,7 +684,7 @@ static int anchored_retry_impl(const char *entry, const gik_template *anch, cons
       HIP_OK(hipGetLastError());
     }
     return anchored_attempt(anch, base, w.T, w.q_seed, count, scenes ? &compact : nullptr, w.scratch, w.Y, w.stats, w.q, w.pos_err,
-                            w.rot_err, w.clearance, links, stream);
+                            w.rot_err, w.clearance, mode, stream);
   });
 }
 

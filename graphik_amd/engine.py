@@ -115,13 +115,16 @@ def check_retry_args(retries, pos_tol, rot_tol, q_limits, n, clear_tol=None, ret
     return int(retries), lo, hi
 
 
-def check_clearance_mode(clearance_mode, has_links=True):
-    """clearance_mode of an anchored solve -> gik_anchored_retry_opts.clearance_mode (0 nodes, 1 links), checked on the
-    host before any device call: ValueError for another word, and for "links" where no links are attached."""
-    if clearance_mode not in _ffi.CLEARANCE_MODES:
-        raise ValueError(f"clearance_mode must be 'nodes' or 'links', got {clearance_mode!r}")
-    if clearance_mode == "links" and not has_links:
-        raise ValueError("clearance_mode='links' needs a link set: this problem was built without links")
+def check_clearance_mode(clearance_mode, has_links=True, has_self=True):
+    """clearance_mode of an anchored solve -> gik_anchored_retry_opts.clearance_mode (0 nodes, 1 links, 2 links+self),
+    checked on the host before any device call: ValueError for another word, for "links" where no links are attached and
+    for "links+self" where no self pairs are."""
+    if not isinstance(clearance_mode, str) or clearance_mode not in _ffi.CLEARANCE_MODES:
+        raise ValueError(f"clearance_mode must be 'nodes', 'links' or 'links+self', got {clearance_mode!r}")
+    if clearance_mode != "nodes" and not has_links:
+        raise ValueError(f"clearance_mode={clearance_mode!r} needs a link set: this problem was built without links")
+    if clearance_mode == "links+self" and not has_self:
+        raise ValueError("clearance_mode='links+self' needs self pairs: this problem was built without self_pairs")
     return _ffi.CLEARANCE_MODES[clearance_mode]
 
 
@@ -298,6 +301,7 @@ class Template:
         self._h = h
         self.n_link = None      # (attach_links)
         self.link_hinges = False
+        self.n_self = None      # (attach_self_pairs)
         self._read_info()
         deg = np.bincount(np.concatenate([self.term_i, self.term_j]), minlength=self.N).max()
         # compiled slot count of the wavefront variant the library chose (or the raw degree: workgroup / node-per-lane paths)
@@ -605,7 +609,7 @@ class Template:
                 _ffi.check(self.lib.gik_ik_batch_seeded(self._h, T.data_ptr(), q0.data_ptr(), B, *answer, self._stream()))
         return _result(out, (B, self.N, self.k), extras)
 
-    def _retry_buffers(self, out, B, nbytes, lo, hi):
+    def _retry_buffers(self, out, B, nbytes, lo, hi, limits=True):
         """The restart buffers of one call with retries > 0, taken from `out` where it carries them: ("attempt" [B] int32,
         "retry_ws" of at least nbytes -- what the call's gik_*retry_ws_bytes reported --, "q_lo", "q_hi" on the device);
         a missing one is allocated, or uploaded from the checked limits lo / hi."""
@@ -615,6 +619,8 @@ class Template:
         ws = out.get("retry_ws")
         if ws is None or ws.numel() * ws.element_size() < nbytes:
             ws = torch.empty(max((nbytes + 7) // 8, 1), dtype=torch.float64, device=self.device)
+        if not limits:      # (a call with retries = 0 draws no seeds)
+            return attempt, ws, None, None
         q_lo = out["q_lo"] if "q_lo" in out else _dev(lo, self.device)
         q_hi = out["q_hi"] if "q_hi" in out else _dev(hi, self.device)
         return attempt, ws, q_lo, q_hi
@@ -729,6 +735,53 @@ class Template:
         return self._clearance_of(self.lib.gik_anchored_link_clearance, self.lib.gik_anchored_link_clearance_scenes, Y_full,
                                   scenes, scene_id)
 
+    def attach_self_pairs(self, pair_l, pair_m):
+        """The link pairs of the self clearance (gik_anchored_attach_self_pairs), once, after attach_links: pair p is
+        links pair_l[p] and pair_m[p] of the attached set."""
+        assert self.anchored
+        l = np.ascontiguousarray(pair_l, dtype=np.int32).reshape(-1)
+        m = np.ascontiguousarray(pair_m, dtype=np.int32).reshape(-1)
+        if len(l) != len(m):
+            raise ValueError("pair_l and pair_m must have one entry per pair")
+        with torch.cuda.device(self.device):
+            _ffi.check(self.lib.gik_anchored_attach_self_pairs(self._h, len(l), l.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                               m.ctypes.data_as(C.POINTER(C.c_int32))))
+        self.n_self = len(l)
+
+    def anchored_self_clearance(self, Y_full):
+        """Full point matrices [B, full_N, 3] -> self clearance [B] on the device (gik_anchored_self_clearance): the
+        minimum over the attached link pairs of the distance between the two capsules; +inf without pairs."""
+        assert self.anchored
+        return self._clearance_of(self.lib.gik_anchored_self_clearance, None, Y_full)
+
+    def anchored_sweep_clearances(self, base, q_a, q_b, samples, link_out=None, self_out=None, ws=None, link=True, self_=True):
+        """anchored_sweep_clearance with two outputs from one realization of the samples (gik_anchored_sweep_clearances):
+        returns (link [B] or None, self [B] or None) -- link / self_ say which are wanted; link_out / self_out [B] and
+        `ws` may be handed in to reuse.  Sampled, not conservative."""
+        assert self.anchored and base.has_pipeline
+        if int(samples) != samples or samples < 1:
+            raise ValueError(f"samples must be an integer of at least 1, got {samples!r}")
+        qa, qb = _dev(q_a, self.device), _dev(q_b, self.device)
+        n = base.n_joints
+        if qa.dim() != 2 or qa.shape[1] != n or qa.shape != qb.shape:
+            raise ValueError(f"q_a and q_b must both have shape [B, {n}], got {list(qa.shape)} and {list(qb.shape)}")
+        qa, qb = qa.contiguous(), qb.contiguous()
+        B, S = qa.shape[0], int(samples)
+        outs = []
+        for want, out in ((link, link_out), (self_, self_out)):
+            if want and out is None:
+                out = torch.empty(B, dtype=torch.float64, device=self.device)
+            assert out is None or (out.is_contiguous() and out.numel() == B)
+            outs.append(out if want else None)
+        nbytes = int(self.lib.gik_anchored_sweep_ws_bytes(self._h, base._h, B, S))
+        if ws is None or ws.numel() * ws.element_size() < nbytes:
+            ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            _ffi.check(self.lib.gik_anchored_sweep_clearances(self._h, base._h, qa.data_ptr(), qb.data_ptr(), B, S, ws.data_ptr(),
+                                                              *(None if o is None else o.data_ptr() for o in outs),
+                                                              self._stream()))
+        return tuple(outs)
+
     def anchored_sweep_clearance(self, base, q_a, q_b, samples, out=None, ws=None):
         """Joint angles q_a, q_b [B,n] (device tensors or arrays) -> [B]: the minimum link clearance over the samples + 1
         configurations on the joint-space line from q_a to q_b (gik_anchored_sweep_clearance).  Sampled, not
@@ -774,15 +827,20 @@ class Template:
         `out` may carry "attempt" [B] int32, "retry_ws" (gik_anchored_retry_ws_bytes) and "q_lo" / "q_hi", and needs
         no "ws": the restart workspace holds that scratch.
 
-        clearance_mode: "nodes" (the joint points, gik_anchored_clearance) or "links" (whole links,
-        gik_anchored_link_clearance; needs attach_links): which clearance comes back and the restart rule reads.
+        clearance_mode: "nodes" (the joint points, gik_anchored_clearance), "links" (whole links,
+        gik_anchored_link_clearance; needs attach_links) or "links+self" (the minimum of that and
+        gik_anchored_self_clearance; needs attach_self_pairs): which clearance comes back and the restart rule reads.
+        "links+self" without retries or scenes is gik_anchored_ik_batch_retry with retries = 0 -- attempt 0 and the merged
+        clearance, nothing else -- on the restart workspace (`out` may carry "retry_ws").
 
         scenes (a SceneSet) with scene_id ([B] ints; optional with one scene): goal b is solved among the spheres of
         scene scene_id[b] instead of the template's own, and its clearance is measured against them
         (gik_anchored_ik_batch_scenes, gik_anchored_ik_batch_retry_scenes); everything else combines with it unchanged.
         scene_id_checked: scene_id is a row of an id array SceneSet.ids() has already checked (solve_trajectory)."""
         assert self.anchored and base.has_pipeline
-        mode = check_clearance_mode(clearance_mode, getattr(self, "n_link", None) is not None)
+        mode = check_clearance_mode(clearance_mode, getattr(self, "n_link", None) is not None,
+                                    getattr(self, "n_self", None) is not None)
+        merged = mode == _ffi.CLEARANCE_LINKS_SELF and clearance and not retries and scenes is None
         if retries:      # (the clearance always comes back then, whatever `clearance` says)
             retries, lo, hi = check_retry_args(retries, pos_tol, rot_tol, q_limits, base.n_joints, clear_tol=clear_tol,
                                                retry_spread=retry_spread, has_center=q_init is not None)
@@ -790,7 +848,7 @@ class Template:
         T, B = base._poses(T_goal)
         sc, ids = self._scene_desc(scenes, scene_id, B, scene_id_checked)
         if out is None:      # (with retries the restart workspace holds the scratch "ws")
-            out = self.alloc_anchored_buffers(base, B, clearance, ws=not retries)
+            out = self.alloc_anchored_buffers(base, B, clearance, ws=not (retries or merged))
         q0 = None if q_init is None else base._seed_angles(q_init, B)
         cl = None
         if clearance:
@@ -813,6 +871,15 @@ class Template:
                         self._h, base._h, T.data_ptr(), seed_ptr, B, C.byref(opts), C.byref(sc), ws.data_ptr(),
                         *answer, cl.data_ptr(), attempt.data_ptr(), self._stream()))
                 return _result(out, (B, self.full_N, 3), {"clearance": cl, "attempt": attempt, "_retry_ws": ws, "_scene_id": ids})
+            if merged:      # attempt 0 of the restart entry: the call, the link clearance, the self clearance merged into it
+                nbytes = self.anchored_retry_ws_bytes(base, B)
+                attempt, ws, _, _ = self._retry_buffers(out, B, nbytes, None, None, limits=False)
+                opts = _ffi.AnchoredRetryOpts(retries=0, clearance_mode=mode, pos_tol=float(pos_tol), rot_tol=float(rot_tol),
+                                              clear_tol=float(clear_tol))
+                _ffi.check(self.lib.gik_anchored_ik_batch_retry(
+                    self._h, base._h, T.data_ptr(), None if q0 is None else q0.data_ptr(), B, C.byref(opts), ws.data_ptr(),
+                    *answer, cl.data_ptr(), attempt.data_ptr(), self._stream()))
+                return _result(out, (B, self.full_N, 3), {"clearance": cl, "_retry_ws": ws, "_attempt": attempt})
             ws = out["ws"]
             assert ws.numel() >= int(self.lib.gik_anchored_ws_doubles(self._h, base._h, B))
             if sc is not None:      # one call: cold or seeded, the clearance of either mode behind it

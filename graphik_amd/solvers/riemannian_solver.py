@@ -599,7 +599,7 @@ class AnchoredProblem:
     without obstacles) fitted to the world frame by its anchors."""
 
     def __init__(self, graph, params=None, device=None, host_only=False, links=None, link_radius=0.0, link_hinges=False,
-                 goal="pose"):
+                 goal="pose", self_pairs=None):
         """host_only: derive the term set only (no device handles) -- what tests/test_host_layer.py
         compares with the reference's own edge construction (tests/golden/ur10_table_intended.npz).
 
@@ -611,7 +611,15 @@ class AnchoredProblem:
         the solve kernel also carries a hinge per (link, sphere) on the distance from the sphere's centre to the link's
         SEGMENT (gik_anchored_attach_links with hinges = 1; link_hinge_terms_host is the numpy mirror of the terms), so
         every solve, restart and tracked waypoint of this problem pushes whole links out of the spheres.  The node
-        hinges stay.  Needs a link set; chains on the 9-slot anchored kernel."""
+        hinges stay.  Needs a link set; chains on the 9-slot anchored kernel.
+        self_pairs: the link pairs whose mutual distance self_clearance / clearance_mode="links+self" measure (link
+        against link: the robot against itself).  None: nothing is attached.  "auto": every pair of the links that share
+        no end row, l < m in link order -- ten pairs for UR10's skeleton.  Or a sequence of (l, m) indices into
+        self.link_names; a pair of links that share a row is refused (its distance is 0 in every configuration).  The
+        links are capsules of link_radius around SEGMENTS: with thick capsules around the short wrist links "auto" reports
+        overlaps the real geometry does not have -- links 2 and 4 of UR10 are joined by a link of 11.5 cm, so at a radius
+        of 6 cm they touch in every configuration -- and such a robot wants an explicit list.  self.self_pairs is the
+        [P, 2] int array (None: not attached)."""
         import copy
         from ..utils.constants import OBSTACLE, ROBOT, TYPE, MAIN_PREFIX
         from .. import _ffi
@@ -629,6 +637,23 @@ class AnchoredProblem:
         obstacles = [n for n in graph.node_ids if graph.nodes[n].get(TYPE) == OBSTACLE]
         bare = copy.deepcopy(graph)
         bare.clear_obstacles()
+        if links is None:
+            links = [(f"p{i}", f"p{i + 1}") for i in range(self.robot.n)]
+        links = [tuple(l) for l in links]
+        for l in links:
+            if len(l) != 2 or any(name not in bare.node_ids for name in l):
+                raise ValueError(f"link {l!r}: a link is a pair of node names of the robot graph")
+        self.link_names = links
+        self.link_rows = np.array([[bare.index(a), bare.index(b)] for a, b in links], dtype=np.int32).reshape(-1, 2)
+        rho = np.asarray(link_radius, dtype=np.float64)
+        if rho.ndim == 0:
+            rho = np.full(len(links), float(rho))
+        if rho.shape != (len(links),):
+            raise ValueError(f"link_radius must be a scalar or have one entry per link ({len(links)}), got shape {list(rho.shape)}")
+        if not np.all(np.isfinite(rho) & (rho >= 0)):
+            raise ValueError("link_radius must be finite and at least 0")
+        self.link_radius = np.ascontiguousarray(rho)
+        self.self_pairs = self._check_self_pairs(self_pairs, self.link_rows)
         self.base = BatchProblem(bare, use_limits=True, params=params, device=device, host_only=host_only)
         if not host_only and not self.base.device_pipeline:
             raise NotImplementedError("robot graph beyond the device pipeline")
@@ -670,22 +695,6 @@ class AnchoredProblem:
         self.free_names = names
         self.free_terms = (ti, tj, tk, target)
         self.obs_mask = np.array(mask, dtype=np.int32)
-        if links is None:
-            links = [(f"p{i}", f"p{i + 1}") for i in range(self.robot.n)]
-        links = [tuple(l) for l in links]
-        for l in links:
-            if len(l) != 2 or any(name not in bare.node_ids for name in l):
-                raise ValueError(f"link {l!r}: a link is a pair of node names of the robot graph")
-        self.link_names = links
-        self.link_rows = np.array([[bare.index(a), bare.index(b)] for a, b in links], dtype=np.int32).reshape(-1, 2)
-        rho = np.asarray(link_radius, dtype=np.float64)
-        if rho.ndim == 0:
-            rho = np.full(len(links), float(rho))
-        if rho.shape != (len(links),):
-            raise ValueError(f"link_radius must be a scalar or have one entry per link ({len(links)}), got shape {list(rho.shape)}")
-        if not np.all(np.isfinite(rho) & (rho >= 0)):
-            raise ValueError("link_radius must be finite and at least 0")
-        self.link_radius = np.ascontiguousarray(rho)
         if host_only:
             self.template = None
             return
@@ -698,6 +707,40 @@ class AnchoredProblem:
                           anchor_full_index=anchors, axis_length=graph.axis_length))
         if len(links):
             self.template.attach_links(self.link_rows[:, 0], self.link_rows[:, 1], self.link_radius, hinges=self.link_hinges)
+        if self.self_pairs is not None:
+            self.template.attach_self_pairs(self.self_pairs[:, 0], self.self_pairs[:, 1])
+
+    @staticmethod
+    def _check_self_pairs(self_pairs, link_rows):
+        """self_pairs of __init__ -> [P, 2] int32 (None: none), checked on the host: ValueError for pairs without links, an
+        index outside the links, l == m, and an explicit pair whose links share an end row."""
+        if self_pairs is None:
+            return None
+        n_link = len(link_rows)
+        if n_link == 0:
+            raise ValueError("self_pairs needs a link set: links=[] attaches none")
+        shares = lambda l, m: bool(set(link_rows[l].tolist()) & set(link_rows[m].tolist()))      # noqa: E731
+        if isinstance(self_pairs, str):
+            if self_pairs != "auto":
+                raise ValueError(f"self_pairs must be None, 'auto' or a sequence of (l, m) link indices, got {self_pairs!r}")
+            pairs = [(l, m) for l in range(n_link) for m in range(l + 1, n_link) if not shares(l, m)]
+        else:
+            pairs = []
+            for pr in self_pairs:
+                if len(pr) != 2 or any(isinstance(i, (bool, np.bool_)) or int(i) != i for i in pr):
+                    raise ValueError(f"self pair {pr!r}: a pair is two link indices (l, m)")
+                l, m = int(pr[0]), int(pr[1])
+                if not (0 <= l < n_link and 0 <= m < n_link):
+                    raise ValueError(f"self pair {pr!r}: a link index is outside [0, {n_link})")
+                if l == m:
+                    raise ValueError(f"self pair {pr!r}: l == m names one link twice")
+                if shares(l, m):
+                    raise ValueError(f"self pair {pr!r}: the two links share an end row, their distance is 0 in every configuration")
+                pairs.append((l, m))
+        from .. import _ffi
+        if len(pairs) > _ffi.SELF_MAX_PAIRS:
+            raise ValueError(f"at most {_ffi.SELF_MAX_PAIRS} self pairs, got {len(pairs)}")
+        return np.array(pairs, dtype=np.int32).reshape(-1, 2)
 
     def goal_anchors(self, T_goals):
         """[B,4,4] -> [B, 2*3]: p_n, q_n world positions (graph_revolute.py:243-249)."""
@@ -737,7 +780,9 @@ class AnchoredProblem:
         link that crosses a sphere between two of them -- or "links": it is that of whole links
         (self.link_clearance; the problem must have links), with retries=0 too.  On a problem built with
         link_hinges=True the solve itself carries link hinges, so clearance_mode="links" then has hinges behind it: the
-        rule reads a clearance the cost acts on.
+        rule reads a clearance the cost acts on.  "links+self" (the problem must have self_pairs): the minimum of the
+        link clearance and self.self_clearance of the same points -- an answer whose links pass through each other has
+        failed the rule like one whose links pass through a sphere.  Nothing in the cost acts on the self clearance.
 
         retries > 0 (gik_anchored_ik_batch_retry): a goal that fails -- stop != 0, pos_err > pos_tol, rot_err >
         rot_tol or clearance < -clear_tol, so an answer on its goal with a joint point (clearance_mode="nodes") or
@@ -753,7 +798,7 @@ class AnchoredProblem:
         the whole batch, whatever the mix -- and "clearance" is measured against them.  Every other keyword combines with
         it.  Goal b's answer is, bit for bit, that of an AnchoredProblem built with scene scene_id[b]'s spheres."""
         T = np.asarray(T_goals, dtype=float)
-        check_clearance_mode(clearance_mode, len(self.link_names) > 0)
+        check_clearance_mode(clearance_mode, len(self.link_names) > 0, self.self_pairs is not None)
         retry = self._retry_args(retries, retry_seed, pos_tol, rot_tol, clear_tol, retry_spread, q_limits, q_init is not None)
         if q_init is not None:
             q_init = _seed_angles(q_init, T.shape[0], self.robot.n)
@@ -792,7 +837,8 @@ class AnchoredProblem:
         clearance over S + 1 joint-space samples between waypoint l-1's answer (q_start for waypoint 0) and waypoint
         l's (sweep_clearance(q[:, l-1], q[:, l], S)), one gik_anchored_sweep_clearance call per waypoint on the rows
         already on the device.  It is sampled, not conservative -- pick S from the joint step between waypoints --
-        and it is reported only: the restart rule does not read it.
+        and it is reported only: the restart rule does not read it.  With clearance_mode="links+self" the same call
+        (gik_anchored_sweep_clearances, one realization of the samples) also gives info["sweep_self_clearance"] [B, L].
 
         scenes (scene_set(...)) with scene_id: [B] ints -- a scene per path -- or [B, L] -- a scene per waypoint, which
         is a moving obstacle: waypoint l of path b is solved among the spheres of scene scene_id[b, l].  Optional with
@@ -804,7 +850,7 @@ class AnchoredProblem:
         T = np.asarray(T_path, dtype=float)
         B = T.shape[0]
         q0 = _seed_angles(q_start, B, self.robot.n, "q_start")
-        check_clearance_mode(clearance_mode, len(self.link_names) > 0)
+        check_clearance_mode(clearance_mode, len(self.link_names) > 0, self.self_pairs is not None)
         if sweep is not None and scenes is not None:
             raise ValueError("sweep= with scenes= is not supported: the sweep clearance measures the problem's own obstacles")
         ids = None      # [L, B] int32 on the device: waypoint-major, a row per step
@@ -827,10 +873,16 @@ class AnchoredProblem:
         if retry:      # (the restart workspace holds the anchored scratch too; with scenes, a compact batch's ids behind it)
             planes.append("attempt")
             nbytes = tpl.anchored_retry_ws_bytes(base, B, scenes=scenes is not None)
+        elif clearance_mode == "links+self" and scenes is None:      # (attempt 0 of the restart entry: its workspace)
+            shared["retry_ws"] = torch.empty(max((tpl.anchored_retry_ws_bytes(base, B) + 7) // 8, 1), dtype=torch.float64,
+                                             device=tpl.device)
         else:
             shared["ws"] = tpl.alloc_anchored_buffers(base, B)["ws"]
+        sweep_self = bool(sweep) and clearance_mode == "links+self"
         if sweep:      # one workspace for all waypoints
             planes.append("sweep_clearance")
+            if sweep_self:
+                planes.append("sweep_self_clearance")
             sweep_ws = torch.empty(max(int(tpl.lib.gik_anchored_sweep_ws_bytes(tpl._h, base._h, B, sweep)) // 8, 1),
                                    dtype=torch.float64, device=tpl.device)
 
@@ -840,7 +892,10 @@ class AnchoredProblem:
             l = next(waypoint)
             tpl.anchored_ik(base, T_l, q_init=q_prev, out=out, clearance=True, clearance_mode=clearance_mode, scenes=scenes,
                             scene_id=None if ids is None else ids[l], scene_id_checked=True, **retry)
-            if sweep:
+            if sweep_self:
+                tpl.anchored_sweep_clearances(base, q_prev, out["q"], sweep, link_out=out["sweep_clearance"],
+                                              self_out=out["sweep_self_clearance"], ws=sweep_ws)
+            elif sweep:
                 tpl.anchored_sweep_clearance(base, q_prev, out["q"], sweep, out=out["sweep_clearance"], ws=sweep_ws)
 
         return _track(tpl, T, q0, (tpl.full_N, 3), return_Y, planes, step, shared, nbytes, retry.get("q_limits"))
@@ -883,6 +938,65 @@ class AnchoredProblem:
             val = np.sqrt(dot(v, v)) - np.sqrt(r2)[None, None, :] - self.link_radius[None, :, None]
             val = np.where(np.isnan(L2), np.nan, val)
         return np.where(np.isnan(val).any(axis=(1, 2)), np.nan, np.where(np.isnan(val), np.inf, val).min(axis=(1, 2)))
+
+    def self_clearance(self, Y_full):
+        """min over the self pairs (l, m) of the distance between the capsules of links l and m per goal: the host mirror
+        of gik_anchored_self_clearance, the same operations in the same order.  Y_full [B, N_robot, 3] (numpy).  With
+        link l from a1 to b1 and link m from a2 to b2:  d1 = b1 - a1, d2 = b2 - a2, r = a1 - a2, a = d1.d1, e = d2.d2,
+        f = d2.r, c = d1.r, b = d1.d2, den = a e - b b;  s = clamp((b f - c e) / den, 0, 1) where a > 0 and den > 0, else
+        0;  t = (b s + f) / e where e > 0, else the t < 0 branch is taken;  where t < 0: t = 0, s = clamp(-c / a, 0, 1);  where t > 1: t = 1,
+        s = clamp((b - c) / a, 0, 1) (0 where a == 0);  v = (a1 + s d1) - (a2 + t d2), value = |v| - rho_l - rho_m.
+        >= 0: no two measured links overlap.  No pair: +inf; a NaN coordinate of a measured link's end: NaN for that
+        goal.  Reads self.link_rows, self.link_radius and self.self_pairs only."""
+        Y = np.asarray(Y_full, dtype=np.float64)
+        if Y.ndim == 2:
+            Y = Y[None]
+        B = Y.shape[0]
+        pairs = None if self.self_pairs is None else np.asarray(self.self_pairs, dtype=np.int64).reshape(-1, 2)
+        if pairs is None or len(pairs) == 0:
+            return np.full(B, np.inf)
+        rows, rho = np.asarray(self.link_rows), np.asarray(self.link_radius, dtype=np.float64)
+        l, m = pairs[:, 0], pairs[:, 1]
+        a1, b1 = Y[:, rows[l, 0]], Y[:, rows[l, 1]]                # [B, P, 3]
+        a2, b2 = Y[:, rows[m, 0]], Y[:, rows[m, 1]]
+        dot = lambda x, y: x[..., 0] * y[..., 0] + x[..., 1] * y[..., 1] + x[..., 2] * y[..., 2]   # noqa: E731
+
+        def clamp(x):
+            x = np.where(x > 0.0, x, 0.0)
+            return np.where(x < 1.0, x, 1.0)
+
+        with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+            d1, d2, r = b1 - a1, b2 - a2, a1 - a2
+            a, e, f, c, b = dot(d1, d1), dot(d2, d2), dot(d2, r), dot(d1, r), dot(d1, d2)
+            den = a * e - b * b
+            s = np.where((a > 0.0) & (den > 0.0), clamp((b * f - c * e) / den), 0.0)
+            t = np.where(e > 0.0, (b * s + f) / e, -1.0)          # (a zero-length second link: the t = 0 branch)
+            s_lo = np.where(a > 0.0, clamp(-c / a), 0.0)
+            s_hi = np.where(a > 0.0, clamp((b - c) / a), 0.0)
+            s = np.where(t < 0.0, s_lo, np.where(t > 1.0, s_hi, s))
+            t = np.where(t < 0.0, 0.0, np.where(t > 1.0, 1.0, t))
+            v = (a1 + s[..., None] * d1) - (a2 + t[..., None] * d2)
+            val = np.sqrt(dot(v, v)) - rho[l][None, :] - rho[m][None, :]
+            val = np.where(np.isnan(a) | np.isnan(e), np.nan, val)
+        return np.where(np.isnan(val).any(axis=1), np.nan, np.where(np.isnan(val), np.inf, val).min(axis=1))
+
+    def sweep_self_clearance_host(self, q_a, q_b, samples):
+        """The numpy mirror of sweep_self_clearance: self_clearance of BatchProblem.seed_points at every sample, the
+        minimum over the samples, NaN if any sample is NaN."""
+        qs = self.sweep_points(q_a, q_b, samples)
+        S1, B, n = qs.shape
+        cl = self.self_clearance(self.base.seed_points(qs.reshape(S1 * B, n))).reshape(S1, B)
+        return np.where(np.isnan(cl).any(axis=0), np.nan, np.where(np.isnan(cl), np.inf, cl).min(axis=0))
+
+    def sweep_self_clearance(self, q_a, q_b, samples):
+        """Joint angles q_a, q_b [B, n] -> device tensor [B]: the minimum self clearance over the samples + 1
+        configurations of sweep_clearance (gik_anchored_sweep_clearances; the problem must have self_pairs).  Like it, the
+        sweep is SAMPLED, NOT CONSERVATIVE: two links can meet and part between two samples.
+        sweep_self_clearance_host is the numpy mirror."""
+        S = self._check_samples(samples)
+        if self.self_pairs is None:
+            raise ValueError("sweep_self_clearance needs self pairs: this problem was built without self_pairs")
+        return self.template.anchored_sweep_clearances(self.base.template, q_a, q_b, S, link=False)[1]
 
     @staticmethod
     def link_foot_host(a, b, c):

@@ -628,13 +628,52 @@ int gik_anchored_sweep_clearance(const gik_template *anch, const gik_template *b
                                  const double *d_q_b, int B, int samples, double *d_ws, double *d_clearance,
                                  void *stream);
 
+/* ---- self-collision clearance: link against link (opt-in) ----------------------------------------
+ * The link clearance measures the links against the world.  Against the robot itself it sees nothing: an answer whose
+ * wrist passes through its own upper arm is clear of every sphere.  The self clearance is the same measure between two
+ * links of the attached set.
+ *
+ * gik_anchored_attach_self_pairs: the link pairs that are measured, attached once, AFTER the links: pair p is links
+ *   pair_l[p] and pair_m[p] of the set of gik_anchored_attach_links.  n_pair is within 0 .. 2016 (every pair of 64
+ *   links).  Refused with a message: a handle that is not a fixed-anchor template, no links attached, pairs already
+ *   attached, n_pair out of range, a null array with n_pair > 0, an index outside [0, n_link), l == m.  A pair of links
+ *   that SHARE AN END ROW is legal here: its distance is 0 and its value -link_radius[l] - link_radius[m], whatever the
+ *   configuration -- the caller leaves such pairs out (the Python layer refuses them).
+ * gik_anchored_self_clearance: d_clearance [B] = min over the attached pairs (l, m) of
+ *       d1 = b1 - a1, d2 = b2 - a2, r = a1 - a2      (a1 -> b1: link l; a2 -> b2: link m)
+ *       a = d1.d1, e = d2.d2, f = d2.r, c = d1.r, b = d1.d2, den = a e - b b
+ *       s = (a > 0 && den > 0) ? clamp((b f - c e) / den, 0, 1) : 0;      t = e > 0 ? (b s + f) / e : -1
+ *       t < 0:  t = 0, s = a > 0 ? clamp(-c / a, 0, 1) : 0;      t > 1:  t = 1, s = a > 0 ? clamp((b - c) / a, 0, 1) : 0
+ *       v = (a1 + s d1) - (a2 + t d2);      |v| - link_radius[l] - link_radius[m]
+ *   on d_Y_full [B][full_N*3]: the distance between the two capsules (a zero-length link is its point: e == 0 takes the t < 0 branch; parallel links
+ *   take s = 0 and the clamps; crossing links give -link_radius[l] - link_radius[m]).  >= 0: no two measured links
+ *   overlap.  No pair attached (n_pair == 0): +infinity.  A NaN coordinate of an end of a measured link: NaN for that goal
+ *   alone.  Up to 16 pairs four goals share a wavefront, beyond that a goal has its own.  Refused: what
+ *   gik_anchored_link_clearance refuses, and a template without self pairs attached.  B == 0 returns 0.
+ * gik_anchored_sweep_clearances: gik_anchored_sweep_clearance with two optional outputs over ONE interpolation and ONE
+ *   realization of the B (samples + 1) configurations: d_link_out [B] (what gik_anchored_sweep_clearance writes, bit for
+ *   bit) and d_self_out [B], the minimum over the samples of the self clearance.  LIKE IT, THE SWEEP IS SAMPLED, NOT
+ *   CONSERVATIVE: two links can meet and part between two samples; pick `samples` from the joint step as there.
+ *   d_ws: the same workspace, gik_anchored_sweep_ws_bytes.  Refused: what gik_anchored_sweep_clearance refuses, both
+ *   outputs null, d_self_out given on a template without self pairs attached.  B == 0 returns 0.
+ * clearance_mode = GIK_CLEARANCE_LINKS_SELF (below) puts min(link clearance, self clearance) behind the restart rule. */
+int gik_anchored_attach_self_pairs(gik_template *anch, int n_pair, const int32_t *pair_l, const int32_t *pair_m);
+int gik_anchored_self_clearance(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance,
+                                void *stream);
+int gik_anchored_sweep_clearances(const gik_template *anch, const gik_template *base, const double *d_q_a,
+                                  const double *d_q_b, int B, int samples, double *d_ws,
+                                  double *d_link_out /* may be NULL */, double *d_self_out /* may be NULL */,
+                                  void *stream);
+
 /* ---- restarts in the anchored solve, with a clearance rule (opt-in) -----------------------------
  * The restarts of gik_ik_batch_retry for the fixed-anchor formulation.  The obstacle hinges are soft cost terms: an
  * answer can stop on its gradient bar with the end effector on the goal and a joint point inside a sphere, which the rule
  * of the plain restarts calls a success.  Here the rule also reads the answer's clearance: that of the masked nodes
  * (gik_anchored_clearance; clearance_mode = GIK_CLEARANCE_NODES, the default), which does not see a link that crosses a
  * sphere between two nodes outside it, or that of whole links (gik_anchored_link_clearance; GIK_CLEARANCE_LINKS, for a
- * template with links attached).  The rule is the same for both; only the array it reads differs:
+ * template with links attached), or the minimum of that and the self clearance (gik_anchored_self_clearance;
+ * GIK_CLEARANCE_LINKS_SELF, for a template with self pairs attached).  The rule is the same for all; only the array it
+ * reads differs:
  *
  * failed(goal)  :=  stats.stop != 0  ||  !(pos_err <= pos_tol)  ||  !(rot_err <= rot_tol)  ||  !(clearance >= -clear_tol)
  *                   -- a NaN clearance counts as failed; +infinity (no obstacle, no masked node) never fails a goal.
@@ -672,7 +711,9 @@ int gik_anchored_sweep_clearance(const gik_template *anch, const gik_template *b
  *   d_attempt[g] = a > 0 holds exactly what gik_anchored_ik_batch_seeded returns for that goal alone from the seed of
  *   (seed, g, a).  With clearance_mode = GIK_CLEARANCE_LINKS every clearance of the call -- attempt 0's in d_clearance,
  *   each restart's on its compact batch, what the merge moves -- is gik_anchored_link_clearance of the same point
- *   matrices instead; select, score and merge are unchanged.  gik_anchored_last_solve_ms reports the solve kernel of the LAST attempt that ran.
+ *   matrices instead; select, score and merge are unchanged.  With GIK_CLEARANCE_LINKS_SELF it is the NaN-propagating
+ *   minimum of that and gik_anchored_self_clearance of the same point matrices: the link launch, then the self kernel
+ *   merging into its output on the same stream.  gik_anchored_last_solve_ms reports the solve kernel of the LAST attempt that ran.
  *   d_ws: caller-owned, gik_anchored_retry_ws_bytes(anch, base, B) bytes, 8-byte aligned: the scratch of one anchored
  *   call (attempt 0 and the restarts use it in turn) plus compact buffers sized for the case that every goal fails.
  *   It is needed with retries = 0 as well.
@@ -681,12 +722,14 @@ int gik_anchored_sweep_clearance(const gik_template *anch, const gik_template *b
  *   cannot be seeded, if d_q_init is given or retries > 0); retries outside 0 .. 63; a null d_clearance, d_attempt or
  *   workspace; and with retries > 0 null limits, a pos_tol, rot_tol or clear_tol that is not positive, a spread
  *   that is negative or NaN, spread > 0 with a null d_q_init (a cold batch has no centre); a clearance_mode that is
- *   neither 0 nor 1, and 1 on a template without links.  B == 0 returns 0.                                     */
+ *   neither 0 nor 1 (nor, on a template with self pairs attached, 2), and 1 on a template without links.
+ *   B == 0 returns 0.                                                                                          */
 #define GIK_CLEARANCE_NODES 0
 #define GIK_CLEARANCE_LINKS 1
+#define GIK_CLEARANCE_LINKS_SELF 2      /* min(link clearance, self clearance); a value only with self pairs attached */
 typedef struct {
   int32_t retries;        /* further attempts for goals that failed: 0 .. 63                              */
-  int32_t clearance_mode; /* GIK_CLEARANCE_NODES (0) or GIK_CLEARANCE_LINKS (1): which clearance the rule reads */
+  int32_t clearance_mode; /* GIK_CLEARANCE_NODES (0), _LINKS (1) or _LINKS_SELF (2): which clearance the rule reads */
   uint64_t seed;          /* of the generator; the same seed gives the same answers                       */
   double pos_tol;         /* a goal succeeds with stop == 0, pos_err <= pos_tol, rot_err <= rot_tol ...   */
   double rot_tol;
@@ -735,7 +778,8 @@ int gik_anchored_ik_batch_retry(const gik_template *anch, const gik_template *ba
  * gik_solve_batch_scenes: gik_solve_batch on an anchored template, with the scene builds of its solve kernel.
  * gik_anchored_ik_batch_scenes: gik_anchored_ik_batch (d_q_init NULL: the cold start) or gik_anchored_ik_batch_seeded with
  *   the scene solve and, where d_clearance is given, the scene clearance of the answer: that of the masked nodes
- *   (clearance_mode = GIK_CLEARANCE_NODES) or of whole links (GIK_CLEARANCE_LINKS; links attached).
+ *   (clearance_mode = GIK_CLEARANCE_NODES), of whole links (GIK_CLEARANCE_LINKS; links attached), or the minimum of
+ *   that and the self clearance, which no scene changes (GIK_CLEARANCE_LINKS_SELF; self pairs attached).
  * gik_anchored_clearance_scenes / gik_anchored_link_clearance_scenes: the two clearances with goal b measured against
  *   scene d_scene_id[b].  A scene without spheres: +infinity.
  * gik_anchored_ik_batch_retry_scenes: gik_anchored_ik_batch_retry with the scene carried through attempt 0, every
