@@ -55,6 +55,32 @@ __device__ inline bool plain_in_exec(double mv, double mp, double dHd, double e,
                  "v"(t2hi));
   return ok != 0ull;
 }
+// plain_in_exec with the model test taken where the two model values already are: in the lanes that hold value 6 of the
+// still distributed sums of this step (wd) and of the previous one (wd_prev), both vector operands of the first compare.
+// The two v_readlane of the model value and the v_mov_b64 that put the previous one into a vector register leave every
+// step.  The first compare leaves garbage in the lanes of the other seven values; the five behind it have wave-uniform
+// operands and keep or clear every lane alike, so the model lane's bit of the last mask is the conjunction.  No copy of
+// EXEC is taken: the block closes with EXEC = all 64 lanes, so the caller must be a whole wavefront with every lane
+// enabled -- the nine-slot lone wavefront's hot loop (rtr_solve_one, LONE_LOOP, which asserts the wavefront's size; its
+// branches are wave-uniform).  Opening the block with EXEC = the model lane alone (s_mov_b64 exec, 1 << 24) and testing
+// the mask against zero is one scalar instruction less and 3 % slower: a scalar write of EXEC in front of the compares
+// has to wait for every VALU instruction in flight (NOTEBOOK 38).  NaN semantics and hazards as in plain_in_exec.
+__device__ inline bool plain_in_exec_lane(double wd, double wd_prev, double dHd, double e, double T, double beta,
+                                          double rr, double t2hi, int j, int jmax_v) {
+  constexpr int lane = wave_sum8_lane(6);
+  unsigned long long ok;
+  asm volatile("v_cmpx_lt_f64_e64 %0, %1, %2\n\t"
+               "v_cmpx_gt_f64_e64 %0, %3, 0\n\t"
+               "v_cmpx_gt_i32_e64 %0, %10, %9\n\t"
+               "v_cmpx_lt_f64_e64 %0, %4, %5\n\t"
+               "v_cmpx_ge_f64_e64 %0, %6, %7\n\t"
+               "v_cmpx_nle_f64_e64 %0, %8, %11\n\t"
+               "s_mov_b64 exec, -1"
+               : "=&s"(ok)
+               : "v"(wd), "v"(wd_prev), "s"(dHd), "v"(e), "v"(T), "v"(beta), "s"(1e-3), "v"(rr), "s"(j), "v"(jmax_v),
+                 "v"(t2hi));
+  return (ok & (1ull << lane)) != 0ull;
+}
 
 struct RtrOut {
   double f, gradnorm;
@@ -552,20 +578,28 @@ __device__ inline void rtr_solve_one(Ctx &cx, const Params &p, const gik_trace &
           (void)step;
           // One step's scalars, shared by its three parts below: `step` (above) in pieces, the same statements in the same
           // order; its comments are not repeated here.
+          // One thing differs from `step` in where it is done, not in what is done: the model value is not read into scalar
+          // registers.  It stays in its lanes of the distributed sum -- wa / wb by role, like the other two-set values;
+          // before a solve's first step the "previous" one holds :485's +inf -- where plain_in_exec_lane compares the
+          // two; the cold block reads the lane when it needs the values (NOTEBOOK 38).
+          static_assert(WAVE == 64, "plain_in_exec_lane closes with EXEC = 64 lanes: one whole wavefront, all enabled");
           double Hdelta, d_Hd, model_value, r_r, alpha, e_Pe_new, beta_p, new_r_r, beta, rr_test;
-          // the product, the reduction and the test: true when the step is anything but a plain one
-          auto step_test = [&](const double ec, const double hc, const double pc) __attribute__((always_inline)) -> bool {
+          double wa = 0.0, wb = __builtin_inf();
+          // the product, the reduction and the test: true when the step is anything but a plain one.  wc: this step's
+          // distributed sum (written), wp: the previous step's
+          auto step_test = [&](const double ec, const double hc, const double pc, double &wc, const double wp)
+                               __attribute__((always_inline)) -> bool {
             const double H = cx.ehess_end_slotwise();   // :497
             double v[8] = {cx.Q[0] * H, cx.Q[1] * H, cx.Q[2] * H,      delta * H,
                            w * H,       H * H,       ec * fma(0.5, hc, g), r * r};
             const double wd = wave_sum8_distributed(v);
 #pragma unroll
             for (int q = 0; q < 8; ++q)
-              if (q != 5) v[q] = readlane_f64(wd, wave_sum8_lane(q));
+              if (q != 5 && q != 6) v[q] = readlane_f64(wd, wave_sum8_lane(q));
             const double Hd_Hd = readlane_f64(fma(-v[2], v[2], fma(-v[1], v[1], fma(-v[0], v[0], wd))), wave_sum8_lane(5));
             Hdelta = fma(-cx.Q[2], v[2], fma(-cx.Q[1], v[1], fma(-cx.Q[0], v[0], H)));
             d_Hd = v[3];                             // :500
-            model_value = v[6];                      // :551 evaluated at the current eta
+            wc = wd;                                 // :551 evaluated at the current eta: value 6, left in its lanes
             r_r = v[7];                              // :564 exact
             const double rho = frcp1(d_Hd);
             alpha = r_r * rho;                       // :503
@@ -574,7 +608,7 @@ __device__ inline void rtr_solve_one(Ctx &cx, const Params &p, const gik_trace &
             new_r_r = beta_p * r_r;                                                      // :564 predicted
             beta = beta_p;
             rr_test = new_r_r;
-            return !plain_in_exec(model_value, model_prev, d_Hd, e_Pe_new, T_cur, beta_p, new_r_r, target2_hi, j, maxinner_m1);
+            return !plain_in_exec_lane(wd, wp, d_Hd, e_Pe_new, T_cur, beta_p, new_r_r, target2_hi, j, maxinner_m1);
           };
           // the cold block behind it: true when tCG ends (result in eta_l / Heta_l, or `bad`), false when the step turns out
           // to be a plain one after all (beta and new_r_r may have been re-summed)
@@ -672,8 +706,7 @@ __device__ inline void rtr_solve_one(Ctx &cx, const Params &p, const gik_trace &
           auto step_update = [&](const double ec, const double hc, double &en, double &hn, double &pn)
                                  __attribute__((always_inline)) {
             ++j;
-            pn = e_Pe_new;                                    // :537
-            model_prev = model_value;
+            pn = e_Pe_new;                                    // :537  (model_prev: this step's wc is the next one's wp)
             en = fma(alpha, delta, ec);                       // :538 (reads the old delta)
             w = fma(-alpha, Hdelta, w);
             delta = fma(beta, delta, w);                      // :593
@@ -689,17 +722,22 @@ __device__ inline void rtr_solve_one(Ctx &cx, const Params &p, const gik_trace &
             t = ea, ea = eb, eb = t;
             t = ha, ha = hb, hb = t;
             t = pa, pa = pb, pb = t;
+            t = wa, wa = wb, wb = t;
           };
           if (p.maxinner > 0)
             for (;;) {
               bool second;
               for (;;) {                             // :495
-                if (__builtin_expect(step_test(ea, ha, pa), 0)) { second = false; break; }
+                if (__builtin_expect(step_test(ea, ha, pa, wa, wb), 0)) { second = false; break; }
                 step_update(ea, ha, eb, hb, pb);
-                if (__builtin_expect(step_test(eb, hb, pb), 0)) { second = true; break; }
+                if (__builtin_expect(step_test(eb, hb, pb, wb, wa), 0)) { second = true; break; }
                 step_update(eb, hb, ea, ha, pa);
               }
               if (second) swap_sets();
+              // (this step's sum is in wa now and the previous step's in wb; after the step is finished below and the
+              //  sets are swapped once more, wb holds this step's: what the next step_test of the first role compares with)
+              model_value = readlane_f64(wa, wave_sum8_lane(6));
+              model_prev = readlane_f64(wb, wave_sum8_lane(6));
               if (step_cold(ea, ha, pa, eb, hb)) break;
               step_update(ea, ha, eb, hb, pb);
               swap_sets();
