@@ -115,6 +115,7 @@ class AnchoredRetryOpts(C.Structure):
 CLEARANCE_NODES, CLEARANCE_LINKS, CLEARANCE_LINKS_SELF = 0, 1, 2
 CLEARANCE_MODES = {"nodes": CLEARANCE_NODES, "links": CLEARANCE_LINKS, "links+self": CLEARANCE_LINKS_SELF}
 SELF_MAX_PAIRS = 2016      # every pair of 64 links
+SELF_HINGE_MAX_PAIRS = 16  # pairs the solve carries hinges for (gik_anchored_attach_self_hinges)
 
 
 class LinkDesc(C.Structure):
@@ -158,6 +159,7 @@ SYMBOLS = {
     "gik_anchored_sweep_clearance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                                C.c_void_p, C.c_void_p]),
     "gik_anchored_attach_self_pairs": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "gik_anchored_attach_self_hinges": (C.c_int, [C.c_void_p]),
     "gik_anchored_self_clearance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "gik_anchored_sweep_clearances": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -17,7 +17,7 @@ REPO = os.path.dirname(HERE)
 SRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib", "libgraphik_amd.so")
 DEV_LIB = os.path.join(HERE, "lib", "exp", "libgraphik_amd_dev.so")
-SOURCES = ["gik_host.hip", "gik_k_wave3.hip", "gik_k_wave3_strict.hip", "gik_k_anch.hip", "gik_k_anch_link.hip", "gik_k_anch_scene.hip", "gik_k_wave2.hip",
+SOURCES = ["gik_host.hip", "gik_k_wave3.hip", "gik_k_wave3_strict.hip", "gik_k_anch.hip", "gik_k_anch_link.hip", "gik_k_anch_scene.hip", "gik_k_anch_self.hip", "gik_k_wave2.hip",
            "gik_k_block.hip", "gik_k_npt.hip", "gik_k_npt4.hip", "gik_k_quad.hip", "gik_k_prep.hip", "gik_k_retry.hip", "gik_k_anch_seed.hip",
            "gik_k_order.hip", "gik_host_anch.hip"]      # (the second host unit last: the link order of the others is what it was)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
@@ -27,7 +27,7 @@ LINK_FLAGS = ["--offload-arch=gfx950", "-shared", "-fPIC"]
 # branch in every step -- 191 instead of 185 instructions per step of the lone-wavefront build (NOTEBOOK 12).
 UNIT_FLAGS = {"gik_k_wave3_strict.hip": ["-mllvm", "-structurizecfg-skip-uniform-regions"],
               # the second host unit launches kernels of other units by their prototypes and has no device side at all:
-              # compiled host-only, the library embeds the same fifteen code objects as before the unit existed
+              # compiled host-only, it adds no code object to the library (one per kernel unit and one for gik_host.hip)
               "gik_host_anch.hip": ["--cuda-host-only"]}
 
 

@@ -24,8 +24,8 @@
 //                           SEGMENTS less both radii (anch_self_pair), optionally merged into the value already there.
 //                           Up to 16 pairs: four goals per wavefront, lane 16 g + p on pair p of goal slot g, the
 //                           minimum and the NaN flag per 16-lane row.  More: one wavefront per goal, as the link kernel.
-// anch_link_pair, anch_self_pair, anch_link_foot (the pair function of the solve kernel's link hinges), anch_sweep_interp
-// and anch_sweep_min are __host__ __device__, so that a host program can walk them.
+// anch_link_pair, anch_self_pair, anch_link_foot and anch_self_feet (the pair functions of the solve kernel's link and self
+// hinges), anch_self_res, anch_sweep_interp and anch_sweep_min are __host__ __device__, so that a host program can walk them.
 // Plain kernels, defined where GIK_DEFINE_ANCH_SEED_KERNELS is set (gik_k_anch_seed.hip); every other unit that includes
 // this header -- the two host units, which launch them -- sees prototypes.
 #pragma once
@@ -175,6 +175,61 @@ __host__ __device__ inline void anch_link_foot(const double *a, const double *b,
   m[1] = (w * a[1] + t * b[1]) - s[1];
   m[2] = (w * a[2] + t * b[2]) - s[2];
   d = m[0] * m[0] + m[1] * m[1] + m[2] * m[2];
+}
+
+// The (link, link) pair as the solve kernel's self hinge reads it (WaveCtx<.., SELF>, gik_wave.hip.h): the foot parameters
+// (s, t) of anch_self_pair by its branches operation for operation (the e == 0 branch included), the vector
+// v = (a1 + s d1) - (a2 + t d2) between the closest points and d = v.v, so that sqrt(d) - rho1 - rho2 is anch_self_pair's
+// value bit for bit: the hinge and the clearance agree on what "inside" is.  Every product and sum is rounded on its own
+// (AnchoredProblem.self_feet_host is the same operations in numpy).  Exactly parallel overlapping links take the foot
+// pair of the s = 0 branch: finite, a kink of measure zero.
+__host__ __device__ inline void anch_self_feet(const double *a1, const double *b1, const double *a2, const double *b2, double &s,
+                                               double &t, double (&v)[3], double &d) {
+#pragma clang fp contract(off)
+  const double d1x = b1[0] - a1[0], d1y = b1[1] - a1[1], d1z = b1[2] - a1[2];
+  const double d2x = b2[0] - a2[0], d2y = b2[1] - a2[1], d2z = b2[2] - a2[2];
+  const double rx = a1[0] - a2[0], ry = a1[1] - a2[1], rz = a1[2] - a2[2];
+  const double a = d1x * d1x + d1y * d1y + d1z * d1z;
+  const double e = d2x * d2x + d2y * d2y + d2z * d2z;
+  const double f = d2x * rx + d2y * ry + d2z * rz;
+  const double c = d1x * rx + d1y * ry + d1z * rz;
+  const double b = d1x * d2x + d1y * d2y + d1z * d2z;
+  const double den = a * e - b * b;
+  s = 0.0;
+  if (a > 0.0 && den > 0.0) {
+    s = (b * f - c * e) / den;
+    s = s > 0.0 ? s : 0.0;
+    s = s < 1.0 ? s : 1.0;
+  }
+  t = e > 0.0 ? (b * s + f) / e : -1.0;
+  if (t < 0.0) {
+    t = 0.0;
+    s = 0.0;
+    if (a > 0.0) {
+      s = -c / a;
+      s = s > 0.0 ? s : 0.0;
+      s = s < 1.0 ? s : 1.0;
+    }
+  } else if (t > 1.0) {
+    t = 1.0;
+    s = 0.0;
+    if (a > 0.0) {
+      s = (b - c) / a;
+      s = s > 0.0 ? s : 0.0;
+      s = s < 1.0 ? s : 1.0;
+    }
+  }
+  v[0] = (a1[0] + s * d1x) - (a2[0] + t * d2x);
+  v[1] = (a1[1] + s * d1y) - (a2[1] + t * d2y);
+  v[2] = (a1[2] + s * d1z) - (a2[2] + t * d2z);
+  d = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
+}
+// the residual of a self hinge, R = rho1 + rho2 and d of anch_self_feet: R^2 - d in two rounded operations.  Active where
+// it is positive; R = 0 gives -d <= 0, never active.
+__host__ __device__ inline double anch_self_res(double R, double d) {
+#pragma clang fp contract(off)
+  const double R2 = R * R;
+  return R2 - d;
 }
 
 // sample s of 0 .. S between two joint angles: two rounded products and one rounded sum, as the retry seeds are

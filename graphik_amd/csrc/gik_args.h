@@ -22,6 +22,7 @@ constexpr int ANCH_MAXOBS = 128; // obstacles (staged in LDS: 32 B each)
 static_assert(SCENE_MAX_SPHERES == ANCH_MAXOBS, "gik_scenes.h restates this constant");
 constexpr int ANCH_LMAX = 2;      // link hinges (WaveCtx<.., LINKS>): links per free node
 constexpr int ANCH_LROWS = 22;  // rows of the per-node link tables: 3 N <= 64 gives 21 free nodes, + one inert row for idle lanes
+constexpr int ANCH_SELF_HMAX = 16;   // self hinges (WaveCtx<.., SELF>): link pairs per template, a pair per lane of a 16-lane row
 
 constexpr int MIG_SIMDS = 1 << 14;      // SIMD slots of the spread table (MigCtl::simd_run, gik_rtr.hip.h)
 
@@ -63,6 +64,15 @@ struct AnchLinkRec {
                    // end's row (tile row of a free node / row of sh_anch), [23:16] the slot whose neighbour it is (0xff: none)
   uint32_t pad;
 };
+
+// a self hinge (WaveCtx<.., SELF>): the four ends a1, b1, a2, b2 of a link pair, each a free row (6 * row, tile 0) or an
+// anchor row (the anchor table's offset + 4 * row) as a double offset from the tiles -- the encoding of link_other -- and
+// R = rho_l + rho_m.  An unused entry is all zero: R = 0 is never active.
+struct AnchSelfDesc {
+  uint16_t off[4];
+  double R;
+};
+static_assert(sizeof(AnchSelfDesc) == 16, "kernel ABI");
 
 // launch-invariant tables of the workgroup-per-problem path (device pointers; gik_template_create)
 struct BlockTabs {
@@ -115,6 +125,7 @@ struct AnchArgs {
   unsigned long long obs_mask;  // bit i: free node i carries the obstacle hinges
   int n_obs, n_goal, goal_row0; // goal anchors occupy rows goal_row0 .. goal_row0 + n_goal - 1
   const AnchLinkRec *link_rec = nullptr;   // [ANCH_LMAX][ANCH_LROWS] link hinges per free node (LINKS kernels only)
+  const AnchSelfDesc *self_desc = nullptr; // [ANCH_SELF_HMAX] self hinges (SELF kernels only)
 };
 
 struct SolveArgs {

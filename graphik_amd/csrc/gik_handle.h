@@ -45,6 +45,9 @@ struct gik_template {
   // the link pairs of gik_anchored_attach_self_pairs (anch_self_clearance_kernel); n_self < 0: none attached
   int *d_self_l = nullptr, *d_self_m = nullptr;   // [n_self] indices into the link arrays
   int n_self = -1;
+  bool self_hinges = false;                       // gik_anchored_attach_self_hinges: the solve kernels are the SELF builds
+  std::vector<int> h_link_a, h_link_b, h_self_l, h_self_m;   // host copies of the link set and the pairs, and the radii:
+  std::vector<double> h_link_rho;                 // what gik_anchored_attach_self_hinges builds its descriptors from
   std::vector<int> h_free_full, h_anchor_full;    // host copies of d_free_full / d_anchor_full and of the slot table:
   std::vector<uint32_t> h_slot_meta;              // what the attach call builds the per-node link records from
   double axis_length = 1.0;

@@ -21,7 +21,7 @@
 #include <thread>
 
 namespace gik {
-GIK_ALL_KERNELS(GIK_EXTERN_TEMPLATE)
+GIK_ALL_KERNELS(GIK_EXTERN_TEMPLATE)      // (the self-hinge group, beside it: at the end of gik_kernels.hip.h)
 
 // the compiled node-per-lane variants
 struct NptVariant {
@@ -57,8 +57,9 @@ typedef size_t (*lds_fn)(int);
 // A build a form does not have stays null.
 // (PER_EDGE: hessian_form = GIK_HESS_PER_EDGE, k = 3, TrustRegions; ANCHORED: the fixed-anchor formulation, k = 3, theta == 1;
 // ANCHORED_LINK: ... with link hinges.  Creation never asks for that form: gik_anchored_attach_links with hinges = 1
-// re-resolves an anchored 9-slot template to it)
-enum Form { COLUMN, PER_EDGE, ANCHORED, ANCHORED_LINK };
+// re-resolves an anchored 9-slot template to it; ANCHORED_SELF / ANCHORED_LINK_SELF: either with self hinges,
+// gik_anchored_attach_self_hinges re-resolves to the one that matches the template's current form)
+enum Form { COLUMN, PER_EDGE, ANCHORED, ANCHORED_LINK, ANCHORED_SELF, ANCHORED_LINK_SELF };
 struct WaveRow {
   int K, slots;
   Form form;
@@ -75,7 +76,8 @@ struct WaveRow {
 // build -- the per-edge form always, the column form at <3, 9> only.
 template <int K, int D, Form F, unsigned MORE = (F == PER_EDGE ? W_SPREAD : 0u)>
 static WaveRow wave_row() {
-  constexpr unsigned B = F == PER_EDGE ? W_PER_EDGE : F == ANCHORED ? W_ANCH : F == ANCHORED_LINK ? W_ANCH | W_LINKS : 0u;
+  constexpr unsigned B = F == PER_EDGE ? W_PER_EDGE : F == ANCHORED ? W_ANCH : F == ANCHORED_LINK ? W_ANCH | W_LINKS :
+                         F == ANCHORED_SELF ? W_ANCH | W_SELF : F == ANCHORED_LINK_SELF ? W_ANCH | W_LINKS | W_SELF : 0u;
   WaveRow r{K, D, F};
   r.solve = rtr_wave_kernel<K, D, B | W_THETA1>;
   if constexpr ((B & W_ANCH) == 0) r.solve_theta = rtr_wave_kernel<K, D, B>;
@@ -93,6 +95,7 @@ static WaveRow wave_row() {
 // workgroup kernels on the planar trees -- both stay)
 static const WaveRow kWaveRows[] = {
     wave_row<3, 9, COLUMN, W_SPREAD>(), wave_row<3, 9, PER_EDGE>(), wave_row<3, 9, ANCHORED>(), wave_row<3, 9, ANCHORED_LINK>(),
+    wave_row<3, 9, ANCHORED_SELF>(), wave_row<3, 9, ANCHORED_LINK_SELF>(),
     wave_row<3, 10, COLUMN>(), wave_row<3, 10, PER_EDGE>(),
     wave_row<3, 20, ANCHORED>(),
     wave_row<2, 6, COLUMN>(), wave_row<2, 16, COLUMN>(), wave_row<2, 31, COLUMN>()};
@@ -593,6 +596,9 @@ int gik_anchored_attach_links(gik_template *anch, const gik_link_desc *d) {
   anch->d_link_a = la;
   anch->d_link_b = lb;
   anch->d_link_rho = lr;
+  anch->h_link_a.assign(d->link_a, d->link_a + d->n_link);
+  anch->h_link_b.assign(d->link_b, d->link_b + d->n_link);
+  anch->h_link_rho.assign(d->link_radius, d->link_radius + d->n_link);
   if (d->hinges) {
     // the template's solve and known-answer kernels become the link row's, with their LDS bytes and occupancy
     const WaveRow *row = find_row(3, ANCHORED_LINK, 9);
@@ -630,7 +636,41 @@ int gik_anchored_attach_self_pairs(gik_template *anch, int n_pair, const int32_t
   if (!ok) return fail(e + ": device upload failed");
   anch->d_self_l = pl;
   anch->d_self_m = pm;
+  anch->h_self_l.assign(pair_l, pair_l + n_pair);
+  anch->h_self_m.assign(pair_m, pair_m + n_pair);
   anch->n_self = n_pair;
+  return 0;
+}
+
+// self hinges: the attached pairs become terms of the solve.  The template's solve, known-answer and scene kernels are
+// resolved again, to the SELF row of its current form (with or without link hinges), with their LDS bytes and occupancy.
+int gik_anchored_attach_self_hinges(gik_template *anch) {
+  using namespace gik;
+  const std::string e("gik_anchored_attach_self_hinges");
+  if (!anch) return fail(e + ": null argument");
+  if (!anch->anchored) return fail(e + ": the handle must be a fixed-anchor template (gik_template_create_anchored)");
+  if (anch->self_hinges) return fail(e + ": self hinges already attached");
+  if (anch->n_link < 0) return fail(e + ": no links attached (gik_anchored_attach_links comes first)");
+  if (anch->n_self < 0) return fail(e + ": no self pairs attached (gik_anchored_attach_self_pairs comes first)");
+  if (anch->n_self > ANCH_SELF_HMAX)
+    return fail(e + ": " + std::to_string(anch->n_self) + " self pairs attached; the solve carries hinges for at most 16");
+  if (anch->maxdeg != 9)
+    return fail(e + ": self hinges need the 9-slot fixed-anchor kernel; this template runs the " + std::to_string(anch->maxdeg) +
+                "-slot variant, which has none");
+  std::vector<AnchSelfDesc> descs;
+  const std::string why = self_hinge_descs(anch->h_free_full, anch->h_anchor_full, anch->h_link_a, anch->h_link_b, anch->h_link_rho,
+                                           anch->h_self_l, anch->h_self_m, descs);
+  if (!why.empty()) return fail(e + ": " + why);
+  const WaveRow *row = find_row(3, anch->link_hinges ? ANCHORED_LINK_SELF : ANCHORED_SELF, 9);
+  bool ok = true;
+  const AnchSelfDesc *dd = upload(anch, descs.data(), descs.size(), ok);
+  int occ = 0;
+  if (!ok || hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)row->solve, WAVE, row->lds(anch->T)) != hipSuccess)
+    return fail(e + ": device upload failed");
+  anch->an.self_desc = dd;
+  install_row(anch, row);
+  anch->f.waves_per_cu = std::max(1, std::min(occ, 32));
+  anch->self_hinges = true;
   return 0;
 }
 
@@ -1366,7 +1406,7 @@ int gik_template_get_info(const gik_template *t, gik_template_info *info) {
   info->lds_bytes = (int32_t)t->smem_bytes;
   info->clique_closed_form = t->clique_mode;
   info->hessian_form = (t->hess_per_edge || t->f.is_block) ? GIK_HESS_PER_EDGE : GIK_HESS_COLUMN;
-  info->anchored = t->anchored ? (t->link_hinges ? 3 : 1) : 0;
+  info->anchored = t->anchored ? (1 | (t->link_hinges ? 2 : 0) | (t->self_hinges ? 4 : 0)) : 0;
   info->has_pipeline = t->has_pipe ? 1 : 0;
   info->prepare_is_block = t->prep.plan.block() ? 1 : 0;
   info->node_per_lane = t->f.is_npt ? t->npt_variant->NW : 0;

@@ -49,6 +49,15 @@
   X(void rtr_wave_scene_kernel<3, 9, W_THETA1 | W_ANCH>(SolveArgs, SceneArgs))           \
   X(void rtr_wave_scene_kernel<3, 20, W_THETA1 | W_ANCH>(SolveArgs, SceneArgs))          \
   X(void rtr_wave_scene_kernel<3, 9, W_THETA1 | W_ANCH | W_LINKS>(SolveArgs, SceneArgs))
+// ... with self hinges (gik_anchored_attach_self_hinges), without and with link hinges: solve, known answers, scenes.
+// A group of its own beside GIK_ALL_KERNELS (gik_k_anch_self.hip): gik_kernels.hip.h declares it for the host unit.
+#define GIK_KERNELS_ANCH_SELF(X)                                                                  \
+  X(void rtr_wave_kernel<3, 9, W_THETA1 | W_ANCH | W_SELF>(SolveArgs))                            \
+  X(void rtr_wave_kernel<3, 9, W_THETA1 | W_ANCH | W_LINKS | W_SELF>(SolveArgs))                  \
+  X(void kat_wave_kernel<3, 9, W_ANCH | W_SELF>(KatArgs))                                         \
+  X(void kat_wave_kernel<3, 9, W_ANCH | W_LINKS | W_SELF>(KatArgs))                               \
+  X(void rtr_wave_scene_kernel<3, 9, W_THETA1 | W_ANCH | W_SELF>(SolveArgs, SceneArgs))           \
+  X(void rtr_wave_scene_kernel<3, 9, W_THETA1 | W_ANCH | W_LINKS | W_SELF>(SolveArgs, SceneArgs))
 // one unknown per lane, k = 2
 #define GIK_KERNELS_WAVE2(X)                          \
   X(void rtr_wave_kernel<2, 6, W_THETA1>(SolveArgs))  \

@@ -520,4 +520,30 @@ static std::string link_hinge_records(int N, int maxdeg, const std::vector<uint3
   return "";
 }
 
+// The descriptors of WaveCtx<.., SELF> ([ANCH_SELF_HMAX], zero = unused), or the reason of a refusal: pair p's four ends
+// a_l, b_l, a_m, b_m as offsets from the tiles (a free row: 6 * row; an anchor row: 0x8000 | 4 * row) and R = rho_l + rho_m.
+static std::string self_hinge_descs(const std::vector<int> &free_full, const std::vector<int> &anchor_full, const std::vector<int> &link_a,
+                                    const std::vector<int> &link_b, const std::vector<double> &link_rho, const std::vector<int> &pair_l,
+                                    const std::vector<int> &pair_m, std::vector<AnchSelfDesc> &descs) {
+  descs.assign((size_t)ANCH_SELF_HMAX, AnchSelfDesc{{0, 0, 0, 0}, 0.0});
+  auto find = [](const std::vector<int> &v, int row) {
+    for (size_t i = 0; i < v.size(); ++i)
+      if (v[i] == row) return (int)i;
+    return -1;
+  };
+  for (size_t p = 0; p < pair_l.size(); ++p) {
+    const int link[2] = {pair_l[p], pair_m[p]};
+    for (int q = 0; q < 4; ++q) {
+      const int l = link[q >> 1], row = (q & 1) ? link_b[l] : link_a[l];
+      const int fr = find(free_full, row), an = fr < 0 ? find(anchor_full, row) : -1;
+      if (fr < 0 && an < 0)
+        return "link " + std::to_string(l) + " of pair " + std::to_string(p) + " ends at row " + std::to_string(row) +
+               ", which is neither a free node nor an anchor row";
+      descs[p].off[q] = (uint16_t)(fr >= 0 ? 6 * fr : (0x8000 | (4 * an)));
+    }
+    descs[p].R = link_rho[link[0]] + link_rho[link[1]];
+  }
+  return "";
+}
+
 }  // namespace gik

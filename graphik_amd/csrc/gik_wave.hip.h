@@ -341,11 +341,27 @@ __host__ __device__ inline uint32_t link_meta_pack(int is_b, int other_const, in
 __host__ __device__ inline void anch_link_foot(const double *a, const double *b, const double *s, double &t, double (&m)[3],
                                                double &d);
 
+// SELF: self hinges on top (opt-in per template, gik_anchored_attach_self_hinges).  A pair p = (l, m) of attached links with
+// ends A1, B1 and A2, B2 -- free rows, base anchors or goal anchors -- R = rho_l + rho_m and the feet (s, t) of anch_self_pair:
+//     v = (1 - s) A1 + s B1 - (1 - t) A2 - t B2,   d = v.v,   res = R^2 - d,   active <=> res > 0,   c = -res
+//     f += res^2,   G_P += w_P 2 c v,   H_P += w_P Bh om,   w = (1 - s, s, -(1 - t), -t),   Bh = 2 (2 v v^T + c I),
+//     om = sum_Q w_Q W_Q    (W of a constant end: 0)
+// The gradient is exact wherever the closest pair of points is unique (envelope theorem); the Hessian is the frozen-(s, t)
+// model, for the reasons given for the links.  The four ends of a pair are in general no graph neighbours, so nothing goes
+// into the slot table: the pairs have a pass of their own.  Lane p < 16 evaluates pair p from the natural-order tile (one
+// lane per pair: one set of bits per pair), cost() adds its res^2 to the one wave sum, commit() leaves (s, t, v, c) of
+// every pair in LDS and the wave-uniform mask of the active ones in scalar registers, and commit() and ehess() walk the
+// mask's set bits, every lane adding where its node is an end of the pair.  An empty mask costs ehess() one scalar branch.
+__host__ __device__ inline void anch_self_feet(const double *a1, const double *b1, const double *a2, const double *b2, double &s,
+                                               double &t, double (&v)[3], double &d);      // (gik_anch_seed.hip.h, as above)
+__host__ __device__ inline double anch_self_res(double R, double d);
+
 // SLIM: the layout of the per-edge product form (WaveCtxStrict, gik_wave_strict.hip.h): only the natural-order tile,
 // and slot metadata / slot records of the slots a lane OWNS (node slots comp, comp + 3, ...) -- 8.3 instead of 18.9 KB
 // of LDS per wavefront on a 7-DOF arm, which is what lets three wavefronts share a SIMD (153 VGPRs).
-template <int K, int MAXDEG, bool ANCH = false, bool SLIM = false, bool LINKS = false>
+template <int K, int MAXDEG, bool ANCH = false, bool SLIM = false, bool LINKS = false, bool SELF = false>
 struct WaveCtx {
+  static_assert(!SELF || (ANCH && MAXDEG == 9), "self hinges: the 9-slot fixed-anchor context");
   static_assert(!SLIM || (K == 3 && !ANCH), "the slim layout belongs to the 3-D per-edge context");
   static_assert(!LINKS || (ANCH && MAXDEG == 9), "link hinges: the 9-slot fixed-anchor context");
   static constexpr int RS = (K == 3) ? 6 : 2;  // LDS row stride in doubles (48 B / 16 B)
@@ -354,6 +370,9 @@ struct WaveCtx {
   static constexpr bool SLIM_LAYOUT = SLIM;
   static constexpr int NTILE = SLIM ? 1 : K;   // tiles kept in LDS
   static constexpr int NSL = SLIM ? (MAXDEG + 2) / 3 : MAXDEG;   // slots per lane in the LDS tables
+  struct SelfState {       // (SELF) a pair at the last commit(): feet, v, c = -res (0: inactive)
+    double s, t, v[3], c;
+  };
   // Per (slot, lane) record for cost()/commit(): the residual target of the slot's term and the
   // clamp bounds that encode its kind -- EQ (-inf, +inf), LOWER (0, +inf), UPPER (-inf, 0),
   // padding (0, 0) -- so that with u = target - d the residual is clamp(u, lo, hi) for every kind
@@ -372,7 +391,8 @@ struct WaveCtx {
            (HAS_CK ? sizeof(double) * 4 * WAVE : 0) +
            (ANCH ? sizeof(double) * 4 * (ANCH_MAXA + ANCH_MAXOBS) + 16 * (size_t)ANCH_PMAX * WAVE +
                        48 * (size_t)WAVE : 0) +
-           (LINKS ? sizeof(double) * ANCH_MAXOBS + (sizeof(AnchLinkRec) + sizeof(LinkObs)) * (size_t)ANCH_LMAX * ANCH_LROWS : 0);
+           (LINKS ? sizeof(double) * ANCH_MAXOBS + (sizeof(AnchLinkRec) + sizeof(LinkObs)) * (size_t)ANCH_LMAX * ANCH_LROWS : 0) +
+           (SELF ? (sizeof(AnchSelfDesc) + sizeof(SelfState)) * (size_t)ANCH_SELF_HMAX : 0);
   }
   // ---- fixed-anchor data (ANCH) ----
   // Everything per lane lives in LDS records (the 9-slot kernel has no VGPR to spare: per-lane
@@ -539,6 +559,41 @@ struct WaveCtx {
       n.pad = 0u;
       st = n;
     }
+  }
+  // ---- self hinges (SELF) ----
+  AnchSelfDesc *sh_sdesc;  // [ANCH_SELF_HMAX]
+  SelfState *sh_sst;       // [ANCH_SELF_HMAX]
+  int self_anch_off;       // sh_anch - sh_tile (doubles)
+  uint64_t self_mask;      // wave-uniform: the pairs active at the last commit()
+  // (after init_anchored, and after init_links where the build has them: the tables follow theirs)
+  __device__ inline void init_self(const AnchSelfDesc *desc) {
+    if constexpr (LINKS) sh_sdesc = reinterpret_cast<AnchSelfDesc *>(sh_lost + ANCH_LMAX * ANCH_LROWS);
+    else sh_sdesc = reinterpret_cast<AnchSelfDesc *>(sh_ost + WAVE);
+    sh_sst = reinterpret_cast<SelfState *>(sh_sdesc + ANCH_SELF_HMAX);
+    self_anch_off = (int)(sh_anch - sh_tile);
+    self_mask = 0ull;
+    __builtin_amdgcn_wave_barrier();
+    if (lane < ANCH_SELF_HMAX) sh_sdesc[lane] = desc[lane];
+    __builtin_amdgcn_wave_barrier();
+  }
+  __device__ inline int self_off(uint32_t o) const { return (o & 0x8000u) ? self_anch_off + (int)(o & 0x7fffu) : (int)o; }
+  // pair (lane & 15) at the point whose rows are in tile 0: its feet and v, and its residual where it is active on a pair
+  // lane, else 0
+  __device__ inline double self_pair(double &s, double &t, double (&v)[3]) const {
+    const AnchSelfDesc ds = sh_sdesc[lane & (ANCH_SELF_HMAX - 1)];
+    double d;
+    anch_self_feet(sh_tile + self_off(ds.off[0]), sh_tile + self_off(ds.off[1]), sh_tile + self_off(ds.off[2]),
+                   sh_tile + self_off(ds.off[3]), s, t, v, d);
+    const double res = anch_self_res(ds.R, d);
+    return (lane < ANCH_SELF_HMAX && res > 0.0) ? res : 0.0;
+  }
+  // this lane's weight in a pair: the sum of w_P over the ends P that are its node (an anchor end is nobody's)
+  __device__ inline double self_weight(const AnchSelfDesc &ds, const SelfState &st) const {
+    double w = (int)ds.off[0] == nat_off ? 1.0 - st.s : 0.0;
+    w += (int)ds.off[1] == nat_off ? st.s : 0.0;
+    w -= (int)ds.off[2] == nat_off ? 1.0 - st.t : 0.0;
+    w -= (int)ds.off[3] == nat_off ? st.t : 0.0;
+    return active ? w : 0.0;
   }
   __device__ inline void init_anchored(const uint64_t obs_mask, const double *obs, int n_obs_, bool cull) {
     sh_anch = sh_ck + 4 * WAVE;
@@ -814,6 +869,12 @@ struct WaveCtx {
         __builtin_amdgcn_wave_barrier();   // the near lists are written by one lane of a node and read by all three
       }
     }
+    if constexpr (SELF) {
+      // a pair enters f once, on its lane: doubled before the halving.  Nothing active: every lane adds 0.0
+      double s_, t_, v_[3];
+      const double rs = self_pair(s_, t_, v_);
+      return 0.5 * wave_sum(((active && comp == 0) ? f : 0.0) + 2.0 * (rs * rs));
+    }
     return 0.5 * wave_sum((active && comp == 0) ? f : 0.0);
   }
 
@@ -929,6 +990,24 @@ struct WaveCtx {
         }
       }
     }
+    if constexpr (SELF) {
+      // the pairs at this point (the bits cost() summed): state for ehess(), and their gradient
+      double s_, t_, v_[3];
+      const double rs = self_pair(s_, t_, v_);
+      self_mask = __builtin_amdgcn_ballot_w64(rs > 0.0);
+      if (lane < ANCH_SELF_HMAX) {
+        const SelfState st = {s_, t_, {v_[0], v_[1], v_[2]}, -rs};
+        sh_sst[lane] = st;
+      }
+      __builtin_amdgcn_wave_barrier();
+      for (uint64_t m = self_mask; m != 0ull; m &= m - 1ull) {
+        const int p = __builtin_ctzll(m);
+        const AnchSelfDesc ds = sh_sdesc[p];      // wave-uniform addresses: broadcast reads
+        const SelfState st = sh_sst[p];
+        const double vc = comp == 0 ? st.v[0] : (comp == 1 ? st.v[1] : st.v[2]);
+        G = fma(self_weight(ds, st) * st.c, vc, G);
+      }
+    }
 #pragma unroll
     for (int q = 0; q < K; ++q) {
       double t = 0.0;
@@ -983,6 +1062,29 @@ struct WaveCtx {
       H += bit_select(comp >= 2, wave_shr<2>(p[2]), wave_shl<1>(p[2]));
     } else {
       H += bit_select(comp >= 1, wave_shr<1>(p[1]), wave_shl<1>(p[1]));
+    }
+    if constexpr (SELF) {
+      if (self_mask != 0ull) {      // (wave-uniform: one scalar branch where nothing is active)
+        for (uint64_t m = self_mask; m != 0ull; m &= m - 1ull) {
+          const int pr = __builtin_ctzll(m);
+          const AnchSelfDesc ds = sh_sdesc[pr];
+          const SelfState st = sh_sst[pr];
+          const double w4[4] = {1.0 - st.s, st.s, st.t - 1.0, -st.t};
+          double om[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {      // the W rows of the free ends from tile 0; a constant end has W = 0
+            const uint32_t o = ds.off[e];
+            const double *r = sh_tile + ((o & 0x8000u) ? 0u : o);
+            const double wf = (o & 0x8000u) ? 0.0 : w4[e];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) om[q] = fma(wf, r[q], om[q]);
+          }
+          const double vo = fma(st.v[2], om[2], fma(st.v[1], om[1], st.v[0] * om[0]));
+          const double vc = comp == 0 ? st.v[0] : (comp == 1 ? st.v[1] : st.v[2]);
+          const double oc = comp == 0 ? om[0] : (comp == 1 ? om[1] : om[2]);
+          H = fma(self_weight(ds, st), 2.0 * fma(2.0 * vc, vo, st.c * oc), H);
+        }
+      }
     }
     return H;
   }

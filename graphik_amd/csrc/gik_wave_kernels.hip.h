@@ -1,6 +1,6 @@
 // graphik_amd/csrc/gik_wave_kernels.hip.h -- the kernels of the one-wavefront-per-problem family (gfx950), as templates.
-// Instantiated in gik_k_wave3.hip, gik_k_wave3_strict.hip, gik_k_wave2.hip, gik_k_anch.hip, gik_k_anch_link.hip and
-// gik_k_anch_scene.hip (gik_instances.h).
+// Instantiated in gik_k_wave3.hip, gik_k_wave3_strict.hip, gik_k_wave2.hip, gik_k_anch.hip, gik_k_anch_link.hip,
+// gik_k_anch_scene.hip and gik_k_anch_self.hip (gik_instances.h).
 //
 //   rtr_wave_kernel : whole Riemannian trust-region solve (TrustRegions.solve +
 //                     _truncated_conjugate_gradient, graphik/solvers/trust_region.py:112-599)
@@ -63,11 +63,12 @@ enum WaveBuild : unsigned {
   // gik_template_desc.hessian_form = GIK_HESS_PER_EDGE), k = 3 free-free graphs
   W_PER_EDGE = 8,
   W_LINKS = 16,    // link hinges in the fixed-anchor solve (WaveCtx<.., LINKS>, gik_anchored_attach_links with hinges = 1)
+  W_SELF = 32,     // self hinges in the fixed-anchor solve (WaveCtx<.., SELF>, gik_anchored_attach_self_hinges)
 };
 // the context a build runs on
 template <int K, int MAXDEG, unsigned BUILD>
 using WaveBuildCtx = std::conditional_t<(BUILD & W_PER_EDGE) != 0, WaveCtxStrict<MAXDEG>,
-                                        WaveCtx<K, MAXDEG, (BUILD & W_ANCH) != 0, false, (BUILD & W_LINKS) != 0>>;
+                                        WaveCtx<K, MAXDEG, (BUILD & W_ANCH) != 0, false, (BUILD & W_LINKS) != 0, (BUILD & W_SELF) != 0>>;
 // SCENES is not a bit but an entry point, rtr_wave_scene_kernel: per-goal obstacle scenes in the fixed-anchor solve
 // (gik_solve_batch_scenes).  The scene set is a second kernel
 // argument (SceneArgs, gik_scenes.h; SolveArgs and with it every other kernel stay as they are): a.an.obs is then the
@@ -80,8 +81,9 @@ using WaveBuildCtx = std::conditional_t<(BUILD & W_PER_EDGE) != 0, WaveCtxStrict
 template <int K, int MAXDEG, unsigned BUILD, bool SCENES = false>
 __device__ __forceinline__ void rtr_wave_run(const SolveArgs &a, const SceneArgs &sc = SceneArgs()) {
   constexpr bool THETA_ONE = BUILD & W_THETA1, ANCH = BUILD & W_ANCH, MIG = BUILD & W_SPREAD, STRICT = BUILD & W_PER_EDGE,
-                 LINKS = BUILD & W_LINKS;
+                 LINKS = BUILD & W_LINKS, SELF = BUILD & W_SELF;
   static_assert(!SCENES || ANCH, "scenes: the fixed-anchor kernels");
+  static_assert(!SELF || (ANCH && MAXDEG == 9), "self hinges: the 9-slot fixed-anchor kernel");
   static_assert(!LINKS || (ANCH && MAXDEG == 9), "link hinges: the 9-slot fixed-anchor kernel");
   static_assert(!ANCH || K == 3, "the fixed-anchor formulation is 3-D");
   static_assert(!MIG || !ANCH, "tail spreading: two waves per SIMD, i.e. not the anchored variant");
@@ -103,6 +105,7 @@ __device__ __forceinline__ void rtr_wave_run(const SolveArgs &a, const SceneArgs
     // (a scene build starts with no obstacle staged: the first claimed problem brings its scene)
     cx.init_anchored(a.an.obs_mask, a.an.obs, SCENES ? 0 : a.an.n_obs, !(a.dbg & 128));
     if constexpr (LINKS) cx.init_links(a.an.link_rec);
+    if constexpr (SELF) cx.init_self(a.an.self_desc);
     for (int t = lane; t < a.T; t += WAVE) sh_tgt[t] = a.targets[t];
     for (int t = lane; t < 4 * ANCH_MAXA; t += WAVE) cx.sh_anch[t] = a.an.anch_const[t];
     __builtin_amdgcn_wave_barrier();
@@ -347,8 +350,8 @@ __global__ void __launch_bounds__(WAVE, 2) rcg_wave_kernel(SolveArgs a) {
 
 template <int K, int MAXDEG, unsigned BUILD = 0>
 __global__ void __launch_bounds__(WAVE) kat_wave_kernel(KatArgs a) {
-  static_assert(!(BUILD & ~(W_ANCH | W_PER_EDGE | W_LINKS)), "known answers: the anchored, per-edge and link builds");
-  constexpr bool ANCH = BUILD & W_ANCH, LINKS = BUILD & W_LINKS;
+  static_assert(!(BUILD & ~(W_ANCH | W_PER_EDGE | W_LINKS | W_SELF)), "known answers: the anchored, per-edge, link and self builds");
+  constexpr bool ANCH = BUILD & W_ANCH, LINKS = BUILD & W_LINKS, SELF = BUILD & W_SELF;
   using Ctx = WaveBuildCtx<K, MAXDEG, BUILD>;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int lane = threadIdx.x;
@@ -366,6 +369,7 @@ __global__ void __launch_bounds__(WAVE) kat_wave_kernel(KatArgs a) {
   if constexpr (ANCH) {
     cx.init_anchored(a.an.obs_mask, a.an.obs, a.an.n_obs, true);
     if constexpr (LINKS) cx.init_links(a.an.link_rec);
+    if constexpr (SELF) cx.init_self(a.an.self_desc);
     for (int t = lane; t < 4 * ANCH_MAXA; t += WAVE) cx.sh_anch[t] = a.an.anch_const[t];
     __builtin_amdgcn_wave_barrier();
     if (lane < 3 * a.an.n_goal)

@@ -302,6 +302,7 @@ class Template:
         self.n_link = None      # (attach_links)
         self.link_hinges = False
         self.n_self = None      # (attach_self_pairs)
+        self.self_hinges = False
         self._read_info()
         deg = np.bincount(np.concatenate([self.term_i, self.term_j]), minlength=self.N).max()
         # compiled slot count of the wavefront variant the library chose (or the raw degree: workgroup / node-per-lane paths)
@@ -747,6 +748,16 @@ class Template:
             _ffi.check(self.lib.gik_anchored_attach_self_pairs(self._h, len(l), l.ctypes.data_as(C.POINTER(C.c_int32)),
                                                                m.ctypes.data_as(C.POINTER(C.c_int32))))
         self.n_self = len(l)
+
+    def attach_self_hinges(self):
+        """Self hinges (gik_anchored_attach_self_hinges), once, after attach_self_pairs: the attached pairs (at most 16)
+        become terms of the solve -- every later call on this template, the known-answer entry points included, runs
+        the self builds of its kernels; self.self_hinges and bit 4 of self.info["anchored"] (5, with link hinges 7) say so."""
+        assert self.anchored
+        with torch.cuda.device(self.device):
+            _ffi.check(self.lib.gik_anchored_attach_self_hinges(self._h))
+        self.self_hinges = True
+        self._read_info()      # (other kernels, LDS bytes and occupancy)
 
     def anchored_self_clearance(self, Y_full):
         """Full point matrices [B, full_N, 3] -> self clearance [B] on the device (gik_anchored_self_clearance): the

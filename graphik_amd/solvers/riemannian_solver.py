@@ -599,7 +599,7 @@ class AnchoredProblem:
     without obstacles) fitted to the world frame by its anchors."""
 
     def __init__(self, graph, params=None, device=None, host_only=False, links=None, link_radius=0.0, link_hinges=False,
-                 goal="pose", self_pairs=None):
+                 goal="pose", self_pairs=None, self_hinges=False):
         """host_only: derive the term set only (no device handles) -- what tests/test_host_layer.py
         compares with the reference's own edge construction (tests/golden/ur10_table_intended.npz).
 
@@ -619,7 +619,12 @@ class AnchoredProblem:
         links are capsules of link_radius around SEGMENTS: with thick capsules around the short wrist links "auto" reports
         overlaps the real geometry does not have -- links 2 and 4 of UR10 are joined by a link of 11.5 cm, so at a radius
         of 6 cm they touch in every configuration -- and such a robot wants an explicit list.  self.self_pairs is the
-        [P, 2] int array (None: not attached)."""
+        [P, 2] int array (None: not attached).
+        self_hinges: False -- the pairs are measured only: nothing in the cost acts on the self clearance, a restart
+        finds a self-clear answer by landing elsewhere -- or True: the solve kernel also carries a hinge per pair on the
+        distance between the two SEGMENTS (gik_anchored_attach_self_hinges; self_hinge_terms_host is the numpy mirror of the
+        terms), so every solve, restart, scene and tracked waypoint of this problem pushes the robot's own links apart.
+        Needs self_pairs, at most 16 of them; chains on the 9-slot anchored kernel; with or without link_hinges."""
         import copy
         from ..utils.constants import OBSTACLE, ROBOT, TYPE, MAIN_PREFIX
         from .. import _ffi
@@ -633,6 +638,11 @@ class AnchoredProblem:
         if link_hinges and links is not None and len(links) == 0:
             raise ValueError("link_hinges=True needs a link set: links=[] attaches none")
         self.link_hinges = bool(link_hinges)
+        if not isinstance(self_hinges, (bool, np.bool_)):      # (before any device call)
+            raise ValueError(f"self_hinges must be a bool, got {self_hinges!r}")
+        if self_hinges and self_pairs is None:
+            raise ValueError("self_hinges=True needs self pairs: self_pairs=None attaches none")
+        self.self_hinges = bool(self_hinges)
         self.graph, self.robot = graph, graph.robot
         obstacles = [n for n in graph.node_ids if graph.nodes[n].get(TYPE) == OBSTACLE]
         bare = copy.deepcopy(graph)
@@ -654,6 +664,8 @@ class AnchoredProblem:
             raise ValueError("link_radius must be finite and at least 0")
         self.link_radius = np.ascontiguousarray(rho)
         self.self_pairs = self._check_self_pairs(self_pairs, self.link_rows)
+        if self.self_hinges and len(self.self_pairs) > _ffi.SELF_HINGE_MAX_PAIRS:
+            raise ValueError(f"self_hinges=True takes at most {_ffi.SELF_HINGE_MAX_PAIRS} self pairs, got {len(self.self_pairs)}")
         self.base = BatchProblem(bare, use_limits=True, params=params, device=device, host_only=host_only)
         if not host_only and not self.base.device_pipeline:
             raise NotImplementedError("robot graph beyond the device pipeline")
@@ -709,6 +721,8 @@ class AnchoredProblem:
             self.template.attach_links(self.link_rows[:, 0], self.link_rows[:, 1], self.link_radius, hinges=self.link_hinges)
         if self.self_pairs is not None:
             self.template.attach_self_pairs(self.self_pairs[:, 0], self.self_pairs[:, 1])
+        if self.self_hinges:
+            self.template.attach_self_hinges()
 
     @staticmethod
     def _check_self_pairs(self_pairs, link_rows):
@@ -782,7 +796,8 @@ class AnchoredProblem:
         link_hinges=True the solve itself carries link hinges, so clearance_mode="links" then has hinges behind it: the
         rule reads a clearance the cost acts on.  "links+self" (the problem must have self_pairs): the minimum of the
         link clearance and self.self_clearance of the same points -- an answer whose links pass through each other has
-        failed the rule like one whose links pass through a sphere.  Nothing in the cost acts on the self clearance.
+        failed the rule like one whose links pass through a sphere.  Nothing in the cost acts on the self clearance unless the
+        problem was built with self_hinges=True.
 
         retries > 0 (gik_anchored_ik_batch_retry): a goal that fails -- stop != 0, pos_err > pos_tol, rot_err >
         rot_tol or clearance < -clear_tol, so an answer on its goal with a joint point (clearance_mode="nodes") or
@@ -1070,6 +1085,70 @@ class AnchoredProblem:
                 if ib is not None:
                     G[ib] += t * 2.0 * c * m
                     H[ib] += t * hv
+        return f, G, H
+
+    @staticmethod
+    def self_feet_host(a1, b1, a2, b2):
+        """One (link, link) pair -> (s, t, v, d): the foot parameters of self_clearance, v = (a1 + s d1) - (a2 + t d2)
+        and d = v.v, in scalar doubles -- the operations of the device pair function (anch_self_feet) in its order, so
+        sqrt(d) - rho_l - rho_m is self_clearance's value of the pair bit for bit."""
+        a1, b1, a2, b2 = ([float(x) for x in p] for p in (a1, b1, a2, b2))
+        d1 = [b1[q] - a1[q] for q in range(3)]
+        d2 = [b2[q] - a2[q] for q in range(3)]
+        r = [a1[q] - a2[q] for q in range(3)]
+        dot = lambda x, y: x[0] * y[0] + x[1] * y[1] + x[2] * y[2]      # noqa: E731
+        clamp = lambda x: (x if x < 1.0 else 1.0) if x > 0.0 else 0.0      # noqa: E731
+        a, e, f, c, b = dot(d1, d1), dot(d2, d2), dot(d2, r), dot(d1, r), dot(d1, d2)
+        den = a * e - b * b
+        s = clamp((b * f - c * e) / den) if (a > 0.0 and den > 0.0) else 0.0
+        t = (b * s + f) / e if e > 0.0 else -1.0
+        if t < 0.0:
+            t, s = 0.0, (clamp(-c / a) if a > 0.0 else 0.0)
+        elif t > 1.0:
+            t, s = 1.0, (clamp((b - c) / a) if a > 0.0 else 0.0)
+        v = np.array([(a1[q] + s * d1[q]) - (a2[q] + t * d2[q]) for q in range(3)])
+        return s, t, v, float(v[0] * v[0] + v[1] * v[1] + v[2] * v[2])
+
+    def self_hinge_terms_host(self, Y_free, W, goal_anchor, frozen_st=None):
+        """(f, G, H) of the self hinges alone at one point: Y_free, W [Nf, 3], goal_anchor [n_goal * 3], in the
+        conventions of link_hinge_terms_host (f = sum res^2, G = 1/2 grad f, H = 1/2 Hess f [W]).  Per self pair (l, m),
+        with A1, B1 the ends of link l, A2, B2 those of link m, R = rho_l + rho_m and (s, t, v, d) of self_feet_host:
+            res = R^2 - d,  active <=> res > 0,  c = -res,  w = (1 - s, s, -(1 - t), -t) on (A1, B1, A2, B2)
+            f += res^2;  G_P += w_P 2 c v;  om = sum_Q w_Q W_Q;  H_P += w_P 2 (2 (v.om) v + c om)
+        Contributions to a constant end are dropped (its W is 0); a pair whose four ends are constants adds to f alone.
+        The gradient is exact wherever the closest points are unique (envelope theorem), H is the frozen-(s, t) model
+        the solve kernel uses.  frozen_st: {pair: (s, t)} to evaluate at instead of the feet of this point (what a
+        finite difference of the frozen gradient needs); active pairs' (s, t) come back in self.last_self_st."""
+        Y = np.asarray(Y_free, dtype=np.float64)
+        f, G, H = 0.0, np.zeros_like(Y), np.zeros_like(Y)
+        self.last_self_st = {}
+        if self.self_pairs is None:
+            return f, G, H
+        ends = self.link_ends_host(Y, W, goal_anchor)
+        for p, (l, m) in enumerate(np.asarray(self.self_pairs).tolist()):
+            (A1, W1, i1), (B1, X1, j1) = ends[l]
+            (A2, W2, i2), (B2, X2, j2) = ends[m]
+            s, t, v, d = self.self_feet_host(A1, B1, A2, B2)
+            if frozen_st is not None:
+                if p not in frozen_st:
+                    continue
+                s, t = frozen_st[p]
+                v = (A1 + s * (B1 - A1)) - (A2 + t * (B2 - A2))
+                d = float(v[0] * v[0] + v[1] * v[1] + v[2] * v[2])
+            R = float(self.link_radius[l]) + float(self.link_radius[m])
+            res = R * R - d
+            if not res > 0.0 and frozen_st is None:
+                continue
+            self.last_self_st[p] = (s, t)
+            c = -res
+            f += res * res
+            w = (1.0 - s, s, -(1.0 - t), -t)
+            om = w[0] * W1 + w[1] * X1 + w[2] * W2 + w[3] * X2
+            hv = 2.0 * (2.0 * (v @ om) * v + c * om)
+            for wP, iP in zip(w, (i1, j1, i2, j2)):
+                if iP is not None:
+                    G[iP] += wP * 2.0 * c * v
+                    H[iP] += wP * hv
         return f, G, H
 
     def sweep_points(self, q_a, q_b, samples):

@@ -656,8 +656,22 @@ int gik_anchored_sweep_clearance(const gik_template *anch, const gik_template *b
  *   CONSERVATIVE: two links can meet and part between two samples; pick `samples` from the joint step as there.
  *   d_ws: the same workspace, gik_anchored_sweep_ws_bytes.  Refused: what gik_anchored_sweep_clearance refuses, both
  *   outputs null, d_self_out given on a template without self pairs attached.  B == 0 returns 0.
- * clearance_mode = GIK_CLEARANCE_LINKS_SELF (below) puts min(link clearance, self clearance) behind the restart rule. */
+ * clearance_mode = GIK_CLEARANCE_LINKS_SELF (below) puts min(link clearance, self clearance) behind the restart rule.
+ * gik_anchored_attach_self_hinges: SELF HINGES (opt-in), once, AFTER gik_anchored_attach_self_pairs: the attached pairs
+ *   become terms of the solve, so that the trust-region solve itself pushes the robot's links apart.  Per pair (l, m)
+ *   with R = link_radius[l] + link_radius[m] and (s, t), v of the formulas above:
+ *       d = v.v,  res = R^2 - d,  active where res > 0,  c = -res,  w = (1 - s, s, -(1 - t), -t) on the ends a1, b1, a2, b2
+ *       f += res^2;   G_P += w_P 2 c v;   H_P += w_P 2 (2 v v^T + c I) (sum_Q w_Q W_Q)      (a constant end: W = 0, no G, no H)
+ *   sqrt(d) - R is gik_anchored_self_clearance's value of the pair bit for bit.  The gradient is exact wherever the
+ *   closest pair of points is unique; the Hessian is the model with (s, t) frozen.  A pair with R == 0 is never active.
+ *   The template's solve, known-answer and scene kernels become the self builds of its current form (with or without
+ *   link hinges), with their LDS bytes and occupancy (gik_template_info.anchored gains bit 4: 5, or 7 with link hinges);
+ *   every later call on the template runs them.  With no pair active a solve's results are those of the build without.
+ *   Refused with a message, nothing launched: a handle that is not a fixed-anchor template, a second call, no links
+ *   attached, no self pairs attached, more than 16 pairs attached (the clearance keeps its 2016), a template on the
+ *   20-slot kernel, a link of a pair that ends at a row which is neither a free node nor an anchor row. */
 int gik_anchored_attach_self_pairs(gik_template *anch, int n_pair, const int32_t *pair_l, const int32_t *pair_m);
+int gik_anchored_attach_self_hinges(gik_template *anch);
 int gik_anchored_self_clearance(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance,
                                 void *stream);
 int gik_anchored_sweep_clearances(const gik_template *anch, const gik_template *base, const double *d_q_a,
