@@ -8,9 +8,9 @@
 //                           (anchor_world), never from the seed: the goal nodes' seed rows are dropped.  One thread
 //                           per double of the output, consecutive lanes on consecutive doubles.
 //   anch_clearance_kernel : one wavefront per goal: min over (free node i with obs_node_mask[i], obstacle o) of
-//                           |Y_i - c_o| - r_o on a full point matrix.  Lanes stride over the pairs, then a wave
-//                           min-reduction by shuffles (no LDS, no atomics).  No pair: +inf.  A NaN coordinate of a
-//                           masked node: NaN for that goal.
+//                           |Y_i - c_o| - r_o on a full point matrix (wave_pair_min: lanes stride over the pairs, then
+//                           a wave min-reduction by shuffles, no LDS, no atomics).  No pair: +inf.  A NaN coordinate of
+//                           a masked node: NaN for that goal.
 //   anch_link_clearance_kernel : the same wave, over (link l, obstacle o): the distance from the sphere's centre to the
 //                           SEGMENT between two rows of the point matrix, less the radius and the link's own
 //                           thickness (anch_link_pair).  A link can cross a sphere with both ends outside it, which
@@ -24,8 +24,8 @@
 //                           SEGMENTS less both radii (anch_self_pair), optionally merged into the value already there.
 //                           Up to 16 pairs: four goals per wavefront, lane 16 g + p on pair p of goal slot g, the
 //                           minimum and the NaN flag per 16-lane row.  More: one wavefront per goal, as the link kernel.
-// anch_link_pair, anch_self_pair, anch_link_foot and anch_self_feet (the pair functions of the solve kernel's link and self
-// hinges), anch_self_res, anch_sweep_interp and anch_sweep_min are __host__ __device__, so that a host program can walk them.
+// The pair functions themselves (anch_link_pair, anch_self_pair, anch_sweep_interp, anch_sweep_min) are gik_anch_pairs.h's,
+// shared with the hinges of the solve kernels.
 // Plain kernels, defined where GIK_DEFINE_ANCH_SEED_KERNELS is set (gik_k_anch_seed.hip); every other unit that includes
 // this header -- the two host units, which launch them -- sees prototypes.
 #pragma once
@@ -33,6 +33,7 @@
 #include <hip/hip_runtime.h>
 
 #include "gik_anch_glue.hip.h"      // (anchor_world)
+#include "gik_anch_pairs.h"
 #include "gik_args.h"
 #include "gik_scenes.h"
 
@@ -83,177 +84,6 @@ struct AnchSweepMinArgs {
   int B, S;
 };
 
-// clearance of one (link, sphere) pair: a, b the link's ends, s = (centre, r^2), rho the link's radius.  The nearest
-// point of the segment is a + t (b - a), t clamped to [0, 1]; a zero-length link is its point.  Every product and sum
-// is rounded on its own (AnchoredProblem.link_clearance is the same operations in numpy).  A NaN in either end comes
-// out as NaN: one in b alone would otherwise be lost where L2 > 0 is false.
-__host__ __device__ inline double anch_link_pair(const double *a, const double *b, const double *s, double rho) {
-#pragma clang fp contract(off)
-  const double dx = b[0] - a[0], dy = b[1] - a[1], dz = b[2] - a[2];
-  const double L2 = dx * dx + dy * dy + dz * dz;
-  const double ux = s[0] - a[0], uy = s[1] - a[1], uz = s[2] - a[2];
-  double t = 0.0;
-  if (L2 > 0.0) {
-    t = (ux * dx + uy * dy + uz * dz) / L2;
-    t = t > 0.0 ? t : 0.0;
-    t = t < 1.0 ? t : 1.0;
-  }
-  const double vx = ux - t * dx, vy = uy - t * dy, vz = uz - t * dz;
-  const double v = sqrt(vx * vx + vy * vy + vz * vz) - sqrt(s[3]) - rho;
-  return L2 != L2 ? __builtin_nan("") : v;
-}
-
-// clearance of one (link, link) pair: the distance between the segments a1 -> b1 and a2 -> b2 less the two radii.  The
-// closest points are a1 + s d1 and a2 + t d2: s from the unconstrained minimum clamped to [0, 1], t from s, and where t
-// leaves [0, 1] it is clamped and s taken again for that end.  A zero-length link is its point (a == 0: s = 0 and t is
-// the foot of that point; e == 0: t = 0 and s is; both: the distance of the two points); parallel links (den == 0) take s = 0 and the
-// clamps; crossing links give -rho1 - rho2.  Every product and sum is rounded on its own (AnchoredProblem.self_clearance
-// is the same operations in numpy).  A NaN in any end comes out as NaN: every coordinate enters a or e.
-__host__ __device__ inline double anch_self_pair(const double *a1, const double *b1, const double *a2, const double *b2,
-                                                 double rho1, double rho2) {
-#pragma clang fp contract(off)
-  const double d1x = b1[0] - a1[0], d1y = b1[1] - a1[1], d1z = b1[2] - a1[2];
-  const double d2x = b2[0] - a2[0], d2y = b2[1] - a2[1], d2z = b2[2] - a2[2];
-  const double rx = a1[0] - a2[0], ry = a1[1] - a2[1], rz = a1[2] - a2[2];
-  const double a = d1x * d1x + d1y * d1y + d1z * d1z;
-  const double e = d2x * d2x + d2y * d2y + d2z * d2z;
-  const double f = d2x * rx + d2y * ry + d2z * rz;
-  const double c = d1x * rx + d1y * ry + d1z * rz;
-  const double b = d1x * d2x + d1y * d2y + d1z * d2z;
-  const double den = a * e - b * b;
-  double s = 0.0;
-  if (a > 0.0 && den > 0.0) {
-    s = (b * f - c * e) / den;
-    s = s > 0.0 ? s : 0.0;
-    s = s < 1.0 ? s : 1.0;
-  }
-  // (a zero-length second link has no t to solve for: it takes the t = 0 branch, whose s is the foot of its point)
-  double t = e > 0.0 ? (b * s + f) / e : -1.0;
-  if (t < 0.0) {
-    t = 0.0;
-    s = 0.0;
-    if (a > 0.0) {
-      s = -c / a;
-      s = s > 0.0 ? s : 0.0;
-      s = s < 1.0 ? s : 1.0;
-    }
-  } else if (t > 1.0) {
-    t = 1.0;
-    s = 0.0;
-    if (a > 0.0) {
-      s = (b - c) / a;
-      s = s > 0.0 ? s : 0.0;
-      s = s < 1.0 ? s : 1.0;
-    }
-  }
-  const double vx = (a1[0] + s * d1x) - (a2[0] + t * d2x);
-  const double vy = (a1[1] + s * d1y) - (a2[1] + t * d2y);
-  const double vz = (a1[2] + s * d1z) - (a2[2] + t * d2z);
-  const double v = sqrt(vx * vx + vy * vy + vz * vz) - rho1 - rho2;
-  return (a != a || e != e) ? __builtin_nan("") : v;
-}
-
-// The (link, sphere) pair as the solve kernel's link hinge reads it (WaveCtx<.., LINKS>, gik_wave.hip.h): the foot
-// parameter t of anch_link_pair, the vector m = (1 - t) a + t b - c from the sphere's centre to the foot, and d = m.m.
-// The hinge is  res = (r + rho)^2 - d > 0.  Every product and sum is rounded on its own
-// (AnchoredProblem.link_hinge_terms_host is the same operations in numpy); t = 0 gives m = a - c and t = 1 gives
-// m = b - c exactly, so a link that clamps to an end carries that end's node residual.
-__host__ __device__ inline void anch_link_foot(const double *a, const double *b, const double *s, double &t, double (&m)[3],
-                                               double &d) {
-#pragma clang fp contract(off)
-  const double dx = b[0] - a[0], dy = b[1] - a[1], dz = b[2] - a[2];
-  const double L2 = dx * dx + dy * dy + dz * dz;
-  const double ux = s[0] - a[0], uy = s[1] - a[1], uz = s[2] - a[2];
-  t = 0.0;
-  if (L2 > 0.0) {
-    t = (ux * dx + uy * dy + uz * dz) / L2;
-    t = t > 0.0 ? t : 0.0;
-    t = t < 1.0 ? t : 1.0;
-  }
-  const double w = 1.0 - t;
-  m[0] = (w * a[0] + t * b[0]) - s[0];
-  m[1] = (w * a[1] + t * b[1]) - s[1];
-  m[2] = (w * a[2] + t * b[2]) - s[2];
-  d = m[0] * m[0] + m[1] * m[1] + m[2] * m[2];
-}
-
-// The (link, link) pair as the solve kernel's self hinge reads it (WaveCtx<.., SELF>, gik_wave.hip.h): the foot parameters
-// (s, t) of anch_self_pair by its branches operation for operation (the e == 0 branch included), the vector
-// v = (a1 + s d1) - (a2 + t d2) between the closest points and d = v.v, so that sqrt(d) - rho1 - rho2 is anch_self_pair's
-// value bit for bit: the hinge and the clearance agree on what "inside" is.  Every product and sum is rounded on its own
-// (AnchoredProblem.self_feet_host is the same operations in numpy).  Exactly parallel overlapping links take the foot
-// pair of the s = 0 branch: finite, a kink of measure zero.
-__host__ __device__ inline void anch_self_feet(const double *a1, const double *b1, const double *a2, const double *b2, double &s,
-                                               double &t, double (&v)[3], double &d) {
-#pragma clang fp contract(off)
-  const double d1x = b1[0] - a1[0], d1y = b1[1] - a1[1], d1z = b1[2] - a1[2];
-  const double d2x = b2[0] - a2[0], d2y = b2[1] - a2[1], d2z = b2[2] - a2[2];
-  const double rx = a1[0] - a2[0], ry = a1[1] - a2[1], rz = a1[2] - a2[2];
-  const double a = d1x * d1x + d1y * d1y + d1z * d1z;
-  const double e = d2x * d2x + d2y * d2y + d2z * d2z;
-  const double f = d2x * rx + d2y * ry + d2z * rz;
-  const double c = d1x * rx + d1y * ry + d1z * rz;
-  const double b = d1x * d2x + d1y * d2y + d1z * d2z;
-  const double den = a * e - b * b;
-  s = 0.0;
-  if (a > 0.0 && den > 0.0) {
-    s = (b * f - c * e) / den;
-    s = s > 0.0 ? s : 0.0;
-    s = s < 1.0 ? s : 1.0;
-  }
-  t = e > 0.0 ? (b * s + f) / e : -1.0;
-  if (t < 0.0) {
-    t = 0.0;
-    s = 0.0;
-    if (a > 0.0) {
-      s = -c / a;
-      s = s > 0.0 ? s : 0.0;
-      s = s < 1.0 ? s : 1.0;
-    }
-  } else if (t > 1.0) {
-    t = 1.0;
-    s = 0.0;
-    if (a > 0.0) {
-      s = (b - c) / a;
-      s = s > 0.0 ? s : 0.0;
-      s = s < 1.0 ? s : 1.0;
-    }
-  }
-  v[0] = (a1[0] + s * d1x) - (a2[0] + t * d2x);
-  v[1] = (a1[1] + s * d1y) - (a2[1] + t * d2y);
-  v[2] = (a1[2] + s * d1z) - (a2[2] + t * d2z);
-  d = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
-}
-// the residual of a self hinge, R = rho1 + rho2 and d of anch_self_feet: R^2 - d in two rounded operations.  Active where
-// it is positive; R = 0 gives -d <= 0, never active.
-__host__ __device__ inline double anch_self_res(double R, double d) {
-#pragma clang fp contract(off)
-  const double R2 = R * R;
-  return R2 - d;
-}
-
-// sample s of 0 .. S between two joint angles: two rounded products and one rounded sum, as the retry seeds are
-// written; s = 0 gives qa and s = S gives qb (finite angles; the sign of a zero aside)
-__host__ __device__ inline double anch_sweep_interp(double qa, double qb, int s, int S) {
-#pragma clang fp contract(off)
-  const double w = (double)s / (double)S;
-  const double pa = (1.0 - w) * qa;
-  const double pb = w * qb;
-  return pa + pb;
-}
-
-// min of n values `stride` apart; a NaN among them gives NaN (fmin would drop it)
-__host__ __device__ inline double anch_sweep_min(const double *c, int n, size_t stride) {
-  double m = __builtin_huge_val();
-  bool nan = false;
-  for (int s = 0; s < n; ++s) {
-    const double v = c[(size_t)s * stride];
-    nan |= v != v;
-    m = v < m ? v : m;
-  }
-  return nan ? __builtin_nan("") : m;
-}
-
 // (AnchGlueArgs: Y_full_in = seed_kernel's output, Y_free / anchor_goal out; Y_full_out unused)
 __global__ void __launch_bounds__(ANCH_SCATTER_NT) anch_scatter_kernel(AnchGlueArgs a)
 #ifndef GIK_DEFINE_ANCH_SEED_KERNELS
@@ -277,53 +107,41 @@ __global__ void __launch_bounds__(ANCH_SCATTER_NT) anch_scatter_kernel(AnchGlueA
 }
 #endif
 
-__global__ void __launch_bounds__(WAVE) anch_clearance_kernel(AnchClearArgs a)
-#ifndef GIK_DEFINE_ANCH_SEED_KERNELS
-    ;
-#else
-{
-  const int lane = threadIdx.x, pairs = a.n_node * a.n_obs;
-  for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
-    const double *Y = a.Y_full + (size_t)b * a.full_N * 3;
-    double m = __builtin_huge_val();
-    bool nan = false;
-    for (int p = lane; p < pairs; p += WAVE) {
-      const int i = p / a.n_obs, o = p - i * a.n_obs;
-      const double *y = Y + a.node_full[i] * 3, *s = a.obs + o * 4;
-      const double dx = y[0] - s[0], dy = y[1] - s[1], dz = y[2] - s[2];
-      const double v = sqrt(dx * dx + dy * dy + dz * dz) - sqrt(s[3]);
-      nan |= v != v;
-      m = fmin(m, v);
-    }
-    for (int off = WAVE / 2; off > 0; off >>= 1) m = fmin(m, __shfl_xor(m, off));
-    if (__any(nan)) m = __builtin_nan("");
-    if (lane == 0) a.clearance[b] = m;
+#ifdef GIK_DEFINE_ANCH_SEED_KERNELS
+// The minimum of value(p) over p = 0 .. pairs - 1 by one whole wavefront, handed back in every lane: lane l takes
+// p = l, l + 64, ..., then a butterfly of shuffles.  No pair: +inf.  A NaN value in any lane: NaN (fmin would drop it).
+template <class Value>
+__device__ inline double wave_pair_min(int lane, int pairs, Value value) {
+  double m = __builtin_huge_val();
+  bool nan = false;
+  for (int p = lane; p < pairs; p += WAVE) {
+    const double v = value(p);
+    nan |= v != v;
+    m = fmin(m, v);
   }
+  for (int off = WAVE / 2; off > 0; off >>= 1) m = fmin(m, __shfl_xor(m, off));
+  return __any(nan) ? __builtin_nan("") : m;
 }
-#endif
 
-__global__ void __launch_bounds__(WAVE) anch_link_clearance_kernel(AnchLinkArgs a)
-#ifndef GIK_DEFINE_ANCH_SEED_KERNELS
-    ;
-#else
-{
-  const int lane = threadIdx.x, pairs = a.n_link * a.n_obs;
-  for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
-    const double *Y = a.Y_full + (size_t)b * a.full_N * 3;
-    double m = __builtin_huge_val();
-    bool nan = false;
-    for (int p = lane; p < pairs; p += WAVE) {
-      const int l = p / a.n_obs, o = p - l * a.n_obs;
-      const double v = anch_link_pair(Y + a.link_a[l] * 3, Y + a.link_b[l] * 3, a.obs + o * 4, a.link_rho[l]);
-      nan |= v != v;
-      m = fmin(m, v);
-    }
-    for (int off = WAVE / 2; off > 0; off >>= 1) m = fmin(m, __shfl_xor(m, off));
-    if (__any(nan)) m = __builtin_nan("");
-    if (lane == 0) a.clearance[b] = m;
-  }
+// goal b of the node clearance against the n_obs rows at obs: the template's own, or a scene's
+__device__ inline double anch_node_min(const AnchClearArgs &a, int b, const double *obs, int n_obs) {
+  const double *Y = a.Y_full + (size_t)b * a.full_N * 3;
+  return wave_pair_min(threadIdx.x, a.n_node * n_obs, [&](int p) {
+    const int i = p / n_obs, o = p - i * n_obs;
+    const double *y = Y + a.node_full[i] * 3, *s = obs + o * 4;
+    const double dx = y[0] - s[0], dy = y[1] - s[1], dz = y[2] - s[2];
+    return sqrt(dx * dx + dy * dy + dz * dz) - sqrt(s[3]);
+  });
 }
-#endif
+
+// ... and of the link clearance
+__device__ inline double anch_link_min(const AnchLinkArgs &a, int b, const double *obs, int n_obs) {
+  const double *Y = a.Y_full + (size_t)b * a.full_N * 3;
+  return wave_pair_min(threadIdx.x, a.n_link * n_obs, [&](int p) {
+    const int l = p / n_obs, o = p - l * n_obs;
+    return anch_link_pair(Y + a.link_a[l] * 3, Y + a.link_b[l] * 3, obs + o * 4, a.link_rho[l]);
+  });
+}
 
 // pair p of one goal's point matrix (anch_self_clearance_kernel)
 __device__ inline double anch_self_value(const AnchSelfArgs &a, const double *Y, int p) {
@@ -341,6 +159,40 @@ __device__ inline void anch_self_store(const AnchSelfArgs &a, int b, double m) {
   }
   a.clearance[b] = m;
 }
+
+// The obstacle rows of goal b's scene (gik_scene_set): a.obs is [n_scene][stride][4] and a.n_obs is not read; the goal is
+// measured against the first n_obs[s] rows of scene s = scene_id[b] (null: scene 0), id and count clamped as the solve
+// kernel clamps them (SceneArgs, gik_scenes.h).
+__device__ inline const double *anch_scene_rows(const SceneArgs &sc, const double *obs, int b, int &n) {
+  const int s = scene_clamp_id(sc.scene_id ? sc.scene_id[b] : 0, sc.n_scene);
+  n = scene_clamp_count(sc.n_obs[s], sc.stride);
+  return obs + (size_t)s * (size_t)sc.stride * 4;
+}
+#endif
+
+__global__ void __launch_bounds__(WAVE) anch_clearance_kernel(AnchClearArgs a)
+#ifndef GIK_DEFINE_ANCH_SEED_KERNELS
+    ;
+#else
+{
+  for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
+    const double m = anch_node_min(a, b, a.obs, a.n_obs);
+    if (threadIdx.x == 0) a.clearance[b] = m;
+  }
+}
+#endif
+
+__global__ void __launch_bounds__(WAVE) anch_link_clearance_kernel(AnchLinkArgs a)
+#ifndef GIK_DEFINE_ANCH_SEED_KERNELS
+    ;
+#else
+{
+  for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
+    const double m = anch_link_min(a, b, a.obs, a.n_obs);
+    if (threadIdx.x == 0) a.clearance[b] = m;
+  }
+}
+#endif
 
 __global__ void __launch_bounds__(WAVE) anch_self_clearance_kernel(AnchSelfArgs a)
 #ifndef GIK_DEFINE_ANCH_SEED_KERNELS
@@ -367,55 +219,25 @@ __global__ void __launch_bounds__(WAVE) anch_self_clearance_kernel(AnchSelfArgs 
   }
   for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
     const double *Y = a.Y_full + (size_t)b * a.full_N * 3;
-    double m = __builtin_huge_val();
-    bool nan = false;
-    for (int p = lane; p < a.n_pair; p += WAVE) {
-      const double v = anch_self_value(a, Y, p);
-      nan |= v != v;
-      m = fmin(m, v);
-    }
-    for (int off = WAVE / 2; off > 0; off >>= 1) m = fmin(m, __shfl_xor(m, off));
-    if (__any(nan)) m = __builtin_nan("");
+    const double m = wave_pair_min(lane, a.n_pair, [&](int p) { return anch_self_value(a, Y, p); });
     if (lane == 0) anch_self_store(a, b, m);
   }
 }
 #endif
 
 // ---- per-goal obstacle scenes (gik_scene_set) ----
-// The two clearance kernels above with the obstacle rows looked up per goal: a.obs is [n_scene][stride][4] and a.n_obs is
-// not read; goal b is measured against the first n_obs[s] rows of scene s = scene_id[b] (null: scene 0), id and count
-// clamped as the solve kernel clamps them (SceneArgs, gik_scenes.h).  The same pairs through the same expressions; a minimum does not depend on the
-// order of its terms.
-__device__ inline const double *anch_scene_rows(const SceneArgs &sc, const double *obs, int b, int &n) {
-  const int s = scene_clamp_id(sc.scene_id ? sc.scene_id[b] : 0, sc.n_scene);
-  n = scene_clamp_count(sc.n_obs[s], sc.stride);
-  return obs + (size_t)s * (size_t)sc.stride * 4;
-}
-
+// The two clearance kernels above with the obstacle rows looked up per goal (anch_scene_rows): the same pairs through the
+// same per-goal body.
 __global__ void __launch_bounds__(WAVE) anch_clearance_scene_kernel(AnchClearArgs a, SceneArgs sc)
 #ifndef GIK_DEFINE_ANCH_SEED_KERNELS
     ;
 #else
 {
-  const int lane = threadIdx.x;
   for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
     int n_obs;
     const double *obs = anch_scene_rows(sc, a.obs, b, n_obs);
-    const int pairs = a.n_node * n_obs;
-    const double *Y = a.Y_full + (size_t)b * a.full_N * 3;
-    double m = __builtin_huge_val();
-    bool nan = false;
-    for (int p = lane; p < pairs; p += WAVE) {
-      const int i = p / n_obs, o = p - i * n_obs;
-      const double *y = Y + a.node_full[i] * 3, *s = obs + o * 4;
-      const double dx = y[0] - s[0], dy = y[1] - s[1], dz = y[2] - s[2];
-      const double v = sqrt(dx * dx + dy * dy + dz * dz) - sqrt(s[3]);
-      nan |= v != v;
-      m = fmin(m, v);
-    }
-    for (int off = WAVE / 2; off > 0; off >>= 1) m = fmin(m, __shfl_xor(m, off));
-    if (__any(nan)) m = __builtin_nan("");
-    if (lane == 0) a.clearance[b] = m;
+    const double m = anch_node_min(a, b, obs, n_obs);
+    if (threadIdx.x == 0) a.clearance[b] = m;
   }
 }
 #endif
@@ -425,23 +247,11 @@ __global__ void __launch_bounds__(WAVE) anch_link_clearance_scene_kernel(AnchLin
     ;
 #else
 {
-  const int lane = threadIdx.x;
   for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
     int n_obs;
     const double *obs = anch_scene_rows(sc, a.obs, b, n_obs);
-    const int pairs = a.n_link * n_obs;
-    const double *Y = a.Y_full + (size_t)b * a.full_N * 3;
-    double m = __builtin_huge_val();
-    bool nan = false;
-    for (int p = lane; p < pairs; p += WAVE) {
-      const int l = p / n_obs, o = p - l * n_obs;
-      const double v = anch_link_pair(Y + a.link_a[l] * 3, Y + a.link_b[l] * 3, obs + o * 4, a.link_rho[l]);
-      nan |= v != v;
-      m = fmin(m, v);
-    }
-    for (int off = WAVE / 2; off > 0; off >>= 1) m = fmin(m, __shfl_xor(m, off));
-    if (__any(nan)) m = __builtin_nan("");
-    if (lane == 0) a.clearance[b] = m;
+    const double m = anch_link_min(a, b, obs, n_obs);
+    if (threadIdx.x == 0) a.clearance[b] = m;
   }
 }
 #endif

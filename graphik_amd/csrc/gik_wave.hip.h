@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "graphik_amd.h"
+#include "gik_anch_pairs.h"      // (the pair functions of the link and self hinges)
 #include "gik_args.h"
 #include "gik_scenes.h"
 
@@ -321,7 +322,8 @@ struct Row {
 
 // LINKS: link hinges on top (opt-in per template, gik_anchored_attach_links with hinges = 1).  A link l = (a, b, rho) is
 // the segment between two rows of the full point matrix -- free rows of Y, constant base anchors or the per-problem goal
-// anchors -- and a capsule radius.  Against a sphere (C, r) with R = r + rho and the foot parameter t of anch_link_pair:
+// anchors -- and a capsule radius.  Against a sphere (C, r) with R = r + rho and (t, m, d) of anch_link_foot
+// (gik_anch_pairs.h; the link clearance takes its foot parameter from the same function):
 //     m = (1 - t) A + t B - C,   d = m.m,   res = R^2 - d,   active <=> res > 0,   c = d - R^2
 //     f += res^2,   G_A += (1 - t) 2 c m,   G_B += t 2 c m,
 //     H_A += (1 - t) Bh w,  H_B += t Bh w,   Bh = 2 (2 m m^T + c I),   w = (1 - t) W_A + t W_B    (W of a constant end: 0)
@@ -337,12 +339,10 @@ struct Row {
 __host__ __device__ inline uint32_t link_meta_pack(int is_b, int other_const, int other_row, int slot) {
   return 1u | ((uint32_t)is_b << 1) | ((uint32_t)other_const << 2) | ((uint32_t)other_row << 8) | ((uint32_t)slot << 16);
 }
-// (gik_anch_seed.hip.h, next to anch_link_pair; a translation unit that instantiates LINKS includes it)
-__host__ __device__ inline void anch_link_foot(const double *a, const double *b, const double *s, double &t, double (&m)[3],
-                                               double &d);
 
 // SELF: self hinges on top (opt-in per template, gik_anchored_attach_self_hinges).  A pair p = (l, m) of attached links with
-// ends A1, B1 and A2, B2 -- free rows, base anchors or goal anchors -- R = rho_l + rho_m and the feet (s, t) of anch_self_pair:
+// ends A1, B1 and A2, B2 -- free rows, base anchors or goal anchors -- R = rho_l + rho_m and (s, t, v, d) of anch_self_feet
+// (gik_anch_pairs.h; the self clearance is sqrt(d) - R of the same function) and res of anch_self_res:
 //     v = (1 - s) A1 + s B1 - (1 - t) A2 - t B2,   d = v.v,   res = R^2 - d,   active <=> res > 0,   c = -res
 //     f += res^2,   G_P += w_P 2 c v,   H_P += w_P Bh om,   w = (1 - s, s, -(1 - t), -t),   Bh = 2 (2 v v^T + c I),
 //     om = sum_Q w_Q W_Q    (W of a constant end: 0)
@@ -352,9 +352,6 @@ __host__ __device__ inline void anch_link_foot(const double *a, const double *b,
 // lane per pair: one set of bits per pair), cost() adds its res^2 to the one wave sum, commit() leaves (s, t, v, c) of
 // every pair in LDS and the wave-uniform mask of the active ones in scalar registers, and commit() and ehess() walk the
 // mask's set bits, every lane adding where its node is an end of the pair.  An empty mask costs ehess() one scalar branch.
-__host__ __device__ inline void anch_self_feet(const double *a1, const double *b1, const double *a2, const double *b2, double &s,
-                                               double &t, double (&v)[3], double &d);      // (gik_anch_seed.hip.h, as above)
-__host__ __device__ inline double anch_self_res(double R, double d);
 
 // SLIM: the layout of the per-edge product form (WaveCtxStrict, gik_wave_strict.hip.h): only the natural-order tile,
 // and slot metadata / slot records of the slots a lane OWNS (node slots comp, comp + 3, ...) -- 8.3 instead of 18.9 KB

@@ -584,6 +584,56 @@ class BatchProblem:
         return pos, rot
 
 
+# ---- the pair geometry of AnchoredProblem's numpy mirrors, once (the device side: csrc/gik_anch_pairs.h) ----------------
+# Elementwise float64 numpy on arrays of ends [..., 3]: the operations of the device pair functions in their order, every
+# product and sum rounded on its own, whether the arrays hold a batch (the clearances) or one pair (the *_host feet).
+def _dot3(x, y):
+    return x[..., 0] * y[..., 0] + x[..., 1] * y[..., 1] + x[..., 2] * y[..., 2]
+
+
+def _clamp01(x):
+    x = np.where(x > 0.0, x, 0.0)
+    return np.where(x < 1.0, x, 1.0)
+
+
+def _nan_min(x, axis):
+    """The minimum along axis (an int or a tuple); a NaN among the values gives NaN."""
+    return np.where(np.isnan(x).any(axis=axis), np.nan, np.where(np.isnan(x), np.inf, x).min(axis=axis))
+
+
+def _link_foot(a, b, c):
+    """A link from a to b against a centre c -> (d, L2, u, t): d = b - a, L2 = d.d, u = c - a and the foot parameter
+    t = min(max(u.d / L2, 0), 1), 0 for a zero-length link.  What link_clearance and link_foot_host share; their vectors
+    (u - t d and ((1 - t) a + t b) - c) round differently, as on the device, and both sets of bits are pinned by tests."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        d = b - a
+        L2 = _dot3(d, d)
+        u = c - a
+        t = np.where(L2 > 0.0, _clamp01(_dot3(u, d) / L2), 0.0)
+    return d, L2, u, t
+
+
+def _segment_feet(a1, b1, a2, b2):
+    """The closest points of the segments a1 -> b1 and a2 -> b2 -> (s, t, v, d): they are a1 + s d1 and a2 + t d2,
+    v = (a1 + s d1) - (a2 + t d2) and d = v.v.  With d1 = b1 - a1, d2 = b2 - a2, r = a1 - a2, a = d1.d1, e = d2.d2,
+    f = d2.r, c = d1.r, b = d1.d2, den = a e - b b:  s = clamp((b f - c e) / den, 0, 1) where a > 0 and den > 0, else 0;
+    t = (b s + f) / e where e > 0, else the t < 0 branch is taken;  where t < 0: t = 0, s = clamp(-c / a, 0, 1);  where
+    t > 1: t = 1, s = clamp((b - c) / a, 0, 1) (0 where a == 0).  A NaN coordinate reaches v -- through s d1 or t d2 even
+    where s or t is 0 -- so d is NaN without a guard of its own."""
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        d1, d2, r = b1 - a1, b2 - a2, a1 - a2
+        a, e, f, c, b = _dot3(d1, d1), _dot3(d2, d2), _dot3(d2, r), _dot3(d1, r), _dot3(d1, d2)
+        den = a * e - b * b
+        s = np.where((a > 0.0) & (den > 0.0), _clamp01((b * f - c * e) / den), 0.0)
+        t = np.where(e > 0.0, (b * s + f) / e, -1.0)          # (a zero-length second link: the t = 0 branch)
+        s_lo = np.where(a > 0.0, _clamp01(-c / a), 0.0)
+        s_hi = np.where(a > 0.0, _clamp01((b - c) / a), 0.0)
+        s = np.where(t < 0.0, s_lo, np.where(t > 1.0, s_hi, s))
+        t = np.where(t < 0.0, 0.0, np.where(t > 1.0, 1.0, t))
+        v = (a1 + s[..., None] * d1) - (a2 + t[..., None] * d2)
+        return s, t, v, _dot3(v, v)
+
+
 class AnchoredProblem:
     """Opt-in "intended" obstacle semantics.  graph_base.py:182-211 ties every
     node with a known position -- base frame, goal nodes, obstacle centres -- to the others by
@@ -940,27 +990,17 @@ class AnchoredProblem:
         b = Y[:, self.link_rows[:, 1], None, :]
         c = obstacles[None, None, :, :3]                          # [1, 1, n_obs, 3]
         r2 = obstacles[:, 3] ** 2                                 # (what the template holds: the squared radius)
-        dot = lambda x, y: x[..., 0] * y[..., 0] + x[..., 1] * y[..., 1] + x[..., 2] * y[..., 2]   # noqa: E731
-        with np.errstate(invalid="ignore", divide="ignore"):
-            d = b - a
-            L2 = dot(d, d)                                        # [B, n_link, 1]
-            u = c - a
-            t = dot(u, d) / L2
-            t = np.where(t > 0.0, t, 0.0)
-            t = np.where(t < 1.0, t, 1.0)
-            t = np.where(L2 > 0.0, t, 0.0)
+        d, L2, u, t = _link_foot(a, b, c)                         # (L2 [B, n_link, 1], t [B, n_link, n_obs])
+        with np.errstate(invalid="ignore"):
             v = u - t[..., None] * d
-            val = np.sqrt(dot(v, v)) - np.sqrt(r2)[None, None, :] - self.link_radius[None, :, None]
+            val = np.sqrt(_dot3(v, v)) - np.sqrt(r2)[None, None, :] - self.link_radius[None, :, None]
             val = np.where(np.isnan(L2), np.nan, val)
-        return np.where(np.isnan(val).any(axis=(1, 2)), np.nan, np.where(np.isnan(val), np.inf, val).min(axis=(1, 2)))
+        return _nan_min(val, axis=(1, 2))
 
     def self_clearance(self, Y_full):
         """min over the self pairs (l, m) of the distance between the capsules of links l and m per goal: the host mirror
         of gik_anchored_self_clearance, the same operations in the same order.  Y_full [B, N_robot, 3] (numpy).  With
-        link l from a1 to b1 and link m from a2 to b2:  d1 = b1 - a1, d2 = b2 - a2, r = a1 - a2, a = d1.d1, e = d2.d2,
-        f = d2.r, c = d1.r, b = d1.d2, den = a e - b b;  s = clamp((b f - c e) / den, 0, 1) where a > 0 and den > 0, else
-        0;  t = (b s + f) / e where e > 0, else the t < 0 branch is taken;  where t < 0: t = 0, s = clamp(-c / a, 0, 1);  where t > 1: t = 1,
-        s = clamp((b - c) / a, 0, 1) (0 where a == 0);  v = (a1 + s d1) - (a2 + t d2), value = |v| - rho_l - rho_m.
+        link l from a1 to b1, link m from a2 to b2 and d of _segment_feet(a1, b1, a2, b2):  value = sqrt(d) - rho_l - rho_m.
         >= 0: no two measured links overlap.  No pair: +inf; a NaN coordinate of a measured link's end: NaN for that
         goal.  Reads self.link_rows, self.link_radius and self.self_pairs only."""
         Y = np.asarray(Y_full, dtype=np.float64)
@@ -974,34 +1014,13 @@ class AnchoredProblem:
         l, m = pairs[:, 0], pairs[:, 1]
         a1, b1 = Y[:, rows[l, 0]], Y[:, rows[l, 1]]                # [B, P, 3]
         a2, b2 = Y[:, rows[m, 0]], Y[:, rows[m, 1]]
-        dot = lambda x, y: x[..., 0] * y[..., 0] + x[..., 1] * y[..., 1] + x[..., 2] * y[..., 2]   # noqa: E731
-
-        def clamp(x):
-            x = np.where(x > 0.0, x, 0.0)
-            return np.where(x < 1.0, x, 1.0)
-
-        with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
-            d1, d2, r = b1 - a1, b2 - a2, a1 - a2
-            a, e, f, c, b = dot(d1, d1), dot(d2, d2), dot(d2, r), dot(d1, r), dot(d1, d2)
-            den = a * e - b * b
-            s = np.where((a > 0.0) & (den > 0.0), clamp((b * f - c * e) / den), 0.0)
-            t = np.where(e > 0.0, (b * s + f) / e, -1.0)          # (a zero-length second link: the t = 0 branch)
-            s_lo = np.where(a > 0.0, clamp(-c / a), 0.0)
-            s_hi = np.where(a > 0.0, clamp((b - c) / a), 0.0)
-            s = np.where(t < 0.0, s_lo, np.where(t > 1.0, s_hi, s))
-            t = np.where(t < 0.0, 0.0, np.where(t > 1.0, 1.0, t))
-            v = (a1 + s[..., None] * d1) - (a2 + t[..., None] * d2)
-            val = np.sqrt(dot(v, v)) - rho[l][None, :] - rho[m][None, :]
-            val = np.where(np.isnan(a) | np.isnan(e), np.nan, val)
-        return np.where(np.isnan(val).any(axis=1), np.nan, np.where(np.isnan(val), np.inf, val).min(axis=1))
+        with np.errstate(invalid="ignore"):
+            return _nan_min(np.sqrt(_segment_feet(a1, b1, a2, b2)[3]) - rho[l][None, :] - rho[m][None, :], axis=1)
 
     def sweep_self_clearance_host(self, q_a, q_b, samples):
         """The numpy mirror of sweep_self_clearance: self_clearance of BatchProblem.seed_points at every sample, the
         minimum over the samples, NaN if any sample is NaN."""
-        qs = self.sweep_points(q_a, q_b, samples)
-        S1, B, n = qs.shape
-        cl = self.self_clearance(self.base.seed_points(qs.reshape(S1 * B, n))).reshape(S1, B)
-        return np.where(np.isnan(cl).any(axis=0), np.nan, np.where(np.isnan(cl), np.inf, cl).min(axis=0))
+        return self._sweep_min_host(q_a, q_b, samples, self.self_clearance)
 
     def sweep_self_clearance(self, q_a, q_b, samples):
         """Joint angles q_a, q_b [B, n] -> device tensor [B]: the minimum self clearance over the samples + 1
@@ -1016,19 +1035,11 @@ class AnchoredProblem:
     @staticmethod
     def link_foot_host(a, b, c):
         """One (link, sphere centre) pair -> (t, m, d): the foot parameter of link_clearance, m = (1 - t) a + t b - c and
-        d = m.m, in scalar doubles -- the operations of the device pair function (anch_link_foot) in its order."""
-        a, b, c = ([float(v) for v in x] for x in (a, b, c))
-        dx, dy, dz = b[0] - a[0], b[1] - a[1], b[2] - a[2]
-        L2 = dx * dx + dy * dy + dz * dz
-        ux, uy, uz = c[0] - a[0], c[1] - a[1], c[2] - a[2]
-        t = 0.0
-        if L2 > 0.0:
-            t = (ux * dx + uy * dy + uz * dz) / L2
-            t = t if t > 0.0 else 0.0
-            t = t if t < 1.0 else 1.0
-        w = 1.0 - t
-        m = np.array([(w * a[q] + t * b[q]) - c[q] for q in range(3)])
-        return t, m, float(m[0] * m[0] + m[1] * m[1] + m[2] * m[2])
+        d = m.m -- the operations of the device pair function (anch_link_foot) in its order."""
+        a, b, c = (np.asarray(x, dtype=np.float64) for x in (a, b, c))
+        t = _link_foot(a, b, c)[3]
+        m = ((1.0 - t) * a + t * b) - c
+        return float(t), m, float(_dot3(m, m))
 
     def link_ends_host(self, Y_free, W, goal_anchor):
         """Per link: ((A, W_A, i_A), (B, W_B, i_B)) -- position, direction and free-node index of either end at the point
@@ -1090,24 +1101,10 @@ class AnchoredProblem:
     @staticmethod
     def self_feet_host(a1, b1, a2, b2):
         """One (link, link) pair -> (s, t, v, d): the foot parameters of self_clearance, v = (a1 + s d1) - (a2 + t d2)
-        and d = v.v, in scalar doubles -- the operations of the device pair function (anch_self_feet) in its order, so
-        sqrt(d) - rho_l - rho_m is self_clearance's value of the pair bit for bit."""
-        a1, b1, a2, b2 = ([float(x) for x in p] for p in (a1, b1, a2, b2))
-        d1 = [b1[q] - a1[q] for q in range(3)]
-        d2 = [b2[q] - a2[q] for q in range(3)]
-        r = [a1[q] - a2[q] for q in range(3)]
-        dot = lambda x, y: x[0] * y[0] + x[1] * y[1] + x[2] * y[2]      # noqa: E731
-        clamp = lambda x: (x if x < 1.0 else 1.0) if x > 0.0 else 0.0      # noqa: E731
-        a, e, f, c, b = dot(d1, d1), dot(d2, d2), dot(d2, r), dot(d1, r), dot(d1, d2)
-        den = a * e - b * b
-        s = clamp((b * f - c * e) / den) if (a > 0.0 and den > 0.0) else 0.0
-        t = (b * s + f) / e if e > 0.0 else -1.0
-        if t < 0.0:
-            t, s = 0.0, (clamp(-c / a) if a > 0.0 else 0.0)
-        elif t > 1.0:
-            t, s = 1.0, (clamp((b - c) / a) if a > 0.0 else 0.0)
-        v = np.array([(a1[q] + s * d1[q]) - (a2[q] + t * d2[q]) for q in range(3)])
-        return s, t, v, float(v[0] * v[0] + v[1] * v[1] + v[2] * v[2])
+        and d = v.v -- the operations of the device pair function (anch_self_feet) in its order, and the function
+        self_clearance takes its distance from."""
+        s, t, v, d = _segment_feet(*(np.asarray(p, dtype=np.float64) for p in (a1, b1, a2, b2)))
+        return float(s), float(t), v, float(d)
 
     def self_hinge_terms_host(self, Y_free, W, goal_anchor, frozen_st=None):
         """(f, G, H) of the self hinges alone at one point: Y_free, W [Nf, 3], goal_anchor [n_goal * 3], in the
@@ -1164,10 +1161,14 @@ class AnchoredProblem:
     def sweep_clearance_host(self, q_a, q_b, samples):
         """The numpy mirror of sweep_clearance: link_clearance of BatchProblem.seed_points at every sample, the minimum
         over the samples, NaN if any sample is NaN."""
+        return self._sweep_min_host(q_a, q_b, samples, self.link_clearance)
+
+    def _sweep_min_host(self, q_a, q_b, samples, clearance):
+        """clearance (a mirror: full point matrices -> [B]) of BatchProblem.seed_points at every sample of a sweep, and
+        the minimum over the samples."""
         qs = self.sweep_points(q_a, q_b, samples)
         S1, B, n = qs.shape
-        cl = self.link_clearance(self.base.seed_points(qs.reshape(S1 * B, n))).reshape(S1, B)
-        return np.where(np.isnan(cl).any(axis=0), np.nan, np.where(np.isnan(cl), np.inf, cl).min(axis=0))
+        return _nan_min(clearance(self.base.seed_points(qs.reshape(S1 * B, n))).reshape(S1, B), axis=0)
 
     def sweep_clearance(self, q_a, q_b, samples):
         """Joint angles q_a, q_b [B, n] -> device tensor [B]: the minimum link clearance over the samples + 1

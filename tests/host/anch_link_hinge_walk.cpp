@@ -1,14 +1,16 @@
-// tests/host/anch_link_hinge_walk.cpp -- the pair function of the link hinges (anch_link_foot, gik_anch_seed.hip.h) as a
+// tests/host/anch_link_hinge_walk.cpp -- the pair function of the link hinges (anch_link_foot, gik_anch_pairs.h) as a
 // program of its own: walked over random point matrices x the chain's skeleton x spheres on exactly sized heap arrays,
 // zero-length links, links through a centre and nanometre links among them, against a long-double restatement.
 // tests/test_anchored_link_hinges_host.py compiles it (host only, with the address and undefined-behaviour sanitizers)
-// and runs it; it prints "ok ..." and one pinned pair, which must be the numpy mirror's.
+// and runs it; it prints "ok ...", one pinned pair, which must be the numpy mirror's, and the digest of (t, m, d) of every random
+// cell (walk_digest.h).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 
-#include "gik_anch_seed.hip.h"
+#include "gik_anch_pairs.h"
+#include "walk_digest.h"
 
 using namespace gik;
 
@@ -69,6 +71,7 @@ int main() {
     obs[o * 4 + 3] = r * r;
   }
   double worst_t = 0.0, worst_m = 0.0, worst_d = 0.0;
+  WalkDigest dg;
   int clamp0 = 0, clamp1 = 0, inner = 0, zero = 0, active = 0;
   for (int b = 0; b < CELLS; ++b) {
     double *y = Y.data() + (size_t)b * full_N * 3;
@@ -84,6 +87,7 @@ int main() {
       const double *pa = y + la[l] * 3, *pb = y + lb[l] * 3, *s = obs.data() + o * 4;
       double t, m[3], d;
       anch_link_foot(pa, pb, s, t, m, d);
+      dg.add(t), dg.add(m[0]), dg.add(m[1]), dg.add(m[2]), dg.add(d);
       long double tr, mr[3], dr;
       foot_ref(pa, pb, s, tr, mr, dr);
       CHECK(t >= 0.0 && t <= 1.0 && d >= 0.0);
@@ -120,5 +124,6 @@ int main() {
   std::printf("ok cells %d pairs %d zero %d end_a %d end_b %d interior %d active %d worst %.3g %.3g %.3g\n", CELLS,
               CELLS * n_link * n_obs, zero, clamp0, clamp1, inner, active, worst_t, worst_m, worst_d);
   std::printf("pinned t %a m %a %a %a d %a\n", t, m[0], m[1], m[2], d);
+  std::printf("digest %016llx\n", (unsigned long long)dg.h);
   return 0;
 }

@@ -1,13 +1,14 @@
-// tests/host/anch_link_walk.cpp -- the host side of the link clearance and its sweep (gik_anch_seed.hip.h) as a program
+// tests/host/anch_link_walk.cpp -- the host side of the link clearance and its sweep (gik_anch_pairs.h) as a program
 // of its own: anch_link_pair, anch_sweep_interp and anch_sweep_min walked over a few hundred random and degenerate cells
 // on exactly sized heap arrays, against a long-double restatement.  tests/test_anchored_links_host.py compiles it (host
-// only, with the address and undefined-behaviour sanitizers) and runs it; it prints "ok ..." and two pinned values.
+// only, with the address and undefined-behaviour sanitizers) and runs it; it prints "ok ...", two pinned values and the digest of every pair value of the random cells (walk_digest.h).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 
-#include "gik_anch_seed.hip.h"
+#include "gik_anch_pairs.h"
+#include "walk_digest.h"
 
 using namespace gik;
 
@@ -66,6 +67,7 @@ int main() {
     obs[o * 4 + 3] = r * r;
   }
   double worst = 0.0;
+  WalkDigest dg;
   int clamp0 = 0, clamp1 = 0, inner = 0, zero = 0, negative = 0;
   for (int b = 0; b < CELLS; ++b) {
     double *y = Y.data() + (size_t)b * full_N * 3;
@@ -82,6 +84,7 @@ int main() {
       const int l = p / n_obs, o = p - l * n_obs;
       const double *pa = y + la[l] * 3, *pb = y + lb[l] * 3, *s = obs.data() + o * 4;
       const double v = anch_link_pair(pa, pb, s, rho[l]);
+      dg.add(v);
       const long double ref = pair_ref(pa, pb, s, rho[l]);
       const double err = (double)fabsl((long double)v - ref);
       worst = err > worst ? err : worst;
@@ -135,5 +138,6 @@ int main() {
   std::printf("ok cells %d pairs %d zero %d end_a %d end_b %d interior %d colliding %d worst %.3g\n", CELLS,
               CELLS * n_link * n_obs, zero, clamp0, clamp1, inner, negative, worst);
   std::printf("pinned pair %a interp %a\n", anch_link_pair(a, b, s, 0.03), anch_sweep_interp(0.3, -1.7, 3, 7));
+  std::printf("digest %016llx\n", (unsigned long long)dg.h);
   return 0;
 }

@@ -1,18 +1,21 @@
-// tests/host/anch_self_hinge_walk.cpp -- the pair function of the self hinges (anch_self_feet, gik_anch_seed.hip.h) as a
+// tests/host/anch_self_hinge_walk.cpp -- the pair function of the self hinges (anch_self_feet, gik_anch_pairs.h) as a
 // program of its own: walked over the hand-made and planted cells of anch_self_walk.cpp (zero-length, crossing, nanometre,
 // parallel overlapping / disjoint / exact-multiple links) and over 400 random point matrices x every pair of 12 links, on
-// exactly sized heap arrays.  Checked: sqrt(d) - rho - rho' is anch_self_pair's value in all 64 bits; (s, t) lie in [0, 1],
+// exactly sized heap arrays.  Checked: sqrt(d) - rho - rho' is anch_self_pair's value in all 64 bits (true by
+// construction since anch_self_pair calls anch_self_feet; what the bits were before is the digest's to say); (s, t) lie in [0, 1],
 // v is the vector between the points they name and d its square, and |v| is the distance of the two segments, each
 // against a long-double restatement; the residual is finite, and never positive with R = 0.
 // tests/test_anchored_self_hinges_host.py compiles it (host only, with the address and undefined-behaviour sanitizers) and
-// runs it; it prints "ok ..." with the worst differences, and one pinned pair.
+// runs it; it prints "ok ..." with the worst differences, one pinned pair, and the digest of (s, t, v, d) of every random
+// cell (walk_digest.h).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
-#include "gik_anch_seed.hip.h"
+#include "gik_anch_pairs.h"
+#include "walk_digest.h"
 
 using namespace gik;
 
@@ -159,6 +162,7 @@ int main() {
   const int n_pair = (int)pl.size();
   CHECK(n_pair == 66);
   int cells[9] = {0}, active = 0;
+  WalkDigest dg;
   for (int b = 0; b < CELLS; ++b) {
     double *y = Y.data() + (size_t)b * full_N * 3;
     for (int e = 0; e < full_N * 3; ++e) y[e] = uniform(-0.6, 0.6);
@@ -191,6 +195,7 @@ int main() {
       ++cells[cell];
       double s, t, v[3], d;
       anch_self_feet(a1, b1, a2, b2, s, t, v, d);
+      dg.add(s), dg.add(t), dg.add(v[0]), dg.add(v[1]), dg.add(v[2]), dg.add(d);
       active += anch_self_res(0.03 + 0.03, d) > 0.0;
     }
   }
@@ -204,5 +209,6 @@ int main() {
   double s, t, v[3], d;
   anch_self_feet(a1, b1, a2, b2, s, t, v, d);
   std::printf("pinned s %a t %a v %a %a %a d %a value %a\n", s, t, v[0], v[1], v[2], d, std::sqrt(d) - 0.03 - 0.02);
+  std::printf("digest %016llx\n", (unsigned long long)dg.h);
   return 0;
 }

@@ -1,14 +1,16 @@
-// tests/host/anch_self_walk.cpp -- the pair function of the self clearance (anch_self_pair, gik_anch_seed.hip.h) as a
+// tests/host/anch_self_walk.cpp -- the pair function of the self clearance (anch_self_pair, gik_anch_pairs.h) as a
 // program of its own: walked over hand-made cells and over 400 random point matrices x every pair of 12 links, with
 // planted parallel, crossing, zero-length and nanometre-long links, on exactly sized heap arrays, against a long-double
 // restatement.  tests/test_anchored_self_host.py compiles it (host only, with the address and undefined-behaviour
-// sanitizers) and runs it; it prints "ok ..." with the worst difference, and one pinned value.
+// sanitizers) and runs it; it prints "ok ..." with the worst difference, one pinned value, and the digest of every
+// pair value of the random cells (walk_digest.h).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 
-#include "gik_anch_seed.hip.h"
+#include "gik_anch_pairs.h"
+#include "walk_digest.h"
 
 using namespace gik;
 
@@ -132,6 +134,7 @@ int main() {
   const int n_pair = (int)pl.size();
   CHECK(n_pair == 66);
   double worst = 0.0;
+  WalkDigest dg;
   int cell[9] = {0}, negative = 0, den0 = 0;
   for (int b = 0; b < CELLS; ++b) {
     double *y = Y.data() + (size_t)b * full_N * 3;
@@ -163,6 +166,7 @@ int main() {
       const int l = pl[p], k = pm[p];
       const double *a1 = y + la[l] * 3, *b1 = y + lb[l] * 3, *a2 = y + la[k] * 3, *b2 = y + lb[k] * 3;
       const double v = anch_self_pair(a1, b1, a2, b2, rho[l], rho[k]);
+      dg.add(v);
       CHECK(v == v);
       const double err = (double)fabsl((long double)v - pair_ref(a1, b1, a2, b2, rho[l], rho[k]));
       worst = err > worst ? err : worst;
@@ -182,5 +186,6 @@ int main() {
   std::printf(" colliding %d worst %.3g\n", negative, worst);
   const double a1[3] = {0.1, -0.2, 0.3}, b1[3] = {0.7, 0.4, -0.1}, a2[3] = {0.35, 0.2, 0.25}, b2[3] = {-0.15, 0.6, 0.45};
   std::printf("pinned pair %a\n", anch_self_pair(a1, b1, a2, b2, 0.03, 0.02));
+  std::printf("digest %016llx\n", (unsigned long long)dg.h);
   return 0;
 }

@@ -16,6 +16,10 @@ from conftest import REPO, make_graph
 
 # anch_link_foot of a = (.1, -.2, .3), b = (.7, .4, -.1), c = (.35, .2, .25): tests/host/anch_link_hinge_walk.cpp prints it
 PINNED_A, PINNED_B, PINNED_C = (0.1, -0.2, 0.3), (0.7, 0.4, -0.1), (0.35, 0.2, 0.25)
+# the "digest" line of tests/host/anch_link_hinge_walk.cpp (walk_digest.h: FNV-1a over the bits of (t, m, d) of its
+# random cells), as that program prints it when compiled against the headers of c11b7a7, where anch_link_foot stood
+# next to a second copy of its foot parameter
+PARENT_DIGEST = "9bbfbba67255d075"
 
 
 def _rs():
@@ -213,7 +217,7 @@ def test_abi_carries_the_hinges_field():
 
 # ---- 4. the device pair function, walked on the host under sanitizers ----------------------------------------
 def test_pair_function_walked_by_a_sanitized_host_program(tmp_path):
-    """tests/host/anch_link_hinge_walk.cpp: host-only compile of gik_anch_seed.hip.h (no device code, nothing loaded into
+    """tests/host/anch_link_hinge_walk.cpp: host-only compile of gik_anch_pairs.h (no device code, nothing loaded into
     this interpreter), -fsanitize=address,undefined, run as a program.  It walks anch_link_foot over 400 point matrices x
     66 pairs against a long-double restatement and prints one pinned pair, which must be the mirror's, bit for bit."""
     import shutil
@@ -237,4 +241,5 @@ def test_pair_function_walked_by_a_sanitized_host_program(tmp_path):
     tok = lines[1].split()
     assert [tok[0], tok[1], tok[3], tok[7]] == ["pinned", "t", "m", "d"] and len(tok) == 9
     assert [float.fromhex(tok[i]) for i in (2, 4, 5, 6, 8)] == [t, *m, d]
+    assert lines[2].split() == ["digest", PARENT_DIGEST]
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr

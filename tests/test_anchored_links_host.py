@@ -17,6 +17,10 @@ from test_anchored_seeded_host import host_problem
 
 PINNED_PAIR = "0x1.bd10b276dadacp-5"          # a = (.1, -.2, .3), b = (.7, .4, -.1), c = (.35, .2, .25), r^2 = .01, rho = .03
 PINNED_INTERP = "-0x1.1d41d41d41d42p-1"       # (1 - 3/7) 0.3 + (3/7) (-1.7)
+# the "digest" line of tests/host/anch_link_walk.cpp (walk_digest.h: FNV-1a over the bits of every pair value of its
+# random cells), as that program prints it when compiled against the headers of c11b7a7, where anch_link_pair had its
+# foot parameter written out
+PARENT_DIGEST = "675263e7176170bd"
 
 
 def _rs():
@@ -236,7 +240,7 @@ def test_abi_carries_the_link_entry_points():
 
 # ---- 4. the header's helpers in a program of their own, under the sanitizers -------------------------------------
 def test_header_helpers_walked_by_a_sanitized_host_program(tmp_path):
-    """tests/host/anch_link_walk.cpp: host-only compile of gik_anch_seed.hip.h (no device code, nothing loaded into this
+    """tests/host/anch_link_walk.cpp: host-only compile of gik_anch_pairs.h (no device code, nothing loaded into this
     interpreter), -fsanitize=address,undefined, run as a program.  It walks anch_link_pair over 400 point matrices x 66
     pairs against a long-double restatement, anch_sweep_interp and anch_sweep_min, and prints two pinned values, which
     must be the mirror's."""
@@ -257,4 +261,5 @@ def test_header_helpers_walked_by_a_sanitized_host_program(tmp_path):
     lines = r.stdout.strip().splitlines()
     assert lines[0].startswith("ok cells 400 pairs 26400 ") and "FAILED" not in r.stdout
     assert lines[1].split() == ["pinned", "pair", PINNED_PAIR, "interp", PINNED_INTERP]
+    assert lines[2].split() == ["digest", PARENT_DIGEST]
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr

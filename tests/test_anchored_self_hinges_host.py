@@ -21,6 +21,10 @@ RHO = 0.03
 # anch_self_feet of the pinned pair of tests/host/anch_self_walk.cpp: tests/host/anch_self_hinge_walk.cpp prints it
 PINNED = ((0.1, -0.2, 0.3), (0.7, 0.4, -0.1), (0.35, 0.2, 0.25), (-0.15, 0.6, 0.45))
 PINNED_PAIR = "0x1.131b36db275a9p-3"      # anch_self_pair of the same ends with radii 0.03 and 0.02 (test_anchored_self_host.py)
+# the "digest" line of tests/host/anch_self_hinge_walk.cpp (walk_digest.h: FNV-1a over the bits of (s, t, v, d) of its
+# random cells), as that program prints it when compiled against the headers of c11b7a7, where anch_self_feet stood
+# next to a second copy of its branches
+PARENT_DIGEST = "fe2f9f30117cc5f9"
 
 
 def _rs():
@@ -83,7 +87,7 @@ def hinge_configurations(name):
 
 # ---- 1. the device pair function, walked on the host under sanitizers ----------------------------------------
 def test_pair_function_walked_by_a_sanitized_host_program(tmp_path):
-    """tests/host/anch_self_hinge_walk.cpp: host-only compile of gik_anch_seed.hip.h (no device code, nothing loaded into
+    """tests/host/anch_self_hinge_walk.cpp: host-only compile of gik_anch_pairs.h (no device code, nothing loaded into
     this interpreter), -fsanitize=address,undefined, run as a program.  It walks anch_self_feet over the planted cells of
     anch_self_walk.cpp and 400 point matrices x 66 pairs: sqrt(d) - rho - rho' is anch_self_pair's value in all 64 bits,
     and distance, vector and square agree with a long-double restatement to the project's 1e-12 (measured worst: distance
@@ -112,6 +116,7 @@ def test_pair_function_walked_by_a_sanitized_host_program(tmp_path):
     assert [float.fromhex(tok[i]) for i in (2, 4, 6, 7, 8, 10)] == [s, t, *v, d]
     assert 0.0 < s < 1.0 and t == 0.0      # (the far link's start is the nearest point)
     assert float(np.sqrt(d) - 0.03 - 0.02).hex() == tok[12] == PINNED_PAIR
+    assert lines[2].split() == ["digest", PARENT_DIGEST]
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
 
 

@@ -16,7 +16,11 @@ import pytest
 
 from conftest import REPO, make_graph
 
-PINNED_PAIR = "0x1.131b36db275a9p-3"      # the last line of tests/host/anch_self_walk.cpp: its four ends, radii 0.03 and 0.02
+PINNED_PAIR = "0x1.131b36db275a9p-3"      # the pinned line of tests/host/anch_self_walk.cpp: its four ends, radii 0.03 and 0.02
+# the "digest" line of tests/host/anch_self_walk.cpp (walk_digest.h: FNV-1a over the bits of every pair value of its
+# random cells), as that program prints it when compiled against the headers of c11b7a7, where anch_self_pair was a
+# copy of anch_self_feet's branches
+PARENT_DIGEST = "a918a60f3b204b35"
 RHO = 0.03
 
 
@@ -250,7 +254,7 @@ def test_abi_carries_the_self_entry_points():
 
 # ---- 4. the pair function in a program of its own, under the sanitizers ------------------------------------------
 def test_pair_function_walked_by_a_sanitized_host_program(tmp_path):
-    """tests/host/anch_self_walk.cpp: host-only compile of gik_anch_seed.hip.h (no device code, nothing loaded into this
+    """tests/host/anch_self_walk.cpp: host-only compile of gik_anch_pairs.h (no device code, nothing loaded into this
     interpreter), -fsanitize=address,undefined, run as a program.  It walks anch_self_pair over hand-made cells and 400
     point matrices x 66 pairs against a long-double restatement (measured worst difference: 4.9e-16; the bar is the
     1e-12 the project holds device against mirror to), and prints one pinned value, which must be the mirror's."""
@@ -271,4 +275,5 @@ def test_pair_function_walked_by_a_sanitized_host_program(tmp_path):
     assert lines[0].startswith("ok cells 400 pairs 26400 ") and "FAILED" not in r.stdout
     assert float(lines[0].split()[-1]) < 1e-12
     assert lines[1].split() == ["pinned", "pair", PINNED_PAIR]
+    assert lines[2].split() == ["digest", PARENT_DIGEST]
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr

@@ -5,14 +5,17 @@ bit for bit.
 A table of scenarios (SCENARIOS) runs solve_batch, solve_trajectory, AnchoredProblem.solve / solve_trajectory,
 Template.ik and Template.anchored_ik over the paths the fold touched: cold, seeded ([n] and [B, n]), Y_init, restarts
 (cold, seeded, local), the host paths of graphs off the device pipeline, planar poses, tracking with and without the
-point matrices, both clearance modes, the sweep, link hinges, and reused `out` buffers.  Every returned array is hashed
+point matrices, the clearance modes (nodes, links, links+self), per-goal scenes, the sweep, link and self hinges, and
+reused `out` buffers.  Every returned array is hashed
 by key (sha256 over dtype, shape and bytes; not hashed: time, solve_time, inner_executed, flags and keys that begin
 with "_") and compared with tests/golden/python_layer_parent.json, which tools/python_layer_digest.py recorded on the
 MI355X from a checkout of the parent commit with this table.  The recording refuses a file in which a restart scenario
 improved no goal (attempt all zero) or a clearance scenario has no finite clearance; the test checks the same of the
 file it reads, so no scenario passes on a path that did nothing.  (planar_cold was recorded again when prep_quad_kernel's
 K x K Jacobi schedule became a function of the goal alone, docs/NOTEBOOK.md 36: the floating-point arrays moved in their
-last bits, every count stayed; the entry says so.)
+last bits, every count stayed; the entry says so.  The file was recorded again from a checkout of c11b7a7 when the
+self clearance, the scenes and the self hinges joined the table, docs/NOTEBOOK.md 40: every hash that was there before
+came out unchanged.)
 
 Shapes: B = 5 goals (a multiple of nothing), trajectories of L = 3 waypoints for B = 4 paths.  Inputs: conftest.make_graph
 and the inputs of the anchored host tests (collision_input, tracking_input, TWIN_MAXITER, TWIN_SEED); fixed seeds."""
@@ -94,11 +97,13 @@ def plain_paths():
 
 
 @functools.lru_cache(maxsize=None)
-def anchored(maxiter=None, link_hinges=False):
-    """One AnchoredProblem (UR10 + table, skeleton links) per iteration budget and hinge setting."""
+def anchored(maxiter=None, link_hinges=False, self_pairs=None, self_hinges=False):
+    """One AnchoredProblem (UR10 + table, skeleton links) per iteration budget and hinge setting; with self pairs the
+    links are capsules of 3 cm."""
     robot, graph = make_graph("ur10_table")
     params = None if maxiter is None else {"maxiter": maxiter}
-    return robot, _rs().AnchoredProblem(graph, params=params, link_hinges=link_hinges)
+    return robot, _rs().AnchoredProblem(graph, params=params, link_hinges=link_hinges, self_pairs=self_pairs,
+                                        self_hinges=self_hinges, link_radius=0.0 if self_pairs is None else 0.03)
 
 
 @functools.lru_cache(maxsize=None)
@@ -153,18 +158,22 @@ def _track(start, **kw):
     return run
 
 
-def _anch(maxiter=None, seeded=False, link_hinges=False, **kw):
+def _anch(maxiter=None, seeded=False, link_hinges=False, self_pairs=None, self_hinges=False, scenes=False, **kw):
     def run():
         T, seeds = anchored_goals()
-        ap = anchored(maxiter, link_hinges)[1]
-        return host(ap.solve(T, q_init=seeds if seeded else None, **kw))
+        ap = anchored(maxiter, link_hinges, self_pairs, self_hinges)[1]
+        extra = {}
+        if scenes:      # three scenes, goal b in scene b % 3: the table, the table 0.2 m further in x, its first ten spheres
+            extra = dict(scenes=ap.scene_set([ap.obstacles, ap.obstacles + np.array([0.2, 0.0, 0.0, 0.0]), ap.obstacles[:10]]),
+                         scene_id=(np.arange(B) % 3).astype(np.int32))
+        return host(ap.solve(T, q_init=seeds if seeded else None, **kw, **extra))
     return run
 
 
-def _anch_track(maxiter=None, start="own", **kw):
+def _anch_track(maxiter=None, start="own", self_pairs=None, **kw):
     def run():
         T, q_own, q_hit = anchored_paths()
-        ap = anchored(maxiter)[1]
+        ap = anchored(maxiter, False, self_pairs)[1]
         return triple(ap.solve_trajectory(T, q_own if start == "own" else q_hit, **kw))
     return run
 
@@ -226,6 +235,12 @@ SCENARIOS = {
     "anch_track_retry_clearance_links": _anch_track(TWIN_MAXITER, "hit", retries=1, retry_seed=TWIN_SEED, retry_spread=0.3,
                                                     clearance_mode="links"),
     "anch_hinges_seeded_clearance_links": _anch(seeded=True, link_hinges=True, clearance_mode="links"),
+    # anchored: self pairs ("auto", capsules of 3 cm) and per-goal scenes
+    "anch_self_cold_clearance_links_self": _anch(self_pairs="auto", clearance=True, clearance_mode="links+self"),
+    "anch_scenes_seeded_clearance_links": _anch(seeded=True, scenes=True, clearance_mode="links"),
+    "anch_self_hinges_seeded_clearance_links_self": _anch(seeded=True, self_pairs="auto", self_hinges=True,
+                                                          clearance_mode="links+self"),
+    "anch_self_track_sweep_clearance_links_self": _anch_track(self_pairs="auto", sweep=2, clearance_mode="links+self"),
     # reused buffers
     "reuse_ik": _reuse_ik,
     "reuse_anchored_ik_clearance": _reuse_anchored_ik,
