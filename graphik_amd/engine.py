@@ -115,6 +115,25 @@ def check_retry_args(retries, pos_tol, rot_tol, q_limits, n, clear_tol=None, ret
     return int(retries), lo, hi
 
 
+def _retry_opts(retries, retry_seed, pos_tol, rot_tol, q_lo, q_hi, mode=None, clear_tol=None, retry_spread=0.0):
+    """Checked restart arguments -> the options record of the restart entries: gik_retry_opts (Template.ik), or with
+    `mode` (the clearance mode, from check_clearance_mode) and clear_tol gik_anchored_retry_opts (Template.anchored_ik).
+    q_lo / q_hi: the limits on the device.  retries == 0 -- attempt 0 alone, the merged clearance of "links+self" --
+    draws no seeds: the seed, the limits and the spread stay zero whatever was passed."""
+    opts = _ffi.RetryOpts() if mode is None else _ffi.AnchoredRetryOpts(clearance_mode=mode, clear_tol=float(clear_tol))
+    opts.retries, opts.pos_tol, opts.rot_tol = int(retries), float(pos_tol), float(rot_tol)
+    if retries:
+        opts.seed, opts.d_q_lo, opts.d_q_hi = int(retry_seed) & (2 ** 64 - 1), q_lo.data_ptr(), q_hi.data_ptr()
+        if mode is not None:
+            opts.spread = float(retry_spread)
+    return opts
+
+
+def workspace(nbytes, device):
+    """A device buffer of at least nbytes bytes (what a gik_*_ws_bytes query reported) as float64, never empty."""
+    return torch.empty(max((nbytes + 7) // 8, 1), dtype=torch.float64, device=device)
+
+
 def check_clearance_mode(clearance_mode, has_links=True, has_self=True):
     """clearance_mode of an anchored solve -> gik_anchored_retry_opts.clearance_mode (0 nodes, 1 links, 2 links+self),
     checked on the host before any device call: ValueError for another word, for "links" where no links are attached and
@@ -126,6 +145,13 @@ def check_clearance_mode(clearance_mode, has_links=True, has_self=True):
     if clearance_mode == "links+self" and not has_self:
         raise ValueError("clearance_mode='links+self' needs self pairs: this problem was built without self_pairs")
     return _ffi.CLEARANCE_MODES[clearance_mode]
+
+
+def restart_like(retries, clearance_mode, clearance=True, scenes=None):
+    """Does an anchored solve run on the restart entries (gik_anchored_ik_batch_retry[_scenes]) and their workspace
+    "retry_ws"?  With retries > 0; and in "links+self" with a clearance and neither restarts nor scenes, which is attempt
+    0 of that entry alone.  Every other solve runs on the scratch "ws"."""
+    return bool(retries) or (clearance_mode == "links+self" and bool(clearance) and scenes is None)
 
 
 def pack_scenes(scenes, stride=None):
@@ -271,33 +297,32 @@ class Template:
         self.params["solver"] = self.solver
         h = C.c_void_p()
         self.anchored = anchored is not None
-        with torch.cuda.device(self.device):
-            if anchored is None:
-                _ffi.check(self.lib.gik_template_create(C.byref(d), C.byref(h)))
-            else:
-                ad, keep = _ffi.AnchoredDesc(), {}
+        if anchored is None:
+            self._call("gik_template_create", C.byref(d), C.byref(h))
+        else:
+            ad, keep = _ffi.AnchoredDesc(), {}
 
-                def arr(name, dt):
-                    keep[name] = np.ascontiguousarray(anchored[name], dtype=dt)
-                    return keep[name].ctypes.data_as(C.POINTER(C.c_double if dt == np.float64 else C.c_int32))
+            def arr(name, dt):
+                keep[name] = np.ascontiguousarray(anchored[name], dtype=dt)
+                return keep[name].ctypes.data_as(C.POINTER(C.c_double if dt == np.float64 else C.c_int32))
 
-                ad.anchor_pos = arr("anchor_pos", np.float64)
-                ad.n_anchor = len(keep["anchor_pos"])
-                ad.n_goal_anchor = int(anchored["n_goal_anchor"])
-                ad.term_target = arr("term_target", np.float64)
-                assert len(keep["term_target"]) == self.T
-                ad.pin_node, ad.pin_anchor = arr("pin_node", np.int32), arr("pin_anchor", np.int32)
-                ad.pin_kind, ad.pin_target = arr("pin_kind", np.int32), arr("pin_target", np.float64)
-                ad.n_pin = len(keep["pin_node"])
-                ad.obs = arr("obs", np.float64)
-                ad.n_obs = len(keep["obs"])
-                ad.obs_node_mask = arr("obs_node_mask", np.int32)
-                ad.full_N = int(anchored["full_N"])
-                ad.free_full_index = arr("free_full_index", np.int32)
-                ad.anchor_full_index = arr("anchor_full_index", np.int32)
-                ad.axis_length = float(anchored["axis_length"])
-                self.n_goal_anchor, self.full_N = ad.n_goal_anchor, ad.full_N
-                _ffi.check(self.lib.gik_template_create_anchored(C.byref(d), C.byref(ad), C.byref(h)))
+            ad.anchor_pos = arr("anchor_pos", np.float64)
+            ad.n_anchor = len(keep["anchor_pos"])
+            ad.n_goal_anchor = int(anchored["n_goal_anchor"])
+            ad.term_target = arr("term_target", np.float64)
+            assert len(keep["term_target"]) == self.T
+            ad.pin_node, ad.pin_anchor = arr("pin_node", np.int32), arr("pin_anchor", np.int32)
+            ad.pin_kind, ad.pin_target = arr("pin_kind", np.int32), arr("pin_target", np.float64)
+            ad.n_pin = len(keep["pin_node"])
+            ad.obs = arr("obs", np.float64)
+            ad.n_obs = len(keep["obs"])
+            ad.obs_node_mask = arr("obs_node_mask", np.int32)
+            ad.full_N = int(anchored["full_N"])
+            ad.free_full_index = arr("free_full_index", np.int32)
+            ad.anchor_full_index = arr("anchor_full_index", np.int32)
+            ad.axis_length = float(anchored["axis_length"])
+            self.n_goal_anchor, self.full_N = ad.n_goal_anchor, ad.full_N
+            self._call("gik_template_create_anchored", C.byref(d), C.byref(ad), C.byref(h))
         self._h = h
         self.n_link = None      # (attach_links)
         self.link_hinges = False
@@ -312,7 +337,7 @@ class Template:
         """What the library decided for this handle (gik_template_get_info); read again after attach_pipeline,
         which decides the prepare kernel."""
         info = _ffi.TemplateInfo()
-        _ffi.check(self.lib.gik_template_get_info(self._h, C.byref(info)))
+        self._call("gik_template_get_info", self._h, C.byref(info))
         self.info = {f: getattr(info, f) for f, _ in _ffi.TemplateInfo._fields_ if f != "reserved"}
 
     @classmethod
@@ -336,9 +361,8 @@ class Template:
         if len(terms) != len(w):
             raise ValueError("one weight per term")
         n = 0 if self.claim_order == "off" else len(terms)
-        with torch.cuda.device(self.device):
-            _ffi.check(self.lib.gik_template_set_claim_key(self._h, n, terms.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                           w.ctypes.data_as(C.POINTER(C.c_double))))
+        self._call("gik_template_set_claim_key", self._h, n, terms.ctypes.data_as(C.POINTER(C.c_int32)),
+                   w.ctypes.data_as(C.POINTER(C.c_double)))
         self._read_info()
 
     def claim_order_of(self, keys):
@@ -346,16 +370,14 @@ class Template:
         (gik_claim_order_sort): stable, NaN last."""
         k = torch.as_tensor(keys, dtype=torch.float32).to(self.device).contiguous()
         order = torch.full((k.numel(),), -1, dtype=torch.int32, device=self.device)
-        with torch.cuda.device(self.device):
-            _ffi.check(self.lib.gik_claim_order_sort(k.data_ptr(), k.numel(), order.data_ptr(), self._stream()))
+        self._call("gik_claim_order_sort", k.data_ptr(), k.numel(), order.data_ptr(), self._stream())
         return order
 
     def claim_keys(self, targets):
         """targets [B,T] -> the claim keys [B] float32 of this template (gik_claim_order_keys)."""
         t = _dev(targets, self.device)
         keys = torch.empty(t.shape[0], dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _ffi.check(self.lib.gik_claim_order_keys(self._h, t.data_ptr(), t.shape[0], keys.data_ptr(), self._stream()))
+        self._call("gik_claim_order_keys", self._h, t.data_ptr(), t.shape[0], keys.data_ptr(), self._stream())
         return keys
 
     # -- helpers ------------------------------------------------------------------------------
@@ -372,6 +394,14 @@ class Template:
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _call(self, name, *args):
+        """Every call of an export that returns a status code: `name` is looked up in the library and called with `args`
+        while this template's device is the current one; a status other than 0 raises GikError with gik_last_error().
+        (The size queries -- gik_*_ws_bytes, gik_anchored_ws_doubles -- return sizes and launch nothing: they are called
+        directly.)"""
+        with torch.cuda.device(self.device):
+            _ffi.check(getattr(self.lib, name)(*args))
 
     def _vec(self, Y):
         Y = _dev(Y, self.device)
@@ -395,18 +425,14 @@ class Template:
         Y, B = self._vec(Y)
         t = self._tg(targets, B)
         out = torch.empty(B, dtype=torch.float64, device=self.device)
-        with torch.cuda.device(self.device):
-            _ffi.check(self.lib.gik_cost(self._h, Y.data_ptr(), t.data_ptr(), B, out.data_ptr(),
-                                         self._stream()))
+        self._call("gik_cost", self._h, Y.data_ptr(), t.data_ptr(), B, out.data_ptr(), self._stream())
         return out
 
     def grad(self, Y, targets):
         Y, B = self._vec(Y)
         t = self._tg(targets, B)
         out = torch.empty_like(Y)
-        with torch.cuda.device(self.device):
-            _ffi.check(self.lib.gik_grad(self._h, Y.data_ptr(), t.data_ptr(), B, out.data_ptr(),
-                                         self._stream()))
+        self._call("gik_grad", self._h, Y.data_ptr(), t.data_ptr(), B, out.data_ptr(), self._stream())
         return out.reshape(B, self.N, self.k)
 
     def cost_and_grad(self, Y, targets):
@@ -415,9 +441,7 @@ class Template:
         t = self._tg(targets, B)
         f = torch.empty(B, dtype=torch.float64, device=Y.device)
         out = torch.empty_like(Y)
-        with torch.cuda.device(self.device):
-            _ffi.check(self.lib.gik_cost_and_grad(self._h, Y.data_ptr(), t.data_ptr(), B, f.data_ptr(),
-                                                  out.data_ptr(), self._stream()))
+        self._call("gik_cost_and_grad", self._h, Y.data_ptr(), t.data_ptr(), B, f.data_ptr(), out.data_ptr(), self._stream())
         return f, out.reshape(B, self.N, self.k)
 
     def hess(self, Y, W, targets):
@@ -425,18 +449,14 @@ class Template:
         W, _ = self._vec(W)
         t = self._tg(targets, B)
         out = torch.empty_like(Y)
-        with torch.cuda.device(self.device):
-            _ffi.check(self.lib.gik_hess(self._h, Y.data_ptr(), W.data_ptr(), t.data_ptr(), B,
-                                         out.data_ptr(), self._stream()))
+        self._call("gik_hess", self._h, Y.data_ptr(), W.data_ptr(), t.data_ptr(), B, out.data_ptr(), self._stream())
         return out.reshape(B, self.N, self.k)
 
     def proj(self, Y, Z):
         Y, B = self._vec(Y)
         Z, _ = self._vec(Z)
         out = torch.empty_like(Y)
-        with torch.cuda.device(self.device):
-            _ffi.check(self.lib.gik_proj(self._h, Y.data_ptr(), Z.data_ptr(), B, out.data_ptr(),
-                                         self._stream()))
+        self._call("gik_proj", self._h, Y.data_ptr(), Z.data_ptr(), B, out.data_ptr(), self._stream())
         return out.reshape(B, self.N, self.k)
 
     # -- device pre/post-processing ----------------------------------------------------------
@@ -492,10 +512,9 @@ class Template:
             d.goal_pair_b = arr("gb", goal_pair_b, np.int32)
             if ee_goal_len is not None:                  # planar trees: the link parent(e) -> e per end effector
                 d.ee_goal_len = arr("el", ee_goal_len, np.float64)
-        with torch.cuda.device(self.device):
-            _ffi.check(self.lib.gik_pipeline_attach(self._h, C.byref(d)))
-            for e, (x, y) in (point_axis or {}).items():
-                _ffi.check(self.lib.gik_pipeline_set_point_axis(self._h, int(e), float(x), float(y)))
+        self._call("gik_pipeline_attach", self._h, C.byref(d))
+        for e, (x, y) in (point_axis or {}).items():
+            self._call("gik_pipeline_set_point_axis", self._h, int(e), float(x), float(y))
         self.n_joints = int(d.n_joints)
         self.has_pipeline = True
         self._read_info()
@@ -514,11 +533,8 @@ class Template:
         targets = torch.empty(B, self.T, dtype=torch.float64, device=self.device)
         Y0 = torch.empty(B, self.N * self.k, dtype=torch.float64, device=self.device)
         Kc = torch.zeros(B, dtype=torch.int32, device=self.device) if return_K else None
-        with torch.cuda.device(self.device):
-            _ffi.check(self.lib.gik_prepare_batch(self._h, T.data_ptr(), B, targets.data_ptr(),
-                                                  Y0.data_ptr(),
-                                                  Kc.data_ptr() if return_K else None,
-                                                  self._stream()))
+        self._call("gik_prepare_batch", self._h, T.data_ptr(), B, targets.data_ptr(), Y0.data_ptr(),
+                   Kc.data_ptr() if return_K else None, self._stream())
         Y0 = Y0.reshape(B, self.N, self.k)
         return (targets, Y0, Kc) if return_K else (targets, Y0)
 
@@ -533,10 +549,8 @@ class Template:
                "lb": torch.empty(B, self.N, self.N, **f64), "ub": torch.empty(B, self.N, self.N, **f64),
                "eig": torch.empty(B, 3, self.N, **f64)}
         dg = _ffi.PrepareDiag(out["lb"].data_ptr(), out["ub"].data_ptr(), out["eig"].data_ptr())
-        with torch.cuda.device(self.device):
-            _ffi.check(self.lib.gik_prepare_batch_debug(self._h, T.data_ptr(), B, out["targets"].data_ptr(),
-                                                        out["Y_init"].data_ptr(), out["K"].data_ptr(),
-                                                        C.byref(dg), self._stream()))
+        self._call("gik_prepare_batch_debug", self._h, T.data_ptr(), B, out["targets"].data_ptr(), out["Y_init"].data_ptr(),
+                   out["K"].data_ptr(), C.byref(dg), self._stream())
         out["Y_init"] = out["Y_init"].reshape(B, self.N, self.k)
         return out
 
@@ -547,10 +561,8 @@ class Template:
         q = torch.empty(B, self.n_joints, dtype=torch.float64, device=self.device)
         pe = torch.empty(B, dtype=torch.float64, device=self.device)
         re = torch.empty(B, dtype=torch.float64, device=self.device)
-        with torch.cuda.device(self.device):
-            _ffi.check(self.lib.gik_recover_batch(self._h, Y.data_ptr(), T.data_ptr(), B,
-                                                  q.data_ptr(), pe.data_ptr(), re.data_ptr(),
-                                                  self._stream()))
+        self._call("gik_recover_batch", self._h, Y.data_ptr(), T.data_ptr(), B, q.data_ptr(), pe.data_ptr(), re.data_ptr(),
+                   self._stream())
         return q, pe, re
 
     def _seed_angles(self, q_init, B):
@@ -567,9 +579,8 @@ class Template:
         q = self._seed_angles(q_init, B)
         targets = torch.empty(B, self.T, dtype=torch.float64, device=self.device)
         Y0 = torch.empty(B, self.N * self.k, dtype=torch.float64, device=self.device)
-        with torch.cuda.device(self.device):
-            _ffi.check(self.lib.gik_seed_batch(self._h, T.data_ptr(), q.data_ptr(), B, targets.data_ptr(),
-                                               Y0.data_ptr(), self._stream()))
+        self._call("gik_seed_batch", self._h, T.data_ptr(), q.data_ptr(), B, targets.data_ptr(), Y0.data_ptr(),
+                   self._stream())
         return targets, Y0.reshape(B, self.N, self.k)
 
     def ik(self, T_goal, out=None, q_init=None, retries=0, retry_seed=0, pos_tol=0.01, rot_tol=0.01, q_limits=None):
@@ -595,19 +606,16 @@ class Template:
         q0 = None if q_init is None else self._seed_angles(q_init, B)
         answer = [out[key].data_ptr() for key in ("targets", "Y", "stats", "q", "pos_err", "rot_err")]
         extras = {}
-        with torch.cuda.device(self.device):
-            if retries:
-                attempt, ws, q_lo, q_hi = self._retry_buffers(out, B, int(self.lib.gik_retry_ws_bytes(self._h, B)), lo, hi)
-                opts = _ffi.RetryOpts(retries=retries, seed=int(retry_seed) & (2 ** 64 - 1), pos_tol=float(pos_tol),
-                                      rot_tol=float(rot_tol), d_q_lo=q_lo.data_ptr(), d_q_hi=q_hi.data_ptr())
-                _ffi.check(self.lib.gik_ik_batch_retry(self._h, T.data_ptr(), None if q0 is None else q0.data_ptr(), B,
-                                                       C.byref(opts), ws.data_ptr(), *answer, attempt.data_ptr(),
-                                                       self._stream()))
-                extras = {"attempt": attempt, "_retry_ws": ws}      # (the workspace lives as long as the result)
-            elif q0 is None:
-                _ffi.check(self.lib.gik_ik_batch(self._h, T.data_ptr(), B, *answer, self._stream()))
-            else:
-                _ffi.check(self.lib.gik_ik_batch_seeded(self._h, T.data_ptr(), q0.data_ptr(), B, *answer, self._stream()))
+        if retries:
+            attempt, ws, q_lo, q_hi = self._retry_buffers(out, B, self.retry_ws_bytes(B), lo, hi)
+            opts = _retry_opts(retries, retry_seed, pos_tol, rot_tol, q_lo, q_hi)
+            self._call("gik_ik_batch_retry", self._h, T.data_ptr(), None if q0 is None else q0.data_ptr(), B, C.byref(opts),
+                       ws.data_ptr(), *answer, attempt.data_ptr(), self._stream())
+            extras = {"attempt": attempt, "_retry_ws": ws}      # (the workspace lives as long as the result)
+        elif q0 is None:
+            self._call("gik_ik_batch", self._h, T.data_ptr(), B, *answer, self._stream())
+        else:
+            self._call("gik_ik_batch_seeded", self._h, T.data_ptr(), q0.data_ptr(), B, *answer, self._stream())
         return _result(out, (B, self.N, self.k), extras)
 
     def _retry_buffers(self, out, B, nbytes, lo, hi, limits=True):
@@ -619,12 +627,21 @@ class Template:
             attempt = torch.empty(B, dtype=torch.int32, device=self.device)
         ws = out.get("retry_ws")
         if ws is None or ws.numel() * ws.element_size() < nbytes:
-            ws = torch.empty(max((nbytes + 7) // 8, 1), dtype=torch.float64, device=self.device)
+            ws = workspace(nbytes, self.device)
         if not limits:      # (a call with retries = 0 draws no seeds)
             return attempt, ws, None, None
         q_lo = out["q_lo"] if "q_lo" in out else _dev(lo, self.device)
         q_hi = out["q_hi"] if "q_hi" in out else _dev(hi, self.device)
         return attempt, ws, q_lo, q_hi
+
+    def retry_ws_bytes(self, B):
+        """Bytes of the restart workspace ("retry_ws") of one ik call of B goals with retries > 0 (gik_retry_ws_bytes)."""
+        return int(self.lib.gik_retry_ws_bytes(self._h, B))
+
+    def anchored_sweep_ws_bytes(self, base, B, samples):
+        """Bytes of the workspace ("ws") of one anchored_sweep_clearance[s] call of B rows and `samples` samples
+        (gik_anchored_sweep_ws_bytes)."""
+        return int(self.lib.gik_anchored_sweep_ws_bytes(self._h, base._h, B, samples))
 
     def anchored_retry_ws_bytes(self, base, B, scenes=False):
         """Bytes of the restart workspace ("retry_ws") of one anchored_ik call of B goals with retries > 0:
@@ -658,9 +675,8 @@ class Template:
         ws = torch.empty(max(int(self.lib.gik_anchored_ws_doubles(self._h, base._h, B)), 1), **f64)
         Y_free = torch.empty(B, self.N * 3, **f64)
         goal = torch.empty(B, self.n_goal_anchor * 3, **f64)
-        with torch.cuda.device(self.device):
-            _ffi.check(self.lib.gik_anchored_seed_batch(self._h, base._h, T.data_ptr(), q.data_ptr(), B, ws.data_ptr(),
-                                                        Y_free.data_ptr(), goal.data_ptr(), self._stream()))
+        self._call("gik_anchored_seed_batch", self._h, base._h, T.data_ptr(), q.data_ptr(), B, ws.data_ptr(),
+                   Y_free.data_ptr(), goal.data_ptr(), self._stream())
         return Y_free.reshape(B, self.N, 3), goal
 
     def anchored_clearance(self, Y_full, scenes=None, scene_id=None):
@@ -669,11 +685,11 @@ class Template:
         obstacles; +inf without obstacles.  scenes (a SceneSet) / scene_id [B]: goal b against the spheres of its
         scene instead of the template's own (gik_anchored_clearance_scenes)."""
         assert self.anchored
-        return self._clearance_of(self.lib.gik_anchored_clearance, self.lib.gik_anchored_clearance_scenes, Y_full, scenes, scene_id)
+        return self._clearance_of("gik_anchored_clearance", Y_full, scenes, scene_id)
 
-    def _clearance_of(self, clear_fn, scene_fn, Y_full, scenes=None, scene_id=None):
-        """Full point matrices [B, full_N, 3] (or [full_N, 3]) as a contiguous [B, full_N*3] buffer -> clear_fn's [B], or
-        with a scene set scene_fn's."""
+    def _clearance_of(self, name, Y_full, scenes=None, scene_id=None):
+        """Full point matrices [B, full_N, 3] (or [full_N, 3]) as a contiguous [B, full_N*3] buffer -> the [B] of the
+        export `name`, or with a scene set of `name`_scenes."""
         Y = _dev(Y_full, self.device)
         if Y.dim() == 2:
             Y = Y[None]
@@ -682,11 +698,10 @@ class Template:
         sc, ids = self._scene_desc(scenes, scene_id, B)
         Y = Y.reshape(B, self.full_N * 3).contiguous()
         out = torch.empty(B, dtype=torch.float64, device=self.device)
-        with torch.cuda.device(self.device):
-            if sc is None:
-                _ffi.check(clear_fn(self._h, Y.data_ptr(), B, out.data_ptr(), self._stream()))
-            else:
-                _ffi.check(scene_fn(self._h, Y.data_ptr(), B, C.byref(sc), out.data_ptr(), self._stream()))
+        if sc is None:
+            self._call(name, self._h, Y.data_ptr(), B, out.data_ptr(), self._stream())
+        else:
+            self._call(name + "_scenes", self._h, Y.data_ptr(), B, C.byref(sc), out.data_ptr(), self._stream())
         return out
 
     def _scene_desc(self, scenes, scene_id, B, checked=False):
@@ -722,8 +737,7 @@ class Template:
         d = _ffi.LinkDesc(n_link=len(a), hinges=int(hinges), link_a=a.ctypes.data_as(C.POINTER(C.c_int32)),
                           link_b=b.ctypes.data_as(C.POINTER(C.c_int32)),
                           link_radius=r.ctypes.data_as(C.POINTER(C.c_double)))
-        with torch.cuda.device(self.device):
-            _ffi.check(self.lib.gik_anchored_attach_links(self._h, C.byref(d)))
+        self._call("gik_anchored_attach_links", self._h, C.byref(d))
         self.n_link = len(a)
         self.link_hinges = bool(hinges)
         self._read_info()      # (hinges: other kernels, LDS bytes and occupancy)
@@ -733,8 +747,7 @@ class Template:
         minimum over the attached links and the obstacles of the distance from the sphere to the link's capsule;
         +inf without obstacles or links.  scenes / scene_id: as anchored_clearance (gik_anchored_link_clearance_scenes)."""
         assert self.anchored
-        return self._clearance_of(self.lib.gik_anchored_link_clearance, self.lib.gik_anchored_link_clearance_scenes, Y_full,
-                                  scenes, scene_id)
+        return self._clearance_of("gik_anchored_link_clearance", Y_full, scenes, scene_id)
 
     def attach_self_pairs(self, pair_l, pair_m):
         """The link pairs of the self clearance (gik_anchored_attach_self_pairs), once, after attach_links: pair p is
@@ -744,9 +757,8 @@ class Template:
         m = np.ascontiguousarray(pair_m, dtype=np.int32).reshape(-1)
         if len(l) != len(m):
             raise ValueError("pair_l and pair_m must have one entry per pair")
-        with torch.cuda.device(self.device):
-            _ffi.check(self.lib.gik_anchored_attach_self_pairs(self._h, len(l), l.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                               m.ctypes.data_as(C.POINTER(C.c_int32))))
+        self._call("gik_anchored_attach_self_pairs", self._h, len(l), l.ctypes.data_as(C.POINTER(C.c_int32)),
+                   m.ctypes.data_as(C.POINTER(C.c_int32)))
         self.n_self = len(l)
 
     def attach_self_hinges(self):
@@ -754,8 +766,7 @@ class Template:
         become terms of the solve -- every later call on this template, the known-answer entry points included, runs
         the self builds of its kernels; self.self_hinges and bit 4 of self.info["anchored"] (5, with link hinges 7) say so."""
         assert self.anchored
-        with torch.cuda.device(self.device):
-            _ffi.check(self.lib.gik_anchored_attach_self_hinges(self._h))
+        self._call("gik_anchored_attach_self_hinges", self._h)
         self.self_hinges = True
         self._read_info()      # (other kernels, LDS bytes and occupancy)
 
@@ -763,41 +774,25 @@ class Template:
         """Full point matrices [B, full_N, 3] -> self clearance [B] on the device (gik_anchored_self_clearance): the
         minimum over the attached link pairs of the distance between the two capsules; +inf without pairs."""
         assert self.anchored
-        return self._clearance_of(self.lib.gik_anchored_self_clearance, None, Y_full)
+        return self._clearance_of("gik_anchored_self_clearance", Y_full)
 
     def anchored_sweep_clearances(self, base, q_a, q_b, samples, link_out=None, self_out=None, ws=None, link=True, self_=True):
         """anchored_sweep_clearance with two outputs from one realization of the samples (gik_anchored_sweep_clearances):
         returns (link [B] or None, self [B] or None) -- link / self_ say which are wanted; link_out / self_out [B] and
         `ws` may be handed in to reuse.  Sampled, not conservative."""
-        assert self.anchored and base.has_pipeline
-        if int(samples) != samples or samples < 1:
-            raise ValueError(f"samples must be an integer of at least 1, got {samples!r}")
-        qa, qb = _dev(q_a, self.device), _dev(q_b, self.device)
-        n = base.n_joints
-        if qa.dim() != 2 or qa.shape[1] != n or qa.shape != qb.shape:
-            raise ValueError(f"q_a and q_b must both have shape [B, {n}], got {list(qa.shape)} and {list(qb.shape)}")
-        qa, qb = qa.contiguous(), qb.contiguous()
-        B, S = qa.shape[0], int(samples)
-        outs = []
-        for want, out in ((link, link_out), (self_, self_out)):
-            if want and out is None:
-                out = torch.empty(B, dtype=torch.float64, device=self.device)
-            assert out is None or (out.is_contiguous() and out.numel() == B)
-            outs.append(out if want else None)
-        nbytes = int(self.lib.gik_anchored_sweep_ws_bytes(self._h, base._h, B, S))
-        if ws is None or ws.numel() * ws.element_size() < nbytes:
-            ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=self.device)
-        with torch.cuda.device(self.device):
-            _ffi.check(self.lib.gik_anchored_sweep_clearances(self._h, base._h, qa.data_ptr(), qb.data_ptr(), B, S, ws.data_ptr(),
-                                                              *(None if o is None else o.data_ptr() for o in outs),
-                                                              self._stream()))
-        return tuple(outs)
+        return tuple(self._sweep("gik_anchored_sweep_clearances", base, q_a, q_b, samples, (link, self_), (link_out, self_out), ws))
 
     def anchored_sweep_clearance(self, base, q_a, q_b, samples, out=None, ws=None):
         """Joint angles q_a, q_b [B,n] (device tensors or arrays) -> [B]: the minimum link clearance over the samples + 1
         configurations on the joint-space line from q_a to q_b (gik_anchored_sweep_clearance).  Sampled, not
         conservative: pick `samples` from the joint step.  `out` [B] and `ws` (gik_anchored_sweep_ws_bytes, as float64)
         may be handed in to reuse."""
+        return self._sweep("gik_anchored_sweep_clearance", base, q_a, q_b, samples, (True,), (out,), ws)[0]
+
+    def _sweep(self, name, base, q_a, q_b, samples, wanted, outs, ws):
+        """The body of both sweep methods: the checks of samples, q_a and q_b, one [B] output per entry of `wanted` -- the
+        caller's tensor from `outs`, a new one where that is None, NULL where it is not wanted --, the workspace, and the
+        call of the export `name`.  Returns the outputs as a list, None for one not wanted."""
         assert self.anchored and base.has_pipeline
         if int(samples) != samples or samples < 1:
             raise ValueError(f"samples must be an integer of at least 1, got {samples!r}")
@@ -807,16 +802,18 @@ class Template:
             raise ValueError(f"q_a and q_b must both have shape [B, {n}], got {list(qa.shape)} and {list(qb.shape)}")
         qa, qb = qa.contiguous(), qb.contiguous()
         B, S = qa.shape[0], int(samples)
-        if out is None:
-            out = torch.empty(B, dtype=torch.float64, device=self.device)
-        nbytes = int(self.lib.gik_anchored_sweep_ws_bytes(self._h, base._h, B, S))
+        res = []
+        for want, out in zip(wanted, outs):
+            if want and out is None:
+                out = torch.empty(B, dtype=torch.float64, device=self.device)
+            assert out is None or (out.is_contiguous() and out.numel() == B)
+            res.append(out if want else None)
+        nbytes = self.anchored_sweep_ws_bytes(base, B, S)
         if ws is None or ws.numel() * ws.element_size() < nbytes:
-            ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=self.device)
-        assert out.is_contiguous() and out.numel() == B
-        with torch.cuda.device(self.device):
-            _ffi.check(self.lib.gik_anchored_sweep_clearance(self._h, base._h, qa.data_ptr(), qb.data_ptr(), B, S,
-                                                             ws.data_ptr(), out.data_ptr(), self._stream()))
-        return out      # (ws goes back to the allocator of this stream, behind the kernels that use it)
+            ws = workspace(nbytes, self.device)
+        self._call(name, self._h, base._h, qa.data_ptr(), qb.data_ptr(), B, S, ws.data_ptr(),
+                   *(None if o is None else o.data_ptr() for o in res), self._stream())
+        return res      # (ws goes back to the allocator of this stream, behind the kernels that use it)
 
     def anchored_ik(self, base, T_goal, q_init=None, out=None, clearance=False, retries=0, retry_seed=0, pos_tol=0.01,
                     rot_tol=0.01, clear_tol=1e-4, retry_spread=0.0, q_limits=None, clearance_mode="nodes", scenes=None,
@@ -851,67 +848,51 @@ class Template:
         assert self.anchored and base.has_pipeline
         mode = check_clearance_mode(clearance_mode, getattr(self, "n_link", None) is not None,
                                     getattr(self, "n_self", None) is not None)
-        merged = mode == _ffi.CLEARANCE_LINKS_SELF and clearance and not retries and scenes is None
+        restart = restart_like(retries, clearance_mode, clearance, scenes)
+        lo = hi = None
         if retries:      # (the clearance always comes back then, whatever `clearance` says)
             retries, lo, hi = check_retry_args(retries, pos_tol, rot_tol, q_limits, base.n_joints, clear_tol=clear_tol,
                                                retry_spread=retry_spread, has_center=q_init is not None)
             clearance = True
         T, B = base._poses(T_goal)
         sc, ids = self._scene_desc(scenes, scene_id, B, scene_id_checked)
-        if out is None:      # (with retries the restart workspace holds the scratch "ws")
-            out = self.alloc_anchored_buffers(base, B, clearance, ws=not (retries or merged))
+        if out is None:      # (the restart workspace holds the scratch "ws")
+            out = self.alloc_anchored_buffers(base, B, clearance, ws=not restart)
         q0 = None if q_init is None else base._seed_angles(q_init, B)
         cl = None
         if clearance:
             cl = out["clearance"] if "clearance" in out else torch.empty(B, dtype=torch.float64, device=self.device)
+        seed_ptr, cl_ptr = (None if t is None else t.data_ptr() for t in (q0, cl))
+        scene = () if sc is None else (C.byref(sc),)      # (the scenes entries take it in front of the workspace)
         answer = [out[key].data_ptr() for key in ("Y", "stats", "q", "pos_err", "rot_err")]
-        with torch.cuda.device(self.device):
-            if retries:
-                nbytes = self.anchored_retry_ws_bytes(base, B, scenes=sc is not None)
-                attempt, ws, q_lo, q_hi = self._retry_buffers(out, B, nbytes, lo, hi)
-                opts = _ffi.AnchoredRetryOpts(retries=retries, clearance_mode=mode, seed=int(retry_seed) & (2 ** 64 - 1),
-                                              pos_tol=float(pos_tol), rot_tol=float(rot_tol), d_q_lo=q_lo.data_ptr(),
-                                              d_q_hi=q_hi.data_ptr(), clear_tol=float(clear_tol), spread=float(retry_spread))
-                seed_ptr = None if q0 is None else q0.data_ptr()
-                if sc is None:
-                    _ffi.check(self.lib.gik_anchored_ik_batch_retry(
-                        self._h, base._h, T.data_ptr(), seed_ptr, B, C.byref(opts), ws.data_ptr(),
-                        *answer, cl.data_ptr(), attempt.data_ptr(), self._stream()))
-                else:
-                    _ffi.check(self.lib.gik_anchored_ik_batch_retry_scenes(
-                        self._h, base._h, T.data_ptr(), seed_ptr, B, C.byref(opts), C.byref(sc), ws.data_ptr(),
-                        *answer, cl.data_ptr(), attempt.data_ptr(), self._stream()))
-                return _result(out, (B, self.full_N, 3), {"clearance": cl, "attempt": attempt, "_retry_ws": ws, "_scene_id": ids})
-            if merged:      # attempt 0 of the restart entry: the call, the link clearance, the self clearance merged into it
-                nbytes = self.anchored_retry_ws_bytes(base, B)
-                attempt, ws, _, _ = self._retry_buffers(out, B, nbytes, None, None, limits=False)
-                opts = _ffi.AnchoredRetryOpts(retries=0, clearance_mode=mode, pos_tol=float(pos_tol), rot_tol=float(rot_tol),
-                                              clear_tol=float(clear_tol))
-                _ffi.check(self.lib.gik_anchored_ik_batch_retry(
-                    self._h, base._h, T.data_ptr(), None if q0 is None else q0.data_ptr(), B, C.byref(opts), ws.data_ptr(),
-                    *answer, cl.data_ptr(), attempt.data_ptr(), self._stream()))
-                return _result(out, (B, self.full_N, 3), {"clearance": cl, "_retry_ws": ws, "_attempt": attempt})
+        after = None      # the clearance export to launch behind the solve, where the entry does not measure it itself
+        if restart:      # retries = 0: attempt 0 alone -- the call, the link clearance, the self clearance merged into it
+            nbytes = self.anchored_retry_ws_bytes(base, B, scenes=sc is not None)
+            attempt, ws, q_lo, q_hi = self._retry_buffers(out, B, nbytes, lo, hi, limits=bool(retries))
+            opts = _retry_opts(retries, retry_seed, pos_tol, rot_tol, q_lo, q_hi, mode, clear_tol, retry_spread)
+            name = "gik_anchored_ik_batch_retry" if sc is None else "gik_anchored_ik_batch_retry_scenes"
+            args = (seed_ptr, B, C.byref(opts), *scene, ws.data_ptr(), *answer, cl_ptr, attempt.data_ptr())
+            extras = {"clearance": cl, "attempt" if retries else "_attempt": attempt, "_retry_ws": ws}
+        else:
             ws = out["ws"]
             assert ws.numel() >= int(self.lib.gik_anchored_ws_doubles(self._h, base._h, B))
+            extras = {"_ws": ws, "clearance": cl} if clearance else {"_ws": ws}
             if sc is not None:      # one call: cold or seeded, the clearance of either mode behind it
-                _ffi.check(self.lib.gik_anchored_ik_batch_scenes(
-                    self._h, base._h, T.data_ptr(), None if q0 is None else q0.data_ptr(), B, C.byref(sc), ws.data_ptr(),
-                    *answer, None if cl is None else cl.data_ptr(), mode, self._stream()))
-                extras = {"_ws": ws, "_scene_id": ids}
-                return _result(out, (B, self.full_N, 3), {**extras, "clearance": cl} if clearance else extras)
-            if q0 is None:
-                _ffi.check(self.lib.gik_anchored_ik_batch(self._h, base._h, T.data_ptr(), B, ws.data_ptr(), *answer,
-                                                          self._stream()))
-                after = clearance
+                name, args = "gik_anchored_ik_batch_scenes", (seed_ptr, B, *scene, ws.data_ptr(), *answer, cl_ptr, mode)
+            elif q0 is None:
+                name, args = "gik_anchored_ik_batch", (B, ws.data_ptr(), *answer)
+                if clearance:
+                    after = "gik_anchored_link_clearance" if mode == _ffi.CLEARANCE_LINKS else "gik_anchored_clearance"
             else:      # (the seeded call measures the joint points itself; whole links are measured after it)
-                after = clearance and mode == _ffi.CLEARANCE_LINKS
-                _ffi.check(self.lib.gik_anchored_ik_batch_seeded(
-                    self._h, base._h, T.data_ptr(), q0.data_ptr(), B, ws.data_ptr(), *answer,
-                    None if cl is None or after else cl.data_ptr(), self._stream()))
-            if after:
-                clear_fn = self.lib.gik_anchored_link_clearance if mode == _ffi.CLEARANCE_LINKS else self.lib.gik_anchored_clearance
-                _ffi.check(clear_fn(self._h, out["Y"].data_ptr(), B, cl.data_ptr(), self._stream()))
-        return _result(out, (B, self.full_N, 3), {"_ws": ws, "clearance": cl} if clearance else {"_ws": ws})
+                if clearance and mode == _ffi.CLEARANCE_LINKS:
+                    after = "gik_anchored_link_clearance"
+                name, args = "gik_anchored_ik_batch_seeded", (seed_ptr, B, ws.data_ptr(), *answer, None if after else cl_ptr)
+        if retries or sc is not None:
+            extras["_scene_id"] = ids      # (read by the kernel: lives as long as the result; None without scenes)
+        self._call(name, self._h, base._h, T.data_ptr(), *args, self._stream())
+        if after:
+            self._call(after, self._h, out["Y"].data_ptr(), B, cl_ptr, self._stream())
+        return _result(out, (B, self.full_N, 3), extras)
 
     def alloc_ik_buffers(self, B):
         f64 = dict(dtype=torch.float64, device=self.device)
@@ -941,16 +922,11 @@ class Template:
                 fill = float("nan") if dt == torch.float64 else -9
                 keep[name] = torch.full((B, trace_cap), fill, dtype=dt, device=self.device)
                 setattr(tr, "d_" + name, keep[name].data_ptr())
-        with torch.cuda.device(self.device):
-            if sc is None:
-                _ffi.check(self.lib.gik_solve_batch(self._h, Y.data_ptr(), t.data_ptr(), B,
-                                                    out.data_ptr(), stats.data_ptr(),
-                                                    C.byref(tr) if tr is not None else None,
-                                                    self._stream()))
-            else:
-                _ffi.check(self.lib.gik_solve_batch_scenes(self._h, Y.data_ptr(), t.data_ptr(), B, out.data_ptr(),
-                                                           stats.data_ptr(), C.byref(tr) if tr is not None else None,
-                                                           C.byref(sc), self._stream()))
+        args = (self._h, Y.data_ptr(), t.data_ptr(), B, out.data_ptr(), stats.data_ptr(), C.byref(tr) if tr is not None else None)
+        if sc is None:
+            self._call("gik_solve_batch", *args, self._stream())
+        else:
+            self._call("gik_solve_batch_scenes", *args, C.byref(sc), self._stream())
         res = {"x": out.reshape(B, self.N, self.k)}
         if ids is not None:
             res["_scene_id"] = ids      # (read by the kernel: lives as long as the result)

@@ -16,7 +16,8 @@ import time
 import numpy as np
 import torch
 
-from ..engine import Template, _alloc_stats, _decode_stats, build_terms, check_clearance_mode, check_retry_args
+from ..engine import (Template, _alloc_stats, _decode_stats, build_terms, check_clearance_mode, check_retry_args, restart_like,
+                      workspace)
 from ..utils import dgp
 from ..utils.constants import POS
 from ..utils.lie import as_matrix
@@ -873,13 +874,9 @@ class AnchoredProblem:
     def _retry_args(self, retries, retry_seed, pos_tol, rot_tol, clear_tol, retry_spread, q_limits, has_center=True):
         """The restart arguments of solve / solve_trajectory, checked here before any device call, as the keywords
         Template.anchored_ik takes ({} with retries == 0); q_limits defaults to the robot's limits_arrays()."""
-        if not retries:
-            return {}
-        q_limits = self.robot.limits_arrays() if q_limits is None else q_limits
-        retries, lo, hi = check_retry_args(retries, pos_tol, rot_tol, q_limits, self.robot.n, clear_tol=clear_tol,
-                                           retry_spread=retry_spread, has_center=has_center)
-        return dict(retries=retries, retry_seed=retry_seed, pos_tol=pos_tol, rot_tol=rot_tol, clear_tol=clear_tol,
-                    retry_spread=retry_spread, q_limits=(lo, hi))
+        q_limits = self.robot.limits_arrays() if retries and q_limits is None else q_limits
+        return _retry_kwargs(retries, retry_seed, pos_tol, rot_tol, q_limits, self.robot.n, has_center, clear_tol=clear_tol,
+                             retry_spread=retry_spread)
 
     def solve_trajectory(self, T_path, q_start, return_Y=False, retries=0, retry_seed=0, pos_tol=0.01, rot_tol=0.01,
                          clear_tol=1e-4, retry_spread=0.0, q_limits=None, clearance_mode="nodes", sweep=None, scenes=None,
@@ -935,21 +932,20 @@ class AnchoredProblem:
         retry = self._retry_args(retries, retry_seed, pos_tol, rot_tol, clear_tol, retry_spread, q_limits)
         tpl, base = self.template, self.base.template
         planes, shared, nbytes = ["clearance"], {}, None
-        if retry:      # (the restart workspace holds the anchored scratch too; with scenes, a compact batch's ids behind it)
-            planes.append("attempt")
+        if restart_like(retries, clearance_mode, True, scenes):
+            # one restart workspace for all waypoints: it holds the anchored scratch too and, with scenes, a compact
+            # batch's ids behind it; without restarts it serves attempt 0 of the restart entry alone
             nbytes = tpl.anchored_retry_ws_bytes(base, B, scenes=scenes is not None)
-        elif clearance_mode == "links+self" and scenes is None:      # (attempt 0 of the restart entry: its workspace)
-            shared["retry_ws"] = torch.empty(max((tpl.anchored_retry_ws_bytes(base, B) + 7) // 8, 1), dtype=torch.float64,
-                                             device=tpl.device)
         else:
             shared["ws"] = tpl.alloc_anchored_buffers(base, B)["ws"]
+        if retry:
+            planes.append("attempt")
         sweep_self = bool(sweep) and clearance_mode == "links+self"
         if sweep:      # one workspace for all waypoints
             planes.append("sweep_clearance")
             if sweep_self:
                 planes.append("sweep_self_clearance")
-            sweep_ws = torch.empty(max(int(tpl.lib.gik_anchored_sweep_ws_bytes(tpl._h, base._h, B, sweep)) // 8, 1),
-                                   dtype=torch.float64, device=tpl.device)
+            sweep_ws = workspace(tpl.anchored_sweep_ws_bytes(base, B, sweep), tpl.device)
 
         waypoint = iter(range(T.shape[1]))
 
@@ -1264,6 +1260,16 @@ def _seed_angles(q_init, B, n, name="q_init"):
     return np.ascontiguousarray(q)
 
 
+def _retry_kwargs(retries, retry_seed, pos_tol, rot_tol, q_limits, n, has_center=True, **anchored):
+    """The restart keywords of one call, checked here before any device call: {} with retries == 0, else what
+    Template.ik takes -- retries, retry_seed, pos_tol, rot_tol and q_limits as the checked (lo, hi) -- and, for
+    Template.anchored_ik, its own two: anchored = clear_tol and retry_spread (has_center: the call has a q_init)."""
+    if not retries:
+        return {}
+    retries, lo, hi = check_retry_args(retries, pos_tol, rot_tol, q_limits, n, has_center=has_center, **anchored)
+    return dict(retries=retries, retry_seed=retry_seed, pos_tol=pos_tol, rot_tol=rot_tol, q_limits=(lo, hi), **anchored)
+
+
 def retry_uniform_host(seed, goals, attempt, n):
     """The restart generator's uniform numbers in [0, 1), [len(goals), n]: splitmix64's finaliser over the
     counter of (goal, attempt, joint) in uint64 arithmetic -- bit for bit what retry_seed_kernel draws
@@ -1363,13 +1369,9 @@ def solve_batch(graph, T_goals, use_limits=True, params=None, device=None, Y_ini
         if Y_init is not None:
             raise ValueError("pass Y_init or q_init, not both")
         q_init = _seed_angles(q_init, T.shape[0], graph.robot.n)
-    retry = {}
-    if retries:
-        if Y_init is not None:
-            raise ValueError("retries > 0 cannot be combined with Y_init (pass q_init, or no start at all)")
-        check_retry_args(retries, pos_tol, rot_tol, graph.robot.limits_arrays(), graph.robot.n)
-        retry = dict(retries=retries, retry_seed=retry_seed, pos_tol=pos_tol, rot_tol=rot_tol,
-                     q_limits=graph.robot.limits_arrays())
+    if retries and Y_init is not None:
+        raise ValueError("retries > 0 cannot be combined with Y_init (pass q_init, or no start at all)")
+    retry = _retry_kwargs(retries, retry_seed, pos_tol, rot_tol, graph.robot.limits_arrays() if retries else None, graph.robot.n)
     prob = _problem_for(graph, use_limits, params, device, goal)
     if retries and not prob.device_pipeline:
         raise ValueError("retries > 0 needs the device pipeline, which this graph is outside of")
@@ -1432,16 +1434,14 @@ def solve_trajectory(graph, T_path, q_start, use_limits=True, params=None, devic
     B, L = T.shape[:2]
     n = graph.robot.n
     q0 = _seed_angles(q_start, B, n, "q_start")
-    retry = {}
-    if retries:
-        _, q_lo, q_hi = check_retry_args(retries, pos_tol, rot_tol, graph.robot.limits_arrays(), n)
-        retry = dict(retries=retries, retry_seed=retry_seed, pos_tol=pos_tol, rot_tol=rot_tol)
+    retry = _retry_kwargs(retries, retry_seed, pos_tol, rot_tol, graph.robot.limits_arrays() if retries else None, n)
     prob = _problem_for(graph, use_limits, params, device, goal)
     if not prob.device_pipeline:
         qs, Ys, infos, dt = [], [], [], 0.0
         q_prev = q0
+        own = {key: v for key, v in retry.items() if key != "q_limits"}      # (solve_batch reads the robot's limits itself)
         for l in range(L):
-            q_prev, Y, info = solve_batch(graph, T[:, l], use_limits, params, device, q_init=q_prev, goal=goal, **retry)
+            q_prev, Y, info = solve_batch(graph, T[:, l], use_limits, params, device, q_init=q_prev, goal=goal, **own)
             qs.append(q_prev)
             Ys.append(Y)
             infos.append(info)
@@ -1453,10 +1453,7 @@ def solve_trajectory(graph, T_path, q_start, use_limits=True, params=None, devic
         return np.stack(qs, axis=1), (np.stack(Ys, axis=1) if return_Y else None), out
     tpl = prob.template
     shared = {"targets": torch.empty(B, tpl.T, dtype=torch.float64, device=tpl.device)}
-    nbytes = None
-    if retries:
-        retry["q_limits"] = (q_lo, q_hi)
-        nbytes = int(tpl.lib.gik_retry_ws_bytes(tpl._h, B))
+    nbytes = tpl.retry_ws_bytes(B) if retry else None
 
     def step(T_l, q_prev, out):
         tpl.ik(T_l, out=out, q_init=q_prev, **retry)
@@ -1470,8 +1467,8 @@ def _track(tpl, T, q0, Y_shape, return_Y, planes, step, shared, retry_ws_bytes=N
     q_prev [B, n] that seed it (q0, then waypoint l-1's answer -- they never leave the device), and `out`, its rows of
     the result storage: "Y" (row 0 every time unless return_Y), "stats", "q", "pos_err", "rot_err", one [B] row per
     name in `planes` ("attempt": int32, zero where no call writes it; the others float64) and what the waypoints
-    share: `shared` and, with retry_ws_bytes (the caller's gik_*retry_ws_bytes) and q_limits = (q_lo, q_hi), one
-    restart workspace "retry_ws" and one upload of the limits "q_lo" / "q_hi".  One synchronisation after the last
+    share: `shared`, with retry_ws_bytes (the caller's restart workspace size in bytes) one restart workspace "retry_ws"
+    and with q_limits = (q_lo, q_hi) one upload of the limits "q_lo" / "q_hi".  One synchronisation after the last
     waypoint.  Returns q [B, L, n], Y [B, L, *Y_shape] (None unless return_Y) and info: [B, L] arrays of the stats
     and the planes, plus solve_time."""
     B, L = T.shape[:2]
@@ -1486,8 +1483,9 @@ def _track(tpl, T, q0, Y_shape, return_Y, planes, step, shared, retry_ws_bytes=N
             for name in ("pos_err", "rot_err", *planes)}
     shared = dict(shared)
     if retry_ws_bytes is not None:
-        shared.update(retry_ws=torch.empty(max((retry_ws_bytes + 7) // 8, 1), **f64),
-                      q_lo=torch.from_numpy(q_limits[0]).to(dev), q_hi=torch.from_numpy(q_limits[1]).to(dev))
+        shared["retry_ws"] = workspace(retry_ws_bytes, dev)
+    if q_limits is not None:
+        shared.update(q_lo=torch.from_numpy(q_limits[0]).to(dev), q_hi=torch.from_numpy(q_limits[1]).to(dev))
     q_prev = torch.from_numpy(q0).to(dev)      # (its own tensor: the start angles outlive waypoint 0's solve)
     torch.cuda.synchronize(dev)
     t0 = time.time()

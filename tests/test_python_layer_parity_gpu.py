@@ -5,17 +5,19 @@ bit for bit.
 A table of scenarios (SCENARIOS) runs solve_batch, solve_trajectory, AnchoredProblem.solve / solve_trajectory,
 Template.ik and Template.anchored_ik over the paths the fold touched: cold, seeded ([n] and [B, n]), Y_init, restarts
 (cold, seeded, local), the host paths of graphs off the device pipeline, planar poses, tracking with and without the
-point matrices, the clearance modes (nodes, links, links+self), per-goal scenes, the sweep, link and self hinges, and
-reused `out` buffers.  Every returned array is hashed
+point matrices, the clearance modes (nodes, links, links+self), per-goal scenes (cold, seeded, with restarts, per
+waypoint), the sweep, link and self hinges, reused `out` buffers, and the small Template methods (the costgrd twins,
+prepare, recover, seed, the clearances, the sweep, Template.solve with scenes).  Every returned array is hashed
 by key (sha256 over dtype, shape and bytes; not hashed: time, solve_time, inner_executed, flags and keys that begin
 with "_") and compared with tests/golden/python_layer_parent.json, which tools/python_layer_digest.py recorded on the
 MI355X from a checkout of the parent commit with this table.  The recording refuses a file in which a restart scenario
 improved no goal (attempt all zero) or a clearance scenario has no finite clearance; the test checks the same of the
 file it reads, so no scenario passes on a path that did nothing.  (planar_cold was recorded again when prep_quad_kernel's
 K x K Jacobi schedule became a function of the goal alone, docs/NOTEBOOK.md 36: the floating-point arrays moved in their
-last bits, every count stayed; the entry says so.  The file was recorded again from a checkout of c11b7a7 when the
-self clearance, the scenes and the self hinges joined the table, docs/NOTEBOOK.md 40: every hash that was there before
-came out unchanged.)
+last bits, every count stayed.  The file was recorded again from a checkout of c11b7a7 when the self clearance, the
+scenes and the self hinges joined the table, docs/NOTEBOOK.md 40, and from a checkout of d57bfde when six scenarios
+for the entries and branches the table had missed joined it, docs/NOTEBOOK.md 41: both times every hash that was there
+before came out unchanged.)
 
 Shapes: B = 5 goals (a multiple of nothing), trajectories of L = 3 waypoints for B = 4 paths.  Inputs: conftest.make_graph
 and the inputs of the anchored host tests (collision_input, tracking_input, TWIN_MAXITER, TWIN_SEED); fixed seeds."""
@@ -163,19 +165,60 @@ def _anch(maxiter=None, seeded=False, link_hinges=False, self_pairs=None, self_h
         T, seeds = anchored_goals()
         ap = anchored(maxiter, link_hinges, self_pairs, self_hinges)[1]
         extra = {}
-        if scenes:      # three scenes, goal b in scene b % 3: the table, the table 0.2 m further in x, its first ten spheres
-            extra = dict(scenes=ap.scene_set([ap.obstacles, ap.obstacles + np.array([0.2, 0.0, 0.0, 0.0]), ap.obstacles[:10]]),
-                         scene_id=(np.arange(B) % 3).astype(np.int32))
+        if scenes:      # three scenes, goal b in scene b % 3
+            extra = dict(scenes=_three_scenes(ap), scene_id=(np.arange(B) % 3).astype(np.int32))
         return host(ap.solve(T, q_init=seeds if seeded else None, **kw, **extra))
     return run
 
 
-def _anch_track(maxiter=None, start="own", self_pairs=None, **kw):
+def _three_scenes(ap):
+    """The table, the table 0.2 m further in x, its first ten spheres."""
+    return ap.scene_set([ap.obstacles, ap.obstacles + np.array([0.2, 0.0, 0.0, 0.0]), ap.obstacles[:10]])
+
+
+def _anch_track(maxiter=None, start="own", self_pairs=None, scenes=False, **kw):
     def run():
         T, q_own, q_hit = anchored_paths()
         ap = anchored(maxiter, False, self_pairs)[1]
-        return triple(ap.solve_trajectory(T, q_own if start == "own" else q_hit, **kw))
+        extra = {}
+        if scenes:      # a scene per waypoint: waypoint l of path b in scene (b + l) % 3
+            extra = dict(scenes=_three_scenes(ap),
+                         scene_id=((np.arange(PATHS)[:, None] + np.arange(WAYPOINTS)[None, :]) % 3).astype(np.int32))
+        return triple(ap.solve_trajectory(T, q_own if start == "own" else q_hit, **kw, **extra))
     return run
+
+
+def _template_entries():
+    """The small Template methods, each result under its own key: the costgrd twins, prepare, recover and seed on the
+    LWA4D template; on the anchored one (UR10 + table, self pairs) the seed, the clearances against its own obstacles
+    and against scenes, the sweep, and Template.solve with scenes."""
+    rs = _rs()
+    robot, graph, T, seeds = plain("lwa4d")
+    tpl = rs.BatchProblem(graph).template
+    out = {}
+    targets, Y0 = tpl.prepare(T)
+    W = np.random.RandomState(104).randn(*Y0.shape)
+    out["prepare_targets"], out["prepare_Y"] = targets, Y0
+    out["cost"], out["grad"] = tpl.cost(Y0, targets), tpl.grad(Y0, targets)
+    out["cost_and_grad_f"], out["cost_and_grad_G"] = tpl.cost_and_grad(Y0, targets)
+    out["hess"], out["proj"] = tpl.hess(Y0, W, targets), tpl.proj(Y0, W)
+    out["recover_q"], out["recover_pos_err"], out["recover_rot_err"] = tpl.recover(Y0, T)
+    out["seed_targets"], out["seed_Y"] = tpl.seed(T, seeds)
+    Ta, seeds_a = anchored_goals()
+    ap = anchored(None, False, "auto")[1]
+    atpl, base = ap.template, ap.base.template
+    Y_free, goal = atpl.anchored_seed(base, Ta, seeds_a)
+    out["anchored_seed_Y"], out["anchored_seed_goal"] = Y_free, goal
+    answer = ap.solve(Ta, q_init=seeds_a)
+    sc = dict(scenes=_three_scenes(ap), scene_id=(np.arange(B) % 3).astype(np.int32))
+    out["clearance"] = atpl.anchored_clearance(answer["x"])
+    out["clearance_scenes"] = atpl.anchored_clearance(answer["x"], **sc)
+    out["link_clearance"] = atpl.anchored_link_clearance(answer["x"])
+    out["link_clearance_scenes"] = atpl.anchored_link_clearance(answer["x"], **sc)
+    out["self_clearance"] = atpl.anchored_self_clearance(answer["x"])
+    out["sweep_clearance"] = atpl.anchored_sweep_clearance(base, seeds_a, answer["q"], 3)
+    out.update({"solve_scenes_" + key: v for key, v in host(atpl.solve(Y_free, goal, **sc)).items()})
+    return host(out)
 
 
 def _reuse(call, alloc):
@@ -241,6 +284,17 @@ SCENARIOS = {
     "anch_self_hinges_seeded_clearance_links_self": _anch(seeded=True, self_pairs="auto", self_hinges=True,
                                                           clearance_mode="links+self"),
     "anch_self_track_sweep_clearance_links_self": _anch_track(self_pairs="auto", sweep=2, clearance_mode="links+self"),
+    # anchored: the entries and branches the table missed until docs/NOTEBOOK.md 41 -- restarts among scenes, scenes with
+    # a null seed, restarts in "links+self", a scene per waypoint, tracking on the shared restart workspace
+    "anch_scenes_retry_seeded_clearance_links": _anch(TWIN_MAXITER, seeded=True, scenes=True, retries=2, retry_seed=TWIN_SEED,
+                                                      clearance_mode="links"),
+    "anch_scenes_cold_clearance_nodes": _anch(scenes=True, clearance=True),
+    "anch_self_retry_cold_clearance_links_self": _anch(TWIN_MAXITER, self_pairs="auto", retries=2, retry_seed=TWIN_SEED,
+                                                       clearance_mode="links+self"),
+    "anch_scenes_track_clearance_links": _anch_track(scenes=True, clearance_mode="links"),
+    "anch_self_track_clearance_links_self": _anch_track(self_pairs="auto", clearance_mode="links+self"),
+    # the small Template methods
+    "template_entries_clearance": _template_entries,
     # reused buffers
     "reuse_ik": _reuse_ik,
     "reuse_anchored_ik_clearance": _reuse_anchored_ik,
