@@ -116,6 +116,7 @@ CLEARANCE_NODES, CLEARANCE_LINKS, CLEARANCE_LINKS_SELF = 0, 1, 2
 CLEARANCE_MODES = {"nodes": CLEARANCE_NODES, "links": CLEARANCE_LINKS, "links+self": CLEARANCE_LINKS_SELF}
 SELF_MAX_PAIRS = 2016      # every pair of 64 links
 SELF_HINGE_MAX_PAIRS = 16  # pairs the solve carries hinges for (gik_anchored_attach_self_hinges)
+HALF_MAX = 8               # half-spaces per template (gik_anchored_attach_halfspaces)
 
 
 class LinkDesc(C.Structure):
@@ -160,6 +161,8 @@ SYMBOLS = {
                                                C.c_void_p, C.c_void_p]),
     "gik_anchored_attach_self_pairs": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "gik_anchored_attach_self_hinges": (C.c_int, [C.c_void_p]),
+    "gik_anchored_attach_halfspaces": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "gik_anchored_halfspace_clearance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "gik_anchored_self_clearance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "gik_anchored_sweep_clearances": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p]),

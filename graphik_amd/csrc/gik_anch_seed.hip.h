@@ -24,6 +24,11 @@
 //                           SEGMENTS less both radii (anch_self_pair), optionally merged into the value already there.
 //                           Up to 16 pairs: four goals per wavefront, lane 16 g + p on pair p of goal slot g, the
 //                           minimum and the NaN flag per 16-lane row.  More: one wavefront per goal, as the link kernel.
+//   anch_half_clearance_kernel : against the template's half-spaces (gik_anchored_attach_halfspaces): one wavefront per goal,
+//                           min over (item, end row P, half-space h) of s_h(P) - margin with s_h = ((nx x + ny y) + nz z) - d0,
+//                           every product and sum rounded on its own.  The items are the masked free nodes with their
+//                           margins, or the attached links -- both end rows, constants included -- with their radii.
+//                           Optionally merged into the value already there, like the self kernel.  A NaN coordinate: NaN.
 // The pair functions themselves (anch_link_pair, anch_self_pair, anch_sweep_interp, anch_sweep_min) are gik_anch_pairs.h's,
 // shared with the hinges of the solve kernels.
 // Plain kernels, defined where GIK_DEFINE_ANCH_SEED_KERNELS is set (gik_k_anch_seed.hip); every other unit that includes
@@ -69,6 +74,16 @@ struct AnchSelfArgs {
   double *clearance;         // [B]
   int B, full_N, n_pair;
   int merge;                 // 0: clearance[b] = the minimum; 1: the NaN-propagating minimum of it and clearance[b]
+};
+
+struct AnchHalfArgs {
+  const double *Y_full;      // [B][full_N*3]
+  const double *half;        // [n_half][4] nx, ny, nz, d0
+  const int *row_a, *row_b;  // [n_item] rows of the full point matrix: a node (row_b null), or the two ends of a link
+  const double *margin;      // [n_item] the node's margin, or the link's radius
+  double *clearance;         // [B]
+  int B, full_N, n_item, n_half;
+  int merge;                 // as AnchSelfArgs
 };
 
 struct AnchSweepInterpArgs {
@@ -221,6 +236,32 @@ __global__ void __launch_bounds__(WAVE) anch_self_clearance_kernel(AnchSelfArgs 
     const double *Y = a.Y_full + (size_t)b * a.full_N * 3;
     const double m = wave_pair_min(lane, a.n_pair, [&](int p) { return anch_self_value(a, Y, p); });
     if (lane == 0) anch_self_store(a, b, m);
+  }
+}
+#endif
+
+__global__ void __launch_bounds__(WAVE) anch_half_clearance_kernel(AnchHalfArgs a)
+#ifndef GIK_DEFINE_ANCH_SEED_KERNELS
+    ;
+#else
+{
+  const int ends = a.row_b ? 2 : 1;
+  for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
+    const double *Y = a.Y_full + (size_t)b * a.full_N * 3;
+    double m = wave_pair_min(threadIdx.x, a.n_item * ends * a.n_half, [&](int p) {
+      const int h = p % a.n_half, ie = p / a.n_half, i = ie / ends;
+      const double *y = Y + ((ie - i * ends) ? a.row_b[i] : a.row_a[i]) * 3, *n = a.half + h * 4;
+      // (the rounding intrinsics: no product is contracted into a sum, the numpy mirror has the same bits)
+      const double s = __dsub_rn(__dadd_rn(__dadd_rn(__dmul_rn(n[0], y[0]), __dmul_rn(n[1], y[1])), __dmul_rn(n[2], y[2])), n[3]);
+      return __dsub_rn(s, a.margin[i]);
+    });
+    if (threadIdx.x == 0) {
+      if (a.merge) {
+        const double old = a.clearance[b];
+        m = (old != old || m != m) ? __builtin_nan("") : (old < m ? old : m);
+      }
+      a.clearance[b] = m;
+    }
   }
 }
 #endif

@@ -23,6 +23,8 @@ static_assert(SCENE_MAX_SPHERES == ANCH_MAXOBS, "gik_scenes.h restates this cons
 constexpr int ANCH_LMAX = 2;      // link hinges (WaveCtx<.., LINKS>): links per free node
 constexpr int ANCH_LROWS = 22;  // rows of the per-node link tables: 3 N <= 64 gives 21 free nodes, + one inert row for idle lanes
 constexpr int ANCH_SELF_HMAX = 16;   // self hinges (WaveCtx<.., SELF>): link pairs per template, a pair per lane of a 16-lane row
+constexpr int ANCH_HALF_MAX = 8;      // half-space obstacles (WaveCtx<.., HALF>): planes per template, 32 B each in LDS
+constexpr int ANCH_HALF_ROWS = 34;    // rows of the per-node margin table: the 33 tile rows (idle lanes read the dump row's), even
 
 constexpr int MIG_SIMDS = 1 << 14;      // SIMD slots of the spread table (MigCtl::simd_run, gik_rtr.hip.h)
 
@@ -180,6 +182,10 @@ struct SolveArgs {
   BlockTabs bt;                    // workgroup-per-problem path
   NptTabs nt;                      // node-per-lane path (rtr_npt_kernel)
   double *npt_ctg_ws = nullptr;    // graphs beyond 128 nodes: [grid][ctg_doubles] clique target triangles (global memory)
+  // half-space obstacles (HALF kernels only; gik_anchored_attach_halfspaces).  At the end: every other kernel's offsets stay
+  const double *half = nullptr;    // [n_half][4] unit normal nx, ny, nz and offset d0: the allowed side is n.p - d0 >= 0
+  const double *half_mu = nullptr; // [N] margin of each free node, metres (read where obs_mask has the node's bit)
+  int n_half = 0;
 };
 
 struct KatArgs {
@@ -195,6 +201,9 @@ struct KatArgs {
   BlockTabs bt;
   NptTabs nt;
   double *npt_ctg_ws = nullptr;   // see SolveArgs
+  const double *half = nullptr;   // half-space obstacles, as in SolveArgs
+  const double *half_mu = nullptr;
+  int n_half = 0;
 };
 
 // ---- prepare, recover, seed, anchored glue ---------------------------------------------------

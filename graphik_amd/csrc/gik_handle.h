@@ -46,6 +46,11 @@ struct gik_template {
   int *d_self_l = nullptr, *d_self_m = nullptr;   // [n_self] indices into the link arrays
   int n_self = -1;
   bool self_hinges = false;                       // gik_anchored_attach_self_hinges: the solve kernels are the SELF builds
+  // the half-spaces of gik_anchored_attach_halfspaces (n_half == 0: none attached): the solve kernels are the HALF builds
+  double *d_half = nullptr;                       // [n_half][4] nx, ny, nz, d0
+  double *d_half_mu = nullptr;                    // [N] margin per free node (0 where the node carries no hinges)
+  double *d_half_mu_clear = nullptr;              // [n_clear] ... of the masked nodes, in d_clear_full's order (anch_half_clearance_kernel)
+  int n_half = 0;
   std::vector<int> h_link_a, h_link_b, h_self_l, h_self_m;   // host copies of the link set and the pairs, and the radii:
   std::vector<double> h_link_rho;                 // what gik_anchored_attach_self_hinges builds its descriptors from
   std::vector<int> h_free_full, h_anchor_full;    // host copies of d_free_full / d_anchor_full and of the slot table:

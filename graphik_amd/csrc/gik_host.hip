@@ -21,7 +21,7 @@
 #include <thread>
 
 namespace gik {
-GIK_ALL_KERNELS(GIK_EXTERN_TEMPLATE)      // (the self-hinge group, beside it: at the end of gik_kernels.hip.h)
+GIK_ALL_KERNELS(GIK_EXTERN_TEMPLATE)      // (the self-hinge and half-space groups, beside it: at the end of gik_kernels.hip.h)
 
 // the compiled node-per-lane variants
 struct NptVariant {
@@ -58,8 +58,9 @@ typedef size_t (*lds_fn)(int);
 // (PER_EDGE: hessian_form = GIK_HESS_PER_EDGE, k = 3, TrustRegions; ANCHORED: the fixed-anchor formulation, k = 3, theta == 1;
 // ANCHORED_LINK: ... with link hinges.  Creation never asks for that form: gik_anchored_attach_links with hinges = 1
 // re-resolves an anchored 9-slot template to it; ANCHORED_SELF / ANCHORED_LINK_SELF: either with self hinges,
-// gik_anchored_attach_self_hinges re-resolves to the one that matches the template's current form)
-enum Form { COLUMN, PER_EDGE, ANCHORED, ANCHORED_LINK, ANCHORED_SELF, ANCHORED_LINK_SELF };
+// gik_anchored_attach_self_hinges re-resolves to the one that matches the template's current form; ANCHORED_HALF /
+// ANCHORED_LINK_HALF: either with half-space obstacles, gik_anchored_attach_halfspaces does the same)
+enum Form { COLUMN, PER_EDGE, ANCHORED, ANCHORED_LINK, ANCHORED_SELF, ANCHORED_LINK_SELF, ANCHORED_HALF, ANCHORED_LINK_HALF };
 struct WaveRow {
   int K, slots;
   Form form;
@@ -77,7 +78,8 @@ struct WaveRow {
 template <int K, int D, Form F, unsigned MORE = (F == PER_EDGE ? W_SPREAD : 0u)>
 static WaveRow wave_row() {
   constexpr unsigned B = F == PER_EDGE ? W_PER_EDGE : F == ANCHORED ? W_ANCH : F == ANCHORED_LINK ? W_ANCH | W_LINKS :
-                         F == ANCHORED_SELF ? W_ANCH | W_SELF : F == ANCHORED_LINK_SELF ? W_ANCH | W_LINKS | W_SELF : 0u;
+                         F == ANCHORED_SELF ? W_ANCH | W_SELF : F == ANCHORED_LINK_SELF ? W_ANCH | W_LINKS | W_SELF :
+                         F == ANCHORED_HALF ? W_ANCH | W_HALF : F == ANCHORED_LINK_HALF ? W_ANCH | W_LINKS | W_HALF : 0u;
   WaveRow r{K, D, F};
   r.solve = rtr_wave_kernel<K, D, B | W_THETA1>;
   if constexpr ((B & W_ANCH) == 0) r.solve_theta = rtr_wave_kernel<K, D, B>;
@@ -96,6 +98,7 @@ static WaveRow wave_row() {
 static const WaveRow kWaveRows[] = {
     wave_row<3, 9, COLUMN, W_SPREAD>(), wave_row<3, 9, PER_EDGE>(), wave_row<3, 9, ANCHORED>(), wave_row<3, 9, ANCHORED_LINK>(),
     wave_row<3, 9, ANCHORED_SELF>(), wave_row<3, 9, ANCHORED_LINK_SELF>(),
+    wave_row<3, 9, ANCHORED_HALF>(), wave_row<3, 9, ANCHORED_LINK_HALF>(),
     wave_row<3, 10, COLUMN>(), wave_row<3, 10, PER_EDGE>(),
     wave_row<3, 20, ANCHORED>(),
     wave_row<2, 6, COLUMN>(), wave_row<2, 16, COLUMN>(), wave_row<2, 31, COLUMN>()};
@@ -575,6 +578,8 @@ int gik_anchored_attach_links(gik_template *anch, const gik_link_desc *d) {
   if (!anch->anchored) return fail(e + ": the handle must be a fixed-anchor template (gik_template_create_anchored)");
   if (anch->n_link >= 0) return fail(e + ": links already attached");
   if (d->hinges != 0 && d->hinges != 1) return fail(e + ": hinges must be 0 (measure only) or 1 (the solve carries link hinges)");
+  if (d->hinges && anch->n_half > 0)
+    return fail(e + ": half-spaces are attached; link hinges come before gik_anchored_attach_halfspaces, which is called last");
   if (d->n_link < 0 || d->n_link > ANCH_MAXLINK) return fail(e + ": n_link must be within 0 .. 64");
   if (d->n_link > 0 && (!d->link_a || !d->link_b || !d->link_radius)) return fail(e + ": null link array");
   for (int l = 0; l < d->n_link; ++l) {
@@ -650,6 +655,7 @@ int gik_anchored_attach_self_hinges(gik_template *anch) {
   if (!anch) return fail(e + ": null argument");
   if (!anch->anchored) return fail(e + ": the handle must be a fixed-anchor template (gik_template_create_anchored)");
   if (anch->self_hinges) return fail(e + ": self hinges already attached");
+  if (anch->n_half > 0) return fail(e + ": half-spaces are attached; the solve has no build with self hinges and half-spaces");
   if (anch->n_link < 0) return fail(e + ": no links attached (gik_anchored_attach_links comes first)");
   if (anch->n_self < 0) return fail(e + ": no self pairs attached (gik_anchored_attach_self_pairs comes first)");
   if (anch->n_self > ANCH_SELF_HMAX)
@@ -671,6 +677,54 @@ int gik_anchored_attach_self_hinges(gik_template *anch) {
   install_row(anch, row);
   anch->f.waves_per_cu = std::max(1, std::min(occ, 32));
   anch->self_hinges = true;
+  return 0;
+}
+
+// half-space obstacles: floors and walls as terms of the solve and of every clearance the library reports.  Called last.  The
+// template's solve, known-answer and scene kernels are resolved again, to the HALF row of its current form.
+int gik_anchored_attach_halfspaces(gik_template *anch, int n_half, const double *halfspaces, const double *node_margin) {
+  using namespace gik;
+  const std::string e("gik_anchored_attach_halfspaces");
+  if (!anch) return fail(e + ": null argument");
+  if (!anch->anchored) return fail(e + ": the handle must be a fixed-anchor template (gik_template_create_anchored)");
+  if (anch->n_half > 0) return fail(e + ": half-spaces already attached");
+  if (n_half < 1 || n_half > ANCH_HALF_MAX) return fail(e + ": n_half must be within 1 .. 8");
+  if (!halfspaces || !node_margin) return fail(e + ": null array");
+  for (int h = 0; h < n_half; ++h) {
+    const double *p = halfspaces + 4 * h;
+    for (int q = 0; q < 4; ++q)
+      if (!(p[q] - p[q] == 0.0)) return fail(e + ": half-space " + std::to_string(h) + " has an entry that is not finite");
+    const double n2 = p[0] * p[0] + p[1] * p[1] + p[2] * p[2];
+    if (!(n2 - 1.0 <= 1e-12 && 1.0 - n2 <= 1e-12))
+      return fail(e + ": half-space " + std::to_string(h) + ": the normal must have unit length (| |n|^2 - 1 | <= 1e-12)");
+  }
+  std::vector<double> mu((size_t)anch->N, 0.0), mu_clear;
+  for (int i = 0; i < anch->N; ++i) {
+    if (!((anch->an.obs_mask >> i) & 1ull)) continue;      // (read where obs_node_mask is 1)
+    if (!(node_margin[i] >= 0.0) || node_margin[i] == __builtin_huge_val())
+      return fail(e + ": node_margin[" + std::to_string(i) + "] must be finite and at least 0");
+    mu[(size_t)i] = node_margin[i];
+    mu_clear.push_back(node_margin[i]);      // (d_clear_full lists the masked nodes in this order)
+  }
+  if ((int)mu_clear.size() != anch->n_clear) return fail(e + ": the handle's masked nodes and its clearance rows disagree");
+  if (anch->maxdeg != 9)
+    return fail(e + ": half-spaces need the 9-slot fixed-anchor kernel; this template runs the " + std::to_string(anch->maxdeg) +
+                "-slot variant, which has none");
+  if (anch->self_hinges) return fail(e + ": self hinges are attached; the solve has no build with self hinges and half-spaces");
+  const WaveRow *row = find_row(3, anch->link_hinges ? ANCHORED_LINK_HALF : ANCHORED_HALF, 9);
+  bool ok = true;
+  double *dh = const_cast<double *>(upload(anch, halfspaces, (size_t)n_half * 4, ok));
+  double *dm = const_cast<double *>(upload(anch, mu.data(), mu.size(), ok));
+  double *dc = const_cast<double *>(upload(anch, mu_clear.data(), mu_clear.size(), ok));
+  int occ = 0;
+  if (!ok || hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)row->solve, WAVE, row->lds(anch->T)) != hipSuccess)
+    return fail(e + ": device upload failed");
+  anch->d_half = dh;
+  anch->d_half_mu = dm;
+  anch->d_half_mu_clear = dc;
+  install_row(anch, row);
+  anch->f.waves_per_cu = std::max(1, std::min(occ, 32));
+  anch->n_half = n_half;
   return 0;
 }
 
@@ -1070,6 +1124,9 @@ static int launch_kat(const gik_template *t, int mode, const double *d_Y, const 
     a.an = t->an;
     a.an.anchor_goal = d_targets;          // (anchored templates: the per-problem input is the goal anchors)
     a.targets = t->d_targets_const;
+    a.half = t->d_half;
+    a.half_mu = t->d_half_mu;
+    a.n_half = t->n_half;
   }
   if (t->quad_solve && (t->f.dbg & 16384) && !(t->f.dbg & (1 | 8192))) {
     hipLaunchKernelGGL(kat_quad_kernel<6>, dim3((B + QUAD_SLOTS - 1) / QUAD_SLOTS), dim3(WAVE), t->quad_smem,
@@ -1156,6 +1213,9 @@ static void fill_args(const gik_template *t, gik::SolveArgs &a, const double *d_
     a.an = t->an;
     a.an.anchor_goal = d_targets;          // anchored templates: per-problem goal anchors [B][n_goal*3]
     a.targets = t->d_targets_const;
+    a.half = t->d_half;
+    a.half_mu = t->d_half_mu;
+    a.n_half = t->n_half;
   }
   a.dbg = t->f.dbg;
   a.dbg_buf = nullptr;
@@ -1406,7 +1466,7 @@ int gik_template_get_info(const gik_template *t, gik_template_info *info) {
   info->lds_bytes = (int32_t)t->smem_bytes;
   info->clique_closed_form = t->clique_mode;
   info->hessian_form = (t->hess_per_edge || t->f.is_block) ? GIK_HESS_PER_EDGE : GIK_HESS_COLUMN;
-  info->anchored = t->anchored ? (1 | (t->link_hinges ? 2 : 0) | (t->self_hinges ? 4 : 0)) : 0;
+  info->anchored = t->anchored ? (1 | (t->link_hinges ? 2 : 0) | (t->self_hinges ? 4 : 0) | (t->n_half > 0 ? 8 : 0)) : 0;
   info->has_pipeline = t->has_pipe ? 1 : 0;
   info->prepare_is_block = t->prep.plan.block() ? 1 : 0;
   info->node_per_lane = t->f.is_npt ? t->npt_variant->NW : 0;

@@ -285,14 +285,45 @@ static int anchored_self_clearance_launch(const gik_template *anch, const double
   return 0;
 }
 
+// against the half-spaces of gik_anchored_attach_halfspaces (the handle has some): the masked nodes with their margins, or
+// with links the attached links with their radii.  merge: the minimum with what d_clearance holds.
+static int anchored_half_clearance_launch(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance, bool links,
+                                          bool merge, void *stream) {
+  using namespace gik;
+  AnchHalfArgs c;
+  c.Y_full = d_Y_full;
+  c.half = anch->d_half;
+  c.row_a = links ? anch->d_link_a : anch->d_clear_full;
+  c.row_b = links ? anch->d_link_b : nullptr;
+  c.margin = links ? anch->d_link_rho : anch->d_half_mu_clear;
+  c.clearance = d_clearance;
+  c.B = B;
+  c.full_N = anch->full_N;
+  c.n_item = links ? anch->n_link : anch->n_clear;
+  c.n_half = anch->n_half;
+  c.merge = merge ? 1 : 0;
+  hipLaunchKernelGGL(anch_half_clearance_kernel, dim3(std::min(B, anch->f.n_cu * 32)), dim3(WAVE), 0, (hipStream_t)stream, c);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// on a handle with half-spaces every clearance the library reports is the minimum of the spheres' and theirs: the merge
+// launch behind the sphere launch, on the same stream
+static int fold_halfspaces(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance, bool links, void *stream) {
+  return anch->n_half > 0 ? anchored_half_clearance_launch(anch, d_Y_full, B, d_clearance, links, true, stream) : 0;
+}
+
 // the clearance of one clearance_mode (checked: clearance_mode_refusal) of B point matrices.  GIK_CLEARANCE_LINKS_SELF:
 // the link launch, then the self kernel merging into its output -- the self clearance does not depend on the scene.
 static int anchored_mode_clearance_launch(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance, int mode,
                                           void *stream, const gik_scene_set *scenes) {
-  if (mode == GIK_CLEARANCE_NODES) return anchored_clearance_launch(anch, d_Y_full, B, d_clearance, stream, scenes);
-  const int rc = anchored_link_clearance_launch(anch, d_Y_full, B, d_clearance, stream, scenes);
-  if (rc || mode == GIK_CLEARANCE_LINKS) return rc;
-  return anchored_self_clearance_launch(anch, d_Y_full, B, d_clearance, true, stream);
+  if (mode == GIK_CLEARANCE_NODES) {
+    const int rc = anchored_clearance_launch(anch, d_Y_full, B, d_clearance, stream, scenes);
+    return rc ? rc : fold_halfspaces(anch, d_Y_full, B, d_clearance, false, stream);
+  }
+  int rc = anchored_link_clearance_launch(anch, d_Y_full, B, d_clearance, stream, scenes);
+  if (!rc && mode != GIK_CLEARANCE_LINKS) rc = anchored_self_clearance_launch(anch, d_Y_full, B, d_clearance, true, stream);
+  return rc ? rc : fold_halfspaces(anch, d_Y_full, B, d_clearance, true, stream);      // (the room is the same in every scene)
 }
 
 // the start point from joint-configuration seeds (gik_anch_seed.hip.h): seed_kernel on the robot graph into the workspace,
@@ -449,8 +480,9 @@ static int anchored_clearance_entry(const char *entry, const gik_template *anch,
   if (refuse_capture(entry, stream)) return -1;
   if (B == 0) return 0;
   if (!d_Y_full || !d_clearance) return fail(e + ": null buffer");
-  return links ? anchored_link_clearance_launch(anch, d_Y_full, B, d_clearance, stream, scenes)      // (scenes: null without)
-               : anchored_clearance_launch(anch, d_Y_full, B, d_clearance, stream, scenes);
+  const int rc = links ? anchored_link_clearance_launch(anch, d_Y_full, B, d_clearance, stream, scenes)      // (scenes: null without)
+                       : anchored_clearance_launch(anch, d_Y_full, B, d_clearance, stream, scenes);
+  return rc ? rc : fold_halfspaces(anch, d_Y_full, B, d_clearance, links, stream);
 }
 
 int gik_anchored_clearance(const gik_template *anch, const double *d_Y_full, int B, double *d_clearance, void *stream) {
@@ -466,6 +498,22 @@ int gik_anchored_clearance_scenes(const gik_template *anch, const double *d_Y_fu
 int gik_anchored_link_clearance_scenes(const gik_template *anch, const double *d_Y_full, int B, const gik_scene_set *scenes,
                                        double *d_clearance, void *stream) {
   return anchored_clearance_entry("gik_anchored_link_clearance_scenes", anch, true, true, scenes, d_Y_full, B, d_clearance, stream);
+}
+
+// against the half-spaces alone (gik_anchored_attach_halfspaces): what the entries above fold into theirs
+int gik_anchored_halfspace_clearance(const gik_template *anch, const double *d_Y_full, int B, int links, double *d_clearance,
+                                     void *stream) {
+  using gik::fail;
+  const std::string e("gik_anchored_halfspace_clearance");
+  if (!anch || B < 0) return fail(e + ": bad argument");
+  if (!anch->anchored) return fail(e + ": the handle must be a fixed-anchor template (gik_template_create_anchored)");
+  if (anch->n_half <= 0) return fail(e + ": no half-spaces attached (gik_anchored_attach_halfspaces)");
+  if (links != 0 && links != 1) return fail(e + ": links must be 0 (the masked nodes) or 1 (the attached links)");
+  if (links && anch->n_link < 0) return fail(e + ": no links attached (gik_anchored_attach_links)");
+  if (refuse_capture("gik_anchored_halfspace_clearance", stream)) return -1;
+  if (B == 0) return 0;
+  if (!d_Y_full || !d_clearance) return fail(e + ": null buffer");
+  return anchored_half_clearance_launch(anch, d_Y_full, B, d_clearance, links != 0, false, stream);
 }
 
 // link against link: the pairs of gik_anchored_attach_self_pairs (none: +infinity, as the kernel leaves it)
@@ -538,6 +586,7 @@ static int anchored_sweep_impl(const char *entry, bool two_outputs, const gik_te
     if (!out) continue;
     rc = k == 0 ? anchored_link_clearance_launch(anch, w.Y, M, w.cl, stream)
                 : anchored_self_clearance_launch(anch, w.Y, M, w.cl, false, stream);
+    if (!rc && k == 0) rc = fold_halfspaces(anch, w.Y, M, w.cl, true, stream);      // (per sample, before the minimum)
     if (rc) return rc;
     AnchSweepMinArgs ma;
     ma.cl = w.cl;

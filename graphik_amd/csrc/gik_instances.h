@@ -58,6 +58,15 @@
   X(void kat_wave_kernel<3, 9, W_ANCH | W_LINKS | W_SELF>(KatArgs))                               \
   X(void rtr_wave_scene_kernel<3, 9, W_THETA1 | W_ANCH | W_SELF>(SolveArgs, SceneArgs))           \
   X(void rtr_wave_scene_kernel<3, 9, W_THETA1 | W_ANCH | W_LINKS | W_SELF>(SolveArgs, SceneArgs))
+// ... with half-space obstacles (gik_anchored_attach_halfspaces), without and with link hinges: solve, known answers, scenes.
+// Beside GIK_ALL_KERNELS too (gik_k_anch_half.hip), declared for the host unit by gik_kernels.hip.h.
+#define GIK_KERNELS_ANCH_HALF(X)                                                                  \
+  X(void rtr_wave_kernel<3, 9, W_THETA1 | W_ANCH | W_HALF>(SolveArgs))                            \
+  X(void rtr_wave_kernel<3, 9, W_THETA1 | W_ANCH | W_LINKS | W_HALF>(SolveArgs))                  \
+  X(void kat_wave_kernel<3, 9, W_ANCH | W_HALF>(KatArgs))                                         \
+  X(void kat_wave_kernel<3, 9, W_ANCH | W_LINKS | W_HALF>(KatArgs))                               \
+  X(void rtr_wave_scene_kernel<3, 9, W_THETA1 | W_ANCH | W_HALF>(SolveArgs, SceneArgs))           \
+  X(void rtr_wave_scene_kernel<3, 9, W_THETA1 | W_ANCH | W_LINKS | W_HALF>(SolveArgs, SceneArgs))
 // one unknown per lane, k = 2
 #define GIK_KERNELS_WAVE2(X)                          \
   X(void rtr_wave_kernel<2, 6, W_THETA1>(SolveArgs))  \

@@ -356,8 +356,19 @@ __host__ __device__ inline uint32_t link_meta_pack(int is_b, int other_const, in
 // SLIM: the layout of the per-edge product form (WaveCtxStrict, gik_wave_strict.hip.h): only the natural-order tile,
 // and slot metadata / slot records of the slots a lane OWNS (node slots comp, comp + 3, ...) -- 8.3 instead of 18.9 KB
 // of LDS per wavefront on a 7-DOF arm, which is what lets three wavefronts share a SIMD (153 VGPRs).
-template <int K, int MAXDEG, bool ANCH = false, bool SLIM = false, bool LINKS = false, bool SELF = false>
+
+// HALF: half-space obstacles on top (opt-in per template, gik_anchored_attach_halfspaces): floors and walls.  A half-space
+// h = (n, d0) with |n| = 1 allows s_h(p) = n.p - d0 >= 0; every free node i that carries the obstacle hinges (obs_mask) has
+// a margin mu_i >= 0 and, per half-space,
+//     res = mu_i - s_h(Y_i),   active <=> res > 0,   f += res^2,   G_i += -res n,   H_i += (n . W_i) n
+// The anchors fix the world frame, so s_h is linear in one row of Y: the Hessian block n n^T is exact wherever the active set
+// does not change -- no frozen foot.  Like every anchor term it touches cost(), commit() and the diagonal block `ba` only.
+// A linear function on a segment takes its minimum at an end, so a margin equal to a capsule's radius keeps the whole link
+// on the allowed side: no link code.  At most ANCH_HALF_MAX planes, walked wave-uniformly from LDS (no near lists); the
+// margins are a per-node LDS row.  Not with self hinges.
+template <int K, int MAXDEG, bool ANCH = false, bool SLIM = false, bool LINKS = false, bool SELF = false, bool HALF = false>
 struct WaveCtx {
+  static_assert(!HALF || (ANCH && MAXDEG == 9 && !SELF), "half-spaces: the 9-slot fixed-anchor context, without self hinges");
   static_assert(!SELF || (ANCH && MAXDEG == 9), "self hinges: the 9-slot fixed-anchor context");
   static_assert(!SLIM || (K == 3 && !ANCH), "the slim layout belongs to the 3-D per-edge context");
   static_assert(!LINKS || (ANCH && MAXDEG == 9), "link hinges: the 9-slot fixed-anchor context");
@@ -389,7 +400,8 @@ struct WaveCtx {
            (ANCH ? sizeof(double) * 4 * (ANCH_MAXA + ANCH_MAXOBS) + 16 * (size_t)ANCH_PMAX * WAVE +
                        48 * (size_t)WAVE : 0) +
            (LINKS ? sizeof(double) * ANCH_MAXOBS + (sizeof(AnchLinkRec) + sizeof(LinkObs)) * (size_t)ANCH_LMAX * ANCH_LROWS : 0) +
-           (SELF ? (sizeof(AnchSelfDesc) + sizeof(SelfState)) * (size_t)ANCH_SELF_HMAX : 0);
+           (SELF ? (sizeof(AnchSelfDesc) + sizeof(SelfState)) * (size_t)ANCH_SELF_HMAX : 0) +
+           (HALF ? sizeof(double) * (4 * (size_t)ANCH_HALF_MAX + (size_t)ANCH_HALF_ROWS) : 0);
   }
   // ---- fixed-anchor data (ANCH) ----
   // Everything per lane lives in LDS records (the 9-slot kernel has no VGPR to spare: per-lane
@@ -591,6 +603,30 @@ struct WaveCtx {
     w -= (int)ds.off[2] == nat_off ? 1.0 - st.t : 0.0;
     w -= (int)ds.off[3] == nat_off ? st.t : 0.0;
     return active ? w : 0.0;
+  }
+  // ---- half-space obstacles (HALF) ----
+  // The tables follow the last table of the build (the link tables, else the near lists), found from there at every use:
+  // no pointer is kept, the 9-slot context has no register to spare.
+  int n_half;              // wave-uniform
+  __device__ inline double *half_tab() const {      // [ANCH_HALF_MAX][4] nx, ny, nz, d0
+    if constexpr (LINKS) return reinterpret_cast<double *>(sh_lost + ANCH_LMAX * ANCH_LROWS);
+    else return reinterpret_cast<double *>(sh_ost + WAVE);
+  }
+  __device__ inline const double *half_mu_row() const { return half_tab() + 4 * ANCH_HALF_MAX; }   // [ANCH_HALF_ROWS] by tile row
+  // (after init_anchored, and after init_links where the build has them)
+  __device__ inline void init_half(const double *half, int n, const double *mu, int N) {
+    n_half = n < ANCH_HALF_MAX ? n : ANCH_HALF_MAX;
+    double *tab = half_tab();
+    __builtin_amdgcn_wave_barrier();
+    if (lane < 4 * ANCH_HALF_MAX) tab[lane] = lane < 4 * n_half ? half[lane] : 0.0;
+    if (lane < ANCH_HALF_ROWS) tab[4 * ANCH_HALF_MAX + lane] = lane < N ? mu[lane] : 0.0;
+    __builtin_amdgcn_wave_barrier();
+  }
+  // half-space h at this lane's node (its row in natural component order): max(mu - s_h, 0) where the node carries the
+  // hinges, else 0.  The three lanes of a node run the same operations on the same numbers: one residual per term.
+  __device__ inline double half_residual(const Row<K> &nat, const double4 &p, double mu) const {
+    const double s = fma(p.z, nat.v[K - 1], fma(p.y, nat.v[1], p.x * nat.v[0])) - p.w;
+    return obs_lane ? fmax(mu - s, 0.0) : 0.0;
   }
   __device__ inline void init_anchored(const uint64_t obs_mask, const double *obs, int n_obs_, bool cull) {
     sh_anch = sh_ck + 4 * WAVE;
@@ -852,6 +888,16 @@ struct WaveCtx {
         }
         obs_store(nat, slack, idx, cnt);
       }
+      if constexpr (HALF) {
+        // once per (node, half-space), like a pin term; an inactive one adds fma(0, 0, fa) = fa
+        const double mu = half_mu_row()[node];
+#pragma unroll 1
+        for (int h = 0; h < n_half; ++h) {
+          const double4 p = *reinterpret_cast<const double4 *>(half_tab() + 4 * h);   // wave-uniform
+          const double res = half_residual(nat, p, mu);
+          fa = fma(res, res, fa);
+        }
+      }
       f = fma(2.0, fa, f);
       if constexpr (LINKS) {
         // a pair enters f once: a link between two free nodes is evaluated at both (halved below), one with a constant
@@ -968,6 +1014,23 @@ struct WaveCtx {
         for (int q = 0; q < K; ++q) ba[q] = fma(a2, y[q], ba[q]);
         ba[0] += c;
         G = fma(c, y[0], G);
+      }
+      if constexpr (HALF) {
+        // 1/2 grad = -res n and 1/2 Hess = n n^T (exact): bsum = 2 ba, so the row of n n^T / 2, rotated like bq
+        const double mu = half_mu_row()[node];
+#pragma unroll 1
+        for (int h = 0; h < n_half; ++h) {
+          const double4 p = *reinterpret_cast<const double4 *>(half_tab() + 4 * h);
+          const double res = half_residual(nat, p, mu);
+          if (__builtin_amdgcn_ballot_w64(res != 0.0) == 0ull) continue;   // nobody is beyond this plane
+          const double nn[3] = {p.x, p.y, p.z};
+          double y[K];
+          rotate_nat(nn, y);
+          const double a = (res != 0.0) ? 0.5 * y[0] : 0.0;
+#pragma unroll
+          for (int q = 0; q < K; ++q) ba[q] = fma(a, y[q], ba[q]);
+          G = fma(-0.5 * res, y[0], G);
+        }
       }
       if constexpr (LINKS) {
 #pragma unroll 1

@@ -1,6 +1,6 @@
 // graphik_amd/csrc/gik_wave_kernels.hip.h -- the kernels of the one-wavefront-per-problem family (gfx950), as templates.
 // Instantiated in gik_k_wave3.hip, gik_k_wave3_strict.hip, gik_k_wave2.hip, gik_k_anch.hip, gik_k_anch_link.hip,
-// gik_k_anch_scene.hip and gik_k_anch_self.hip (gik_instances.h).
+// gik_k_anch_scene.hip, gik_k_anch_self.hip and gik_k_anch_half.hip (gik_instances.h).
 //
 //   rtr_wave_kernel : whole Riemannian trust-region solve (TrustRegions.solve +
 //                     _truncated_conjugate_gradient, graphik/solvers/trust_region.py:112-599)
@@ -64,11 +64,13 @@ enum WaveBuild : unsigned {
   W_PER_EDGE = 8,
   W_LINKS = 16,    // link hinges in the fixed-anchor solve (WaveCtx<.., LINKS>, gik_anchored_attach_links with hinges = 1)
   W_SELF = 32,     // self hinges in the fixed-anchor solve (WaveCtx<.., SELF>, gik_anchored_attach_self_hinges)
+  W_HALF = 64,     // half-space obstacles in the fixed-anchor solve (WaveCtx<.., HALF>, gik_anchored_attach_halfspaces)
 };
 // the context a build runs on
 template <int K, int MAXDEG, unsigned BUILD>
 using WaveBuildCtx = std::conditional_t<(BUILD & W_PER_EDGE) != 0, WaveCtxStrict<MAXDEG>,
-                                        WaveCtx<K, MAXDEG, (BUILD & W_ANCH) != 0, false, (BUILD & W_LINKS) != 0, (BUILD & W_SELF) != 0>>;
+                                        WaveCtx<K, MAXDEG, (BUILD & W_ANCH) != 0, false, (BUILD & W_LINKS) != 0, (BUILD & W_SELF) != 0,
+                                                (BUILD & W_HALF) != 0>>;
 // SCENES is not a bit but an entry point, rtr_wave_scene_kernel: per-goal obstacle scenes in the fixed-anchor solve
 // (gik_solve_batch_scenes).  The scene set is a second kernel
 // argument (SceneArgs, gik_scenes.h; SolveArgs and with it every other kernel stay as they are): a.an.obs is then the
@@ -81,8 +83,9 @@ using WaveBuildCtx = std::conditional_t<(BUILD & W_PER_EDGE) != 0, WaveCtxStrict
 template <int K, int MAXDEG, unsigned BUILD, bool SCENES = false>
 __device__ __forceinline__ void rtr_wave_run(const SolveArgs &a, const SceneArgs &sc = SceneArgs()) {
   constexpr bool THETA_ONE = BUILD & W_THETA1, ANCH = BUILD & W_ANCH, MIG = BUILD & W_SPREAD, STRICT = BUILD & W_PER_EDGE,
-                 LINKS = BUILD & W_LINKS, SELF = BUILD & W_SELF;
+                 LINKS = BUILD & W_LINKS, SELF = BUILD & W_SELF, HALF = BUILD & W_HALF;
   static_assert(!SCENES || ANCH, "scenes: the fixed-anchor kernels");
+  static_assert(!HALF || (ANCH && MAXDEG == 9 && !SELF), "half-spaces: the 9-slot fixed-anchor kernel, without self hinges");
   static_assert(!SELF || (ANCH && MAXDEG == 9), "self hinges: the 9-slot fixed-anchor kernel");
   static_assert(!LINKS || (ANCH && MAXDEG == 9), "link hinges: the 9-slot fixed-anchor kernel");
   static_assert(!ANCH || K == 3, "the fixed-anchor formulation is 3-D");
@@ -106,6 +109,7 @@ __device__ __forceinline__ void rtr_wave_run(const SolveArgs &a, const SceneArgs
     cx.init_anchored(a.an.obs_mask, a.an.obs, SCENES ? 0 : a.an.n_obs, !(a.dbg & 128));
     if constexpr (LINKS) cx.init_links(a.an.link_rec);
     if constexpr (SELF) cx.init_self(a.an.self_desc);
+    if constexpr (HALF) cx.init_half(a.half, a.n_half, a.half_mu, a.N);
     for (int t = lane; t < a.T; t += WAVE) sh_tgt[t] = a.targets[t];
     for (int t = lane; t < 4 * ANCH_MAXA; t += WAVE) cx.sh_anch[t] = a.an.anch_const[t];
     __builtin_amdgcn_wave_barrier();
@@ -350,8 +354,9 @@ __global__ void __launch_bounds__(WAVE, 2) rcg_wave_kernel(SolveArgs a) {
 
 template <int K, int MAXDEG, unsigned BUILD = 0>
 __global__ void __launch_bounds__(WAVE) kat_wave_kernel(KatArgs a) {
-  static_assert(!(BUILD & ~(W_ANCH | W_PER_EDGE | W_LINKS | W_SELF)), "known answers: the anchored, per-edge, link and self builds");
-  constexpr bool ANCH = BUILD & W_ANCH, LINKS = BUILD & W_LINKS, SELF = BUILD & W_SELF;
+  static_assert(!(BUILD & ~(W_ANCH | W_PER_EDGE | W_LINKS | W_SELF | W_HALF)),
+                "known answers: the anchored, per-edge, link, self and half-space builds");
+  constexpr bool ANCH = BUILD & W_ANCH, LINKS = BUILD & W_LINKS, SELF = BUILD & W_SELF, HALF = BUILD & W_HALF;
   using Ctx = WaveBuildCtx<K, MAXDEG, BUILD>;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int lane = threadIdx.x;
@@ -370,6 +375,7 @@ __global__ void __launch_bounds__(WAVE) kat_wave_kernel(KatArgs a) {
     cx.init_anchored(a.an.obs_mask, a.an.obs, a.an.n_obs, true);
     if constexpr (LINKS) cx.init_links(a.an.link_rec);
     if constexpr (SELF) cx.init_self(a.an.self_desc);
+    if constexpr (HALF) cx.init_half(a.half, a.n_half, a.half_mu, a.N);
     for (int t = lane; t < 4 * ANCH_MAXA; t += WAVE) cx.sh_anch[t] = a.an.anch_const[t];
     __builtin_amdgcn_wave_barrier();
     if (lane < 3 * a.an.n_goal)

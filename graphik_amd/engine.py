@@ -328,6 +328,7 @@ class Template:
         self.link_hinges = False
         self.n_self = None      # (attach_self_pairs)
         self.self_hinges = False
+        self.n_half = 0         # (attach_halfspaces)
         self._read_info()
         deg = np.bincount(np.concatenate([self.term_i, self.term_j]), minlength=self.N).max()
         # compiled slot count of the wavefront variant the library chose (or the raw degree: workgroup / node-per-lane paths)
@@ -775,6 +776,42 @@ class Template:
         minimum over the attached link pairs of the distance between the two capsules; +inf without pairs."""
         assert self.anchored
         return self._clearance_of("gik_anchored_self_clearance", Y_full)
+
+    def attach_halfspaces(self, halfspaces, node_margin):
+        """Half-space obstacles (gik_anchored_attach_halfspaces), once and last -- after attach_links / attach_self_pairs:
+        halfspaces [H, 4] rows (nx, ny, nz, d0) with |n| = 1, H within 1 .. 8, the allowed side n.p - d0 >= 0;
+        node_margin [N] metres per free node (read where obs_node_mask is 1).  Every later call on this template, the
+        known-answer entry points included, runs the half-space builds of its kernels, and every clearance it reports is
+        the minimum of the spheres' and anchored_halfspace_clearance; self.n_half and bit 8 of self.info["anchored"]
+        (9, with link hinges 11) say so."""
+        assert self.anchored
+        h = np.ascontiguousarray(halfspaces, dtype=np.float64)
+        m = np.ascontiguousarray(node_margin, dtype=np.float64).reshape(-1)
+        if h.ndim != 2 or h.shape[1] != 4:
+            raise ValueError(f"halfspaces must have shape [H, 4], got {list(h.shape)}")
+        if len(m) != self.N:
+            raise ValueError(f"node_margin must have one entry per free node ({self.N}), got {len(m)}")
+        self._call("gik_anchored_attach_halfspaces", self._h, len(h), h.ctypes.data_as(C.POINTER(C.c_double)),
+                   m.ctypes.data_as(C.POINTER(C.c_double)))
+        self.n_half = len(h)
+        self._read_info()      # (other kernels, LDS bytes and occupancy)
+
+    def anchored_halfspace_clearance(self, Y_full, links=False):
+        """Full point matrices [B, full_N, 3] -> [B] on the device (gik_anchored_halfspace_clearance): the minimum over the
+        masked free nodes and the half-spaces of n.Y_i - d0 - margin_i, or with links=True over both end rows of every
+        attached link of n.P - d0 - link_radius.  What anchored_clearance / anchored_link_clearance fold into theirs."""
+        assert self.anchored
+        if not isinstance(links, (bool, np.bool_)):
+            raise TypeError(f"links must be a bool, got {links!r}")
+        Y = _dev(Y_full, self.device)
+        if Y.dim() == 2:
+            Y = Y[None]
+        B = Y.shape[0]
+        assert Y.numel() == B * self.full_N * 3, (tuple(Y.shape), (B, self.full_N, 3))
+        Y = Y.reshape(B, self.full_N * 3).contiguous()
+        out = torch.empty(B, dtype=torch.float64, device=self.device)
+        self._call("gik_anchored_halfspace_clearance", self._h, Y.data_ptr(), B, int(links), out.data_ptr(), self._stream())
+        return out
 
     def anchored_sweep_clearances(self, base, q_a, q_b, samples, link_out=None, self_out=None, ws=None, link=True, self_=True):
         """anchored_sweep_clearance with two outputs from one realization of the samples (gik_anchored_sweep_clearances):

@@ -650,7 +650,7 @@ class AnchoredProblem:
     without obstacles) fitted to the world frame by its anchors."""
 
     def __init__(self, graph, params=None, device=None, host_only=False, links=None, link_radius=0.0, link_hinges=False,
-                 goal="pose", self_pairs=None, self_hinges=False):
+                 goal="pose", self_pairs=None, self_hinges=False, halfspaces=None, halfspace_margin=None):
         """host_only: derive the term set only (no device handles) -- what tests/test_host_layer.py
         compares with the reference's own edge construction (tests/golden/ur10_table_intended.npz).
 
@@ -675,7 +675,17 @@ class AnchoredProblem:
         finds a self-clear answer by landing elsewhere -- or True: the solve kernel also carries a hinge per pair on the
         distance between the two SEGMENTS (gik_anchored_attach_self_hinges; self_hinge_terms_host is the numpy mirror of the
         terms), so every solve, restart, scene and tracked waypoint of this problem pushes the robot's own links apart.
-        Needs self_pairs, at most 16 of them; chains on the 9-slot anchored kernel; with or without link_hinges."""
+        Needs self_pairs, at most 16 of them; chains on the 9-slot anchored kernel; with or without link_hinges.
+        halfspaces: floors and walls, an array-like [H, 4] of (nx, ny, nz, d0) rows, H within 1 .. 8: the allowed side of
+        row h is n.p - d0 >= 0 (each row is divided by |n| here; self.halfspaces holds the result).  Every masked free node i
+        then carries the hinge max(0, margin_i - (n.Y_i - d0))^2 per half-space in the solve
+        (gik_anchored_attach_halfspaces; halfspace_terms_host is the numpy mirror), and every clearance the device reports
+        -- solve, restarts, scenes, tracking, sweeps -- is the minimum of the spheres' and halfspace_clearance.  With scenes
+        the half-spaces stay the problem's: the room.  None: nothing is attached, the problem runs what it ran.
+        halfspace_margin: None -- each masked free node gets the largest link_radius among the attached links that end at
+        it (0 without), which keeps whole capsules on the allowed side: a linear function on a segment takes its minimum at
+        an end --, or a scalar, or one entry per free node (self.free_names), metres, >= 0.  self.halfspace_margin holds it.
+        Chains on the 9-slot anchored kernel; with or without link_hinges; not together with self_hinges."""
         import copy
         from ..utils.constants import OBSTACLE, ROBOT, TYPE, MAIN_PREFIX
         from .. import _ffi
@@ -694,6 +704,7 @@ class AnchoredProblem:
         if self_hinges and self_pairs is None:
             raise ValueError("self_hinges=True needs self pairs: self_pairs=None attaches none")
         self.self_hinges = bool(self_hinges)
+        self.halfspaces = self._check_halfspaces(halfspaces, halfspace_margin, self.self_hinges)      # (before any device call)
         self.graph, self.robot = graph, graph.robot
         obstacles = [n for n in graph.node_ids if graph.nodes[n].get(TYPE) == OBSTACLE]
         bare = copy.deepcopy(graph)
@@ -758,6 +769,7 @@ class AnchoredProblem:
         self.free_names = names
         self.free_terms = (ti, tj, tk, target)
         self.obs_mask = np.array(mask, dtype=np.int32)
+        self.halfspace_margin = self._halfspace_margins(halfspace_margin)
         if host_only:
             self.template = None
             return
@@ -774,6 +786,124 @@ class AnchoredProblem:
             self.template.attach_self_pairs(self.self_pairs[:, 0], self.self_pairs[:, 1])
         if self.self_hinges:
             self.template.attach_self_hinges()
+        if self.halfspaces is not None:      # (last: it re-resolves the kernels of the form the calls above left)
+            self.template.attach_halfspaces(self.halfspaces, self.halfspace_margin)
+
+    @staticmethod
+    def _check_halfspaces(halfspaces, halfspace_margin, self_hinges):
+        """halfspaces of __init__ -> [H, 4] float64 with unit normals (None: none), checked on the host: ValueError for a
+        shape other than [H, 4], H outside 1 .. 8, a zero or non-finite normal, a non-finite offset, a margin without
+        half-spaces, and self_hinges=True together with halfspaces."""
+        from .. import _ffi
+        if halfspaces is None:
+            if halfspace_margin is not None:
+                raise ValueError("halfspace_margin needs halfspaces: halfspaces=None attaches none")
+            return None
+        if self_hinges:
+            raise ValueError("halfspaces together with self_hinges=True is not supported: the solve has no such build")
+        try:
+            h = np.array(halfspaces, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("halfspaces must be an array-like of shape [H, 4]: rows (nx, ny, nz, d0)") from None
+        if h.ndim != 2 or h.shape[1] != 4:
+            raise ValueError(f"halfspaces must have shape [H, 4] (rows nx, ny, nz, d0), got {list(h.shape)}")
+        if not 1 <= len(h) <= _ffi.HALF_MAX:
+            raise ValueError(f"halfspaces takes 1 .. {_ffi.HALF_MAX} rows, got {len(h)}")
+        if not np.all(np.isfinite(h)):
+            raise ValueError("halfspaces has non-finite entries")
+        norm = np.sqrt(_dot3(h, h))
+        if not np.all(np.isfinite(norm) & (norm > 0.0)):
+            raise ValueError("halfspaces: a normal (nx, ny, nz) is zero or overflows")
+        return np.ascontiguousarray(h / norm[:, None])      # (| |n|^2 - 1 | is then a few ulp: the C entry asks for 1e-12)
+
+    def _halfspace_margins(self, halfspace_margin):
+        """halfspace_margin of __init__ -> [len(free)] float64 (None without half-spaces): the default from the link radii,
+        a scalar broadcast, or one entry per free node; ValueError for another shape and for a negative or non-finite entry."""
+        if self.halfspaces is None:
+            return None
+        Nf = len(self.free)
+        if halfspace_margin is None:
+            mu = np.zeros(Nf)
+            for (ra, rb), rho in zip(np.asarray(self.link_rows).tolist(), self.link_radius):
+                for r in (ra, rb):
+                    if r in self.free:
+                        f = self.free.index(r)
+                        mu[f] = max(mu[f], float(rho))
+            return np.where(self.obs_mask == 1, mu, 0.0)
+        try:
+            mu = np.array(halfspace_margin, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("halfspace_margin must be None, a scalar or one entry per free node") from None
+        if mu.ndim == 0:
+            mu = np.full(Nf, float(mu))
+        if mu.shape != (Nf,):
+            raise ValueError(f"halfspace_margin must be a scalar or have one entry per free node ({Nf}), got shape {list(mu.shape)}")
+        if not np.all(np.isfinite(mu) & (mu >= 0)):
+            raise ValueError("halfspace_margin must be finite and at least 0")
+        return np.ascontiguousarray(mu)
+
+    @staticmethod
+    def _halfspace_s(P, h):
+        """s_h(P) = ((nx x + ny y) + nz z) - d0 for points P [..., 3] against rows h [H, 4] -> [..., H]: every product and
+        sum rounded on its own, the bits of anch_half_clearance_kernel."""
+        P = P[..., None, :]
+        return ((h[:, 0] * P[..., 0] + h[:, 1] * P[..., 1]) + h[:, 2] * P[..., 2]) - h[:, 3]
+
+    def halfspace_clearance(self, Y_full, links=False):
+        """min over (masked free node i, half-space h) of s_h(Y_i) - margin_i per goal, or with links=True over (link l,
+        both of its end rows, h) of s_h(P) - link_radius[l]: the host mirror of gik_anchored_halfspace_clearance, the same
+        operations in the same order.  Y_full [B, N_robot, 3] (numpy).  >= 0: every measured point keeps its margin to
+        every plane; with the default margins the node value bounds the link value over the links with a free end.  No
+        half-spaces, no masked node or no link: +inf; a NaN coordinate of a measured row: NaN for that goal."""
+        Y = np.asarray(Y_full, dtype=np.float64)
+        if Y.ndim == 2:
+            Y = Y[None]
+        B = Y.shape[0]
+        if self.halfspaces is None:
+            return np.full(B, np.inf)
+        if links:
+            rows = np.asarray(self.link_rows, dtype=np.int64).reshape(-1, 2)
+            if len(rows) == 0:
+                return np.full(B, np.inf)
+            P = Y[:, rows]                                                          # [B, n_link, 2, 3]
+            with np.errstate(invalid="ignore"):
+                val = self._halfspace_s(P, self.halfspaces) - np.asarray(self.link_radius)[None, :, None, None]
+            return _nan_min(val, axis=(1, 2, 3))
+        nodes = [self.free[i] for i in range(len(self.free)) if self.obs_mask[i] == 1]
+        if not nodes:
+            return np.full(B, np.inf)
+        mu = self.halfspace_margin[self.obs_mask == 1]
+        with np.errstate(invalid="ignore"):
+            val = self._halfspace_s(Y[:, nodes], self.halfspaces) - mu[None, :, None]
+        return _nan_min(val, axis=(1, 2))
+
+    def halfspace_terms_host(self, Y_free, W, frozen_active=None):
+        """(f, G, H) of the half-space hinges alone at one point: Y_free, W [Nf, 3], in the conventions of
+        link_hinge_terms_host (f = sum res^2, G = 1/2 grad f, H = 1/2 Hess f [W]).  Per (masked free node i, half-space h):
+            res = margin_i - (n.Y_i - d0),  active <=> res > 0
+            f += res^2;  G_i += -res n;  H_i += (n . W_i) n
+        H is exact wherever the active set does not change.  Unmasked nodes carry nothing; the anchors are constants.
+        frozen_active: a set of (free node, half-space) to take as the active set instead of this point's (what a finite
+        difference of the gradient across a boundary needs); this point's own comes back in self.last_half_active."""
+        Y, W = np.asarray(Y_free, dtype=np.float64), np.asarray(W, dtype=np.float64)
+        f, G, H = 0.0, np.zeros_like(Y), np.zeros_like(Y)
+        self.last_half_active = set()
+        if self.halfspaces is None:
+            return f, G, H
+        for i in range(len(self.free)):
+            if self.obs_mask[i] != 1:
+                continue
+            for h, (nx, ny, nz, d0) in enumerate(self.halfspaces):
+                n = np.array([nx, ny, nz])
+                res = self.halfspace_margin[i] - (float(n @ Y[i]) - d0)
+                if res > 0.0:
+                    self.last_half_active.add((i, h))
+                if not ((i, h) in frozen_active if frozen_active is not None else res > 0.0):
+                    continue
+                f += res * res
+                G[i] += -res * n
+                H[i] += float(n @ W[i]) * n
+        return f, G, H
 
     @staticmethod
     def _check_self_pairs(self_pairs, link_rows):

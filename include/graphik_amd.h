@@ -228,7 +228,8 @@ typedef struct {
   int32_t lds_bytes;           /* dynamic LDS per wavefront / workgroup of the solve kernel         */
   int32_t clique_closed_form;  /* GIK_CLIQUE_* in effect                                            */
   int32_t anchored;            /* bit 0: fixed-anchor template; bit 1: link hinges are on (gik_anchored_attach_links
-                                  with hinges = 1): 0, 1 or 3                                          */
+                                  with hinges = 1): 0, 1 or 3; bit 2: self hinges (5, 7); bit 3: half-space
+                                  obstacles (gik_anchored_attach_halfspaces): 9, or 11 with link hinges   */
   int32_t has_pipeline;
   int32_t prepare_is_block;    /* workgroup-per-goal prepare kernel                                 */
   int32_t node_per_lane;       /* != 0: an is_block graph solved by the node-per-lane kernel instead of the
@@ -678,6 +679,43 @@ int gik_anchored_sweep_clearances(const gik_template *anch, const gik_template *
                                   const double *d_q_b, int B, int samples, double *d_ws,
                                   double *d_link_out /* may be NULL */, double *d_self_out /* may be NULL */,
                                   void *stream);
+
+/* ---- half-space obstacles in the fixed-anchor solve: floors and walls (opt-in) ---------------------
+ * A half-space h is (n_h, d_h) with |n_h| = 1; the allowed side is s_h(p) = n_h.p - d_h >= 0.  The anchors fix the world
+ * frame, so s_h is a linear function of one row of the point matrix.
+ * gik_anchored_attach_halfspaces: once and LAST -- after gik_anchored_attach_links and gik_anchored_attach_self_pairs where
+ *   those are used.  halfspaces [n_half][4] holds (nx, ny, nz, d0) per row, n_half within 1 .. 8; node_margin [N] holds a
+ *   margin mu_i >= 0 in metres per free node, read where obs_node_mask is 1.  Every masked free node i then carries, per
+ *   half-space,
+ *       res = mu_i - s_h(Y_i),  active where res > 0 (a node exactly on the boundary is inactive)
+ *       f += res^2;   G_i += -res n_h;   H_i += (n_h . W_i) n_h      (G = 1/2 grad f, H = 1/2 Hess f [W], as everywhere)
+ *   The Hessian block n n^T is exact wherever the active set does not change.  Unmasked nodes and anchors carry nothing.
+ *   A linear function on a segment takes its minimum at an end: with mu_i = the radius of the capsules that end at node
+ *   i, the node terms keep whole links on the allowed side, with or without link hinges.
+ *   The template's solve, known-answer and scene kernels become the half-space builds of its current form (with or
+ *   without link hinges), with their LDS bytes and occupancy (gik_template_info.anchored gains bit 8: 9, or 11 with link
+ *   hinges); every later call on the template runs them.  With no half-space active a solve's results are those of the
+ *   build without.  With scenes the half-spaces stay constants of the handle -- the room; the spheres vary per goal.
+ *   Refused with a message, nothing uploaded: a handle that is not a fixed-anchor template, a second call, n_half outside
+ *   1 .. 8, a null array, an entry that is not finite, | |n|^2 - 1 | > 1e-12, a margin of a masked node that is negative
+ *   or not finite, a template on the 20-slot kernel, a template with self hinges attached.  On a handle with half-spaces
+ *   gik_anchored_attach_self_hinges, and gik_anchored_attach_links with hinges = 1, are refused and leave it unchanged.
+ * gik_anchored_halfspace_clearance: d_clearance [B] on d_Y_full [B][full_N*3] =
+ *       links = 0: min over (masked free node i, h) of s_h(Y_i) - mu_i
+ *       links = 1: min over (attached link l, both of its end rows P -- anchors and goal rows included --, h) of
+ *                  s_h(P) - link_radius[l]
+ *   with s_h = ((nx x + ny y) + nz z) - d0, every product and sum rounded on its own.  No node or no link: +infinity.  A
+ *   NaN coordinate: NaN for that goal alone.  Refused: what gik_anchored_link_clearance refuses, a template without
+ *   half-spaces, links outside {0, 1}, and links = 1 without links attached.  B == 0 returns 0.
+ * On a handle with half-spaces EVERY clearance the library reports is the NaN-propagating minimum of the spheres' value and
+ * this one (links = 0 behind the node clearance, 1 behind the link modes): gik_anchored_clearance, _link_clearance and their
+ * scene variants, the clearance of every solve entry and restart in every clearance_mode, and the link output of both sweep
+ * entries, per sample and before the minimum over the samples.  The restart rule therefore reads the room too.
+ * gik_anchored_self_clearance stays what it is. */
+int gik_anchored_attach_halfspaces(gik_template *anch, int n_half, const double *halfspaces /* [n_half][4]: nx, ny, nz, d0 */,
+                                   const double *node_margin /* [N] free nodes, metres; read where obs_node_mask is 1 */);
+int gik_anchored_halfspace_clearance(const gik_template *anch, const double *d_Y_full, int B, int links /* 0: nodes, 1: links */,
+                                     double *d_clearance, void *stream);
 
 /* ---- restarts in the anchored solve, with a clearance rule (opt-in) -----------------------------
  * The restarts of gik_ik_batch_retry for the fixed-anchor formulation.  The obstacle hinges are soft cost terms: an
