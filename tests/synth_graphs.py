@@ -330,12 +330,16 @@ REFUSED = {
 # instantiations that the existing suite reaches (anchored formulation, prepare kernels): named, not re-tested
 _PREP_HOST = "tests/test_prepare_boundaries_gpu.py::test_prepare_against_the_host"
 _PREP_MULTI = "tests/test_prepare_boundaries_gpu.py::test_a_workgroup_that_takes_more_than_one_goal"
+_HINGE_TWIN = "tests/test_anchored_hinge_twin_gpu.py::test_solve_against_the_numpy_twin"
+_SELF_SCENES = "tests/test_anchored_self_hinges_gpu.py::test_scenes_are_bit_identical_to_their_own_templates"
+_HALF_SCENES = "tests/test_anchored_halfspaces_gpu.py::test_scenes_are_bit_identical_to_their_own_templates"
 EXISTING = {
     "rtr_wave_kernel<3,9,W_THETA1|W_ANCH>": ["tests/test_hip_gpu.py::test_anchored_trajectory_against_oracle",
                                              "tests/test_hip_gpu.py::test_anchored_pipeline"],
     "kat_wave_kernel<3,9,W_ANCH>": ["tests/test_hip_gpu.py::test_anchored_kernel_known_answers"],
     # ... with link hinges (UR10 + table, AnchoredProblem(link_hinges=True))
-    "rtr_wave_kernel<3,9,W_THETA1|W_ANCH|W_LINKS>": ["tests/test_anchored_link_hinges_gpu.py::test_the_blind_spot_closes",
+    "rtr_wave_kernel<3,9,W_THETA1|W_ANCH|W_LINKS>": [_HINGE_TWIN,
+                                                     "tests/test_anchored_link_hinges_gpu.py::test_the_blind_spot_closes",
                                                      "tests/test_anchored_link_hinges_gpu.py::test_the_new_kernel_group_is_what_the_hinge_template_runs"],
     "kat_wave_kernel<3,9,W_ANCH|W_LINKS>": ["tests/test_anchored_link_hinges_gpu.py::test_link_hinge_known_answers"],
     # ... the scene entries: the synthetic cases near9 / a20_full of tests/synth_anchored_scenes.py (9 and 20 slots, asserted
@@ -345,6 +349,21 @@ EXISTING = {
     "rtr_wave_scene_kernel<3,20,W_THETA1|W_ANCH>": ["tests/test_anchored_scenes_gpu.py::test_template_level_bit_identity",
                                                     "tests/test_anchored_scenes_gpu.py::test_a_wave_changes_scene_between_problems"],
     "rtr_wave_scene_kernel<3,9,W_THETA1|W_ANCH|W_LINKS>": ["tests/test_anchored_scenes_gpu.py::test_ur10_three_scenes"],
+    # the self-hinge and half-space groups (GIK_KERNELS_ANCH_SELF, GIK_KERNELS_ANCH_HALF, beside GIK_ALL_KERNELS): the solve
+    # builds against the numpy trust-region twin (HINGE_TWIN_CASES below names the cases), the known-answer builds against
+    # numpy, the scene builds bit-identical to their own templates
+    "rtr_wave_kernel<3,9,W_THETA1|W_ANCH|W_SELF>": [_HINGE_TWIN],
+    "rtr_wave_kernel<3,9,W_THETA1|W_ANCH|W_LINKS|W_SELF>": [_HINGE_TWIN],
+    "rtr_wave_kernel<3,9,W_THETA1|W_ANCH|W_HALF>": [_HINGE_TWIN],
+    "rtr_wave_kernel<3,9,W_THETA1|W_ANCH|W_LINKS|W_HALF>": [_HINGE_TWIN],
+    "kat_wave_kernel<3,9,W_ANCH|W_SELF>": ["tests/test_anchored_self_hinges_gpu.py::test_self_hinge_known_answers"],
+    "kat_wave_kernel<3,9,W_ANCH|W_LINKS|W_SELF>": ["tests/test_anchored_self_hinges_gpu.py::test_self_hinge_known_answers"],
+    "kat_wave_kernel<3,9,W_ANCH|W_HALF>": ["tests/test_anchored_halfspaces_gpu.py::test_halfspace_known_answers"],
+    "kat_wave_kernel<3,9,W_ANCH|W_LINKS|W_HALF>": ["tests/test_anchored_halfspaces_gpu.py::test_halfspace_known_answers"],
+    "rtr_wave_scene_kernel<3,9,W_THETA1|W_ANCH|W_SELF>": [_SELF_SCENES],
+    "rtr_wave_scene_kernel<3,9,W_THETA1|W_ANCH|W_LINKS|W_SELF>": [_SELF_SCENES],
+    "rtr_wave_scene_kernel<3,9,W_THETA1|W_ANCH|W_HALF>": [_HALF_SCENES],
+    "rtr_wave_scene_kernel<3,9,W_THETA1|W_ANCH|W_LINKS|W_HALF>": [_HALF_SCENES],
     # the prepare kernels: against the host restatement at every size boundary (the case table of tests/synth_prepare.py,
     # tests/test_prepare_boundaries_host.py keeps it complete), and the older kernel-against-kernel comparisons
     "prep_block_kernel<true>": [_PREP_HOST, _PREP_MULTI, "tests/test_hip_gpu.py::test_block_prepare_kernel_equals_wave_kernel"],
@@ -354,6 +373,14 @@ EXISTING = {
     "prep_quad_kernel<13>": [_PREP_HOST, _PREP_MULTI, "tests/test_hip_gpu.py::test_quad_prepare_kernel_against_wave_kernel"],
     "prep_quad_kernel<0>": [_PREP_HOST, _PREP_MULTI,
                             "tests/test_hip_gpu.py::test_planar_chains_of_other_sizes_on_the_quad_kernels"],
+}
+# the solve builds with hinges -> the cases of tests/test_anchored_hinge_twin_host.py that pin them against the numpy twin
+HINGE_TWIN_CASES = {
+    "rtr_wave_kernel<3,9,W_THETA1|W_ANCH|W_LINKS>": ["links"],
+    "rtr_wave_kernel<3,9,W_THETA1|W_ANCH|W_SELF>": ["self"],
+    "rtr_wave_kernel<3,9,W_THETA1|W_ANCH|W_LINKS|W_SELF>": ["self_links"],
+    "rtr_wave_kernel<3,9,W_THETA1|W_ANCH|W_HALF>": ["half", "half8"],
+    "rtr_wave_kernel<3,9,W_THETA1|W_ANCH|W_LINKS|W_HALF>": ["half_links"],
 }
 # compiled but outside this matrix on purpose, with the reason (none at present: the 20-slot anchored kernels are
 # reached through tests/synth_anchored.py's case table)
@@ -380,9 +407,13 @@ def coverage():
     return cov
 
 
+# kernel groups that stand beside GIK_ALL_KERNELS (units of their own, declared for the host unit by gik_kernels.hip.h)
+BESIDE_ALL_KERNELS = ("GIK_KERNELS_ANCH_SELF", "GIK_KERNELS_ANCH_HALF")
+
+
 def compiled_instances(text=None):
-    """The instantiations GIK_ALL_KERNELS expands to (gik_instances.h), without blanks:
-    'rtr_wave_kernel<3,9,W_THETA1>' etc."""
+    """The instantiations GIK_ALL_KERNELS expands to (gik_instances.h) and those of the groups beside it
+    (BESIDE_ALL_KERNELS), without blanks: 'rtr_wave_kernel<3,9,W_THETA1>' etc."""
     if text is None:
         with open(INSTANCES_H) as f:
             text = f.read()
@@ -392,6 +423,8 @@ def compiled_instances(text=None):
     m = re.search(r"#define\s+GIK_ALL_KERNELS\(X\)((?:[^\n]*\\\n)*[^\n]*)", text)
     assert m, "GIK_ALL_KERNELS not found"
     used = re.findall(r"(GIK_KERNELS_\w+)\(X\)", m.group(1))
+    assert not set(BESIDE_ALL_KERNELS) & set(used), "a group beside GIK_ALL_KERNELS is now inside it"
+    used += list(BESIDE_ALL_KERNELS)
     out = []
     for g in used:
         assert g in groups, g

@@ -23,7 +23,7 @@ def test_every_instantiation_has_a_case():
     missing, stale = _gaps()
     assert not missing, f"compiled kernels without a case in tests/synth_graphs.py: {missing}"
     assert not stale, f"coverage entries for kernels gik_instances.h no longer compiles: {stale}"
-    assert len(sg.compiled_instances()) >= 50      # (the parser found the groups: 58 when this was written)
+    assert len(sg.compiled_instances()) >= 62      # (the parser found the groups: 75 with the two beside GIK_ALL_KERNELS)
 
 
 def test_a_new_instantiation_without_a_case_fails():
@@ -38,6 +38,42 @@ def test_a_new_instantiation_without_a_case_fails():
     assert dropped != text
     missing, stale = _gaps(dropped)
     assert not missing and stale == ["rcg_wave_kernel<2,31>"]
+    # the groups beside GIK_ALL_KERNELS are parsed too: a member more, a member less, a group gone
+    extra = "  X(void rtr_wave_kernel<3, 20, W_THETA1 | W_ANCH | W_HALF>(SolveArgs))  \\\n"
+    anchor = "#define GIK_KERNELS_ANCH_HALF(X)                                                                  \\\n"
+    assert anchor in text
+    missing, stale = _gaps(text.replace(anchor, anchor + extra))
+    assert missing == ["rtr_wave_kernel<3,20,W_THETA1|W_ANCH|W_HALF>"] and not stale
+    dropped = re.sub(r"[^\n]*X\(void kat_wave_kernel<3, 9, W_ANCH \| W_LINKS \| W_SELF>\(KatArgs\)\)[^\n]*\n", "", text)
+    assert dropped != text
+    missing, stale = _gaps(dropped)
+    assert not missing and stale == ["kat_wave_kernel<3,9,W_ANCH|W_LINKS|W_SELF>"]
+    with pytest.raises(AssertionError, match="GIK_KERNELS_ANCH_SELF"):
+        sg.compiled_instances(text.replace("#define GIK_KERNELS_ANCH_SELF(X)", "#define GIK_KERNELS_ANCH_SELF_GONE(X)"))
+
+
+def test_the_groups_beside_all_kernels_are_in_the_table():
+    """GIK_KERNELS_ANCH_SELF and GIK_KERNELS_ANCH_HALF: six instantiations each, every one compiled once and with an entry
+    of its own in EXISTING, the solve builds through a case of the numpy twin's table."""
+    import test_anchored_hinge_twin_host as th
+    with open(sg.INSTANCES_H) as f:
+        text = f.read()
+    compiled = sg.compiled_instances()
+    for group in sg.BESIDE_ALL_KERNELS:
+        m = re.search(rf"#define\s+{group}\(X\)((?:[^\n]*\\\n)*[^\n]*)", text)
+        members = [re.sub(r"\s+", "", s) for s in re.findall(r"X\(\s*void\s+(\w+\s*<[^>]*>)\s*\(", m.group(1))]
+        assert len(members) == 6
+        for inst in members:
+            assert compiled.count(inst) == 1 and sg.EXISTING.get(inst), inst
+            if inst.startswith("rtr_wave_kernel"):
+                assert sg.EXISTING[inst] == [sg._HINGE_TWIN] and sg.HINGE_TWIN_CASES.get(inst), inst
+    # every case of the twin's table is named by the solve build it pins, and by no other
+    flags = {3: "W_LINKS", 5: "W_SELF", 7: "W_LINKS|W_SELF", 9: "W_HALF", 11: "W_LINKS|W_HALF"}
+    for case, c in th.CASES.items():
+        named = [inst for inst, cases in sg.HINGE_TWIN_CASES.items() if case in cases]
+        assert named == [f"rtr_wave_kernel<3,9,W_THETA1|W_ANCH|{flags[c['build']]}>"], (case, named)
+    assert all(sg._HINGE_TWIN in sg.EXISTING[inst] for inst in sg.HINGE_TWIN_CASES)
+    assert sorted(c for cases in sg.HINGE_TWIN_CASES.values() for c in cases) == sorted(th.CASES)
 
 
 def test_named_existing_tests_exist():
