@@ -21,7 +21,7 @@
 #include <thread>
 
 namespace gik {
-GIK_ALL_KERNELS(GIK_EXTERN_TEMPLATE)      // (the self-hinge and half-space groups, beside it: at the end of gik_kernels.hip.h)
+GIK_ALL_KERNELS(GIK_EXTERN_TEMPLATE)      // (every group of gik_instances.h: the one expansion on the host side)
 
 // the compiled node-per-lane variants
 struct NptVariant {
@@ -53,17 +53,15 @@ typedef void (*scene_fn)(SolveArgs, SceneArgs);
 typedef void (*kat_fn)(KatArgs);
 typedef size_t (*lds_fn)(int);
 
-// The compiled one-unknown-per-lane builds: one row per (K, slots, form), exactly what gik_instances.h instantiates.
-// A build a form does not have stays null.
-// (PER_EDGE: hessian_form = GIK_HESS_PER_EDGE, k = 3, TrustRegions; ANCHORED: the fixed-anchor formulation, k = 3, theta == 1;
-// ANCHORED_LINK: ... with link hinges.  Creation never asks for that form: gik_anchored_attach_links with hinges = 1
-// re-resolves an anchored 9-slot template to it; ANCHORED_SELF / ANCHORED_LINK_SELF: either with self hinges,
-// gik_anchored_attach_self_hinges re-resolves to the one that matches the template's current form; ANCHORED_HALF /
-// ANCHORED_LINK_HALF: either with half-space obstacles, gik_anchored_attach_halfspaces does the same)
-enum Form { COLUMN, PER_EDGE, ANCHORED, ANCHORED_LINK, ANCHORED_SELF, ANCHORED_LINK_SELF, ANCHORED_HALF, ANCHORED_LINK_HALF };
+// The compiled one-unknown-per-lane builds: one row per (K, slots, build word), exactly what gik_instances.h instantiates.
+// A row is named by the WaveBuild bits its kernels share: the word without W_THETA1 and W_SPREAD, which name kernels
+// within a row.  A kernel a row does not have stays null.  (PER_EDGE: hessian_form = GIK_HESS_PER_EDGE, k = 3, TrustRegions;
+// W_ANCH: the fixed-anchor formulation, k = 3, theta == 1.  Creation asks for COLUMN or W_ANCH only: the rows with
+// W_LINKS, W_SELF, W_HALF are what the attach entries re-resolve a 9-slot fixed-anchor template to, reresolve_anchored)
+constexpr unsigned COLUMN = 0u, PER_EDGE = W_PER_EDGE;
 struct WaveRow {
   int K, slots;
-  Form form;
+  unsigned build;
   solve_fn solve = nullptr;         // theta == 1 (reference default)
   solve_fn solve_theta = nullptr;   // any theta
   solve_fn solve_cg = nullptr;      // ConjugateGradient
@@ -72,18 +70,15 @@ struct WaveRow {
   kat_fn kat = nullptr;
   lds_fn lds = nullptr;
 };
-// Every kernel of a row, named by the form's flag bits (WaveBuild).  The free-free forms compile an any-theta build, the
-// column form ConjugateGradient, the anchored forms a scene entry; MORE: W_SPREAD where the form has a tail-spreading
-// build -- the per-edge form always, the column form at <3, 9> only.
-template <int K, int D, Form F, unsigned MORE = (F == PER_EDGE ? W_SPREAD : 0u)>
+// Every kernel of a row, named by the row's word B.  The free-free rows compile an any-theta build, the column row
+// ConjugateGradient, the anchored rows a scene entry; MORE: W_SPREAD where the row has a tail-spreading build -- the
+// per-edge rows always, the column row at <3, 9> only.
+template <int K, int D, unsigned B, unsigned MORE = (B == PER_EDGE ? W_SPREAD : 0u)>
 static WaveRow wave_row() {
-  constexpr unsigned B = F == PER_EDGE ? W_PER_EDGE : F == ANCHORED ? W_ANCH : F == ANCHORED_LINK ? W_ANCH | W_LINKS :
-                         F == ANCHORED_SELF ? W_ANCH | W_SELF : F == ANCHORED_LINK_SELF ? W_ANCH | W_LINKS | W_SELF :
-                         F == ANCHORED_HALF ? W_ANCH | W_HALF : F == ANCHORED_LINK_HALF ? W_ANCH | W_LINKS | W_HALF : 0u;
-  WaveRow r{K, D, F};
+  WaveRow r{K, D, B};
   r.solve = rtr_wave_kernel<K, D, B | W_THETA1>;
   if constexpr ((B & W_ANCH) == 0) r.solve_theta = rtr_wave_kernel<K, D, B>;
-  if constexpr (F == COLUMN) r.solve_cg = rcg_wave_kernel<K, D>;
+  if constexpr (B == COLUMN) r.solve_cg = rcg_wave_kernel<K, D>;
   if constexpr ((MORE & W_SPREAD) != 0) r.solve_spread = rtr_wave_kernel<K, D, B | W_THETA1 | W_SPREAD>;
   if constexpr ((B & W_ANCH) != 0) r.solve_scene = rtr_wave_scene_kernel<K, D, B | W_THETA1>;
   r.kat = kat_wave_kernel<K, D, B>;
@@ -96,19 +91,23 @@ static WaveRow wave_row() {
 // tools/gpu_variants.py.  <3,10> 48 B: -1.3 % against <3,9>; <2,16> 168 B: 5x faster than the
 // workgroup kernels on the planar trees -- both stay)
 static const WaveRow kWaveRows[] = {
-    wave_row<3, 9, COLUMN, W_SPREAD>(), wave_row<3, 9, PER_EDGE>(), wave_row<3, 9, ANCHORED>(), wave_row<3, 9, ANCHORED_LINK>(),
-    wave_row<3, 9, ANCHORED_SELF>(), wave_row<3, 9, ANCHORED_LINK_SELF>(),
-    wave_row<3, 9, ANCHORED_HALF>(), wave_row<3, 9, ANCHORED_LINK_HALF>(),
+    wave_row<3, 9, COLUMN, W_SPREAD>(), wave_row<3, 9, PER_EDGE>(), wave_row<3, 9, W_ANCH>(), wave_row<3, 9, W_ANCH | W_LINKS>(),
+    wave_row<3, 9, W_ANCH | W_SELF>(), wave_row<3, 9, W_ANCH | W_LINKS | W_SELF>(),
+    wave_row<3, 9, W_ANCH | W_HALF>(), wave_row<3, 9, W_ANCH | W_LINKS | W_HALF>(),
     wave_row<3, 10, COLUMN>(), wave_row<3, 10, PER_EDGE>(),
-    wave_row<3, 20, ANCHORED>(),
+    wave_row<3, 20, W_ANCH>(),
     wave_row<2, 6, COLUMN>(), wave_row<2, 16, COLUMN>(), wave_row<2, 31, COLUMN>()};
 
-// the row of (K, form) with the fewest slots that hold `slots` terms per node, or null
-static const WaveRow *find_row(int K, Form form, int slots) {
+// the row of (K, build) with the fewest slots that hold `slots` terms per node, or null
+static const WaveRow *find_row(int K, unsigned build, int slots) {
   const WaveRow *best = nullptr;
   for (const WaveRow &r : kWaveRows)
-    if (r.K == K && r.form == form && r.slots >= slots && (!best || r.slots < best->slots)) best = &r;
+    if (r.K == K && r.build == build && r.slots >= slots && (!best || r.slots < best->slots)) best = &r;
   return best;
+}
+// the row word of a fixed-anchor template's state: what its kernels are the builds of (gik_template_get_info reports it)
+static unsigned anchored_build(const gik_template *t) {
+  return W_ANCH | (t->link_hinges ? W_LINKS : 0u) | (t->self_hinges ? W_SELF : 0u) | (t->n_half > 0 ? W_HALF : 0u);
 }
 
 }  // namespace gik
@@ -279,8 +278,19 @@ static void install_row(gik_template *t, const WaveRow *r) {
   kn.solve_spread = (cg || !theta1) ? nullptr : r->solve_spread;
   kn.solve_scene = r->solve_scene;
   kn.kat = r->kat;
-  kn.occupancy = (const void *)(r->form == PER_EDGE ? (kn.solve_spread ? kn.solve_spread : kn.solve) : (cg ? r->solve_cg : r->solve));
+  kn.occupancy = (const void *)(r->build == PER_EDGE ? (kn.solve_spread ? kn.solve_spread : kn.solve) : (cg ? r->solve_cg : r->solve));
   t->smem_bytes = r->lds(t->T);
+}
+// A 9-slot fixed-anchor template's kernels resolved again, to the row of `build` (an attach entry's: anchored_build with
+// its family's bit), with their LDS bytes and occupancy.  Nothing of the template changes unless the device answers.
+static int reresolve_anchored(gik_template *anch, unsigned build, const std::string &entry) {
+  const WaveRow *row = find_row(3, build, 9);
+  int occ = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)row->solve, WAVE, row->lds(anch->T)) != hipSuccess)
+    return fail(entry + ": device upload failed");
+  install_row(anch, row);
+  anch->f.waves_per_cu = std::max(1, std::min(occ, 32));
+  return 0;
 }
 
 // The kernels this template launches, chosen once from path, solver, theta, anchored and Hessian form; with them
@@ -300,7 +310,7 @@ static int resolve_kernels(gik_template *t, const gik_template_desc *d, const Wa
   // selects; an explicit GIK_HESS_PER_EDGE without such a kernel is refused.
   const WaveRow *pe = find_row(d->k, PER_EDGE, row->slots);
   if (k3 && d->hessian_form != GIK_HESS_COLUMN) {
-    const bool have = row->form == COLUMN && !cg && pe && pe->slots == row->slots && pe->solve && pe->solve_theta;
+    const bool have = row->build == COLUMN && !cg && pe && pe->slots == row->slots && pe->solve && pe->solve_theta;
     if (!have && d->hessian_form == GIK_HESS_PER_EDGE)
       return fail("hessian_form = GIK_HESS_PER_EDGE: wavefront kernel of 3-D free-free graphs, TrustRegions only");
     t->hess_per_edge = have;
@@ -449,7 +459,7 @@ static int create_impl(const gik_template_desc *d, const gik_anchored_desc *ad, 
   // the node-per-lane kernel for 3-D graphs beyond one wavefront, trust-region solver, theta = 1 (force_block_path: 1 = never, 2 = always)
   const bool big = d->N > BLOCK_MAXN;
   const WaveRow *row = nullptr;
-  if (d->N * d->k <= WAVE && d->N <= 32 && !d->force_block_path) row = find_row(d->k, ad ? ANCHORED : COLUMN, maxdeg);
+  if (d->N * d->k <= WAVE && d->N <= 32 && !d->force_block_path) row = find_row(d->k, ad ? W_ANCH : COLUMN, maxdeg);
   t->f.is_block = !row;      // (also: a node busier than any wave variant)
   if (t->f.is_block && ad) return fail("anchored templates need N * k <= 64 free unknowns and at most 20 terms per node");
   const bool npt_wanted = t->f.is_block && d->k == 3 && d->solver == GIK_SOLVER_TRUST_REGIONS && d->theta == 1.0 && !ad &&
@@ -570,7 +580,7 @@ int gik_template_create_anchored(const gik_template_desc *d, const gik_anchored_
   return create_impl(d, ad, out);
 }
 
-// the links of the link clearance; with hinges = 1 the template's kernels are resolved again (the ANCHORED_LINK row)
+// the links of the link clearance; with hinges = 1 the template's kernels are resolved again (the W_LINKS row)
 int gik_anchored_attach_links(gik_template *anch, const gik_link_desc *d) {
   using namespace gik;
   const std::string e("gik_anchored_attach_links");
@@ -606,14 +616,10 @@ int gik_anchored_attach_links(gik_template *anch, const gik_link_desc *d) {
   anch->h_link_rho.assign(d->link_radius, d->link_radius + d->n_link);
   if (d->hinges) {
     // the template's solve and known-answer kernels become the link row's, with their LDS bytes and occupancy
-    const WaveRow *row = find_row(3, ANCHORED_LINK, 9);
     const AnchLinkRec *dr = upload(anch, recs.data(), recs.size(), ok);
-    int occ = 0;
-    if (!ok || hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)row->solve, WAVE, row->lds(anch->T)) != hipSuccess)
-      return fail(e + ": device upload failed");
+    if (!ok) return fail(e + ": device upload failed");
+    if (reresolve_anchored(anch, anchored_build(anch) | W_LINKS, e)) return -1;
     anch->an.link_rec = dr;
-    install_row(anch, row);
-    anch->f.waves_per_cu = std::max(1, std::min(occ, 32));
     anch->link_hinges = true;
   }
   anch->n_link = d->n_link;
@@ -667,15 +673,11 @@ int gik_anchored_attach_self_hinges(gik_template *anch) {
   const std::string why = self_hinge_descs(anch->h_free_full, anch->h_anchor_full, anch->h_link_a, anch->h_link_b, anch->h_link_rho,
                                            anch->h_self_l, anch->h_self_m, descs);
   if (!why.empty()) return fail(e + ": " + why);
-  const WaveRow *row = find_row(3, anch->link_hinges ? ANCHORED_LINK_SELF : ANCHORED_SELF, 9);
   bool ok = true;
   const AnchSelfDesc *dd = upload(anch, descs.data(), descs.size(), ok);
-  int occ = 0;
-  if (!ok || hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)row->solve, WAVE, row->lds(anch->T)) != hipSuccess)
-    return fail(e + ": device upload failed");
+  if (!ok) return fail(e + ": device upload failed");
+  if (reresolve_anchored(anch, anchored_build(anch) | W_SELF, e)) return -1;
   anch->an.self_desc = dd;
-  install_row(anch, row);
-  anch->f.waves_per_cu = std::max(1, std::min(occ, 32));
   anch->self_hinges = true;
   return 0;
 }
@@ -711,19 +713,15 @@ int gik_anchored_attach_halfspaces(gik_template *anch, int n_half, const double 
     return fail(e + ": half-spaces need the 9-slot fixed-anchor kernel; this template runs the " + std::to_string(anch->maxdeg) +
                 "-slot variant, which has none");
   if (anch->self_hinges) return fail(e + ": self hinges are attached; the solve has no build with self hinges and half-spaces");
-  const WaveRow *row = find_row(3, anch->link_hinges ? ANCHORED_LINK_HALF : ANCHORED_HALF, 9);
   bool ok = true;
   double *dh = const_cast<double *>(upload(anch, halfspaces, (size_t)n_half * 4, ok));
   double *dm = const_cast<double *>(upload(anch, mu.data(), mu.size(), ok));
   double *dc = const_cast<double *>(upload(anch, mu_clear.data(), mu_clear.size(), ok));
-  int occ = 0;
-  if (!ok || hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void *)row->solve, WAVE, row->lds(anch->T)) != hipSuccess)
-    return fail(e + ": device upload failed");
+  if (!ok) return fail(e + ": device upload failed");
+  if (reresolve_anchored(anch, anchored_build(anch) | W_HALF, e)) return -1;
   anch->d_half = dh;
   anch->d_half_mu = dm;
   anch->d_half_mu_clear = dc;
-  install_row(anch, row);
-  anch->f.waves_per_cu = std::max(1, std::min(occ, 32));
   anch->n_half = n_half;
   return 0;
 }
@@ -1466,7 +1464,8 @@ int gik_template_get_info(const gik_template *t, gik_template_info *info) {
   info->lds_bytes = (int32_t)t->smem_bytes;
   info->clique_closed_form = t->clique_mode;
   info->hessian_form = (t->hess_per_edge || t->f.is_block) ? GIK_HESS_PER_EDGE : GIK_HESS_COLUMN;
-  info->anchored = t->anchored ? (1 | (t->link_hinges ? 2 : 0) | (t->self_hinges ? 4 : 0) | (t->n_half > 0 ? 8 : 0)) : 0;
+  const unsigned build = t->anchored ? gik::anchored_build(t) : 0u;      // (the ABI's bits are not the W_* bits: mapped one by one)
+  info->anchored = (build & gik::W_ANCH ? 1 : 0) | (build & gik::W_LINKS ? 2 : 0) | (build & gik::W_SELF ? 4 : 0) | (build & gik::W_HALF ? 8 : 0);
   info->has_pipeline = t->has_pipe ? 1 : 0;
   info->prepare_is_block = t->prep.plan.block() ? 1 : 0;
   info->node_per_lane = t->f.is_npt ? t->npt_variant->NW : 0;

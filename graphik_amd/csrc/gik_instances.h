@@ -49,8 +49,8 @@
   X(void rtr_wave_scene_kernel<3, 9, W_THETA1 | W_ANCH>(SolveArgs, SceneArgs))           \
   X(void rtr_wave_scene_kernel<3, 20, W_THETA1 | W_ANCH>(SolveArgs, SceneArgs))          \
   X(void rtr_wave_scene_kernel<3, 9, W_THETA1 | W_ANCH | W_LINKS>(SolveArgs, SceneArgs))
-// ... with self hinges (gik_anchored_attach_self_hinges), without and with link hinges: solve, known answers, scenes.
-// A group of its own beside GIK_ALL_KERNELS (gik_k_anch_self.hip): gik_kernels.hip.h declares it for the host unit.
+// ... with self hinges (gik_anchored_attach_self_hinges), without and with link hinges: solve, known answers, scenes
+// (gik_k_anch_self.hip)
 #define GIK_KERNELS_ANCH_SELF(X)                                                                  \
   X(void rtr_wave_kernel<3, 9, W_THETA1 | W_ANCH | W_SELF>(SolveArgs))                            \
   X(void rtr_wave_kernel<3, 9, W_THETA1 | W_ANCH | W_LINKS | W_SELF>(SolveArgs))                  \
@@ -58,8 +58,8 @@
   X(void kat_wave_kernel<3, 9, W_ANCH | W_LINKS | W_SELF>(KatArgs))                               \
   X(void rtr_wave_scene_kernel<3, 9, W_THETA1 | W_ANCH | W_SELF>(SolveArgs, SceneArgs))           \
   X(void rtr_wave_scene_kernel<3, 9, W_THETA1 | W_ANCH | W_LINKS | W_SELF>(SolveArgs, SceneArgs))
-// ... with half-space obstacles (gik_anchored_attach_halfspaces), without and with link hinges: solve, known answers, scenes.
-// Beside GIK_ALL_KERNELS too (gik_k_anch_half.hip), declared for the host unit by gik_kernels.hip.h.
+// ... with half-space obstacles (gik_anchored_attach_halfspaces), without and with link hinges: solve, known answers, scenes
+// (gik_k_anch_half.hip)
 #define GIK_KERNELS_ANCH_HALF(X)                                                                  \
   X(void rtr_wave_kernel<3, 9, W_THETA1 | W_ANCH | W_HALF>(SolveArgs))                            \
   X(void rtr_wave_kernel<3, 9, W_THETA1 | W_ANCH | W_LINKS | W_HALF>(SolveArgs))                  \
@@ -118,4 +118,5 @@
 
 #define GIK_ALL_KERNELS(X)                                                                                      \
   GIK_KERNELS_WAVE3(X) GIK_KERNELS_WAVE3_STRICT(X) GIK_KERNELS_ANCH(X) GIK_KERNELS_ANCH_LINK(X) GIK_KERNELS_ANCH_SCENE(X) \
+  GIK_KERNELS_ANCH_SELF(X) GIK_KERNELS_ANCH_HALF(X)                                                             \
   GIK_KERNELS_WAVE2(X) GIK_KERNELS_BLOCK(X) GIK_KERNELS_NPT(X) GIK_KERNELS_NPT4(X) GIK_KERNELS_QUAD(X) GIK_KERNELS_PREP(X)

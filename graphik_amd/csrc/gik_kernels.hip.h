@@ -10,12 +10,3 @@
 #include "gik_prep_quad.hip.h"
 #include "gik_recover_seed.hip.h"
 #include "gik_anch_glue.hip.h"
-
-// The groups that stand beside GIK_ALL_KERNELS (gik_instances.h), the fixed-anchor kernels with self hinges and those with
-// half-space obstacles, declared here for the same reason gik_host.hip declares the others: their addresses refer to
-// gik_k_anch_self.hip's and gik_k_anch_half.hip's symbols.
-#include "gik_instances.h"
-namespace gik {
-GIK_KERNELS_ANCH_SELF(GIK_EXTERN_TEMPLATE)
-GIK_KERNELS_ANCH_HALF(GIK_EXTERN_TEMPLATE)
-}

@@ -349,7 +349,7 @@ EXISTING = {
     "rtr_wave_scene_kernel<3,20,W_THETA1|W_ANCH>": ["tests/test_anchored_scenes_gpu.py::test_template_level_bit_identity",
                                                     "tests/test_anchored_scenes_gpu.py::test_a_wave_changes_scene_between_problems"],
     "rtr_wave_scene_kernel<3,9,W_THETA1|W_ANCH|W_LINKS>": ["tests/test_anchored_scenes_gpu.py::test_ur10_three_scenes"],
-    # the self-hinge and half-space groups (GIK_KERNELS_ANCH_SELF, GIK_KERNELS_ANCH_HALF, beside GIK_ALL_KERNELS): the solve
+    # the self-hinge and half-space groups (GIK_KERNELS_ANCH_SELF, GIK_KERNELS_ANCH_HALF): the solve
     # builds against the numpy trust-region twin (HINGE_TWIN_CASES below names the cases), the known-answer builds against
     # numpy, the scene builds bit-identical to their own templates
     "rtr_wave_kernel<3,9,W_THETA1|W_ANCH|W_SELF>": [_HINGE_TWIN],
@@ -407,26 +407,25 @@ def coverage():
     return cov
 
 
-# kernel groups that stand beside GIK_ALL_KERNELS (units of their own, declared for the host unit by gik_kernels.hip.h)
-BESIDE_ALL_KERNELS = ("GIK_KERNELS_ANCH_SELF", "GIK_KERNELS_ANCH_HALF")
-
-
-def compiled_instances(text=None):
-    """The instantiations GIK_ALL_KERNELS expands to (gik_instances.h) and those of the groups beside it
-    (BESIDE_ALL_KERNELS), without blanks: 'rtr_wave_kernel<3,9,W_THETA1>' etc."""
+def macro_body(name, text=None):
+    """The replacement text of `#define <name>(X) ...` in gik_instances.h (or `text`), continuation lines included."""
     if text is None:
         with open(INSTANCES_H) as f:
             text = f.read()
-    groups = {}
-    for m in re.finditer(r"#define\s+(GIK_KERNELS_\w+)\(X\)((?:[^\n]*\\\n)*[^\n]*)", text):
-        groups[m.group(1)] = re.findall(r"X\(\s*void\s+(\w+\s*<[^>]*>)\s*\(", m.group(2))
-    m = re.search(r"#define\s+GIK_ALL_KERNELS\(X\)((?:[^\n]*\\\n)*[^\n]*)", text)
-    assert m, "GIK_ALL_KERNELS not found"
-    used = re.findall(r"(GIK_KERNELS_\w+)\(X\)", m.group(1))
-    assert not set(BESIDE_ALL_KERNELS) & set(used), "a group beside GIK_ALL_KERNELS is now inside it"
-    used += list(BESIDE_ALL_KERNELS)
+    m = re.search(rf"#define\s+{name}\(X\)((?:[^\n]*\\\n)*[^\n]*)", text)
+    assert m, name + " not found"
+    return m.group(1)
+
+
+def group_members(name, text=None):
+    """The instantiations of the group `#define <name>(X)`, in its order and without blanks:
+    'rtr_wave_kernel<3,9,W_THETA1>' etc."""
+    return [re.sub(r"\s+", "", s) for s in re.findall(r"X\(\s*void\s+(\w+\s*<[^>]*>)\s*\(", macro_body(name, text))]
+
+
+def compiled_instances(text=None):
+    """The instantiations GIK_ALL_KERNELS expands to (gik_instances.h): the members of every group it names."""
     out = []
-    for g in used:
-        assert g in groups, g
-        out += [re.sub(r"\s+", "", s) for s in groups[g]]
+    for g in re.findall(r"(GIK_KERNELS_\w+)\(X\)", macro_body("GIK_ALL_KERNELS", text)):
+        out += group_members(g, text)
     return out

@@ -238,19 +238,18 @@ def test_header_bindings_and_kernel_group():
     assert re.search(r"#define\s+GIK_ABI_VERSION\s+12\b", header)
     args = open(os.path.join(REPO, "graphik_amd", "csrc", "gik_args.h")).read()
     assert re.search(r"constexpr int ANCH_HALF_MAX = 8;", args) and _ffi.HALF_MAX == 8
-    text = open(os.path.join(REPO, "graphik_amd", "csrc", "gik_instances.h")).read()
-    m = re.search(r"#define\s+GIK_KERNELS_ANCH_HALF\(X\)((?:[^\n]*\\\n)*[^\n]*)", text)
-    assert m, "GIK_KERNELS_ANCH_HALF not found"
-    group = {re.sub(r"\s+", "", s) for s in re.findall(r"X\(\s*void\s+(\w+\s*<[^>]*>)\s*\(", m.group(1))}
-    assert group == {f"{k}<3,9,{flags}>" for k, flags in (
+    import synth_graphs as sg
+    group = sg.group_members("GIK_KERNELS_ANCH_HALF")
+    assert len(group) == 6 and set(group) == {f"{k}<3,9,{flags}>" for k, flags in (
         ("rtr_wave_kernel", "W_THETA1|W_ANCH|W_HALF"), ("rtr_wave_kernel", "W_THETA1|W_ANCH|W_LINKS|W_HALF"),
         ("kat_wave_kernel", "W_ANCH|W_HALF"), ("kat_wave_kernel", "W_ANCH|W_LINKS|W_HALF"),
         ("rtr_wave_scene_kernel", "W_THETA1|W_ANCH|W_HALF"), ("rtr_wave_scene_kernel", "W_THETA1|W_ANCH|W_LINKS|W_HALF"))}
-    all_k = re.search(r"#define\s+GIK_ALL_KERNELS\(X\)((?:[^\n]*\\\n)*[^\n]*)", text).group(1)
-    assert "GIK_KERNELS_ANCH_HALF" not in all_k
-    host = open(os.path.join(REPO, "graphik_amd", "csrc", "gik_kernels.hip.h")).read()
+    assert "GIK_KERNELS_ANCH_HALF(X)" in sg.macro_body("GIK_ALL_KERNELS")
+    umbrella = open(os.path.join(REPO, "graphik_amd", "csrc", "gik_kernels.hip.h")).read()
+    host = open(os.path.join(REPO, "graphik_amd", "csrc", "gik_host.hip")).read()
     unit = open(os.path.join(REPO, "graphik_amd", "csrc", "gik_k_anch_half.hip")).read()
-    assert "GIK_KERNELS_ANCH_HALF(GIK_EXTERN_TEMPLATE)" in host and "GIK_KERNELS_ANCH_HALF(GIK_INSTANTIATE)" in unit
+    assert "GIK_KERNELS_ANCH_HALF(GIK_EXTERN_TEMPLATE)" not in umbrella and "GIK_KERNELS_ANCH_HALF(GIK_INSTANTIATE)" in unit
+    assert re.findall(r"GIK_\w+\(GIK_EXTERN_TEMPLATE\)", host) == ["GIK_ALL_KERNELS(GIK_EXTERN_TEMPLATE)"]
     assert re.findall(r'#include "([^"]+)"', unit) == ["gik_wave_kernels.hip.h", "gik_instances.h"]
     from graphik_amd import build
     assert build.SOURCES.index("gik_k_anch_half.hip") < build.SOURCES.index("gik_host_anch.hip")

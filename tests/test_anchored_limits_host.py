@@ -364,10 +364,7 @@ def test_the_case_table_covers_the_anchored_kernels():
     cov = sg.coverage()
     assert not any("ANCH" in k or re.search(r"wave_kernel<3,\d+,[^>]*W_ANCH", k) for k in sg.OUT_OF_SCOPE)
     assert all(why for why in sg.OUT_OF_SCOPE.values())
-    with open(sg.INSTANCES_H) as f:
-        text = f.read()
-    m = re.search(r"#define\s+GIK_KERNELS_ANCH\(X\)((?:[^\n]*\\\n)*[^\n]*)", text)
-    group = [re.sub(r"\s+", "", s) for s in re.findall(r"X\(\s*void\s+(\w+\s*<[^>]*>)\s*\(", m.group(1))]
+    group = sg.group_members("GIK_KERNELS_ANCH")
     assert len(group) == 4
     for inst in group:
         by_case = [c for c in cov[inst] if c.startswith("anchored:")]

@@ -296,14 +296,10 @@ def test_the_new_kernel_group_is_what_the_hinge_template_runs(torch_cuda):
     known-answer kernel, both in the coverage table of tests/synth_graphs.py; the hinge
     template of the tests above reports them through gik_template_get_info: 3-D, 9 slots, anchored with link hinges
     (anchored = 3), at the LDS bytes of the link context and four waves per CU."""
-    text = open(os.path.join(REPO, "graphik_amd", "csrc", "gik_instances.h")).read()
-    m = re.search(r"#define\s+GIK_KERNELS_ANCH_LINK\(X\)((?:[^\n]*\\\n)*[^\n]*)", text)
-    assert m, "GIK_KERNELS_ANCH_LINK not found"
-    group = {re.sub(r"\s+", "", s) for s in re.findall(r"X\(\s*void\s+(\w+\s*<[^>]*>)\s*\(", m.group(1))}
-    all_k = re.search(r"#define\s+GIK_ALL_KERNELS\(X\)((?:[^\n]*\\\n)*[^\n]*)", text).group(1)
-    # in the table of tests/synth_graphs.py, and covered there by a test that exists
-    assert "GIK_KERNELS_ANCH_LINK(X)" in all_k
     import synth_graphs as sg
+    group = set(sg.group_members("GIK_KERNELS_ANCH_LINK"))
+    # in the table of tests/synth_graphs.py, and covered there by a test that exists
+    assert "GIK_KERNELS_ANCH_LINK(X)" in sg.macro_body("GIK_ALL_KERNELS")
     cov, compiled = sg.coverage(), sg.compiled_instances()
     assert group <= set(compiled) and all(cov.get(inst) for inst in group)
     robot, graph, on = _table(True)

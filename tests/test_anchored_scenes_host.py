@@ -231,13 +231,15 @@ def test_scene_kernels_sit_in_the_table():
     import synth_graphs as sg
     text = open(INSTANCES_H).read()
     assert ANCH_GROUP in text and ANCH_LINK_GROUP in text          # the anchored groups: exactly these members, in this order
-    m = re.search(r"#define\s+GIK_KERNELS_ANCH_SCENE\(X\)((?:[^\n]*\\\n)*[^\n]*)", text)
-    group = [re.sub(r"\s+", "", s) for s in re.findall(r"X\(\s*void\s+(\w+\s*<[^>]*>)\s*\(", m.group(1))]
-    assert group == SCENE_GROUP
-    # one table: every anchored group is in GIK_ALL_KERNELS, the host unit expands that and no group on its own, and every
-    # scene build is covered by a test that exists
-    all_k = re.search(r"#define\s+GIK_ALL_KERNELS\(X\)((?:[^\n]*\\\n)*[^\n]*)", text).group(1)
-    assert all(g in all_k for g in ("GIK_KERNELS_ANCH(X)", "GIK_KERNELS_ANCH_SCENE(X)", "GIK_KERNELS_ANCH_LINK(X)"))
+    assert sg.group_members("GIK_KERNELS_ANCH_SCENE") == SCENE_GROUP
+    # one table: every anchored group is in GIK_ALL_KERNELS, the host unit expands that and no group on its own -- nor does
+    # any header --, and every scene build is covered by a test that exists
+    all_k = sg.macro_body("GIK_ALL_KERNELS")
+    assert all(g in all_k for g in ("GIK_KERNELS_ANCH(X)", "GIK_KERNELS_ANCH_SCENE(X)", "GIK_KERNELS_ANCH_LINK(X)",
+                                    "GIK_KERNELS_ANCH_SELF(X)", "GIK_KERNELS_ANCH_HALF(X)"))
+    csrc = os.path.join(REPO, "graphik_amd", "csrc")
+    for header in sorted(f for f in os.listdir(csrc) if f.endswith(".h")):
+        assert not re.search(r"GIK_\w+\(GIK_EXTERN_TEMPLATE\)", open(os.path.join(csrc, header)).read()), header
     compiled, cov = sg.compiled_instances(), sg.coverage()
     for inst in SCENE_GROUP:
         assert compiled.count(inst) == 1 and cov.get(inst), inst

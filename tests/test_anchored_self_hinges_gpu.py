@@ -351,20 +351,19 @@ def test_refusals_of_attach_self_hinges(torch_cuda):
 
 
 def test_the_new_kernel_group_is_what_the_self_hinge_templates_run(torch_cuda):
-    """GIK_KERNELS_ANCH_SELF (gik_instances.h) holds six instantiations and is expanded beside GIK_ALL_KERNELS, not inside
-    it; each of the six is what a template of the tests above launches: the solve, known-answer and scene kernels of the
-    form gik_template_get_info reports -- 3-D, 9 slots, anchored = 5 (self hinges) and 7 (with link hinges) -- at the LDS
-    bytes of the self context and four waves per CU."""
-    text = open(os.path.join(REPO, "graphik_amd", "csrc", "gik_instances.h")).read()
-    m = re.search(r"#define\s+GIK_KERNELS_ANCH_SELF\(X\)((?:[^\n]*\\\n)*[^\n]*)", text)
-    assert m, "GIK_KERNELS_ANCH_SELF not found"
-    group = {re.sub(r"\s+", "", s) for s in re.findall(r"X\(\s*void\s+(\w+\s*<[^>]*>)\s*\(", m.group(1))}
+    """GIK_KERNELS_ANCH_SELF (gik_instances.h) holds six instantiations and is a group of GIK_ALL_KERNELS, which the host
+    unit expands once; each of the six is what a template of the tests above launches: the solve, known-answer and scene
+    kernels of the form gik_template_get_info reports -- 3-D, 9 slots, anchored = 5 (self hinges) and 7 (with link
+    hinges) -- at the LDS bytes of the self context and four waves per CU."""
+    import synth_graphs as sg
+    group = set(sg.group_members("GIK_KERNELS_ANCH_SELF"))
     assert len(group) == 6
-    all_k = re.search(r"#define\s+GIK_ALL_KERNELS\(X\)((?:[^\n]*\\\n)*[^\n]*)", text).group(1)
-    assert "GIK_KERNELS_ANCH_SELF" not in all_k
-    host = open(os.path.join(REPO, "graphik_amd", "csrc", "gik_kernels.hip.h")).read()      # (the host unit's umbrella header)
+    assert "GIK_KERNELS_ANCH_SELF(X)" in sg.macro_body("GIK_ALL_KERNELS")
+    umbrella = open(os.path.join(REPO, "graphik_amd", "csrc", "gik_kernels.hip.h")).read()
+    host = open(os.path.join(REPO, "graphik_amd", "csrc", "gik_host.hip")).read()
     unit = open(os.path.join(REPO, "graphik_amd", "csrc", "gik_k_anch_self.hip")).read()
-    assert "GIK_KERNELS_ANCH_SELF(GIK_EXTERN_TEMPLATE)" in host and "GIK_KERNELS_ANCH_SELF(GIK_INSTANTIATE)" in unit
+    assert "GIK_KERNELS_ANCH_SELF(GIK_EXTERN_TEMPLATE)" not in umbrella and "GIK_KERNELS_ANCH_SELF(GIK_INSTANTIATE)" in unit
+    assert re.findall(r"GIK_\w+\(GIK_EXTERN_TEMPLATE\)", host) == ["GIK_ALL_KERNELS(GIK_EXTERN_TEMPLATE)"]
     ran = set()
     for link_hinges in (False, True):
         robot, graph, on = _problem("ur10_table", link_hinges=link_hinges)

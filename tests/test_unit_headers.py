@@ -19,7 +19,7 @@ from conftest import REPO
 
 CSRC = os.path.join(REPO, "graphik_amd", "csrc")
 WAVE_UNITS = ["gik_k_wave3.hip", "gik_k_wave3_strict.hip", "gik_k_wave2.hip", "gik_k_anch.hip", "gik_k_anch_link.hip",
-              "gik_k_anch_scene.hip"]
+              "gik_k_anch_scene.hip", "gik_k_anch_self.hip", "gik_k_anch_half.hip"]
 FAMILY = {      # context and driver headers, then the family's kernels
     "wave": {"gik_wave_strict.hip.h", "gik_wave_kernels.hip.h"},
     "block": {"gik_block.hip.h", "gik_block_kernels.hip.h"},

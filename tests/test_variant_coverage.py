@@ -23,7 +23,7 @@ def test_every_instantiation_has_a_case():
     missing, stale = _gaps()
     assert not missing, f"compiled kernels without a case in tests/synth_graphs.py: {missing}"
     assert not stale, f"coverage entries for kernels gik_instances.h no longer compiles: {stale}"
-    assert len(sg.compiled_instances()) >= 62      # (the parser found the groups: 75 with the two beside GIK_ALL_KERNELS)
+    assert len(sg.compiled_instances()) == 75      # (what GIK_ALL_KERNELS yields: the parser found every group)
 
 
 def test_a_new_instantiation_without_a_case_fails():
@@ -38,7 +38,8 @@ def test_a_new_instantiation_without_a_case_fails():
     assert dropped != text
     missing, stale = _gaps(dropped)
     assert not missing and stale == ["rcg_wave_kernel<2,31>"]
-    # the groups beside GIK_ALL_KERNELS are parsed too: a member more, a member less, a group gone
+    # the self-hinge and half-space groups: a member more, a member less, a group gone (GIK_ALL_KERNELS then names a group
+    # that no longer exists)
     extra = "  X(void rtr_wave_kernel<3, 20, W_THETA1 | W_ANCH | W_HALF>(SolveArgs))  \\\n"
     anchor = "#define GIK_KERNELS_ANCH_HALF(X)                                                                  \\\n"
     assert anchor in text
@@ -52,16 +53,13 @@ def test_a_new_instantiation_without_a_case_fails():
         sg.compiled_instances(text.replace("#define GIK_KERNELS_ANCH_SELF(X)", "#define GIK_KERNELS_ANCH_SELF_GONE(X)"))
 
 
-def test_the_groups_beside_all_kernels_are_in_the_table():
+def test_the_self_and_half_groups_are_in_the_table():
     """GIK_KERNELS_ANCH_SELF and GIK_KERNELS_ANCH_HALF: six instantiations each, every one compiled once and with an entry
     of its own in EXISTING, the solve builds through a case of the numpy twin's table."""
     import test_anchored_hinge_twin_host as th
-    with open(sg.INSTANCES_H) as f:
-        text = f.read()
     compiled = sg.compiled_instances()
-    for group in sg.BESIDE_ALL_KERNELS:
-        m = re.search(rf"#define\s+{group}\(X\)((?:[^\n]*\\\n)*[^\n]*)", text)
-        members = [re.sub(r"\s+", "", s) for s in re.findall(r"X\(\s*void\s+(\w+\s*<[^>]*>)\s*\(", m.group(1))]
+    for group in ("GIK_KERNELS_ANCH_SELF", "GIK_KERNELS_ANCH_HALF"):
+        members = sg.group_members(group)
         assert len(members) == 6
         for inst in members:
             assert compiled.count(inst) == 1 and sg.EXISTING.get(inst), inst
