@@ -104,10 +104,11 @@ size_t gik_retry_ws_bytes(const gik_template *t, int B) {
 
 // The restart loop of gik_ik_batch_retry and the anchored restart entries, after their attempt 0.  The caller fills the three
 // argument structs as the step exports fill them, but for count and attempt number, and its own refusals have ruled out
-// what those exports refuse (NOTEBOOK 31); attempt(count) queues one solve of the compact arrays.  t gives the grid.
-template <typename Attempt>
+// what those exports refuse (NOTEBOOK 31); seed_step(seeds) queues the seeds of the compact slots (retry_seed_launch, or
+// the screened step); attempt(count) queues one solve of the compact arrays.  t gives the grid.
+template <typename SeedStep, typename Attempt>
 static int retry_loop(const char *entry, const gik_template *t, int retries, const gik::RetrySelectArgs &select,
-                      gik::RetrySeedArgs seeds, gik::RetryMergeArgs merge, void *stream, Attempt attempt) {
+                      gik::RetrySeedArgs seeds, gik::RetryMergeArgs merge, void *stream, SeedStep seed_step, Attempt attempt) {
   using gik::fail;
   hipStream_t s = (hipStream_t)stream;
   for (int a = 1, rc = 0; a <= retries; ++a) {
@@ -121,7 +122,7 @@ static int retry_loop(const char *entry, const gik_template *t, int retries, con
     if (count == 0) break;
     seeds.count = merge.count = count;
     seeds.attempt = merge.attempt_no = a;
-    if ((rc = retry_seed_launch(t, seeds, stream)) || (rc = attempt(count)) || (rc = retry_merge_launch(t, merge, stream))) return rc;
+    if ((rc = seed_step(seeds)) || (rc = attempt(count)) || (rc = retry_merge_launch(t, merge, stream))) return rc;
   }
   return 0;
 }
@@ -156,7 +157,8 @@ int gik_ik_batch_retry(const gik_template *t, const double *d_T_goal, const doub
                                0, pose_width(t), t->pc.n_joints, 0};
   const RetryMergeArgs merge = {w.idx, w.Y, w.stats, w.q, w.pos_err, w.rot_err, nullptr,
                                 d_Y, d_stats, d_q, d_pos_err, d_rot_err, nullptr, d_attempt, tol, 0, t->N * t->f.K, t->pc.n_joints, 0};
-  return retry_loop("gik_ik_batch_retry", t, opts->retries, select, seeds, merge, stream, [&](int count) {
+  const auto seed_step = [&](const RetrySeedArgs &a) { return retry_seed_launch(t, a, stream); };
+  return retry_loop("gik_ik_batch_retry", t, opts->retries, select, seeds, merge, stream, seed_step, [&](int count) {
     int rc = gik_seed_batch(t, w.T, w.q_seed, count, w.targets, w.Y, stream);
     if (!rc) rc = gik_solve_batch(t, w.Y, w.targets, count, w.Y, w.stats, nullptr, stream);
     return rc ? rc : gik_recover_batch(t, w.Y, w.T, count, w.q, w.pos_err, w.rot_err, stream);
@@ -671,12 +673,93 @@ size_t gik_anchored_retry_ws_bytes(const gik_template *anch, const gik_template 
   return anch_retry_ws(anch, base, B, nullptr).bytes;      // (without the scene entry's ids)
 }
 
+// ---- screened restart seeds: C candidates per failed goal, the first clear one starts the restart ----
+// the workspace of the screened step over d_ws behind `head` bytes (gik_plan.h), or with a null d_ws its size
+static gik::AnchScreenWs anch_screen_ws(const gik_template *anch, const gik_template *base, int B, int C, size_t head, void *d_ws) {
+  return gik::anch_screen_ws(base->pc.n_joints, pose_width(base), base->T, anch->full_N, B, C, head, d_ws);
+}
+static size_t anch_screen_head(const gik_template *anch, const gik_template *base, int B) {
+  return gik::anch_screen_head(base->pc.n_joints, pose_width(base), base->T, base->N, anch->N, anch->an.n_goal, anch->full_N, B);
+}
+
+// what is wrong with a candidate count or a batch of that many candidates, or nothing
+static std::string candidates_fault(int candidates, int B) {
+  if (candidates < 1 || candidates > gik::RETRY_MAX_CANDIDATES) return "candidates must be within 1 .. 16";
+  if ((size_t)B * (size_t)candidates > (size_t)INT_MAX) return "B * candidates must fit an int";
+  return std::string();
+}
+
+// The screened seed step on checked arguments, a.count > 0: the candidates of every slot, candidate-major; their
+// realization by the robot graph's seed kernel (its targets go unread), as the sweep realizes its samples; their
+// clearance in the call's mode, against the goal's scene where there are scenes (the ids tiled to the candidates);
+// the pick, whose angles go where retry_seed_kernel would have written its one row.
+static int screened_seed_launch(const gik_template *anch, const gik_template *base, const gik::RetrySeedArgs &a, int candidates,
+                                int mode, double clear_tol, const gik_scene_set *scenes, const gik::AnchScreenWs &w,
+                                int32_t *d_pick, double *d_pick_clearance, void *stream) {
+  using namespace gik;
+  const int M = a.count * candidates;
+  const int32_t *goal_ids = scenes ? scenes->d_scene_id : nullptr;
+  const RetryCandidateArgs ca = {a.T_goal, a.idx, a.q_lo, a.q_hi, a.q_center, goal_ids, a.T_out, w.T, w.q, w.ids,
+                                 a.spread, a.seed, a.count, a.pose_w, a.n, a.attempt, candidates};
+  hipLaunchKernelGGL(retry_candidate_kernel, dim3(retry_grid(base, a.count)), dim3(RETRY_WAVE), 0, (hipStream_t)stream, ca);
+  HIP_OK(hipGetLastError());
+  int rc = gik_seed_batch(base, w.T, w.q, M, w.targets, w.Y, stream);
+  if (rc) return rc;
+  gik_scene_set tiled;
+  if (scenes) {
+    tiled = *scenes;
+    if (goal_ids) tiled.d_scene_id = w.ids;
+  }
+  if ((rc = anchored_mode_clearance_launch(anch, w.Y, M, w.cl, mode, stream, scenes ? &tiled : nullptr))) return rc;
+  const RetryPickArgs pa = {w.cl, w.q, a.q_out, d_pick ? d_pick : w.pick, d_pick_clearance, clear_tol, a.count, a.n, candidates};
+  hipLaunchKernelGGL(retry_pick_kernel, dim3(retry_grid(base, a.count)), dim3(RETRY_WAVE), 0, (hipStream_t)stream, pa);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+size_t gik_anchored_retry_seeds_screened_ws_bytes(const gik_template *anch, const gik_template *base, int count, int candidates) {
+  if (!anch || !base || !anchored_pair_fault(anch, base, 0).empty() || count < 0 || !candidates_fault(candidates, count).empty())
+    return 0;
+  return anch_screen_ws(anch, base, count, candidates, 0, nullptr).bytes;
+}
+
+int gik_anchored_retry_seeds_screened(const gik_template *anch, const gik_template *base, const double *d_T_goal,
+                                      const int32_t *d_idx, int count, uint64_t seed, int attempt, const double *d_q_lo,
+                                      const double *d_q_hi, const double *d_q_center, double spread, int candidates,
+                                      int clearance_mode, double clear_tol, const gik_scene_set *scenes, void *d_ws,
+                                      double *d_T_out, double *d_q_out, int32_t *d_pick, double *d_pick_clearance, void *stream) {
+  using namespace gik;
+  const char *entry = "gik_anchored_retry_seeds_screened";
+  const std::string e(entry);
+  if (!anch || !base || count < 0) return fail(e + ": bad argument");
+  if (const std::string why = anchored_pair_fault(anch, base, PAIR_3D | PAIR_SEEDABLE); !why.empty()) return fail(e + ": " + why);
+  if (scenes && scene_refusal(entry, anch, scenes)) return -1;
+  if (clearance_mode_refusal(e, anch, clearance_mode)) return -1;
+  if (attempt < 0 || attempt > 63) return fail(e + ": attempt must be within 0 .. 63");
+  if (!d_q_lo || !d_q_hi) return fail(e + ": null joint limits (d_q_lo / d_q_hi, [n] each, are required)");
+  if (!(spread >= 0.0)) return fail(e + ": spread must be at least 0");
+  if (spread > 0.0 && !d_q_center) return fail(e + ": spread > 0 needs the centre rows d_q_center [B][n]");
+  if (const std::string why = candidates_fault(candidates, count); !why.empty()) return fail(e + ": " + why);
+  if (!(clear_tol > 0.0)) return fail(e + ": clear_tol must be positive");
+  if (refuse_capture(entry, stream)) return -1;
+  if (count == 0) return 0;
+  if (!d_ws) return fail(e + ": null workspace (gik_anchored_retry_seeds_screened_ws_bytes)");
+  if ((uintptr_t)d_ws % 8) return fail(e + ": the workspace must be 8-byte aligned");
+  if (!d_T_goal || !d_idx || !d_T_out || !d_q_out) return fail(e + ": null buffer");
+  const RetrySeedArgs a = {d_T_goal, d_idx, d_q_lo, d_q_hi, d_q_center, d_T_out, d_q_out, spread, seed,
+                           count, pose_width(base), base->pc.n_joints, attempt};
+  return screened_seed_launch(anch, base, a, candidates, clearance_mode, clear_tol, scenes,
+                              anch_screen_ws(anch, base, count, candidates, 0, d_ws), d_pick, d_pick_clearance, stream);
+}
+
 // gik_anchored_ik_batch_retry and, with a scene set, gik_anchored_ik_batch_retry_scenes: the scene goes through attempt 0,
-// every compact batch (its ids gathered into the workspace's last array) and every clearance.
+// every compact batch (its ids gathered into the workspace's last array) and every clearance.  screened:
+// gik_anchored_ik_batch_retry_screened, whose restarts take their seeds from the screened step with `candidates` draws per
+// slot (its arrays lie behind the ids in the workspace); not screened: one seed per slot, `candidates` is not read.
 static int anchored_retry_impl(const char *entry, const gik_template *anch, const gik_template *base, const double *d_T_goal,
                                const double *d_q_init, int B, const gik_anchored_retry_opts *opts, const gik_scene_set *scenes,
                                bool with_scenes, void *d_ws, double *d_Y_full, gik_stats *d_stats, double *d_q, double *d_pos_err,
-                               double *d_rot_err, double *d_clearance, int32_t *d_attempt, void *stream) {
+                               double *d_rot_err, double *d_clearance, int32_t *d_attempt, void *stream, bool screened, int candidates) {
   using namespace gik;
   const std::string e(entry);
   // every refusal comes before anything is queued
@@ -697,10 +780,14 @@ static int anchored_retry_impl(const char *entry, const gik_template *anch, cons
     if (opts->spread > 0.0 && !d_q_init)
       return fail(e + ": spread > 0 needs d_q_init, the centre the seeds are drawn around (a cold batch has none)");
   }
+  if (screened) {
+    if (const std::string why = candidates_fault(candidates, B); !why.empty()) return fail(e + ": " + why);
+    if (!(opts->clear_tol > 0.0)) return fail(e + ": clear_tol must be positive");
+  }
   if (refuse_capture(entry, stream)) return -1;
   if (B == 0) return 0;
   if (!d_clearance || !d_attempt) return fail(e + ": null d_clearance or d_attempt");
-  if (!d_ws) return fail(e + ": null workspace (gik_anchored_retry_ws_bytes)");
+  if (!d_ws) return fail(e + (screened ? ": null workspace (gik_anchored_ik_batch_retry_screened_ws_bytes)" : ": null workspace (gik_anchored_retry_ws_bytes)"));
   if ((uintptr_t)d_ws % 8) return fail(e + ": the workspace must be 8-byte aligned");
   if (!d_T_goal || !d_Y_full || !d_stats || !d_q || !d_pos_err || !d_rot_err) return fail(e + ": null buffer");
   hipStream_t s = (hipStream_t)stream;
@@ -726,7 +813,12 @@ static int anchored_retry_impl(const char *entry, const gik_template *anch, cons
                                local ? opts->spread : 0.0, opts->seed, 0, pose_width(base), base->pc.n_joints, 0};
   const RetryMergeArgs merge = {w.idx, w.Y, w.stats, w.q, w.pos_err, w.rot_err, w.clearance,
                                 d_Y_full, d_stats, d_q, d_pos_err, d_rot_err, d_clearance, d_attempt, tol, 0, anch->full_N * 3, base->pc.n_joints, 0};
-  return retry_loop(entry, base, opts->retries, select, seeds, merge, stream, [&](int count) {
+  const AnchScreenWs sw = screened ? anch_screen_ws(anch, base, B, candidates, anch_screen_head(anch, base, B), d_ws) : AnchScreenWs();
+  const auto seed_step = [&](const RetrySeedArgs &a) {
+    return screened ? screened_seed_launch(anch, base, a, candidates, mode, opts->clear_tol, scenes, sw, nullptr, nullptr, stream)
+                    : retry_seed_launch(base, a, stream);
+  };
+  return retry_loop(entry, base, opts->retries, select, seeds, merge, stream, seed_step, [&](int count) {
     if (scenes && scenes->d_scene_id) {
       hipLaunchKernelGGL(scene_gather_kernel, dim3((count + ANCH_SCATTER_NT - 1) / ANCH_SCATTER_NT), dim3(ANCH_SCATTER_NT), 0, s,
                          scenes->d_scene_id, w.idx, count, w.ids);
@@ -742,7 +834,7 @@ int gik_anchored_ik_batch_retry(const gik_template *anch, const gik_template *ba
                                 double *d_Y_full, gik_stats *d_stats, double *d_q, double *d_pos_err, double *d_rot_err,
                                 double *d_clearance, int32_t *d_attempt, void *stream) {
   return anchored_retry_impl("gik_anchored_ik_batch_retry", anch, base, d_T_goal, d_q_init, B, opts, nullptr, false, d_ws, d_Y_full,
-                             d_stats, d_q, d_pos_err, d_rot_err, d_clearance, d_attempt, stream);
+                             d_stats, d_q, d_pos_err, d_rot_err, d_clearance, d_attempt, stream, false, 1);
 }
 
 int gik_anchored_ik_batch_retry_scenes(const gik_template *anch, const gik_template *base, const double *d_T_goal,
@@ -750,7 +842,21 @@ int gik_anchored_ik_batch_retry_scenes(const gik_template *anch, const gik_templ
                                        const gik_scene_set *scenes, void *d_ws, double *d_Y_full, gik_stats *d_stats, double *d_q,
                                        double *d_pos_err, double *d_rot_err, double *d_clearance, int32_t *d_attempt, void *stream) {
   return anchored_retry_impl("gik_anchored_ik_batch_retry_scenes", anch, base, d_T_goal, d_q_init, B, opts, scenes, true, d_ws,
-                             d_Y_full, d_stats, d_q, d_pos_err, d_rot_err, d_clearance, d_attempt, stream);
+                             d_Y_full, d_stats, d_q, d_pos_err, d_rot_err, d_clearance, d_attempt, stream, false, 1);
+}
+
+size_t gik_anchored_ik_batch_retry_screened_ws_bytes(const gik_template *anch, const gik_template *base, int B, int candidates) {
+  if (!anch || !base || !anchored_pair_fault(anch, base, 0).empty() || B < 0 || !candidates_fault(candidates, B).empty()) return 0;
+  return anch_screen_ws(anch, base, B, candidates, anch_screen_head(anch, base, B), nullptr).bytes;
+}
+
+int gik_anchored_ik_batch_retry_screened(const gik_template *anch, const gik_template *base, const double *d_T_goal,
+                                         const double *d_q_init, int B, const gik_anchored_retry_opts *opts, int candidates,
+                                         const gik_scene_set *scenes, void *d_ws, double *d_Y_full, gik_stats *d_stats,
+                                         double *d_q, double *d_pos_err, double *d_rot_err, double *d_clearance,
+                                         int32_t *d_attempt, void *stream) {
+  return anchored_retry_impl("gik_anchored_ik_batch_retry_screened", anch, base, d_T_goal, d_q_init, B, opts, scenes, scenes != nullptr,
+                             d_ws, d_Y_full, d_stats, d_q, d_pos_err, d_rot_err, d_clearance, d_attempt, stream, true, candidates);
 }
 
 double gik_anchored_last_solve_ms(const gik_template *anch) {

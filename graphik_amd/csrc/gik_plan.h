@@ -415,4 +415,35 @@ inline AnchRetryWs anch_retry_ws(int n_joints, int pose_w, int base_T, int base_
   return w;
 }
 
+// The workspace of the screened restart seeds (gik_anchored_retry_seeds_screened: gik_anchored_retry_seeds_screened_ws_bytes = bytes),
+// every array sized for M = B C candidates, candidate-major [C][B]:
+//   candidate angles [M][n] | poses for the seed kernel [M][pose_w] | its targets [M][T_base] (not read) |
+//   point matrices [M][full_N*3] | clearances [M] | tiled scene ids [M] int32 | picks [B] int32
+// In gik_anchored_ik_batch_retry_screened it lies behind the anchored restart workspace and its ids, at `head` bytes:
+// head = 0 for the stand-alone step; anch_screen_head(...) for the loop, so that the arrays in front keep their places.
+struct AnchScreenWs {
+  double *q, *T, *targets, *Y, *cl;
+  int32_t *ids, *pick;
+  size_t bytes;      // head included
+};
+inline AnchScreenWs anch_screen_ws(int n_joints, int pose_w, int base_T, int full_N, int B, int C, size_t head, void *ws) {
+  const size_t M = (size_t)B * (size_t)C;
+  WsCarve c = {reinterpret_cast<uintptr_t>(ws), head};
+  AnchScreenWs w;
+  w.q = c.take<double>(M * (size_t)n_joints);
+  w.T = c.take<double>(M * (size_t)pose_w);
+  w.targets = c.take<double>(M * (size_t)base_T);
+  w.Y = c.take<double>(M * (size_t)full_N * 3);
+  w.cl = c.take<double>(M);
+  w.ids = c.take<int32_t>(M);
+  w.pick = c.take<int32_t>((size_t)B);
+  w.bytes = c.off;
+  return w;
+}
+// where the screen arrays begin in the workspace of gik_anchored_ik_batch_retry_screened: behind AnchRetryWs and its ids
+inline size_t anch_screen_head(int n_joints, int pose_w, int base_T, int base_N, int free_N, int n_goal, int full_N, int B) {
+  const AnchRetryWs w = anch_retry_ws(n_joints, pose_w, base_T, base_N, free_N, n_goal, full_N, B, nullptr);
+  return reinterpret_cast<uintptr_t>(w.ids) + ((size_t)B * sizeof(int32_t) + 7) / 8 * 8;
+}
+
 }  // namespace gik

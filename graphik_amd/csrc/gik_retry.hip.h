@@ -11,6 +11,13 @@
 //   retry_merge_kernel  : one wavefront per compact slot: the retry's answer -- point row, stats, q, both errors and,
 //                         where there is one, the clearance -- replaces the goal's incumbent if and only if it is
 //                         better; rows that are not replaced are not written.
+//   retry_candidate_kernel : retry_seed_kernel's loop over C candidates per slot (opt-in screening of the anchored
+//                         restarts): candidate c of (seed, goal, attempt) is the seed formula under
+//                         retry_candidate_seed(seed, c), so candidate 0 is retry_seed_kernel's row, bit for bit.  The
+//                         candidates are laid out candidate-major, [C][count], with a pose row each for the robot
+//                         graph's seed kernel and, with scenes, the goal's scene id.
+//   retry_pick_kernel   : one wavefront per compact slot: retry_pick over the slot's C clearances, the chosen angles
+//                         into the compact seed array.
 // The anchored solve adds the answer's clearance to the rule (an answer that sits on its goal with a joint point -- or,
 // where the caller hands in the link clearance, any part of a link -- inside a sphere has failed).  The plain solve has
 // no clearance: its kernels get null clearance pointers, which read as +inf, and +inf drops out of the rule.
@@ -58,6 +65,29 @@ __host__ __device__ inline bool retry_better(int stop_r, double pos_r, double ro
   const bool ok_r = !retry_failed(stop_r, pos_r, rot_r, clear_r, t);
   const bool ok_i = !retry_failed(stop_i, pos_i, rot_i, clear_i, t);
   return (ok_r && !ok_i) || (ok_r == ok_i && retry_score(pos_r, rot_r, clear_r, t) < retry_score(pos_i, rot_i, clear_i, t));
+}
+
+// ---- candidate screening: C seeds per failed goal, the restart starts from the first clear one ----
+constexpr int RETRY_MAX_CANDIDATES = GIK_RETRY_MAX_CANDIDATES;
+
+// the generator seed of candidate c: candidate 0 is the call's own seed (mod 2^64, as the unsigned product wraps)
+__host__ __device__ inline uint64_t retry_candidate_seed(uint64_t seed, int c) {
+  return seed + (uint64_t)c * 0xD1342543DE82EF95ull;
+}
+
+// Which of C candidates a restart starts from; cl[c * stride] is the clearance of candidate c's realization.  The first
+// in candidate order with clearance >= -clear_tol -- what retry_failed passes; +inf qualifies, so a problem with nothing
+// to measure picks candidate 0.  None: the largest clearance, the lowest c on a tie; a NaN never wins.  All NaN: 0.
+__host__ __device__ inline int retry_pick(const double *cl, int C, size_t stride, double clear_tol) {
+  int best = 0;
+  bool none = true;
+  double best_v = 0.0;
+  for (int c = 0; c < C; ++c) {
+    const double v = cl[(size_t)c * stride];
+    if (v >= -clear_tol) return c;
+    if (v == v && (none || v > best_v)) best = c, best_v = v, none = false;
+  }
+  return best;
 }
 
 // one seed angle.  u = retry_uniform(seed, goal, attempt, joint).  spread == 0: lo + u (hi - lo), one rounded product and
@@ -120,6 +150,31 @@ struct RetryMergeArgs {
   int count, row, n, attempt_no;
 };
 
+struct RetryCandidateArgs {
+  const double *T_goal;     // [B][pose_w]
+  const int *idx;           // [count]
+  const double *q_lo, *q_hi;   // [n]
+  const double *q_center;   // [B][n], indexed by goal; read only if spread > 0
+  const int *scene_id;      // [B] scene of each goal, or null
+  double *T_out;            // [count][pose_w]: the compact pose rows, as retry_seed_kernel writes them
+  double *T_c;              // [C][count][pose_w]: the same row per candidate, the seed kernel's goal argument
+  double *q_c;              // [C][count][n]
+  int *ids_c;               // [C][count]: scene_id[goal] per candidate; written only where scene_id is given
+  double spread;
+  uint64_t seed;
+  int count, pose_w, n, attempt, candidates;
+};
+
+struct RetryPickArgs {
+  const double *cl;         // [C][count] clearance of every candidate
+  const double *q_c;        // [C][count][n]
+  double *q_out;            // [count][n]: the picked candidate's angles
+  int *pick;                // [count], or null
+  double *pick_clearance;   // [count], or null
+  double clear_tol;
+  int count, n, candidates;
+};
+
 // splitmix64 finaliser over the counter of (goal, attempt, joint): 53 uniform bits in [0, 1)
 __host__ __device__ inline double retry_uniform(uint64_t seed, uint64_t goal, int attempt, int joint) {
   const uint64_t c = (goal * 64u + (uint64_t)attempt) * 128u + (uint64_t)joint + 1u;
@@ -166,6 +221,52 @@ __global__ void __launch_bounds__(RETRY_WAVE) retry_seed_kernel(RetrySeedArgs a)
       const double u = retry_uniform(a.seed, (uint64_t)g, a.attempt, j);
       const double c = local ? a.q_center[(size_t)g * a.n + j] : 0.0;
       a.q_out[(size_t)r * a.n + j] = retry_seed_value(u, a.q_lo[j], a.q_hi[j], c, a.spread);
+    }
+  }
+}
+#endif
+
+__global__ void __launch_bounds__(RETRY_WAVE) retry_candidate_kernel(RetryCandidateArgs a)
+#ifndef GIK_DEFINE_RETRY_KERNELS
+    ;
+#else
+{
+  const int lane = threadIdx.x;
+  const bool local = a.spread > 0.0;
+  for (int r = blockIdx.x; r < a.count; r += gridDim.x) {
+    const int g = a.idx[r];
+    const double *src = a.T_goal + (size_t)g * a.pose_w;
+    double *dst = a.T_out + (size_t)r * a.pose_w;
+    for (int e = lane; e < a.pose_w; e += RETRY_WAVE) dst[e] = src[e];
+    for (int c = 0; c < a.candidates; ++c) {
+      const size_t m = (size_t)c * a.count + r;
+      const uint64_t seed_c = retry_candidate_seed(a.seed, c);
+      for (int e = lane; e < a.pose_w; e += RETRY_WAVE) a.T_c[m * a.pose_w + e] = src[e];
+      for (int j = lane; j < a.n; j += RETRY_WAVE) {
+        const double u = retry_uniform(seed_c, (uint64_t)g, a.attempt, j);
+        const double ctr = local ? a.q_center[(size_t)g * a.n + j] : 0.0;
+        a.q_c[m * a.n + j] = retry_seed_value(u, a.q_lo[j], a.q_hi[j], ctr, a.spread);
+      }
+      if (a.scene_id && lane == 0) a.ids_c[m] = a.scene_id[g];
+    }
+  }
+}
+#endif
+
+__global__ void __launch_bounds__(RETRY_WAVE) retry_pick_kernel(RetryPickArgs a)
+#ifndef GIK_DEFINE_RETRY_KERNELS
+    ;
+#else
+{
+  const int lane = threadIdx.x;
+  for (int r = blockIdx.x; r < a.count; r += gridDim.x) {
+    // every lane takes the same pick from the same loads
+    const int c = retry_pick(a.cl + r, a.candidates, (size_t)a.count, a.clear_tol);
+    const size_t m = (size_t)c * a.count + r;
+    for (int j = lane; j < a.n; j += RETRY_WAVE) a.q_out[(size_t)r * a.n + j] = a.q_c[m * a.n + j];
+    if (lane == 0) {
+      if (a.pick) a.pick[r] = c;
+      if (a.pick_clearance) a.pick_clearance[r] = a.cl[m];
     }
   }
 }

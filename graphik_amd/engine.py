@@ -115,6 +115,21 @@ def check_retry_args(retries, pos_tol, rot_tol, q_limits, n, clear_tol=None, ret
     return int(retries), lo, hi
 
 
+RETRY_MAX_CANDIDATES = 16                        # GIK_RETRY_MAX_CANDIDATES (include/graphik_amd.h)
+RETRY_CANDIDATE_STEP = 0xD1342543DE82EF95        # candidate c draws under the seed (seed + c * this) mod 2^64
+
+
+def check_retry_candidates(retry_candidates, retries=None):
+    """retry_candidates of an anchored solve, checked on the host before any device call: an int within 1 .. 16, and
+    above 1 only with retries > 0 (retries=None: the stand-alone step, which has no retries).  ValueError otherwise."""
+    if isinstance(retry_candidates, (bool, np.bool_)) or not isinstance(retry_candidates, (int, np.integer)) or \
+            not 1 <= int(retry_candidates) <= RETRY_MAX_CANDIDATES:
+        raise ValueError(f"retry_candidates must be an integer within 1 .. {RETRY_MAX_CANDIDATES}, got {retry_candidates!r}")
+    if retries is not None and int(retry_candidates) > 1 and not retries:
+        raise ValueError("retry_candidates > 1 needs retries > 0: the candidates are drawn for the restarts")
+    return int(retry_candidates)
+
+
 def _retry_opts(retries, retry_seed, pos_tol, rot_tol, q_lo, q_hi, mode=None, clear_tol=None, retry_spread=0.0):
     """Checked restart arguments -> the options record of the restart entries: gik_retry_opts (Template.ik), or with
     `mode` (the clearance mode, from check_clearance_mode) and clear_tol gik_anchored_retry_opts (Template.anchored_ik).
@@ -651,6 +666,57 @@ class Template:
         nbytes = int(self.lib.gik_anchored_retry_ws_bytes(self._h, base._h, B))
         return (nbytes + 7) // 8 * 8 + 4 * B if scenes else nbytes
 
+    def anchored_retry_screened_ws_bytes(self, base, B, candidates):
+        """Bytes of the restart workspace ("retry_ws") of one anchored_ik call of B goals with retry_candidates > 1
+        (gik_anchored_ik_batch_retry_screened_ws_bytes), with or without scenes."""
+        return int(self.lib.gik_anchored_ik_batch_retry_screened_ws_bytes(self._h, base._h, B, candidates))
+
+    def anchored_retry_seeds_screened(self, base, T_goal, idx, retry_seed, attempt, candidates, q_limits, center=None, spread=0.0,
+                                      clearance_mode="nodes", clear_tol=1e-4, scenes=None, scene_id=None):
+        """The screened seed step of the anchored restarts alone (gik_anchored_retry_seeds_screened): for compact slot r,
+        goal g = idx[r] of the goal poses T_goal [B, 4, 4], `candidates` seeds of (retry_seed, g, attempt) are drawn
+        inside q_limits = (q_lo [n], q_hi [n]) -- around center [B, n] (by goal) with spread > 0 --, realized and measured
+        in clearance_mode, against scene scene_id[g] ([B], by goal) where scenes is given, and the first clear one is
+        picked (AnchoredProblem.screened_seeds_host is the numpy mirror).  Returns device tensors: "q" [count, n] the
+        picked angles, "T" [count, 4, 4] the pose rows, "pick" [count] int32 and "clearance" [count]."""
+        assert self.anchored and base.has_pipeline
+        mode = check_clearance_mode(clearance_mode, getattr(self, "n_link", None) is not None,
+                                    getattr(self, "n_self", None) is not None)
+        candidates = check_retry_candidates(candidates)
+        if not clear_tol > 0:
+            raise ValueError("clear_tol must be positive")
+        if not spread >= 0:
+            raise ValueError(f"spread must be at least 0 (radians), got {spread!r}")
+        if spread > 0 and center is None:
+            raise ValueError("spread > 0 needs the centre rows")
+        T, B = base._poses(T_goal)
+        n = base.n_joints
+        if not isinstance(idx, torch.Tensor):
+            idx = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int32))
+        idx = idx.to(device=self.device, dtype=torch.int32).contiguous()
+        assert idx.dim() == 1
+        count = idx.numel()
+        lo, hi = (_dev(np.ascontiguousarray(a, dtype=np.float64), self.device) for a in q_limits)
+        assert lo.numel() == n and hi.numel() == n
+        ctr = None
+        if center is not None:      # (a NaN centre row is allowed: it gives a NaN seed, as the device entry says)
+            ctr = _dev(np.ascontiguousarray(center, dtype=np.float64) if not isinstance(center, torch.Tensor) else center,
+                       self.device).contiguous()
+            assert tuple(ctr.shape) == (B, n), (tuple(ctr.shape), (B, n))
+        sc, ids = self._scene_desc(scenes, scene_id, B)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        q = torch.empty(count, n, **f64)
+        T_out = torch.empty(count, T.numel() // max(B, 1), **f64)
+        pick = torch.empty(count, dtype=torch.int32, device=self.device)
+        cl = torch.empty(count, **f64)
+        ws = workspace(int(self.lib.gik_anchored_retry_seeds_screened_ws_bytes(self._h, base._h, count, candidates)), self.device)
+        self._call("gik_anchored_retry_seeds_screened", self._h, base._h, T.data_ptr(), idx.data_ptr(), count,
+                   int(retry_seed) & (2 ** 64 - 1), int(attempt), lo.data_ptr(), hi.data_ptr(),
+                   None if ctr is None else ctr.data_ptr(), float(spread), candidates, mode, float(clear_tol),
+                   None if sc is None else C.byref(sc), ws.data_ptr(), T_out.data_ptr(), q.data_ptr(), pick.data_ptr(),
+                   cl.data_ptr(), self._stream())
+        return {"q": q, "T": T_out.reshape(count, 4, 4), "pick": pick, "clearance": cl, "_ws": ws, "_scene_id": ids}
+
     def alloc_anchored_buffers(self, base, B, clearance=False, ws=True):
         """The buffers of one anchored_ik call of B goals (its `out`): the scratch "ws" (ws=False leaves it out: a call
         with retries > 0 keeps that scratch in its restart workspace), the full point matrix "Y" [B, full_N*3], "stats",
@@ -854,7 +920,7 @@ class Template:
 
     def anchored_ik(self, base, T_goal, q_init=None, out=None, clearance=False, retries=0, retry_seed=0, pos_tol=0.01,
                     rot_tol=0.01, clear_tol=1e-4, retry_spread=0.0, q_limits=None, clearance_mode="nodes", scenes=None,
-                    scene_id=None, scene_id_checked=False):
+                    scene_id=None, scene_id_checked=False, retry_candidates=1):
         """Whole pipeline through the fixed-anchor solve: `base` is the robot graph's Template (no
         obstacles) with its pipeline attached.  Without q_init the start point is the robot graph's bound
         smoothing + MDS one fitted to the anchors (gik_anchored_ik_batch); with q_init (seed joint angles
@@ -881,8 +947,13 @@ class Template:
         scenes (a SceneSet) with scene_id ([B] ints; optional with one scene): goal b is solved among the spheres of
         scene scene_id[b] instead of the template's own, and its clearance is measured against them
         (gik_anchored_ik_batch_scenes, gik_anchored_ik_batch_retry_scenes); everything else combines with it unchanged.
-        scene_id_checked: scene_id is a row of an id array SceneSet.ids() has already checked (solve_trajectory)."""
+        scene_id_checked: scene_id is a row of an id array SceneSet.ids() has already checked (solve_trajectory).
+
+        retry_candidates (1 .. 16; above 1 needs retries > 0): every restart draws that many candidate seeds per failed
+        goal, measures their realizations in clearance_mode and starts from the first one that is clear
+        (gik_anchored_ik_batch_retry_screened, with or without scenes).  1: the entries above, one blind seed."""
         assert self.anchored and base.has_pipeline
+        retry_candidates = check_retry_candidates(retry_candidates, retries)
         mode = check_clearance_mode(clearance_mode, getattr(self, "n_link", None) is not None,
                                     getattr(self, "n_self", None) is not None)
         restart = restart_like(retries, clearance_mode, clearance, scenes)
@@ -904,10 +975,15 @@ class Template:
         answer = [out[key].data_ptr() for key in ("Y", "stats", "q", "pos_err", "rot_err")]
         after = None      # the clearance export to launch behind the solve, where the entry does not measure it itself
         if restart:      # retries = 0: attempt 0 alone -- the call, the link clearance, the self clearance merged into it
-            nbytes = self.anchored_retry_ws_bytes(base, B, scenes=sc is not None)
+            screened = retry_candidates > 1
+            nbytes = self.anchored_retry_screened_ws_bytes(base, B, retry_candidates) if screened else \
+                self.anchored_retry_ws_bytes(base, B, scenes=sc is not None)
             attempt, ws, q_lo, q_hi = self._retry_buffers(out, B, nbytes, lo, hi, limits=bool(retries))
             opts = _retry_opts(retries, retry_seed, pos_tol, rot_tol, q_lo, q_hi, mode, clear_tol, retry_spread)
-            name = "gik_anchored_ik_batch_retry" if sc is None else "gik_anchored_ik_batch_retry_scenes"
+            if screened:      # (one entry with a nullable scene set)
+                name, scene = "gik_anchored_ik_batch_retry_screened", (retry_candidates, None if sc is None else C.byref(sc))
+            else:
+                name = "gik_anchored_ik_batch_retry" if sc is None else "gik_anchored_ik_batch_retry_scenes"
             args = (seed_ptr, B, C.byref(opts), *scene, ws.data_ptr(), *answer, cl_ptr, attempt.data_ptr())
             extras = {"clearance": cl, "attempt" if retries else "_attempt": attempt, "_retry_ws": ws}
         else:

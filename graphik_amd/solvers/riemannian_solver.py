@@ -16,7 +16,8 @@ import time
 import numpy as np
 import torch
 
-from ..engine import (Template, _alloc_stats, _decode_stats, build_terms, check_clearance_mode, check_retry_args, restart_like,
+from ..engine import (RETRY_CANDIDATE_STEP, Template, _alloc_stats, _decode_stats, build_terms, check_clearance_mode,
+                      check_retry_args, check_retry_candidates, restart_like,
                       workspace)
 from ..utils import dgp
 from ..utils.constants import POS
@@ -963,7 +964,8 @@ class AnchoredProblem:
         return SceneSet(scenes, self.template.device)
 
     def solve(self, T_goals, q_init=None, clearance=False, retries=0, retry_seed=0, pos_tol=0.01, rot_tol=0.01,
-              clear_tol=1e-4, retry_spread=0.0, q_limits=None, clearance_mode="nodes", scenes=None, scene_id=None):
+              clear_tol=1e-4, retry_spread=0.0, q_limits=None, clearance_mode="nodes", scenes=None, scene_id=None,
+              retry_candidates=1):
         """Goal poses -> dict of device tensors (x [B, N_robot, 3], q, pos_err, rot_err, stats).
 
         q_init (warm start): joint angles [B,n] or [n]; the solve then starts from the realization of
@@ -992,25 +994,89 @@ class AnchoredProblem:
         scenes (scene_set(...)) with scene_id ([B] ints within [0, S), numpy or a device tensor; optional with one
         scene): goal b is solved among the spheres of scene scene_id[b] instead of the problem's own -- one launch over
         the whole batch, whatever the mix -- and "clearance" is measured against them.  Every other keyword combines with
-        it.  Goal b's answer is, bit for bit, that of an AnchoredProblem built with scene scene_id[b]'s spheres."""
+        it.  Goal b's answer is, bit for bit, that of an AnchoredProblem built with scene scene_id[b]'s spheres.
+
+        retry_candidates (an int within 1 .. 16; above 1 needs retries > 0): a restart draws that many candidate seeds per
+        failed goal instead of one, measures the robot as each candidate places it with the clearance the rule reads
+        (clearance_mode, half-spaces, the goal's scene) and starts from the first that is clear -- or, where none is, from
+        the one with the largest clearance.  screened_seeds_host is the numpy mirror of the choice; a goal with
+        "attempt" = a > 0 holds what solve(T[g:g+1], q_init=that pick) returns.  1 (the default): one blind seed, the
+        call as it was."""
         T = np.asarray(T_goals, dtype=float)
         check_clearance_mode(clearance_mode, len(self.link_names) > 0, self.self_pairs is not None)
-        retry = self._retry_args(retries, retry_seed, pos_tol, rot_tol, clear_tol, retry_spread, q_limits, q_init is not None)
+        retry = self._retry_args(retries, retry_seed, pos_tol, rot_tol, clear_tol, retry_spread, q_limits, q_init is not None,
+                                 retry_candidates)
         if q_init is not None:
             q_init = _seed_angles(q_init, T.shape[0], self.robot.n)
         return self.template.anchored_ik(self.base.template, T, q_init=q_init, clearance=clearance or q_init is not None,
                                          clearance_mode=clearance_mode, scenes=scenes, scene_id=scene_id, **retry)
 
-    def _retry_args(self, retries, retry_seed, pos_tol, rot_tol, clear_tol, retry_spread, q_limits, has_center=True):
+    def _retry_args(self, retries, retry_seed, pos_tol, rot_tol, clear_tol, retry_spread, q_limits, has_center=True,
+                    retry_candidates=1):
         """The restart arguments of solve / solve_trajectory, checked here before any device call, as the keywords
-        Template.anchored_ik takes ({} with retries == 0); q_limits defaults to the robot's limits_arrays()."""
+        Template.anchored_ik takes ({} with retries == 0); q_limits defaults to the robot's limits_arrays().
+        retry_candidates is among them only above 1."""
+        retry_candidates = check_retry_candidates(retry_candidates, retries)
         q_limits = self.robot.limits_arrays() if retries and q_limits is None else q_limits
-        return _retry_kwargs(retries, retry_seed, pos_tol, rot_tol, q_limits, self.robot.n, has_center, clear_tol=clear_tol,
-                             retry_spread=retry_spread)
+        kw = _retry_kwargs(retries, retry_seed, pos_tol, rot_tol, q_limits, self.robot.n, has_center, clear_tol=clear_tol,
+                           retry_spread=retry_spread)
+        if retry_candidates > 1:
+            kw["retry_candidates"] = retry_candidates
+        return kw
+
+    def candidate_clearance_host(self, q, clearance_mode="nodes", obstacles=None):
+        """Joint angles [M, n] -> [M]: the clearance a screened restart measures a candidate seed with -- that of the
+        robot graph's realization of q (BatchProblem.seed_points: every row where the configuration puts it, the end
+        effector included) in clearance_mode, the half-spaces folded in: the minimum of the existing mirrors, NaN if any
+        part is NaN.  obstacles: [m, 4] to measure against instead of the problem's own (a scene)."""
+        check_clearance_mode(clearance_mode, len(self.link_names) > 0, self.self_pairs is not None)
+        Y = self.base.seed_points(np.asarray(q, dtype=np.float64))
+        with np.errstate(invalid="ignore"):
+            if clearance_mode == "nodes":
+                none = len(self.obstacles if obstacles is None else np.reshape(obstacles, (-1, 4))) == 0
+                parts = [np.full(len(Y), np.inf) if none else self.clearance(Y, obstacles=obstacles)]
+            else:
+                parts = [self.link_clearance(Y, obstacles=obstacles)]
+                if clearance_mode == "links+self":
+                    parts.append(self.self_clearance(Y))
+            if self.halfspaces is not None:
+                parts.append(self.halfspace_clearance(Y, links=clearance_mode != "nodes"))
+        return _nan_min(np.stack(parts, axis=0), axis=0)
+
+    def screened_seeds_host(self, seed, goals, attempt, candidates, q_lo, q_hi, center=None, spread=0.0, clearance_mode="nodes",
+                            clear_tol=1e-4, obstacles=None):
+        """The numpy mirror of the screened seed step (gik_anchored_retry_seeds_screened): for every goal index in `goals`,
+        `candidates` seeds -- candidate c is retry_seeds_host((seed + c * 0xD1342543DE82EF95) mod 2^64, goals, attempt,
+        ...), so candidate 0 is the unscreened seed --, each measured by candidate_clearance_host, and retry_pick_host's
+        choice among them.  center [len(goals), n]: as retry_seeds_host.  obstacles: None -- the problem's own -- or
+        [m, 4], one scene for every goal, or a sequence of one [m_g, 4] per goal in `goals`.
+        Returns (q [G, n] the picked angles, pick [G] int, clearance [G] of the pick); the whole table is left in
+        self.last_screen = (q_c [C, G, n], clearance_c [C, G])."""
+        C = check_retry_candidates(candidates)
+        if not clear_tol > 0:
+            raise ValueError("clear_tol must be positive")
+        goals = np.asarray(goals, dtype=np.int64).reshape(-1)
+        G = len(goals)
+        q_c = np.stack([retry_seeds_host((int(seed) + c * RETRY_CANDIDATE_STEP) & (2 ** 64 - 1), goals, attempt, q_lo, q_hi,
+                                         center=center, spread=spread) for c in range(C)], axis=0)
+        per_goal = obstacles is not None and not (isinstance(obstacles, np.ndarray) and obstacles.ndim == 2)
+        if per_goal:
+            obstacles = [np.asarray(o, dtype=np.float64).reshape(-1, 4) for o in obstacles]
+            if len(obstacles) != G:
+                raise ValueError(f"obstacles must be one [m, 4] array or one per goal ({G}), got {len(obstacles)}")
+            cl = np.empty((C, G))
+            for g in range(G):
+                cl[:, g] = self.candidate_clearance_host(q_c[:, g], clearance_mode, obstacles[g])
+        else:
+            cl = self.candidate_clearance_host(q_c.reshape(C * G, -1), clearance_mode, obstacles).reshape(C, G)
+        pick = retry_pick_host(cl, clear_tol)
+        self.last_screen = (q_c, cl)
+        cols = np.arange(G)
+        return q_c[pick, cols], pick, cl[pick, cols]
 
     def solve_trajectory(self, T_path, q_start, return_Y=False, retries=0, retry_seed=0, pos_tol=0.01, rot_tol=0.01,
                          clear_tol=1e-4, retry_spread=0.0, q_limits=None, clearance_mode="nodes", sweep=None, scenes=None,
-                         scene_id=None):
+                         scene_id=None, retry_candidates=1):
         """Path tracking among the obstacles: B paths of L waypoints, T_path [B, L, 4, 4].  Waypoint 0
         is seeded by q_start ([B,n] or [n]), waypoint l by the joint angles recovered at waypoint l-1,
         which never leave the device: L calls of gik_anchored_ik_batch_seeded on one stream, one
@@ -1021,7 +1087,8 @@ class AnchoredProblem:
         waypoint (the rule of solve(), clearance included) is solved again before it seeds the next one, and
         the rescued angles are what the next waypoint starts from.  retry_spread > 0 keeps the restarts within
         that many radians of the previous waypoint's angles.  The stream then synchronises once per attempt
-        and waypoint; info["attempt"] [B, L] int32 says which attempt each waypoint holds.
+        and waypoint; info["attempt"] [B, L] int32 says which attempt each waypoint holds.  retry_candidates (1 .. 16;
+        above 1 needs retries > 0) is passed on to every waypoint's solve: its restarts screen that many candidate seeds.
 
         clearance_mode: as in solve() -- which clearance info["clearance"] holds and the rule reads; with
         link_hinges=True clearance_mode="links" has hinges behind it at every waypoint.
@@ -1059,13 +1126,16 @@ class AnchoredProblem:
             sweep = self._check_samples(sweep, "sweep")
             if not len(self.link_names):
                 raise ValueError("sweep needs a link set: this problem was built without links")
-        retry = self._retry_args(retries, retry_seed, pos_tol, rot_tol, clear_tol, retry_spread, q_limits)
+        retry = self._retry_args(retries, retry_seed, pos_tol, rot_tol, clear_tol, retry_spread, q_limits,
+                                 retry_candidates=retry_candidates)
         tpl, base = self.template, self.base.template
         planes, shared, nbytes = ["clearance"], {}, None
         if restart_like(retries, clearance_mode, True, scenes):
             # one restart workspace for all waypoints: it holds the anchored scratch too and, with scenes, a compact
             # batch's ids behind it; without restarts it serves attempt 0 of the restart entry alone
             nbytes = tpl.anchored_retry_ws_bytes(base, B, scenes=scenes is not None)
+            if "retry_candidates" in retry:      # (and the screened step's arrays behind those)
+                nbytes = tpl.anchored_retry_screened_ws_bytes(base, B, retry["retry_candidates"])
         else:
             shared["ws"] = tpl.alloc_anchored_buffers(base, B)["ws"]
         if retry:
@@ -1441,6 +1511,20 @@ def retry_seeds_host(seed, goals, attempt, q_lo, q_hi, center=None, spread=0.0):
         raise ValueError(f"center must have shape {list(u.shape)}, got {list(c.shape)}")
     t = 2.0 * u - 1.0                                   # exact: u is a 53-bit fraction
     return np.minimum(np.maximum(c + np.float64(spread) * t, lo[None, :]), hi[None, :])
+
+
+def retry_pick_host(clearance, clear_tol=1e-4):
+    """Host mirror of retry_pick (gik_retry.hip.h): clearance [C, G] of C candidates per goal -> [G] the picked
+    candidate.  The first c with clearance >= -clear_tol (+inf qualifies); none: the c of the largest clearance, the
+    lowest on a tie, a NaN never winning; all NaN: 0."""
+    cl = np.asarray(clearance, dtype=np.float64)
+    if cl.ndim == 1:
+        cl = cl[:, None]
+    with np.errstate(invalid="ignore"):
+        clear = cl >= -clear_tol
+        largest = (cl == np.where(np.isnan(cl), -np.inf, cl).max(axis=0)[None, :]) & ~np.isnan(cl)
+    # (argmax takes the first True; a column without one -- all NaN -- gives 0)
+    return np.where(clear.any(axis=0), clear.argmax(axis=0), largest.argmax(axis=0)).astype(np.int64)
 
 
 def anchored_retry_failed(stop, pos_err, rot_err, clearance, pos_tol=0.01, rot_tol=0.01, clear_tol=1e-4):

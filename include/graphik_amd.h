@@ -867,6 +867,51 @@ int gik_anchored_ik_batch_retry_scenes(const gik_template *anch, const gik_templ
                                        double *d_Y_full, gik_stats *d_stats, double *d_q, double *d_pos_err,
                                        double *d_rot_err, double *d_clearance, int32_t *d_attempt, void *stream);
 
+/* ---- screened restart seeds in the fixed-anchor solve (opt-in) -----------------------------------
+ * A restart's seed is drawn blind: with a floor under the robot, most uniform draws already lie below it, and the rule
+ * above would call the seed itself failed.  The screened step draws `candidates` (C, 1 .. 16) seeds per failed goal,
+ * realizes each on the robot graph, measures each with the clearance the call's rule reads, and starts the restart from
+ * the first clear one.  All of it on the device, on the call's stream, with no host synchronisation of its own.
+ *
+ * candidate c of (seed, g, attempt)  :=  the seed of gik_anchored_retry_seeds under seed_c = seed + c * 0xD1342543DE82EF95
+ *                                        (mod 2^64): same generator, limits, centre and spread.  Candidate 0 is that
+ *                                        entry's row, bit for bit; retry_seeds_host(seed_c, ...) is the numpy mirror.
+ * clearance_c  :=  the clearance, in clearance_mode, of the robot graph's realization of the candidate -- every row where
+ *                  the configuration puts it, the end effector included (not where the goal puts it) --, half-spaces
+ *                  folded in where the handle has them, against the GOAL's scene where a scene set is given.
+ * pick         :=  the first c with clearance_c >= -clear_tol (+infinity qualifies: nothing to measure picks 0); none:
+ *                  the c of the largest clearance, the lowest on a tie, a NaN never winning; all NaN: 0.
+ *
+ * gik_anchored_retry_seeds_screened: gik_anchored_retry_seeds with the pick's angles in d_q_out [count][n]; d_T_out as
+ *   there.  scenes may be NULL (the template's own obstacles); its d_scene_id is indexed by GOAL, [B], like d_q_center.
+ *   Optional outputs: d_pick [count] int32, the picked c per slot, and d_pick_clearance [count], its clearance.
+ *   d_ws: gik_anchored_retry_seeds_screened_ws_bytes(anch, base, count, candidates) bytes, 8-byte aligned (0: bad arguments).
+ *   With candidates = 1 it writes the bits of gik_anchored_retry_seeds.
+ * gik_anchored_ik_batch_retry_screened: gik_anchored_ik_batch_retry (scenes NULL) or gik_anchored_ik_batch_retry_scenes
+ *   with every restart's seed step replaced by the screened one, in opts->clearance_mode and with opts->clear_tol;
+ *   attempt 0, select and merge are theirs.  A goal with d_attempt[g] = a > 0 holds what gik_anchored_ik_batch_seeded
+ *   returns for it alone from the pick of (seed, g, a).  d_ws: gik_anchored_ik_batch_retry_screened_ws_bytes(anch, base, B,
+ *   candidates) bytes, 8-byte aligned: the workspace of the scenes entry with the screened step's behind it.
+ * Refused, with a message, before anything is queued: what the siblings refuse (gik_anchored_retry_seeds; the restart
+ *   entries; a scene set as the scene calls refuse it; a clearance_mode as they refuse it; a capturing stream),
+ *   candidates outside 1 .. 16, a clear_tol that is not positive, a null or misaligned workspace.  count / B == 0 returns 0. */
+#define GIK_RETRY_MAX_CANDIDATES 16      /* candidates per slot of the screened entries: 1 .. 16 */
+size_t gik_anchored_retry_seeds_screened_ws_bytes(const gik_template *anch, const gik_template *base, int count, int candidates);
+int gik_anchored_retry_seeds_screened(const gik_template *anch, const gik_template *base, const double *d_T_goal,
+                                      const int32_t *d_idx, int count, uint64_t seed, int attempt, const double *d_q_lo,
+                                      const double *d_q_hi, const double *d_q_center /* [B][n]; may be NULL if spread == 0 */,
+                                      double spread, int candidates, int clearance_mode, double clear_tol,
+                                      const gik_scene_set *scenes /* may be NULL */, void *d_ws, double *d_T_out,
+                                      double *d_q_out, int32_t *d_pick /* may be NULL */,
+                                      double *d_pick_clearance /* may be NULL */, void *stream);
+size_t gik_anchored_ik_batch_retry_screened_ws_bytes(const gik_template *anch, const gik_template *base, int B, int candidates);
+int gik_anchored_ik_batch_retry_screened(const gik_template *anch, const gik_template *base, const double *d_T_goal,
+                                         const double *d_q_init /* may be NULL */, int B,
+                                         const gik_anchored_retry_opts *opts, int candidates,
+                                         const gik_scene_set *scenes /* may be NULL */, void *d_ws, double *d_Y_full,
+                                         gik_stats *d_stats, double *d_q, double *d_pos_err, double *d_rot_err,
+                                         double *d_clearance, int32_t *d_attempt, void *stream);
+
 /* Duration (ms, HIP events on the call's stream) of the anchored solve kernel inside the most
  * recent gik_anchored_ik_batch / gik_anchored_ik_batch_seeded on this handle; waits for it.  < 0 if there was none. */
 double gik_anchored_last_solve_ms(const gik_template *anch);
