@@ -196,6 +196,18 @@ SYMBOLS = {
     "gik_anchored_ik_batch_retry_screened": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                                        C.POINTER(AnchoredRetryOpts), C.c_int, C.POINTER(SceneSet)] +
                                              8 * [C.c_void_p] + [C.c_void_p]),
+    "gik_atlas_nearest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
+    "gik_anchored_atlas_seeds_ws_bytes": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    "gik_anchored_atlas_seeds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                           C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.POINTER(SceneSet)] +
+                                 5 * [C.c_void_p] + [C.c_void_p]),
+    "gik_anchored_ik_batch_atlas_ws_bytes": (C.c_size_t, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "gik_anchored_ik_batch_atlas": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                              C.POINTER(AnchoredRetryOpts), C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                              C.POINTER(SceneSet)] + 8 * [C.c_void_p] + [C.c_void_p]),
+    "gik_anchored_atlas_picks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
     "gik_template_destroy": (None, [C.c_void_p]),
     "gik_template_get_info": (C.c_int, [C.c_void_p, C.POINTER(TemplateInfo)]),
     "gik_template_set_claim_key": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),

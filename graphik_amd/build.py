@@ -19,7 +19,7 @@ LIB = os.path.join(HERE, "lib", "libgraphik_amd.so")
 DEV_LIB = os.path.join(HERE, "lib", "exp", "libgraphik_amd_dev.so")
 SOURCES = ["gik_host.hip", "gik_k_wave3.hip", "gik_k_wave3_strict.hip", "gik_k_anch.hip", "gik_k_anch_link.hip", "gik_k_anch_scene.hip", "gik_k_anch_self.hip", "gik_k_wave2.hip",
            "gik_k_block.hip", "gik_k_npt.hip", "gik_k_npt4.hip", "gik_k_quad.hip", "gik_k_prep.hip", "gik_k_retry.hip", "gik_k_anch_seed.hip",
-           "gik_k_order.hip", "gik_k_anch_half.hip", "gik_host_anch.hip"]      # (the second host unit last: the link order of the others is what it was)
+           "gik_k_order.hip", "gik_k_anch_half.hip", "gik_k_atlas.hip", "gik_host_anch.hip"]      # (the second host unit last: the link order of the others is what it was)
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 LINK_FLAGS = ["--offload-arch=gfx950", "-shared", "-fPIC"]
 # Per translation unit.  The per-edge kernels: their tCG loop branches only on wave-uniform conditions (UNI in

@@ -1,11 +1,12 @@
 // graphik_amd/csrc/gik_host_anch.hip -- the second host unit: the restarts and the fixed-anchor (obstacle) solve, with
 // their part of the C ABI of include/graphik_amd.h.  A client of gik_host.hip: it reaches templates and the prepare / seed /
 // solve / recover path only through the library's exports and the helpers of gik_handle.h (gik_anchored_attach_links is
-// creation and lives there).  It launches the plain kernels of gik_retry.hip.h, gik_anch_seed.hip.h and gik_anch_glue.hip.h
-// by their prototypes: no device code is compiled here, and no solve kernel's header is seen.
+// creation and lives there).  It launches the plain kernels of gik_retry.hip.h, gik_atlas.hip.h, gik_anch_seed.hip.h and
+// gik_anch_glue.hip.h by their prototypes: no device code is compiled here, and no solve kernel's header is seen.
 
 #include "gik_handle.h"
 #include "gik_retry.hip.h"
+#include "gik_atlas.hip.h"
 #include "gik_anch_glue.hip.h"
 #include "gik_anch_seed.hip.h"
 #include "gik_plan.h"
@@ -692,16 +693,30 @@ static std::string candidates_fault(int candidates, int B) {
 // The screened seed step on checked arguments, a.count > 0: the candidates of every slot, candidate-major; their
 // realization by the robot graph's seed kernel (its targets go unread), as the sweep realizes its samples; their
 // clearance in the call's mode, against the goal's scene where there are scenes (the ids tiled to the candidates);
-// the pick, whose angles go where retry_seed_kernel would have written its one row.
+// the pick, whose angles go where retry_seed_kernel would have written its one row.  atlas: null -- the candidates are
+// drawn (retry_candidate_kernel) --, or the second candidate source: neighbour ranks [first, first + candidates) of every
+// slot's goal (atlas_candidate_kernel; a.idx may then be null: slot r is goal r), and with `note` the picked row by goal.
+struct AtlasSource {
+  const double *q;        // [M][n]
+  const int32_t *nbr;     // [B][stride], by goal
+  int M, stride, first;
+  int32_t *note;          // [B], or null
+};
 static int screened_seed_launch(const gik_template *anch, const gik_template *base, const gik::RetrySeedArgs &a, int candidates,
                                 int mode, double clear_tol, const gik_scene_set *scenes, const gik::AnchScreenWs &w,
-                                int32_t *d_pick, double *d_pick_clearance, void *stream) {
+                                int32_t *d_pick, double *d_pick_clearance, void *stream, const AtlasSource *atlas = nullptr) {
   using namespace gik;
   const int M = a.count * candidates;
   const int32_t *goal_ids = scenes ? scenes->d_scene_id : nullptr;
-  const RetryCandidateArgs ca = {a.T_goal, a.idx, a.q_lo, a.q_hi, a.q_center, goal_ids, a.T_out, w.T, w.q, w.ids,
-                                 a.spread, a.seed, a.count, a.pose_w, a.n, a.attempt, candidates};
-  hipLaunchKernelGGL(retry_candidate_kernel, dim3(retry_grid(base, a.count)), dim3(RETRY_WAVE), 0, (hipStream_t)stream, ca);
+  if (atlas) {
+    const AtlasCandidateArgs ca = {a.T_goal, a.idx, atlas->q, atlas->nbr, goal_ids, a.T_out, w.T, w.q, w.ids,
+                                   a.count, a.pose_w, a.n, candidates, atlas->first, atlas->stride, atlas->M};
+    hipLaunchKernelGGL(atlas_candidate_kernel, dim3(retry_grid(base, a.count)), dim3(ATLAS_WAVE), 0, (hipStream_t)stream, ca);
+  } else {
+    const RetryCandidateArgs ca = {a.T_goal, a.idx, a.q_lo, a.q_hi, a.q_center, goal_ids, a.T_out, w.T, w.q, w.ids,
+                                   a.spread, a.seed, a.count, a.pose_w, a.n, a.attempt, candidates};
+    hipLaunchKernelGGL(retry_candidate_kernel, dim3(retry_grid(base, a.count)), dim3(RETRY_WAVE), 0, (hipStream_t)stream, ca);
+  }
   HIP_OK(hipGetLastError());
   int rc = gik_seed_batch(base, w.T, w.q, M, w.targets, w.Y, stream);
   if (rc) return rc;
@@ -714,6 +729,12 @@ static int screened_seed_launch(const gik_template *anch, const gik_template *ba
   const RetryPickArgs pa = {w.cl, w.q, a.q_out, d_pick ? d_pick : w.pick, d_pick_clearance, clear_tol, a.count, a.n, candidates};
   hipLaunchKernelGGL(retry_pick_kernel, dim3(retry_grid(base, a.count)), dim3(RETRY_WAVE), 0, (hipStream_t)stream, pa);
   HIP_OK(hipGetLastError());
+  if (atlas && atlas->note) {
+    const AtlasNoteArgs na = {a.idx, atlas->nbr, pa.pick, atlas->note, a.count, atlas->first, atlas->stride};
+    hipLaunchKernelGGL(atlas_note_kernel, dim3((a.count + ATLAS_NOTE_NT - 1) / ATLAS_NOTE_NT), dim3(ATLAS_NOTE_NT), 0,
+                       (hipStream_t)stream, na);
+    HIP_OK(hipGetLastError());
+  }
   return 0;
 }
 
@@ -857,6 +878,202 @@ int gik_anchored_ik_batch_retry_screened(const gik_template *anch, const gik_tem
                                          int32_t *d_attempt, void *stream) {
   return anchored_retry_impl("gik_anchored_ik_batch_retry_screened", anch, base, d_T_goal, d_q_init, B, opts, scenes, scenes != nullptr,
                              d_ws, d_Y_full, d_stats, d_q, d_pos_err, d_rot_err, d_clearance, d_attempt, stream, true, candidates);
+}
+
+// ---- goal-aware seeds from a configuration atlas (gik_atlas.hip.h) ----------------------------------------
+// the key width of a base template -- 6: p_e and q_e, 3: the p_e of a position goal -- or 0 with the reason in *why
+static int atlas_key_width(const gik_template *base, std::string *why) {
+  if (!base->has_pipe) return *why = "no pipeline attached to the base template (gik_pipeline_attach)", 0;
+  if (base->f.K != 3) return *why = "the base template is planar: the atlas key is that of a 3-D graph", 0;
+  if (base->pc.n_ee != 1) return *why = "the base template has more than one end effector", 0;
+  if (base->pc.goal_node[0] < 0) return *why = "the base template's first goal slot is inert", 0;
+  if (base->pc.goal_node[1] >= 0) return 6;
+  if (base->pc.pos_goal_mask & 1) return 3;
+  return *why = "the base template has an inert goal slot that is not a position goal's", 0;
+}
+
+// what is wrong with a neighbour count, a table size or a batch of that many neighbours, or nothing
+static std::string atlas_fault(int K, int atlas_count, int count) {
+  if (K < 1 || K > gik::ATLAS_MAX_K) return "K must be within 1 .. 64";
+  if (atlas_count < 1 || atlas_count > (1 << 30)) return "atlas_count must be within 1 .. 2^30";
+  if ((size_t)count * (size_t)K > (size_t)INT_MAX) return "count * K must fit an int";
+  return std::string();
+}
+
+// the nearest launch on checked arguments, count > 0
+static int atlas_nearest_launch(const gik_template *base, int W, const double *d_keys, int M, const double *d_T_goal,
+                                const int32_t *d_idx, int count, int K, int32_t *d_nbr, double *d_dist, void *stream) {
+  using namespace gik;
+  const AtlasNearestArgs a = {d_keys, d_T_goal, d_idx, d_nbr, d_dist, base->pc.ee_len[0], M, count, K, pose_width(base), W};
+  const int groups = (count + ATLAS_GOALS - 1) / ATLAS_GOALS;
+  hipLaunchKernelGGL(atlas_nearest_kernel, dim3(std::min(groups, base->f.n_cu * 32)), dim3(ATLAS_WAVE), 0, (hipStream_t)stream, a);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+int gik_atlas_nearest(const gik_template *base, const double *d_atlas_keys, int atlas_count, const double *d_T_goal,
+                      const int32_t *d_idx, int count, int K, int32_t *d_nbr, double *d_dist, void *stream) {
+  using namespace gik;
+  const std::string e("gik_atlas_nearest");
+  if (!base || count < 0) return fail(e + ": bad argument");
+  std::string why;
+  const int W = atlas_key_width(base, &why);
+  if (!W) return fail(e + ": " + why);
+  if (why = atlas_fault(K, atlas_count, count); !why.empty()) return fail(e + ": " + why);
+  if (!d_atlas_keys) return fail(e + ": null atlas (d_atlas_keys [W][atlas_count] is required)");
+  if (refuse_capture("gik_atlas_nearest", stream)) return -1;
+  if (count == 0) return 0;
+  if (!d_T_goal || !d_nbr) return fail(e + ": null buffer");
+  return atlas_nearest_launch(base, W, d_atlas_keys, atlas_count, d_T_goal, d_idx, count, K, d_nbr, d_dist, stream);
+}
+
+size_t gik_anchored_atlas_seeds_ws_bytes(const gik_template *anch, const gik_template *base, int count, int candidates) {
+  return gik_anchored_retry_seeds_screened_ws_bytes(anch, base, count, candidates);      // (the screened step's arrays)
+}
+
+int gik_anchored_atlas_seeds(const gik_template *anch, const gik_template *base, const double *d_atlas_q, int atlas_count,
+                             const double *d_T_goal, const int32_t *d_idx, int count, const int32_t *d_nbr, int nbr_stride,
+                             int first, int candidates, int clearance_mode, double clear_tol, const gik_scene_set *scenes,
+                             void *d_ws, double *d_T_out, double *d_q_out, int32_t *d_pick, double *d_pick_clearance,
+                             void *stream) {
+  using namespace gik;
+  const char *entry = "gik_anchored_atlas_seeds";
+  const std::string e(entry);
+  if (!anch || !base || count < 0) return fail(e + ": bad argument");
+  if (const std::string why = anchored_pair_fault(anch, base, PAIR_3D | PAIR_SEEDABLE); !why.empty()) return fail(e + ": " + why);
+  if (scenes && scene_refusal(entry, anch, scenes)) return -1;
+  if (clearance_mode_refusal(e, anch, clearance_mode)) return -1;
+  if (const std::string why = candidates_fault(candidates, count); !why.empty()) return fail(e + ": " + why);
+  if (atlas_count < 1 || atlas_count > (1 << 30)) return fail(e + ": atlas_count must be within 1 .. 2^30");
+  if (first < 0 || nbr_stride < 1 || first > nbr_stride - candidates)
+    return fail(e + ": ranks first .. first + candidates - 1 must lie within 0 .. nbr_stride - 1");
+  if (!(clear_tol > 0.0)) return fail(e + ": clear_tol must be positive");
+  if (!d_atlas_q) return fail(e + ": null atlas (d_atlas_q [atlas_count][n] is required)");
+  if (refuse_capture(entry, stream)) return -1;
+  if (count == 0) return 0;
+  if (!d_ws) return fail(e + ": null workspace (gik_anchored_atlas_seeds_ws_bytes)");
+  if ((uintptr_t)d_ws % 8) return fail(e + ": the workspace must be 8-byte aligned");
+  if (!d_T_goal || !d_nbr || !d_T_out || !d_q_out) return fail(e + ": null buffer");
+  const RetrySeedArgs a = {d_T_goal, d_idx, nullptr, nullptr, nullptr, d_T_out, d_q_out, 0.0, 0,
+                           count, pose_width(base), base->pc.n_joints, 0};
+  const AtlasSource src = {d_atlas_q, d_nbr, atlas_count, nbr_stride, first, nullptr};
+  return screened_seed_launch(anch, base, a, candidates, clearance_mode, clear_tol, scenes,
+                              anch_screen_ws(anch, base, count, candidates, 0, d_ws), d_pick, d_pick_clearance, stream, &src);
+}
+
+// the workspace of gik_anchored_ik_batch_atlas over d_ws (gik_plan.h), or with a null d_ws its size
+static gik::AnchAtlasWs anch_atlas_ws(const gik_template *anch, const gik_template *base, int B, int C, int retries, void *d_ws) {
+  return gik::anch_atlas_ws(base->pc.n_joints, pose_width(base), base->T, anch->full_N, B, C, retries,
+                            anch_screen_head(anch, base, B), d_ws);
+}
+
+// what is wrong with the (candidates, retries) of an atlas batch, or nothing
+static std::string atlas_batch_fault(int candidates, int retries, int B) {
+  if (retries < 0 || retries > 63) return "retries must be within 0 .. 63";
+  if (const std::string why = candidates_fault(candidates, B); !why.empty()) return why;
+  if ((retries + 1) * candidates > gik::ATLAS_MAX_K) return "K = (retries + 1) * candidates must be within 1 .. 64";
+  return std::string();
+}
+
+size_t gik_anchored_ik_batch_atlas_ws_bytes(const gik_template *anch, const gik_template *base, int B, int candidates, int retries) {
+  if (!anch || !base || !anchored_pair_fault(anch, base, 0).empty() || B < 0 || !atlas_batch_fault(candidates, retries, B).empty() ||
+      (size_t)B * (size_t)((retries + 1) * candidates) > (size_t)INT_MAX)
+    return 0;
+  return anch_atlas_ws(anch, base, B, candidates, retries, nullptr).bytes;
+}
+
+int gik_anchored_ik_batch_atlas(const gik_template *anch, const gik_template *base, const double *d_T_goal, const double *d_q_init,
+                                int B, const gik_anchored_retry_opts *opts, int candidates, const double *d_atlas_keys,
+                                const double *d_atlas_q, int atlas_count, const gik_scene_set *scenes, void *d_ws, double *d_Y_full,
+                                gik_stats *d_stats, double *d_q, double *d_pos_err, double *d_rot_err, double *d_clearance,
+                                int32_t *d_attempt, void *stream) {
+  using namespace gik;
+  const char *entry = "gik_anchored_ik_batch_atlas";
+  const std::string e(entry);
+  // every refusal comes before anything is queued
+  if (!anch || !base || B < 0 || !opts) return fail(e + ": bad argument");
+  if (const std::string why = anchored_pair_fault(anch, base, PAIR_3D | PAIR_SEEDABLE); !why.empty()) return fail(e + ": " + why);
+  if (scenes && scene_refusal(entry, anch, scenes)) return -1;
+  if (clearance_mode_refusal(e, anch, opts->clearance_mode)) return -1;
+  const int mode = opts->clearance_mode, retries = opts->retries;
+  std::string why;
+  const int W = atlas_key_width(base, &why);
+  if (!W) return fail(e + ": " + why);
+  if (why = atlas_batch_fault(candidates, retries, B); !why.empty()) return fail(e + ": " + why);
+  const int K = (retries + 1) * candidates;
+  if (why = atlas_fault(K, atlas_count, B); !why.empty()) return fail(e + ": " + why);
+  if (K > atlas_count) return fail(e + ": K = (retries + 1) * candidates exceeds atlas_count");
+  if (!(opts->pos_tol > 0.0) || !(opts->rot_tol > 0.0)) return fail(e + ": pos_tol and rot_tol must be positive");
+  if (!(opts->clear_tol > 0.0)) return fail(e + ": clear_tol must be positive");
+  if (opts->spread != 0.0) return fail(e + ": spread must be 0 (the restarts start from atlas rows, not from draws around d_q_init)");
+  if (!d_atlas_keys || !d_atlas_q) return fail(e + ": null atlas (d_atlas_keys [W][atlas_count] and d_atlas_q [atlas_count][n] are required)");
+  if (refuse_capture(entry, stream)) return -1;
+  if (B == 0) return 0;
+  if (!d_clearance || !d_attempt) return fail(e + ": null d_clearance or d_attempt");
+  if (!d_ws) return fail(e + ": null workspace (gik_anchored_ik_batch_atlas_ws_bytes)");
+  if ((uintptr_t)d_ws % 8) return fail(e + ": the workspace must be 8-byte aligned");
+  if (!d_T_goal || !d_Y_full || !d_stats || !d_q || !d_pos_err || !d_rot_err) return fail(e + ": null buffer");
+  hipStream_t s = (hipStream_t)stream;
+  const AnchRetryWs w = anch_retry_ws(anch, base, B, d_ws);
+  const AnchAtlasWs aw = anch_atlas_ws(anch, base, B, candidates, retries, d_ws);
+  const AnchScreenWs sw = anch_screen_ws(anch, base, B, candidates, aw.screen_head, d_ws);
+  HIP_OK(hipMemsetAsync(d_attempt, 0, (size_t)B * sizeof(int32_t), s));
+  HIP_OK(hipMemsetAsync(aw.rows, 0xFF, (size_t)B * (size_t)(retries + 1) * sizeof(int32_t), s));      // (-1: no atlas row)
+  int rc = atlas_nearest_launch(base, W, d_atlas_keys, atlas_count, d_T_goal, nullptr, B, K, aw.nbr, nullptr, stream);
+  if (rc) return rc;
+  gik_scene_set compact;      // the scene set of a compact batch: its ids are gathered into w.ids
+  if (scenes) {
+    compact = *scenes;
+    if (scenes->d_scene_id) compact.d_scene_id = w.ids;
+  }
+  const RetrySeedArgs seeds = {d_T_goal, w.idx, nullptr, nullptr, nullptr, w.T, w.q_seed, 0.0, 0, 0, pose_width(base), base->pc.n_joints, 0};
+  AtlasSource src = {d_atlas_q, aw.nbr, atlas_count, K, 0, aw.rows};
+  if (!d_q_init) {      // attempt 0 from the pick among ranks [0, C) of every goal: slot r is goal r
+    RetrySeedArgs all = seeds;
+    all.idx = nullptr;
+    all.q_out = aw.q0;
+    all.count = B;
+    if ((rc = screened_seed_launch(anch, base, all, candidates, mode, opts->clear_tol, scenes, sw, nullptr, nullptr, stream, &src))) return rc;
+  }
+  rc = anchored_attempt(anch, base, d_T_goal, d_q_init ? d_q_init : aw.q0, B, scenes, w.scratch, d_Y_full, d_stats, d_q, d_pos_err,
+                        d_rot_err, d_clearance, mode, stream);
+  if (rc) return rc;
+  const RetryTol tol = {opts->pos_tol, opts->rot_tol, opts->clear_tol};
+  const RetrySelectArgs select = {d_stats, d_pos_err, d_rot_err, d_clearance, tol, w.idx, w.count, B};
+  const RetryMergeArgs merge = {w.idx, w.Y, w.stats, w.q, w.pos_err, w.rot_err, w.clearance,
+                                d_Y_full, d_stats, d_q, d_pos_err, d_rot_err, d_clearance, d_attempt, tol, 0, anch->full_N * 3, base->pc.n_joints, 0};
+  const auto seed_step = [&](const RetrySeedArgs &a) {      // ranks [a C, (a + 1) C) of the failed goals
+    src.first = a.attempt * candidates;
+    src.note = aw.rows + (size_t)a.attempt * (size_t)B;
+    return screened_seed_launch(anch, base, a, candidates, mode, opts->clear_tol, scenes, sw, nullptr, nullptr, stream, &src);
+  };
+  return retry_loop(entry, base, retries, select, seeds, merge, stream, seed_step, [&](int count) {
+    if (scenes && scenes->d_scene_id) {
+      hipLaunchKernelGGL(scene_gather_kernel, dim3((count + ANCH_SCATTER_NT - 1) / ANCH_SCATTER_NT), dim3(ANCH_SCATTER_NT), 0, s,
+                         scenes->d_scene_id, w.idx, count, w.ids);
+      HIP_OK(hipGetLastError());
+    }
+    return anchored_attempt(anch, base, w.T, w.q_seed, count, scenes ? &compact : nullptr, w.scratch, w.Y, w.stats, w.q, w.pos_err,
+                            w.rot_err, w.clearance, mode, stream);
+  });
+}
+
+int gik_anchored_atlas_picks(const gik_template *anch, const gik_template *base, int B, int candidates, int retries, const void *d_ws,
+                             const int32_t *d_attempt, int32_t *d_atlas_pick, void *stream) {
+  using namespace gik;
+  const std::string e("gik_anchored_atlas_picks");
+  if (!anch || !base || B < 0) return fail(e + ": bad argument");
+  if (const std::string why = anchored_pair_fault(anch, base, 0); !why.empty()) return fail(e + ": " + why);
+  if (const std::string why = atlas_batch_fault(candidates, retries, B); !why.empty()) return fail(e + ": " + why);
+  if (refuse_capture("gik_anchored_atlas_picks", stream)) return -1;
+  if (B == 0) return 0;
+  if (!d_ws || (uintptr_t)d_ws % 8) return fail(e + ": null or misaligned workspace (that of gik_anchored_ik_batch_atlas)");
+  if (!d_attempt || !d_atlas_pick) return fail(e + ": null buffer");
+  const AnchAtlasWs aw = anch_atlas_ws(anch, base, B, candidates, retries, const_cast<void *>(d_ws));
+  const AtlasKeptArgs a = {d_attempt, aw.rows, d_atlas_pick, B, retries + 1};
+  hipLaunchKernelGGL(atlas_kept_kernel, dim3((B + ATLAS_NOTE_NT - 1) / ATLAS_NOTE_NT), dim3(ATLAS_NOTE_NT), 0, (hipStream_t)stream, a);
+  HIP_OK(hipGetLastError());
+  return 0;
 }
 
 double gik_anchored_last_solve_ms(const gik_template *anch) {

@@ -446,4 +446,27 @@ inline size_t anch_screen_head(int n_joints, int pose_w, int base_T, int base_N,
   return reinterpret_cast<uintptr_t>(w.ids) + ((size_t)B * sizeof(int32_t) + 7) / 8 * 8;
 }
 
+// The workspace of gik_anchored_ik_batch_atlas (gik_anchored_ik_batch_atlas_ws_bytes = bytes): behind the anchored restart
+// workspace and its ids (`head` = anch_screen_head(...), so that every array in front keeps its place), with
+// K = (retries + 1) C neighbours per goal:
+//   neighbour table [B][K] int32 | attempt-0 seed angles [B][n] | noted atlas rows [retries + 1][B] int32 |
+//   the screened step's arrays for B C candidates (AnchScreenWs at screen_head)
+struct AnchAtlasWs {
+  int32_t *nbr, *rows;
+  double *q0;
+  size_t screen_head;      // where the AnchScreenWs begins
+  size_t bytes;            // head and the screen arrays included
+};
+inline AnchAtlasWs anch_atlas_ws(int n_joints, int pose_w, int base_T, int full_N, int B, int C, int retries, size_t head, void *ws) {
+  const size_t b = (size_t)B, K = ((size_t)retries + 1) * (size_t)C;
+  WsCarve c = {reinterpret_cast<uintptr_t>(ws), head};
+  AnchAtlasWs w;
+  w.nbr = c.take<int32_t>(b * K);
+  w.q0 = c.take<double>(b * (size_t)n_joints);
+  w.rows = c.take<int32_t>(b * ((size_t)retries + 1));
+  w.screen_head = c.off;
+  w.bytes = anch_screen_ws(n_joints, pose_w, base_T, full_N, B, C, w.screen_head, nullptr).bytes;
+  return w;
+}
+
 }  // namespace gik

@@ -119,15 +119,29 @@ RETRY_MAX_CANDIDATES = 16                        # GIK_RETRY_MAX_CANDIDATES (inc
 RETRY_CANDIDATE_STEP = 0xD1342543DE82EF95        # candidate c draws under the seed (seed + c * this) mod 2^64
 
 
-def check_retry_candidates(retry_candidates, retries=None):
+def check_retry_candidates(retry_candidates, retries=None, what="retry_candidates"):
     """retry_candidates of an anchored solve, checked on the host before any device call: an int within 1 .. 16, and
-    above 1 only with retries > 0 (retries=None: the stand-alone step, which has no retries).  ValueError otherwise."""
+    above 1 only with retries > 0 (retries=None: the stand-alone step, which has no retries).  ValueError otherwise.
+    what: the keyword's name in the message (atlas_candidates takes the same range)."""
     if isinstance(retry_candidates, (bool, np.bool_)) or not isinstance(retry_candidates, (int, np.integer)) or \
             not 1 <= int(retry_candidates) <= RETRY_MAX_CANDIDATES:
-        raise ValueError(f"retry_candidates must be an integer within 1 .. {RETRY_MAX_CANDIDATES}, got {retry_candidates!r}")
+        raise ValueError(f"{what} must be an integer within 1 .. {RETRY_MAX_CANDIDATES}, got {retry_candidates!r}")
     if retries is not None and int(retry_candidates) > 1 and not retries:
         raise ValueError("retry_candidates > 1 needs retries > 0: the candidates are drawn for the restarts")
     return int(retry_candidates)
+
+
+ATLAS_MAX_NEIGHBOURS = 64                        # GIK_ATLAS_MAX_NEIGHBOURS (include/graphik_amd.h)
+
+
+def check_atlas_k(k, count, what="k"):
+    """A neighbour count of the atlas entries, checked on the host before any device call: an int within 1 .. 64 and,
+    where `count` (the atlas's rows) is given, at most that.  ValueError otherwise."""
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= ATLAS_MAX_NEIGHBOURS:
+        raise ValueError(f"{what} must be an integer within 1 .. {ATLAS_MAX_NEIGHBOURS}, got {k!r}")
+    if count is not None and int(k) > count:
+        raise ValueError(f"{what} = {int(k)} exceeds the atlas's {count} rows")
+    return int(k)
 
 
 def _retry_opts(retries, retry_seed, pos_tol, rot_tol, q_lo, q_hi, mode=None, clear_tol=None, retry_spread=0.0):
@@ -532,6 +546,7 @@ class Template:
         for e, (x, y) in (point_axis or {}).items():
             self._call("gik_pipeline_set_point_axis", self._h, int(e), float(x), float(y))
         self.n_joints = int(d.n_joints)
+        self.goal_slots = (int(d.goal_node0), int(d.goal_node1))      # (-1: the inert odd slot of a position goal)
         self.has_pipeline = True
         self._read_info()
 
@@ -716,6 +731,72 @@ class Template:
                    None if sc is None else C.byref(sc), ws.data_ptr(), T_out.data_ptr(), q.data_ptr(), pick.data_ptr(),
                    cl.data_ptr(), self._stream())
         return {"q": q, "T": T_out.reshape(count, 4, 4), "pick": pick, "clearance": cl, "_ws": ws, "_scene_id": ids}
+
+    def atlas_key_width(self):
+        """Doubles per atlas key on this robot-graph template (gik_atlas_nearest): 6 -- p_e and q_e of a pose goal --, or 3,
+        the p_e of a position goal."""
+        return 3 * sum(1 for g in self.goal_slots if g >= 0)
+
+    def atlas_nearest(self, atlas, T_goal, k, idx=None, dist=True):
+        """The k (1 .. 64) atlas rows nearest to each goal, on this robot-graph template (gik_atlas_nearest): `atlas` holds
+        the device tensors keys [W, M] (component-major) and count = M; T_goal [B, 4, 4]; idx (optional, [count] int32):
+        slot r is goal idx[r].  Returns device tensors (nbr [count, k] int32, dist [count, k] or None): ascending in
+        (distance, row), -1 / +inf where fewer than k rows have a finite distance.
+        riemannian_solver.atlas_nearest_host is the numpy mirror."""
+        check_atlas_k(k, None)
+        if atlas.width != self.atlas_key_width():
+            raise ValueError(f"the atlas has keys of width {atlas.width}, this template's goals have {self.atlas_key_width()}")
+        T, B = self._poses(T_goal)
+        if idx is not None:
+            if not isinstance(idx, torch.Tensor):
+                idx = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int32))
+            idx = idx.to(device=self.device, dtype=torch.int32).contiguous()
+            assert idx.dim() == 1
+        count = B if idx is None else idx.numel()
+        nbr = torch.empty(count, int(k), dtype=torch.int32, device=self.device)
+        d = torch.empty(count, int(k), dtype=torch.float64, device=self.device) if dist else None
+        self._call("gik_atlas_nearest", self._h, atlas.d_keys.data_ptr(), atlas.count, T.data_ptr(),
+                   None if idx is None else idx.data_ptr(), count, int(k), nbr.data_ptr(), None if d is None else d.data_ptr(),
+                   self._stream())
+        return nbr, d
+
+    def anchored_atlas_seeds(self, base, atlas, T_goal, nbr, candidates, first=0, idx=None, clearance_mode="nodes", clear_tol=1e-4,
+                             scenes=None, scene_id=None):
+        """The screened seed step with the atlas as its candidate source (gik_anchored_atlas_seeds): candidate c of slot r
+        (goal g = idx[r], or r) is atlas row nbr[g, first + c]; nbr [B, K] int32 on the device, indexed by goal (what
+        base.atlas_nearest returns without idx).  Returns what anchored_retry_seeds_screened returns
+        (AnchoredProblem.atlas_seeds_host is the numpy mirror)."""
+        assert self.anchored and base.has_pipeline
+        mode = check_clearance_mode(clearance_mode, getattr(self, "n_link", None) is not None,
+                                    getattr(self, "n_self", None) is not None)
+        candidates = check_retry_candidates(candidates)
+        if not clear_tol > 0:
+            raise ValueError("clear_tol must be positive")
+        T, B = base._poses(T_goal)
+        n = base.n_joints
+        assert nbr.dtype == torch.int32 and nbr.dim() == 2 and nbr.shape[0] == B and nbr.is_contiguous()
+        if idx is not None:
+            if not isinstance(idx, torch.Tensor):
+                idx = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int32))
+            idx = idx.to(device=self.device, dtype=torch.int32).contiguous()
+        count = B if idx is None else idx.numel()
+        sc, ids = self._scene_desc(scenes, scene_id, B)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        q = torch.empty(count, n, **f64)
+        T_out = torch.empty(count, T.numel() // max(B, 1), **f64)
+        pick = torch.empty(count, dtype=torch.int32, device=self.device)
+        cl = torch.empty(count, **f64)
+        ws = workspace(int(self.lib.gik_anchored_atlas_seeds_ws_bytes(self._h, base._h, count, candidates)), self.device)
+        self._call("gik_anchored_atlas_seeds", self._h, base._h, atlas.d_q.data_ptr(), atlas.count, T.data_ptr(),
+                   None if idx is None else idx.data_ptr(), count, nbr.data_ptr(), int(nbr.shape[1]), int(first), candidates,
+                   mode, float(clear_tol), None if sc is None else C.byref(sc), ws.data_ptr(), T_out.data_ptr(), q.data_ptr(),
+                   pick.data_ptr(), cl.data_ptr(), self._stream())
+        return {"q": q, "T": T_out.reshape(count, 4, 4), "pick": pick, "clearance": cl, "_ws": ws, "_scene_id": ids}
+
+    def anchored_atlas_ws_bytes(self, base, B, candidates, retries):
+        """Bytes of the restart workspace ("retry_ws") of one anchored_ik call of B goals with atlas=
+        (gik_anchored_ik_batch_atlas_ws_bytes), with or without scenes."""
+        return int(self.lib.gik_anchored_ik_batch_atlas_ws_bytes(self._h, base._h, B, candidates, retries))
 
     def alloc_anchored_buffers(self, base, B, clearance=False, ws=True):
         """The buffers of one anchored_ik call of B goals (its `out`): the scratch "ws" (ws=False leaves it out: a call
@@ -920,7 +1001,7 @@ class Template:
 
     def anchored_ik(self, base, T_goal, q_init=None, out=None, clearance=False, retries=0, retry_seed=0, pos_tol=0.01,
                     rot_tol=0.01, clear_tol=1e-4, retry_spread=0.0, q_limits=None, clearance_mode="nodes", scenes=None,
-                    scene_id=None, scene_id_checked=False, retry_candidates=1):
+                    scene_id=None, scene_id_checked=False, retry_candidates=1, atlas=None, atlas_candidates=1):
         """Whole pipeline through the fixed-anchor solve: `base` is the robot graph's Template (no
         obstacles) with its pipeline attached.  Without q_init the start point is the robot graph's bound
         smoothing + MDS one fitted to the anchors (gik_anchored_ik_batch); with q_init (seed joint angles
@@ -951,13 +1032,34 @@ class Template:
 
         retry_candidates (1 .. 16; above 1 needs retries > 0): every restart draws that many candidate seeds per failed
         goal, measures their realizations in clearance_mode and starts from the first one that is clear
-        (gik_anchored_ik_batch_retry_screened, with or without scenes).  1: the entries above, one blind seed."""
+        (gik_anchored_ik_batch_retry_screened, with or without scenes).  1: the entries above, one blind seed.
+
+        atlas (an object with the device tensors d_keys [W, M], d_q [M, n] and count = M: riemannian_solver.SeedAtlas) with
+        atlas_candidates = C (1 .. 16): gik_anchored_ik_batch_atlas -- attempt 0 starts from the pick among the C atlas rows
+        nearest to the goal (from q_init where that is given), restart a from the pick among ranks [a C, (a + 1) C); no
+        seed is drawn, so retry_seed and q_limits are not read and retry_spread must be 0.  (retries + 1) C is at most 64
+        and at most atlas.count.  Adds "atlas_pick" [B] int32: the atlas row the answer each goal holds started from, -1
+        where it started from q_init.  None (the default): the call as it was."""
         assert self.anchored and base.has_pipeline
         retry_candidates = check_retry_candidates(retry_candidates, retries)
+        if atlas is not None:
+            atlas_candidates = check_retry_candidates(atlas_candidates, what="atlas_candidates")
+            if retry_candidates > 1:
+                raise ValueError("atlas= with retry_candidates > 1 is not supported: the restarts take atlas rows, not draws")
+            if retry_spread > 0:
+                raise ValueError("atlas= with retry_spread > 0 is not supported: the restarts take atlas rows, not draws around q_init")
+            if int(retries) == retries and 0 <= int(retries) <= RETRY_MAX:
+                check_atlas_k((int(retries) + 1) * atlas_candidates, atlas.count, "(retries + 1) * atlas_candidates")
+            if atlas.width != base.atlas_key_width():
+                raise ValueError(f"the atlas has keys of width {atlas.width}, the base template's goals have {base.atlas_key_width()}")
+            if retries and q_limits is None:      # (not read: no seed is drawn)
+                q_limits = (np.zeros(base.n_joints), np.zeros(base.n_joints))
         mode = check_clearance_mode(clearance_mode, getattr(self, "n_link", None) is not None,
                                     getattr(self, "n_self", None) is not None)
-        restart = restart_like(retries, clearance_mode, clearance, scenes)
+        restart = restart_like(retries, clearance_mode, clearance, scenes) or atlas is not None
         lo = hi = None
+        if atlas is not None:
+            clearance = True
         if retries:      # (the clearance always comes back then, whatever `clearance` says)
             retries, lo, hi = check_retry_args(retries, pos_tol, rot_tol, q_limits, base.n_joints, clear_tol=clear_tol,
                                                retry_spread=retry_spread, has_center=q_init is not None)
@@ -976,11 +1078,17 @@ class Template:
         after = None      # the clearance export to launch behind the solve, where the entry does not measure it itself
         if restart:      # retries = 0: attempt 0 alone -- the call, the link clearance, the self clearance merged into it
             screened = retry_candidates > 1
-            nbytes = self.anchored_retry_screened_ws_bytes(base, B, retry_candidates) if screened else \
+            nbytes = self.anchored_atlas_ws_bytes(base, B, atlas_candidates, int(retries)) if atlas is not None else \
+                self.anchored_retry_screened_ws_bytes(base, B, retry_candidates) if screened else \
                 self.anchored_retry_ws_bytes(base, B, scenes=sc is not None)
-            attempt, ws, q_lo, q_hi = self._retry_buffers(out, B, nbytes, lo, hi, limits=bool(retries))
-            opts = _retry_opts(retries, retry_seed, pos_tol, rot_tol, q_lo, q_hi, mode, clear_tol, retry_spread)
-            if screened:      # (one entry with a nullable scene set)
+            attempt, ws, q_lo, q_hi = self._retry_buffers(out, B, nbytes, lo, hi, limits=bool(retries) and atlas is None)
+            opts = _retry_opts(retries if atlas is None else 0, retry_seed, pos_tol, rot_tol, q_lo, q_hi, mode, clear_tol, retry_spread)
+            if atlas is not None:      # (no seed, no limits, no spread: the options of attempt 0 with the retry count)
+                opts.retries = int(retries)
+                name = "gik_anchored_ik_batch_atlas"
+                scene = (atlas_candidates, atlas.d_keys.data_ptr(), atlas.d_q.data_ptr(), atlas.count,
+                         None if sc is None else C.byref(sc))
+            elif screened:      # (one entry with a nullable scene set)
                 name, scene = "gik_anchored_ik_batch_retry_screened", (retry_candidates, None if sc is None else C.byref(sc))
             else:
                 name = "gik_anchored_ik_batch_retry" if sc is None else "gik_anchored_ik_batch_retry_scenes"
@@ -1005,6 +1113,11 @@ class Template:
         self._call(name, self._h, base._h, T.data_ptr(), *args, self._stream())
         if after:
             self._call(after, self._h, out["Y"].data_ptr(), B, cl_ptr, self._stream())
+        if atlas is not None:
+            extras["atlas_pick"] = torch.empty(B, dtype=torch.int32, device=self.device)
+            extras["_atlas"] = atlas      # (its tensors are read by the kernels: lives as long as the result)
+            self._call("gik_anchored_atlas_picks", self._h, base._h, B, atlas_candidates, int(retries), ws.data_ptr(),
+                       attempt.data_ptr(), extras["atlas_pick"].data_ptr(), self._stream())
         return _result(out, (B, self.full_N, 3), extras)
 
     def alloc_ik_buffers(self, B):

@@ -16,8 +16,8 @@ import time
 import numpy as np
 import torch
 
-from ..engine import (RETRY_CANDIDATE_STEP, Template, _alloc_stats, _decode_stats, build_terms, check_clearance_mode,
-                      check_retry_args, check_retry_candidates, restart_like,
+from ..engine import (RETRY_CANDIDATE_STEP, Template, _alloc_stats, _decode_stats, build_terms, check_atlas_k,
+                      check_clearance_mode, check_retry_args, check_retry_candidates, restart_like,
                       workspace)
 from ..utils import dgp
 from ..utils.constants import POS
@@ -963,9 +963,82 @@ class AnchoredProblem:
             raise ValueError("a host-only problem has no device to upload scenes to")
         return SceneSet(scenes, self.template.device)
 
+    def seed_atlas(self, size=65536, seed=0, q_limits=None, clearance_mode="nodes", clear_tol=1e-4):
+        """A SeedAtlas of this problem: the rows of retry_seeds_host(seed, arange(size), 0, lo, hi) -- uniform inside
+        q_limits, default the robot's limits_arrays() -- whose realization is clear of the room,
+        candidate_clearance_host(q, clearance_mode) >= -clear_tol, with their keys (base.seed_points, the goal rows).
+        Host numpy, about a second for 65536 rows; the device is touched only by the upload at the end (not at all on a
+        host-only problem)."""
+        if isinstance(size, (bool, np.bool_)) or int(size) != size or size < 1:
+            raise ValueError(f"size must be a positive integer, got {size!r}")
+        if not clear_tol > 0:
+            raise ValueError("clear_tol must be positive")
+        check_clearance_mode(clearance_mode, len(self.link_names) > 0, self.self_pairs is not None)
+        lo, hi = self.robot.limits_arrays() if q_limits is None else q_limits
+        q = retry_seeds_host(seed, np.arange(int(size)), 0, lo, hi)
+        return SeedAtlas.from_configurations(self, q, clearance_mode, clear_tol, keep_clear_only=True)
+
+    def _check_atlas(self, atlas):
+        """atlas of a call -> itself: a SeedAtlas whose key width is this problem's base template's, uploaded."""
+        if not isinstance(atlas, SeedAtlas):
+            raise TypeError("atlas must be a SeedAtlas (AnchoredProblem.seed_atlas, SeedAtlas.from_configurations)")
+        width = 3 * len(self.base.goal_nodes)
+        if atlas.width != width:
+            raise ValueError(f"the atlas has keys of width {atlas.width}, this problem's goals have {width}")
+        if atlas.q.shape[1] != self.robot.n:
+            raise ValueError(f"the atlas has rows of {atlas.q.shape[1]} angles, the robot has {self.robot.n} joints")
+        return atlas
+
+    def atlas_nearest(self, T_goals, atlas, k):
+        """Goal poses [B, 4, 4] -> device (idx [B, k] int32, dist [B, k]): the k (1 .. 64) rows of `atlas` whose key lies
+        nearest to each goal's (gik_atlas_nearest on the robot graph's template), ascending in (distance, row); -1 / +inf
+        where fewer than k rows have a finite distance.  atlas_nearest_host(atlas.keys, goal_anchors(T_goals), k) is the
+        mirror, equal in idx and in the bits of dist."""
+        self._check_atlas(atlas)
+        k = check_atlas_k(k, None)
+        if self.template is None:
+            raise ValueError("a host-only problem has no device: atlas_nearest_host is the mirror")
+        if atlas.d_keys is None:
+            atlas.upload(self.template.device)
+        return self.base.template.atlas_nearest(atlas, np.asarray(T_goals, dtype=float), k)
+
+    def atlas_seeds_host(self, T_goals, atlas, candidates, first=0, clearance_mode="nodes", clear_tol=1e-4, obstacles=None):
+        """The numpy mirror of the atlas seed step (gik_anchored_atlas_seeds over all goals): candidate c of goal g is the
+        atlas row of rank first + c among the goal's nearest (atlas_nearest_host; a missing rank is a NaN row), each
+        measured by candidate_clearance_host, and retry_pick_host's choice among them.  obstacles: as screened_seeds_host
+        (None, one [m, 4] scene, or one per goal).  Returns (q [G, n] the picked angles, pick [G] int, clearance [G] of
+        the pick); self.last_atlas = (rows [C, G] the candidates' atlas rows, q_c [C, G, n], clearance_c [C, G])."""
+        self._check_atlas(atlas)
+        C = check_retry_candidates(candidates)
+        if isinstance(first, (bool, np.bool_)) or int(first) != first or first < 0:
+            raise ValueError(f"first must be a non-negative integer, got {first!r}")
+        first = int(first)
+        check_atlas_k(first + C, None, "first + candidates")
+        if not clear_tol > 0:
+            raise ValueError("clear_tol must be positive")
+        T = np.asarray(T_goals, dtype=float)
+        G = len(T)
+        nbr, _ = atlas_nearest_host(atlas.keys, self.goal_anchors(T), first + C)
+        rows = np.ascontiguousarray(nbr[:, first:first + C].T)                      # [C, G]
+        q_c = np.where((rows >= 0)[..., None], atlas.q[np.maximum(rows, 0)], np.nan)
+        per_goal = obstacles is not None and not (isinstance(obstacles, np.ndarray) and obstacles.ndim == 2)
+        if per_goal:
+            obstacles = [np.asarray(o, dtype=np.float64).reshape(-1, 4) for o in obstacles]
+            if len(obstacles) != G:
+                raise ValueError(f"obstacles must be one [m, 4] array or one per goal ({G}), got {len(obstacles)}")
+            cl = np.empty((C, G))
+            for g in range(G):
+                cl[:, g] = self.candidate_clearance_host(q_c[:, g], clearance_mode, obstacles[g])
+        else:
+            cl = self.candidate_clearance_host(q_c.reshape(C * G, -1), clearance_mode, obstacles).reshape(C, G)
+        pick = retry_pick_host(cl, clear_tol)
+        self.last_atlas = (rows, q_c, cl)
+        cols = np.arange(G)
+        return q_c[pick, cols], pick, cl[pick, cols]
+
     def solve(self, T_goals, q_init=None, clearance=False, retries=0, retry_seed=0, pos_tol=0.01, rot_tol=0.01,
               clear_tol=1e-4, retry_spread=0.0, q_limits=None, clearance_mode="nodes", scenes=None, scene_id=None,
-              retry_candidates=1):
+              retry_candidates=1, atlas=None, atlas_candidates=1):
         """Goal poses -> dict of device tensors (x [B, N_robot, 3], q, pos_err, rot_err, stats).
 
         q_init (warm start): joint angles [B,n] or [n]; the solve then starts from the realization of
@@ -1001,15 +1074,43 @@ class AnchoredProblem:
         (clearance_mode, half-spaces, the goal's scene) and starts from the first that is clear -- or, where none is, from
         the one with the largest clearance.  screened_seeds_host is the numpy mirror of the choice; a goal with
         "attempt" = a > 0 holds what solve(T[g:g+1], q_init=that pick) returns.  1 (the default): one blind seed, the
-        call as it was."""
+        call as it was.
+
+        atlas (a SeedAtlas: seed_atlas, SeedAtlas.from_configurations) with atlas_candidates = C (1 .. 16): a seed that
+        knows the goal (gik_anchored_ik_batch_atlas).  Without q_init attempt 0 starts from the pick -- the first clear
+        one, as above -- among the C atlas rows whose end effector lies nearest to the goal's; restart a of a failed goal
+        starts from the pick among ranks [a C, (a + 1) C).  With q_init attempt 0 starts there and the restarts alone
+        take atlas rows.  Combines with clearance_mode and scenes / scene_id; retry_seed and q_limits are not read.
+        ValueError before any device call: retry_spread > 0, retry_candidates > 1, (retries + 1) C above 64 or above
+        atlas.count, an atlas whose key width is not this problem's.  A goal with "attempt" = a holds what
+        solve(T[g:g+1], q_init=atlas_seeds_host(T, atlas, C, first=a C, ...)[0][g:g+1]) returns; "atlas_pick" [B] int32
+        names the atlas row it started from (-1: from q_init).  None (the default): the call as it was."""
         T = np.asarray(T_goals, dtype=float)
         check_clearance_mode(clearance_mode, len(self.link_names) > 0, self.self_pairs is not None)
+        extra = {}
+        if atlas is not None:
+            self._check_atlas(atlas)
+            C = check_retry_candidates(atlas_candidates, what="atlas_candidates")
+            if retry_spread > 0:
+                raise ValueError("atlas= with retry_spread > 0 is not supported: the restarts take atlas rows, not draws around q_init")
+            if check_retry_candidates(retry_candidates) > 1:
+                raise ValueError("atlas= with retry_candidates > 1 is not supported: the restarts take atlas rows, not draws")
+            if int(retries) == retries and 0 <= int(retries) <= 63:      # (anything else is _retry_args' to refuse)
+                check_atlas_k((int(retries) + 1) * C, atlas.count, "(retries + 1) * atlas_candidates")
+            extra = dict(atlas=atlas, atlas_candidates=C)
+        elif atlas_candidates != 1:
+            raise ValueError("atlas_candidates needs atlas=")
         retry = self._retry_args(retries, retry_seed, pos_tol, rot_tol, clear_tol, retry_spread, q_limits, q_init is not None,
                                  retry_candidates)
         if q_init is not None:
             q_init = _seed_angles(q_init, T.shape[0], self.robot.n)
+        if atlas is not None:
+            if not retry:      # (attempt 0 alone still runs on the atlas entry, under the call's tolerances)
+                retry = dict(pos_tol=pos_tol, rot_tol=rot_tol, clear_tol=clear_tol)
+            if atlas.d_keys is None:
+                atlas.upload(self.template.device)
         return self.template.anchored_ik(self.base.template, T, q_init=q_init, clearance=clearance or q_init is not None,
-                                         clearance_mode=clearance_mode, scenes=scenes, scene_id=scene_id, **retry)
+                                         clearance_mode=clearance_mode, scenes=scenes, scene_id=scene_id, **retry, **extra)
 
     def _retry_args(self, retries, retry_seed, pos_tol, rot_tol, clear_tol, retry_spread, q_limits, has_center=True,
                     retry_candidates=1):
@@ -1525,6 +1626,84 @@ def retry_pick_host(clearance, clear_tol=1e-4):
         largest = (cl == np.where(np.isnan(cl), -np.inf, cl).max(axis=0)[None, :]) & ~np.isnan(cl)
     # (argmax takes the first True; a column without one -- all NaN -- gives 0)
     return np.where(clear.any(axis=0), clear.argmax(axis=0), largest.argmax(axis=0)).astype(np.int64)
+
+
+def atlas_nearest_host(keys, goal_keys, K, chunk=64):
+    """Host mirror of gik_atlas_nearest: keys [M, W] (one row per atlas row), goal_keys [G, W] -> (nbr [G, K] int32,
+    dist [G, K]): per goal the K rows with the smallest (d, m), ascending, d = (...((t0 t0 + t1 t1) + t2 t2) ...) with
+    t_c = goal_keys[g, c] - keys[m, c] -- every difference, product and sum rounded on its own, in column order, so the
+    bits of the device's --, by a stable sort.  A NaN or infinite d is never listed; where fewer than K rows are listed
+    the rest is -1 / +inf.  chunk: goals per pass (the table of distances is [chunk, M])."""
+    keys = np.asarray(keys, dtype=np.float64)
+    g = np.asarray(goal_keys, dtype=np.float64)
+    if keys.ndim != 2 or g.ndim != 2 or keys.shape[1] != g.shape[1]:
+        raise ValueError(f"keys [M, W] and goal_keys [G, W] must share W, got {list(keys.shape)} and {list(g.shape)}")
+    K = check_atlas_k(K, None, "K")
+    G, M, W = g.shape[0], keys.shape[0], keys.shape[1]
+    nbr = np.full((G, K), -1, dtype=np.int32)
+    dist = np.full((G, K), np.inf)
+    take = min(K, M)
+    for s in range(0, G, chunk):
+        gs = g[s:s + chunk]
+        with np.errstate(invalid="ignore", over="ignore"):
+            t = gs[:, None, 0] - keys[None, :, 0]
+            d = t * t
+            for c in range(1, W):
+                t = gs[:, None, c] - keys[None, :, c]
+                d = d + t * t
+        d = np.where(np.isfinite(d), d, np.inf)
+        order = np.argsort(d, axis=1, kind="stable")[:, :take]
+        dk = np.take_along_axis(d, order, axis=1)
+        nbr[s:s + chunk, :take] = np.where(np.isfinite(dk), order, -1)
+        dist[s:s + chunk, :take] = dk
+    return nbr, dist
+
+
+class SeedAtlas:
+    """A configuration atlas for goal-aware seeds of the anchored solve (AnchoredProblem.solve(..., atlas=)): joint
+    configurations that are clear of the room, each with its key -- the positions its end effector's goal nodes take.
+    Holds q [M, n], keys [M, W] and clearance [M] as numpy arrays, count = M, width = W and, once uploaded, the device
+    tensors d_q [M, n] and d_keys [W, M] (component-major, what gik_atlas_nearest reads).  Built on the host by
+    AnchoredProblem.seed_atlas or from_configurations; the upload is the only device work."""
+
+    def __init__(self, q, keys, clearance, device=None):
+        self.q, self.keys, self.clearance = (np.array(a, dtype=np.float64, order="C") for a in (q, keys, clearance))      # (copies)
+        if self.q.ndim != 2 or self.keys.ndim != 2 or len(self.keys) != len(self.q) or self.clearance.shape != (len(self.q),):
+            raise ValueError("a SeedAtlas takes q [M, n], keys [M, W] and clearance [M]")
+        if len(self.q) == 0:
+            raise ValueError("the atlas is empty: no configuration passed the clearance filter")
+        self.count, self.width = int(self.keys.shape[0]), int(self.keys.shape[1])
+        self.d_q = self.d_keys = None
+        if device is not None:
+            self.upload(device)
+
+    def upload(self, device):
+        """Copy q and the component-major keys to `device` (once; a later call moves them)."""
+        self.d_q = torch.from_numpy(self.q).to(device)
+        self.d_keys = torch.from_numpy(np.array(self.keys.T, order="C")).to(device)
+        return self
+
+    @classmethod
+    def from_configurations(cls, problem, q, clearance_mode="nodes", clear_tol=1e-4, keep_clear_only=False, obstacles=None):
+        """The atlas of the caller's own rows q [M, n] -- the answers of an earlier batch, say -- for the AnchoredProblem
+        `problem`: keys from its robot graph's realization (base.seed_points, the goal rows), clearance from
+        candidate_clearance_host(q, clearance_mode, obstacles).  keep_clear_only: keep the rows with clearance >=
+        -clear_tol only (the default keeps every row).  Uploaded unless the problem is host-only."""
+        q = np.atleast_2d(np.asarray(q, dtype=np.float64))
+        if q.ndim != 2 or q.shape[1] != problem.robot.n:
+            raise ValueError(f"q must have shape [M, {problem.robot.n}], got {list(q.shape)}")
+        if not clear_tol > 0:
+            raise ValueError("clear_tol must be positive")
+        rows = 8192      # per pass: the mirrors form [rows, links, obstacles, 3] arrays
+        cl = np.concatenate([problem.candidate_clearance_host(q[s:s + rows], clearance_mode, obstacles) for s in range(0, len(q), rows)])
+        if keep_clear_only:
+            with np.errstate(invalid="ignore"):
+                keep = cl >= -clear_tol
+            q, cl = q[keep], cl[keep]
+        goal_rows = problem.base.goal_nodes
+        keys = np.concatenate([problem.base.seed_points(q[s:s + rows])[:, goal_rows].reshape(-1, 3 * len(goal_rows))
+                               for s in range(0, len(q), rows)]) if len(q) else np.zeros((0, 3 * len(goal_rows)))
+        return cls(q, keys, cl, None if problem.template is None else problem.template.device)
 
 
 def anchored_retry_failed(stop, pos_err, rot_err, clearance, pos_tol=0.01, rot_tol=0.01, clear_tol=1e-4):

@@ -912,6 +912,70 @@ int gik_anchored_ik_batch_retry_screened(const gik_template *anch, const gik_tem
                                          gik_stats *d_stats, double *d_q, double *d_pos_err, double *d_rot_err,
                                          double *d_clearance, int32_t *d_attempt, void *stream);
 
+/* ---- goal-aware seeds from a configuration atlas (opt-in) --------------------------------------------
+ * Every other start point -- bound smoothing + MDS, a draw inside the limits, a draw around d_q_init -- ignores the goal.
+ * An atlas is a table of M joint configurations that are clear of the room, each with its KEY: the positions its end
+ * effector's goal nodes take.  A goal starts from the clear configuration whose key lies nearest to its own.
+ *
+ * key of a configuration q  :=  rows goal_node[g] of the robot graph's realization of q (gik_seed_batch), g over the live
+ *                               goal nodes: p_e and q_e for a pose goal (W = 6), p_e alone for a position goal (W = 3).
+ * key of a goal pose T      :=  the same nodes as the goal puts them: p_e = T[:3, 3], q_e = p_e + axis_length * T[:3, 2],
+ *                               one rounded product and one rounded sum per component.
+ * d(goal, row m)            :=  (...((t0 t0 + t1 t1) + t2 t2) ... + t_{W-1} t_{W-1}), t_c = goal key[c] - d_atlas_keys[c][m]:
+ *                               every difference, product and sum rounded on its own, in this order.
+ * d_atlas_keys [W][M] is component-major; d_atlas_q [M][n] holds the rows' joint angles.  The library keeps neither.
+ *
+ * gik_atlas_nearest: for compact slot r -- goal d_idx[r], or r where d_idx is NULL -- the K (1 .. 64) rows with the
+ *   smallest (d, m) in lexicographic order, ascending, into d_nbr [count][K] int32 and, where given, their d into d_dist
+ *   [count][K].  A NaN or infinite d is never listed; where fewer than K rows are listed the rest is -1 / +infinity.
+ *   `base` is the robot graph's template with its pipeline attached: 3-D, one end effector, pose goals or (W = 3) a
+ *   position goal.  atlas_nearest_host is the numpy mirror, equal in the index and in the bits of d.
+ * gik_anchored_atlas_seeds: the screened seed step (gik_anchored_retry_seeds_screened) with the atlas as its candidate
+ *   source: candidate c (0 .. candidates - 1) of slot r, goal g, is row d_nbr[g * nbr_stride + first + c] of d_atlas_q --
+ *   d_nbr is indexed by GOAL, [B][nbr_stride], what gik_atlas_nearest writes with a NULL d_idx.  A row of -1 is a NaN
+ *   candidate: it is measured as NaN and never picked unless every candidate is one, and then that goal alone gets NaN
+ *   angles.  Realization, clearance (clearance_mode, half-spaces, the goal's scene), the pick and every output are the
+ *   screened step's.  With candidates = 1 and first = 0 it writes the nearest row's angles.
+ *   d_ws: gik_anchored_atlas_seeds_ws_bytes(anch, base, count, candidates) bytes, 8-byte aligned.
+ * gik_anchored_ik_batch_atlas: gik_anchored_ik_batch_retry_screened with the atlas in place of the random draws.  One
+ *   gik_atlas_nearest launch over all B goals with K = (opts->retries + 1) * candidates.  Attempt 0 starts from the pick
+ *   among ranks [0, candidates) where d_q_init is NULL (the seeded path, with or without scenes), from d_q_init
+ *   otherwise; restart a >= 1 of a failed goal starts from the pick among ranks [a * candidates, (a + 1) * candidates).
+ *   Select, merge and the one count copy per attempt are the restart loop's.  A goal with d_attempt[g] = a holds what
+ *   gik_anchored_ik_batch_seeded returns for it alone from that pick.  opts->seed, d_q_lo and d_q_hi are not read.
+ *   d_ws: gik_anchored_ik_batch_atlas_ws_bytes(anch, base, B, candidates, opts->retries) bytes, 8-byte aligned: the
+ *   workspace of the scenes entry with the neighbour table, the attempt-0 seeds, the noted rows and the screened
+ *   step's arrays behind it.
+ * gik_anchored_atlas_picks: after gik_anchored_ik_batch_atlas on the same stream, workspace, B, candidates and retries:
+ *   d_atlas_pick [B] int32, the atlas row the answer each goal holds started from; -1 where it started from d_q_init.
+ * Refused, with a message, before anything is queued: what the siblings refuse (the handle pair, a base that cannot be
+ *   seeded, a scene set, a clearance_mode, tolerances that are not positive, a capturing stream); a base template that
+ *   is planar, has more than one end effector or an inert goal slot other than a position goal's; K outside 1 .. 64;
+ *   for gik_anchored_ik_batch_atlas K > atlas_count and opts->spread != 0; count * K beyond INT_MAX; an atlas_count
+ *   below 1 or above 2^30; null atlas arrays; first < 0 or first + candidates > nbr_stride; a null or misaligned
+ *   workspace.  count / B == 0 returns 0. */
+#define GIK_ATLAS_MAX_NEIGHBOURS 64      /* K of gik_atlas_nearest: 1 .. 64 */
+int gik_atlas_nearest(const gik_template *base, const double *d_atlas_keys, int atlas_count, const double *d_T_goal,
+                      const int32_t *d_idx /* may be NULL */, int count, int K, int32_t *d_nbr,
+                      double *d_dist /* may be NULL */, void *stream);
+size_t gik_anchored_atlas_seeds_ws_bytes(const gik_template *anch, const gik_template *base, int count, int candidates);
+int gik_anchored_atlas_seeds(const gik_template *anch, const gik_template *base, const double *d_atlas_q, int atlas_count,
+                             const double *d_T_goal, const int32_t *d_idx /* may be NULL */, int count,
+                             const int32_t *d_nbr, int nbr_stride, int first, int candidates, int clearance_mode,
+                             double clear_tol, const gik_scene_set *scenes /* may be NULL */, void *d_ws, double *d_T_out,
+                             double *d_q_out, int32_t *d_pick /* may be NULL */,
+                             double *d_pick_clearance /* may be NULL */, void *stream);
+size_t gik_anchored_ik_batch_atlas_ws_bytes(const gik_template *anch, const gik_template *base, int B, int candidates,
+                                            int retries);
+int gik_anchored_ik_batch_atlas(const gik_template *anch, const gik_template *base, const double *d_T_goal,
+                                const double *d_q_init /* may be NULL */, int B, const gik_anchored_retry_opts *opts,
+                                int candidates, const double *d_atlas_keys, const double *d_atlas_q, int atlas_count,
+                                const gik_scene_set *scenes /* may be NULL */, void *d_ws, double *d_Y_full,
+                                gik_stats *d_stats, double *d_q, double *d_pos_err, double *d_rot_err,
+                                double *d_clearance, int32_t *d_attempt, void *stream);
+int gik_anchored_atlas_picks(const gik_template *anch, const gik_template *base, int B, int candidates, int retries,
+                             const void *d_ws, const int32_t *d_attempt, int32_t *d_atlas_pick, void *stream);
+
 /* Duration (ms, HIP events on the call's stream) of the anchored solve kernel inside the most
  * recent gik_anchored_ik_batch / gik_anchored_ik_batch_seeded on this handle; waits for it.  < 0 if there was none. */
 double gik_anchored_last_solve_ms(const gik_template *anch);
