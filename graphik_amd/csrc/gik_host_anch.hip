@@ -3,6 +3,9 @@
 // solve / recover path only through the library's exports and the helpers of gik_handle.h (gik_anchored_attach_links is
 // creation and lives there).  It launches the plain kernels of gik_retry.hip.h, gik_atlas.hip.h, gik_anch_seed.hip.h and
 // gik_anch_glue.hip.h by their prototypes: no device code is compiled here, and no solve kernel's header is seen.
+// Written once: a kernel launch (launch), the refusal pair of a workspace (workspace_refusal), one anchored solve
+// (anchored_attempt), the screened seed step behind its two exports (screened_step_entry) and the restart driver behind the
+// four restart entries (anchored_restarts), which takes where the seeds come from as a value (SeedSource).
 
 #include "gik_handle.h"
 #include "gik_retry.hip.h"
@@ -17,31 +20,39 @@
 // doubles of one goal: a (K+1) x (K+1) pose per end effector
 static int pose_width(const gik_template *t) { return t->pc.n_ee * (t->f.K + 1) * (t->f.K + 1); }
 
+// one kernel launch of this unit: no dynamic LDS; 0, or -1 with the launch error as the message
+template <typename... Params, typename... Args>
+static int launch(void (*kernel)(Params...), dim3 grid, dim3 block, void *stream, const Args &...args) {
+  using gik::fail;
+  hipLaunchKernelGGL(kernel, grid, block, 0, (hipStream_t)stream, args...);
+  HIP_OK(hipGetLastError());
+  return 0;
+}
+
+// the refusal pair of a caller-owned workspace, under the entry's name e; size_query: the export that says how large it is
+static int workspace_refusal(const std::string &e, const void *d_ws, const char *size_query) {
+  if (!d_ws) return gik::fail(e + ": null workspace (" + size_query + ")");
+  if ((uintptr_t)d_ws % 8) return gik::fail(e + ": the workspace must be 8-byte aligned");
+  return 0;
+}
+
 // ---- restarts from random joint configurations (gik_retry.hip.h) --------------------------------------
 // The three launches behind gik_retry_* and gik_anchored_retry_*.  Those exports make their refusals and fill the arguments,
 // in the order of the structs; the plain ones have no clearance (null pointers: +inf, and any positive clear_tol), no centre
 // and spread 0.  t gives the grid (the anchored calls: the base template).
 static int retry_select_launch(const gik::RetrySelectArgs &a, void *stream) {
   using namespace gik;
-  hipLaunchKernelGGL(retry_select_kernel, dim3((a.B + RETRY_WAVE - 1) / RETRY_WAVE), dim3(RETRY_WAVE), 0, (hipStream_t)stream, a);
-  HIP_OK(hipGetLastError());
-  return 0;
+  return launch(retry_select_kernel, dim3((a.B + RETRY_WAVE - 1) / RETRY_WAVE), dim3(RETRY_WAVE), stream, a);
 }
 
 static int retry_grid(const gik_template *t, int count) { return std::min(count, t->f.n_cu * 8); }
 
 static int retry_seed_launch(const gik_template *t, const gik::RetrySeedArgs &a, void *stream) {
-  using namespace gik;
-  hipLaunchKernelGGL(retry_seed_kernel, dim3(retry_grid(t, a.count)), dim3(RETRY_WAVE), 0, (hipStream_t)stream, a);
-  HIP_OK(hipGetLastError());
-  return 0;
+  return launch(gik::retry_seed_kernel, dim3(retry_grid(t, a.count)), dim3(gik::RETRY_WAVE), stream, a);
 }
 
 static int retry_merge_launch(const gik_template *t, const gik::RetryMergeArgs &a, void *stream) {
-  using namespace gik;
-  hipLaunchKernelGGL(retry_merge_kernel, dim3(retry_grid(t, a.count)), dim3(RETRY_WAVE), 0, (hipStream_t)stream, a);
-  HIP_OK(hipGetLastError());
-  return 0;
+  return launch(gik::retry_merge_kernel, dim3(retry_grid(t, a.count)), dim3(gik::RETRY_WAVE), stream, a);
 }
 
 // gik_retry_select and, with a clearance in the rule, gik_anchored_retry_select, which says its name (e) in every message.
@@ -141,8 +152,7 @@ int gik_ik_batch_retry(const gik_template *t, const double *d_T_goal, const doub
     if (!opts->d_q_lo || !opts->d_q_hi)
       return fail("gik_ik_batch_retry: null joint limits (opts->d_q_lo / d_q_hi, [n] each, are what the seeds are drawn from)");
     if (!(opts->pos_tol > 0.0) || !(opts->rot_tol > 0.0)) return fail("gik_ik_batch_retry: pos_tol and rot_tol must be positive");
-    if (!d_ws && B > 0) return fail("gik_ik_batch_retry: null workspace (gik_retry_ws_bytes)");
-    if ((uintptr_t)d_ws % 8) return fail("gik_ik_batch_retry: the workspace must be 8-byte aligned");
+    if ((d_ws || B > 0) && workspace_refusal("gik_ik_batch_retry", d_ws, "gik_retry_ws_bytes")) return -1;      // (B == 0: may be null)
   }
   if (refuse_capture("gik_ik_batch_retry", stream)) return -1;
   if (B == 0) return 0;
@@ -233,12 +243,8 @@ static int anchored_clearance_launch(const gik_template *anch, const double *d_Y
   c.n_node = anch->n_clear;
   c.n_obs = scenes ? 0 : anch->an.n_obs;
   const dim3 grid(std::min(B, anch->f.n_cu * 32));
-  if (scenes)
-    hipLaunchKernelGGL(anch_clearance_scene_kernel, grid, dim3(WAVE), 0, (hipStream_t)stream, c, scene_args(scenes));
-  else
-    hipLaunchKernelGGL(anch_clearance_kernel, grid, dim3(WAVE), 0, (hipStream_t)stream, c);
-  HIP_OK(hipGetLastError());
-  return 0;
+  return scenes ? launch(anch_clearance_scene_kernel, grid, dim3(WAVE), stream, c, scene_args(scenes))
+                : launch(anch_clearance_kernel, grid, dim3(WAVE), stream, c);
 }
 
 // the same of whole links (gik_anchored_attach_links; gik_anch_seed.hip.h)
@@ -257,12 +263,8 @@ static int anchored_link_clearance_launch(const gik_template *anch, const double
   c.n_link = anch->n_link;
   c.n_obs = scenes ? 0 : anch->an.n_obs;
   const dim3 grid(std::min(B, anch->f.n_cu * 32));
-  if (scenes)
-    hipLaunchKernelGGL(anch_link_clearance_scene_kernel, grid, dim3(WAVE), 0, (hipStream_t)stream, c, scene_args(scenes));
-  else
-    hipLaunchKernelGGL(anch_link_clearance_kernel, grid, dim3(WAVE), 0, (hipStream_t)stream, c);
-  HIP_OK(hipGetLastError());
-  return 0;
+  return scenes ? launch(anch_link_clearance_scene_kernel, grid, dim3(WAVE), stream, c, scene_args(scenes))
+                : launch(anch_link_clearance_kernel, grid, dim3(WAVE), stream, c);
 }
 
 // link against link (gik_anchored_attach_self_pairs; gik_anch_seed.hip.h): up to 16 pairs four goals share a wavefront.
@@ -283,9 +285,7 @@ static int anchored_self_clearance_launch(const gik_template *anch, const double
   c.n_pair = anch->n_self;
   c.merge = merge ? 1 : 0;
   const int waves = c.n_pair <= ANCH_SELF_ROW ? (B + 3) / 4 : B;
-  hipLaunchKernelGGL(anch_self_clearance_kernel, dim3(std::min(waves, anch->f.n_cu * 32)), dim3(WAVE), 0, (hipStream_t)stream, c);
-  HIP_OK(hipGetLastError());
-  return 0;
+  return launch(anch_self_clearance_kernel, dim3(std::min(waves, anch->f.n_cu * 32)), dim3(WAVE), stream, c);
 }
 
 // against the half-spaces of gik_anchored_attach_halfspaces (the handle has some): the masked nodes with their margins, or
@@ -305,9 +305,7 @@ static int anchored_half_clearance_launch(const gik_template *anch, const double
   c.n_item = links ? anch->n_link : anch->n_clear;
   c.n_half = anch->n_half;
   c.merge = merge ? 1 : 0;
-  hipLaunchKernelGGL(anch_half_clearance_kernel, dim3(std::min(B, anch->f.n_cu * 32)), dim3(WAVE), 0, (hipStream_t)stream, c);
-  HIP_OK(hipGetLastError());
-  return 0;
+  return launch(anch_half_clearance_kernel, dim3(std::min(B, anch->f.n_cu * 32)), dim3(WAVE), stream, c);
 }
 
 // on a handle with half-spaces every clearance the library reports is the minimum of the spheres' and theirs: the merge
@@ -339,10 +337,7 @@ static int anchored_seed_launch(const gik_template *anch, const gik_template *ba
   if (rc) return rc;
   const AnchGlueArgs g = anch_glue_args(anch, d_T_goal, B, w.Y_full0, Y_free, goal, nullptr);
   const size_t n = (size_t)B * ((size_t)g.Nf + (size_t)g.n_goal) * 3;
-  hipLaunchKernelGGL(anch_scatter_kernel, dim3((unsigned)((n + ANCH_SCATTER_NT - 1) / ANCH_SCATTER_NT)), dim3(ANCH_SCATTER_NT),
-                     0, (hipStream_t)stream, g);
-  HIP_OK(hipGetLastError());
-  return 0;
+  return launch(anch_scatter_kernel, dim3((unsigned)((n + ANCH_SCATTER_NT - 1) / ANCH_SCATTER_NT)), dim3(ANCH_SCATTER_NT), stream, g);
 }
 
 // One anchored solve on checked arguments, B > 0: what every solve entry and every restart queues.  The start point, cold
@@ -366,8 +361,7 @@ static int anchored_attempt(const gik_template *anch, const gik_template *base, 
     if (rc) return rc;
     g = anch_glue_args(anch, d_T_goal, B, w.Y_full0, w.Y_free, w.goal, d_Y_full);
     // ... mapped onto the world frame by its anchors; free rows = anchored start point
-    hipLaunchKernelGGL(anch_init_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, g);
-    HIP_OK(hipGetLastError());
+    if (launch(anch_init_kernel, dim3((B + 63) / 64), dim3(64), stream, g)) return -1;
   }
   // timing events around the solve (diagnostics only; created with the handle).  The pair is
   // recorded under a lock so that gik_anchored_last_solve_ms never reads a half-recorded pair;
@@ -384,8 +378,7 @@ static int anchored_attempt(const gik_template *anch, const gik_template *base, 
     std::lock_guard<std::mutex> lock(ma->ev_mutex);
     (void)hipEventRecord(ma->ev_solve1, (hipStream_t)stream);
   }
-  hipLaunchKernelGGL(anch_gather_kernel, dim3((g.B + 63) / 64), dim3(64), 0, (hipStream_t)stream, g);
-  HIP_OK(hipGetLastError());
+  if (launch(anch_gather_kernel, dim3((g.B + 63) / 64), dim3(64), stream, g)) return -1;
   rc = gik_recover_batch(base, g.Y_full_out, g.T_goal, g.B, d_q, d_pos_err, d_rot_err, stream);
   if (rc || !d_clearance) return rc;
   return anchored_mode_clearance_launch(anch, g.Y_full_out, g.B, d_clearance, mode, stream, scenes);
@@ -578,11 +571,10 @@ static int anchored_sweep_impl(const char *entry, bool two_outputs, const gik_te
   ia.pose_w = pose_width(base);
   const size_t nt = (size_t)M * ((size_t)ia.n + (size_t)ia.pose_w);
   if ((nt + ANCH_SCATTER_NT - 1) / ANCH_SCATTER_NT > (size_t)INT_MAX) return fail(e + ": the batch is too large");
-  hipLaunchKernelGGL(anch_sweep_interp_kernel, dim3((unsigned)((nt + ANCH_SCATTER_NT - 1) / ANCH_SCATTER_NT)),
-                     dim3(ANCH_SCATTER_NT), 0, (hipStream_t)stream, ia);
-  HIP_OK(hipGetLastError());
+  const dim3 interp_grid((unsigned)((nt + ANCH_SCATTER_NT - 1) / ANCH_SCATTER_NT));
+  int rc = launch(anch_sweep_interp_kernel, interp_grid, dim3(ANCH_SCATTER_NT), stream, ia);
   // the realization of every sample: seed_kernel's joint-frame walk on the robot graph (its targets go unread)
-  int rc = gik_seed_batch(base, w.T, w.q, M, w.targets, w.Y, stream);
+  if (!rc) rc = gik_seed_batch(base, w.T, w.q, M, w.targets, w.Y, stream);
   if (rc) return rc;
   for (int k = 0; k < 2; ++k) {      // (one stream: the second clearance overwrites w.cl behind the first minimum)
     double *out = k == 0 ? d_link_out : d_self_out;
@@ -596,9 +588,7 @@ static int anchored_sweep_impl(const char *entry, bool two_outputs, const gik_te
     ma.clearance = out;
     ma.B = B;
     ma.S = samples;
-    hipLaunchKernelGGL(anch_sweep_min_kernel, dim3((B + ANCH_SCATTER_NT - 1) / ANCH_SCATTER_NT), dim3(ANCH_SCATTER_NT), 0,
-                       (hipStream_t)stream, ma);
-    HIP_OK(hipGetLastError());
+    if (launch(anch_sweep_min_kernel, dim3((B + ANCH_SCATTER_NT - 1) / ANCH_SCATTER_NT), dim3(ANCH_SCATTER_NT), stream, ma)) return -1;
   }
   return 0;
 }
@@ -708,17 +698,17 @@ static int screened_seed_launch(const gik_template *anch, const gik_template *ba
   using namespace gik;
   const int M = a.count * candidates;
   const int32_t *goal_ids = scenes ? scenes->d_scene_id : nullptr;
+  int rc = 0;
   if (atlas) {
     const AtlasCandidateArgs ca = {a.T_goal, a.idx, atlas->q, atlas->nbr, goal_ids, a.T_out, w.T, w.q, w.ids,
                                    a.count, a.pose_w, a.n, candidates, atlas->first, atlas->stride, atlas->M};
-    hipLaunchKernelGGL(atlas_candidate_kernel, dim3(retry_grid(base, a.count)), dim3(ATLAS_WAVE), 0, (hipStream_t)stream, ca);
+    rc = launch(atlas_candidate_kernel, dim3(retry_grid(base, a.count)), dim3(ATLAS_WAVE), stream, ca);
   } else {
     const RetryCandidateArgs ca = {a.T_goal, a.idx, a.q_lo, a.q_hi, a.q_center, goal_ids, a.T_out, w.T, w.q, w.ids,
                                    a.spread, a.seed, a.count, a.pose_w, a.n, a.attempt, candidates};
-    hipLaunchKernelGGL(retry_candidate_kernel, dim3(retry_grid(base, a.count)), dim3(RETRY_WAVE), 0, (hipStream_t)stream, ca);
+    rc = launch(retry_candidate_kernel, dim3(retry_grid(base, a.count)), dim3(RETRY_WAVE), stream, ca);
   }
-  HIP_OK(hipGetLastError());
-  int rc = gik_seed_batch(base, w.T, w.q, M, w.targets, w.Y, stream);
+  if (!rc) rc = gik_seed_batch(base, w.T, w.q, M, w.targets, w.Y, stream);
   if (rc) return rc;
   gik_scene_set tiled;
   if (scenes) {
@@ -727,15 +717,37 @@ static int screened_seed_launch(const gik_template *anch, const gik_template *ba
   }
   if ((rc = anchored_mode_clearance_launch(anch, w.Y, M, w.cl, mode, stream, scenes ? &tiled : nullptr))) return rc;
   const RetryPickArgs pa = {w.cl, w.q, a.q_out, d_pick ? d_pick : w.pick, d_pick_clearance, clear_tol, a.count, a.n, candidates};
-  hipLaunchKernelGGL(retry_pick_kernel, dim3(retry_grid(base, a.count)), dim3(RETRY_WAVE), 0, (hipStream_t)stream, pa);
-  HIP_OK(hipGetLastError());
-  if (atlas && atlas->note) {
-    const AtlasNoteArgs na = {a.idx, atlas->nbr, pa.pick, atlas->note, a.count, atlas->first, atlas->stride};
-    hipLaunchKernelGGL(atlas_note_kernel, dim3((a.count + ATLAS_NOTE_NT - 1) / ATLAS_NOTE_NT), dim3(ATLAS_NOTE_NT), 0,
-                       (hipStream_t)stream, na);
-    HIP_OK(hipGetLastError());
-  }
-  return 0;
+  rc = launch(retry_pick_kernel, dim3(retry_grid(base, a.count)), dim3(RETRY_WAVE), stream, pa);
+  if (rc || !atlas || !atlas->note) return rc;
+  // the atlas row each slot's pick names, by goal
+  const AtlasNoteArgs na = {a.idx, atlas->nbr, pa.pick, atlas->note, a.count, atlas->first, atlas->stride};
+  return launch(atlas_note_kernel, dim3((a.count + ATLAS_NOTE_NT - 1) / ATLAS_NOTE_NT), dim3(ATLAS_NOTE_NT), stream, na);
+}
+
+// The two exports of that step, gik_anchored_retry_seeds_screened and gik_anchored_atlas_seeds: the refusals they share --
+// the pair, the scene set, the mode; behind own_fault(), the entry's own in its order (what is wrong, or nothing), the
+// capture, the workspace and the buffers -- and the launch.  a: the step's arguments but for pose_w and n, filled here.
+template <typename OwnFault>
+static int screened_step_entry(const char *entry, const char *size_query, const gik_template *anch, const gik_template *base,
+                               gik::RetrySeedArgs a, int candidates, int mode, double clear_tol, const gik_scene_set *scenes,
+                               void *d_ws, int32_t *d_pick, double *d_pick_clearance, void *stream, const AtlasSource *atlas,
+                               OwnFault own_fault) {
+  using namespace gik;
+  const std::string e(entry);
+  if (!anch || !base || a.count < 0) return fail(e + ": bad argument");
+  if (const std::string why = anchored_pair_fault(anch, base, PAIR_3D | PAIR_SEEDABLE); !why.empty()) return fail(e + ": " + why);
+  if (scenes && scene_refusal(entry, anch, scenes)) return -1;
+  if (clearance_mode_refusal(e, anch, mode)) return -1;
+  if (const std::string why = own_fault(); !why.empty()) return fail(e + ": " + why);
+  if (refuse_capture(entry, stream)) return -1;
+  if (a.count == 0) return 0;
+  if (workspace_refusal(e, d_ws, size_query)) return -1;
+  const int32_t *rows_of = atlas ? atlas->nbr : a.idx;      // (an atlas call may have no idx: slot r is goal r)
+  if (!a.T_goal || !rows_of || !a.T_out || !a.q_out) return fail(e + ": null buffer");
+  a.pose_w = pose_width(base);
+  a.n = base->pc.n_joints;
+  return screened_seed_launch(anch, base, a, candidates, mode, clear_tol, scenes, anch_screen_ws(anch, base, a.count, candidates, 0, d_ws),
+                              d_pick, d_pick_clearance, stream, atlas);
 }
 
 size_t gik_anchored_retry_seeds_screened_ws_bytes(const gik_template *anch, const gik_template *base, int count, int candidates) {
@@ -749,34 +761,38 @@ int gik_anchored_retry_seeds_screened(const gik_template *anch, const gik_templa
                                       const double *d_q_hi, const double *d_q_center, double spread, int candidates,
                                       int clearance_mode, double clear_tol, const gik_scene_set *scenes, void *d_ws,
                                       double *d_T_out, double *d_q_out, int32_t *d_pick, double *d_pick_clearance, void *stream) {
-  using namespace gik;
-  const char *entry = "gik_anchored_retry_seeds_screened";
-  const std::string e(entry);
-  if (!anch || !base || count < 0) return fail(e + ": bad argument");
-  if (const std::string why = anchored_pair_fault(anch, base, PAIR_3D | PAIR_SEEDABLE); !why.empty()) return fail(e + ": " + why);
-  if (scenes && scene_refusal(entry, anch, scenes)) return -1;
-  if (clearance_mode_refusal(e, anch, clearance_mode)) return -1;
-  if (attempt < 0 || attempt > 63) return fail(e + ": attempt must be within 0 .. 63");
-  if (!d_q_lo || !d_q_hi) return fail(e + ": null joint limits (d_q_lo / d_q_hi, [n] each, are required)");
-  if (!(spread >= 0.0)) return fail(e + ": spread must be at least 0");
-  if (spread > 0.0 && !d_q_center) return fail(e + ": spread > 0 needs the centre rows d_q_center [B][n]");
-  if (const std::string why = candidates_fault(candidates, count); !why.empty()) return fail(e + ": " + why);
-  if (!(clear_tol > 0.0)) return fail(e + ": clear_tol must be positive");
-  if (refuse_capture(entry, stream)) return -1;
-  if (count == 0) return 0;
-  if (!d_ws) return fail(e + ": null workspace (gik_anchored_retry_seeds_screened_ws_bytes)");
-  if ((uintptr_t)d_ws % 8) return fail(e + ": the workspace must be 8-byte aligned");
-  if (!d_T_goal || !d_idx || !d_T_out || !d_q_out) return fail(e + ": null buffer");
-  const RetrySeedArgs a = {d_T_goal, d_idx, d_q_lo, d_q_hi, d_q_center, d_T_out, d_q_out, spread, seed,
-                           count, pose_width(base), base->pc.n_joints, attempt};
-  return screened_seed_launch(anch, base, a, candidates, clearance_mode, clear_tol, scenes,
-                              anch_screen_ws(anch, base, count, candidates, 0, d_ws), d_pick, d_pick_clearance, stream);
+  const gik::RetrySeedArgs a = {d_T_goal, d_idx, d_q_lo, d_q_hi, d_q_center, d_T_out, d_q_out, spread, seed, count, 0, 0, attempt};
+  const auto own_fault = [&]() -> std::string {      // what this entry alone refuses, in its order
+    if (attempt < 0 || attempt > 63) return "attempt must be within 0 .. 63";
+    if (!d_q_lo || !d_q_hi) return "null joint limits (d_q_lo / d_q_hi, [n] each, are required)";
+    if (!(spread >= 0.0)) return "spread must be at least 0";
+    if (spread > 0.0 && !d_q_center) return "spread > 0 needs the centre rows d_q_center [B][n]";
+    if (const std::string why = candidates_fault(candidates, count); !why.empty()) return why;
+    if (!(clear_tol > 0.0)) return "clear_tol must be positive";
+    return std::string();
+  };
+  return screened_step_entry("gik_anchored_retry_seeds_screened", "gik_anchored_retry_seeds_screened_ws_bytes", anch, base, a,
+                             candidates, clearance_mode, clear_tol, scenes, d_ws, d_pick, d_pick_clearance, stream, nullptr,
+                             own_fault);
 }
 
-// gik_anchored_ik_batch_retry and, with a scene set, gik_anchored_ik_batch_retry_scenes: the scene goes through attempt 0,
-// every compact batch (its ids gathered into the workspace's last array) and every clearance.  screened:
-// gik_anchored_ik_batch_retry_screened, whose restarts take their seeds from the screened step with `candidates` draws per
-// slot (its arrays lie behind the ids in the workspace); not screened: one seed per slot, `candidates` is not read.
+// ---- the restart entries: each makes its own refusals, under its own name, and hands over to anchored_restarts ----
+// Where the restart seeds come from.  candidates 0: one blind draw per failed goal (retry_seed_kernel).  C > 0: the screened
+// step picks among C draws per failed goal or, with the tables of an atlas, among the C neighbour ranks [a C, (a + 1) C) of
+// restart a -- and a cold attempt 0 then starts from the pick among ranks [0, C).
+struct SeedSource {
+  int candidates;
+  const double *atlas_keys, *atlas_q;      // [W][M] and [M][n], or null: draws
+  int atlas_count, key_width;              // M, W
+  const char *size_query;                  // the export that sizes the entry's workspace
+};
+static int anchored_restarts(const char *entry, const gik_template *anch, const gik_template *base, const double *d_T_goal,
+                             const double *d_q_init, int B, const gik_anchored_retry_opts *opts, const gik_scene_set *scenes,
+                             const SeedSource &src, void *d_ws, double *d_Y_full, gik_stats *d_stats, double *d_q, double *d_pos_err,
+                             double *d_rot_err, double *d_clearance, int32_t *d_attempt, void *stream);
+
+// The refusals of gik_anchored_ik_batch_retry and, with a scene set, gik_anchored_ik_batch_retry_scenes; screened:
+// gik_anchored_ik_batch_retry_screened, `candidates` draws per slot (not screened: `candidates` is not read).
 static int anchored_retry_impl(const char *entry, const gik_template *anch, const gik_template *base, const double *d_T_goal,
                                const double *d_q_init, int B, const gik_anchored_retry_opts *opts, const gik_scene_set *scenes,
                                bool with_scenes, void *d_ws, double *d_Y_full, gik_stats *d_stats, double *d_q, double *d_pos_err,
@@ -789,7 +805,6 @@ static int anchored_retry_impl(const char *entry, const gik_template *anch, cons
   if (with_scenes && scene_refusal(entry, anch, scenes)) return -1;
   if (opts->retries < 0 || opts->retries > 63) return fail(e + ": retries must be within 0 .. 63");
   if (clearance_mode_refusal(e, anch, opts->clearance_mode)) return -1;
-  const int mode = opts->clearance_mode;
   if ((d_q_init || opts->retries > 0) && !base->seed_ok)
     return fail(e + ": the base graph cannot be seeded on the device: " + base->seed_why);
   if (opts->retries > 0) {
@@ -805,49 +820,10 @@ static int anchored_retry_impl(const char *entry, const gik_template *anch, cons
     if (const std::string why = candidates_fault(candidates, B); !why.empty()) return fail(e + ": " + why);
     if (!(opts->clear_tol > 0.0)) return fail(e + ": clear_tol must be positive");
   }
-  if (refuse_capture(entry, stream)) return -1;
-  if (B == 0) return 0;
-  if (!d_clearance || !d_attempt) return fail(e + ": null d_clearance or d_attempt");
-  if (!d_ws) return fail(e + (screened ? ": null workspace (gik_anchored_ik_batch_retry_screened_ws_bytes)" : ": null workspace (gik_anchored_retry_ws_bytes)"));
-  if ((uintptr_t)d_ws % 8) return fail(e + ": the workspace must be 8-byte aligned");
-  if (!d_T_goal || !d_Y_full || !d_stats || !d_q || !d_pos_err || !d_rot_err) return fail(e + ": null buffer");
-  hipStream_t s = (hipStream_t)stream;
-  const AnchRetryWs w = anch_retry_ws(anch, base, B, d_ws);
-  const bool local = opts->retries > 0 && opts->spread > 0.0;
-  const size_t n = (size_t)base->pc.n_joints;
-  // the centre of local mode is what attempt 0 started from; d_q_init may be d_q, which attempt 0 overwrites
-  if (local) HIP_OK(hipMemcpyAsync(w.q_center, d_q_init, (size_t)B * n * sizeof(double), hipMemcpyDeviceToDevice, s));
-  HIP_OK(hipMemsetAsync(d_attempt, 0, (size_t)B * sizeof(int32_t), s));
-  gik_scene_set compact;      // the scene set of a compact batch: its ids are gathered into w.ids
-  if (scenes) {
-    compact = *scenes;
-    if (scenes->d_scene_id) compact.d_scene_id = w.ids;
-  }
-  // link modes: the rule below is the same, the array it reads holds the clearance of whole links, or the minimum of
-  // that and the self clearance
-  const int rc = anchored_attempt(anch, base, d_T_goal, d_q_init, B, scenes, w.scratch, d_Y_full, d_stats, d_q, d_pos_err,
-                                  d_rot_err, d_clearance, mode, stream);
-  if (rc) return rc;
-  const RetryTol tol = {opts->pos_tol, opts->rot_tol, opts->clear_tol};
-  const RetrySelectArgs select = {d_stats, d_pos_err, d_rot_err, d_clearance, tol, w.idx, w.count, B};
-  const RetrySeedArgs seeds = {d_T_goal, w.idx, opts->d_q_lo, opts->d_q_hi, local ? w.q_center : nullptr, w.T, w.q_seed,
-                               local ? opts->spread : 0.0, opts->seed, 0, pose_width(base), base->pc.n_joints, 0};
-  const RetryMergeArgs merge = {w.idx, w.Y, w.stats, w.q, w.pos_err, w.rot_err, w.clearance,
-                                d_Y_full, d_stats, d_q, d_pos_err, d_rot_err, d_clearance, d_attempt, tol, 0, anch->full_N * 3, base->pc.n_joints, 0};
-  const AnchScreenWs sw = screened ? anch_screen_ws(anch, base, B, candidates, anch_screen_head(anch, base, B), d_ws) : AnchScreenWs();
-  const auto seed_step = [&](const RetrySeedArgs &a) {
-    return screened ? screened_seed_launch(anch, base, a, candidates, mode, opts->clear_tol, scenes, sw, nullptr, nullptr, stream)
-                    : retry_seed_launch(base, a, stream);
-  };
-  return retry_loop(entry, base, opts->retries, select, seeds, merge, stream, seed_step, [&](int count) {
-    if (scenes && scenes->d_scene_id) {
-      hipLaunchKernelGGL(scene_gather_kernel, dim3((count + ANCH_SCATTER_NT - 1) / ANCH_SCATTER_NT), dim3(ANCH_SCATTER_NT), 0, s,
-                         scenes->d_scene_id, w.idx, count, w.ids);
-      HIP_OK(hipGetLastError());
-    }
-    return anchored_attempt(anch, base, w.T, w.q_seed, count, scenes ? &compact : nullptr, w.scratch, w.Y, w.stats, w.q, w.pos_err,
-                            w.rot_err, w.clearance, mode, stream);
-  });
+  const SeedSource src = {screened ? candidates : 0, nullptr, nullptr, 0, 0,
+                          screened ? "gik_anchored_ik_batch_retry_screened_ws_bytes" : "gik_anchored_retry_ws_bytes"};
+  return anchored_restarts(entry, anch, base, d_T_goal, d_q_init, B, opts, scenes, src, d_ws, d_Y_full, d_stats, d_q, d_pos_err, d_rot_err,
+                           d_clearance, d_attempt, stream);
 }
 
 int gik_anchored_ik_batch_retry(const gik_template *anch, const gik_template *base, const double *d_T_goal,
@@ -906,9 +882,7 @@ static int atlas_nearest_launch(const gik_template *base, int W, const double *d
   using namespace gik;
   const AtlasNearestArgs a = {d_keys, d_T_goal, d_idx, d_nbr, d_dist, base->pc.ee_len[0], M, count, K, pose_width(base), W};
   const int groups = (count + ATLAS_GOALS - 1) / ATLAS_GOALS;
-  hipLaunchKernelGGL(atlas_nearest_kernel, dim3(std::min(groups, base->f.n_cu * 32)), dim3(ATLAS_WAVE), 0, (hipStream_t)stream, a);
-  HIP_OK(hipGetLastError());
-  return 0;
+  return launch(atlas_nearest_kernel, dim3(std::min(groups, base->f.n_cu * 32)), dim3(ATLAS_WAVE), stream, a);
 }
 
 int gik_atlas_nearest(const gik_template *base, const double *d_atlas_keys, int atlas_count, const double *d_T_goal,
@@ -936,29 +910,19 @@ int gik_anchored_atlas_seeds(const gik_template *anch, const gik_template *base,
                              int first, int candidates, int clearance_mode, double clear_tol, const gik_scene_set *scenes,
                              void *d_ws, double *d_T_out, double *d_q_out, int32_t *d_pick, double *d_pick_clearance,
                              void *stream) {
-  using namespace gik;
-  const char *entry = "gik_anchored_atlas_seeds";
-  const std::string e(entry);
-  if (!anch || !base || count < 0) return fail(e + ": bad argument");
-  if (const std::string why = anchored_pair_fault(anch, base, PAIR_3D | PAIR_SEEDABLE); !why.empty()) return fail(e + ": " + why);
-  if (scenes && scene_refusal(entry, anch, scenes)) return -1;
-  if (clearance_mode_refusal(e, anch, clearance_mode)) return -1;
-  if (const std::string why = candidates_fault(candidates, count); !why.empty()) return fail(e + ": " + why);
-  if (atlas_count < 1 || atlas_count > (1 << 30)) return fail(e + ": atlas_count must be within 1 .. 2^30");
-  if (first < 0 || nbr_stride < 1 || first > nbr_stride - candidates)
-    return fail(e + ": ranks first .. first + candidates - 1 must lie within 0 .. nbr_stride - 1");
-  if (!(clear_tol > 0.0)) return fail(e + ": clear_tol must be positive");
-  if (!d_atlas_q) return fail(e + ": null atlas (d_atlas_q [atlas_count][n] is required)");
-  if (refuse_capture(entry, stream)) return -1;
-  if (count == 0) return 0;
-  if (!d_ws) return fail(e + ": null workspace (gik_anchored_atlas_seeds_ws_bytes)");
-  if ((uintptr_t)d_ws % 8) return fail(e + ": the workspace must be 8-byte aligned");
-  if (!d_T_goal || !d_nbr || !d_T_out || !d_q_out) return fail(e + ": null buffer");
-  const RetrySeedArgs a = {d_T_goal, d_idx, nullptr, nullptr, nullptr, d_T_out, d_q_out, 0.0, 0,
-                           count, pose_width(base), base->pc.n_joints, 0};
-  const AtlasSource src = {d_atlas_q, d_nbr, atlas_count, nbr_stride, first, nullptr};
-  return screened_seed_launch(anch, base, a, candidates, clearance_mode, clear_tol, scenes,
-                              anch_screen_ws(anch, base, count, candidates, 0, d_ws), d_pick, d_pick_clearance, stream, &src);
+  const gik::RetrySeedArgs a = {d_T_goal, d_idx, nullptr, nullptr, nullptr, d_T_out, d_q_out, 0.0, 0, count, 0, 0, 0};
+  const AtlasSource rows = {d_atlas_q, d_nbr, atlas_count, nbr_stride, first, nullptr};
+  const auto own_fault = [&]() -> std::string {      // what this entry alone refuses, in its order
+    if (const std::string why = candidates_fault(candidates, count); !why.empty()) return why;
+    if (atlas_count < 1 || atlas_count > (1 << 30)) return "atlas_count must be within 1 .. 2^30";
+    if (first < 0 || nbr_stride < 1 || first > nbr_stride - candidates)
+      return "ranks first .. first + candidates - 1 must lie within 0 .. nbr_stride - 1";
+    if (!(clear_tol > 0.0)) return "clear_tol must be positive";
+    if (!d_atlas_q) return "null atlas (d_atlas_q [atlas_count][n] is required)";
+    return std::string();
+  };
+  return screened_step_entry("gik_anchored_atlas_seeds", "gik_anchored_atlas_seeds_ws_bytes", anch, base, a, candidates,
+                             clearance_mode, clear_tol, scenes, d_ws, d_pick, d_pick_clearance, stream, &rows, own_fault);
 }
 
 // the workspace of gik_anchored_ik_batch_atlas over d_ws (gik_plan.h), or with a null d_ws its size
@@ -982,6 +946,83 @@ size_t gik_anchored_ik_batch_atlas_ws_bytes(const gik_template *anch, const gik_
   return anch_atlas_ws(anch, base, B, candidates, retries, nullptr).bytes;
 }
 
+// The one restart driver, behind gik_anchored_ik_batch_retry, _retry_scenes, _retry_screened and _atlas, on arguments their
+// refusals have checked.  It ends the refusal sequence they share -- the capture, the empty batch, the outputs, the workspace,
+// the buffers -- and then queues, in this order: the centre copy of local mode; the memset of d_attempt; with an atlas the
+// memset of the noted rows (-1: no atlas row), the nearest launch over all goals and, cold, the pick among ranks [0, C) of
+// every goal (slot r is goal r); attempt 0; retry_loop.  A scene set goes through attempt 0, every compact batch (its ids
+// gathered into w.ids) and every clearance.  In the link modes the rule is the same: the array it reads holds the clearance
+// of whole links, or the minimum of that and the self clearance.
+static int anchored_restarts(const char *entry, const gik_template *anch, const gik_template *base, const double *d_T_goal,
+                             const double *d_q_init, int B, const gik_anchored_retry_opts *opts, const gik_scene_set *scenes,
+                             const SeedSource &src, void *d_ws, double *d_Y_full, gik_stats *d_stats, double *d_q, double *d_pos_err,
+                             double *d_rot_err, double *d_clearance, int32_t *d_attempt, void *stream) {
+  using namespace gik;
+  const std::string e(entry);
+  if (refuse_capture(entry, stream)) return -1;
+  if (B == 0) return 0;
+  if (!d_clearance || !d_attempt) return fail(e + ": null d_clearance or d_attempt");
+  if (workspace_refusal(e, d_ws, src.size_query)) return -1;
+  if (!d_T_goal || !d_Y_full || !d_stats || !d_q || !d_pos_err || !d_rot_err) return fail(e + ": null buffer");
+  hipStream_t s = (hipStream_t)stream;
+  const int mode = opts->clearance_mode, retries = opts->retries, C = src.candidates, n = base->pc.n_joints;
+  const bool atlas = src.atlas_q != nullptr, local = retries > 0 && opts->spread > 0.0;
+  // the workspace: the restart arrays; behind them the screened step's, with an atlas the neighbour table in between
+  const AnchRetryWs w = anch_retry_ws(anch, base, B, d_ws);
+  const AnchAtlasWs aw = atlas ? anch_atlas_ws(anch, base, B, C, retries, d_ws) : AnchAtlasWs();
+  const size_t screen_head = atlas ? aw.screen_head : anch_screen_head(anch, base, B);
+  const AnchScreenWs sw = C ? anch_screen_ws(anch, base, B, C, screen_head, d_ws) : AnchScreenWs();
+  gik_scene_set compact;      // the scene set of a compact batch: its ids are gathered into w.ids
+  if (scenes) {
+    compact = *scenes;
+    if (scenes->d_scene_id) compact.d_scene_id = w.ids;
+  }
+  const RetryTol tol = {opts->pos_tol, opts->rot_tol, opts->clear_tol};
+  const RetrySelectArgs select = {d_stats, d_pos_err, d_rot_err, d_clearance, tol, w.idx, w.count, B};
+  // (an atlas step reads none of the draws' fields: the limits, the centre, the spread, the seed)
+  const RetrySeedArgs seeds = {d_T_goal, w.idx, opts->d_q_lo, opts->d_q_hi, local ? w.q_center : nullptr, w.T, w.q_seed,
+                               local ? opts->spread : 0.0, opts->seed, 0, pose_width(base), n, 0};
+  const RetryMergeArgs merge = {w.idx, w.Y, w.stats, w.q, w.pos_err, w.rot_err, w.clearance,
+                                d_Y_full, d_stats, d_q, d_pos_err, d_rot_err, d_clearance, d_attempt, tol, 0, anch->full_N * 3, n, 0};
+  AtlasSource rows = {src.atlas_q, aw.nbr, src.atlas_count, (retries + 1) * C, 0, aw.rows};
+  const auto seed_step = [&](const RetrySeedArgs &a) {      // the seeds of attempt a.attempt; atlas: from ranks [a C, (a + 1) C)
+    if (!C) return retry_seed_launch(base, a, stream);
+    if (atlas) {
+      rows.first = a.attempt * C;
+      rows.note = aw.rows + (size_t)a.attempt * (size_t)B;
+    }
+    return screened_seed_launch(anch, base, a, C, mode, opts->clear_tol, scenes, sw, nullptr, nullptr, stream, atlas ? &rows : nullptr);
+  };
+  // the centre of local mode is what attempt 0 started from; d_q_init may be d_q, which attempt 0 overwrites
+  if (local) HIP_OK(hipMemcpyAsync(w.q_center, d_q_init, (size_t)B * (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
+  HIP_OK(hipMemsetAsync(d_attempt, 0, (size_t)B * sizeof(int32_t), s));
+  int rc = 0;
+  if (atlas) {
+    HIP_OK(hipMemsetAsync(aw.rows, 0xFF, (size_t)B * (size_t)(retries + 1) * sizeof(int32_t), s));
+    rc = atlas_nearest_launch(base, src.key_width, src.atlas_keys, src.atlas_count, d_T_goal, nullptr, B, rows.stride, aw.nbr, nullptr,
+                              stream);
+    if (!rc && !d_q_init) {
+      RetrySeedArgs all = seeds;
+      all.idx = nullptr;
+      all.q_out = aw.q0;
+      all.count = B;
+      rc = seed_step(all);
+      d_q_init = aw.q0;
+    }
+  }
+  if (!rc) rc = anchored_attempt(anch, base, d_T_goal, d_q_init, B, scenes, w.scratch, d_Y_full, d_stats, d_q, d_pos_err, d_rot_err,
+                                 d_clearance, mode, stream);
+  if (rc) return rc;
+  return retry_loop(entry, base, retries, select, seeds, merge, stream, seed_step, [&](int count) {
+    if (scenes && scenes->d_scene_id) {      // the compact batch's scene ids
+      const dim3 grid((count + ANCH_SCATTER_NT - 1) / ANCH_SCATTER_NT);
+      if (launch(scene_gather_kernel, grid, dim3(ANCH_SCATTER_NT), stream, scenes->d_scene_id, w.idx, count, w.ids)) return -1;
+    }
+    return anchored_attempt(anch, base, w.T, w.q_seed, count, scenes ? &compact : nullptr, w.scratch, w.Y, w.stats, w.q, w.pos_err,
+                            w.rot_err, w.clearance, mode, stream);
+  });
+}
+
 int gik_anchored_ik_batch_atlas(const gik_template *anch, const gik_template *base, const double *d_T_goal, const double *d_q_init,
                                 int B, const gik_anchored_retry_opts *opts, int candidates, const double *d_atlas_keys,
                                 const double *d_atlas_q, int atlas_count, const gik_scene_set *scenes, void *d_ws, double *d_Y_full,
@@ -995,7 +1036,7 @@ int gik_anchored_ik_batch_atlas(const gik_template *anch, const gik_template *ba
   if (const std::string why = anchored_pair_fault(anch, base, PAIR_3D | PAIR_SEEDABLE); !why.empty()) return fail(e + ": " + why);
   if (scenes && scene_refusal(entry, anch, scenes)) return -1;
   if (clearance_mode_refusal(e, anch, opts->clearance_mode)) return -1;
-  const int mode = opts->clearance_mode, retries = opts->retries;
+  const int retries = opts->retries;
   std::string why;
   const int W = atlas_key_width(base, &why);
   if (!W) return fail(e + ": " + why);
@@ -1007,55 +1048,9 @@ int gik_anchored_ik_batch_atlas(const gik_template *anch, const gik_template *ba
   if (!(opts->clear_tol > 0.0)) return fail(e + ": clear_tol must be positive");
   if (opts->spread != 0.0) return fail(e + ": spread must be 0 (the restarts start from atlas rows, not from draws around d_q_init)");
   if (!d_atlas_keys || !d_atlas_q) return fail(e + ": null atlas (d_atlas_keys [W][atlas_count] and d_atlas_q [atlas_count][n] are required)");
-  if (refuse_capture(entry, stream)) return -1;
-  if (B == 0) return 0;
-  if (!d_clearance || !d_attempt) return fail(e + ": null d_clearance or d_attempt");
-  if (!d_ws) return fail(e + ": null workspace (gik_anchored_ik_batch_atlas_ws_bytes)");
-  if ((uintptr_t)d_ws % 8) return fail(e + ": the workspace must be 8-byte aligned");
-  if (!d_T_goal || !d_Y_full || !d_stats || !d_q || !d_pos_err || !d_rot_err) return fail(e + ": null buffer");
-  hipStream_t s = (hipStream_t)stream;
-  const AnchRetryWs w = anch_retry_ws(anch, base, B, d_ws);
-  const AnchAtlasWs aw = anch_atlas_ws(anch, base, B, candidates, retries, d_ws);
-  const AnchScreenWs sw = anch_screen_ws(anch, base, B, candidates, aw.screen_head, d_ws);
-  HIP_OK(hipMemsetAsync(d_attempt, 0, (size_t)B * sizeof(int32_t), s));
-  HIP_OK(hipMemsetAsync(aw.rows, 0xFF, (size_t)B * (size_t)(retries + 1) * sizeof(int32_t), s));      // (-1: no atlas row)
-  int rc = atlas_nearest_launch(base, W, d_atlas_keys, atlas_count, d_T_goal, nullptr, B, K, aw.nbr, nullptr, stream);
-  if (rc) return rc;
-  gik_scene_set compact;      // the scene set of a compact batch: its ids are gathered into w.ids
-  if (scenes) {
-    compact = *scenes;
-    if (scenes->d_scene_id) compact.d_scene_id = w.ids;
-  }
-  const RetrySeedArgs seeds = {d_T_goal, w.idx, nullptr, nullptr, nullptr, w.T, w.q_seed, 0.0, 0, 0, pose_width(base), base->pc.n_joints, 0};
-  AtlasSource src = {d_atlas_q, aw.nbr, atlas_count, K, 0, aw.rows};
-  if (!d_q_init) {      // attempt 0 from the pick among ranks [0, C) of every goal: slot r is goal r
-    RetrySeedArgs all = seeds;
-    all.idx = nullptr;
-    all.q_out = aw.q0;
-    all.count = B;
-    if ((rc = screened_seed_launch(anch, base, all, candidates, mode, opts->clear_tol, scenes, sw, nullptr, nullptr, stream, &src))) return rc;
-  }
-  rc = anchored_attempt(anch, base, d_T_goal, d_q_init ? d_q_init : aw.q0, B, scenes, w.scratch, d_Y_full, d_stats, d_q, d_pos_err,
-                        d_rot_err, d_clearance, mode, stream);
-  if (rc) return rc;
-  const RetryTol tol = {opts->pos_tol, opts->rot_tol, opts->clear_tol};
-  const RetrySelectArgs select = {d_stats, d_pos_err, d_rot_err, d_clearance, tol, w.idx, w.count, B};
-  const RetryMergeArgs merge = {w.idx, w.Y, w.stats, w.q, w.pos_err, w.rot_err, w.clearance,
-                                d_Y_full, d_stats, d_q, d_pos_err, d_rot_err, d_clearance, d_attempt, tol, 0, anch->full_N * 3, base->pc.n_joints, 0};
-  const auto seed_step = [&](const RetrySeedArgs &a) {      // ranks [a C, (a + 1) C) of the failed goals
-    src.first = a.attempt * candidates;
-    src.note = aw.rows + (size_t)a.attempt * (size_t)B;
-    return screened_seed_launch(anch, base, a, candidates, mode, opts->clear_tol, scenes, sw, nullptr, nullptr, stream, &src);
-  };
-  return retry_loop(entry, base, retries, select, seeds, merge, stream, seed_step, [&](int count) {
-    if (scenes && scenes->d_scene_id) {
-      hipLaunchKernelGGL(scene_gather_kernel, dim3((count + ANCH_SCATTER_NT - 1) / ANCH_SCATTER_NT), dim3(ANCH_SCATTER_NT), 0, s,
-                         scenes->d_scene_id, w.idx, count, w.ids);
-      HIP_OK(hipGetLastError());
-    }
-    return anchored_attempt(anch, base, w.T, w.q_seed, count, scenes ? &compact : nullptr, w.scratch, w.Y, w.stats, w.q, w.pos_err,
-                            w.rot_err, w.clearance, mode, stream);
-  });
+  const SeedSource src = {candidates, d_atlas_keys, d_atlas_q, atlas_count, W, "gik_anchored_ik_batch_atlas_ws_bytes"};
+  return anchored_restarts(entry, anch, base, d_T_goal, d_q_init, B, opts, scenes, src, d_ws, d_Y_full, d_stats, d_q, d_pos_err, d_rot_err,
+                           d_clearance, d_attempt, stream);
 }
 
 int gik_anchored_atlas_picks(const gik_template *anch, const gik_template *base, int B, int candidates, int retries, const void *d_ws,
@@ -1071,9 +1066,7 @@ int gik_anchored_atlas_picks(const gik_template *anch, const gik_template *base,
   if (!d_attempt || !d_atlas_pick) return fail(e + ": null buffer");
   const AnchAtlasWs aw = anch_atlas_ws(anch, base, B, candidates, retries, const_cast<void *>(d_ws));
   const AtlasKeptArgs a = {d_attempt, aw.rows, d_atlas_pick, B, retries + 1};
-  hipLaunchKernelGGL(atlas_kept_kernel, dim3((B + ATLAS_NOTE_NT - 1) / ATLAS_NOTE_NT), dim3(ATLAS_NOTE_NT), 0, (hipStream_t)stream, a);
-  HIP_OK(hipGetLastError());
-  return 0;
+  return launch(atlas_kept_kernel, dim3((B + ATLAS_NOTE_NT - 1) / ATLAS_NOTE_NT), dim3(ATLAS_NOTE_NT), stream, a);
 }
 
 double gik_anchored_last_solve_ms(const gik_template *anch) {

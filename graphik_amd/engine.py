@@ -6,6 +6,7 @@ of omega / psi_L / psi_U apply to each, and exposes batched cost / egrad / ehess
 trust-region solve on the GPU.  All array arguments are torch tensors on the HIP device
 (fp64, contiguous); numpy inputs are copied to the device for convenience.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -176,11 +177,53 @@ def check_clearance_mode(clearance_mode, has_links=True, has_self=True):
     return _ffi.CLEARANCE_MODES[clearance_mode]
 
 
-def restart_like(retries, clearance_mode, clearance=True, scenes=None):
-    """Does an anchored solve run on the restart entries (gik_anchored_ik_batch_retry[_scenes]) and their workspace
-    "retry_ws"?  With retries > 0; and in "links+self" with a clearance and neither restarts nor scenes, which is attempt
-    0 of that entry alone.  Every other solve runs on the scratch "ws"."""
-    return bool(retries) or (clearance_mode == "links+self" and bool(clearance) and scenes is None)
+def check_atlas_args(atlas, atlas_candidates, retries, retry_candidates, retry_spread, spread_first=False):
+    """The atlas keywords of an anchored solve (Template.anchored_ik; AnchoredProblem.solve, whose order is spread_first),
+    checked on the host before any device call: atlas_candidates within 1 .. 16, retry_candidates 1, no retry_spread,
+    (retries + 1) * atlas_candidates within 1 .. 64 and atlas.count.  Returns atlas_candidates as an int; ValueError otherwise."""
+    cand = check_retry_candidates(atlas_candidates, what="atlas_candidates")
+    spread = "atlas= with retry_spread > 0 is not supported: the restarts take atlas rows, not draws around q_init"
+    if spread_first and retry_spread > 0:
+        raise ValueError(spread)
+    if check_retry_candidates(retry_candidates) > 1:
+        raise ValueError("atlas= with retry_candidates > 1 is not supported: the restarts take atlas rows, not draws")
+    if retry_spread > 0:
+        raise ValueError(spread)
+    if int(retries) == retries and 0 <= int(retries) <= RETRY_MAX:
+        check_atlas_k((int(retries) + 1) * cand, atlas.count, "(retries + 1) * atlas_candidates")
+    return cand
+
+
+AnchoredCallPlan = collections.namedtuple("AnchoredCallPlan", "entry ws_query ws_ints args after restart")
+
+
+def anchored_call_plan(seeded, clearance, clearance_mode, scenes, retries, retry_candidates=1, atlas_candidates=None):
+    """The C entry of one Template.anchored_ik call from its checked keywords alone -- no tensor, no library call: seeded (a
+    q_init is given), clearance (as passed), clearance_mode (the word), scenes (a set is given), retries, retry_candidates,
+    atlas_candidates (None: no atlas).  Returns the entry's name; ws_query, the export that sizes its workspace, and ws_ints,
+    that query's integers behind (anch, base, B); args, the names of the entry's arguments between the goal poses and the
+    stream ("answer": the five answer pointers; "null": the seeded entry's clearance where `after` measures instead); after,
+    the clearance export to launch behind an entry that does not measure the call's clearance itself; restart: a restart
+    entry, whose workspace "retry_ws" holds the scratch "ws" too -- with retries > 0, with an atlas, and in "links+self"
+    with a clearance and neither restarts nor scenes, which is attempt 0 of gik_anchored_ik_batch_retry alone."""
+    def plan(entry, ws_query, ws_ints, middle, after=None):
+        restart = ws_query != "gik_anchored_ws_doubles"
+        args = ("q_init", "B", "opts", *middle, "ws", "answer", "clearance", "attempt") if restart else middle
+        return AnchoredCallPlan("gik_anchored_ik_batch" + entry, ws_query, ws_ints, args, after, restart)
+    if atlas_candidates is not None:
+        return plan("_atlas", "gik_anchored_ik_batch_atlas_ws_bytes", (atlas_candidates, int(retries)),
+                    ("candidates", "atlas_keys", "atlas_q", "atlas_count", "scenes"))
+    if retry_candidates > 1:      # (one entry with a nullable scene set)
+        return plan("_retry_screened", "gik_anchored_ik_batch_retry_screened_ws_bytes", (retry_candidates,), ("candidates", "scenes"))
+    if retries or (clearance_mode == "links+self" and clearance and not scenes):
+        return plan("_retry_scenes" if scenes else "_retry", "gik_anchored_retry_ws_bytes", (), ("scenes",) if scenes else ())
+    if scenes:      # one call: cold or seeded, the clearance of either mode behind it
+        return plan("_scenes", "gik_anchored_ws_doubles", (), ("q_init", "B", "scenes", "ws", "answer", "clearance", "mode"))
+    links = "gik_anchored_link_clearance" if clearance and clearance_mode == "links" else None
+    if not seeded:
+        return plan("", "gik_anchored_ws_doubles", (), ("B", "ws", "answer"), links or ("gik_anchored_clearance" if clearance else None))
+    # (the seeded call measures the joint points itself; whole links are measured after it)
+    return plan("_seeded", "gik_anchored_ws_doubles", (), ("q_init", "B", "ws", "answer", "null" if links else "clearance"), links)
 
 
 def pack_scenes(scenes, stride=None):
@@ -681,10 +724,12 @@ class Template:
         nbytes = int(self.lib.gik_anchored_retry_ws_bytes(self._h, base._h, B))
         return (nbytes + 7) // 8 * 8 + 4 * B if scenes else nbytes
 
-    def anchored_retry_screened_ws_bytes(self, base, B, candidates):
-        """Bytes of the restart workspace ("retry_ws") of one anchored_ik call of B goals with retry_candidates > 1
-        (gik_anchored_ik_batch_retry_screened_ws_bytes), with or without scenes."""
-        return int(self.lib.gik_anchored_ik_batch_retry_screened_ws_bytes(self._h, base._h, B, candidates))
+    def anchored_plan_ws_bytes(self, base, B, plan):
+        """Bytes of the workspace of one anchored_ik call of B goals on `plan`: "retry_ws" if plan.restart, else "ws"."""
+        if plan.ws_query == "gik_anchored_retry_ws_bytes":
+            return self.anchored_retry_ws_bytes(base, B, scenes="scenes" in plan.args)
+        size = int(getattr(self.lib, plan.ws_query)(self._h, base._h, B, *plan.ws_ints))
+        return 8 * size if plan.ws_query == "gik_anchored_ws_doubles" else size
 
     def anchored_retry_seeds_screened(self, base, T_goal, idx, retry_seed, attempt, candidates, q_limits, center=None, spread=0.0,
                                       clearance_mode="nodes", clear_tol=1e-4, scenes=None, scene_id=None):
@@ -694,6 +739,33 @@ class Template:
         in clearance_mode, against scene scene_id[g] ([B], by goal) where scenes is given, and the first clear one is
         picked (AnchoredProblem.screened_seeds_host is the numpy mirror).  Returns device tensors: "q" [count, n] the
         picked angles, "T" [count, 4, 4] the pose rows, "pick" [count] int32 and "clearance" [count]."""
+        def source(T, B, idx):      # the draws' arguments around (T_goal, idx, count)
+            n = base.n_joints
+            lo, hi = (_dev(np.ascontiguousarray(a, dtype=np.float64), self.device) for a in q_limits)
+            assert idx is not None and lo.numel() == n and hi.numel() == n
+            ctr = None
+            if center is not None:      # (a NaN centre row is allowed: it gives a NaN seed, as the device entry says)
+                ctr = center if isinstance(center, torch.Tensor) else np.ascontiguousarray(center, dtype=np.float64)
+                ctr = _dev(ctr, self.device).contiguous()
+                assert tuple(ctr.shape) == (B, n), (tuple(ctr.shape), (B, n))
+            return (), (int(retry_seed) & (2 ** 64 - 1), int(attempt), lo.data_ptr(), hi.data_ptr(),
+                        None if ctr is None else ctr.data_ptr(), float(spread)), (lo, hi, ctr)
+        return self._screened_step("gik_anchored_retry_seeds_screened", base, T_goal, idx, candidates, clearance_mode, clear_tol, scenes,
+                                   scene_id, source, spread, center is not None)
+
+    def _idx(self, idx):
+        """Goal indices of compact slots (a sequence, an array or a tensor) -> a contiguous [count] int32 device tensor."""
+        if not isinstance(idx, torch.Tensor):
+            idx = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int32))
+        idx = idx.to(device=self.device, dtype=torch.int32).contiguous()
+        assert idx.dim() == 1
+        return idx
+
+    def _screened_step(self, name, base, T_goal, idx, candidates, clearance_mode, clear_tol, scenes, scene_id, source, spread=0.0,
+                       has_center=True):
+        """The body of anchored_retry_seeds_screened and anchored_atlas_seeds: the checks they share, the outputs, the
+        workspace (name + "_ws_bytes") and the call of the export `name`.  source(T, B, idx) returns the entry's arguments
+        in front of and behind (T_goal, idx, count), and the tensors those point into; spread: that of the draws."""
         assert self.anchored and base.has_pipeline
         mode = check_clearance_mode(clearance_mode, getattr(self, "n_link", None) is not None,
                                     getattr(self, "n_self", None) is not None)
@@ -702,34 +774,22 @@ class Template:
             raise ValueError("clear_tol must be positive")
         if not spread >= 0:
             raise ValueError(f"spread must be at least 0 (radians), got {spread!r}")
-        if spread > 0 and center is None:
+        if spread > 0 and not has_center:
             raise ValueError("spread > 0 needs the centre rows")
         T, B = base._poses(T_goal)
-        n = base.n_joints
-        if not isinstance(idx, torch.Tensor):
-            idx = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int32))
-        idx = idx.to(device=self.device, dtype=torch.int32).contiguous()
-        assert idx.dim() == 1
-        count = idx.numel()
-        lo, hi = (_dev(np.ascontiguousarray(a, dtype=np.float64), self.device) for a in q_limits)
-        assert lo.numel() == n and hi.numel() == n
-        ctr = None
-        if center is not None:      # (a NaN centre row is allowed: it gives a NaN seed, as the device entry says)
-            ctr = _dev(np.ascontiguousarray(center, dtype=np.float64) if not isinstance(center, torch.Tensor) else center,
-                       self.device).contiguous()
-            assert tuple(ctr.shape) == (B, n), (tuple(ctr.shape), (B, n))
+        idx = None if idx is None else self._idx(idx)
+        front, behind, keep = source(T, B, idx)      # (keep: the source's device tensors, alive until the call is queued)
+        count = B if idx is None else idx.numel()
         sc, ids = self._scene_desc(scenes, scene_id, B)
         f64 = dict(dtype=torch.float64, device=self.device)
-        q = torch.empty(count, n, **f64)
+        q = torch.empty(count, base.n_joints, **f64)
         T_out = torch.empty(count, T.numel() // max(B, 1), **f64)
         pick = torch.empty(count, dtype=torch.int32, device=self.device)
         cl = torch.empty(count, **f64)
-        ws = workspace(int(self.lib.gik_anchored_retry_seeds_screened_ws_bytes(self._h, base._h, count, candidates)), self.device)
-        self._call("gik_anchored_retry_seeds_screened", self._h, base._h, T.data_ptr(), idx.data_ptr(), count,
-                   int(retry_seed) & (2 ** 64 - 1), int(attempt), lo.data_ptr(), hi.data_ptr(),
-                   None if ctr is None else ctr.data_ptr(), float(spread), candidates, mode, float(clear_tol),
-                   None if sc is None else C.byref(sc), ws.data_ptr(), T_out.data_ptr(), q.data_ptr(), pick.data_ptr(),
-                   cl.data_ptr(), self._stream())
+        ws = workspace(int(getattr(self.lib, name + "_ws_bytes")(self._h, base._h, count, candidates)), self.device)
+        self._call(name, self._h, base._h, *front, T.data_ptr(), None if idx is None else idx.data_ptr(), count, *behind, candidates,
+                   mode, float(clear_tol), None if sc is None else C.byref(sc), ws.data_ptr(), T_out.data_ptr(), q.data_ptr(),
+                   pick.data_ptr(), cl.data_ptr(), self._stream())
         return {"q": q, "T": T_out.reshape(count, 4, 4), "pick": pick, "clearance": cl, "_ws": ws, "_scene_id": ids}
 
     def atlas_key_width(self):
@@ -747,11 +807,7 @@ class Template:
         if atlas.width != self.atlas_key_width():
             raise ValueError(f"the atlas has keys of width {atlas.width}, this template's goals have {self.atlas_key_width()}")
         T, B = self._poses(T_goal)
-        if idx is not None:
-            if not isinstance(idx, torch.Tensor):
-                idx = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int32))
-            idx = idx.to(device=self.device, dtype=torch.int32).contiguous()
-            assert idx.dim() == 1
+        idx = None if idx is None else self._idx(idx)
         count = B if idx is None else idx.numel()
         nbr = torch.empty(count, int(k), dtype=torch.int32, device=self.device)
         d = torch.empty(count, int(k), dtype=torch.float64, device=self.device) if dist else None
@@ -766,37 +822,11 @@ class Template:
         (goal g = idx[r], or r) is atlas row nbr[g, first + c]; nbr [B, K] int32 on the device, indexed by goal (what
         base.atlas_nearest returns without idx).  Returns what anchored_retry_seeds_screened returns
         (AnchoredProblem.atlas_seeds_host is the numpy mirror)."""
-        assert self.anchored and base.has_pipeline
-        mode = check_clearance_mode(clearance_mode, getattr(self, "n_link", None) is not None,
-                                    getattr(self, "n_self", None) is not None)
-        candidates = check_retry_candidates(candidates)
-        if not clear_tol > 0:
-            raise ValueError("clear_tol must be positive")
-        T, B = base._poses(T_goal)
-        n = base.n_joints
-        assert nbr.dtype == torch.int32 and nbr.dim() == 2 and nbr.shape[0] == B and nbr.is_contiguous()
-        if idx is not None:
-            if not isinstance(idx, torch.Tensor):
-                idx = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int32))
-            idx = idx.to(device=self.device, dtype=torch.int32).contiguous()
-        count = B if idx is None else idx.numel()
-        sc, ids = self._scene_desc(scenes, scene_id, B)
-        f64 = dict(dtype=torch.float64, device=self.device)
-        q = torch.empty(count, n, **f64)
-        T_out = torch.empty(count, T.numel() // max(B, 1), **f64)
-        pick = torch.empty(count, dtype=torch.int32, device=self.device)
-        cl = torch.empty(count, **f64)
-        ws = workspace(int(self.lib.gik_anchored_atlas_seeds_ws_bytes(self._h, base._h, count, candidates)), self.device)
-        self._call("gik_anchored_atlas_seeds", self._h, base._h, atlas.d_q.data_ptr(), atlas.count, T.data_ptr(),
-                   None if idx is None else idx.data_ptr(), count, nbr.data_ptr(), int(nbr.shape[1]), int(first), candidates,
-                   mode, float(clear_tol), None if sc is None else C.byref(sc), ws.data_ptr(), T_out.data_ptr(), q.data_ptr(),
-                   pick.data_ptr(), cl.data_ptr(), self._stream())
-        return {"q": q, "T": T_out.reshape(count, 4, 4), "pick": pick, "clearance": cl, "_ws": ws, "_scene_id": ids}
-
-    def anchored_atlas_ws_bytes(self, base, B, candidates, retries):
-        """Bytes of the restart workspace ("retry_ws") of one anchored_ik call of B goals with atlas=
-        (gik_anchored_ik_batch_atlas_ws_bytes), with or without scenes."""
-        return int(self.lib.gik_anchored_ik_batch_atlas_ws_bytes(self._h, base._h, B, candidates, retries))
+        def source(T, B, idx):      # the table in front of (T_goal, idx, count), the ranks behind
+            assert nbr.dtype == torch.int32 and nbr.dim() == 2 and nbr.shape[0] == B and nbr.is_contiguous()
+            return (atlas.d_q.data_ptr(), atlas.count), (nbr.data_ptr(), int(nbr.shape[1]), int(first)), None
+        return self._screened_step("gik_anchored_atlas_seeds", base, T_goal, idx, candidates, clearance_mode, clear_tol, scenes, scene_id,
+                                   source)
 
     def alloc_anchored_buffers(self, base, B, clearance=False, ws=True):
         """The buffers of one anchored_ik call of B goals (its `out`): the scratch "ws" (ws=False leaves it out: a call
@@ -1042,77 +1072,56 @@ class Template:
         where it started from q_init.  None (the default): the call as it was."""
         assert self.anchored and base.has_pipeline
         retry_candidates = check_retry_candidates(retry_candidates, retries)
+        # 1. the checks
         if atlas is not None:
-            atlas_candidates = check_retry_candidates(atlas_candidates, what="atlas_candidates")
-            if retry_candidates > 1:
-                raise ValueError("atlas= with retry_candidates > 1 is not supported: the restarts take atlas rows, not draws")
-            if retry_spread > 0:
-                raise ValueError("atlas= with retry_spread > 0 is not supported: the restarts take atlas rows, not draws around q_init")
-            if int(retries) == retries and 0 <= int(retries) <= RETRY_MAX:
-                check_atlas_k((int(retries) + 1) * atlas_candidates, atlas.count, "(retries + 1) * atlas_candidates")
+            atlas_candidates = check_atlas_args(atlas, atlas_candidates, retries, retry_candidates, retry_spread)
             if atlas.width != base.atlas_key_width():
                 raise ValueError(f"the atlas has keys of width {atlas.width}, the base template's goals have {base.atlas_key_width()}")
             if retries and q_limits is None:      # (not read: no seed is drawn)
                 q_limits = (np.zeros(base.n_joints), np.zeros(base.n_joints))
         mode = check_clearance_mode(clearance_mode, getattr(self, "n_link", None) is not None,
                                     getattr(self, "n_self", None) is not None)
-        restart = restart_like(retries, clearance_mode, clearance, scenes) or atlas is not None
         lo = hi = None
-        if atlas is not None:
-            clearance = True
-        if retries:      # (the clearance always comes back then, whatever `clearance` says)
+        if retries:
             retries, lo, hi = check_retry_args(retries, pos_tol, rot_tol, q_limits, base.n_joints, clear_tol=clear_tol,
                                                retry_spread=retry_spread, has_center=q_init is not None)
-            clearance = True
+        # 2. the plan: retries = 0 on a restart entry is attempt 0 alone -- the call, the link clearance, the self clearance merged
+        plan = anchored_call_plan(q_init is not None, clearance, clearance_mode, scenes is not None, retries, retry_candidates,
+                                  None if atlas is None else atlas_candidates)
+        clearance = bool(clearance or retries or atlas is not None)      # (it always comes back then, whatever `clearance` says)
+        # 3. the pointers and the call
         T, B = base._poses(T_goal)
         sc, ids = self._scene_desc(scenes, scene_id, B, scene_id_checked)
         if out is None:      # (the restart workspace holds the scratch "ws")
-            out = self.alloc_anchored_buffers(base, B, clearance, ws=not restart)
+            out = self.alloc_anchored_buffers(base, B, clearance, ws=not plan.restart)
         q0 = None if q_init is None else base._seed_angles(q_init, B)
         cl = None
         if clearance:
             cl = out["clearance"] if "clearance" in out else torch.empty(B, dtype=torch.float64, device=self.device)
         seed_ptr, cl_ptr = (None if t is None else t.data_ptr() for t in (q0, cl))
-        scene = () if sc is None else (C.byref(sc),)      # (the scenes entries take it in front of the workspace)
-        answer = [out[key].data_ptr() for key in ("Y", "stats", "q", "pos_err", "rot_err")]
-        after = None      # the clearance export to launch behind the solve, where the entry does not measure it itself
-        if restart:      # retries = 0: attempt 0 alone -- the call, the link clearance, the self clearance merged into it
-            screened = retry_candidates > 1
-            nbytes = self.anchored_atlas_ws_bytes(base, B, atlas_candidates, int(retries)) if atlas is not None else \
-                self.anchored_retry_screened_ws_bytes(base, B, retry_candidates) if screened else \
-                self.anchored_retry_ws_bytes(base, B, scenes=sc is not None)
-            attempt, ws, q_lo, q_hi = self._retry_buffers(out, B, nbytes, lo, hi, limits=bool(retries) and atlas is None)
+        val = dict(q_init=seed_ptr, B=B, scenes=None if sc is None else C.byref(sc), clearance=cl_ptr, null=None, mode=mode,
+                   candidates=retry_candidates)
+        if plan.restart:
+            attempt, ws, q_lo, q_hi = self._retry_buffers(out, B, self.anchored_plan_ws_bytes(base, B, plan), lo, hi,
+                                                          limits=bool(retries) and atlas is None)
             opts = _retry_opts(retries if atlas is None else 0, retry_seed, pos_tol, rot_tol, q_lo, q_hi, mode, clear_tol, retry_spread)
             if atlas is not None:      # (no seed, no limits, no spread: the options of attempt 0 with the retry count)
                 opts.retries = int(retries)
-                name = "gik_anchored_ik_batch_atlas"
-                scene = (atlas_candidates, atlas.d_keys.data_ptr(), atlas.d_q.data_ptr(), atlas.count,
-                         None if sc is None else C.byref(sc))
-            elif screened:      # (one entry with a nullable scene set)
-                name, scene = "gik_anchored_ik_batch_retry_screened", (retry_candidates, None if sc is None else C.byref(sc))
-            else:
-                name = "gik_anchored_ik_batch_retry" if sc is None else "gik_anchored_ik_batch_retry_scenes"
-            args = (seed_ptr, B, C.byref(opts), *scene, ws.data_ptr(), *answer, cl_ptr, attempt.data_ptr())
+                val.update(candidates=atlas_candidates, atlas_keys=atlas.d_keys.data_ptr(), atlas_q=atlas.d_q.data_ptr(), atlas_count=atlas.count)
+            val.update(opts=C.byref(opts), attempt=attempt.data_ptr())
             extras = {"clearance": cl, "attempt" if retries else "_attempt": attempt, "_retry_ws": ws}
         else:
             ws = out["ws"]
             assert ws.numel() >= int(self.lib.gik_anchored_ws_doubles(self._h, base._h, B))
             extras = {"_ws": ws, "clearance": cl} if clearance else {"_ws": ws}
-            if sc is not None:      # one call: cold or seeded, the clearance of either mode behind it
-                name, args = "gik_anchored_ik_batch_scenes", (seed_ptr, B, *scene, ws.data_ptr(), *answer, cl_ptr, mode)
-            elif q0 is None:
-                name, args = "gik_anchored_ik_batch", (B, ws.data_ptr(), *answer)
-                if clearance:
-                    after = "gik_anchored_link_clearance" if mode == _ffi.CLEARANCE_LINKS else "gik_anchored_clearance"
-            else:      # (the seeded call measures the joint points itself; whole links are measured after it)
-                if clearance and mode == _ffi.CLEARANCE_LINKS:
-                    after = "gik_anchored_link_clearance"
-                name, args = "gik_anchored_ik_batch_seeded", (seed_ptr, B, ws.data_ptr(), *answer, None if after else cl_ptr)
+        val["ws"] = ws.data_ptr()
+        answer = [out[key].data_ptr() for key in ("Y", "stats", "q", "pos_err", "rot_err")]
+        args = [v for name in plan.args for v in (answer if name == "answer" else [val[name]])]
         if retries or sc is not None:
             extras["_scene_id"] = ids      # (read by the kernel: lives as long as the result; None without scenes)
-        self._call(name, self._h, base._h, T.data_ptr(), *args, self._stream())
-        if after:
-            self._call(after, self._h, out["Y"].data_ptr(), B, cl_ptr, self._stream())
+        self._call(plan.entry, self._h, base._h, T.data_ptr(), *args, self._stream())
+        if plan.after:      # the clearance of an entry that does not measure it itself
+            self._call(plan.after, self._h, out["Y"].data_ptr(), B, cl_ptr, self._stream())
         if atlas is not None:
             extras["atlas_pick"] = torch.empty(B, dtype=torch.int32, device=self.device)
             extras["_atlas"] = atlas      # (its tensors are read by the kernels: lives as long as the result)

@@ -16,8 +16,8 @@ import time
 import numpy as np
 import torch
 
-from ..engine import (RETRY_CANDIDATE_STEP, Template, _alloc_stats, _decode_stats, build_terms, check_atlas_k,
-                      check_clearance_mode, check_retry_args, check_retry_candidates, restart_like,
+from ..engine import (RETRY_CANDIDATE_STEP, Template, _alloc_stats, _decode_stats, anchored_call_plan, build_terms,
+                      check_atlas_args, check_atlas_k, check_clearance_mode, check_retry_args, check_retry_candidates,
                       workspace)
 from ..utils import dgp
 from ..utils.constants import POS
@@ -1090,14 +1090,8 @@ class AnchoredProblem:
         extra = {}
         if atlas is not None:
             self._check_atlas(atlas)
-            C = check_retry_candidates(atlas_candidates, what="atlas_candidates")
-            if retry_spread > 0:
-                raise ValueError("atlas= with retry_spread > 0 is not supported: the restarts take atlas rows, not draws around q_init")
-            if check_retry_candidates(retry_candidates) > 1:
-                raise ValueError("atlas= with retry_candidates > 1 is not supported: the restarts take atlas rows, not draws")
-            if int(retries) == retries and 0 <= int(retries) <= 63:      # (anything else is _retry_args' to refuse)
-                check_atlas_k((int(retries) + 1) * C, atlas.count, "(retries + 1) * atlas_candidates")
-            extra = dict(atlas=atlas, atlas_candidates=C)
+            extra = dict(atlas=atlas, atlas_candidates=check_atlas_args(atlas, atlas_candidates, retries, retry_candidates,
+                                                                        retry_spread, spread_first=True))
         elif atlas_candidates != 1:
             raise ValueError("atlas_candidates needs atlas=")
         retry = self._retry_args(retries, retry_seed, pos_tol, rot_tol, clear_tol, retry_spread, q_limits, q_init is not None,
@@ -1231,12 +1225,11 @@ class AnchoredProblem:
                                  retry_candidates=retry_candidates)
         tpl, base = self.template, self.base.template
         planes, shared, nbytes = ["clearance"], {}, None
-        if restart_like(retries, clearance_mode, True, scenes):
-            # one restart workspace for all waypoints: it holds the anchored scratch too and, with scenes, a compact
-            # batch's ids behind it; without restarts it serves attempt 0 of the restart entry alone
-            nbytes = tpl.anchored_retry_ws_bytes(base, B, scenes=scenes is not None)
-            if "retry_candidates" in retry:      # (and the screened step's arrays behind those)
-                nbytes = tpl.anchored_retry_screened_ws_bytes(base, B, retry["retry_candidates"])
+        plan = anchored_call_plan(True, True, clearance_mode, scenes is not None, retries, retry.get("retry_candidates", 1))
+        if plan.restart:
+            # one restart workspace for all waypoints, sized by the plan every waypoint's anchored_ik runs on: it holds the
+            # anchored scratch too; without restarts it serves attempt 0 of the restart entry alone
+            nbytes = tpl.anchored_plan_ws_bytes(base, B, plan)
         else:
             shared["ws"] = tpl.alloc_anchored_buffers(base, B)["ws"]
         if retry:

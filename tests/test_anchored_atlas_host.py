@@ -260,6 +260,49 @@ def test_atlas_arguments_are_refused_before_any_device_call():
         tpl.__dict__.clear()      # (nothing for __del__ to free)
 
 
+def test_atlas_refusals_keep_their_texts_and_each_callers_order():
+    """engine.check_atlas_args behind AnchoredProblem.solve and Template.anchored_ik: the whole text of each ValueError, and
+    with two faults at once the one each caller has always raised first -- solve: the key width, retry_spread,
+    retry_candidates, K; anchored_ik: retry_candidates, retry_spread, K, the key width."""
+    import re
+    from graphik_amd.engine import Template
+    rs = _rs()
+    robot, ap = floor_problem()
+    T, q0 = room_goals()[1][:2], room_goals()[2][:2]
+    A = room_atlas()
+    tiny = rs.SeedAtlas(A.q[:5], A.keys[:5], A.clearance[:5])
+    narrow_tiny = rs.SeedAtlas(A.q[:5], A.keys[:5, :3], A.clearance[:5])
+    spread = "atlas= with retry_spread > 0 is not supported: the restarts take atlas rows, not draws around q_init"
+    draws = "atlas= with retry_candidates > 1 is not supported: the restarts take atlas rows, not draws"
+    rows = "(retries + 1) * atlas_candidates = 6 exceeds the atlas's 5 rows"
+    both = dict(q_init=q0, retries=1, retry_spread=0.2, retry_candidates=2)
+    many = dict(retries=2, atlas_candidates=2)
+    tpl = Template.__new__(Template)
+    tpl.anchored = True
+    base = _NoDevice()
+    base.__dict__.update(has_pipeline=True, atlas_key_width=lambda: 6)
+    lim = dict(q_limits=robot.limits_arrays())
+    try:
+        for call, kw, text in (
+                (ap.solve, dict(atlas=A, q_init=q0, retries=1, retry_spread=0.2), spread),
+                (ap.solve, dict(atlas=A, retries=1, retry_candidates=2), draws),
+                (ap.solve, dict(atlas=tiny, **many), rows),
+                (ap.solve, dict(atlas=A, **both), spread),
+                (ap.solve, dict(atlas=tiny, q_init=q0, retry_spread=0.2, **many), spread),
+                (ap.solve, dict(atlas=tiny, retry_candidates=2, **many), draws),
+                (ap.solve, dict(atlas=narrow_tiny, **many), "the atlas has keys of width 3, this problem's goals have 6"),
+                (lambda T, **kw: Template.anchored_ik(tpl, base, T, **kw), dict(atlas=A, **both, **lim), draws),
+                (lambda T, **kw: Template.anchored_ik(tpl, base, T, **kw), dict(atlas=tiny, q_init=q0, retry_spread=0.2, **many), spread),
+                (lambda T, **kw: Template.anchored_ik(tpl, base, T, **kw), dict(atlas=tiny, retry_candidates=2, **many, **lim), draws),
+                (lambda T, **kw: Template.anchored_ik(tpl, base, T, **kw), dict(atlas=narrow_tiny, **many), rows),
+                (lambda T, **kw: Template.anchored_ik(tpl, base, T, **kw), dict(atlas=narrow_tiny),
+                 "the atlas has keys of width 3, the base template's goals have 6")):
+            with pytest.raises(ValueError, match="^" + re.escape(text) + "$"):
+                call(T, **kw)
+    finally:
+        tpl.__dict__.clear()      # (nothing for __del__ to free)
+
+
 def test_abi_carries_the_atlas_entry_points():
     from graphik_amd import _ffi, build
     for name in ("gik_atlas_nearest", "gik_anchored_atlas_seeds", "gik_anchored_atlas_seeds_ws_bytes",

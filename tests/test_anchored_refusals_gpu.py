@@ -10,6 +10,10 @@ record the value.  Left out, because they cannot be had without queuing work or 
   - gik_anchored_retry_select with a null d_stats, d_pos_err, d_rot_err or d_clearance: refused after the memset of d_count;
   - a base graph that cannot be seeded on the device, is planar or has another node count than the template's full_N; link
     hinges that gik_anchored_attach_links cannot build.
+The table was recorded again from a checkout of bcb1840 when the exports of the later features joined it -- the half-space and
+the self clearance, the sweep with two outputs, the screened seed step and its batch entry, the atlas entries, with their
+sizes -- ahead of the fold of the restart entries onto one driver (docs/NOTEBOOK.md 47): the 306 cases it had came out unchanged.
+Their handles come from the problems the half-space and the self tests build.
 Then the sizes of the three workspaces whose layouts gik_plan.h holds, against the closed forms of tests/test_ws_layouts.py,
 and the Python layer's one helper for the restart workspace with a scene set."""
 import ctypes as C
@@ -21,15 +25,24 @@ from types import SimpleNamespace
 import numpy as np
 import pytest
 
-from conftest import GOLDEN
+from conftest import GOLDEN, make_graph
+from test_anchored_halfspaces_gpu import _problem as _half_problem
+from test_anchored_halfspaces_host import FLOOR
 from test_anchored_links_gpu import _problem
+from test_anchored_self_gpu import _problem as _self_problem
 from test_ws_layouts import STATS, pad8
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN_FILE = os.path.join(GOLDEN, "anchored_refusals_parent.json")
 B = 2
+ATLAS_ROWS = 16
 SIZE = "(a size: 0 on a bad pair, no message)"
+
+
+def _rs():
+    from graphik_amd.solvers import riemannian_solver as rs
+    return rs
 
 
 @functools.lru_cache(maxsize=None)
@@ -62,6 +75,23 @@ def env():
     e.S = ap.scene_set([ap.obstacles, ap.obstacles + np.array([0.2, 0.0, 0.0, 0.0])])
     e.ids = torch.zeros(B, dtype=torch.int32, device="cuda")
     e.stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    # the handles of the later features, from the problems their own tests build: self pairs on UR10 + table (selft, with
+    # its robot graph sbase), a floor under the UR10 with links (half) and without (half_bare)
+    sp = _self_problem()[2]
+    e.selft, e.sbase = sp.template, sp.base.template
+    e.half = _half_problem()[2].template
+    e.half_bare = _rs().AnchoredProblem(make_graph("ur10")[1], links=[], halfspaces=[FLOOR]).template
+    assert getattr(e.selft, "n_self", None) is not None and getattr(tpl, "n_self", None) is None
+    assert e.half.n_half == 1 and e.half.n_link is not None and e.half_bare.n_half == 1 and e.half_bare.n_link is None
+    e._problems = (sp,)
+    # the screened step's workspace, the larger of the two batch workspaces (4 candidates; one restart), a 16-row atlas
+    e.scw = torch.zeros(int(e.lib.gik_anchored_retry_seeds_screened_ws_bytes(tpl._h, base._h, B, 4)) // 8 + 1, **f64)
+    e.aws = torch.zeros(max(int(e.lib.gik_anchored_ik_batch_atlas_ws_bytes(tpl._h, base._h, B, 4, 1)),
+                            int(e.lib.gik_anchored_ik_batch_retry_screened_ws_bytes(tpl._h, base._h, B, 4))) // 8 + 1, **f64)
+    e.keys, e.aq = torch.zeros(6, ATLAS_ROWS, **f64), torch.zeros(ATLAS_ROWS, n, **f64)
+    e.nbr, e.dist = torch.zeros(B, 8, dtype=torch.int32, device="cuda"), torch.zeros(B, 8, **f64)
+    e.pick, e.pick_cl = torch.zeros(B, dtype=torch.int32, device="cuda"), torch.zeros(B, **f64)
+    e.self_out = torch.zeros(B, **f64)
     return e
 
 
@@ -96,6 +126,9 @@ def cases(e=None):
     scene_faults = {"null scene set": None, "n_scene 0": scene(n_scene=0), "stride 129": scene(stride=129),
                     "null d_scene_id with two scenes": scene(ids=False), "null d_n_obs": scene(n_obs=False),
                     "null d_obs": scene(obs=False)}
+    given_scene_faults = {what: sc for what, sc in scene_faults.items() if sc is not None}      # (entries whose scene set may be null)
+    candidate_faults = (("candidates 0", dict(candidates=0)), ("candidates 17", dict(candidates=17)),
+                        ("B * candidates above an int", dict(B=2 ** 30)))
 
     def opts(retries=1, mode=0, lo=True, hi=True, pos_tol=0.01, rot_tol=0.01, clear_tol=1e-4, spread=0.0):
         o = ffi.AnchoredRetryOpts(retries=retries, clearance_mode=mode, seed=1, pos_tol=pos_tol, rot_tol=rot_tol,
@@ -182,14 +215,16 @@ def cases(e=None):
     add("gik_anchored_sweep_clearance", sweep, "without links + samples 0", anch=bare, samples=0)
     add("gik_anchored_sweep_clearance", sweep, "samples 0 + null q_a", samples=0, q_a=None)
 
-    # ---- the two restart entries
-    for with_scenes in (False, True):
-        export = "gik_anchored_ik_batch_retry" + ("_scenes" if with_scenes else "")
+    # ---- the three restart entries that draw their seeds
+    for export in ("gik_anchored_ik_batch_retry", "gik_anchored_ik_batch_retry_scenes", "gik_anchored_ik_batch_retry_screened"):
+        with_scenes, screened = export.endswith("_scenes"), export.endswith("_screened")
         d = dict(anch=tpl, base=base, T=_p(e.T), q_init=_p(e.q0), B=B, opts=opts())
         if with_scenes:
             d["scenes"] = scene()
-        make = _entry(getattr(lib, export), **d, ws=_p(e.rws), **answer, clearance=_p(o["clearance"]), attempt=_p(e.attempt),
-                      stream=e.stream)
+        if screened:      # (candidates, then a scene set that may be null)
+            d.update(candidates=4, scenes=None)
+        make = _entry(getattr(lib, export), **d, ws=_p(e.aws if screened else e.rws), **answer, clearance=_p(o["clearance"]),
+                      attempt=_p(e.attempt), stream=e.stream)
         for what, over in pair:
             add(export, make, what, **over)
         add(export, make, "null opts", opts=None)
@@ -208,7 +243,7 @@ def cases(e=None):
         add(export, make, "null clearance", clearance=None)
         add(export, make, "null attempt", attempt=None)
         add(export, make, "null ws", ws=None)
-        add(export, make, "ws off 8-byte alignment", ws=_p(e.rws) + 4)
+        add(export, make, "ws off 8-byte alignment", ws=_p(e.aws if screened else e.rws) + 4)
         for b in ("T", *answer):
             add(export, make, "null " + b, **{b: None})
         add(export, make, "null clearance + null ws", clearance=None, ws=None)
@@ -220,6 +255,20 @@ def cases(e=None):
             add(export, make, "base has no pipeline + null scene set", base=tpl, scenes=None)
             add(export, make, "null scene set + retries 64", scenes=None, opts=opts(retries=64))
             add(export, make, "stride 129 + mode 2", scenes=scene_faults["stride 129"], opts=opts(mode=2))
+        if screened:
+            for what, sc in given_scene_faults.items():
+                add(export, make, what, scenes=sc)
+            for what, over in candidate_faults:
+                add(export, make, what, **over)
+            add(export, make, "clear_tol 0, no retries", opts=opts(retries=0, clear_tol=0.0))
+            add(export, make, "base has no pipeline + n_scene 0", base=tpl, scenes=scene_faults["n_scene 0"])
+            add(export, make, "base has no pipeline + candidates 0", base=tpl, candidates=0)
+            add(export, make, "n_scene 0 + retries 64", scenes=scene_faults["n_scene 0"], opts=opts(retries=64))
+            add(export, make, "stride 129 + mode 2", scenes=scene_faults["stride 129"], opts=opts(mode=2))
+            add(export, make, "mode 2 + candidates 0", opts=opts(mode=2), candidates=0)
+            add(export, make, "spread -0.1 + candidates 0", opts=opts(spread=-0.1), candidates=0)
+            add(export, make, "candidates 0 + null clearance", candidates=0, clearance=None)
+            add(export, make, "ws off 8-byte alignment + null T", ws=_p(e.aws) + 4, T=None)
 
     # ---- the three steps of a restart
     select = _entry(lib.gik_anchored_retry_select, stats=_p(o["stats"]), pos_err=_p(o["pos_err"]), rot_err=_p(o["rot_err"]),
@@ -272,6 +321,155 @@ def cases(e=None):
                        ("link 0 outside + link 1 negative radius", dict(d=links(a=(N, 0), radius=(0.0, -1.0)))),
                        ("link 0 nan radius + link 1 outside", dict(d=links(b=(4, N), radius=(float("nan"), 0.0))))):
         add("gik_anchored_attach_links", attach, what, **over)
+
+    # ---- the half-space and the self clearance, the sweep with two outputs
+    selft, sbase, half, half_bare = e.selft._h, e.sbase._h, e.half._h, e.half_bare._h
+    ex = "gik_anchored_halfspace_clearance"
+    make = _entry(getattr(lib, ex), anch=half, Y=_p(o["Y"]), B=B, links=0, clearance=_p(o["clearance"]), stream=e.stream)
+    for what, over in (("null anch", dict(anch=None)), ("B -1", dict(B=-1)), ("anch is not anchored", dict(anch=base)),
+                       ("without half-spaces", dict(anch=tpl)), ("links 2", dict(links=2)),
+                       ("links 1 without links", dict(anch=half_bare, links=1)), ("null Y", dict(Y=None)),
+                       ("null clearance", dict(clearance=None)), ("B -1 + anch is not anchored", dict(B=-1, anch=base)),
+                       ("without half-spaces + links 2", dict(anch=tpl, links=2)), ("links 2 + null Y", dict(links=2, Y=None)),
+                       ("links 1 without links + null Y", dict(anch=half_bare, links=1, Y=None))):
+        add(ex, make, what, **over)
+    ex = "gik_anchored_self_clearance"
+    make = _entry(getattr(lib, ex), anch=selft, Y=_p(o["Y"]), B=B, clearance=_p(o["clearance"]), stream=e.stream)
+    for what, over in (("null anch", dict(anch=None)), ("B -1", dict(B=-1)), ("anch is not anchored", dict(anch=base)),
+                       ("without links", dict(anch=bare)), ("without self pairs", dict(anch=tpl)), ("null Y", dict(Y=None)),
+                       ("null clearance", dict(clearance=None)), ("B -1 + anch is not anchored", dict(B=-1, anch=base)),
+                       ("without links + null clearance", dict(anch=bare, clearance=None)),
+                       ("without self pairs + null Y", dict(anch=tpl, Y=None))):
+        add(ex, make, what, **over)
+    ex = "gik_anchored_sweep_clearances"
+    make = _entry(getattr(lib, ex), anch=selft, base=sbase, q_a=_p(e.q0), q_b=_p(e.q1), B=B, samples=4, ws=_p(e.sws),
+                  link_out=_p(o["clearance"]), self_out=_p(e.self_out), stream=e.stream)
+    for what, over in pair:
+        add(ex, make, what, **over)
+    for what, over in (("without links", dict(anch=bare)), ("samples 0", dict(samples=0)),
+                       ("B (samples + 1) above an int", dict(samples=2 ** 31 - 1)),
+                       ("both outputs null", dict(link_out=None, self_out=None)), ("self_out without self pairs", dict(anch=tpl)),
+                       ("null q_a", dict(q_a=None)), ("null q_b", dict(q_b=None)), ("null ws", dict(ws=None)),
+                       ("base has no pipeline + without links", dict(base=tpl, anch=bare)),
+                       ("without links + samples 0", dict(anch=bare, samples=0)),
+                       ("samples 0 + both outputs null", dict(samples=0, link_out=None, self_out=None)),
+                       ("both outputs null, without self pairs", dict(anch=tpl, link_out=None, self_out=None)),
+                       ("self_out without self pairs + null q_a", dict(anch=tpl, q_a=None))):
+        add(ex, make, what, **over)
+
+    # ---- the screened seed step and the atlas: the nearest rows, the seed step, the batch entry, its picks
+    step_modes = (("mode 2", dict(mode=2)), ("mode -1", dict(mode=-1)), ("mode links without links", dict(anch=bare, mode=1)))
+    step_ws = (("null ws", dict(ws=None)), ("ws off 8-byte alignment", dict(ws=_p(e.scw) + 4)))
+    step_out = dict(ws=_p(e.scw), T_out=_p(e.poses), q_out=_p(e.q1), pick=_p(e.pick), pick_clearance=_p(e.pick_cl), stream=e.stream)
+    ex = "gik_anchored_retry_seeds_screened"
+    make = _entry(getattr(lib, ex), anch=tpl, base=base, T=_p(e.T), idx=_p(e.idx), B=B, seed=1, attempt=1, q_lo=_p(e.lo),
+                  q_hi=_p(e.hi), q_center=_p(e.q0), spread=0.0, candidates=4, mode=0, clear_tol=1e-4, scenes=None, **step_out)
+    for what, over in (*pair, *((w, dict(scenes=sc)) for w, sc in given_scene_faults.items()), *step_modes,
+                       ("attempt -1", dict(attempt=-1)), ("attempt 64", dict(attempt=64)), ("null q_lo", dict(q_lo=None)),
+                       ("null q_hi", dict(q_hi=None)), ("spread -1", dict(spread=-1.0)), ("spread nan", dict(spread=float("nan"))),
+                       ("spread 0.1 without a centre", dict(spread=0.1, q_center=None)), *candidate_faults,
+                       ("clear_tol 0", dict(clear_tol=0.0)), ("clear_tol nan", dict(clear_tol=float("nan"))), *step_ws,
+                       ("null T", dict(T=None)), ("null idx", dict(idx=None)), ("null T_out", dict(T_out=None)),
+                       ("null q_out", dict(q_out=None)),
+                       ("base has no pipeline + n_scene 0", dict(base=tpl, scenes=scene_faults["n_scene 0"])),
+                       ("anch is not anchored + mode 2", dict(anch=base, mode=2)),
+                       ("base has no pipeline + candidates 0", dict(base=tpl, candidates=0)),
+                       ("stride 129 + mode 2", dict(scenes=scene_faults["stride 129"], mode=2)),
+                       ("mode 2 + attempt 64", dict(mode=2, attempt=64)), ("attempt 64 + null q_lo", dict(attempt=64, q_lo=None)),
+                       ("null q_hi + spread -1", dict(q_hi=None, spread=-1.0)),
+                       ("spread 0.1 without a centre + candidates 0", dict(spread=0.1, q_center=None, candidates=0)),
+                       ("candidates 0 + clear_tol 0", dict(candidates=0, clear_tol=0.0)),
+                       ("clear_tol 0 + null ws", dict(clear_tol=0.0, ws=None)), ("null ws + null T", dict(ws=None, T=None)),
+                       ("ws off 8-byte alignment + null T", dict(ws=_p(e.scw) + 4, T=None))):
+        add(ex, make, what, **over)
+    ex = "gik_atlas_nearest"
+    make = _entry(getattr(lib, ex), base=base, keys=_p(e.keys), atlas_count=ATLAS_ROWS, T=_p(e.T), idx=_p(e.idx), B=B, K=4,
+                  nbr=_p(e.nbr), dist=_p(e.dist), stream=e.stream)
+    for what, over in (("null base", dict(base=None)), ("B -1", dict(B=-1)), ("base has no pipeline", dict(base=tpl)),
+                       ("K 0", dict(K=0)), ("K 65", dict(K=65)), ("atlas_count 0", dict(atlas_count=0)),
+                       ("atlas_count above 2^30", dict(atlas_count=2 ** 30 + 1)), ("B * K above an int", dict(B=2 ** 30)),
+                       ("null keys", dict(keys=None)), ("null T", dict(T=None)), ("null nbr", dict(nbr=None)),
+                       ("B -1 + base has no pipeline", dict(B=-1, base=tpl)), ("base has no pipeline + K 0", dict(base=tpl, K=0)),
+                       ("K 0 + atlas_count 0", dict(K=0, atlas_count=0)), ("atlas_count 0 + null keys", dict(atlas_count=0, keys=None)),
+                       ("null keys + null T", dict(keys=None, T=None))):
+        add(ex, make, what, **over)
+    ex = "gik_anchored_atlas_seeds"
+    make = _entry(getattr(lib, ex), anch=tpl, base=base, atlas_q=_p(e.aq), atlas_count=ATLAS_ROWS, T=_p(e.T), idx=_p(e.idx), B=B,
+                  nbr=_p(e.nbr), nbr_stride=8, first=0, candidates=4, mode=0, clear_tol=1e-4, scenes=None, **step_out)
+    for what, over in (*pair, *((w, dict(scenes=sc)) for w, sc in given_scene_faults.items()), *step_modes, *candidate_faults,
+                       ("atlas_count 0", dict(atlas_count=0)), ("atlas_count above 2^30", dict(atlas_count=2 ** 30 + 1)),
+                       ("first -1", dict(first=-1)), ("nbr_stride 0", dict(nbr_stride=0)), ("first 5 of 8 ranks", dict(first=5)),
+                       ("clear_tol 0", dict(clear_tol=0.0)), ("null atlas_q", dict(atlas_q=None)), *step_ws,
+                       ("null T", dict(T=None)), ("null nbr", dict(nbr=None)), ("null T_out", dict(T_out=None)),
+                       ("null q_out", dict(q_out=None)),
+                       ("base has no pipeline + n_scene 0", dict(base=tpl, scenes=scene_faults["n_scene 0"])),
+                       ("anch is not anchored + mode 2", dict(anch=base, mode=2)),
+                       ("base has no pipeline + candidates 0", dict(base=tpl, candidates=0)),
+                       ("stride 129 + mode 2", dict(scenes=scene_faults["stride 129"], mode=2)),
+                       ("mode 2 + candidates 0", dict(mode=2, candidates=0)),
+                       ("candidates 0 + atlas_count 0", dict(candidates=0, atlas_count=0)),
+                       ("atlas_count 0 + first -1", dict(atlas_count=0, first=-1)),
+                       ("first -1 + clear_tol 0", dict(first=-1, clear_tol=0.0)),
+                       ("clear_tol 0 + null atlas_q", dict(clear_tol=0.0, atlas_q=None)),
+                       ("null atlas_q + null ws", dict(atlas_q=None, ws=None)), ("null ws + null T", dict(ws=None, T=None)),
+                       ("ws off 8-byte alignment + null T", dict(ws=_p(e.scw) + 4, T=None))):
+        add(ex, make, what, **over)
+    ex = "gik_anchored_ik_batch_atlas"
+    make = _entry(getattr(lib, ex), anch=tpl, base=base, T=_p(e.T), q_init=_p(e.q0), B=B, opts=opts(), candidates=4,
+                  atlas_keys=_p(e.keys), atlas_q=_p(e.aq), atlas_count=ATLAS_ROWS, scenes=None, ws=_p(e.aws), **answer,
+                  clearance=_p(o["clearance"]), attempt=_p(e.attempt), stream=e.stream)
+    for what, over in (*pair, ("null opts", dict(opts=None)), *((w, dict(scenes=sc)) for w, sc in given_scene_faults.items()),
+                       ("mode 2", dict(opts=opts(mode=2))), ("mode -1, no retries", dict(opts=opts(mode=-1, retries=0))),
+                       ("mode links without links", dict(anch=bare, opts=opts(mode=1))),
+                       ("retries 64", dict(opts=opts(retries=64))), ("retries -1", dict(opts=opts(retries=-1))), *candidate_faults,
+                       ("K 68 above 64", dict(opts=opts(retries=16))), ("atlas_count 0", dict(atlas_count=0)),
+                       ("atlas_count above 2^30", dict(atlas_count=2 ** 30 + 1)),
+                       ("B * K above an int", dict(B=2 ** 30, candidates=1)), ("K 8 above atlas_count 7", dict(atlas_count=7)),
+                       ("pos_tol 0", dict(opts=opts(pos_tol=0.0))), ("rot_tol nan", dict(opts=opts(rot_tol=float("nan")))),
+                       ("clear_tol 0, no retries", dict(opts=opts(clear_tol=0.0, retries=0))),
+                       ("spread 0.1", dict(opts=opts(spread=0.1))), ("spread -0.1", dict(opts=opts(spread=-0.1))),
+                       ("null atlas_keys", dict(atlas_keys=None)), ("null atlas_q", dict(atlas_q=None)),
+                       ("null clearance", dict(clearance=None)), ("null attempt", dict(attempt=None)), ("null ws", dict(ws=None)),
+                       ("ws off 8-byte alignment", dict(ws=_p(e.aws) + 4)), *(("null " + b, {b: None}) for b in ("T", *answer)),
+                       ("base has no pipeline + n_scene 0", dict(base=tpl, scenes=scene_faults["n_scene 0"])),
+                       ("anch is not anchored + mode 2", dict(anch=base, opts=opts(mode=2))),
+                       ("base has no pipeline + candidates 0", dict(base=tpl, candidates=0)),
+                       ("stride 129 + mode 2", dict(scenes=scene_faults["stride 129"], opts=opts(mode=2))),
+                       ("mode 2 + retries 64", dict(opts=opts(mode=2, retries=64))),
+                       ("retries 64 + candidates 0", dict(opts=opts(retries=64), candidates=0)),
+                       ("candidates 0 + atlas_count 0", dict(candidates=0, atlas_count=0)),
+                       ("atlas_count 0 + pos_tol 0", dict(atlas_count=0, opts=opts(pos_tol=0.0))),
+                       ("K 8 above atlas_count 7 + clear_tol 0", dict(atlas_count=7, opts=opts(clear_tol=0.0))),
+                       ("clear_tol 0 + null atlas_q", dict(opts=opts(clear_tol=0.0), atlas_q=None)),
+                       ("spread 0.1 + null atlas_keys", dict(opts=opts(spread=0.1), atlas_keys=None)),
+                       ("null atlas_q + null clearance", dict(atlas_q=None, clearance=None)),
+                       ("null clearance + null ws", dict(clearance=None, ws=None)), ("null ws + null T", dict(ws=None, T=None)),
+                       ("ws off 8-byte alignment + null T", dict(ws=_p(e.aws) + 4, T=None))):
+        add(ex, make, what, **over)
+    ex = "gik_anchored_atlas_picks"
+    make = _entry(getattr(lib, ex), anch=tpl, base=base, B=B, candidates=4, retries=1, ws=_p(e.aws), attempt=_p(e.attempt),
+                  atlas_pick=_p(e.pick), stream=e.stream)
+    for what, over in (*pair, ("retries -1", dict(retries=-1)), ("retries 64", dict(retries=64)), *candidate_faults,
+                       ("K 68 above 64", dict(retries=16)), ("null ws", dict(ws=None)),
+                       ("ws off 8-byte alignment", dict(ws=_p(e.aws) + 4)), ("null attempt", dict(attempt=None)),
+                       ("null atlas_pick", dict(atlas_pick=None)), ("B -1 + base has no pipeline", dict(B=-1, base=tpl)),
+                       ("base has no pipeline + retries 64", dict(base=tpl, retries=64)),
+                       ("retries 64 + candidates 0", dict(retries=64, candidates=0)),
+                       ("candidates 0 + null ws", dict(candidates=0, ws=None)), ("null ws + null attempt", dict(ws=None, attempt=None))):
+        add(ex, make, what, **over)
+
+    # ---- the sizes of the screened and the atlas workspaces
+    for ex, d in (("gik_anchored_retry_seeds_screened_ws_bytes", dict(candidates=4)),
+                  ("gik_anchored_ik_batch_retry_screened_ws_bytes", dict(candidates=4)),
+                  ("gik_anchored_atlas_seeds_ws_bytes", dict(candidates=4)),
+                  ("gik_anchored_ik_batch_atlas_ws_bytes", dict(candidates=4, retries=1))):
+        make = _entry(getattr(lib, ex), anch=tpl, base=base, B=B, **d)
+        for what, over in (*pair, *candidate_faults):
+            add(ex, make, what, kind="size", **over)
+    atlas_bytes = _entry(lib.gik_anchored_ik_batch_atlas_ws_bytes, anch=tpl, base=base, B=B, candidates=4, retries=1)
+    for what, over in (("retries -1", dict(retries=-1)), ("retries 64", dict(retries=64)), ("K 68 above 64", dict(retries=16)),
+                       ("B * K above an int", dict(B=2 ** 30, candidates=1))):
+        add("gik_anchored_ik_batch_atlas_ws_bytes", atlas_bytes, what, kind="size", **over)
 
     # ---- the three sizes
     ws_doubles = _entry(lib.gik_anchored_ws_doubles, anch=tpl, base=base, B=B)

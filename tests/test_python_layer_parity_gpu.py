@@ -17,7 +17,9 @@ K x K Jacobi schedule became a function of the goal alone, docs/NOTEBOOK.md 36: 
 last bits, every count stayed.  The file was recorded again from a checkout of c11b7a7 when the self clearance, the
 scenes and the self hinges joined the table, docs/NOTEBOOK.md 40, and from a checkout of d57bfde when six scenarios
 for the entries and branches the table had missed joined it, docs/NOTEBOOK.md 41: both times every hash that was there
-before came out unchanged.)
+before came out unchanged.  And from a checkout of bcb1840 when the screened restarts, the atlas, the floor problem and the
+step entries joined it, docs/NOTEBOOK.md 47: 33 scenarios unchanged byte for byte, and the 29 hashes of the small-methods
+scenario unchanged beside its 14 new keys.  An atlas scenario whose atlas_pick names no row is refused like the others.)
 
 Shapes: B = 5 goals (a multiple of nothing), trajectories of L = 3 waypoints for B = 4 paths.  Inputs: conftest.make_graph
 and the inputs of the anchored host tests (collision_input, tracking_input, TWIN_MAXITER, TWIN_SEED); fixed seeds."""
@@ -31,6 +33,7 @@ import pytest
 
 from conftest import GOLDEN, make_graph
 from test_anchored_retry_host import TWIN_MAXITER, TWIN_SEED
+from test_anchored_screen_host import FLOOR, RHO, pi_limits
 from test_anchored_seeded_host import collision_input, tracking_input
 
 pytestmark = pytest.mark.gpu
@@ -109,6 +112,24 @@ def anchored(maxiter=None, link_hinges=False, self_pairs=None, self_hinges=False
 
 
 @functools.lru_cache(maxsize=None)
+def room(maxiter=None):
+    """The anchored problem of the screened and the atlas tests per iteration budget: UR10 + table, 3 cm capsules, every
+    self pair, and a floor 10 cm under the base (halfspaces=[FLOOR]).  The table stays in the problem with the floor: the
+    goals and seeds of this file (anchored_goals) are chosen against its spheres and _three_scenes is made of them, so one
+    problem serves the screened, the atlas and the floor scenarios ("anch_floor_*": the floor on top of the table).  Its
+    atlas keeps 94 of the 512 draws (183 with the floor alone); the largest K used is 6."""
+    robot, graph = make_graph("ur10_table")
+    params = None if maxiter is None else {"maxiter": maxiter}
+    return robot, _rs().AnchoredProblem(graph, params=params, link_radius=RHO, self_pairs="auto", halfspaces=[list(FLOOR)])
+
+
+@functools.lru_cache(maxsize=None)
+def room_atlas():
+    """512 draws, the rows that are clear of the room in "links+self"."""
+    return room()[1].seed_atlas(size=512, seed=3, clearance_mode="links+self")
+
+
+@functools.lru_cache(maxsize=None)
 def anchored_goals():
     """(goal poses [B, 4, 4] of clear configurations, seeds [B, n] in collision)."""
     robot = anchored()[0]
@@ -160,13 +181,16 @@ def _track(start, **kw):
     return run
 
 
-def _anch(maxiter=None, seeded=False, link_hinges=False, self_pairs=None, self_hinges=False, scenes=False, **kw):
+def _anch(maxiter=None, seeded=False, link_hinges=False, self_pairs=None, self_hinges=False, scenes=False, in_room=False,
+          atlas=False, **kw):
     def run():
         T, seeds = anchored_goals()
-        ap = anchored(maxiter, link_hinges, self_pairs, self_hinges)[1]
+        ap = room(maxiter)[1] if in_room else anchored(maxiter, link_hinges, self_pairs, self_hinges)[1]
         extra = {}
+        if atlas:
+            extra["atlas"] = room_atlas()
         if scenes:      # three scenes, goal b in scene b % 3
-            extra = dict(scenes=_three_scenes(ap), scene_id=(np.arange(B) % 3).astype(np.int32))
+            extra.update(scenes=_three_scenes(ap), scene_id=(np.arange(B) % 3).astype(np.int32))
         return host(ap.solve(T, q_init=seeds if seeded else None, **kw, **extra))
     return run
 
@@ -176,10 +200,10 @@ def _three_scenes(ap):
     return ap.scene_set([ap.obstacles, ap.obstacles + np.array([0.2, 0.0, 0.0, 0.0]), ap.obstacles[:10]])
 
 
-def _anch_track(maxiter=None, start="own", self_pairs=None, scenes=False, **kw):
+def _anch_track(maxiter=None, start="own", self_pairs=None, scenes=False, in_room=False, **kw):
     def run():
         T, q_own, q_hit = anchored_paths()
-        ap = anchored(maxiter, False, self_pairs)[1]
+        ap = room(maxiter)[1] if in_room else anchored(maxiter, False, self_pairs)[1]
         extra = {}
         if scenes:      # a scene per waypoint: waypoint l of path b in scene (b + l) % 3
             extra = dict(scenes=_three_scenes(ap),
@@ -218,6 +242,19 @@ def _template_entries():
     out["self_clearance"] = atpl.anchored_self_clearance(answer["x"])
     out["sweep_clearance"] = atpl.anchored_sweep_clearance(base, seeds_a, answer["q"], 3)
     out.update({"solve_scenes_" + key: v for key, v in host(atpl.solve(Y_free, goal, **sc)).items()})
+    # the step entries of the screened and the atlas restarts, and the half-space clearance, in the room
+    rp, A = room()[1], room_atlas()
+    rtpl, rbase = rp.template, rp.base.template
+    mode = dict(clearance_mode="links+self")
+    step = rtpl.anchored_retry_seeds_screened(rbase, Ta, np.arange(B), TWIN_SEED, 1, 4, pi_limits(), **mode)
+    out.update({"screened_seeds_" + key: v for key, v in host(step).items()})
+    out["atlas_nearest_nbr"], out["atlas_nearest_dist"] = nbr, _ = rbase.atlas_nearest(A, Ta, 6)
+    step = rtpl.anchored_atlas_seeds(rbase, A, Ta, nbr, 2, first=2, **mode)
+    out.update({"atlas_seeds_" + key: v for key, v in host(step).items()})
+    in_room = rp.solve(Ta, q_init=seeds_a, **mode)
+    out["halfspace_clearance"] = rtpl.anchored_halfspace_clearance(in_room["x"])
+    out["halfspace_link_clearance"] = rtpl.anchored_halfspace_clearance(in_room["x"], links=True)
+    out["sweep_link_clearance"], out["sweep_self_clearance"] = rtpl.anchored_sweep_clearances(rbase, seeds_a, in_room["q"], 3)
     return host(out)
 
 
@@ -293,6 +330,22 @@ SCENARIOS = {
                                                        clearance_mode="links+self"),
     "anch_scenes_track_clearance_links": _anch_track(scenes=True, clearance_mode="links"),
     "anch_self_track_clearance_links_self": _anch_track(self_pairs="auto", clearance_mode="links+self"),
+    # anchored, in the room (table, capsules, self pairs, floor): screened restarts, seeds from the atlas, and the floor without either
+    "anch_screen_retry_cold_clearance_nodes": _anch(SHORT["maxiter"], in_room=True, retries=2, retry_candidates=4,
+                                                    retry_seed=TWIN_SEED),
+    "anch_screen_scenes_retry_seeded_clearance_links": _anch(SHORT["maxiter"], in_room=True, seeded=True, scenes=True, retries=2,
+                                                             retry_candidates=4, retry_seed=TWIN_SEED, clearance_mode="links"),
+    "anch_screen_track_retry_clearance_nodes": _anch_track(SHORT["maxiter"], "hit", in_room=True, retries=2, retry_candidates=4,
+                                                           retry_seed=TWIN_SEED),
+    "anch_atlas_cold_clearance_links": _anch(SHORT["maxiter"], in_room=True, atlas=True, atlas_candidates=4, clearance_mode="links"),
+    "anch_atlas_retry_cold_clearance_links_self": _anch(SHORT["maxiter"], in_room=True, atlas=True, retries=2, atlas_candidates=2,
+                                                        clearance_mode="links+self"),
+    "anch_atlas_scenes_retry_seeded_clearance_links": _anch(SHORT["maxiter"], in_room=True, atlas=True, seeded=True, scenes=True,
+                                                            retries=2, atlas_candidates=2, clearance_mode="links"),
+    "anch_floor_cold_clearance_nodes": _anch(in_room=True, clearance=True),
+    "anch_floor_cold_clearance_links_self": _anch(in_room=True, clearance=True, clearance_mode="links+self"),
+    "anch_floor_seeded_clearance_nodes": _anch(in_room=True, seeded=True),
+    "anch_floor_seeded_clearance_links_self": _anch(in_room=True, seeded=True, clearance_mode="links+self"),
     # the small Template methods
     "template_entries_clearance": _template_entries,
     # reused buffers
@@ -309,6 +362,8 @@ def conditions(name, arrays):
         cond["attempt_nonzero"] = int(np.count_nonzero(arrays["attempt"]))
     if "clearance" in name:
         cond["clearance_finite"] = int(np.isfinite(arrays["clearance"]).sum())
+    if "atlas" in name:
+        cond["atlas_pick_named"] = int(np.count_nonzero(arrays["atlas_pick"] >= 0))
     return cond
 
 
@@ -327,6 +382,7 @@ def test_the_table_is_the_recorded_one(parent):
         assert all(count > 0 for count in rec["conditions"].values()), (name, rec["conditions"])
         assert ("retry" in name) == ("attempt_nonzero" in rec["conditions"]), name
         assert ("clearance" in name) == ("clearance_finite" in rec["conditions"]), name
+        assert ("atlas" in name) == ("atlas_pick_named" in rec["conditions"]), name
         assert not any(key.startswith("_") or key in NOT_HASHED for key in rec["sha"]), name
 
 
